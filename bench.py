@@ -17,11 +17,13 @@ HBM).  Workload = BASELINE.json config 3, the one the metric is quoted on: 65 53
 the data path has no collective.  Inputs (grid, state) are resident in HBM before the timed region; nothing returns to
 the host inside it.
 
-Timing.  W untimed launches, then BLOCKS of exactly K launches, each block bracketed by barrier + device sync on both
-sides, repeated until at least --min-seconds (0.5 s) of timed launches have run.  Per block: wall time (MAX over ranks)
-and the kernels' own duration from HIP events on the engine's stream (gu_timer_begin/end).  `ms_per_step` / `value` are
-the MEDIAN block; the spread is reported next to them.  roofline.achieved = algorithmic bytes per launch / (median block's
-HIP-event time / K).
+Timing.  W untimed launches and the settle launches of the kind (benchlib/timing.py: a fixed number, so that the store
+pacing has found its period), then ONE block of exactly K launches -- K = --steps is the number of timed launches --
+bracketed by barrier + device sync on both sides: wall time (MAX over ranks) and the kernels' own duration from HIP events
+on the engine's stream (gu_timer_begin/end).  `ms_per_step` / `value` are that block's; roofline.achieved = algorithmic
+bytes per launch / (the block's HIP-event time / K).  Every run issues the same launches on the same inputs, so
+--dump-outputs DIR writes what the last timed launch computed (a seeded sample of its trajectory rows, benchlib/dump.py)
+for a comparison of two builds output for output.
 
 Checks in the same run (rank 0): the FIRST launch is hashed in full and compared with the sha256 the REFERENCE produced
 for exactly this run (tests/golden/digests.json, 65.5 M steps of the reference's own step()); after the timed region the
@@ -54,6 +56,7 @@ from benchlib import checks  # noqa: E402
 from benchlib.checks import reference_digest  # noqa: E402,F401  (tests/test_multiprocess.py reads these through `bench`)
 from benchlib.configs import baseline_configs, other_modes, rccl_view_check, strong_c4  # noqa: E402
 from benchlib.cpu_leg import cpu_baseline, cpu_baseline_all_cores  # noqa: E402
+from benchlib.dump import dump_trajectory  # noqa: E402
 from benchlib.launcher import ensure_library_is_current, spawn_ranks  # noqa: E402
 from benchlib.report import device_block, emit_report, pacing_block, placement_block, topology_block  # noqa: E402
 from benchlib.single_process import run_single_process  # noqa: E402
@@ -105,11 +108,13 @@ def run(args, engine_cls=None, emit=print):
         eng.rollout(T, 'uniform', auto_reset=True, trajectory=True)
     launches += W
 
-    # ---- timed region: blocks of exactly K launches until >= min_seconds
-    wall, kern, own_wall, n_launched = timed_region(eng, ranks, T, K, args.min_seconds)
+    # ---- timed region: the settle launches, then exactly K timed launches
+    wall, kern, own_wall, n_launched = timed_region(eng, ranks, T, K)
     launches += n_launched
     blocks = len(wall)
     dev_info = device_block(engine_cls, device) if rank == 0 else None  # (clocks as they are right behind the timed launches)
+    if args.dump_outputs:  # (before anything below launches again or overwrites the rows)
+        dump_trajectory(eng, N, T, args.dump_outputs, env_id0=rank * N, prefix='rank%d_' % rank if world > 1 else '')
 
     # ---- one instrumented block: an event after every launch (not part of `value`)
     eng.sync()
@@ -234,12 +239,11 @@ def run(args, engine_cls=None, emit=print):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=50, help='launches per timed block')
+    ap.add_argument('--steps', type=int, default=50, help='timed launches')
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--envs', type=int, default=65536, help='envs per GPU')
     ap.add_argument('--T', type=int, default=1000, help='env-steps per launch')
     ap.add_argument('--workload', default='c3', choices=['c2', 'c3', 'c4'])
-    ap.add_argument('--min-seconds', type=float, default=0.5, help='repeat the K-launch block until this much time has been timed')
     ap.add_argument('--c4-envs', type=int, default=C4_TOTAL_ENVS, help='total envs of the strong-scaling config-4 line')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-checks', action='store_true', help='skip the reference-digest / oracle checks of this run')
@@ -252,6 +256,8 @@ def parse_args(argv=None):
     ap.add_argument('--no-live-traffic', action='store_true',
                     help='do not measure roofline.traffic with two short rocprofv3 --pmc child runs (1 GPU only); use the committed profile')
     ap.add_argument('--detail', default='bench_detail.json', help="side file for everything that is not on the line ('' = none)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write what the last timed launch computed to DIR/<name>.npy (float32 / float64, under 64 MB in all)")
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)
     return ap.parse_args(argv)
 

@@ -10,7 +10,7 @@ import griduniverse_amd as gua
 from griduniverse_amd import _lib
 
 from . import checks
-from .timing import launch_ms, settle_launches, spread, timed_region
+from .timing import launch_ms, spread, timed_region
 from .workloads import BYTES_PER_ENV_STEP, C4_TOTAL_ENVS, HBM_PEAK_GBPS, WORKLOAD_SEED, build_workload
 
 
@@ -205,7 +205,7 @@ def rccl_view_check(eng, engine_cls, ranks):
 def strong_c4(args, ranks, engine_cls, device, pacing_block=None):
     """BASELINE.json config 4: 262 144 envs on the 32x32 lava grid IN TOTAL, sharded over the ranks by env index (strong
     scaling), seed 4.  One checked launch (250 steps from reset: every rank compares its shard with the C oracle; on one GPU
-    the whole batch is also hashed against the reference's digest), then timed blocks of K launches of T steps."""
+    the whole batch is also hashed against the reference's digest), then W warm-up launches, the settle launches and one timed block of K launches of T steps."""
     world, rank = ranks.world, ranks.rank
     total = args.c4_envs
     if total % world:
@@ -224,9 +224,9 @@ def strong_c4(args, ranks, engine_cls, device, pacing_block=None):
         ref = checks.reference_digest('c4', template, seed, n, T_check, rank * n) if world == 1 else None
         ref_ok = None if ref is None else checks.sha256_triplet(got) == ref
         del got
-        for _ in range(max(args.warmup, settle_launches(eng, args.T, 'uniform', trajectory=True))):
+        for _ in range(args.warmup):
             eng.rollout(args.T, 'uniform', auto_reset=True, trajectory=True)
-        wall, kern, _, _ = timed_region(eng, ranks, args.T, args.steps, args.min_seconds / 2)
+        wall, kern, _, _ = timed_region(eng, ranks, args.T, args.steps)
         pacing = pacing_block(eng) if pacing_block else None
     finally:
         eng.close()

@@ -1,8 +1,8 @@
 """bench.py --single-process: SURVEY.md 8(e)'s form.  ONE host process, one engine (handle + HIP stream) per device,
 contiguous env-index shards with global env ids g * N .., every launch enqueued device after device so that the GPUs run
 concurrently; the single-array view through ncclCommInitAll + one grouped ncclAllGather (gu_comm_init_all /
-gu_allgather_view_all).  Timed like the multi-process form: blocks of exactly K launches PER DEVICE between device syncs of
-all devices; `value` = all devices' env-steps / median block wall time."""
+gu_allgather_view_all).  Timed like the multi-process form: the settle launches, then one block of exactly K launches PER DEVICE between device
+syncs of all devices; `value` = all devices' env-steps / the block's wall time."""
 import time
 
 import numpy as np
@@ -13,9 +13,10 @@ from griduniverse_amd import _lib
 from . import checks
 from .configs import strong_c4_entry
 from .cpu_leg import cpu_baseline, cpu_baseline_all_cores
+from .dump import dump_trajectory
 from .launcher import ensure_library_is_current
 from .report import device_block, emit_report, pacing_block, placement_block
-from .timing import native_stdout_to_stderr, spread
+from .timing import native_stdout_to_stderr, settle_count, spread
 from .traffic import read_traffic
 from .workloads import BYTES_PER_ENV_STEP, HBM_COPY_GBPS, HBM_PEAK_GBPS, METRIC, WORKLOAD_SEED, build_workload, workload_line
 
@@ -69,14 +70,15 @@ def run_single_process(args, engine_cls=None, emit=print):
         for _ in range(W):
             launch_all()
         launches += W
-        probe = block()[0]
-        blocks = int(min(4000, max(3, np.ceil(args.min_seconds / max(probe, 1e-6)))))
-        wall, kern = [], []
-        for _ in range(blocks):
-            w, k = block()
-            wall.append(w)
-            kern.append(k)
-        launches += (blocks + 1) * K
+        settle = settle_count(engines[0], 'uniform')
+        for _ in range(settle):
+            launch_all()
+        w, k = block()
+        wall, kern, blocks = [w], [k], 1
+        launches += settle + K
+        if args.dump_outputs:  # (before the probe below overwrites the rows)
+            for g, e in enumerate(engines):
+                dump_trajectory(e, N, T, args.dump_outputs, env_id0=g * N, prefix='rank%d_' % g if G > 1 else '')
         dev_info = [device_block(engine_cls, d) for d in sorted(set(devices))]
         post_probe = [e.probe_trajectory() if hasattr(e, 'probe_trajectory') else None for e in engines]
         if not args.no_checks:
@@ -131,13 +133,10 @@ def run_single_process(args, engine_cls=None, emit=print):
             ref_ok = None if ref is None else checks.sha256_triplet(engines[0].read_trajectory(0, T_check)) == ref
             for _ in range(W):
                 launch_all()
-            probe4 = block()[0]
-            blocks4 = int(min(4000, max(3, np.ceil(args.min_seconds / 2 / max(probe4, 1e-6)))))
-            wall4, kern4 = [], []
-            for _ in range(blocks4):
-                w, k = block()
-                wall4.append(w)
-                kern4.append(max(k))
+            for _ in range(settle_count(engines[0], 'uniform')):
+                launch_all()
+            w, k = block()
+            wall4, kern4 = [w], [max(k)]
         finally:
             for e in engines:
                 e.close()

@@ -1,4 +1,4 @@
-"""Timing of bench.py: the host channel between ranks, blocks of exactly K launches between barrier + device sync pairs."""
+"""Timing of bench.py: the host channel between ranks, one block of exactly K launches between barrier + device sync pairs."""
 import contextlib
 import ctypes
 import os
@@ -55,19 +55,17 @@ def timed_block(eng, ranks, T, K):
     return elapsed, kernel_ms
 
 
-def timed_region(eng, ranks, T, K, min_seconds, max_blocks=4000):
-    """One untimed probe block sizes the region (identically on every rank: its time is max-reduced), then B timed blocks.
-    Returns per-block wall seconds and HIP-event ms (each MAX over ranks), this rank's own per-block wall seconds, and the
-    number of launches issued."""
-    probe = ranks.reduce([timed_block(eng, ranks, T, K)[0]], 'MAX')[0]
-    blocks = int(min(max_blocks, max(3, np.ceil(min_seconds / max(probe, 1e-6)))))
-    wall, kern = [], []
-    for _ in range(blocks):
-        e, k = timed_block(eng, ranks, T, K)
-        wall.append(e)
-        kern.append(k)
-    both = ranks.reduce(wall + kern, 'MAX')
-    return both[:blocks], both[blocks:], wall, (blocks + 1) * K
+def timed_region(eng, ranks, T, K):
+    """The settle launches of the kind (settle_launches: a fixed number, untimed), then ONE timed block of exactly K launches, so
+    that --steps is the number of timed launches and every run issues the same launches.  Returns the block's wall seconds and
+    HIP-event ms (each MAX over ranks) and this rank's own wall seconds, each as a one-element list, and the number of launches
+    issued."""
+    settle = settle_launches(eng, T, 'uniform', trajectory=True)
+    for _ in range(settle):
+        eng.rollout(T, 'uniform', auto_reset=True, trajectory=True)
+    e, k = timed_block(eng, ranks, T, K)
+    both = ranks.reduce([e, k], 'MAX')
+    return both[:1], both[1:], [e], 1 + settle + K
 
 
 @contextlib.contextmanager
@@ -98,7 +96,12 @@ def settle_launches(eng, T, policy, **kw):
     """Untimed launches in front of a timed block of a launch kind: 3, or 200 for a kind whose rows keep a store schedule
     (the closed loop of the store pacing runs inside the launches themselves; 200 launches = 20 ms at the headline size)."""
     eng.rollout(T, policy, auto_reset=True, **kw)
-    paced = hasattr(eng, 'rollout_pacing') and eng.rollout_pacing(policy, True, packed=kw.get('trajectory') == 'packed') is not None
+    return settle_count(eng, policy, packed=kw.get('trajectory') == 'packed')
+
+
+def settle_count(eng, policy, packed=False):
+    """settle_launches' number for an engine that has launched the kind at least once."""
+    paced = hasattr(eng, 'rollout_pacing') and eng.rollout_pacing(policy, True, packed=packed) is not None
     return 200 if paced else 3
 
 
