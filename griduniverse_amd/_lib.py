@@ -23,6 +23,7 @@ ERR_NAMES = {-1: 'GU_ERR_INVALID', -2: 'GU_ERR_HIP', -3: 'GU_ERR_NOMEM', -4: 'GU
 
 F_AUTO_RESET, F_TRAJECTORY, F_STATS, F_PINNED_IO, F_PACKED = 1, 2, 4, 8, 16
 POLICY_UNIFORM, POLICY_STREAM, POLICY_GREEDY, POLICY_SAMPLE = 0, 1, 2, 3
+TD_Q_LEARNING, TD_SARSA = 0, 1
 COMM_ID_BYTES = 128
 OPT_UNSET = -2 ** 63
 # gu_set_option / gu_get_option (include/gu.h "options"): name -> id
@@ -79,6 +80,10 @@ SIGNATURES = {
     'gu_set_state': [_vp, _vp, _vp, _vp, _vp],
     'gu_done_indices': [_vp, _vp, _vp],
     'gu_look_step_ahead': [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
+    'gu_td_init': [_vp, _f64],
+    'gu_td_run': [_vp, _i64, _i32, _f64, _f64, _u32, _u32],
+    'gu_td_get_q': [_vp, _i64, _i64, _vp],
+    'gu_td_set_q': [_vp, _i64, _i64, _vp],
     'gu_vi_set': [_vp, _vp, _vp],
     'gu_vi_sweep': [_vp, _f64, _i32, _i32, _vp],
     'gu_vi_run': [_vp, _f64, _f64, _i32, _vp, _vp],

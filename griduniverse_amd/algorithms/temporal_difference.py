@@ -1,0 +1,63 @@
+"""Tabular temporal-difference control: Q-learning (off-policy) and SARSA (on-policy), the next algorithms on the reference's
+roadmap (README.md "Temporal Difference (TD) Learning"; it ships no code for them, so the semantics are this build's:
+include/gu.h, gu_td_run).
+
+`q_learning` / `sarsa` run `num_learners` independent epsilon-greedy learners on the grid of a facade `GridUniverseEnv`, learner e
+in env e of a batch, each with its own float64 Q table, all advanced on the MI355X by one kernel (csrc/gu_td.hip).  The facade's
+own state is left alone.  `greedy_policy` turns a learned table into the reference's policy-matrix format, so it feeds
+`get_policy_map`, `engine.vi_set` and `rollout(policy='greedy')` like a policy from dynamic programming.
+"""
+import numpy as np
+
+from ..vec_env import VecGridUniverse
+
+_CHUNK = 100000  # steps per launch (the launch limit is 1e8; shorter launches keep the device responsive)
+
+
+def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0):
+    L = int(num_learners)
+    if L < 1:
+        raise ValueError('num_learners must be at least 1')
+    if not 0.0 <= float(epsilon) <= 1.0:
+        raise ValueError('epsilon must lie in [0, 1]')
+    vec = VecGridUniverse(L, template=env, seed=seed)
+    try:
+        vec.engine.td_init(q0)
+        vec._td_ready = True
+        vec.reset()
+        left = int(num_steps)
+        while left > 0:
+            T = min(left, _CHUNK)
+            vec.td_run(T, method, alpha, discount_factor, epsilon)
+            left -= T
+        q = vec.q_table()
+    finally:
+        vec.close()
+    return q[0] if L == 1 else q
+
+
+def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):
+    """Epsilon-greedy Q-learning, `num_steps` env steps per learner (episodes restart at a start cell when they end).  Returns
+    Q float64[S][4], or [L][S][4] for L = num_learners > 1."""
+    return _td('q_learning', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0)
+
+
+def sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):
+    """Epsilon-greedy SARSA; arguments and result as `q_learning`."""
+    return _td('sarsa', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0)
+
+
+def greedy_policy(q, env):
+    """Policy matrix [S][4] of the greedy actions of Q [S][4], in the format of the reference's
+    greedy_policy_from_value_function (core/algorithms/utils.py:55-72): the actions whose value equals the row maximum after
+    rounding to 8 decimals share the probability equally; rows of terminal states are all zero."""
+    q = np.asarray(q, np.float64)
+    S = env.world.size
+    if q.shape != (S, 4):
+        raise ValueError('q must have shape ({}, 4), got {}'.format(S, q.shape))
+    rounded = np.around(q, 8)
+    best = rounded == np.around(np.amax(q, axis=1), 8)[:, None]
+    policy = best / best.sum(axis=1, keepdims=True)
+    terminal = np.array([bool(env.is_terminal(s)) for s in range(S)])
+    policy[terminal] = 0.0
+    return policy

@@ -4,6 +4,7 @@
 #include "gu_rng.hpp"
 
 #include <atomic>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -168,7 +169,7 @@ int gu_destroy(gu_handle h)
     gu_placement_release(h);
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
-                    h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt};
+                    h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -236,6 +237,14 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
     const int32_t cell_bytes = (S + 15) & ~15;
     GU_HIP(hipStreamSynchronize(h->stream));
     h->entry_table_ok = false;  // (other cells, other flags)
+    h->td_carry = false;
+    if (h->td_S && h->td_S != W * H) {  // Q tables of another state count belong to another grid: gu_td_init again
+        if (h->d_q) GU_HIP(hipFree(h->d_q));
+        if (h->d_td_next) GU_HIP(hipFree(h->d_td_next));
+        h->d_q = nullptr;
+        h->d_td_next = nullptr;
+        h->td_S = 0;
+    }
     h->nib_valid = false;
     if (h->d_nib) GU_HIP(hipFree(h->d_nib));
     h->d_nib = nullptr;
@@ -380,6 +389,7 @@ int gu_seed(gu_handle h, uint64_t seed)
     h->seed = seed;
     h->seed_prefix = gu_rng_seed_prefix(seed);
     h->steps_taken = 0;
+    h->td_carry = false;
     h->off_lo = h->off_hi = 0;
     h->off_exact = true;
     if (h->graph_exec) {  // captured step launches carry the old seed in their arguments
@@ -645,6 +655,7 @@ int gu_step_graph(gu_handle h, int64_t t0, int64_t T, uint32_t flags)
     }
     GU_HIP(hipGraphLaunch(h->graph_exec, h->stream));
     h->steps_taken += (uint64_t)T;
+    h->td_carry = false;
     return GU_OK;
 }
 
@@ -1092,6 +1103,93 @@ int gu_read_stats(gu_handle h, int64_t *reward_sum, int32_t *episodes)
     return GU_OK;
 }
 
+// ---------------------------------------------------------------------------------- tabular TD control (gu_td.hip)
+int gu_td_init(gu_handle h, double q0)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(std::isfinite(q0), GU_ERR_INVALID, "q0 must be finite");
+    h->td_carry = false;
+    const size_t bytes = (size_t)h->N * (size_t)h->S * 4 * sizeof(double);
+    if (!h->d_q || h->td_S != h->S) {
+        GU_HIP(hipStreamSynchronize(h->stream));
+        if (h->d_q) GU_HIP(hipFree(h->d_q));
+        if (h->d_td_next) GU_HIP(hipFree(h->d_td_next));
+        h->d_q = nullptr;
+        h->d_td_next = nullptr;
+        h->td_S = 0;
+        size_t free_b = 0, total_b = 0;
+        GU_HIP(hipMemGetInfo(&free_b, &total_b));
+        // (what is left has to hold the trajectory buffer and the scratch of other calls too: keep 1 GiB of headroom)
+        GU_REQUIRE(bytes + ((size_t)1 << 30) <= free_b, GU_ERR_NOMEM, "Q tables of %lld envs x %d states need %.2f GiB, %.2f GiB are free",
+                   (long long)h->N, h->S, bytes / 1073741824.0, free_b / 1073741824.0);
+        GU_HIP(hipMalloc(&h->d_q, bytes));
+        GU_HIP(hipMalloc(&h->d_td_next, (size_t)h->N));
+        h->td_S = h->S;
+    }
+    GU_HIP(hipMemsetAsync(h->d_td_next, 0xFF, (size_t)h->N, h->stream));
+    int rc = gu_td_fill(h, q0);
+    if (rc != GU_OK) return rc;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_td_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(T >= 0 && T <= 100000000, GU_ERR_INVALID, "T %lld out of range (0 .. 1e8)", (long long)T);
+    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Q-learning, 1 = SARSA", method);
+    GU_REQUIRE(eps_q16 <= 65536u, GU_ERR_INVALID, "eps_q16 %u above 65536", eps_q16);
+    GU_REQUIRE(std::isfinite(alpha) && std::isfinite(gamma), GU_ERR_INVALID, "alpha and gamma must be finite");
+    GU_REQUIRE((flags & ~(GU_F_TRAJECTORY | GU_F_STATS)) == 0, GU_ERR_INVALID, "gu_td_run accepts GU_F_TRAJECTORY and GU_F_STATS only (flags 0x%x)", flags);
+    if (flags & GU_F_TRAJECTORY)
+        GU_REQUIRE(h->d_traj && T <= h->traj_T, GU_ERR_STATE, "trajectory buffer holds %lld rows, need %lld: call gu_reserve_trajectory",
+                   (long long)h->traj_T, (long long)T);
+    GU_REQUIRE(!h->trail_cap || (flags & GU_F_TRAJECTORY), GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): gu_td_run must write rows (GU_F_TRAJECTORY) to feed it");
+    if (T == 0) return GU_OK;
+    int rc = gu_launch_td(h, T, method, alpha, gamma, eps_q16, flags);
+    if (rc == GU_OK) {
+        h->stats_valid = (flags & GU_F_STATS) != 0;
+        if (flags & GU_F_TRAJECTORY) h->traj_kind = 1;
+    }
+    return rc;
+}
+
+static int gu_td_range(gu_engine *h, int64_t env0, int64_t n, const void *q)
+{
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(q != nullptr, GU_ERR_INVALID, "q is NULL");
+    GU_REQUIRE(env0 >= 0 && n >= 0 && env0 + n <= h->N, GU_ERR_INVALID, "envs [%lld, %lld) outside 0 .. %lld", (long long)env0,
+               (long long)(env0 + n), (long long)h->N);
+    return GU_OK;
+}
+
+int gu_td_get_q(gu_handle h, int64_t env0, int64_t n, double *q)
+{
+    GU_ENTER(h);
+    int rc = gu_td_range(h, env0, n, q);
+    if (rc != GU_OK) return rc;
+    const size_t row = (size_t)h->S * 4;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n) GU_HIP(hipMemcpy(q, h->d_q + (size_t)env0 * row, (size_t)n * row * sizeof(double), hipMemcpyDeviceToHost));
+    return GU_OK;
+}
+
+int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q)
+{
+    GU_ENTER(h);
+    int rc = gu_td_range(h, env0, n, q);
+    if (rc != GU_OK) return rc;
+    h->td_carry = false;
+    const size_t row = (size_t)h->S * 4;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n) GU_HIP(hipMemcpy(h->d_q + (size_t)env0 * row, q, (size_t)n * row * sizeof(double), hipMemcpyHostToDevice));
+    return GU_OK;
+}
+
 // ---------------------------------------------------------------------------------- state
 int gu_get_state(gu_handle h, int32_t *pos, int32_t *done, uint32_t *episode, uint64_t *tcount)
 {
@@ -1113,6 +1211,7 @@ int gu_set_state(gu_handle h, const int32_t *pos, const int32_t *done, const uin
 {
     GU_ENTER(h);
     h->entry_table_ok = false;
+    h->td_carry = false;
     GU_NEED_GRID(h);
     const size_t n = (size_t)h->N;
     if (pos)

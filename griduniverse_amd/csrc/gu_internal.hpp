@@ -257,6 +257,12 @@ struct gu_engine {
     int64_t vi_xcd_torn = 0;        // -DGU_VI_XCD_TORN builds: exchange words found with the right tag and the wrong payload, summed over the per-XCD launches
     int vi_dp_form = 0;             // ... and the last gu_vi_sweep / gu_vi_run / gu_vi_eval_run: 1 per XCD, 2 one workgroup, 3 chip-wide cluster, 4 one launch per round
 
+    // batched tabular TD control (gu_td.hip): off until gu_td_init
+    double *d_q = nullptr;        // [N][td_S][4] one float64 Q table per env
+    int8_t *d_td_next = nullptr;  // [N] SARSA: the action a' carried from one launch to the next (-1: none)
+    int32_t td_S = 0;             // states of the tables (0: none allocated); a grid of another size drops them
+    bool td_carry = false;        // the last call that touched the envs was a SARSA gu_td_run: the next one starts from d_td_next
+
     // agent trail (gu_trail.hip): off unless gu_trail_enable was called
     int32_t trail_cap = 0;             // entries per env (0: off)
     int32_t *d_trail = nullptr;        // [N][trail_cap] ring of cells
@@ -387,6 +393,10 @@ void gu_vi_xcd_free(gu_engine *h);
 int gu_vi_xcd_fused_run(gu_engine *h, const GuXcdPlan &xp, double gamma, int32_t iters, uint32_t flags, double *deltas);
 int gu_vi_xcd_dp_run(gu_engine *h, double gamma, double threshold, bool use_threshold, bool greedy, int32_t max_rounds, int32_t *rounds_done,
                      double *deltas);
+
+// ---- batched tabular TD control (gu_td.hip) ----------------------------------------
+int gu_td_fill(gu_engine *h, double q0);  // every entry of every table = q0 (async)
+int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 
 // ---- agent trail (gu_trail.hip): no-ops while the trail is off ----------------------
 int gu_trail_after_step(gu_engine *h, uint32_t flags);

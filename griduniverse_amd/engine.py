@@ -14,6 +14,7 @@ from .grid import GridSpec
 
 _POLICIES = {'uniform': _lib.POLICY_UNIFORM, 'stream': _lib.POLICY_STREAM, 'greedy': _lib.POLICY_GREEDY,
              'sample': _lib.POLICY_SAMPLE}
+_TD_METHODS = {'q_learning': _lib.TD_Q_LEARNING, 'sarsa': _lib.TD_SARSA, 0: _lib.TD_Q_LEARNING, 1: _lib.TD_SARSA}
 
 
 class Engine(object):
@@ -305,6 +306,32 @@ class Engine(object):
         eps = np.empty(self.N, np.int32)
         check(self.lib.gu_read_stats(self._h, ptr(ret), ptr(eps)))
         return ret, eps
+
+    # ------------------------------------------------------------------ tabular TD control (include/gu.h: gu_td_*)
+    def td_init(self, q0=0.0):
+        """One float64 Q table [S][4] per env, every entry q0."""
+        check(self.lib.gu_td_init(self._h, float(q0)))
+
+    def td_run(self, T, method='q_learning', alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
+        """T epsilon-greedy Q-learning / SARSA iterations per env in one launch (auto-reset always on).  eps_q16: explore
+        probability in 1/65536 (65536 = always).  Rows and statistics as rollout(): read_trajectory / read_stats."""
+        flags = (_lib.F_TRAJECTORY if trajectory else 0) | (_lib.F_STATS if stats else 0)
+        check(self.lib.gu_td_run(self._h, int(T), _TD_METHODS[method], float(alpha), float(gamma), int(eps_q16), flags))
+
+    def td_get_q(self, env0=0, n=None):
+        """float64[n, S, 4]: the tables of envs env0 .. env0+n-1 (all from env0 when n is None)."""
+        n = self.N - int(env0) if n is None else int(n)
+        q = np.empty((max(n, 0), self.spec.S, 4), np.float64)
+        check(self.lib.gu_td_get_q(self._h, int(env0), n, ptr(q)))
+        return q
+
+    def td_set_q(self, q, env0=0):
+        """Install tables float64[n, S, 4] (or [S, 4] for one env) for envs env0 .. env0+n-1."""
+        q = np.asarray(q, np.float64)
+        q = _lib.as_array(q.reshape((-1, self.spec.S, 4)) if q.ndim == 2 else q, np.float64, None, 'q')
+        if q.ndim != 3 or q.shape[1:] != (self.spec.S, 4):
+            raise ValueError('q must have shape (n, {}, 4), got {}'.format(self.spec.S, q.shape))
+        check(self.lib.gu_td_set_q(self._h, int(env0), q.shape[0], ptr(q)))
 
     # ------------------------------------------------------------------ state
     def get_state(self):

@@ -9,6 +9,9 @@ one, keyed by (seed, GLOBAL env id, stream, counter):
     stream 1  start cell      : index = (word(episode) * n_starts) >> 32, episode = resets since gu_seed
     stream 2  sampled actions : u = word(t) / 2**32 against the cumulative policy row
     stream 3  maze generation : draw k of grid g = (word(k) * n) >> 32, keyed by (maze_seed, global grid id)
+    stream 4  TD control      : one word per step of gu_td_run, counter t & 0xFFFFFFFF, epoch t >> 32 (hashed right behind the
+                                seed when it is not zero, as for streams 0 and 2); explore iff (word >> 16) < eps_q16, explore action
+                                word & 3, greedy tie index (((word >> 2) & 0x3FFF) * ties) >> 14
 
 These helpers let a caller reproduce on the host exactly what a `policy='uniform'` rollout did on the device -- e.g.
 to replay the same (grid, seed, action) sequence through the reference's own `step()`.
@@ -30,15 +33,17 @@ def _block(h, k):
     return (h * np.uint64(5) + np.uint64(0xE6546B64)) & _M32
 
 
-def words(seed, env_ids, stream, counters):
-    """uint32 RNG words for broadcastable arrays of global env ids and counters."""
+def words(seed, env_ids, stream, counters, epochs=None):
+    """uint32 RNG words for broadcastable arrays of global env ids and counters (and epochs: hashed behind the seed where not 0)."""
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     env = np.asarray(env_ids, dtype=np.uint64) & _M32
     ctr = np.asarray(counters, dtype=np.uint64) & _M32
-    env, ctr = np.broadcast_arrays(env, ctr)
+    epoch = np.zeros((), np.uint64) if epochs is None else np.asarray(epochs, dtype=np.uint64) & _M32
+    env, ctr, epoch = np.broadcast_arrays(env, ctr, epoch)
     h = np.full(env.shape, 0x9747B28C, dtype=np.uint64)
-    for k in (np.uint64(seed & 0xFFFFFFFF), np.uint64(seed >> 32), env,
-              np.uint64((int(stream) & 0xF) << 28) | (ctr & np.uint64(0x0FFFFFFF))):
+    h = _block(_block(h, np.uint64(seed & 0xFFFFFFFF)), np.uint64(seed >> 32))
+    h = np.where(epoch != 0, _block(h, epoch), h)
+    for k in (env, np.uint64((int(stream) & 0xF) << 28) | (ctr & np.uint64(0x0FFFFFFF))):
         h = _block(h, k)
     high = ctr >> np.uint64(28)
     h = np.where(high != 0, _block(h, high) ^ np.uint64(20), h ^ np.uint64(16))
@@ -61,3 +66,11 @@ def start_indices(seed, env_ids, episodes, n_starts):
     """Index into starting_states chosen at reset number `episodes` (0 = first reset after gu_seed)."""
     w = words(seed, env_ids, 1, episodes).astype(np.uint64)
     return ((w * np.uint64(int(n_starts))) >> np.uint64(32)).astype(np.int32)
+
+
+def epsilon_greedy_words(seed, env_ids, t0, T):
+    """uint32[T, N]: the stream-4 words behind steps t0 .. t0+T-1 (64-bit step counts) of gu_td_run for global env ids `env_ids`.
+    t0 is one count for all, or one per env."""
+    t = np.arange(T, dtype=np.uint64)[:, None] + np.asarray(t0, dtype=np.uint64)
+    env = np.asarray(env_ids, dtype=np.uint64)[None, :]
+    return words(seed, env, 4, t & _M32, t >> np.uint64(32))

@@ -20,6 +20,8 @@ from .grid import GridSpec
 
 
 class VecGridUniverse(object):
+    _td_ready = False  # the engine holds Q tables (td_run / set_q_table allocate them on first use)
+
     def __init__(self, num_envs, grid_shape=(4, 4), *, initial_state=0, goal_states=None, lava_states=None,
                  walls=None, custom_world_fp=None, random_maze=False, template=None, templates=None,
                  device_mazes=None, maze_seed=0, seed=0, device=0, env_id0=0, auto_reset=False, engine_factory=Engine):
@@ -104,6 +106,33 @@ class VecGridUniverse(object):
         if stats:
             out['ret'], out['episodes'] = self.engine.read_stats()
         return out
+
+    def td_run(self, T, method='q_learning', alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
+        """T iterations of batched tabular Q-learning ('q_learning') or SARSA ('sarsa'): env e learns its own Q table [S][4]
+        from its own experience, epsilon-greedy, auto-reset always on (include/gu.h: gu_td_run).  The first call gives every
+        env a table of zeros.  Returns a dict like rollout(): obs/reward/done int32[T, N] when `trajectory`, ret/episodes
+        when `stats`."""
+        if not self._td_ready:
+            self.engine.td_init(0.0)
+            self._td_ready = True
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.td_run(T, method, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
+        out = self.engine.read_trajectory(0, T) if trajectory and T > 0 else {}
+        if stats:
+            out['ret'], out['episodes'] = self.engine.read_stats()
+        return out
+
+    def q_table(self, env0=0, n=None):
+        """float64[n, S, 4]: the Q tables of envs env0 .. env0+n-1 (to the end when n is None)."""
+        return self.engine.td_get_q(env0, n)
+
+    def set_q_table(self, q, env0=0):
+        """Install Q tables float64[n, S, 4] (or [S, 4]) for envs env0 ..; the other envs get tables of zeros if they had none."""
+        if not self._td_ready:
+            self.engine.td_init(0.0)
+            self._td_ready = True
+        self.engine.td_set_q(q, env0)
 
     def done_indices(self):
         return self.engine.done_indices()

@@ -253,6 +253,32 @@ int gu_set_state(gu_handle h, const int32_t *pos, const int32_t *done, const uin
  * bookkeeping (core/algorithms/monte_carlo.py:19-25).  idx has room for N entries. */
 int gu_done_indices(gu_handle h, int32_t *idx, int32_t *count);
 
+/* ---- batched tabular TD control: N independent learners, learner e owns env e and its own float64 table Q_e[S][4] ----
+ * (build-defined: the reference lists Q-learning and SARSA on its roadmap and ships no TD code; tests/_td_oracle.py is the CPU
+ * restatement.)  One iteration of gu_td_run for env e at 64-bit step count t:
+ *   1. if done: reset as gu_step under GU_F_AUTO_RESET does (start from RNG stream 1 at `episode`, then episode += 1) -- always on;
+ *   2. w = the word of RNG stream 4 with counter t & 0xFFFFFFFF and epoch t >> 32 (keyed like streams 0 and 2).  Explore iff
+ *      (w >> 16) < eps_q16 (0 .. 65536; 65536 = always): action w & 3.  Else greedy on Q_e[s]: of the m actions whose value equals
+ *      the row maximum exactly, in ascending order, the one at index (((w >> 2) & 0x3FFF) * m) >> 14.  SARSA uses the carried
+ *      action a' instead -- inside a launch always, and at its start when it directly follows a SARSA gu_td_run on this engine
+ *      (no gu_seed, gu_reset*, gu_step*, gu_rollout, gu_set_state, gu_set_grid(s), gu_generate_mazes, gu_td_init, gu_td_set_q or
+ *      sweep-step call in between);
+ *   3. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
+ *   4. float64, one rounding per operation: m = max Q_e[s'] (Q-learning) or Q_e[s'][a'] with a' drawn at s' by rule 2 from the word
+ *      of the new t and the pre-update row (SARSA; not drawn when d); target = r if d else r + gamma * m;
+ *      Q_e[s][a] += alpha * (target - Q_e[s][a]).
+ * gu_td_init  : allocate the tables (N * S * 32 bytes; GU_ERR_NOMEM when free device memory cannot hold them with 1 GiB to
+ *               spare) and set every entry to q0.  A grid of another size drops the tables (gu_td_init again).
+ * gu_td_run   : T iterations per env in ONE launch (async).  method 0 = Q-learning, 1 = SARSA.  GU_F_TRAJECTORY writes the
+ *               (obs, reward, done) rows as gu_rollout does (gu_read_trajectory), GU_F_STATS the per-env sums for gu_read_stats;
+ *               no other flag.  GU_ERR_STATE before gu_td_init; GU_ERR_INVALID for a method other than 0 / 1, eps_q16 > 65536,
+ *               non-finite alpha or gamma, T < 0.  The step counts advance by T.
+ * gu_td_get_q / gu_td_set_q : tables of envs env0 .. env0+n-1 as q[n][S][4] on the host. */
+int gu_td_init(gu_handle h, double q0);
+int gu_td_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+int gu_td_get_q(gu_handle h, int64_t env0, int64_t n, double *q);
+int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q);
+
 /* ---- look_step_ahead table queries: env:136-155 for n (state, action) pairs (grid 0 of a multi-grid engine) ---- */
 int gu_look_step_ahead(gu_handle h, int64_t n, const int32_t *states, const int32_t *actions,
                        int32_t care_about_terminal, int32_t *next, int32_t *reward, int32_t *done);
