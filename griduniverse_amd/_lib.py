@@ -84,6 +84,9 @@ SIGNATURES = {
     'gu_td_run': [_vp, _i64, _i32, _f64, _f64, _u32, _u32],
     'gu_td_get_q': [_vp, _i64, _i64, _vp],
     'gu_td_set_q': [_vp, _i64, _i64, _vp],
+    'gu_dyna_init': [_vp],
+    'gu_dyna_run': [_vp, _i64, _i32, _f64, _f64, _u32, _u32],
+    'gu_dyna_get_model': [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     'gu_vi_set': [_vp, _vp, _vp],
     'gu_vi_sweep': [_vp, _f64, _i32, _i32, _vp],
     'gu_vi_run': [_vp, _f64, _f64, _i32, _vp, _vp],

@@ -14,6 +14,8 @@
 #include <mutex>
 #include <vector>
 
+static void gu_dyna_free(gu_engine *h);  // (tabular Dyna-Q, below)
+
 // ---------------------------------------------------------------------------------- errors
 static thread_local std::string g_last_error;
 
@@ -169,7 +171,8 @@ int gu_destroy(gu_handle h)
     gu_placement_release(h);
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
-                    h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next};
+                    h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next,
+                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -245,6 +248,8 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
         h->d_td_next = nullptr;
         h->td_S = 0;
     }
+    if (h->dyna_S && h->dyna_S != W * H) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
+    h->dyna_exact = false;  // a kept model may hold outcomes of the old cells: gu_dyna_run compares every observation from now on
     h->nib_valid = false;
     if (h->d_nib) GU_HIP(hipFree(h->d_nib));
     h->d_nib = nullptr;
@@ -1187,6 +1192,103 @@ int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q)
     const size_t row = (size_t)h->S * 4;
     GU_HIP(hipStreamSynchronize(h->stream));
     if (n) GU_HIP(hipMemcpy(h->d_q + (size_t)env0 * row, q, (size_t)n * row * sizeof(double), hipMemcpyHostToDevice));
+    return GU_OK;
+}
+
+// ---------------------------------------------------------------------------------- tabular Dyna-Q (gu_dyna.hip)
+static void gu_dyna_free(gu_engine *h)
+{
+    if (h->d_dyna_model) (void)hipFree(h->d_dyna_model);
+    if (h->d_dyna_list) (void)hipFree(h->d_dyna_list);
+    if (h->d_dyna_count) (void)hipFree(h->d_dyna_count);
+    if (h->d_dyna_seen) (void)hipFree(h->d_dyna_seen);
+    h->d_dyna_model = nullptr;
+    h->d_dyna_list = nullptr;
+    h->d_dyna_count = nullptr;
+    h->d_dyna_seen = nullptr;
+    h->dyna_S = 0;
+    h->dyna_exact = false;
+}
+
+int gu_dyna_init(gu_handle h)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    h->td_carry = false;
+    const size_t pairs = (size_t)h->N * (size_t)h->S * 4;
+    if (!h->d_dyna_model || h->dyna_S != h->S) {
+        GU_HIP(hipStreamSynchronize(h->stream));
+        gu_dyna_free(h);
+        const size_t bytes = pairs * (sizeof(uint64_t) + sizeof(int32_t)) + (size_t)h->N * (sizeof(int32_t) + (size_t)h->S);
+        size_t free_b = 0, total_b = 0;
+        GU_HIP(hipMemGetInfo(&free_b, &total_b));
+        // (the same 1 GiB of headroom as gu_td_init)
+        GU_REQUIRE(bytes + ((size_t)1 << 30) <= free_b, GU_ERR_NOMEM, "Dyna-Q models of %lld envs x %d states need %.2f GiB, %.2f GiB are free",
+                   (long long)h->N, h->S, bytes / 1073741824.0, free_b / 1073741824.0);
+        GU_HIP(hipMalloc(&h->d_dyna_model, pairs * sizeof(uint64_t)));
+        GU_HIP(hipMalloc(&h->d_dyna_list, pairs * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_dyna_count, (size_t)h->N * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_dyna_seen, (size_t)h->N * (size_t)h->S));
+        h->dyna_S = h->S;
+    }
+    h->dyna_exact = true;
+    GU_HIP(hipMemsetAsync(h->d_dyna_model, 0xFF, pairs * sizeof(uint64_t), h->stream));
+    GU_HIP(hipMemsetAsync(h->d_dyna_list, 0xFF, pairs * sizeof(int32_t), h->stream));
+    GU_HIP(hipMemsetAsync(h->d_dyna_count, 0, (size_t)h->N * sizeof(int32_t), h->stream));
+    GU_HIP(hipMemsetAsync(h->d_dyna_seen, 0, (size_t)h->N * (size_t)h->S, h->stream));
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_dyna_run(gu_handle h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(h->d_dyna_model && h->dyna_S == h->S, GU_ERR_STATE, "no Dyna-Q model: call gu_dyna_init first");
+    GU_REQUIRE(P >= 0 && P <= 256, GU_ERR_INVALID, "planning steps %d out of range (0 .. 256)", P);
+    GU_REQUIRE(T >= 0 && T <= 100000000 && T * (int64_t)(P + 1) <= 100000000, GU_ERR_INVALID,
+               "T %lld x (P + 1) = %lld updates out of range (0 .. 1e8)", (long long)T, (long long)T * (P + 1));
+    GU_REQUIRE(eps_q16 <= 65536u, GU_ERR_INVALID, "eps_q16 %u above 65536", eps_q16);
+    GU_REQUIRE(std::isfinite(alpha) && std::isfinite(gamma), GU_ERR_INVALID, "alpha and gamma must be finite");
+    GU_REQUIRE((flags & ~(GU_F_TRAJECTORY | GU_F_STATS)) == 0, GU_ERR_INVALID, "gu_dyna_run accepts GU_F_TRAJECTORY and GU_F_STATS only (flags 0x%x)", flags);
+    if (flags & GU_F_TRAJECTORY)
+        GU_REQUIRE(h->d_traj && T <= h->traj_T, GU_ERR_STATE, "trajectory buffer holds %lld rows, need %lld: call gu_reserve_trajectory",
+                   (long long)h->traj_T, (long long)T);
+    GU_REQUIRE(!h->trail_cap || (flags & GU_F_TRAJECTORY), GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): gu_dyna_run must write rows (GU_F_TRAJECTORY) to feed it");
+    if (T == 0) return GU_OK;
+    int rc = gu_launch_dyna(h, T, P, alpha, gamma, eps_q16, flags);
+    if (rc == GU_OK) {
+        h->stats_valid = (flags & GU_F_STATS) != 0;
+        if (flags & GU_F_TRAJECTORY) h->traj_kind = 1;
+    }
+    return rc;
+}
+
+int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32_t *reward, int32_t *done, int32_t *list, int32_t *count)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_dyna_model && h->dyna_S == h->S, GU_ERR_STATE, "no Dyna-Q model: call gu_dyna_init first");
+    GU_REQUIRE(env0 >= 0 && n >= 0 && env0 + n <= h->N, GU_ERR_INVALID, "envs [%lld, %lld) outside 0 .. %lld", (long long)env0,
+               (long long)(env0 + n), (long long)h->N);
+    const size_t pairs = (size_t)h->S * 4, k = (size_t)n * pairs;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!n) return GU_OK;
+    if (next || reward || done) {
+        std::vector<uint64_t> words(k);
+        GU_HIP(hipMemcpy(words.data(), h->d_dyna_model + (size_t)env0 * pairs, k * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < k; ++i) {
+            const uint64_t w = words[i];
+            const bool seen = w != ~0ull;
+            const uint32_t hi = (uint32_t)(w >> 32);
+            if (next) next[i] = seen ? (int32_t)(hi & 0x7FFFFFFFu) : -1;
+            if (reward) reward[i] = seen ? (int32_t)(uint32_t)w : 0;
+            if (done) done[i] = seen ? (int32_t)(hi >> 31) : 0;
+        }
+    }
+    if (list) GU_HIP(hipMemcpy(list, h->d_dyna_list + (size_t)env0 * pairs, k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (count) GU_HIP(hipMemcpy(count, h->d_dyna_count + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return GU_OK;
 }
 

@@ -262,6 +262,13 @@ struct gu_engine {
     int8_t *d_td_next = nullptr;  // [N] SARSA: the action a' carried from one launch to the next (-1: none)
     int32_t td_S = 0;             // states of the tables (0: none allocated); a grid of another size drops them
     bool td_carry = false;        // the last call that touched the envs was a SARSA gu_td_run: the next one starts from d_td_next
+    // batched tabular Dyna-Q (gu_dyna.hip): off until gu_dyna_init; learns into d_q
+    uint64_t *d_dyna_model = nullptr;  // [N][dyna_S*4] one packed word per (s, a): reward | (s' | done << 31) << 32; ~0 = unobserved
+    int32_t *d_dyna_list = nullptr;    // [N][dyna_S*4] observed pairs s*4+a in the order of first observation (-1 beyond count)
+    int32_t *d_dyna_count = nullptr;   // [N] entries of the list
+    uint8_t *d_dyna_seen = nullptr;    // [N][dyna_S] bit a of byte s: (s, a) observed (the real step's test while dyna_exact)
+    int32_t dyna_S = 0;                // states of the model (0: none allocated); a grid of another size drops it
+    bool dyna_exact = false;           // every observed entry is what the current grid gives: no grid install since gu_dyna_init
 
     // agent trail (gu_trail.hip): off unless gu_trail_enable was called
     int32_t trail_cap = 0;             // entries per env (0: off)
@@ -397,6 +404,9 @@ int gu_vi_xcd_dp_run(gu_engine *h, double gamma, double threshold, bool use_thre
 // ---- batched tabular TD control (gu_td.hip) ----------------------------------------
 int gu_td_fill(gu_engine *h, double q0);  // every entry of every table = q0 (async)
 int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+
+// ---- batched tabular Dyna-Q (gu_dyna.hip) -------------------------------------------
+int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 
 // ---- agent trail (gu_trail.hip): no-ops while the trail is off ----------------------
 int gu_trail_after_step(gu_engine *h, uint32_t flags);

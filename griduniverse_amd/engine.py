@@ -333,6 +333,28 @@ class Engine(object):
             raise ValueError('q must have shape (n, {}, 4), got {}'.format(self.spec.S, q.shape))
         check(self.lib.gu_td_set_q(self._h, int(env0), q.shape[0], ptr(q)))
 
+    # ------------------------------------------------------------------ tabular Dyna-Q (include/gu.h: gu_dyna_*)
+    def dyna_init(self):
+        """A cleared Dyna-Q model per env (count 0, every (s, a) unobserved); the Q tables come from td_init."""
+        check(self.lib.gu_dyna_init(self._h))
+
+    def dyna_run(self, T, planning_steps=10, alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
+        """T real Q-learning steps per env in one launch, each followed by `planning_steps` updates replayed from the env's
+        learned model.  Rows and statistics (real steps only) as td_run()."""
+        flags = (_lib.F_TRAJECTORY if trajectory else 0) | (_lib.F_STATS if stats else 0)
+        check(self.lib.gu_dyna_run(self._h, int(T), int(planning_steps), float(alpha), float(gamma), int(eps_q16), flags))
+
+    def dyna_get_model(self, env0=0, n=None):
+        """The models of envs env0 .. env0+n-1: dict next / reward / done int32[n, S, 4] (unobserved: -1 / 0 / 0),
+        list int32[n, 4S] (observed pairs s*4+a in first-observation order, -1 beyond count) and count int32[n]."""
+        n = self.N - int(env0) if n is None else int(n)
+        n0, S = max(n, 0), self.spec.S
+        out = dict(next=np.empty((n0, S, 4), np.int32), reward=np.empty((n0, S, 4), np.int32), done=np.empty((n0, S, 4), np.int32),
+                   list=np.empty((n0, 4 * S), np.int32), count=np.empty(n0, np.int32))
+        check(self.lib.gu_dyna_get_model(self._h, int(env0), n, ptr(out['next']), ptr(out['reward']), ptr(out['done']),
+                                         ptr(out['list']), ptr(out['count'])))
+        return out
+
     # ------------------------------------------------------------------ state
     def get_state(self):
         pos, don = np.empty(self.N, np.int32), np.empty(self.N, np.int32)

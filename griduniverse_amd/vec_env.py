@@ -21,6 +21,7 @@ from .grid import GridSpec
 
 class VecGridUniverse(object):
     _td_ready = False  # the engine holds Q tables (td_run / set_q_table allocate them on first use)
+    _dyna_ready = False  # ... and Dyna-Q models (dyna_run / model allocate them on first use)
 
     def __init__(self, num_envs, grid_shape=(4, 4), *, initial_state=0, goal_states=None, lava_states=None,
                  walls=None, custom_world_fp=None, random_maze=False, template=None, templates=None,
@@ -133,6 +134,31 @@ class VecGridUniverse(object):
             self.engine.td_init(0.0)
             self._td_ready = True
         self.engine.td_set_q(q, env0)
+
+    def dyna_run(self, T, planning_steps=10, alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
+        """T real steps of batched tabular Dyna-Q: env e learns its own Q table [S][4] with Q-learning and its own model of the
+        env, and replays `planning_steps` model updates after every real step (include/gu.h: gu_dyna_run).  The first call gives
+        every env a table of zeros (if it had none) and an empty model.  Rows and statistics cover the real steps, as td_run()."""
+        if not self._td_ready:
+            self.engine.td_init(0.0)
+            self._td_ready = True
+        if not self._dyna_ready:
+            self.engine.dyna_init()
+            self._dyna_ready = True
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.dyna_run(T, planning_steps, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
+        out = self.engine.read_trajectory(0, T) if trajectory and T > 0 else {}
+        if stats:
+            out['ret'], out['episodes'] = self.engine.read_stats()
+        return out
+
+    def model(self, env0=0, n=None):
+        """The Dyna-Q models of envs env0 .. env0+n-1 (Engine.dyna_get_model); an empty model is allocated on first use."""
+        if not self._dyna_ready:
+            self.engine.dyna_init()
+            self._dyna_ready = True
+        return self.engine.dyna_get_model(env0, n)
 
     def done_indices(self):
         return self.engine.done_indices()

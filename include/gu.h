@@ -261,7 +261,7 @@ int gu_done_indices(gu_handle h, int32_t *idx, int32_t *count);
  *      (w >> 16) < eps_q16 (0 .. 65536; 65536 = always): action w & 3.  Else greedy on Q_e[s]: of the m actions whose value equals
  *      the row maximum exactly, in ascending order, the one at index (((w >> 2) & 0x3FFF) * m) >> 14.  SARSA uses the carried
  *      action a' instead -- inside a launch always, and at its start when it directly follows a SARSA gu_td_run on this engine
- *      (no gu_seed, gu_reset*, gu_step*, gu_rollout, gu_set_state, gu_set_grid(s), gu_generate_mazes, gu_td_init, gu_td_set_q or
+ *      (no gu_seed, gu_reset*, gu_step*, gu_rollout, gu_set_state, gu_set_grid(s), gu_generate_mazes, gu_td_init, gu_td_set_q, gu_dyna_run or
  *      sweep-step call in between);
  *   3. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
  *   4. float64, one rounding per operation: m = max Q_e[s'] (Q-learning) or Q_e[s'][a'] with a' drawn at s' by rule 2 from the word
@@ -278,6 +278,34 @@ int gu_td_init(gu_handle h, double q0);
 int gu_td_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 int gu_td_get_q(gu_handle h, int64_t env0, int64_t n, double *q);
 int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q);
+
+/* ---- batched tabular Dyna-Q: learner e owns env e, its table Q_e[S][4] (the gu_td_* tables) and a learned model ----
+ * (build-defined: the reference lists "Integrating learning and planning (Dyna, ...)" on its roadmap and ships no code; Sutton &
+ * Barto 8.2; tests/_dyna_oracle.py is the CPU restatement.)  The model of learner e: next_e[S][4] (int32, -1 = never observed),
+ * reward_e[S][4] (int32), done_e[S][4] (0/1); list_e[4S], the observed pairs s*4+a in the order they were FIRST observed; count_e,
+ * its entries.  The env is deterministic, so one stored outcome per (s, a) is the whole model.
+ * One iteration of gu_dyna_run for env e at 64-bit step count t:
+ *   1. real step: rules 1-4 of gu_td_run, method 0 (Q-learning), unchanged (lazy auto-reset, the stream-4 word at count t,
+ *      epsilon-greedy with its tie rule, the move, t += 1, the float64 update of Q_e[s][a]);
+ *   2. model: next/reward/done[s][a] = (s', r, d) as observed; if (s, a) had never been observed, list_e[count_e++] = s*4+a;
+ *   3. planning: for j = 0 .. P-1, c = t_old * P + j (64-bit; t_old = the count before rule 1's increment): w = the word of RNG
+ *      stream 5 with counter c & 0xFFFFFFFF and epoch c >> 32 (keyed like stream 4); k = (uint64(w) * count_e) >> 32;
+ *      p = list_e[k], s_p = p >> 2, a_p = p & 3, (s'_p, r_p, d_p) from the model; target = r_p if d_p, else
+ *      r_p + gamma * max Q_e[s'_p] (folded left to right with `>` over the row as it is now, earlier planning updates of this
+ *      iteration included); Q_e[s_p][a_p] += alpha * (target - Q_e[s_p][a_p]), float64, one rounding per operation;
+ *   4. the next iteration chooses its action from the table after planning.
+ * Trajectory rows and GU_F_STATS cover the real steps only.  The step counts advance by T.
+ * gu_dyna_init      : allocate the model of every env (N * S * 49 bytes; GU_ERR_NOMEM under gu_td_init's free-memory rule) and
+ *                     clear it (count 0, all pairs unobserved).  gu_td_init and gu_td_set_q leave the model alone; a grid of another
+ *                     size drops it with the Q tables.
+ * gu_dyna_run       : T iterations per env with P planning updates each, in ONE launch (async).  GU_ERR_STATE without Q tables
+ *                     (gu_td_init) or without a model; GU_ERR_INVALID for P < 0 or P > 256, T * (P + 1) > 1e8, and everything
+ *                     gu_td_run rejects.  T = 0 changes nothing.  Flags as gu_td_run.  Ends the SARSA carry.
+ * gu_dyna_get_model : the model of envs env0 .. env0+n-1 on the host: next, reward, done as [n][S][4] (unobserved pairs: -1, 0, 0),
+ *                     list as [n][4S] (-1 beyond count), count as [n]; any output pointer may be NULL. */
+int gu_dyna_init(gu_handle h);
+int gu_dyna_run(gu_handle h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32_t *reward, int32_t *done, int32_t *list, int32_t *count);
 
 /* ---- look_step_ahead table queries: env:136-155 for n (state, action) pairs (grid 0 of a multi-grid engine) ---- */
 int gu_look_step_ahead(gu_handle h, int64_t n, const int32_t *states, const int32_t *actions,

@@ -1,0 +1,130 @@
+"""Batched tabular Dyna-Q, the parts that need no GPU: the CPU restatement against Q-learning, the stream-5 words, planning
+learning faster than Q-learning, dyna_q's argument checks and the library's new symbols."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from griduniverse_amd import _lib
+from griduniverse_amd.algorithms.dyna import dyna_q
+from griduniverse_amd.envs.griduniverse_env import GridUniverseEnv
+from oracle import c_oracle as C
+from oracle import gu_rng as R
+
+from . import _dyna_oracle as D
+from . import _golden as G
+from . import _td_oracle as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize('W,H', [(4, 4), (8, 8)])
+def test_restatement_without_planning_is_q_learning(W, H):
+    grid = C.Grid.from_lists(W, H, lava=[W + 1])
+    d, o = D.DynaOracle(grid, 9, 40, q0=0.25), O.TdOracle(grid, 9, 40, q0=0.25)
+    assert np.array_equal(d.reset(), o.reset())
+    for T, eps in ((150, 0.3), (90, 1.0)):
+        got, want = d.dyna(T, 0, 0.2, 0.9, int(eps * 65536)), o.run(T, O.Q_LEARNING, 0.2, 0.9, int(eps * 65536))
+        for k in want:
+            assert np.array_equal(got[k], want[k]), k
+    assert d.q.tobytes() == o.q.tobytes()
+    assert np.array_equal(d.state.tcount, o.state.tcount)
+
+
+def test_model_records_every_observed_pair_once():
+    grid = C.Grid.from_lists(4, 4, lava=[6])
+    d = D.DynaOracle(grid, 4, 8)
+    d.reset()
+    d.dyna(200, 3, 0.1, 0.9, 65536)
+    for e in range(8):
+        n = d.count[e]
+        pairs = d.list[e, :n]
+        assert len(set(pairs.tolist())) == n and (d.list[e, n:] == -1).all()
+        assert sorted(pairs.tolist()) == np.flatnonzero(d.next[e].reshape(-1) >= 0).tolist()
+        s, a = pairs >> 2, pairs & 3
+        nxt, rew, done = C.look_step_ahead(grid, s.astype(np.int32), a.astype(np.int32), True)
+        assert np.array_equal(d.next[e][s, a], nxt) and np.array_equal(d.mreward[e][s, a], rew)
+        assert np.array_equal(d.mdone[e][s, a], done.astype(np.int32))
+
+
+def test_stream_5_words_across_the_epoch_boundary():
+    envs = np.array([0, 3, 4095, 2 ** 31 + 1], np.uint64)
+    for c0 in (0, 2 ** 28 - 1, 2 ** 32 - 2, 5 * 2 ** 32 - 1):
+        for i in range(4):
+            c = c0 + i
+            got = D.planning_words(6, envs, np.full(len(envs), c, np.uint64))
+            want = [R.word(6, int(e), 5, c & 0xFFFFFFFF, epoch=c >> 32) for e in envs]
+            assert got.tolist() == want, c
+    # its own stream: not stream 4's word at the same count
+    assert D.planning_words(6, [1], [7])[0] != R.word(6, 1, 4, 7)
+    assert D.planning_words(6, [1], [2 ** 32])[0] != D.planning_words(6, [1], [0])[0]
+
+
+def _shortest_from_start(grid):
+    S = grid.S
+    s = np.repeat(np.arange(S, dtype=np.int32), 4)
+    a = np.tile(np.arange(4, dtype=np.int32), S)
+    nxt = C.look_step_ahead(grid, s, a, True)[0].reshape(S, 4)
+    dist = {int(grid.starts[0]): 0}
+    frontier = [int(grid.starts[0])]
+    while frontier:
+        nf = []
+        for c in frontier:
+            if grid.goal[c] or grid.lava[c]:
+                continue
+            for b in range(4):
+                n = int(nxt[c, b])
+                if n not in dist:
+                    dist[n] = dist[c] + 1
+                    nf.append(n)
+        frontier = nf
+    return min(v for k, v in dist.items() if grid.goal[k])
+
+
+def _greedy_walk(grid, q):
+    s, n = int(grid.starts[0]), 0
+    while not (grid.goal[s] or grid.lava[s]) and n <= grid.S:
+        nxt, _, _ = C.look_step_ahead(grid, np.array([s], np.int32), np.array([int(np.argmax(q[s]))], np.int32), True)
+        s, n = int(nxt[0]), n + 1
+    return n if grid.goal[s] else -1
+
+
+def _steps_to_shortest(grid, P, best, chunk=100, limit=20000):
+    """Real steps until every learner's greedy walk from the start is a shortest path."""
+    d = D.DynaOracle(grid, 3, 4)
+    d.reset()
+    done = 0
+    while done < limit:
+        d.dyna(chunk, P, 0.5, 0.95, int(0.1 * 65536))
+        done += chunk
+        if all(_greedy_walk(grid, d.q[e]) == best for e in range(d.n)):
+            return done
+    return None
+
+
+def test_planning_finds_the_shortest_path_in_fewer_real_steps():
+    grid = C.Grid.from_env(GridUniverseEnv(custom_world_fp=G.level_path('maze_11x11.txt')))
+    best = _shortest_from_start(grid)
+    with_planning = _steps_to_shortest(grid, 20, best)
+    assert with_planning is not None
+    without = _steps_to_shortest(grid, 0, best, limit=with_planning)
+    assert without is None or without > with_planning, (with_planning, without)
+
+
+def test_dyna_q_checks_its_arguments():
+    env = GridUniverseEnv((4, 4))
+    for kw in (dict(planning_steps=-1), dict(planning_steps=257), dict(num_learners=0), dict(epsilon=1.5), dict(epsilon=-0.1)):
+        with pytest.raises(ValueError):
+            dyna_q(env, 10, **kw)
+    with pytest.raises(ValueError):
+        dyna_q(env, -1)
+
+
+def test_library_exports_the_dyna_entry_points():
+    syms = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], stdout=subprocess.PIPE, check=True).stdout.decode()
+    header = open(os.path.join(ROOT, 'include', 'gu.h')).read()
+    for name in ('gu_dyna_init', 'gu_dyna_run', 'gu_dyna_get_model'):
+        assert ' T ' + name + '\n' in syms, name
+        assert name in _lib.SIGNATURES
+        assert 'int ' + name + '(' in header
