@@ -6,7 +6,7 @@ and plans"; it ships no code for it, so the semantics are this build's: include/
 with its own float64 Q table and its own model, all advanced on the MI355X by one kernel (csrc/gu_dyna.hip).  Its result has the
 shape of `q_learning`'s and feeds `greedy_policy` the same way.
 """
-from ..vec_env import VecGridUniverse
+from .temporal_difference import _learn
 
 MAX_PLANNING_STEPS = 256
 _UPDATES = 1000000  # real steps x (planning steps + 1) per launch (the launch limit is 1e8; shorter launches keep the device responsive)
@@ -25,20 +25,5 @@ def dyna_q(env, num_steps, planning_steps=10, alpha=0.1, discount_factor=0.99, e
         raise ValueError('epsilon must lie in [0, 1]')
     if int(num_steps) < 0:
         raise ValueError('num_steps must not be negative')
-    vec = VecGridUniverse(L, template=env, seed=seed)
-    try:
-        vec.engine.td_init(q0)
-        vec._td_ready = True
-        vec.engine.dyna_init()
-        vec._dyna_ready = True
-        vec.reset()
-        chunk = max(1, _UPDATES // (P + 1))
-        left = int(num_steps)
-        while left > 0:
-            T = min(left, chunk)
-            vec.dyna_run(T, P, alpha, discount_factor, epsilon)
-            left -= T
-        q = vec.q_table()
-    finally:
-        vec.close()
-    return q[0] if L == 1 else q
+    return _learn(env, L, seed, q0, num_steps, max(1, _UPDATES // (P + 1)),
+                  lambda vec, T: vec.dyna_run(T, P, alpha, discount_factor, epsilon), model=True)

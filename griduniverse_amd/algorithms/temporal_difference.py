@@ -14,26 +14,34 @@ from ..vec_env import VecGridUniverse
 _CHUNK = 100000  # steps per launch (the launch limit is 1e8; shorter launches keep the device responsive)
 
 
-def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0):
+def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False):
+    """The learner batch of q_learning / sarsa / dyna_q: L learners on the grid of `env`, tables of q0 (and empty models when
+    `model`), `num_steps` real steps each in launches `launch(vec, T)` of at most `chunk` steps.  Returns Q [S][4] or [L][S][4]."""
     L = int(num_learners)
-    if L < 1:
-        raise ValueError('num_learners must be at least 1')
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
     vec = VecGridUniverse(L, template=env, seed=seed)
     try:
-        vec.engine.td_init(q0)
-        vec._td_ready = True
+        vec._ensure_q(q0)
+        if model:
+            vec._ensure_model()
         vec.reset()
         left = int(num_steps)
         while left > 0:
-            T = min(left, _CHUNK)
-            vec.td_run(T, method, alpha, discount_factor, epsilon)
+            T = min(left, chunk)
+            launch(vec, T)
             left -= T
         q = vec.q_table()
     finally:
         vec.close()
     return q[0] if L == 1 else q
+
+
+def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0):
+    if int(num_learners) < 1:
+        raise ValueError('num_learners must be at least 1')
+    if not 0.0 <= float(epsilon) <= 1.0:
+        raise ValueError('epsilon must lie in [0, 1]')
+    return _learn(env, num_learners, seed, q0, num_steps, _CHUNK,
+                  lambda vec, T: vec.td_run(T, method, alpha, discount_factor, epsilon))
 
 
 def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):

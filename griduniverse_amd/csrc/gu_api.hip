@@ -1108,7 +1108,45 @@ int gu_read_stats(gu_handle h, int64_t *reward_sum, int32_t *episodes)
     return GU_OK;
 }
 
-// ---------------------------------------------------------------------------------- tabular TD control (gu_td.hip)
+// ---------------------------------------------------------------------------------- tabular TD control and Dyna-Q
+// (gu_td.hip, gu_dyna.hip; their shared core is gu_tabular.hpp)
+
+// tables of `bytes` for the engine's envs: what is left has to hold the trajectory buffer and the scratch of other calls too, so
+// keep 1 GiB of headroom
+static int gu_tabular_fits(gu_engine *h, size_t bytes, const char *what)
+{
+    size_t free_b = 0, total_b = 0;
+    GU_HIP(hipMemGetInfo(&free_b, &total_b));
+    GU_REQUIRE(bytes + ((size_t)1 << 30) <= free_b, GU_ERR_NOMEM, "%s of %lld envs x %d states need %.2f GiB, %.2f GiB are free", what,
+               (long long)h->N, h->S, bytes / 1073741824.0, free_b / 1073741824.0);
+    return GU_OK;
+}
+
+// the checks of a learner launch of T real steps; P < 0: gu_td_run (one update per step), else gu_dyna_run (P + 1 per step)
+static int gu_tabular_check(gu_engine *h, const char *fn, int64_t T, int32_t P, uint32_t eps_q16, double alpha, double gamma, uint32_t flags)
+{
+    if (P < 0)
+        GU_REQUIRE(T >= 0 && T <= 100000000, GU_ERR_INVALID, "T %lld out of range (0 .. 1e8)", (long long)T);
+    else
+        GU_REQUIRE(T >= 0 && T <= 100000000 && T * (int64_t)(P + 1) <= 100000000, GU_ERR_INVALID,
+                   "T %lld x (P + 1) = %lld updates out of range (0 .. 1e8)", (long long)T, (long long)T * (P + 1));
+    GU_REQUIRE(eps_q16 <= 65536u, GU_ERR_INVALID, "eps_q16 %u above 65536", eps_q16);
+    GU_REQUIRE(std::isfinite(alpha) && std::isfinite(gamma), GU_ERR_INVALID, "alpha and gamma must be finite");
+    GU_REQUIRE((flags & ~(GU_F_TRAJECTORY | GU_F_STATS)) == 0, GU_ERR_INVALID, "%s accepts GU_F_TRAJECTORY and GU_F_STATS only (flags 0x%x)", fn, flags);
+    if (flags & GU_F_TRAJECTORY)
+        GU_REQUIRE(h->d_traj && T <= h->traj_T, GU_ERR_STATE, "trajectory buffer holds %lld rows, need %lld: call gu_reserve_trajectory",
+                   (long long)h->traj_T, (long long)T);
+    GU_REQUIRE(!h->trail_cap || (flags & GU_F_TRAJECTORY), GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): %s must write rows (GU_F_TRAJECTORY) to feed it", fn);
+    return GU_OK;
+}
+
+static int gu_env_range(gu_engine *h, int64_t env0, int64_t n)
+{
+    GU_REQUIRE(env0 >= 0 && n >= 0 && env0 + n <= h->N, GU_ERR_INVALID, "envs [%lld, %lld) outside 0 .. %lld", (long long)env0,
+               (long long)(env0 + n), (long long)h->N);
+    return GU_OK;
+}
+
 int gu_td_init(gu_handle h, double q0)
 {
     GU_ENTER(h);
@@ -1123,11 +1161,8 @@ int gu_td_init(gu_handle h, double q0)
         h->d_q = nullptr;
         h->d_td_next = nullptr;
         h->td_S = 0;
-        size_t free_b = 0, total_b = 0;
-        GU_HIP(hipMemGetInfo(&free_b, &total_b));
-        // (what is left has to hold the trajectory buffer and the scratch of other calls too: keep 1 GiB of headroom)
-        GU_REQUIRE(bytes + ((size_t)1 << 30) <= free_b, GU_ERR_NOMEM, "Q tables of %lld envs x %d states need %.2f GiB, %.2f GiB are free",
-                   (long long)h->N, h->S, bytes / 1073741824.0, free_b / 1073741824.0);
+        int rc = gu_tabular_fits(h, bytes, "Q tables");
+        if (rc != GU_OK) return rc;
         GU_HIP(hipMalloc(&h->d_q, bytes));
         GU_HIP(hipMalloc(&h->d_td_next, (size_t)h->N));
         h->td_S = h->S;
@@ -1144,22 +1179,10 @@ int gu_td_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma
     GU_ENTER(h);
     GU_NEED_GRID(h);
     GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(T >= 0 && T <= 100000000, GU_ERR_INVALID, "T %lld out of range (0 .. 1e8)", (long long)T);
     GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Q-learning, 1 = SARSA", method);
-    GU_REQUIRE(eps_q16 <= 65536u, GU_ERR_INVALID, "eps_q16 %u above 65536", eps_q16);
-    GU_REQUIRE(std::isfinite(alpha) && std::isfinite(gamma), GU_ERR_INVALID, "alpha and gamma must be finite");
-    GU_REQUIRE((flags & ~(GU_F_TRAJECTORY | GU_F_STATS)) == 0, GU_ERR_INVALID, "gu_td_run accepts GU_F_TRAJECTORY and GU_F_STATS only (flags 0x%x)", flags);
-    if (flags & GU_F_TRAJECTORY)
-        GU_REQUIRE(h->d_traj && T <= h->traj_T, GU_ERR_STATE, "trajectory buffer holds %lld rows, need %lld: call gu_reserve_trajectory",
-                   (long long)h->traj_T, (long long)T);
-    GU_REQUIRE(!h->trail_cap || (flags & GU_F_TRAJECTORY), GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): gu_td_run must write rows (GU_F_TRAJECTORY) to feed it");
-    if (T == 0) return GU_OK;
-    int rc = gu_launch_td(h, T, method, alpha, gamma, eps_q16, flags);
-    if (rc == GU_OK) {
-        h->stats_valid = (flags & GU_F_STATS) != 0;
-        if (flags & GU_F_TRAJECTORY) h->traj_kind = 1;
-    }
-    return rc;
+    int rc = gu_tabular_check(h, "gu_td_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    return gu_launch_td(h, T, method, alpha, gamma, eps_q16, flags);
 }
 
 static int gu_td_range(gu_engine *h, int64_t env0, int64_t n, const void *q)
@@ -1167,9 +1190,7 @@ static int gu_td_range(gu_engine *h, int64_t env0, int64_t n, const void *q)
     GU_NEED_GRID(h);
     GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
     GU_REQUIRE(q != nullptr, GU_ERR_INVALID, "q is NULL");
-    GU_REQUIRE(env0 >= 0 && n >= 0 && env0 + n <= h->N, GU_ERR_INVALID, "envs [%lld, %lld) outside 0 .. %lld", (long long)env0,
-               (long long)(env0 + n), (long long)h->N);
-    return GU_OK;
+    return gu_env_range(h, env0, n);
 }
 
 int gu_td_get_q(gu_handle h, int64_t env0, int64_t n, double *q)
@@ -1195,7 +1216,6 @@ int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q)
     return GU_OK;
 }
 
-// ---------------------------------------------------------------------------------- tabular Dyna-Q (gu_dyna.hip)
 static void gu_dyna_free(gu_engine *h)
 {
     if (h->d_dyna_model) (void)hipFree(h->d_dyna_model);
@@ -1220,11 +1240,8 @@ int gu_dyna_init(gu_handle h)
         GU_HIP(hipStreamSynchronize(h->stream));
         gu_dyna_free(h);
         const size_t bytes = pairs * (sizeof(uint64_t) + sizeof(int32_t)) + (size_t)h->N * (sizeof(int32_t) + (size_t)h->S);
-        size_t free_b = 0, total_b = 0;
-        GU_HIP(hipMemGetInfo(&free_b, &total_b));
-        // (the same 1 GiB of headroom as gu_td_init)
-        GU_REQUIRE(bytes + ((size_t)1 << 30) <= free_b, GU_ERR_NOMEM, "Dyna-Q models of %lld envs x %d states need %.2f GiB, %.2f GiB are free",
-                   (long long)h->N, h->S, bytes / 1073741824.0, free_b / 1073741824.0);
+        int rc = gu_tabular_fits(h, bytes, "Dyna-Q models");
+        if (rc != GU_OK) return rc;
         GU_HIP(hipMalloc(&h->d_dyna_model, pairs * sizeof(uint64_t)));
         GU_HIP(hipMalloc(&h->d_dyna_list, pairs * sizeof(int32_t)));
         GU_HIP(hipMalloc(&h->d_dyna_count, (size_t)h->N * sizeof(int32_t)));
@@ -1247,22 +1264,9 @@ int gu_dyna_run(gu_handle h, int64_t T, int32_t P, double alpha, double gamma, u
     GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
     GU_REQUIRE(h->d_dyna_model && h->dyna_S == h->S, GU_ERR_STATE, "no Dyna-Q model: call gu_dyna_init first");
     GU_REQUIRE(P >= 0 && P <= 256, GU_ERR_INVALID, "planning steps %d out of range (0 .. 256)", P);
-    GU_REQUIRE(T >= 0 && T <= 100000000 && T * (int64_t)(P + 1) <= 100000000, GU_ERR_INVALID,
-               "T %lld x (P + 1) = %lld updates out of range (0 .. 1e8)", (long long)T, (long long)T * (P + 1));
-    GU_REQUIRE(eps_q16 <= 65536u, GU_ERR_INVALID, "eps_q16 %u above 65536", eps_q16);
-    GU_REQUIRE(std::isfinite(alpha) && std::isfinite(gamma), GU_ERR_INVALID, "alpha and gamma must be finite");
-    GU_REQUIRE((flags & ~(GU_F_TRAJECTORY | GU_F_STATS)) == 0, GU_ERR_INVALID, "gu_dyna_run accepts GU_F_TRAJECTORY and GU_F_STATS only (flags 0x%x)", flags);
-    if (flags & GU_F_TRAJECTORY)
-        GU_REQUIRE(h->d_traj && T <= h->traj_T, GU_ERR_STATE, "trajectory buffer holds %lld rows, need %lld: call gu_reserve_trajectory",
-                   (long long)h->traj_T, (long long)T);
-    GU_REQUIRE(!h->trail_cap || (flags & GU_F_TRAJECTORY), GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): gu_dyna_run must write rows (GU_F_TRAJECTORY) to feed it");
-    if (T == 0) return GU_OK;
-    int rc = gu_launch_dyna(h, T, P, alpha, gamma, eps_q16, flags);
-    if (rc == GU_OK) {
-        h->stats_valid = (flags & GU_F_STATS) != 0;
-        if (flags & GU_F_TRAJECTORY) h->traj_kind = 1;
-    }
-    return rc;
+    int rc = gu_tabular_check(h, "gu_dyna_run", T, P, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    return gu_launch_dyna(h, T, P, alpha, gamma, eps_q16, flags);
 }
 
 int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32_t *reward, int32_t *done, int32_t *list, int32_t *count)
@@ -1270,8 +1274,8 @@ int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32
     GU_ENTER(h);
     GU_NEED_GRID(h);
     GU_REQUIRE(h->d_dyna_model && h->dyna_S == h->S, GU_ERR_STATE, "no Dyna-Q model: call gu_dyna_init first");
-    GU_REQUIRE(env0 >= 0 && n >= 0 && env0 + n <= h->N, GU_ERR_INVALID, "envs [%lld, %lld) outside 0 .. %lld", (long long)env0,
-               (long long)(env0 + n), (long long)h->N);
+    int rc = gu_env_range(h, env0, n);
+    if (rc != GU_OK) return rc;
     const size_t pairs = (size_t)h->S * 4, k = (size_t)n * pairs;
     GU_HIP(hipStreamSynchronize(h->stream));
     if (!n) return GU_OK;

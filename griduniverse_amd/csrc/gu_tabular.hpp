@@ -1,0 +1,273 @@
+// gu_tabular.hpp -- the core of the batched tabular learners for gfx950 (gu_td.hip: Q-learning and SARSA; gu_dyna.hip: Dyna-Q).
+// N independent learners, learner e owns env e and its own float64 table Q_e[S][4], advanced T real steps per launch.  The
+// semantics are build-defined (the reference has no tabular code) and stated in include/gu.h (gu_td_run, gu_dyna_run).
+//
+// One lane per env, like the rollout.  Per real step the lane (TabLane)
+//   - draws one word of RNG stream 4, keyed by its 64-bit step count t (epsilon test, explore action, tie break),
+//   - moves with the engine's rule (gu_move on the staged cell map, absorbing terminal),
+//   - reads the row Q[s'] (32 bytes: two 16-byte loads) -- the only dependent gather of the step -- and
+//   - writes back the one updated entry Q[s][a] (8 bytes).
+// The row of the current state stays in VGPRs from one step to the next; a wall bump (s' == s) forwards the updated entry
+// instead of reading the row back, and a terminal s' (target = r) reads nothing.
+// Table layout: learner-major, [N][S][4] -- a lane's row is one aligned 32-byte piece, so a step's gather is one memory
+// transaction per lane; the rows of one wave's lanes are S * 32 bytes apart (no coalescing across lanes is possible anyway:
+// the lanes sit in different states).  The host sees the same [n][S][4] (gu_td_get_q / gu_td_set_q copy it as it is).
+// All arithmetic is float64 with one rounding per operation (__dadd_rn / __dmul_rn; the library builds with
+// -ffp-contract=off as well), so the tables are bit-exact against the CPU restatements (tests/_td_oracle.py, _dyna_oracle.py).
+// The kernels stay separate (their register footprints differ); each holds only its update rule around the lane code here.
+#pragma once
+#include "gu_rollout.hpp"  // (gu_map.hpp, gu_blocks, gu_lds_block)
+
+// ---- the fields both kernels read (gu_tabular_args fills them) ----
+struct TabArgs {
+    const uint8_t *cell;
+    int32_t cell_bytes, W;
+    uint64_t lut;
+    int32_t *pos, *reward, *done;
+    uint32_t *episode;
+    const uint32_t *tcount;  // per-env step-count offsets (read only: the count advances with the host's lock-step counter)
+    const int32_t *starts;
+    uint32_t n_starts, seed_prefix, env_id0;
+    int64_t N;
+    int32_t T, S;
+    uint64_t steps_taken;
+    double *q;  // [N][S][4]
+    double alpha, gamma;
+    uint32_t eps_q16;                       // explore iff (word >> 16) < eps_q16; 65536 = always
+    int32_t *tr_obs, *tr_reward, *tr_done;  // GU_F_TRAJECTORY: [T][N] planes, as the rollout writes them (else nullptr)
+    int32_t *ret, *episodes_fin;            // GU_F_STATS (else nullptr)
+    uint64_t *done_bits;
+    GridSel gs;
+};
+
+// ---- one Q row ----
+struct QRow {
+    double v0, v1, v2, v3;
+};
+
+__device__ __forceinline__ QRow gu_q_load(const double *row)
+{
+    const double2 lo = reinterpret_cast<const double2 *>(row)[0], hi = reinterpret_cast<const double2 *>(row)[1];
+    return QRow{lo.x, lo.y, hi.x, hi.y};
+}
+
+// (selects, not an indexed array: the row must stay in registers)
+__device__ __forceinline__ double gu_q_get(const QRow &q, uint32_t a)
+{
+    return a == 0u ? q.v0 : a == 1u ? q.v1 : a == 2u ? q.v2 : q.v3;
+}
+
+__device__ __forceinline__ void gu_q_put(QRow &q, uint32_t a, double v)
+{
+    q.v0 = a == 0u ? v : q.v0;
+    q.v1 = a == 1u ? v : q.v1;
+    q.v2 = a == 2u ? v : q.v2;
+    q.v3 = a == 3u ? v : q.v3;
+}
+
+// the row maximum, folded left to right with `>` (a NaN entry other than the first never wins)
+__device__ __forceinline__ double gu_q_max(const QRow &q)
+{
+    double mx = q.v0;
+    mx = q.v1 > mx ? q.v1 : mx;
+    mx = q.v2 > mx ? q.v2 : mx;
+    return q.v3 > mx ? q.v3 : mx;
+}
+
+// epsilon-greedy on one row with one RNG word (include/gu.h, gu_td_run rule 2): explore iff (w >> 16) < eps_q16, then action
+// w & 3; else the k-th (ascending) of the m actions whose value equals the row maximum exactly, k = (((w >> 2) & 0x3FFF) * m) >> 14.
+// (m = 0 -- only a NaN in action 0 can make it -- falls back to w & 3.)
+__device__ __forceinline__ uint32_t gu_q_action(const QRow &q, uint32_t w, uint32_t eps_q16)
+{
+    const double mx = gu_q_max(q);
+    const uint32_t e0 = q.v0 == mx, e1 = q.v1 == mx, e2 = q.v2 == mx, e3 = q.v3 == mx;
+    const uint32_t m = e0 + e1 + e2 + e3;
+    const uint32_t k = (((w >> 2) & 0x3FFFu) * m) >> 14;
+    // position of the k-th set bit of e0 e1 e2 e3
+    uint32_t a = w & 3u;
+    a = (e0 && k == 0u) ? 0u : a;
+    a = (e1 && k == e0) ? 1u : a;
+    a = (e2 && k == e0 + e1) ? 2u : a;
+    a = (e3 && k == e0 + e1 + e2) ? 3u : a;
+    return (w >> 16) < eps_q16 ? (w & 3u) : a;
+}
+
+// ---- the lane: state, prologue, auto-reset, move, Q[s][a] update, record, epilogue ----
+// A kernel constructs it (staging the map), runs begin .. end on live lanes and ballot on all; its own rule sits between move and step.
+template <bool LDS>
+struct TabLane {
+    CellMap m;
+    LaneGrid lg;
+    int64_t e;
+    uint32_t env, start_prefix, prefix, ep;
+    uint64_t t;
+    double *qe;
+    int32_t s, r, d, ret, fin;
+    QRow q;
+
+    __device__ __forceinline__ TabLane(const TabArgs &a, uint8_t *smem)
+    {
+        m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs);
+        e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+        d = 0;
+    }
+
+    __device__ __forceinline__ void begin(const TabArgs &a)
+    {
+        lg = gu_lane_grid<LDS>(a.gs, a.starts, a.n_starts, (uint32_t)e, m);
+        env = a.env_id0 + (uint32_t)e;
+        start_prefix = gu_rng_prefix(a.seed_prefix, env);  // stream 1: keyed by the episode count, no epoch
+        t = a.steps_taken + (uint64_t)(int64_t)(int32_t)a.tcount[e];
+        // stream 4: the epoch t >> 32 hashed behind the seed, hoisted; recomputed in the step that crosses a multiple of 2^32
+        prefix = gu_rng_prefix(gu_rng_seed_prefix_epoch(a.seed_prefix, (uint32_t)(t >> 32)), env);
+        qe = a.q + e * a.S * 4;
+        s = a.pos[e];
+        r = a.reward[e];
+        d = a.done[e];
+        ep = a.episode[e];
+        q = QRow{0.0, 0.0, 0.0, 0.0};
+        if (!d) q = gu_q_load(qe + (int64_t)s * 4);
+        ret = 0;
+        fin = 0;
+    }
+
+    // lazy auto-reset, as gu_step_kernel does it under GU_F_AUTO_RESET
+    __device__ __forceinline__ void reset(const TabArgs &a)
+    {
+        if (d) {
+            s = lg.starts[gu_rng_start_index(start_prefix, ep, lg.n_starts)];
+            ++ep;
+            d = 0;
+            q = gu_q_load(qe + (int64_t)s * 4);
+        }
+    }
+
+    // the stream-4 word of step t
+    __device__ __forceinline__ uint32_t word() const { return gu_rng_word(prefix, GU_RNG_STREAM_TD, (uint32_t)t); }
+
+    // take action ua from s: sets r and d, advances t (re-keying stream 4 where t crosses a multiple of 2^32), returns s'
+    __device__ __forceinline__ int32_t move(const TabArgs &a, uint32_t ua)
+    {
+        const int32_t s2 = gu_move(s, m.f[s], ua, gu_delta<LDS>(ua, a.lut, a.W));
+        r = m.r[s2];
+        d = (m.f[s2] >> GU_CELL_TERM_BIT) & 1;
+        ++t;
+        if ((uint32_t)t == 0u) prefix = gu_rng_prefix(gu_rng_seed_prefix_epoch(a.seed_prefix, (uint32_t)(t >> 32)), env);
+        return s2;
+    }
+
+    // pre-update Q[s']: the row in registers on a wall bump; not needed behind a terminal s'
+    __device__ __forceinline__ QRow next_row(int32_t s2) const
+    {
+        QRow n = q;
+        if (!d && s2 != s) n = gu_q_load(qe + (int64_t)s2 * 4);
+        return n;
+    }
+
+    // Q[s][ua] += alpha (target - Q[s][ua]) at entry sa = s * 4 + ua, forwarded into n (the row of s') on a wall bump
+    __device__ __forceinline__ void update(const TabArgs &a, int64_t sa, uint32_t ua, int32_t s2, QRow &n, double target)
+    {
+        double qa = gu_q_get(q, ua);
+        qa = __dadd_rn(qa, __dmul_rn(a.alpha, __dsub_rn(target, qa)));
+        qe[sa] = qa;
+        if (s2 == s) gu_q_put(n, ua, qa);
+    }
+
+    // the lane stands in s' with row n: the trajectory row and the statistics of step i
+    __device__ __forceinline__ void step(const TabArgs &a, int32_t i, int32_t s2, const QRow &n)
+    {
+        q = n;
+        s = s2;
+        if (a.tr_obs) {
+            const int64_t row = (int64_t)i * a.N + e;
+            a.tr_obs[row] = s2;
+            a.tr_reward[row] = r;
+            a.tr_done[row] = d;
+        }
+        ret += r;
+        fin += d;
+    }
+
+    __device__ __forceinline__ void end(const TabArgs &a) const
+    {
+        a.pos[e] = s;
+        a.reward[e] = r;
+        a.done[e] = d;
+        a.episode[e] = ep;
+        if (a.ret) {
+            a.ret[e] = ret;
+            a.episodes_fin[e] = fin;
+        }
+    }
+
+    // every lane of the wave, live or not, joins the ballot of done flags
+    __device__ __forceinline__ void ballot(const TabArgs &a) const
+    {
+        const uint64_t bits = __ballot(d != 0);
+        if ((threadIdx.x & 63) == 0 && e < a.N) a.done_bits[e >> 6] = bits;
+    }
+};
+
+// ---- host side ----
+static inline void gu_tabular_args(gu_engine *h, TabArgs &a, int64_t T, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    const bool traj = flags & GU_F_TRAJECTORY, stats = flags & GU_F_STATS;
+    const int64_t rows = traj ? h->traj_T * h->N : 0;
+    a.cell = h->d_cell;
+    a.cell_bytes = h->cell_bytes;
+    a.W = h->W;
+    a.lut = h->delta_lut;
+    a.pos = h->pos();
+    a.reward = h->reward();
+    a.done = h->done();
+    a.episode = h->d_episode;
+    a.tcount = h->d_tcount;
+    a.starts = h->d_starts;
+    a.n_starts = (uint32_t)h->n_starts;
+    a.seed_prefix = h->seed_prefix;
+    a.env_id0 = (uint32_t)h->env_id0;
+    a.N = h->N;
+    a.T = (int32_t)T;
+    a.S = h->S;
+    a.steps_taken = h->steps_taken;
+    a.q = h->d_q;
+    a.alpha = alpha;
+    a.gamma = gamma;
+    a.eps_q16 = eps_q16;
+    a.tr_obs = traj ? h->d_traj : nullptr;
+    a.tr_reward = traj ? h->d_traj + rows : nullptr;
+    a.tr_done = traj ? h->d_traj + 2 * rows : nullptr;
+    a.ret = stats ? h->d_ret : nullptr;
+    a.episodes_fin = stats ? h->d_episodes_fin : nullptr;
+    a.done_bits = h->d_done_bits;
+    a.gs = gu_grid_sel(h);
+}
+
+// launch the LDS instantiation where every block uses one grid whose planes fit, else the L2 one
+template <class A>
+static int gu_tabular_launch(gu_engine *h, void (*lds)(A), void (*l2)(A), const A &a)
+{
+    const int lds_bs = gu_lds_block(h, GU_BLOCK, 2);
+    if (lds_bs)
+        hipLaunchKernelGGL(lds, dim3(gu_blocks(h->N, lds_bs)), dim3(lds_bs), 2 * (size_t)h->cell_bytes, h->stream, a);
+    else
+        hipLaunchKernelGGL(l2, dim3(gu_blocks(h->N, GU_BLOCK)), dim3(GU_BLOCK), 0, h->stream, a);
+    GU_HIP(hipGetLastError());
+    return GU_OK;
+}
+
+// after a launch of T steps: the engine's step count, carried SARSA action, rows and statistics, and the agent trail
+static inline int gu_tabular_after(gu_engine *h, int64_t T, uint32_t flags, bool sarsa)
+{
+    const bool traj = flags & GU_F_TRAJECTORY;
+    h->steps_taken += (uint64_t)T;
+    h->entry_table_ok = false;
+    h->td_carry = sarsa;
+    if (traj) h->traj_written = 1;
+    const int rc = gu_trail_after_rollout(h, T, traj ? 1 : 0, true);
+    if (rc == GU_OK) {
+        h->stats_valid = (flags & GU_F_STATS) != 0;
+        if (traj) h->traj_kind = 1;
+    }
+    return rc;
+}

@@ -17,6 +17,11 @@ _POLICIES = {'uniform': _lib.POLICY_UNIFORM, 'stream': _lib.POLICY_STREAM, 'gree
 _TD_METHODS = {'q_learning': _lib.TD_Q_LEARNING, 'sarsa': _lib.TD_SARSA, 0: _lib.TD_Q_LEARNING, 1: _lib.TD_SARSA}
 
 
+def _learner_flags(trajectory, stats):
+    """The flags of a tabular learner launch (gu_td_run, gu_dyna_run): rows and statistics only."""
+    return (_lib.F_TRAJECTORY if trajectory else 0) | (_lib.F_STATS if stats else 0)
+
+
 class Engine(object):
     def __init__(self, num_envs, spec, device=0, env_id0=0, seed=0):
         if not isinstance(spec, GridSpec):
@@ -315,8 +320,8 @@ class Engine(object):
     def td_run(self, T, method='q_learning', alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
         """T epsilon-greedy Q-learning / SARSA iterations per env in one launch (auto-reset always on).  eps_q16: explore
         probability in 1/65536 (65536 = always).  Rows and statistics as rollout(): read_trajectory / read_stats."""
-        flags = (_lib.F_TRAJECTORY if trajectory else 0) | (_lib.F_STATS if stats else 0)
-        check(self.lib.gu_td_run(self._h, int(T), _TD_METHODS[method], float(alpha), float(gamma), int(eps_q16), flags))
+        check(self.lib.gu_td_run(self._h, int(T), _TD_METHODS[method], float(alpha), float(gamma), int(eps_q16),
+                                 _learner_flags(trajectory, stats)))
 
     def td_get_q(self, env0=0, n=None):
         """float64[n, S, 4]: the tables of envs env0 .. env0+n-1 (all from env0 when n is None)."""
@@ -341,8 +346,8 @@ class Engine(object):
     def dyna_run(self, T, planning_steps=10, alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
         """T real Q-learning steps per env in one launch, each followed by `planning_steps` updates replayed from the env's
         learned model.  Rows and statistics (real steps only) as td_run()."""
-        flags = (_lib.F_TRAJECTORY if trajectory else 0) | (_lib.F_STATS if stats else 0)
-        check(self.lib.gu_dyna_run(self._h, int(T), int(planning_steps), float(alpha), float(gamma), int(eps_q16), flags))
+        check(self.lib.gu_dyna_run(self._h, int(T), int(planning_steps), float(alpha), float(gamma), int(eps_q16),
+                                   _learner_flags(trajectory, stats)))
 
     def dyna_get_model(self, env0=0, n=None):
         """The models of envs env0 .. env0+n-1: dict next / reward / done int32[n, S, 4] (unobserved: -1 / 0 / 0),

@@ -108,21 +108,35 @@ class VecGridUniverse(object):
             out['ret'], out['episodes'] = self.engine.read_stats()
         return out
 
+    def _ensure_q(self, q0=None):
+        """Q tables on the engine: tables of zeros on first use; every entry q0 (again) when q0 is given."""
+        if q0 is not None or not self._td_ready:
+            self.engine.td_init(0.0 if q0 is None else q0)
+            self._td_ready = True
+
+    def _ensure_model(self, clear=False):
+        """Dyna-Q models on the engine: an empty model per env on first use, or when `clear`."""
+        if clear or not self._dyna_ready:
+            self.engine.dyna_init()
+            self._dyna_ready = True
+
+    def _learner_out(self, T, trajectory, stats):
+        """The rows and statistics of the learner launch just made, as rollout() returns them."""
+        out = self.engine.read_trajectory(0, T) if trajectory and T > 0 else {}
+        if stats:
+            out['ret'], out['episodes'] = self.engine.read_stats()
+        return out
+
     def td_run(self, T, method='q_learning', alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
         """T iterations of batched tabular Q-learning ('q_learning') or SARSA ('sarsa'): env e learns its own Q table [S][4]
         from its own experience, epsilon-greedy, auto-reset always on (include/gu.h: gu_td_run).  The first call gives every
         env a table of zeros.  Returns a dict like rollout(): obs/reward/done int32[T, N] when `trajectory`, ret/episodes
         when `stats`."""
-        if not self._td_ready:
-            self.engine.td_init(0.0)
-            self._td_ready = True
+        self._ensure_q()
         if trajectory:
             self.engine.reserve_trajectory(T)
         self.engine.td_run(T, method, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
-        out = self.engine.read_trajectory(0, T) if trajectory and T > 0 else {}
-        if stats:
-            out['ret'], out['episodes'] = self.engine.read_stats()
-        return out
+        return self._learner_out(T, trajectory, stats)
 
     def q_table(self, env0=0, n=None):
         """float64[n, S, 4]: the Q tables of envs env0 .. env0+n-1 (to the end when n is None)."""
@@ -130,34 +144,23 @@ class VecGridUniverse(object):
 
     def set_q_table(self, q, env0=0):
         """Install Q tables float64[n, S, 4] (or [S, 4]) for envs env0 ..; the other envs get tables of zeros if they had none."""
-        if not self._td_ready:
-            self.engine.td_init(0.0)
-            self._td_ready = True
+        self._ensure_q()
         self.engine.td_set_q(q, env0)
 
     def dyna_run(self, T, planning_steps=10, alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
         """T real steps of batched tabular Dyna-Q: env e learns its own Q table [S][4] with Q-learning and its own model of the
         env, and replays `planning_steps` model updates after every real step (include/gu.h: gu_dyna_run).  The first call gives
         every env a table of zeros (if it had none) and an empty model.  Rows and statistics cover the real steps, as td_run()."""
-        if not self._td_ready:
-            self.engine.td_init(0.0)
-            self._td_ready = True
-        if not self._dyna_ready:
-            self.engine.dyna_init()
-            self._dyna_ready = True
+        self._ensure_q()
+        self._ensure_model()
         if trajectory:
             self.engine.reserve_trajectory(T)
         self.engine.dyna_run(T, planning_steps, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
-        out = self.engine.read_trajectory(0, T) if trajectory and T > 0 else {}
-        if stats:
-            out['ret'], out['episodes'] = self.engine.read_stats()
-        return out
+        return self._learner_out(T, trajectory, stats)
 
     def model(self, env0=0, n=None):
         """The Dyna-Q models of envs env0 .. env0+n-1 (Engine.dyna_get_model); an empty model is allocated on first use."""
-        if not self._dyna_ready:
-            self.engine.dyna_init()
-            self._dyna_ready = True
+        self._ensure_model()
         return self.engine.dyna_get_model(env0, n)
 
     def done_indices(self):

@@ -1,5 +1,7 @@
 """Batched tabular Dyna-Q on the device (gu_dyna_run, csrc/gu_dyna.hip) against the CPU restatement tests/_dyna_oracle.py: Q
 tables, every model plane, trajectory rows and statistics compared byte for byte."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -13,45 +15,11 @@ from oracle import c_oracle as C
 
 from . import _dyna_oracle as D
 from . import _golden as G
+from ._tabular_cases import GRIDS, _eps, _grid, _pair, _random_grids, _same, _spec
 
 pytestmark = pytest.mark.gpu
 
-
-def _level(name):
-    sp = G.load_json('levels.json')[name]
-    return dict(W=sp['W'], H=sp['H'], starts=sp['starts'], goals=sp['goals'], lava=sp['lava'], walls=sp['walls'])
-
-
-def _traj_grid(name):
-    meta, _ = G.load_traj(name)
-    return dict(W=meta['W'], H=meta['H'], starts=meta['starts'], goals=meta['goals'], lava=meta['lava'], walls=meta['walls'],
-                reward=meta['reward'])
-
-
-GRIDS = {  # the five grids of test_gpu_td.py
-    'default4x4': lambda: dict(W=4, H=4, starts=[0], goals=[15], lava=[], walls=[]),
-    'test_env': lambda: _level('test_env.txt'),
-    'open8x8': lambda: _traj_grid('c2_open8x8'),
-    'maze11': lambda: _level('maze_11x11.txt'),
-    'lava32': lambda: _traj_grid('c4_lava32'),
-}
-
-
-def _spec(g):
-    return GridSpec(g['W'], g['H'], g['starts'], g['goals'], g['lava'], g['walls'], g.get('reward'))
-
-
-def _grid(g):
-    return C.Grid.from_lists(g['W'], g['H'], walls=g['walls'], goals=g['goals'], lava=g['lava'], starts=g['starts'], reward=g.get('reward'))
-
-
-def _eps(epsilon):
-    return int(round(epsilon * 65536))
-
-
-def _same(got, want, keys=('obs', 'reward', 'done', 'ret', 'episodes')):
-    for k in keys:
-        assert np.asarray(got[k]).astype(np.int64).tobytes() == np.asarray(want[k]).astype(np.int64).tobytes(), k
+_pair = functools.partial(_pair, D.DynaOracle)
 
 
 def _same_model(vec, oracles):
@@ -59,15 +27,6 @@ def _same_model(vec, oracles):
     for k in ('next', 'reward', 'done', 'list', 'count'):
         want = np.concatenate([o.model()[k] for o in oracles])
         assert got[k].tobytes() == want.astype(np.int32).tobytes(), k
-
-
-def _pair(g, N, seed, q0=0.0):
-    vec = gua.VecGridUniverse(N, template=_spec(g), seed=seed)
-    vec.engine.td_init(q0)
-    vec._td_ready = True
-    o = D.DynaOracle(_grid(g), seed, N, q0=q0)
-    assert np.array_equal(vec.reset(), o.reset())
-    return vec, o
 
 
 @pytest.mark.parametrize('P', [0, 1, 5, 50])
@@ -116,14 +75,6 @@ def test_planning_that_rewrites_the_current_row(W, H):
         _same_model(vec, [o])
     finally:
         vec.close()
-
-
-def _random_grids(n, W, H, seed):
-    out = []
-    for k in range(n):
-        wall, start, goal = C.generate_maze(seed, k, W, H)
-        out.append(dict(W=W, H=H, starts=[start], goals=[goal], lava=[], walls=np.flatnonzero(wall).tolist()))
-    return out
 
 
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
@@ -257,8 +208,7 @@ def test_edges_and_errors():
     g = GRIDS['test_env']()
     vec, o = _pair(g, 64, 1, q0=1.25)
     try:
-        vec.engine.dyna_init()
-        vec._dyna_ready = True
+        vec._ensure_model(clear=True)
         eng = vec.engine
         S = _grid(g).S
         before = vec.get_state()

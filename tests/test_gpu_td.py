@@ -1,5 +1,7 @@
 """Batched tabular Q-learning / SARSA on the device (gu_td_run, csrc/gu_td.hip) against the CPU restatement tests/_td_oracle.py:
 Q tables, trajectory rows and statistics compared byte for byte."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -10,58 +12,15 @@ from griduniverse_amd.engine import Engine
 from griduniverse_amd.grid import GridSpec
 from oracle import c_oracle as C
 
-from . import _golden as G
 from . import _td_oracle as O
+from . import _golden as G
+from ._tabular_cases import GRIDS, _eps, _grid, _pair, _random_grids, _same, _spec
 
 pytestmark = pytest.mark.gpu
 
+_pair = functools.partial(_pair, O.TdOracle)
+
 METHODS = {'q_learning': O.Q_LEARNING, 'sarsa': O.SARSA}
-
-
-def _level(name):
-    sp = G.load_json('levels.json')[name]
-    return dict(W=sp['W'], H=sp['H'], starts=sp['starts'], goals=sp['goals'], lava=sp['lava'], walls=sp['walls'])
-
-
-def _traj_grid(name):
-    meta, _ = G.load_traj(name)
-    return dict(W=meta['W'], H=meta['H'], starts=meta['starts'], goals=meta['goals'], lava=meta['lava'], walls=meta['walls'],
-                reward=meta['reward'])
-
-
-GRIDS = {
-    'default4x4': lambda: dict(W=4, H=4, starts=[0], goals=[15], lava=[], walls=[]),
-    'test_env': lambda: _level('test_env.txt'),
-    'open8x8': lambda: _traj_grid('c2_open8x8'),
-    'maze11': lambda: _level('maze_11x11.txt'),
-    'lava32': lambda: _traj_grid('c4_lava32'),
-}
-
-
-def _spec(g):
-    return GridSpec(g['W'], g['H'], g['starts'], g['goals'], g['lava'], g['walls'], g.get('reward'))
-
-
-def _grid(g):
-    return C.Grid.from_lists(g['W'], g['H'], walls=g['walls'], goals=g['goals'], lava=g['lava'], starts=g['starts'], reward=g.get('reward'))
-
-
-def _eps(epsilon):
-    return int(round(epsilon * 65536))
-
-
-def _same(got, want, keys=('obs', 'reward', 'done', 'ret', 'episodes')):
-    for k in keys:
-        assert np.asarray(got[k]).astype(np.int64).tobytes() == np.asarray(want[k]).astype(np.int64).tobytes(), k
-
-
-def _pair(g, N, seed, q0=0.0):
-    vec = gua.VecGridUniverse(N, template=_spec(g), seed=seed)
-    vec.engine.td_init(q0)
-    vec._td_ready = True
-    o = O.TdOracle(_grid(g), seed, N, q0=q0)
-    assert np.array_equal(vec.reset(), o.reset())
-    return vec, o
 
 
 @pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
@@ -114,14 +73,6 @@ def test_sarsa_interrupted_by_reset_starts_with_a_fresh_action():
         assert vec.q_table().tobytes() == o.q.tobytes()
     finally:
         vec.close()
-
-
-def _random_grids(n, W, H, seed):
-    out = []
-    for k in range(n):
-        wall, start, goal = C.generate_maze(seed, k, W, H)
-        out.append(dict(W=W, H=H, starts=[start], goals=[goal], lava=[], walls=np.flatnonzero(wall).tolist()))
-    return out
 
 
 @pytest.mark.parametrize('method', ['q_learning', 'sarsa'])

@@ -43,10 +43,8 @@ def measure(launches, steps, warmup):
                 vec.reset()
                 for P in PLANNING:
                     T = steps if P is None or P < 50 else max(1, steps // 10)
-                    vec.engine.td_init(0.0)
-                    vec._td_ready = True
-                    vec.engine.dyna_init()
-                    vec._dyna_ready = True
+                    vec._ensure_q(0.0)
+                    vec._ensure_model(clear=True)
 
                     def launch():
                         if P is None:

@@ -39,8 +39,7 @@ def measure(launches, steps, warmup):
             try:
                 vec.reset()
                 for method in ('q_learning', 'sarsa'):
-                    vec.engine.td_init(0.0)
-                    vec._td_ready = True
+                    vec._ensure_q(0.0)
                     for _ in range(warmup):
                         vec.td_run(steps, method, alpha=0.1, discount_factor=0.99, epsilon=0.1)
                     vec.engine.timer_begin()
