@@ -6,16 +6,20 @@ include/gu.h, gu_td_run).
 in env e of a batch, each with its own float64 Q table, all advanced on the MI355X by one kernel (csrc/gu_td.hip).  The facade's
 own state is left alone.  `greedy_policy` turns a learned table into the reference's policy-matrix format, so it feeds
 `get_policy_map`, `engine.vi_set` and `rollout(policy='greedy')` like a policy from dynamic programming.
+
+`n_step_sarsa` / `n_step_q_learning` are the n-step variations (Sutton & Barto ch. 7; include/gu.h, gu_nstep_run), on the same
+tables, by csrc/gu_nstep.hip.
 """
 import numpy as np
 
+from .. import _lib
 from ..vec_env import VecGridUniverse
 
 _CHUNK = 100000  # steps per launch (the launch limit is 1e8; shorter launches keep the device responsive)
 
 
 def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False):
-    """The learner batch of q_learning / sarsa / dyna_q: L learners on the grid of `env`, tables of q0 (and empty models when
+    """The learner batch of q_learning / sarsa / n_step_* / dyna_q: L learners on the grid of `env`, tables of q0 (and empty models when
     `model`), `num_steps` real steps each in launches `launch(vec, T)` of at most `chunk` steps.  Returns Q [S][4] or [L][S][4]."""
     L = int(num_learners)
     vec = VecGridUniverse(L, template=env, seed=seed)
@@ -53,6 +57,30 @@ def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num
 def sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):
     """Epsilon-greedy SARSA; arguments and result as `q_learning`."""
     return _td('sarsa', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0)
+
+
+def _nstep(method, env, num_steps, n, alpha, discount_factor, epsilon, num_learners, seed, q0):
+    if not 1 <= int(n) <= _lib.NSTEP_MAX:
+        raise ValueError('n must lie in 1 .. {}'.format(_lib.NSTEP_MAX))
+    if int(num_learners) < 1:
+        raise ValueError('num_learners must be at least 1')
+    if not 0.0 <= float(epsilon) <= 1.0:
+        raise ValueError('epsilon must lie in [0, 1]')
+    # consecutive launches of one method and n carry the window, so chunking changes nothing
+    return _learn(env, num_learners, seed, q0, num_steps, _CHUNK,
+                  lambda vec, T: vec.nstep_run(T, n, method, alpha, discount_factor, epsilon))
+
+
+def n_step_sarsa(env, num_steps, n=4, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):
+    """Epsilon-greedy n-step SARSA (Sutton & Barto 7.2), 1 <= n <= 16, `num_steps` env steps per learner.  Returns Q
+    float64[S][4], or [L][S][4] for L = num_learners > 1.  With n = 1 it is `sarsa`."""
+    return _nstep('sarsa', env, num_steps, n, alpha, discount_factor, epsilon, num_learners, seed, q0)
+
+
+def n_step_q_learning(env, num_steps, n=4, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):
+    """Epsilon-greedy n-step Q-learning, uncorrected (it bootstraps on max Q[S_{t+n}], as asynchronous n-step Q-learning does);
+    arguments and result as `n_step_sarsa`.  With n = 1 it is `q_learning`."""
+    return _nstep('q_learning', env, num_steps, n, alpha, discount_factor, epsilon, num_learners, seed, q0)
 
 
 def greedy_policy(q, env):

@@ -15,6 +15,7 @@
 #include <vector>
 
 static void gu_dyna_free(gu_engine *h);  // (tabular Dyna-Q, below)
+static void gu_nstep_free(gu_engine *h);  // (tabular n-step learners, below)
 
 // ---------------------------------------------------------------------------------- errors
 static thread_local std::string g_last_error;
@@ -172,7 +173,7 @@ int gu_destroy(gu_handle h)
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
                     h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next,
-                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen};
+                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -240,13 +241,14 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
     const int32_t cell_bytes = (S + 15) & ~15;
     GU_HIP(hipStreamSynchronize(h->stream));
     h->entry_table_ok = false;  // (other cells, other flags)
-    h->td_carry = false;
+    gu_tabular_drop_carry(h);
     if (h->td_S && h->td_S != W * H) {  // Q tables of another state count belong to another grid: gu_td_init again
         if (h->d_q) GU_HIP(hipFree(h->d_q));
         if (h->d_td_next) GU_HIP(hipFree(h->d_td_next));
         h->d_q = nullptr;
         h->d_td_next = nullptr;
         h->td_S = 0;
+        gu_nstep_free(h);
     }
     if (h->dyna_S && h->dyna_S != W * H) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
     h->dyna_exact = false;  // a kept model may hold outcomes of the old cells: gu_dyna_run compares every observation from now on
@@ -394,7 +396,7 @@ int gu_seed(gu_handle h, uint64_t seed)
     h->seed = seed;
     h->seed_prefix = gu_rng_seed_prefix(seed);
     h->steps_taken = 0;
-    h->td_carry = false;
+    gu_tabular_drop_carry(h);
     h->off_lo = h->off_hi = 0;
     h->off_exact = true;
     if (h->graph_exec) {  // captured step launches carry the old seed in their arguments
@@ -660,7 +662,7 @@ int gu_step_graph(gu_handle h, int64_t t0, int64_t T, uint32_t flags)
     }
     GU_HIP(hipGraphLaunch(h->graph_exec, h->stream));
     h->steps_taken += (uint64_t)T;
-    h->td_carry = false;
+    gu_tabular_drop_carry(h);
     return GU_OK;
 }
 
@@ -1108,8 +1110,8 @@ int gu_read_stats(gu_handle h, int64_t *reward_sum, int32_t *episodes)
     return GU_OK;
 }
 
-// ---------------------------------------------------------------------------------- tabular TD control and Dyna-Q
-// (gu_td.hip, gu_dyna.hip; their shared core is gu_tabular.hpp)
+// ---------------------------------------------------------------------------------- tabular TD control, Dyna-Q and n-step learners
+// (gu_td.hip, gu_dyna.hip, gu_nstep.hip; their shared core is gu_tabular.hpp)
 
 // tables of `bytes` for the engine's envs: what is left has to hold the trajectory buffer and the scratch of other calls too, so
 // keep 1 GiB of headroom
@@ -1152,7 +1154,7 @@ int gu_td_init(gu_handle h, double q0)
     GU_ENTER(h);
     GU_NEED_GRID(h);
     GU_REQUIRE(std::isfinite(q0), GU_ERR_INVALID, "q0 must be finite");
-    h->td_carry = false;
+    gu_tabular_drop_carry(h);
     const size_t bytes = (size_t)h->N * (size_t)h->S * 4 * sizeof(double);
     if (!h->d_q || h->td_S != h->S) {
         GU_HIP(hipStreamSynchronize(h->stream));
@@ -1209,7 +1211,7 @@ int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q)
     GU_ENTER(h);
     int rc = gu_td_range(h, env0, n, q);
     if (rc != GU_OK) return rc;
-    h->td_carry = false;
+    gu_tabular_drop_carry(h);
     const size_t row = (size_t)h->S * 4;
     GU_HIP(hipStreamSynchronize(h->stream));
     if (n) GU_HIP(hipMemcpy(h->d_q + (size_t)env0 * row, q, (size_t)n * row * sizeof(double), hipMemcpyHostToDevice));
@@ -1234,7 +1236,7 @@ int gu_dyna_init(gu_handle h)
 {
     GU_ENTER(h);
     GU_NEED_GRID(h);
-    h->td_carry = false;
+    gu_tabular_drop_carry(h);
     const size_t pairs = (size_t)h->N * (size_t)h->S * 4;
     if (!h->d_dyna_model || h->dyna_S != h->S) {
         GU_HIP(hipStreamSynchronize(h->stream));
@@ -1296,6 +1298,64 @@ int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32
     return GU_OK;
 }
 
+static void gu_nstep_free(gu_engine *h)
+{
+    if (h->d_nstep_sa) (void)hipFree(h->d_nstep_sa);
+    if (h->d_nstep_r) (void)hipFree(h->d_nstep_r);
+    if (h->d_nstep_cnt) (void)hipFree(h->d_nstep_cnt);
+    h->d_nstep_sa = nullptr;
+    h->d_nstep_r = nullptr;
+    h->d_nstep_cnt = nullptr;
+    h->nstep_key = 0;
+}
+
+int gu_nstep_run(gu_handle h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = n-step Q-learning, 1 = n-step SARSA", method);
+    GU_REQUIRE(n >= 1 && n <= GU_NSTEP_MAX, GU_ERR_INVALID, "n %d out of range (1 .. %d)", n, GU_NSTEP_MAX);
+    int rc = gu_tabular_check(h, "gu_nstep_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    if (!h->d_nstep_sa) {
+        const size_t slots = (size_t)h->N * GU_NSTEP_MAX;
+        GU_HIP(hipStreamSynchronize(h->stream));
+        rc = gu_tabular_fits(h, 2 * slots * sizeof(int32_t) + (size_t)h->N * sizeof(int32_t), "n-step windows");
+        if (rc != GU_OK) return rc;
+        GU_HIP(hipMalloc(&h->d_nstep_sa, slots * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_nstep_r, slots * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_nstep_cnt, (size_t)h->N * sizeof(int32_t)));
+        h->nstep_key = 0;
+    }
+    return gu_launch_nstep(h, T, method, n, alpha, gamma, eps_q16, flags);
+}
+
+int gu_nstep_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    int rc = gu_env_range(h, env0, n);
+    if (rc != GU_OK) return rc;
+    const size_t k = (size_t)n * GU_NSTEP_MAX;
+    std::vector<int32_t> c(n), w_sa(k), w_r(k);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n && h->nstep_key) {  // (a dropped window reads as empty, whatever the device copy still holds)
+        GU_HIP(hipMemcpy(c.data(), h->d_nstep_cnt + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        GU_HIP(hipMemcpy(w_sa.data(), h->d_nstep_sa + (size_t)env0 * GU_NSTEP_MAX, k * sizeof(int32_t), hipMemcpyDeviceToHost));
+        GU_HIP(hipMemcpy(w_r.data(), h->d_nstep_r + (size_t)env0 * GU_NSTEP_MAX, k * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    for (int64_t e = 0; e < n; ++e)
+        for (int32_t j = 0; j < GU_NSTEP_MAX; ++j) {
+            const size_t i = (size_t)e * GU_NSTEP_MAX + j;
+            if (sa) sa[i] = j < c[e] ? w_sa[i] : -1;
+            if (reward) reward[i] = j < c[e] ? w_r[i] : 0;
+        }
+    if (count)
+        for (int64_t e = 0; e < n; ++e) count[e] = c[e];
+    return GU_OK;
+}
+
 // ---------------------------------------------------------------------------------- state
 int gu_get_state(gu_handle h, int32_t *pos, int32_t *done, uint32_t *episode, uint64_t *tcount)
 {
@@ -1317,7 +1377,7 @@ int gu_set_state(gu_handle h, const int32_t *pos, const int32_t *done, const uin
 {
     GU_ENTER(h);
     h->entry_table_ok = false;
-    h->td_carry = false;
+    gu_tabular_drop_carry(h);
     GU_NEED_GRID(h);
     const size_t n = (size_t)h->N;
     if (pos)

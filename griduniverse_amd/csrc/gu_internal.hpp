@@ -262,6 +262,11 @@ struct gu_engine {
     int8_t *d_td_next = nullptr;  // [N] SARSA: the action a' carried from one launch to the next (-1: none)
     int32_t td_S = 0;             // states of the tables (0: none allocated); a grid of another size drops them
     bool td_carry = false;        // the last call that touched the envs was a SARSA gu_td_run: the next one starts from d_td_next
+    // batched tabular n-step Q-learning / SARSA (gu_nstep.hip): learns into d_q; the window is allocated on first use
+    int32_t *d_nstep_sa = nullptr;   // [N][GU_NSTEP_MAX] pending pairs s*4+a, oldest first
+    int32_t *d_nstep_r = nullptr;    // [N][GU_NSTEP_MAX] their rewards
+    int32_t *d_nstep_cnt = nullptr;  // [N] entries of the window
+    int32_t nstep_key = 0;           // gu_nstep_key of the last call that touched the envs if it was a gu_nstep_run, else 0 (window dropped)
     // batched tabular Dyna-Q (gu_dyna.hip): off until gu_dyna_init; learns into d_q
     uint64_t *d_dyna_model = nullptr;  // [N][dyna_S*4] one packed word per (s, a): reward | (s' | done << 31) << 32; ~0 = unobserved
     int32_t *d_dyna_list = nullptr;    // [N][dyna_S*4] observed pairs s*4+a in the order of first observation (-1 beyond count)
@@ -407,6 +412,19 @@ int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, double g
 
 // ---- batched tabular Dyna-Q (gu_dyna.hip) -------------------------------------------
 int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+
+// ---- batched tabular n-step Q-learning / SARSA (gu_nstep.hip) --------------------------
+// the carry key of a gu_nstep_run (never 0): the next launch keeps the window only under the same method and n
+static inline int32_t gu_nstep_key(int32_t method, int32_t n) { return 1 + method + 2 * n; }
+int gu_launch_nstep(gu_engine *h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+
+// every call that touches the envs other than the learner launches ends what the learners carry from one launch to the next:
+// gu_td_run's SARSA action and gu_nstep_run's window (its pending updates are discarded, not flushed)
+static inline void gu_tabular_drop_carry(gu_engine *h)
+{
+    h->td_carry = false;
+    h->nstep_key = 0;
+}
 
 // ---- agent trail (gu_trail.hip): no-ops while the trail is off ----------------------
 int gu_trail_after_step(gu_engine *h, uint32_t flags);

@@ -314,7 +314,7 @@ __global__ void __launch_bounds__(1024) gu_done_compact_kernel(const uint64_t *_
 int gu_launch_reset(gu_engine *h, const uint8_t *d_mask, const int32_t *d_choice, bool only_done)
 {
     h->entry_table_ok = false;  // (a reset may land on a terminal start cell: done = 0 on a terminal cell)
-    h->td_carry = false;
+    gu_tabular_drop_carry(h);
     int trail_rc = gu_trail_before_reset(h, d_mask, only_done);  // (reads the done flags the reset is about to clear)
     if (trail_rc != GU_OK) return trail_rc;
     ResetArgs a{h->pos(), h->done(), h->d_episode, h->d_starts, d_mask, d_choice, h->d_done_bits,
@@ -338,7 +338,7 @@ int gu_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, i
         hipLaunchKernelGGL(gu_step_kernel<false>, dim3(gu_blocks(h->N, GU_BLOCK)), dim3(GU_BLOCK), 0, h->stream, a);
     GU_HIP(hipGetLastError());
     h->steps_taken += 1;
-    h->td_carry = false;
+    gu_tabular_drop_carry(h);
     return gu_trail_after_step(h, flags);
 }
 
@@ -636,7 +636,7 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
     if (!a.straddle && gu_rollout_multi(h, a, policy, auto_mode, traj, stats)) {
         GU_HIP(hipGetLastError());
         h->steps_taken += (uint64_t)T;
-        h->td_carry = false;
+        gu_tabular_drop_carry(h);
         h->entry_table_ok = true;
         return gu_trail_after_rollout(h, T, traj, auto_mode != 0);
     }
@@ -646,7 +646,7 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
             if (rows_rc != GU_OK) return rows_rc;
             GU_HIP(hipGetLastError());
             h->steps_taken += (uint64_t)T;
-            h->td_carry = false;
+            gu_tabular_drop_carry(h);
             h->entry_table_ok = true;
             if (h->device >= 0 && h->device < 64) g_last_rollout_ms[h->device] = gu_wall_ms();
             return gu_trail_after_rollout(h, T, traj, auto_mode != 0);
@@ -663,7 +663,7 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
     if (h->device >= 0 && h->device < 64) g_last_rollout_ms[h->device] = gu_wall_ms();
     GU_HIP(hipGetLastError());
     h->steps_taken += (uint64_t)T;
-    h->td_carry = false;
+    gu_tabular_drop_carry(h);
     h->entry_table_ok = true;
     return gu_trail_after_rollout(h, T, traj, auto_mode != 0);
 }

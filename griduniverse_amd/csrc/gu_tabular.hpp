@@ -1,6 +1,7 @@
-// gu_tabular.hpp -- the core of the batched tabular learners for gfx950 (gu_td.hip: Q-learning and SARSA; gu_dyna.hip: Dyna-Q).
+// gu_tabular.hpp -- the core of the batched tabular learners for gfx950 (gu_td.hip: Q-learning and SARSA; gu_dyna.hip: Dyna-Q;
+// gu_nstep.hip: n-step Q-learning and SARSA).
 // N independent learners, learner e owns env e and its own float64 table Q_e[S][4], advanced T real steps per launch.  The
-// semantics are build-defined (the reference has no tabular code) and stated in include/gu.h (gu_td_run, gu_dyna_run).
+// semantics are build-defined (the reference has no tabular code) and stated in include/gu.h (gu_td_run, gu_dyna_run, gu_nstep_run).
 //
 // One lane per env, like the rollout.  Per real step the lane (TabLane)
 //   - draws one word of RNG stream 4, keyed by its 64-bit step count t (epsilon test, explore action, tie break),
@@ -256,12 +257,14 @@ static int gu_tabular_launch(gu_engine *h, void (*lds)(A), void (*l2)(A), const 
     return GU_OK;
 }
 
-// after a launch of T steps: the engine's step count, carried SARSA action, rows and statistics, and the agent trail
+// after a launch of T steps: the engine's step count, carried SARSA action (the caller sets gu_nstep_run's window carry), rows and
+// statistics, and the agent trail
 static inline int gu_tabular_after(gu_engine *h, int64_t T, uint32_t flags, bool sarsa)
 {
     const bool traj = flags & GU_F_TRAJECTORY;
     h->steps_taken += (uint64_t)T;
     h->entry_table_ok = false;
+    gu_tabular_drop_carry(h);
     h->td_carry = sarsa;
     if (traj) h->traj_written = 1;
     const int rc = gu_trail_after_rollout(h, T, traj ? 1 : 0, true);

@@ -1133,7 +1133,7 @@ int gu_vi_sweep_step(gu_handle h, double gamma, uint32_t flags, double *delta)
     h->vi_cur ^= 1;
     h->greedy_valid = false;
     h->steps_taken += 1;
-    h->td_carry = false;
+    gu_tabular_drop_carry(h);
     if (delta) {
         unsigned long long key = 0;
         if ((rc = gu_read_back(h, &key, h->d_delta, sizeof key)) != GU_OK) return rc;
@@ -1247,7 +1247,7 @@ int gu_vi_sweep_step_run(gu_handle h, double gamma, int32_t iters, uint32_t flag
                 }
                 h->greedy_valid = false;
                 h->steps_taken += (uint64_t)iters;
-                h->td_carry = false;
+                gu_tabular_drop_carry(h);
                 h->vi_run_form = form == 0 ? 1 : 2;
                 return GU_OK;
             }

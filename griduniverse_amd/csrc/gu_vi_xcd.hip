@@ -1046,7 +1046,7 @@ int gu_vi_xcd_fused_run(gu_engine *h, const GuXcdPlan &xp, double gamma, int32_t
         }
         h->greedy_valid = false;
         h->steps_taken += (uint64_t)n;
-        h->td_carry = false;
+        gu_tabular_drop_carry(h);
         total += n;
     }
     return GU_OK;

@@ -18,7 +18,7 @@ _TD_METHODS = {'q_learning': _lib.TD_Q_LEARNING, 'sarsa': _lib.TD_SARSA, 0: _lib
 
 
 def _learner_flags(trajectory, stats):
-    """The flags of a tabular learner launch (gu_td_run, gu_dyna_run): rows and statistics only."""
+    """The flags of a tabular learner launch (gu_td_run, gu_dyna_run, gu_nstep_run): rows and statistics only."""
     return (_lib.F_TRAJECTORY if trajectory else 0) | (_lib.F_STATS if stats else 0)
 
 
@@ -358,6 +358,24 @@ class Engine(object):
                    list=np.empty((n0, 4 * S), np.int32), count=np.empty(n0, np.int32))
         check(self.lib.gu_dyna_get_model(self._h, int(env0), n, ptr(out['next']), ptr(out['reward']), ptr(out['done']),
                                          ptr(out['list']), ptr(out['count'])))
+        return out
+
+    # ------------------------------------------------------------------ tabular n-step Q-learning / SARSA (include/gu.h: gu_nstep_*)
+    def nstep_run(self, T, method='sarsa', n=4, alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
+        """T iterations of n-step Q-learning / SARSA per env in one launch, into the td_init tables.  The window of pending
+        transitions carries into the next nstep_run of the same method and n; any other call in between drops it.  Rows and
+        statistics as td_run()."""
+        check(self.lib.gu_nstep_run(self._h, int(T), _TD_METHODS[method], int(n), float(alpha), float(gamma), int(eps_q16),
+                                    _learner_flags(trajectory, stats)))
+
+    def nstep_get_window(self, env0=0, n=None):
+        """The windows of envs env0 .. env0+n-1: dict sa / reward int32[n, NSTEP_MAX] (pending s*4+a and r, oldest first;
+        -1 / 0 beyond count) and count int32[n] (0 once dropped)."""
+        n = self.N - int(env0) if n is None else int(n)
+        n0 = max(n, 0)
+        out = dict(sa=np.empty((n0, _lib.NSTEP_MAX), np.int32), reward=np.empty((n0, _lib.NSTEP_MAX), np.int32),
+                   count=np.empty(n0, np.int32))
+        check(self.lib.gu_nstep_get_window(self._h, int(env0), n, ptr(out['sa']), ptr(out['reward']), ptr(out['count'])))
         return out
 
     # ------------------------------------------------------------------ state

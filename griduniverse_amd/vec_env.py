@@ -163,6 +163,21 @@ class VecGridUniverse(object):
         self._ensure_model()
         return self.engine.dyna_get_model(env0, n)
 
+    def nstep_run(self, T, n=4, method='sarsa', alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
+        """T iterations of batched tabular n-step SARSA ('sarsa') or n-step Q-learning ('q_learning'), 1 <= n <= 16: env e learns
+        its own Q table [S][4] from n-step returns (include/gu.h: gu_nstep_run).  The first call gives every env a table of zeros.
+        Consecutive calls with the same method and n carry the window of pending transitions; any other call in between drops
+        it.  Rows and statistics as td_run()."""
+        self._ensure_q()
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.nstep_run(T, method, n, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def nstep_window(self, env0=0, n=None):
+        """The n-step windows of envs env0 .. env0+n-1 (Engine.nstep_get_window)."""
+        return self.engine.nstep_get_window(env0, n)
+
     def done_indices(self):
         return self.engine.done_indices()
 

@@ -261,8 +261,8 @@ int gu_done_indices(gu_handle h, int32_t *idx, int32_t *count);
  *      (w >> 16) < eps_q16 (0 .. 65536; 65536 = always): action w & 3.  Else greedy on Q_e[s]: of the m actions whose value equals
  *      the row maximum exactly, in ascending order, the one at index (((w >> 2) & 0x3FFF) * m) >> 14.  SARSA uses the carried
  *      action a' instead -- inside a launch always, and at its start when it directly follows a SARSA gu_td_run on this engine
- *      (no gu_seed, gu_reset*, gu_step*, gu_rollout, gu_set_state, gu_set_grid(s), gu_generate_mazes, gu_td_init, gu_td_set_q, gu_dyna_run or
- *      sweep-step call in between);
+ *      (no gu_seed, gu_reset*, gu_step*, gu_rollout, gu_set_state, gu_set_grid(s), gu_generate_mazes, gu_td_init, gu_td_set_q, gu_dyna_run,
+ *      gu_nstep_run or sweep-step call in between);
  *   3. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
  *   4. float64, one rounding per operation: m = max Q_e[s'] (Q-learning) or Q_e[s'][a'] with a' drawn at s' by rule 2 from the word
  *      of the new t and the pre-update row (SARSA; not drawn when d); target = r if d else r + gamma * m;
@@ -306,6 +306,38 @@ int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q);
 int gu_dyna_init(gu_handle h);
 int gu_dyna_run(gu_handle h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32_t *reward, int32_t *done, int32_t *list, int32_t *count);
+
+/* ---- batched tabular n-step Q-learning and n-step SARSA: learner e owns env e and its table Q_e[S][4] (the gu_td_* tables) ----
+ * (build-defined: the reference lists "Temporal Difference (TD) Learning with variations" on its roadmap and ships no code;
+ * Sutton & Barto ch. 7; method 0 is the uncorrected n-step Q-learning of asynchronous n-step Q-learning, Mnih et al. 2016;
+ * tests/_nstep_oracle.py is the CPU restatement.)  Learner e keeps a WINDOW: the pending transitions (s_k, a_k, r_k), oldest
+ * first, at most n - 1 of them between iterations.  One iteration of gu_nstep_run for env e at 64-bit step count t:
+ *   1. lazy auto-reset, exactly as rule 1 of gu_td_run (the window is empty here: see 5);
+ *   2. action: as rule 2 of gu_td_run (the stream-4 word at t, epsilon, the tie rule).  SARSA takes its carried a' instead,
+ *      under the same conditions as gu_td_run's SARSA (the carry across launches is the window's, below);
+ *   3. (s', r, d) by the engine's move rule; t += 1; append (s, a, r) to the window;
+ *   4. if not d: B from the row of s' BEFORE this iteration's update: max Q_e[s'] folded left to right with `>` (Q-learning), or
+ *      Q_e[s'][a'] with a' drawn at s' by rule 2 from the word of the new t (SARSA).  If the window now holds n entries:
+ *      G = B, then for k from newest to oldest G = r_k + gamma * G; Q_e[s_0][a_0] += alpha * (G - Q_e[s_0][a_0]); drop entry 0;
+ *   5. if d: flush.  For each entry, oldest first, G = the Horner sum of its reward and the rewards of the entries after it,
+ *      without bootstrap (G = r for the newest); the updates apply in that order, each reading Q_e as the ones before it left it
+ *      (a repeated (s, a) compounds).  The window ends empty; SARSA draws no a';
+ *   6. the next iteration chooses from the table after this iteration's updates.
+ * All float64, one rounding per operation (multiply, then add).  With n = 1 this is gu_td_run, byte for byte, for both methods.
+ * CARRY: the window and SARSA's a' persist from one gu_nstep_run to the next when the later call directly follows the earlier one
+ * with the same method and n.  Any other call in between -- everything that ends gu_td_run's SARSA carry, gu_td_run,
+ * gu_dyna_run, a gu_nstep_run with another method or n -- drops both; the pending updates are discarded, not flushed.
+ * gu_nstep_run ends gu_td_run's SARSA carry.
+ * gu_nstep_run        : T iterations per env in ONE launch (async).  method 0 = n-step Q-learning, 1 = n-step SARSA; 1 <= n <=
+ *                       GU_NSTEP_MAX.  GU_ERR_STATE before gu_td_init; GU_ERR_INVALID for a bad method or n and everything
+ *                       gu_td_run rejects.  The window storage (N * 132 bytes) is allocated on first use (GU_ERR_NOMEM under
+ *                       gu_td_init's free-memory rule); a grid of another size drops it with the tables.  T = 0 changes
+ *                       nothing.  Flags, rows and statistics as gu_td_run.  The step counts advance by T.
+ * gu_nstep_get_window : the windows of envs env0 .. env0+n-1 on the host: sa (s*4+a) and reward as [n][GU_NSTEP_MAX], oldest
+ *                       first, (-1, 0) beyond count; count as [n], 0 when the window has been dropped.  Any pointer may be NULL. */
+#define GU_NSTEP_MAX 16
+int gu_nstep_run(gu_handle h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+int gu_nstep_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count);
 
 /* ---- look_step_ahead table queries: env:136-155 for n (state, action) pairs (grid 0 of a multi-grid engine) ---- */
 int gu_look_step_ahead(gu_handle h, int64_t n, const int32_t *states, const int32_t *actions,
