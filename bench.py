@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- env-steps/s of the fused rollout kernel on N MI355X (one process per GPU).
 
-    python bench.py                       # 1 GPU, defaults finish in about a minute
+    python bench.py                       # 1 GPU: the timed launches and the line, in seconds
+    python bench.py --full                # ... and every check and figure beside them (below), in about a minute
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W      # one rank per GPU (what the driver runs)
     python bench.py --gpus N              # started plainly: spawns the N ranks itself (before anything touches a GPU)
@@ -25,16 +26,23 @@ bytes per launch / (the block's HIP-event time / K).  Every run issues the same 
 --dump-outputs DIR writes what the last timed launch computed (a seeded sample of its trajectory rows, benchlib/dump.py)
 for a comparison of two builds output for output.
 
-Checks in the same run (rank 0): the FIRST launch is hashed in full and compared with the sha256 the REFERENCE produced
-for exactly this run (tests/golden/digests.json, 65.5 M steps of the reference's own step()); after the timed region the
-final (pos, done, episode, step count) of a sample of envs is compared with the C oracle advanced by every step launched.
+A plain run does only what the line needs: it sets up, warms up, times the K launches, writes --dump-outputs and prints the
+line (config, timing, the roofline figures the timed block gives, the committed profile's traffic, store pacing, placement).
+Everything else it measures or checks runs with --full only (the --no-* switches then leave single legs out):
+
+- checks (rank 0): the FIRST launch is hashed in full and compared with the sha256 the REFERENCE produced for exactly this run
+  (tests/golden/digests.json, 65.5 M steps of the reference's own step()); after all launches the final (pos, done, episode,
+  step count) of a sample of envs is compared with the C oracle advanced by every step launched;
+- an instrumented block of K more launches (an event after every launch) and the bare store probe on the kept buffer;
+- cpu_baseline, the statistics-only / packed-row launch forms, BASELINE configs 2, 4 (one shard) and 5, roofline.traffic
+  measured by two rocprofv3 --pmc child runs (1 GPU);
+- config 4 -- 262 144 envs on the lava grid in total, split over the ranks -- timed as a strong-scaling line ("strong_c4"), its
+  result checked against the C oracle on every rank (and, on one GPU, against the reference digest);
+- N > 1: after the timed region the RCCL gathered view runs once and is checked against every rank's own shard ("rccl";
+  --gather-view asks for it with one rank too, with or without --full).
 
 Output: ONE JSON line on stdout, under 4 KB (benchlib/report.py: contract keys, config, roofline, cpu_baseline, parity
 bits, other figures as numbers); everything else goes to the side file --detail names (bench_detail.json in the cwd).
-
-N > 1: after the timed region the RCCL gathered view runs once and is checked against every rank's own shard ("rccl"),
-and config 4 -- 262 144 envs on the lava grid in total, split over the ranks -- is timed as a strong-scaling line
-("strong_c4"), its result checked against the C oracle on every rank (and, on one GPU, against the reference digest).
 """
 import argparse
 import os
@@ -91,7 +99,7 @@ def run(args, engine_cls=None, emit=print):
     eng.reset()
     eng.reserve_trajectory(T)
 
-    # ---- launch 1, from reset: checked in full.  (Nothing is asked of the engine but the launches themselves: the store pacing of
+    # ---- launch 1, from reset: checked in full (--full).  (Nothing is asked of the engine but the launches themselves: the store pacing of
     # the rollout kernel is a closed loop that runs inside them from the first one on -- rounds 3 and 4 asked for a search here.)
     launches = 1
     eng.rollout(T, 'uniform', auto_reset=True, trajectory=True)
@@ -116,16 +124,18 @@ def run(args, engine_cls=None, emit=print):
     if args.dump_outputs:  # (before anything below launches again or overwrites the rows)
         dump_trajectory(eng, N, T, args.dump_outputs, env_id0=rank * N, prefix='rank%d_' % rank if world > 1 else '')
 
-    # ---- one instrumented block: an event after every launch (not part of `value`)
-    eng.sync()
-    eng.timer_mark()
-    for _ in range(K):
-        eng.rollout(T, 'uniform', auto_reset=True, trajectory=True)
+    per_launch, post_probe_ms = None, None
+    if args.full:
+        # ---- one instrumented block: an event after every launch (not part of `value`)
+        eng.sync()
         eng.timer_mark()
-    per_launch = eng.timer_laps()
-    launches += K
-    # ---- the bare store probe once more on the kept buffer, right after the timed launches (overwrites the rows, not the state)
-    post_probe_ms = eng.probe_trajectory() if hasattr(eng, 'probe_trajectory') else None
+        for _ in range(K):
+            eng.rollout(T, 'uniform', auto_reset=True, trajectory=True)
+            eng.timer_mark()
+        per_launch = eng.timer_laps()
+        launches += K
+        # ---- the bare store probe once more on the kept buffer, right after the timed launches (overwrites the rows, not the state)
+        post_probe_ms = eng.probe_trajectory() if hasattr(eng, 'probe_trajectory') else None
 
     if rank == 0 and not args.no_checks:
         eng.sync()
@@ -171,8 +181,9 @@ def run(args, engine_cls=None, emit=print):
                        'ms_per_step_min': w_min / K * 1e3, 'ms_per_step_median': w_med / K * 1e3, 'ms_per_step_max': w_max / K * 1e3,
                        'value_min': steps_per_block / w_max, 'value_max': steps_per_block / w_min,
                        'launch_ms_min': k_min / K, 'launch_ms_median': k_med / K, 'launch_ms_max': k_max / K,
-                       'per_launch_ms_min': float(per_launch.min()), 'per_launch_ms_median': float(np.median(per_launch)),
-                       'per_launch_ms_max': float(per_launch.max()), 'launches_total': launches},
+                       'per_launch_ms_min': None if per_launch is None else float(per_launch.min()),
+                       'per_launch_ms_median': None if per_launch is None else float(np.median(per_launch)),
+                       'per_launch_ms_max': None if per_launch is None else float(per_launch.max()), 'launches_total': launches},
             # frac: algorithmic bytes / the kernels' own HIP-event time per launch; frac_wall: / ms_per_step (the driver's clock)
             'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBPS, 'unit': 'GB/s',
                          'frac': achieved / HBM_PEAK_GBPS,
@@ -205,7 +216,7 @@ def run(args, engine_cls=None, emit=print):
             detail['cpu_baseline'] = base
     # ---- LAST: the RCCL gathered view (never run with more than one rank before the driver's own multi-GPU run).  Nothing follows
     # it but the line, and a watchdog stands behind it: a collective that does not come back costs the `rccl` object, not the line.
-    if world > 1 or args.gather_view:
+    if (world > 1 and args.full) or args.gather_view:
         box = {}
 
         def check():
@@ -236,6 +247,11 @@ def run(args, engine_cls=None, emit=print):
     ranks.close()
 
 
+# the legs of a --full run that a --no-* switch leaves out; the instrumented block, the store probe behind the timed launches and
+# the RCCL view of N > 1 ranks are --full's too
+FULL_ONLY = ('no_cpu_baseline', 'no_checks', 'no_strong_c4', 'no_configs', 'no_other_modes', 'no_live_traffic')
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -245,6 +261,8 @@ def parse_args(argv=None):
     ap.add_argument('--T', type=int, default=1000, help='env-steps per launch')
     ap.add_argument('--workload', default='c3', choices=['c2', 'c3', 'c4'])
     ap.add_argument('--c4-envs', type=int, default=C4_TOTAL_ENVS, help='total envs of the strong-scaling config-4 line')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every check and figure beside the timed launches (see the docstring); a plain run leaves them out')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-checks', action='store_true', help='skip the reference-digest / oracle checks of this run')
     ap.add_argument('--no-strong-c4', action='store_true')
@@ -259,7 +277,11 @@ def parse_args(argv=None):
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help="write what the last timed launch computed to DIR/<name>.npy (float32 / float64, under 64 MB in all)")
     ap.add_argument('--pmc-child', action='store_true', help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:  # a plain run: every leg a --no-* switch names is off
+        for leg in FULL_ONLY:
+            setattr(args, leg, True)
+    return args
 
 
 def main(argv=None, engine_cls=None, script=None):
@@ -271,7 +293,7 @@ def main(argv=None, engine_cls=None, script=None):
         pmc_child(args)
         return 0
     if args.single_process:
-        run_single_process(args, engine_cls)
+        run_single_process(args, engine_cls, full=args.full)
         return 0
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return spawn_ranks(args, argv, script or os.path.abspath(__file__), engine_cls)  # (before any HIP call and before libgu.so is loaded)

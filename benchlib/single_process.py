@@ -2,7 +2,8 @@
 contiguous env-index shards with global env ids g * N .., every launch enqueued device after device so that the GPUs run
 concurrently; the single-array view through ncclCommInitAll + one grouped ncclAllGather (gu_comm_init_all /
 gu_allgather_view_all).  Timed like the multi-process form: the settle launches, then one block of exactly K launches PER DEVICE between device
-syncs of all devices; `value` = all devices' env-steps / the block's wall time."""
+syncs of all devices; `value` = all devices' env-steps / the block's wall time.  Checks, the store probe, the view, config 4 and
+the CPU baseline run with --full only, as in bench.py's own flow."""
 import time
 
 import numpy as np
@@ -21,8 +22,9 @@ from .traffic import read_traffic
 from .workloads import BYTES_PER_ENV_STEP, HBM_COPY_GBPS, HBM_PEAK_GBPS, METRIC, WORKLOAD_SEED, build_workload, workload_line
 
 
-def run_single_process(args, engine_cls=None, emit=print):
-    """See the module docstring.  per_rank = every device's own HIP-event time."""
+def run_single_process(args, engine_cls=None, emit=print, full=True):
+    """See the module docstring.  per_rank = every device's own HIP-event time.  `full`: bench.py --full (False for a plain run:
+    no store probe, no view of N > 1 devices; the --no-* switches name the other legs)."""
     engine_cls = engine_cls or gua.Engine
     ensure_library_is_current(engine_cls)
     G, N, T, K, W = args.gpus, args.envs, args.T, args.steps, args.warmup
@@ -80,7 +82,7 @@ def run_single_process(args, engine_cls=None, emit=print):
             for g, e in enumerate(engines):
                 dump_trajectory(e, N, T, args.dump_outputs, env_id0=g * N, prefix='rank%d_' % g if G > 1 else '')
         dev_info = [device_block(engine_cls, d) for d in sorted(set(devices))]
-        post_probe = [e.probe_trajectory() if hasattr(e, 'probe_trajectory') else None for e in engines]
+        post_probe = [e.probe_trajectory() if full and hasattr(e, 'probe_trajectory') else None for e in engines]
         if not args.no_checks:
             for e in engines:
                 e.sync()
@@ -88,7 +90,7 @@ def run_single_process(args, engine_cls=None, emit=print):
             found['final_state_vs_oracle']['launches'] = launches
         # ---- the gathered view: one communicator over all devices of this process, one grouped all-gather
         rccl = None
-        if G > 1 or args.gather_view:
+        if (G > 1 and full) or args.gather_view:
             try:
                 with native_stdout_to_stderr():
                     t0 = time.perf_counter()

@@ -7,6 +7,7 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 from benchlib import dump
 
@@ -15,13 +16,13 @@ BENCH_ON_STUB = os.path.join(ROOT, 'tests', '_bench_stub.py')
 NAMES = {'obs', 'reward', 'done', 'env_id', 'step'}
 
 
-def _bench(out_dir, steps, *extra):
+def _bench(out_dir, steps, *extra, full=True):
     env = dict(os.environ, PYTHONPATH=ROOT, OMP_NUM_THREADS='1')
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     cmd = [sys.executable, BENCH_ON_STUB, '--gpus', '1', '--envs', '512', '--T', '40', '--steps', str(steps), '--warmup', '1',
            '--no-cpu-baseline', '--no-strong-c4', '--no-configs', '--no-other-modes', '--detail', '', '--dump-outputs', str(out_dir)]
-    proc = subprocess.run(cmd + list(extra), env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    proc = subprocess.run(cmd + (['--full'] if full else []) + list(extra), env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert proc.returncode == 0, proc.stderr.decode()[-3000:]
     lines = [ln for ln in proc.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -63,6 +64,25 @@ def test_dump_is_the_last_timed_launch_and_the_same_on_every_run(tmp_path):
     line3, c = _bench(tmp_path / 'c', 3)
     assert line3['steps'] == 3 and line3['timing']['launches_total'] == line['timing']['launches_total'] + 2
     assert not np.array_equal(a['obs'], c['obs'])
+
+
+@pytest.mark.parametrize('form', ['ranks', 'single-process'])
+def test_a_plain_run_ends_with_its_timed_launches_and_dumps_what_a_full_run_dumps(tmp_path, form):
+    """Without --full: no checks, no launch behind the timed block (the dump is the run's last launch), and the same rows as a
+    --full run, whose instrumented block adds K launches behind them (the single-process form has none)."""
+    extra = ['--single-process'] if form == 'single-process' else []
+    line, a = _bench(tmp_path / 'a', 2, *extra, full=False)
+    full, b = _bench(tmp_path / 'b', 2, *extra)
+    for key in ('bit_exact_vs_oracle', 'bit_exact_vs_reference_digest', 'final_state_vs_oracle', 'cpu_baseline', 'strong_c4', 'other_modes',
+                'configs', 'rccl'):
+        assert key not in line, key
+    assert full['bit_exact_vs_oracle'] is True and full['final_state_vs_oracle']['equal'] is True
+    assert line['steps'] == 2 and line['timing']['launches_total'] + (2 if form == 'ranks' else 0) == full['timing']['launches_total']
+    for n in NAMES:
+        assert a[n].tobytes() == b[n].tobytes(), n
+    want = _oracle_rows(line['timing']['launches_total'], 512, 40)
+    for k in ('obs', 'reward', 'done'):
+        assert np.array_equal(a[k], want[k].astype(np.float32)), k
 
 
 def test_dump_sample_stays_under_the_budget():

@@ -30,7 +30,7 @@ def test_default_workload_line_carries_the_contract_and_its_own_checks(tmp_path)
     """Config 3 at full size (65 536 envs x 1000 steps per launch), few launches: metric / unit / config as BASELINE.json names
     them, value = envs x steps x launches / time, the roofline object consistent with the HIP-event launch time, the first
     launch equal to the reference's digest, the final state equal to the oracle, and the CPU baseline beside it."""
-    line, detail = run_bench(tmp_path, '--gpus', '1', '--steps', '5', '--warmup', '2', '--c4-envs', '16384', '--gather-view')
+    line, detail = run_bench(tmp_path, '--gpus', '1', '--steps', '5', '--warmup', '2', '--c4-envs', '16384', '--gather-view', '--full')
     base = json.load(open(os.path.join(ROOT, 'BASELINE.json')))
     assert line['metric'] == base['metric'] and line['unit'] == 'env-steps/s' and line['n_gpus'] == 1
     assert line['steps'] == 5 and line['warmup'] == 2 and line['higher_is_better'] is True and line['scaling'] == 'weak'
@@ -82,12 +82,12 @@ def test_default_workload_line_carries_the_contract_and_its_own_checks(tmp_path)
 def test_other_workloads_and_switches(tmp_path):
     """Config 2 (4096 envs, 8x8) with the checks, and a run with everything optional switched off."""
     line, _ = run_bench(tmp_path, '--workload', 'c2', '--envs', '4096', '--steps', '3', '--warmup', '1', '--no-strong-c4',
-                     '--no-cpu-baseline', '--no-live-traffic')
+                     '--no-cpu-baseline', '--no-live-traffic', '--full')
     assert line['roofline']['traffic_measured_by_child_runs'] is False and line['roofline']['traffic'] is None  # (the committed profile is of the default launch)
     assert line['config']['envs_per_gpu'] == 4096 and line['bit_exact_vs_reference_digest'] is True  # 4096 x 1000 is a captured run
     assert line['final_state_vs_oracle']['equal'] is True and 'cpu_baseline' not in line and 'strong_c4' not in line
     line, _ = run_bench(tmp_path, '--steps', '2', '--warmup', '1', '--no-strong-c4', '--no-cpu-baseline', '--no-checks',
-                     '--no-other-modes', '--envs', '1000', '--T', '77', '--no-live-traffic', '--no-configs')
+                     '--no-other-modes', '--envs', '1000', '--T', '77', '--no-live-traffic', '--no-configs', '--full')
     assert 'other_modes' not in line and 'configs' not in line and 'bit_exact_vs_reference_digest' not in line and line['value'] > 0
 
 
@@ -97,11 +97,33 @@ def test_dump_outputs_is_the_last_timed_launch(tmp_path):
     import numpy as np
     from tests.test_bench_dump import NAMES, _oracle_rows
     args = ('--envs', '4096', '--T', '100', '--steps', '3', '--warmup', '1', '--no-strong-c4', '--no-cpu-baseline', '--no-configs',
-            '--no-other-modes', '--no-live-traffic')
+            '--no-other-modes', '--no-live-traffic', '--full')
     line, _ = run_bench(tmp_path, *(args + ('--dump-outputs', str(tmp_path / 'a'))))
     run_bench(tmp_path, *(args + ('--dump-outputs', str(tmp_path / 'b'))))
     a, b = ({n: np.load(str(tmp_path / d / (n + '.npy'))) for n in NAMES} for d in ('a', 'b'))
     assert all(a[n].tobytes() == b[n].tobytes() for n in NAMES) and a['obs'].shape == (100, 4096)
     want = _oracle_rows(line['timing']['launches_total'] - 3, 4096, 100)  # (the K instrumented launches follow the timed block)
+    for k in ('obs', 'reward', 'done'):
+        assert np.array_equal(a[k], want[k].astype(np.float32)), k
+
+
+def test_a_plain_run_is_its_timed_launches_and_dumps_what_a_full_run_dumps(tmp_path):
+    """Without --full: the line of the timed launches alone (no checks, CPU baseline, traffic runs or other launches), the last
+    timed launch is the run's last launch (the C oracle advanced by every launch), and a --full run dumps the same bytes."""
+    import numpy as np
+    from tests.test_bench_dump import NAMES, _oracle_rows
+    args = ('--envs', '4096', '--T', '100', '--steps', '3', '--warmup', '1')
+    line, detail = run_bench(tmp_path, *(args + ('--dump-outputs', str(tmp_path / 'plain'))))
+    full, _ = run_bench(tmp_path, *(args + ('--full', '--no-strong-c4', '--no-cpu-baseline', '--no-configs', '--no-other-modes',
+                                            '--no-live-traffic', '--dump-outputs', str(tmp_path / 'full'))))
+    for key in ('bit_exact_vs_oracle', 'bit_exact_vs_reference_digest', 'final_state_vs_oracle', 'cpu_baseline', 'strong_c4', 'other_modes',
+                'configs', 'rccl'):
+        assert key not in line, key
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['value'] > 0 and line['roofline']['traffic_measured_by_child_runs'] is False
+    assert detail['roofline']['trajectory_placement'] and detail['roofline']['store_pacing']
+    assert full['final_state_vs_oracle']['equal'] is True and full['timing']['launches_total'] == line['timing']['launches_total'] + 3
+    a, b = ({n: np.load(str(tmp_path / d / (n + '.npy'))) for n in NAMES} for d in ('plain', 'full'))
+    assert all(a[n].tobytes() == b[n].tobytes() for n in NAMES) and a['obs'].shape == (100, 4096)
+    want = _oracle_rows(line['timing']['launches_total'], 4096, 100)
     for k in ('obs', 'reward', 'done'):
         assert np.array_equal(a[k], want[k].astype(np.float32)), k

@@ -31,7 +31,7 @@ def _bench(tmp_path, *args):
     return json.loads(lines[0]), json.load(open(side))
 
 
-SMALL = ['--envs', '16384', '--T', '200', '--steps', '3', '--warmup', '1', '--c4-envs', '16384', '--no-cpu-baseline', '--no-live-traffic']
+SMALL = ['--envs', '16384', '--T', '200', '--steps', '3', '--warmup', '1', '--c4-envs', '16384', '--no-cpu-baseline', '--no-live-traffic', '--full']
 
 
 @pytest.mark.parametrize('order', ['gu_first', 'torch_first'])

@@ -73,7 +73,7 @@ def test_two_rank_shards_and_gathered_view_under_torch_distributed_run(tmp_path)
 
 BENCH_ON_STUB = os.path.join(ROOT, 'tests', '_bench_stub.py')  # bench.main(..., engine_cls=OracleEngine)
 STUB = ['--envs', '512', '--T', '40', '--steps', '2', '--warmup', '1',
-        '--c4-envs', '2048', '--detail', '']
+        '--c4-envs', '2048', '--detail', '', '--full']
 
 
 def _one_json_line(proc):
@@ -206,7 +206,7 @@ def test_eight_gpu_preflight_on_the_stub_engine(form):
     rendezvous) and with --single-process, config 4 at its full 262 144 envs = 32 768 per rank."""
     extra = ['--single-process'] if form == 'single-process' else []
     proc = subprocess.run([sys.executable, BENCH_ON_STUB, '--gpus', '8'] + extra + ['--envs', '256', '--T', '24', '--steps', '2', '--warmup', '1',
-                                                                                    '--c4-envs', '262144', '--detail', ''],
+                                                                                    '--c4-envs', '262144', '--detail', '', '--full'],
                           env=_scrubbed_env(), cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     line = _one_json_line(proc)
     assert line['n_gpus'] == 8 and len(line['per_rank']['value']) == 8
