@@ -90,6 +90,10 @@ SIGNATURES = {
     'gu_dyna_get_model': [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     'gu_nstep_run': [_vp, _i64, _i32, _i32, _f64, _f64, _u32, _u32],
     'gu_nstep_get_window': [_vp, _i64, _i64, _vp, _vp, _vp],
+    'gu_ac_init': [_vp, _f64, _f64],
+    'gu_ac_run': [_vp, _i64, _f64, _f64, _f64, _u32],
+    'gu_ac_get': [_vp, _i64, _i64, _vp, _vp],
+    'gu_ac_set': [_vp, _i64, _i64, _vp, _vp],
     'gu_vi_set': [_vp, _vp, _vp],
     'gu_vi_sweep': [_vp, _f64, _i32, _i32, _vp],
     'gu_vi_run': [_vp, _f64, _f64, _i32, _vp, _vp],

@@ -16,6 +16,7 @@
 
 static void gu_dyna_free(gu_engine *h);  // (tabular Dyna-Q, below)
 static void gu_nstep_free(gu_engine *h);  // (tabular n-step learners, below)
+static void gu_ac_free(gu_engine *h);     // (tabular actor-critic, below)
 
 // ---------------------------------------------------------------------------------- errors
 static thread_local std::string g_last_error;
@@ -173,7 +174,7 @@ int gu_destroy(gu_handle h)
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
                     h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next,
-                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt};
+                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_ac_h, h->d_ac_v};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -251,6 +252,7 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
         gu_nstep_free(h);
     }
     if (h->dyna_S && h->dyna_S != W * H) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
+    if (h->ac_S && h->ac_S != W * H) gu_ac_free(h);  // ... and actor-critic tables: gu_ac_init again
     h->dyna_exact = false;  // a kept model may hold outcomes of the old cells: gu_dyna_run compares every observation from now on
     h->nib_valid = false;
     if (h->d_nib) GU_HIP(hipFree(h->d_nib));
@@ -1353,6 +1355,85 @@ int gu_nstep_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32
         }
     if (count)
         for (int64_t e = 0; e < n; ++e) count[e] = c[e];
+    return GU_OK;
+}
+
+static void gu_ac_free(gu_engine *h)
+{
+    if (h->d_ac_h) (void)hipFree(h->d_ac_h);
+    if (h->d_ac_v) (void)hipFree(h->d_ac_v);
+    h->d_ac_h = nullptr;
+    h->d_ac_v = nullptr;
+    h->ac_S = 0;
+}
+
+int gu_ac_init(gu_handle h, double h0, double v0)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(std::isfinite(h0) && std::isfinite(v0), GU_ERR_INVALID, "h0 and v0 must be finite");
+    gu_tabular_drop_carry(h);
+    if (!h->d_ac_h || h->ac_S != h->S) {
+        GU_HIP(hipStreamSynchronize(h->stream));
+        gu_ac_free(h);
+        const size_t states = (size_t)h->N * (size_t)h->S;
+        int rc = gu_tabular_fits(h, states * 5 * sizeof(double), "actor-critic tables");
+        if (rc != GU_OK) return rc;
+        GU_HIP(hipMalloc(&h->d_ac_h, states * 4 * sizeof(double)));
+        GU_HIP(hipMalloc(&h->d_ac_v, states * sizeof(double)));
+        h->ac_S = h->S;
+    }
+    int rc = gu_ac_fill(h, h0, v0);
+    if (rc != GU_OK) return rc;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_ac_run(gu_handle h, int64_t T, double alpha_actor, double alpha_critic, double gamma, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_ac_h && h->ac_S == h->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first");
+    GU_REQUIRE(std::isfinite(alpha_critic), GU_ERR_INVALID, "alpha_critic must be finite");
+    int rc = gu_tabular_check(h, "gu_ac_run", T, -1, 0u, alpha_actor, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    return gu_launch_ac(h, T, alpha_actor, alpha_critic, gamma, flags);
+}
+
+static int gu_ac_range(gu_engine *h, int64_t env0, int64_t n, const void *pref, const void *v)
+{
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_ac_h && h->ac_S == h->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first");
+    GU_REQUIRE(pref != nullptr || v != nullptr, GU_ERR_INVALID, "pref and v are both NULL");
+    return gu_env_range(h, env0, n);
+}
+
+int gu_ac_get(gu_handle h, int64_t env0, int64_t n, double *pref, double *v)
+{
+    GU_ENTER(h);
+    int rc = gu_ac_range(h, env0, n, pref, v);
+    if (rc != GU_OK) return rc;
+    const size_t S = (size_t)h->S;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n && pref) GU_HIP(hipMemcpy(pref, h->d_ac_h + (size_t)env0 * S * 4, (size_t)n * S * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    if (n && v) GU_HIP(hipMemcpy(v, h->d_ac_v + (size_t)env0 * S, (size_t)n * S * sizeof(double), hipMemcpyDeviceToHost));
+    return GU_OK;
+}
+
+int gu_ac_set(gu_handle h, int64_t env0, int64_t n, const double *pref, const double *v)
+{
+    GU_ENTER(h);
+    int rc = gu_ac_range(h, env0, n, pref, v);
+    if (rc != GU_OK) return rc;
+    const size_t S = (size_t)h->S, k = (size_t)n * S;
+    if (pref)
+        for (size_t i = 0; i < 4 * k; ++i) GU_REQUIRE(std::isfinite(pref[i]), GU_ERR_INVALID, "pref[%zu] is not finite", i);
+    if (v)
+        for (size_t i = 0; i < k; ++i) GU_REQUIRE(std::isfinite(v[i]), GU_ERR_INVALID, "v[%zu] is not finite", i);
+    gu_tabular_drop_carry(h);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n && pref) GU_HIP(hipMemcpy(h->d_ac_h + (size_t)env0 * S * 4, pref, 4 * k * sizeof(double), hipMemcpyHostToDevice));
+    if (n && v) GU_HIP(hipMemcpy(h->d_ac_v + (size_t)env0 * S, v, k * sizeof(double), hipMemcpyHostToDevice));
     return GU_OK;
 }
 

@@ -267,6 +267,10 @@ struct gu_engine {
     int32_t *d_nstep_r = nullptr;    // [N][GU_NSTEP_MAX] their rewards
     int32_t *d_nstep_cnt = nullptr;  // [N] entries of the window
     int32_t nstep_key = 0;           // gu_nstep_key of the last call that touched the envs if it was a gu_nstep_run, else 0 (window dropped)
+    // batched tabular softmax actor-critic (gu_ac.hip): off until gu_ac_init; tables of its own, not d_q
+    double *d_ac_h = nullptr;  // [N][ac_S][4] preferences
+    double *d_ac_v = nullptr;  // [N][ac_S] state values
+    int32_t ac_S = 0;          // states of the tables (0: none allocated); a grid of another size drops them
     // batched tabular Dyna-Q (gu_dyna.hip): off until gu_dyna_init; learns into d_q
     uint64_t *d_dyna_model = nullptr;  // [N][dyna_S*4] one packed word per (s, a): reward | (s' | done << 31) << 32; ~0 = unobserved
     int32_t *d_dyna_list = nullptr;    // [N][dyna_S*4] observed pairs s*4+a in the order of first observation (-1 beyond count)
@@ -417,6 +421,10 @@ int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, double gamm
 // the carry key of a gu_nstep_run (never 0): the next launch keeps the window only under the same method and n
 static inline int32_t gu_nstep_key(int32_t method, int32_t n) { return 1 + method + 2 * n; }
 int gu_launch_nstep(gu_engine *h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+
+// ---- batched tabular softmax actor-critic (gu_ac.hip) ----------------------------------
+int gu_ac_fill(gu_engine *h, double h0, double v0);  // every preference = h0, every value = v0 (async)
+int gu_launch_ac(gu_engine *h, int64_t T, double alpha_actor, double alpha_critic, double gamma, uint32_t flags);
 
 // every call that touches the envs other than the learner launches ends what the learners carry from one launch to the next:
 // gu_td_run's SARSA action and gu_nstep_run's window (its pending updates are discarded, not flushed)

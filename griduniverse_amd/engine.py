@@ -18,7 +18,7 @@ _TD_METHODS = {'q_learning': _lib.TD_Q_LEARNING, 'sarsa': _lib.TD_SARSA, 0: _lib
 
 
 def _learner_flags(trajectory, stats):
-    """The flags of a tabular learner launch (gu_td_run, gu_dyna_run, gu_nstep_run): rows and statistics only."""
+    """The flags of a tabular learner launch (gu_td_run, gu_dyna_run, gu_nstep_run, gu_ac_run): rows and statistics only."""
     return (_lib.F_TRAJECTORY if trajectory else 0) | (_lib.F_STATS if stats else 0)
 
 
@@ -377,6 +377,47 @@ class Engine(object):
                    count=np.empty(n0, np.int32))
         check(self.lib.gu_nstep_get_window(self._h, int(env0), n, ptr(out['sa']), ptr(out['reward']), ptr(out['count'])))
         return out
+
+    # ------------------------------------------------------------------ tabular softmax actor-critic (include/gu.h: gu_ac_*)
+    def ac_init(self, h0=0.0, v0=0.0):
+        """One float64 preference table [S][4] (every entry h0) and one value table [S] (every entry v0) per env."""
+        check(self.lib.gu_ac_init(self._h, float(h0), float(v0)))
+
+    def ac_run(self, T, alpha_actor=0.1, alpha_critic=0.1, gamma=0.99, trajectory=False, stats=False):
+        """T one-step actor-critic iterations per env in one launch (softmax policy, auto-reset always on).  Rows and
+        statistics as td_run()."""
+        check(self.lib.gu_ac_run(self._h, int(T), float(alpha_actor), float(alpha_critic), float(gamma),
+                                 _learner_flags(trajectory, stats)))
+
+    def ac_get(self, env0=0, n=None):
+        """(preferences float64[n, S, 4], values float64[n, S]) of envs env0 .. env0+n-1 (all from env0 when n is None)."""
+        n = self.N - int(env0) if n is None else int(n)
+        S = self.spec.S
+        h, v = np.empty((max(n, 0), S, 4), np.float64), np.empty((max(n, 0), S), np.float64)
+        check(self.lib.gu_ac_get(self._h, int(env0), n, ptr(h), ptr(v)))
+        return h, v
+
+    def ac_set(self, h=None, v=None, env0=0):
+        """Install preferences float64[n, S, 4] (or [S, 4]) and / or values float64[n, S] (or [S]) for envs env0 ..; when both
+        are given they must cover the same envs."""
+        S, n = self.spec.S, None
+        if h is not None:
+            h = np.asarray(h, np.float64)
+            h = _lib.as_array(h.reshape((-1, S, 4)) if h.ndim == 2 else h, np.float64, None, 'h')
+            if h.ndim != 3 or h.shape[1:] != (S, 4):
+                raise ValueError('h must have shape (n, {}, 4), got {}'.format(S, h.shape))
+            n = h.shape[0]
+        if v is not None:
+            v = np.asarray(v, np.float64)
+            v = _lib.as_array(v.reshape((-1, S)) if v.ndim == 1 else v, np.float64, None, 'v')
+            if v.ndim != 2 or v.shape[1] != S:
+                raise ValueError('v must have shape (n, {}), got {}'.format(S, v.shape))
+            if n is not None and v.shape[0] != n:
+                raise ValueError('h and v cover {} and {} envs'.format(n, v.shape[0]))
+            n = v.shape[0]
+        if n is None:
+            raise ValueError('give h, v or both')
+        check(self.lib.gu_ac_set(self._h, int(env0), n, ptr(h) if h is not None else None, ptr(v) if v is not None else None))
 
     # ------------------------------------------------------------------ state
     def get_state(self):

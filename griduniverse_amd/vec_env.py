@@ -14,6 +14,7 @@ keyed by GLOBAL env id, so the union of the shards equals the single-device batc
 for byte (see `parallel.py`).
 """
 
+from . import softmax
 from .engine import Engine
 from .envs.griduniverse_env import GridUniverseEnv
 from .grid import GridSpec
@@ -22,6 +23,7 @@ from .grid import GridSpec
 class VecGridUniverse(object):
     _td_ready = False  # the engine holds Q tables (td_run / set_q_table allocate them on first use)
     _dyna_ready = False  # ... and Dyna-Q models (dyna_run / model allocate them on first use)
+    _ac_ready = False  # ... and actor-critic tables (actor_critic_run / set_actor_critic allocate them on first use)
 
     def __init__(self, num_envs, grid_shape=(4, 4), *, initial_state=0, goal_states=None, lava_states=None,
                  walls=None, custom_world_fp=None, random_maze=False, template=None, templates=None,
@@ -177,6 +179,43 @@ class VecGridUniverse(object):
     def nstep_window(self, env0=0, n=None):
         """The n-step windows of envs env0 .. env0+n-1 (Engine.nstep_get_window)."""
         return self.engine.nstep_get_window(env0, n)
+
+    def _ensure_ac(self, h0=None, v0=None):
+        """Actor-critic tables on the engine: zeros on first use; every entry h0 / v0 (again) when either is given."""
+        if h0 is not None or v0 is not None or not self._ac_ready:
+            self.engine.ac_init(0.0 if h0 is None else h0, 0.0 if v0 is None else v0)
+            self._ac_ready = True
+
+    def actor_critic_run(self, T, actor_lr=0.1, critic_lr=0.1, discount_factor=0.99, trajectory=False, stats=False):
+        """T iterations of batched tabular one-step actor-critic: env e learns its own softmax preferences [S][4] and state
+        values [S] from its own experience, acting on the softmax of its preferences, auto-reset always on (include/gu.h:
+        gu_ac_run).  The first call gives every env tables of zeros.  Returns a dict like td_run()."""
+        self._ensure_ac()
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.ac_run(T, actor_lr, critic_lr, discount_factor, trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def preferences(self, env0=0, n=None):
+        """float64[n, S, 4]: the actor's preference tables of envs env0 .. env0+n-1 (to the end when n is None)."""
+        self._ensure_ac()
+        return self.engine.ac_get(env0, n)[0]
+
+    def state_values(self, env0=0, n=None):
+        """float64[n, S]: the critic's state values of envs env0 .. env0+n-1 (to the end when n is None)."""
+        self._ensure_ac()
+        return self.engine.ac_get(env0, n)[1]
+
+    def set_actor_critic(self, h=None, v=None, env0=0):
+        """Install preferences float64[n, S, 4] and / or values float64[n, S] for envs env0 ..; the other envs get tables of
+        zeros if they had none."""
+        self._ensure_ac()
+        self.engine.ac_set(h, v, env0)
+
+    def softmax_policy(self, env0=0, n=None):
+        """float64[n, S, 4]: the softmax policy pi of envs env0 .. env0+n-1, computed on the host with the same bytes as the
+        device's (griduniverse_amd.softmax)."""
+        return softmax.softmax_policy(self.preferences(env0, n))
 
     def done_indices(self):
         return self.engine.done_indices()

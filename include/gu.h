@@ -339,6 +339,42 @@ int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32
 int gu_nstep_run(gu_handle h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 int gu_nstep_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count);
 
+/* ---- batched tabular one-step actor-critic with a softmax policy: learner e owns env e, preferences H_e[S][4] and values V_e[S] ----
+ * (build-defined: the reference lists "Policy Gradients (MC Policy Gradients and Actor-critic)" on its roadmap and ships no code;
+ * Sutton & Barto 13.5; tests/_ac_oracle.py is the CPU restatement.)  The tables are float64 and the learner's own, not the
+ * gu_td_* Q tables.  All arithmetic is float64 with one rounding per operation (multiply, add, subtract, divide).
+ * THE BUILD'S EXP, gu_exp(x) for x <= 0 (non-finite x: unspecified):
+ *   x < -700: 0.0.  Otherwise k = rint(x * 1.4426950408889634) (half to even);
+ *   r = (x - k * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10;
+ *   p = 1/13!, then p = p * r + c for c = 1/12!, 1/11!, ..., 1/2!, 1, 1 in that order (multiply and add rounded separately;
+ *   each 1/n! is the double nearest to it); result = ldexp(p, k) (k >= -1010 here, so the result is normal and exact).
+ * One iteration of gu_ac_run for env e at 64-bit step count t:
+ *   1. reset: lazy auto-reset, exactly as rule 1 of gu_td_run;
+ *   2. policy: h = H_e[s], m = its maximum folded left to right with `>`; e_b = gu_exp(h_b - m); Z = ((e_0 + e_1) + e_2) + e_3;
+ *      iz = 1 / Z; pi_b = e_b * iz;
+ *   3. action: w = the stream-4 word at t (as rule 2 of gu_td_run); x = (w * 2^-32) * Z; a = the first b with x < c_b,
+ *      c_0 = e_0, c_b = c_{b-1} + e_b, c_3 = Z; 3 if none.  No epsilon: the softmax explores;
+ *   4. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
+ *   5. TD error: delta = (r + gamma * V_e[s']) - V_e[s], V_e[s'] read before this iteration's writes; delta = r - V_e[s] when d
+ *      (H_e[s'] and V_e[s'] are not read then);
+ *   6. critic: V_e[s] = V_e[s] + alpha_critic * delta;
+ *   7. actor: g = alpha_actor * delta; H_e[s][b] = H_e[s][b] + g * ([b == a] - pi_b) for b = 0..3.  There is no gamma^t factor
+ *      ("I" of the textbook's pseudo-code): a deliberate choice, the common form of the continuing, auto-resetting learner;
+ *   8. the next iteration sees the updated row and value (a wall bump, s' == s, included).
+ * gu_ac_run ends gu_td_run's SARSA carry and gu_nstep_run's window and has no carry of its own.
+ * gu_ac_init : allocate both tables (N * S * 40 bytes; GU_ERR_NOMEM under gu_td_init's free-memory rule) and fill every
+ *              preference with h0 and every value with v0; GU_ERR_INVALID for a non-finite h0 or v0.  A grid of another size
+ *              drops the tables (gu_ac_init again).  gu_td_init and gu_td_set_q leave them alone.
+ * gu_ac_run  : T iterations per env in ONE launch (async).  GU_ERR_STATE before gu_ac_init; GU_ERR_INVALID for non-finite rates
+ *              or gamma, T < 0 or T > 1e8, flags other than GU_F_TRAJECTORY | GU_F_STATS.  Rows, statistics, the trajectory
+ *              reservation and the agent trail as gu_td_run.  T = 0 changes nothing.  The step counts advance by T.
+ * gu_ac_get / gu_ac_set : the tables of envs env0 .. env0+n-1 on the host, pref as [n][S][4] and v as [n][S]; either pointer
+ *              may be NULL, not both.  gu_ac_set rejects non-finite entries (GU_ERR_INVALID) before it writes anything. */
+int gu_ac_init(gu_handle h, double h0, double v0);
+int gu_ac_run(gu_handle h, int64_t T, double alpha_actor, double alpha_critic, double gamma, uint32_t flags);
+int gu_ac_get(gu_handle h, int64_t env0, int64_t n, double *pref, double *v);
+int gu_ac_set(gu_handle h, int64_t env0, int64_t n, const double *pref, const double *v);
+
 /* ---- look_step_ahead table queries: env:136-155 for n (state, action) pairs (grid 0 of a multi-grid engine) ---- */
 int gu_look_step_ahead(gu_handle h, int64_t n, const int32_t *states, const int32_t *actions,
                        int32_t care_about_terminal, int32_t *next, int32_t *reward, int32_t *done);

@@ -1,0 +1,109 @@
+"""Batched tabular softmax actor-critic, the parts that need no GPU: the build's exp against math.exp, the product's host softmax
+against the restatement's, a frozen actor, maze learning, the argument checks and the library's new symbols."""
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from griduniverse_amd import _lib
+from griduniverse_amd import softmax as SM
+from griduniverse_amd.algorithms.policy_gradient import actor_critic
+from griduniverse_amd.envs.griduniverse_env import GridUniverseEnv
+from oracle import c_oracle as C
+
+from . import _ac_oracle as A
+from . import _golden as G
+from . import _td_oracle as O
+from .test_dyna_host import _greedy_walk, _shortest_from_start
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _ulps(a, b):
+    return np.abs(np.asarray(a, np.float64).view(np.int64) - np.asarray(b, np.float64).view(np.int64))
+
+
+def test_gu_exp_is_within_one_ulp_of_math_exp():
+    x = np.concatenate([-np.linspace(0.0, 700.0, 400001), -np.random.default_rng(0).uniform(0.0, 700.0, 100000),
+                        -np.logspace(-300, 0, 2000)])
+    want = np.array([math.exp(v) for v in x])
+    assert _ulps(A.gu_exp(x), want).max() <= 1
+    assert A.gu_exp(0.0) == 1.0 and A.gu_exp(-0.0) == 1.0
+    assert A.gu_exp(-700.5) == 0.0 and A.gu_exp(-1e9) == 0.0
+    assert A.gu_exp(-700.0) > 0.0
+
+
+def test_product_softmax_equals_the_restatement_bytes():
+    rng = np.random.default_rng(1)
+    h = np.concatenate([rng.normal(0, 3, (5000, 4)), rng.normal(0, 300, (2000, 4)), np.zeros((3, 4)),
+                        np.array([[1.0, 1.0, -2.0, 1.0], [-800.0, 0.0, 5.0, -705.0], [2.5, 2.5, 2.5, 2.5]])])
+    e, Z, pi = A.softmax(h)
+    e2, Z2 = SM.softmax_terms(h)
+    assert e2.tobytes() == e.tobytes() and Z2.tobytes() == Z.tobytes()
+    assert SM.softmax_policy(h).tobytes() == pi.tobytes()
+    assert SM.gu_exp(-np.linspace(0, 710, 10001)).tobytes() == A.gu_exp(-np.linspace(0, 710, 10001)).tobytes()
+    assert ((Z >= 1.0) & (Z <= 4.0)).all()  # the range the device's reciprocal is built for
+    assert np.abs(pi.sum(axis=1) - 1.0).max() < 1e-15
+    assert np.array_equal(SM.softmax_policy(np.zeros((2, 3, 4))), np.full((2, 3, 4), 0.25))
+
+
+def test_frozen_actor_with_zero_preferences_takes_the_top_two_bits():
+    """actor_lr = 0 and zero preferences: Z = 4 and c = 1, 2, 3, so x = (w 2^-32) 4 picks a = w >> 30."""
+    grid = C.Grid.from_lists(6, 5, goals=[29], lava=[8], walls=[14])
+    o = A.AcOracle(grid, 4, 50)
+    o.reset()
+    for _ in range(300):
+        s, t = o.state.pos.copy(), o.state.tcount.copy()
+        done_before = o.state.done.copy()
+        w = O.words(4, o.env_ids, t)
+        out = o.ac(1, 0.0, 0.3, 0.9)
+        if done_before.any():
+            continue  # (a reset moved the env first; the action is still w >> 30, but s is the start cell)
+        nxt, _, _ = C.look_step_ahead(grid, s, (w >> 30).astype(np.int32), True)
+        assert np.array_equal(out['obs'][0], nxt)
+    assert not o.h.any()  # the actor never moved
+    assert o.v.any()      # the critic did
+
+
+def _steps_to_shortest(grid, best, chunk=100, limit=10000):
+    """Real steps until every learner's argmax walk from the start is a shortest path (alpha_actor = alpha_critic = 0.1,
+    gamma = 0.99, seed 3, four learners)."""
+    o = A.AcOracle(grid, 3, 4)
+    o.reset()
+    done = 0
+    while done < limit:
+        o.ac(chunk, 0.1, 0.1, 0.99)
+        done += chunk
+        if all(_greedy_walk(grid, o.h[e]) == best for e in range(o.n)):
+            return done
+    return None
+
+
+def test_actor_critic_learns_the_shortest_path_in_the_maze():
+    """Measured with this restatement (which the device matches byte for byte): all four learners' argmax walks are the shortest
+    24 steps after 8000 real steps, in line with a throwaway prototype (numpy's RNG) that needed 7000-9500.  The budget is 10 000."""
+    grid = C.Grid.from_env(GridUniverseEnv(custom_world_fp=G.level_path('maze_11x11.txt')))
+    best = _shortest_from_start(grid)
+    assert best == 24
+    assert _steps_to_shortest(grid, best) == 8000
+
+
+def test_actor_critic_checks_its_arguments():
+    env = GridUniverseEnv((4, 4))
+    for kw in (dict(num_learners=0), dict(num_steps=-1), dict(actor_lr=float('nan')), dict(critic_lr=float('inf')),
+               dict(discount_factor=float('nan'))):
+        args = dict(num_steps=10)
+        args.update(kw)
+        with pytest.raises(ValueError):
+            actor_critic(env, **args)
+
+
+def test_library_exports_the_actor_critic_entry_points():
+    syms = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], stdout=subprocess.PIPE, check=True).stdout.decode()
+    header = open(os.path.join(ROOT, 'include', 'gu.h')).read()
+    for name in ('gu_ac_init', 'gu_ac_run', 'gu_ac_get', 'gu_ac_set'):
+        assert ' T ' + name + '\n' in syms, name
+        assert name in _lib.SIGNATURES
+        assert 'int ' + name + '(' in header
