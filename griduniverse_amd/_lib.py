@@ -25,6 +25,7 @@ F_AUTO_RESET, F_TRAJECTORY, F_STATS, F_PINNED_IO, F_PACKED = 1, 2, 4, 8, 16
 POLICY_UNIFORM, POLICY_STREAM, POLICY_GREEDY, POLICY_SAMPLE = 0, 1, 2, 3
 TD_Q_LEARNING, TD_SARSA = 0, 1
 NSTEP_MAX = 16  # GU_NSTEP_MAX: the largest n of gu_nstep_run
+LAMBDA_MAX = 64  # GU_LAMBDA_MAX: the largest K (trace length) of gu_lambda_run
 COMM_ID_BYTES = 128
 OPT_UNSET = -2 ** 63
 # gu_set_option / gu_get_option (include/gu.h "options"): name -> id
@@ -90,6 +91,8 @@ SIGNATURES = {
     'gu_dyna_get_model': [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     'gu_nstep_run': [_vp, _i64, _i32, _i32, _f64, _f64, _u32, _u32],
     'gu_nstep_get_window': [_vp, _i64, _i64, _vp, _vp, _vp],
+    'gu_lambda_run': [_vp, _i64, _i32, _i32, _f64, _f64, _f64, _u32, _u32],
+    'gu_lambda_get_window': [_vp, _i64, _i64, _vp],
     'gu_ac_init': [_vp, _f64, _f64],
     'gu_ac_run': [_vp, _i64, _f64, _f64, _f64, _u32],
     'gu_ac_get': [_vp, _i64, _i64, _vp, _vp],

@@ -8,7 +8,8 @@ own state is left alone.  `greedy_policy` turns a learned table into the referen
 `get_policy_map`, `engine.vi_set` and `rollout(policy='greedy')` like a policy from dynamic programming.
 
 `n_step_sarsa` / `n_step_q_learning` are the n-step variations (Sutton & Barto ch. 7; include/gu.h, gu_nstep_run), on the same
-tables, by csrc/gu_nstep.hip.
+tables, by csrc/gu_nstep.hip.  `sarsa_lambda` / `watkins_q_lambda` are the eligibility-trace variations (Sutton & Barto ch. 12;
+include/gu.h, gu_lambda_run), on the same tables, by csrc/gu_lambda.hip.
 """
 import numpy as np
 
@@ -19,7 +20,7 @@ _CHUNK = 100000  # steps per launch (the launch limit is 1e8; shorter launches k
 
 
 def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False):
-    """The learner batch of q_learning / sarsa / n_step_* / dyna_q: L learners on the grid of `env`, tables of q0 (and empty models when
+    """The learner batch of q_learning / sarsa / n_step_* / *_lambda / dyna_q: L learners on the grid of `env`, tables of q0 (and empty models when
     `model`), `num_steps` real steps each in launches `launch(vec, T)` of at most `chunk` steps.  Returns Q [S][4] or [L][S][4]."""
     L = int(num_learners)
     vec = VecGridUniverse(L, template=env, seed=seed)
@@ -81,6 +82,36 @@ def n_step_q_learning(env, num_steps, n=4, alpha=0.1, discount_factor=0.99, epsi
     """Epsilon-greedy n-step Q-learning, uncorrected (it bootstraps on max Q[S_{t+n}], as asynchronous n-step Q-learning does);
     arguments and result as `n_step_sarsa`.  With n = 1 it is `q_learning`."""
     return _nstep('q_learning', env, num_steps, n, alpha, discount_factor, epsilon, num_learners, seed, q0)
+
+
+def _lambda(method, env, num_steps, lam, trace_len, alpha, discount_factor, epsilon, num_learners, seed, q0):
+    if not 1 <= int(trace_len) <= _lib.LAMBDA_MAX:
+        raise ValueError('trace_len must lie in 1 .. {}'.format(_lib.LAMBDA_MAX))
+    if not 0.0 <= float(lam) <= 1.0:
+        raise ValueError('lam must lie in [0, 1]')
+    if int(num_learners) < 1:
+        raise ValueError('num_learners must be at least 1')
+    if not 0.0 <= float(epsilon) <= 1.0:
+        raise ValueError('epsilon must lie in [0, 1]')
+    # a step costs up to trace_len entry updates, so launches get shorter as traces get longer; consecutive launches of one method
+    # and trace_len carry the window, so chunking changes nothing
+    chunk = min(_CHUNK, _CHUNK * 4 // int(trace_len))
+    return _learn(env, num_learners, seed, q0, num_steps, chunk,
+                  lambda vec, T: vec.lambda_run(T, lam, trace_len, method, alpha, discount_factor, epsilon))
+
+
+def sarsa_lambda(env, num_steps, lam=0.9, trace_len=32, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):
+    """Epsilon-greedy SARSA(lambda) with replacing eligibility traces (Sutton & Barto ch. 12), each trace truncated after
+    `trace_len` (1 .. 64) steps, `num_steps` env steps per learner.  Returns Q float64[S][4], or [L][S][4] for L = num_learners > 1.
+    With lam = 0 or trace_len = 1 it is `sarsa`."""
+    return _lambda('sarsa', env, num_steps, lam, trace_len, alpha, discount_factor, epsilon, num_learners, seed, q0)
+
+
+def watkins_q_lambda(env, num_steps, lam=0.9, trace_len=32, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0,
+                     q0=0.0):
+    """Epsilon-greedy Watkins's Q(lambda): as `sarsa_lambda`, bootstrapping on max Q[s'], and a non-greedy action cuts the traces
+    of the pairs before it.  With lam = 0 or trace_len = 1 it is `q_learning`."""
+    return _lambda('q_learning', env, num_steps, lam, trace_len, alpha, discount_factor, epsilon, num_learners, seed, q0)
 
 
 def greedy_policy(q, env):

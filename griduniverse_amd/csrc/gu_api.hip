@@ -16,6 +16,7 @@
 
 static void gu_dyna_free(gu_engine *h);  // (tabular Dyna-Q, below)
 static void gu_nstep_free(gu_engine *h);  // (tabular n-step learners, below)
+static void gu_lambda_free(gu_engine *h); // (tabular lambda learners, below)
 static void gu_ac_free(gu_engine *h);     // (tabular actor-critic, below)
 
 // ---------------------------------------------------------------------------------- errors
@@ -174,7 +175,7 @@ int gu_destroy(gu_handle h)
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
                     h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next,
-                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_ac_h, h->d_ac_v};
+                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_lambda_w, h->d_ac_h, h->d_ac_v};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -250,6 +251,7 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
         h->d_td_next = nullptr;
         h->td_S = 0;
         gu_nstep_free(h);
+        gu_lambda_free(h);
     }
     if (h->dyna_S && h->dyna_S != W * H) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
     if (h->ac_S && h->ac_S != W * H) gu_ac_free(h);  // ... and actor-critic tables: gu_ac_init again
@@ -1112,8 +1114,8 @@ int gu_read_stats(gu_handle h, int64_t *reward_sum, int32_t *episodes)
     return GU_OK;
 }
 
-// ---------------------------------------------------------------------------------- tabular TD control, Dyna-Q and n-step learners
-// (gu_td.hip, gu_dyna.hip, gu_nstep.hip; their shared core is gu_tabular.hpp)
+// ---------------------------------------------------------------------------------- tabular TD control, Dyna-Q, n-step and lambda learners
+// (gu_td.hip, gu_dyna.hip, gu_nstep.hip, gu_lambda.hip; their shared core is gu_tabular.hpp)
 
 // tables of `bytes` for the engine's envs: what is left has to hold the trajectory buffer and the scratch of other calls too, so
 // keep 1 GiB of headroom
@@ -1355,6 +1357,51 @@ int gu_nstep_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32
         }
     if (count)
         for (int64_t e = 0; e < n; ++e) count[e] = c[e];
+    return GU_OK;
+}
+
+static void gu_lambda_free(gu_engine *h)
+{
+    if (h->d_lambda_w) (void)hipFree(h->d_lambda_w);
+    h->d_lambda_w = nullptr;
+    h->lambda_key = 0;
+}
+
+int gu_lambda_run(gu_handle h, int64_t T, int32_t method, int32_t K, double alpha, double gamma, double lambda, uint32_t eps_q16,
+                  uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Watkins's Q(lambda), 1 = SARSA(lambda)", method);
+    GU_REQUIRE(K >= 1 && K <= GU_LAMBDA_MAX, GU_ERR_INVALID, "K %d out of range (1 .. %d)", K, GU_LAMBDA_MAX);
+    GU_REQUIRE(lambda >= 0.0 && lambda <= 1.0, GU_ERR_INVALID, "lambda %g outside [0, 1]", lambda);
+    int rc = gu_tabular_check(h, "gu_lambda_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    if (!h->d_lambda_w) {
+        const size_t slots = (size_t)h->N * GU_LAMBDA_MAX;
+        GU_HIP(hipStreamSynchronize(h->stream));
+        rc = gu_tabular_fits(h, slots * sizeof(int32_t), "trace windows");
+        if (rc != GU_OK) return rc;
+        GU_HIP(hipMalloc(&h->d_lambda_w, slots * sizeof(int32_t)));
+        h->lambda_key = 0;
+    }
+    return gu_launch_lambda(h, T, method, K, alpha, gamma, lambda, eps_q16, flags);
+}
+
+int gu_lambda_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    int rc = gu_env_range(h, env0, n);
+    if (rc != GU_OK) return rc;
+    GU_REQUIRE(sa != nullptr || n == 0, GU_ERR_INVALID, "sa is NULL");
+    const int32_t K = h->lambda_key ? (h->lambda_key - 1) / 2 : 0;  // (gu_lambda_key; 0: the window was dropped)
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n && K)
+        GU_HIP(hipMemcpy(sa, h->d_lambda_w + (size_t)env0 * GU_LAMBDA_MAX, (size_t)n * GU_LAMBDA_MAX * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int64_t e = 0; e < n; ++e)  // (a dropped window reads as empty, whatever the device copy still holds; ages >= K are not written)
+        for (int32_t j = K; j < GU_LAMBDA_MAX; ++j) sa[(size_t)e * GU_LAMBDA_MAX + j] = -1;
     return GU_OK;
 }
 

@@ -267,6 +267,9 @@ struct gu_engine {
     int32_t *d_nstep_r = nullptr;    // [N][GU_NSTEP_MAX] their rewards
     int32_t *d_nstep_cnt = nullptr;  // [N] entries of the window
     int32_t nstep_key = 0;           // gu_nstep_key of the last call that touched the envs if it was a gu_nstep_run, else 0 (window dropped)
+    // batched tabular SARSA(lambda) / Watkins's Q(lambda) (gu_lambda.hip): learns into d_q; the window is allocated on first use
+    int32_t *d_lambda_w = nullptr;  // [N][GU_LAMBDA_MAX] the trace window, index = age (-1: none)
+    int32_t lambda_key = 0;         // gu_lambda_key of the last call that touched the envs if it was a gu_lambda_run, else 0 (window dropped)
     // batched tabular softmax actor-critic (gu_ac.hip): off until gu_ac_init; tables of its own, not d_q
     double *d_ac_h = nullptr;  // [N][ac_S][4] preferences
     double *d_ac_v = nullptr;  // [N][ac_S] state values
@@ -422,16 +425,23 @@ int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, double gamm
 static inline int32_t gu_nstep_key(int32_t method, int32_t n) { return 1 + method + 2 * n; }
 int gu_launch_nstep(gu_engine *h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 
+// ---- batched tabular SARSA(lambda) / Watkins's Q(lambda) (gu_lambda.hip) ----------------
+// the carry key of a gu_lambda_run (never 0): the next launch keeps the window only under the same method and K
+static inline int32_t gu_lambda_key(int32_t method, int32_t K) { return 1 + method + 2 * K; }
+int gu_launch_lambda(gu_engine *h, int64_t T, int32_t method, int32_t K, double alpha, double gamma, double lambda, uint32_t eps_q16,
+                     uint32_t flags);
+
 // ---- batched tabular softmax actor-critic (gu_ac.hip) ----------------------------------
 int gu_ac_fill(gu_engine *h, double h0, double v0);  // every preference = h0, every value = v0 (async)
 int gu_launch_ac(gu_engine *h, int64_t T, double alpha_actor, double alpha_critic, double gamma, uint32_t flags);
 
 // every call that touches the envs other than the learner launches ends what the learners carry from one launch to the next:
-// gu_td_run's SARSA action and gu_nstep_run's window (its pending updates are discarded, not flushed)
+// gu_td_run's SARSA action, gu_nstep_run's window (its pending updates are discarded, not flushed) and gu_lambda_run's window
 static inline void gu_tabular_drop_carry(gu_engine *h)
 {
     h->td_carry = false;
     h->nstep_key = 0;
+    h->lambda_key = 0;
 }
 
 // ---- agent trail (gu_trail.hip): no-ops while the trail is off ----------------------

@@ -1,5 +1,5 @@
 // gu_tabular.hpp -- the core of the batched tabular learners for gfx950 (gu_td.hip: Q-learning and SARSA; gu_dyna.hip: Dyna-Q;
-// gu_nstep.hip: n-step Q-learning and SARSA).
+// gu_nstep.hip: n-step Q-learning and SARSA; gu_lambda.hip: SARSA(lambda) and Watkins's Q(lambda)).
 // N independent learners, learner e owns env e and its own float64 table Q_e[S][4], advanced T real steps per launch.  The
 // semantics are build-defined (the reference has no tabular code) and stated in include/gu.h (gu_td_run, gu_dyna_run, gu_nstep_run).
 //
@@ -244,15 +244,19 @@ static inline void gu_tabular_args(gu_engine *h, TabArgs &a, int64_t T, double a
     a.gs = gu_grid_sel(h);
 }
 
-// launch the LDS instantiation where every block uses one grid whose planes fit, else the L2 one
+// launch the LDS instantiation where every block uses one grid whose planes fit, else the L2 one; blocks of at most `bs` lanes,
+// and `lane_lds` bytes of dynamic LDS per lane after the planes (gu_lambda.hip's ring; none for the other learners)
 template <class A>
-static int gu_tabular_launch(gu_engine *h, void (*lds)(A), void (*l2)(A), const A &a)
+static int gu_tabular_launch(gu_engine *h, void (*lds)(A), void (*l2)(A), const A &a, int bs = GU_BLOCK, size_t lane_lds = 0)
 {
-    const int lds_bs = gu_lds_block(h, GU_BLOCK, 2);
-    if (lds_bs)
-        hipLaunchKernelGGL(lds, dim3(gu_blocks(h->N, lds_bs)), dim3(lds_bs), 2 * (size_t)h->cell_bytes, h->stream, a);
-    else
-        hipLaunchKernelGGL(l2, dim3(gu_blocks(h->N, GU_BLOCK)), dim3(GU_BLOCK), 0, h->stream, a);
+    const int lds_bs = gu_lds_block(h, bs, 2);
+    if (lds_bs) {
+        const size_t bytes = 2 * (size_t)h->cell_bytes + lane_lds * (size_t)lds_bs;
+        if (bytes > 64 * 1024) GU_HIP(hipFuncSetAttribute((const void *)lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+        hipLaunchKernelGGL(lds, dim3(gu_blocks(h->N, lds_bs)), dim3(lds_bs), bytes, h->stream, a);
+    } else {
+        hipLaunchKernelGGL(l2, dim3(gu_blocks(h->N, bs)), dim3(bs), lane_lds * (size_t)bs, h->stream, a);
+    }
     GU_HIP(hipGetLastError());
     return GU_OK;
 }

@@ -378,6 +378,22 @@ class Engine(object):
         check(self.lib.gu_nstep_get_window(self._h, int(env0), n, ptr(out['sa']), ptr(out['reward']), ptr(out['count'])))
         return out
 
+    # ------------------------------------------------------------------ tabular SARSA(lambda) / Watkins's Q(lambda) (include/gu.h: gu_lambda_*)
+    def lambda_run(self, T, method='sarsa', K=32, lam=0.9, alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
+        """T iterations of SARSA(lambda) ('sarsa') / Watkins's Q(lambda) ('q_learning') per env in one launch, into the td_init
+        tables: replacing traces, truncated after K (1 .. LAMBDA_MAX) steps.  The trace window carries into the next lambda_run of
+        the same method and K; any other call in between drops it.  Rows and statistics as td_run()."""
+        check(self.lib.gu_lambda_run(self._h, int(T), _TD_METHODS[method], int(K), float(alpha), float(gamma), float(lam),
+                                     int(eps_q16), _learner_flags(trajectory, stats)))
+
+    def lambda_get_window(self, env0=0, n=None):
+        """int32[n, LAMBDA_MAX]: the trace windows of envs env0 .. env0+n-1, index = age (the pair s*4+a, -1 for none; all -1
+        once dropped)."""
+        n = self.N - int(env0) if n is None else int(n)
+        sa = np.empty((max(n, 0), _lib.LAMBDA_MAX), np.int32)
+        check(self.lib.gu_lambda_get_window(self._h, int(env0), n, ptr(sa)))
+        return sa
+
     # ------------------------------------------------------------------ tabular softmax actor-critic (include/gu.h: gu_ac_*)
     def ac_init(self, h0=0.0, v0=0.0):
         """One float64 preference table [S][4] (every entry h0) and one value table [S] (every entry v0) per env."""

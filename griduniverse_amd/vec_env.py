@@ -180,6 +180,23 @@ class VecGridUniverse(object):
         """The n-step windows of envs env0 .. env0+n-1 (Engine.nstep_get_window)."""
         return self.engine.nstep_get_window(env0, n)
 
+    def lambda_run(self, T, lam=0.9, trace_len=32, method='sarsa', alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False,
+                   stats=False):
+        """T iterations of batched tabular SARSA(lambda) ('sarsa') or Watkins's Q(lambda) ('q_learning'): env e learns its own Q
+        table [S][4] with replacing eligibility traces, truncated after `trace_len` (1 .. 64) steps (include/gu.h: gu_lambda_run).
+        The first call gives every env a table of zeros.  Consecutive calls with the same method and trace_len carry the trace
+        window; any other call in between drops it.  Rows and statistics as td_run()."""
+        self._ensure_q()
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.lambda_run(T, method, trace_len, lam, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory,
+                               stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def lambda_window(self, env0=0, n=None):
+        """The trace windows of envs env0 .. env0+n-1 (Engine.lambda_get_window): int32[n, 64], index = age."""
+        return self.engine.lambda_get_window(env0, n)
+
     def _ensure_ac(self, h0=None, v0=None):
         """Actor-critic tables on the engine: zeros on first use; every entry h0 / v0 (again) when either is given."""
         if h0 is not None or v0 is not None or not self._ac_ready:

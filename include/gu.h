@@ -339,6 +339,43 @@ int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32
 int gu_nstep_run(gu_handle h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 int gu_nstep_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count);
 
+/* ---- batched tabular SARSA(lambda) and Watkins's Q(lambda): learner e owns env e and its table Q_e[S][4] (the gu_td_* tables) ----
+ * (build-defined: the reference lists "Temporal Difference (TD) Learning with variations" on its roadmap and ships no code;
+ * Sutton & Barto ch. 12, backward view with REPLACING traces truncated after K steps; tests/_lambda_oracle.py is the CPU
+ * restatement.)  Learner e keeps a TRACE WINDOW W_e[j], j = 0 .. GU_LAMBDA_MAX-1: the pair s*4+a whose trace has age j, or -1.
+ * The pairs of a window are distinct; between iterations W_e[0] = -1 and W_e[j] = -1 for every j >= K.
+ * Coefficients, float64, one rounding per operation: c = gamma * lambda, P_0 = 1.0, P_j = P_{j-1} * c.
+ * One iteration of gu_lambda_run for env e at 64-bit step count t:
+ *   1. lazy auto-reset, exactly as rule 1 of gu_td_run (the window is empty here: see 6);
+ *   2. action: as rule 2 of gu_td_run.  SARSA(lambda) takes its carried a' instead, under the same conditions as gu_td_run's SARSA
+ *      (the carry across launches is the window's, below).  Watkins's Q(lambda) only: if Q_e[s][a] == max Q_e[s] (folded left to
+ *      right with `>`, over the row the action was chosen from) is false, the window is emptied first;
+ *   3. (s', r, d) by the engine's move rule; t += 1;
+ *   4. m = max Q_e[s'] (Q(lambda)) or Q_e[s'][a'] with a' drawn at s' by rule 2 from the word of the new t and the pre-update row
+ *      (SARSA(lambda); not drawn when d); target = r if d else r + gamma * m; delta = target - Q_e[s][a]; g = alpha * delta;
+ *   5. if (s, a) is in the window, that entry is removed; W_e[0] = s*4+a.  For every j < K with W_e[j] >= 0 and P_j != 0:
+ *      Q_e[p] = Q_e[p] + g * P_j, p = W_e[j] (distinct pairs: the order does not matter);
+ *   6. if d the window is emptied; else every entry ages by one (W_e[j+1] = W_e[j], j = K-2 .. 0; W_e[0] = -1; age K-1 drops out);
+ *   7. the next iteration chooses from the table after this iteration's updates (a wall bump and window pairs in the row of s'
+ *      included).
+ * With K = 1 (any lambda) or lambda = 0 (any K) this is gu_td_run, byte for byte: method 0 is Q-learning, 1 is SARSA.
+ * CARRY: the window and SARSA's a' persist from one gu_lambda_run to the next when the later call directly follows the earlier one
+ * with the same method and K (alpha, gamma and lambda may change: the ages carry, the new c applies).  Any other call in between --
+ * everything that ends gu_td_run's SARSA carry, gu_td_run, gu_dyna_run, gu_nstep_run, gu_ac_run, a gu_lambda_run with another
+ * method or K -- drops both.  gu_lambda_run ends gu_td_run's SARSA carry and gu_nstep_run's window.
+ * gu_lambda_run        : T iterations per env in ONE launch (async).  method 0 = Watkins's Q(lambda), 1 = SARSA(lambda); 1 <= K
+ *                        <= GU_LAMBDA_MAX; 0 <= lambda <= 1.  GU_ERR_STATE before gu_td_init; GU_ERR_INVALID for a bad method,
+ *                        K or lambda (NaN included) and everything gu_td_run rejects.  The window storage (N * 256 bytes) is
+ *                        allocated on first use (GU_ERR_NOMEM under gu_td_init's free-memory rule); a grid of another size drops
+ *                        it with the tables.  T = 0 changes nothing.  Flags, rows and statistics as gu_td_run.  The step counts
+ *                        advance by T.
+ * gu_lambda_get_window : the windows of envs env0 .. env0+n-1 on the host as sa[n][GU_LAMBDA_MAX], index = age; -1 everywhere once
+ *                        the window has been dropped. */
+#define GU_LAMBDA_MAX 64
+int gu_lambda_run(gu_handle h, int64_t T, int32_t method, int32_t K, double alpha, double gamma, double lambda, uint32_t eps_q16,
+                  uint32_t flags);
+int gu_lambda_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa);
+
 /* ---- batched tabular one-step actor-critic with a softmax policy: learner e owns env e, preferences H_e[S][4] and values V_e[S] ----
  * (build-defined: the reference lists "Policy Gradients (MC Policy Gradients and Actor-critic)" on its roadmap and ships no code;
  * Sutton & Barto 13.5; tests/_ac_oracle.py is the CPU restatement.)  The tables are float64 and the learner's own, not the
