@@ -18,6 +18,7 @@ static void gu_dyna_free(gu_engine *h);  // (tabular Dyna-Q, below)
 static void gu_nstep_free(gu_engine *h);  // (tabular n-step learners, below)
 static void gu_lambda_free(gu_engine *h); // (tabular lambda learners, below)
 static void gu_ac_free(gu_engine *h);     // (tabular actor-critic, below)
+static void gu_reinforce_free(gu_engine *h);  // (tabular REINFORCE, below)
 
 // ---------------------------------------------------------------------------------- errors
 static thread_local std::string g_last_error;
@@ -175,7 +176,7 @@ int gu_destroy(gu_handle h)
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
                     h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next,
-                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_lambda_w, h->d_ac_h, h->d_ac_v};
+                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_lambda_w, h->d_ac_h, h->d_ac_v, h->d_rf_buf, h->d_rf_cnt};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -1412,6 +1413,7 @@ static void gu_ac_free(gu_engine *h)
     h->d_ac_h = nullptr;
     h->d_ac_v = nullptr;
     h->ac_S = 0;
+    gu_reinforce_free(h);
 }
 
 int gu_ac_init(gu_handle h, double h0, double v0)
@@ -1481,6 +1483,63 @@ int gu_ac_set(gu_handle h, int64_t env0, int64_t n, const double *pref, const do
     GU_HIP(hipStreamSynchronize(h->stream));
     if (n && pref) GU_HIP(hipMemcpy(h->d_ac_h + (size_t)env0 * S * 4, pref, 4 * k * sizeof(double), hipMemcpyHostToDevice));
     if (n && v) GU_HIP(hipMemcpy(h->d_ac_v + (size_t)env0 * S, v, k * sizeof(double), hipMemcpyHostToDevice));
+    return GU_OK;
+}
+
+static void gu_reinforce_free(gu_engine *h)
+{
+    if (h->d_rf_buf) (void)hipFree(h->d_rf_buf);
+    if (h->d_rf_cnt) (void)hipFree(h->d_rf_cnt);
+    h->d_rf_buf = nullptr;
+    h->d_rf_cnt = nullptr;
+    h->rf_cap = 0;
+    h->rf_key = 0;
+}
+
+int gu_reinforce_run(gu_handle h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_ac_h && h->ac_S == h->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first");
+    GU_REQUIRE(L >= 1 && L <= GU_REINFORCE_MAX, GU_ERR_INVALID, "L %d out of range (1 .. %d)", L, GU_REINFORCE_MAX);
+    GU_REQUIRE(std::isfinite(alpha_baseline), GU_ERR_INVALID, "alpha_baseline must be finite");
+    int rc = gu_tabular_check(h, "gu_reinforce_run", T, -1, 0u, alpha_actor, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    if (h->rf_cap < L) {  // (a call with another L drops the buffer anyway: nothing to keep)
+        const size_t slots = (size_t)h->N * (size_t)L;
+        GU_HIP(hipStreamSynchronize(h->stream));
+        rc = gu_tabular_fits(h, slots * 2 * sizeof(int32_t) + (size_t)h->N * sizeof(int32_t), "episode buffers");
+        if (rc != GU_OK) return rc;
+        gu_reinforce_free(h);
+        GU_HIP(hipMalloc(&h->d_rf_buf, slots * 2 * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_rf_cnt, (size_t)h->N * sizeof(int32_t)));
+        h->rf_cap = L;
+    }
+    return gu_launch_reinforce(h, T, L, alpha_actor, alpha_baseline, gamma, flags);
+}
+
+int gu_reinforce_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    int rc = gu_env_range(h, env0, n);
+    if (rc != GU_OK) return rc;
+    const int32_t L = h->rf_key;  // (0: the buffer was dropped and reads as empty, whatever the device copy still holds)
+    std::vector<int32_t> c(n), w((size_t)n * (size_t)L * 2);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n && L) {
+        GU_HIP(hipMemcpy(c.data(), h->d_rf_cnt + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        GU_HIP(hipMemcpy2D(w.data(), (size_t)n * 8, h->d_rf_buf + (size_t)env0 * 2, (size_t)h->N * 8, (size_t)n * 8, (size_t)L,
+                           hipMemcpyDeviceToHost));  // rows k = 0 .. L-1 of [L][N], columns env0 .. env0+n-1
+    }
+    for (int64_t e = 0; e < n; ++e)
+        for (int32_t j = 0; j < GU_REINFORCE_MAX; ++j) {
+            const size_t i = (size_t)e * GU_REINFORCE_MAX + j, b = ((size_t)j * n + e) * 2;
+            if (sa) sa[i] = j < c[e] ? w[b] : -1;
+            if (reward) reward[i] = j < c[e] ? w[b + 1] : 0;
+        }
+    if (count)
+        for (int64_t e = 0; e < n; ++e) count[e] = c[e];
     return GU_OK;
 }
 

@@ -274,6 +274,11 @@ struct gu_engine {
     double *d_ac_h = nullptr;  // [N][ac_S][4] preferences
     double *d_ac_v = nullptr;  // [N][ac_S] state values
     int32_t ac_S = 0;          // states of the tables (0: none allocated); a grid of another size drops them
+    // batched tabular REINFORCE with baseline (gu_reinforce.hip): learns into d_ac_h / d_ac_v; the buffers are allocated on first use
+    int32_t *d_rf_buf = nullptr;  // [rf_cap][N] the episode buffers, step-major, oldest first: 8-byte entries {s*4+a, r}
+    int32_t *d_rf_cnt = nullptr;  // [N] their entries
+    int32_t rf_cap = 0;           // entries per env the storage holds (0: none allocated)
+    int32_t rf_key = 0;           // L of the last call that touched the envs if it was a gu_reinforce_run, else 0 (buffer dropped)
     // batched tabular Dyna-Q (gu_dyna.hip): off until gu_dyna_init; learns into d_q
     uint64_t *d_dyna_model = nullptr;  // [N][dyna_S*4] one packed word per (s, a): reward | (s' | done << 31) << 32; ~0 = unobserved
     int32_t *d_dyna_list = nullptr;    // [N][dyna_S*4] observed pairs s*4+a in the order of first observation (-1 beyond count)
@@ -435,13 +440,18 @@ int gu_launch_lambda(gu_engine *h, int64_t T, int32_t method, int32_t K, double 
 int gu_ac_fill(gu_engine *h, double h0, double v0);  // every preference = h0, every value = v0 (async)
 int gu_launch_ac(gu_engine *h, int64_t T, double alpha_actor, double alpha_critic, double gamma, uint32_t flags);
 
+// ---- batched tabular REINFORCE with baseline (gu_reinforce.hip) ------------------------
+int gu_launch_reinforce(gu_engine *h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags);
+
 // every call that touches the envs other than the learner launches ends what the learners carry from one launch to the next:
-// gu_td_run's SARSA action, gu_nstep_run's window (its pending updates are discarded, not flushed) and gu_lambda_run's window
+// gu_td_run's SARSA action, gu_nstep_run's window (its pending updates are discarded, not flushed), gu_lambda_run's window and
+// gu_reinforce_run's episode buffer (its pending transitions are discarded, not learned from)
 static inline void gu_tabular_drop_carry(gu_engine *h)
 {
     h->td_carry = false;
     h->nstep_key = 0;
     h->lambda_key = 0;
+    h->rf_key = 0;
 }
 
 // ---- agent trail (gu_trail.hip): no-ops while the trail is off ----------------------

@@ -435,6 +435,24 @@ class Engine(object):
             raise ValueError('give h, v or both')
         check(self.lib.gu_ac_set(self._h, int(env0), n, ptr(h) if h is not None else None, ptr(v) if v is not None else None))
 
+    # ------------------------------------------------------------------ tabular REINFORCE with baseline (include/gu.h: gu_reinforce_*)
+    def reinforce_run(self, T, L=256, alpha_actor=0.003, alpha_baseline=0.1, gamma=0.99, trajectory=False, stats=False):
+        """T iterations of REINFORCE with baseline per env in one launch, into the ac_init tables: the backward pass over a
+        segment runs when its episode ends or after L (1 .. REINFORCE_MAX) steps.  The episode buffer carries into the next
+        reinforce_run with the same L; any other call in between drops it.  Rows and statistics as td_run()."""
+        check(self.lib.gu_reinforce_run(self._h, int(T), int(L), float(alpha_actor), float(alpha_baseline), float(gamma),
+                                        _learner_flags(trajectory, stats)))
+
+    def reinforce_get_episode(self, env0=0, n=None):
+        """The episode buffers of envs env0 .. env0+n-1: dict sa / reward int32[n, REINFORCE_MAX] (pending s*4+a and r, oldest
+        first; -1 / 0 beyond count) and count int32[n] (0 once dropped)."""
+        n = self.N - int(env0) if n is None else int(n)
+        n0 = max(n, 0)
+        out = dict(sa=np.empty((n0, _lib.REINFORCE_MAX), np.int32), reward=np.empty((n0, _lib.REINFORCE_MAX), np.int32),
+                   count=np.empty(n0, np.int32))
+        check(self.lib.gu_reinforce_get_episode(self._h, int(env0), n, ptr(out['sa']), ptr(out['reward']), ptr(out['count'])))
+        return out
+
     # ------------------------------------------------------------------ state
     def get_state(self):
         pos, don = np.empty(self.N, np.int32), np.empty(self.N, np.int32)

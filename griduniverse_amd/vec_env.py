@@ -213,6 +213,24 @@ class VecGridUniverse(object):
         self.engine.ac_run(T, actor_lr, critic_lr, discount_factor, trajectory, stats)
         return self._learner_out(T, trajectory, stats)
 
+    def reinforce_run(self, T, max_episode_len=256, actor_lr=0.003, baseline_lr=0.1, discount_factor=0.99, trajectory=False,
+                      stats=False):
+        """T iterations of batched tabular REINFORCE with baseline (Monte-Carlo policy gradient): env e acts on the softmax of
+        its own preferences [S][4] and learns them, and its state values [S] as the baseline, from whole-episode returns in a
+        backward pass when its episode ends; an episode still running after `max_episode_len` (1 .. 1024) steps is cut there and
+        its return bootstraps on the baseline (include/gu.h: gu_reinforce_run).  The tables are actor_critic_run's; the first
+        call gives every env tables of zeros.  Consecutive calls with the same max_episode_len carry the episode buffer; any
+        other call in between drops it.  Returns a dict like td_run()."""
+        self._ensure_ac()
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.reinforce_run(T, max_episode_len, actor_lr, baseline_lr, discount_factor, trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def episode_buffer(self, env0=0, n=None):
+        """The episode buffers of envs env0 .. env0+n-1 (Engine.reinforce_get_episode)."""
+        return self.engine.reinforce_get_episode(env0, n)
+
     def preferences(self, env0=0, n=None):
         """float64[n, S, 4]: the actor's preference tables of envs env0 .. env0+n-1 (to the end when n is None)."""
         self._ensure_ac()

@@ -412,6 +412,45 @@ int gu_ac_run(gu_handle h, int64_t T, double alpha_actor, double alpha_critic, d
 int gu_ac_get(gu_handle h, int64_t env0, int64_t n, double *pref, double *v);
 int gu_ac_set(gu_handle h, int64_t env0, int64_t n, const double *pref, const double *v);
 
+/* ---- batched tabular REINFORCE with baseline (Monte-Carlo policy gradient): learner e owns env e and the gu_ac_* tables ----
+ * (build-defined: the first half of the reference's roadmap entry "Policy Gradients (MC Policy Gradients and Actor-critic)", for
+ * which it ships no code; Sutton & Barto 13.3/13.4; tests/_reinforce_oracle.py is the CPU restatement.)  The preferences H_e are
+ * the actor, the values V_e the baseline.  Learner e also keeps an EPISODE BUFFER E_e: the transitions (s_k, a_k, r_k) of its
+ * current segment, oldest first, at most L-1 of them between iterations.  All arithmetic is float64 with one rounding per
+ * operation; gu_exp and the softmax exactly as rule 2 of gu_ac_run.
+ * One iteration of gu_reinforce_run for env e at 64-bit step count t:
+ *   1. reset: lazy auto-reset, exactly as rule 1 of gu_td_run (the buffer is empty here: see 5);
+ *   2. policy and action: rules 2 and 3 of gu_ac_run on H_e[s] as it is now (the stream-4 word at t).  The tables change only in
+ *      rule 5, so inside a segment the policy is fixed;
+ *   3. (s', r, d) by the engine's move rule (absorbing terminal); t += 1; append (s, a, r) to E_e;
+ *   4. if not d and E_e holds fewer than L entries: the iteration ends here;
+ *   5. segment end (d, or E_e holds L entries): G = 0.0 if d, else V_e[s'] read before any write of this pass (a truncated
+ *      segment bootstraps on the baseline; the env is NOT reset and goes on from s').  Then for every entry, newest to oldest:
+ *        G = r_k + gamma * G; delta = G - V_e[s_k]; V_e[s_k] = V_e[s_k] + alpha_baseline * delta;
+ *        pi = the softmax (rule 2 of gu_ac_run) of H_e[s_k] as it is now -- earlier updates of this pass included: a repeated
+ *        state compounds; g = alpha_actor * delta; H_e[s_k][b] = H_e[s_k][b] + g * ([b == a_k] - pi_b) for b = 0..3.
+ *      There is no gamma^k factor, as in rule 7 of gu_ac_run.  E_e ends empty;
+ *   6. the next iteration sees the tables after the pass.
+ * With alpha_baseline = 0 and V = 0 this is plain REINFORCE.  With L = 1 it is gu_ac_run, byte for byte.
+ * CARRY: the buffer persists from one gu_reinforce_run to the next when the later call directly follows the earlier one with the
+ * same L (the rates and gamma may change).  Any other call in between -- everything that drops gu_lambda_run's window, and
+ * gu_td_run, gu_dyna_run, gu_nstep_run, gu_lambda_run, gu_ac_run, gu_ac_init, gu_ac_set, a gu_reinforce_run with another L --
+ * drops it: the pending transitions are discarded, not learned from.  gu_reinforce_run ends gu_td_run's SARSA carry and the
+ * windows of gu_nstep_run and gu_lambda_run.
+ * gu_reinforce_run         : T iterations per env in ONE launch (async).  1 <= L <= GU_REINFORCE_MAX.  GU_ERR_STATE before
+ *                            gu_ac_init; GU_ERR_INVALID for a bad L, non-finite rates or gamma, T < 0 or T > 1e8, flags other
+ *                            than GU_F_TRAJECTORY | GU_F_STATS.  The buffer storage (N * (8 L + 4) bytes) is allocated on first
+ *                            use for the L of the call, and again for a larger one (GU_ERR_NOMEM under gu_td_init's free-memory
+ *                            rule); a grid of another size drops it with the tables.  T = 0 changes nothing.  Rows, statistics,
+ *                            the trajectory reservation and the agent trail as gu_ac_run: the T real steps only.  The step
+ *                            counts advance by T.
+ * gu_reinforce_get_episode : the buffers of envs env0 .. env0+n-1 on the host: sa (s*4+a) and reward as [n][GU_REINFORCE_MAX],
+ *                            oldest first, (-1, 0) beyond count; count as [n], 0 when the buffer has been dropped.  Any pointer
+ *                            may be NULL. */
+#define GU_REINFORCE_MAX 1024
+int gu_reinforce_run(gu_handle h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags);
+int gu_reinforce_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count);
+
 /* ---- look_step_ahead table queries: env:136-155 for n (state, action) pairs (grid 0 of a multi-grid engine) ---- */
 int gu_look_step_ahead(gu_handle h, int64_t n, const int32_t *states, const int32_t *actions,
                        int32_t care_about_terminal, int32_t *next, int32_t *reward, int32_t *done);

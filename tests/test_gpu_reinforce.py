@@ -1,0 +1,392 @@
+"""Batched tabular REINFORCE with baseline on the device (gu_reinforce_run, csrc/gu_reinforce.hip) against the CPU restatement
+tests/_reinforce_oracle.py: preferences, values, trajectory rows, statistics, env state and the episode buffers compared byte for
+byte; against gu_ac_run at L = 1; plus one check of the baseline that does not depend on the restatement."""
+import numpy as np
+import pytest
+
+import griduniverse_amd as gua
+from griduniverse_amd import _lib
+from griduniverse_amd.algorithms import utils
+from griduniverse_amd.algorithms.policy_gradient import reinforce
+from griduniverse_amd.engine import Engine
+from oracle import c_oracle as C
+
+from . import _lambda_oracle as LO
+from . import _nstep_oracle as NO
+from . import _reinforce_oracle as RO
+from . import _td_oracle as O
+from ._tabular_cases import GRIDS, _eps, _grid, _random_grids, _same, _spec
+
+pytestmark = pytest.mark.gpu
+
+
+def _open(W, H):
+    return dict(W=W, H=H, starts=[0], goals=[W * H - 1], lava=[], walls=[])
+
+
+def _pair(g, N, seed, h0=0.0, v0=0.0):
+    vec = gua.VecGridUniverse(N, template=_spec(g), seed=seed)
+    vec._ensure_ac(h0, v0)
+    o = RO.ReinforceOracle(_grid(g), seed, N, h0=h0, v0=v0)
+    assert np.array_equal(vec.reset(), o.reset())
+    return vec, o
+
+
+def _same_tables(vec, o):
+    assert vec.preferences().tobytes() == o.h.tobytes()
+    assert vec.state_values().tobytes() == o.v.tobytes()
+
+
+def _same_buffer(vec, oracles):
+    buf = vec.episode_buffer()
+    assert buf['sa'].shape == (vec.engine.N, _lib.REINFORCE_MAX)
+    assert buf['count'].tobytes() == np.concatenate([o.buf_cnt for o in oracles]).tobytes()
+    assert buf['sa'].tobytes() == np.concatenate([o.buf_sa for o in oracles]).tobytes()
+    assert buf['reward'].tobytes() == np.concatenate([o.buf_r for o in oracles]).tobytes()
+
+
+def _same_state(vec, o):
+    st = vec.get_state()
+    assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'], o.state.done)
+    assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
+
+
+def _launch(vec, o, T, L, aa=0.05, ab=0.3, gamma=0.9):
+    got = vec.reinforce_run(T, L, actor_lr=aa, baseline_lr=ab, discount_factor=gamma, trajectory=True, stats=True)
+    _same(got, o.reinforce(T, L, aa, ab, gamma))
+    _same_tables(vec, o)
+    _same_buffer(vec, [o])
+
+
+# The first launch of each case: the first length from 151 (N = 63) / 37 (N = 4096) on at which, in the restatement, some lane
+# ends the launch on a terminal step and, for L > 1, some lane in the middle of a segment.  (grid, N) -> lengths for L = 1, 7, 64.
+_FIRST_T = {
+    ('default4x4', 63): (152, 151, 151), ('default4x4', 4096): (37, 37, 37),
+    ('lava32', 63): (151, 157, 151), ('lava32', 4096): (39, 39, 39),
+    ('maze11', 63): (223, 208, 249), ('maze11', 4096): (88, 88, 88),
+    ('open8x8', 63): (156, 156, 156), ('open8x8', 4096): (37, 37, 37),
+    ('test_env', 63): (152, 152, 151), ('test_env', 4096): (37, 37, 37),
+}
+
+
+@pytest.mark.parametrize('L', [1, 7, 64])
+@pytest.mark.parametrize('grid', sorted(GRIDS))
+@pytest.mark.parametrize('N', [63, 4096])
+def test_tables_rows_stats_state_and_buffer_equal_the_oracle(grid, N, L):
+    """Two launches.  The first ends with some lanes on a terminal step (_FIRST_T) and, for L > 1, some in the middle of a
+    segment; both are asserted on the restatement."""
+    g = GRIDS[grid]()
+    vec, o = _pair(g, N, 3, 0.5 if N == 63 else 0.0, -0.25 if N == 63 else 0.0)
+    try:
+        for launch, T in enumerate((_FIRST_T[grid, N][(1, 7, 64).index(L)], 151 if N < 4096 else 37)):
+            _launch(vec, o, T, L)
+            _same_state(vec, o)
+            if launch == 0:
+                assert (o.state.done != 0).any() and ((o.buf_cnt > 0).any() or L == 1)
+        assert o.h.any() and o.v.any()
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('grid', ['open8x8', 'maze11'])
+def test_segment_length_one_equals_actor_critic_run(grid):
+    """No restatement involved: L = 1 against gu_ac_run on a second engine."""
+    g = GRIDS[grid]()
+    a = gua.VecGridUniverse(1000, template=_spec(g), seed=11)
+    b = gua.VecGridUniverse(1000, template=_spec(g), seed=11)
+    try:
+        a._ensure_ac(0.5, -0.25)
+        b._ensure_ac(0.5, -0.25)
+        a.reset()
+        b.reset()
+        for T in (300, 211):
+            x = a.actor_critic_run(T, 0.3, 0.2, 0.95, trajectory=True, stats=True)
+            y = b.reinforce_run(T, 1, 0.3, 0.2, 0.95, trajectory=True, stats=True)
+            _same(x, y)
+            assert a.preferences().tobytes() == b.preferences().tobytes()
+            assert a.state_values().tobytes() == b.state_values().tobytes()
+            assert not b.episode_buffer()['count'].any()
+        assert a.preferences().any() and a.state_values().any()
+    finally:
+        a.close()
+        b.close()
+
+
+def test_one_launch_equals_two():
+    g = GRIDS['open8x8']()
+    a = gua.VecGridUniverse(1000, template=_spec(g), seed=11)
+    b = gua.VecGridUniverse(1000, template=_spec(g), seed=11)
+    try:
+        a.reset()
+        b.reset()
+        whole = a.reinforce_run(500, 64, 0.05, 0.2, 0.95, trajectory=True, stats=True)
+        p1 = b.reinforce_run(250, 64, 0.05, 0.2, 0.95, trajectory=True, stats=True)
+        assert b.episode_buffer()['count'].any()  # (something is carried)
+        p2 = b.reinforce_run(250, 64, 0.05, 0.2, 0.95, trajectory=True, stats=True)
+        for k in ('obs', 'reward', 'done'):
+            assert np.concatenate([p1[k], p2[k]]).tobytes() == whole[k].tobytes(), k
+        assert a.preferences().tobytes() == b.preferences().tobytes()
+        assert a.state_values().tobytes() == b.state_values().tobytes()
+        x, y = a.episode_buffer(), b.episode_buffer()
+        for k in x:
+            assert x[k].tobytes() == y[k].tobytes(), k
+    finally:
+        a.close()
+        b.close()
+
+
+def _shared(cls, o):
+    """A restatement of another learner on o's env state and Q tables."""
+    other = cls(o.grid, o.seed, o.n)
+    other.state, other.q = o.state, o.q
+    return other
+
+
+def _between_td(vec, o):
+    _same(vec.td_run(20, 'q_learning', 0.2, 0.9, 0.3, trajectory=True, stats=True), o.run(20, O.Q_LEARNING, 0.2, 0.9, _eps(0.3)))
+
+
+def _between_nstep(vec, o):
+    _same(vec.nstep_run(20, 3, 'q_learning', 0.2, 0.9, 0.3, trajectory=True, stats=True),
+          _shared(NO.NstepOracle, o).nstep(20, O.Q_LEARNING, 3, 0.2, 0.9, _eps(0.3)))
+    o.drop_buffer()
+
+
+def _between_lambda(vec, o):
+    _same(vec.lambda_run(20, 0.8, 8, 'q_learning', 0.2, 0.9, 0.3, trajectory=True, stats=True),
+          _shared(LO.LambdaOracle, o).lam(20, O.Q_LEARNING, 8, 0.8, 0.2, 0.9, _eps(0.3)))
+    o.drop_buffer()
+
+
+def _between_ac(vec, o):
+    _same(vec.actor_critic_run(20, 0.1, 0.2, 0.9, trajectory=True, stats=True), o.ac(20, 0.1, 0.2, 0.9))
+
+
+def _between_set(vec, o):
+    v = np.full((1, o.grid.S), 0.5)
+    vec.set_actor_critic(v=v, env0=5)
+    o.set_ac(v=v, env0=5)
+
+
+def _between_reset(vec, o):
+    mask = np.zeros(o.n, np.uint8)
+    mask[::7] = 1
+    assert np.array_equal(vec.reset(mask), o.reset(mask))
+
+
+def _between_other_len(vec, o):
+    _same(vec.reinforce_run(20, 16, 0.05, 0.3, 0.9, trajectory=True, stats=True), o.reinforce(20, 16, 0.05, 0.3, 0.9))
+
+
+@pytest.mark.parametrize('between', [_between_td, _between_nstep, _between_lambda, _between_ac, _between_set, _between_reset,
+                                     _between_other_len], ids=lambda f: f.__name__[9:])
+def test_another_call_in_between_drops_the_buffer(between):
+    """250 + another call + 250 against the restatement, which drops the buffer there: the pending transitions are not learned
+    from."""
+    g = GRIDS['open8x8']()
+    vec, o = _pair(g, 300, 13)
+    try:
+        vec._ensure_q(0.0)
+        _launch(vec, o, 250, 64)
+        assert o.buf_cnt.any()
+        between(vec, o)
+        if between is not _between_other_len:
+            assert not o.buf_cnt.any() and o.buf_L == 0
+            assert not vec.episode_buffer()['count'].any() and (vec.episode_buffer()['sa'] == -1).all()
+        else:
+            _same_buffer(vec, [o])
+        _launch(vec, o, 250, 64)
+        _same_state(vec, o)
+        assert vec.q_table().tobytes() == o.q.tobytes()
+    finally:
+        vec.close()
+
+
+def test_reinforce_run_drops_the_sarsa_carry_and_both_windows():
+    g = GRIDS['maze11']()
+    vec, o = _pair(g, 200, 9)
+    try:
+        vec._ensure_q(0.0)
+        _same(vec.td_run(40, 'sarsa', 0.2, 0.9, 0.3, trajectory=True, stats=True), o.run(40, O.SARSA, 0.2, 0.9, _eps(0.3)))
+        assert o.carry_valid
+        _launch(vec, o, 30, 7)
+        assert not o.carry_valid
+        _same(vec.td_run(40, 'sarsa', 0.2, 0.9, 0.3, trajectory=True, stats=True), o.run(40, O.SARSA, 0.2, 0.9, _eps(0.3)))
+        assert vec.q_table().tobytes() == o.q.tobytes()
+        _same_tables(vec, o)
+        vec.nstep_run(25, 4, 'sarsa', 0.2, 0.9, 0.3)
+        assert vec.nstep_window()['count'].any()
+        vec.reinforce_run(5, 7)
+        assert not vec.nstep_window()['count'].any()
+        vec.lambda_run(25, 0.9, 8, 'sarsa', 0.2, 0.9, 0.3)
+        assert (vec.lambda_window() >= 0).any()
+        vec.reinforce_run(5, 7)
+        assert (vec.lambda_window() == -1).all()
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('L', [3, 64])
+@pytest.mark.parametrize('W,H', [(2, 2), (4, 4)])
+def test_repeated_states_and_rewritten_rows_on_small_open_grids(W, H, L):
+    """Tiny grids: many wall bumps, states repeated inside a segment (the pass compounds), and with L = 3 truncations whose pass
+    rewrites the row of the state the lane stands in (the next step must act on the rewritten row)."""
+    vec, o = _pair(_open(W, H), 256, 7, 0.5, 1.0)
+    try:
+        for T in (123, 77):
+            _launch(vec, o, T, L, aa=0.2, ab=0.5, gamma=0.8)
+        _same_state(vec, o)
+    finally:
+        vec.close()
+
+
+def _group_launches(vec, oracles, runs):
+    assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+    for T, L in runs:
+        got = vec.reinforce_run(T, L, 0.05, 0.25, 0.9, trajectory=True, stats=True)
+        parts = [o.reinforce(T, L, 0.05, 0.25, 0.9) for o in oracles]
+        _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
+        _same_buffer(vec, oracles)
+    assert vec.preferences().tobytes() == np.concatenate([o.h for o in oracles]).tobytes()
+    assert vec.state_values().tobytes() == np.concatenate([o.v for o in oracles]).tobytes()
+
+
+@pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
+def test_multigrid_learners_equal_the_oracle(n_grids, N):
+    grids = _random_grids(n_grids, 9, 9, 17)
+    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
+    group = N // n_grids
+    oracles = [RO.ReinforceOracle(_grid(g), 6, group, env_id0=k * group) for k, g in enumerate(grids)]
+    try:
+        _group_launches(vec, oracles, [(150, 24), (91, 24)])
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('n_grids', [4, 256])
+def test_device_maze_learners_equal_the_oracle(n_grids):
+    N, W, H, maze_seed = 256, 11, 11, 31
+    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
+    group = N // n_grids
+    oracles = []
+    for k in range(n_grids):
+        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
+        oracles.append(RO.ReinforceOracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]),
+                                          2, group, env_id0=k * group))
+    try:
+        _group_launches(vec, oracles, [(120, 32), (80, 32)])
+    finally:
+        vec.close()
+
+
+def test_step_counts_across_the_epoch_boundary():
+    g = GRIDS['open8x8']()
+    N = 96
+    vec, o = _pair(g, N, 12)
+    try:
+        tc = np.full(N, 2 ** 32 - 100, np.uint64)
+        tc[::3] += 7  # per-env counts: envs cross the boundary at different steps
+        vec.set_state(tcount=tc)
+        o.set_state(tcount=tc)
+        for T in (130, 170):
+            _launch(vec, o, T, 24)
+        assert np.array_equal(vec.get_state()['tcount'], tc + np.uint64(300))
+    finally:
+        vec.close()
+
+
+def test_the_longest_segment():
+    """L = GU_REINFORCE_MAX on an open 32 x 32 grid (a random walk from one corner does not find the other in 1024 steps):
+    segments of 1024 steps, walked back in one pass."""
+    vec, o = _pair(_open(32, 32), 128, 5)
+    try:
+        for T in (1100, 1000):
+            _launch(vec, o, T, _lib.REINFORCE_MAX, aa=0.001, ab=0.1, gamma=0.99)
+    finally:
+        vec.close()
+
+
+def test_errors():
+    g = GRIDS['test_env']()
+    with Engine(8, _spec(g)) as eng:
+        with pytest.raises(gua.GuError) as err:
+            eng.reinforce_run(10)
+        assert err.value.code == -4  # GU_ERR_STATE before gu_ac_init
+        assert not eng.reinforce_get_episode()['count'].any()
+    vec, o = _pair(g, 64, 1)
+    try:
+        eng = vec.engine
+        _launch(vec, o, 30, 16)
+        assert o.buf_cnt.any()
+        for kw in (dict(T=-1), dict(T=100000001), dict(L=0), dict(L=-3), dict(L=_lib.REINFORCE_MAX + 1), dict(aa=float('nan')),
+                   dict(ab=float('inf')), dict(ab=float('nan')), dict(gamma=float('nan')), dict(flags=_lib.F_AUTO_RESET),
+                   dict(flags=_lib.F_PACKED)):
+            args = dict(T=10, L=16, aa=0.1, ab=0.1, gamma=0.9, flags=0)
+            args.update(kw)
+            with pytest.raises(gua.GuError) as err:
+                _lib.check(eng.lib.gu_reinforce_run(eng._h, args['T'], args['L'], args['aa'], args['ab'], args['gamma'], args['flags']))
+            assert err.value.code == -1, kw
+        with pytest.raises(gua.GuError) as err:  # rows without a reservation that holds them
+            eng.reinforce_run(100000, 16, trajectory=True)
+        assert err.value.code == -4
+        with pytest.raises(gua.GuError) as err:
+            eng.reinforce_get_episode(60, 5)
+        assert err.value.code == -1
+        _lib.check(eng.lib.gu_reinforce_get_episode(eng._h, 0, 64, None, None, None))  # any pointer may be NULL
+        vec.reinforce_run(0, 16)  # T = 0 changes nothing ...
+        vec.reinforce_run(0, 5)   # ... whatever its L
+        _same_tables(vec, o)
+        _same_buffer(vec, [o])
+        _launch(vec, o, 20, 16)  # (the rejected calls changed nothing either: the buffer is still carried)
+        _same_state(vec, o)
+        part = vec.episode_buffer(10, 3)
+        assert part['count'].tobytes() == o.buf_cnt[10:13].tobytes() and part['sa'].tobytes() == o.buf_sa[10:13].tobytes()
+    finally:
+        vec.close()
+
+
+def test_reinforce_returns_a_policy_in_actor_critic_format():
+    env = gua.GridUniverseEnv(grid_shape=(5, 5), lava_states=[12])
+    pi, v = reinforce(env, 3000, max_episode_len=64, num_learners=1, seed=1)
+    S = env.world.size
+    assert pi.shape == (S, 4) and v.shape == (S,)
+    terminal = np.array([bool(env.is_terminal(s)) for s in range(S)])
+    assert (pi[terminal] == 0).all() and np.allclose(pi[~terminal].sum(axis=1), 1.0)
+    assert v.any() and (pi[~terminal] != 0.25).any()
+    utils.get_policy_map(pi, (5, 5), mode='ansi')
+    many, vs = reinforce(env, 500, num_learners=3, seed=1)
+    assert many.shape == (3, S, 4) and vs.shape == (3, S)
+
+
+def test_baseline_of_a_frozen_uniform_actor_approaches_the_policy_value():
+    """actor_lr = 0 and zero preferences: every learner acts uniformly at random, so the baseline V approaches the value of the
+    uniform policy, derived from utils.single_step_policy_evaluation as test_gpu_ac.py does (on non-terminal states the learners'
+    value is (v(s) - R(s)) / gamma).  The mean of V over 4096 learners (baseline_lr 0.05, gamma 0.9, L = 64, 10 000 steps, seed 5,
+    the 4x4 default grid) is compared with it on the non-terminal states.
+    Tolerance 0.09: the restatement, run on the CPU for exactly these inputs, gives a largest gap of 0.0690 (state 11, next to
+    the goal), and 1.25 x 0.0690 = 0.0863 rounds up to 0.09; the device matches the restatement byte for byte, so the margin
+    covers the round number only.  The tables of zeros are 8.58 away, so the gap must also stay under 0.858.  (One-step
+    actor-critic at the same point leaves 0.445 at critic_lr 0.1: Monte-Carlo targets do not carry the bootstrap's bias.)"""
+    gamma = 0.9
+    env = gua.GridUniverseEnv((4, 4))
+    S = env.world.size
+    terminal = np.array([bool(env.is_terminal(s)) for s in range(S)])
+    pi = np.full((S, 4), 0.25)
+    pi[terminal] = 0.0  # (the episode ends there)
+    v = np.zeros(S)
+    for _ in range(3000):
+        v = utils.single_step_policy_evaluation(pi, env, gamma, v)
+    want = (v - np.asarray(env.reward_matrix, np.float64)) / gamma
+    vec = gua.VecGridUniverse(4096, template=env, seed=5)
+    try:
+        vec.reset()
+        vec.reinforce_run(10000, 64, actor_lr=0.0, baseline_lr=0.05, discount_factor=gamma)
+        mean = vec.state_values().mean(axis=0)
+        assert not vec.preferences().any()
+    finally:
+        vec.close()
+    gap = np.abs(mean - want)[~terminal].max()
+    zero_gap = np.abs(want[~terminal]).max()
+    print('gap', gap, 'zero tables', zero_gap)
+    assert gap < 0.09, (gap, mean, want)
+    assert zero_gap > 8.0 and gap < zero_gap / 10

@@ -1,0 +1,157 @@
+"""Batched tabular REINFORCE with baseline, the parts that need no GPU: the restatement (tests/_reinforce_oracle.py) against the
+actor-critic restatement at L = 1, against a pass computed by hand and on a truncated segment; maze learning; the argument checks
+and the library's new symbols."""
+import math
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from griduniverse_amd import _lib
+from griduniverse_amd.algorithms.policy_gradient import reinforce
+from griduniverse_amd.envs.griduniverse_env import GridUniverseEnv
+from oracle import c_oracle as C
+
+from . import _ac_oracle as A
+from . import _golden as G
+from . import _reinforce_oracle as R
+from . import _td_oracle as O
+from .test_dyna_host import _greedy_walk, _shortest_from_start
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.mark.parametrize('grid', [lambda: C.Grid.from_lists(6, 5, goals=[29], lava=[8], walls=[14]),
+                                  lambda: C.Grid.from_lists(4, 4, goals=[15])])
+def test_segment_length_one_is_actor_critic_byte_for_byte(grid):
+    """L = 1: G = r + gamma V[s'] (or r), one entry, the same pi -- gu_ac_run's rules 5-7."""
+    a = A.AcOracle(grid(), 4, 50, h0=0.5, v0=-0.25)
+    b = R.ReinforceOracle(grid(), 4, 50, h0=0.5, v0=-0.25)
+    assert np.array_equal(a.reset(), b.reset())
+    for T in (120, 77):
+        x, y = a.ac(T, 0.2, 0.3, 0.9), b.reinforce(T, 1, 0.2, 0.3, 0.9)
+        for k in x:
+            assert x[k].tobytes() == y[k].tobytes(), k
+        assert a.h.tobytes() == b.h.tobytes() and a.v.tobytes() == b.v.tobytes()
+        assert not b.buf_cnt.any()
+    assert a.h.any() and a.v.any()
+
+
+def test_a_three_step_episode_with_a_repeated_state_by_hand():
+    """Corridor 0 1 2 (start 0, goal 2, rewards -1 -1 +10), tables of zeros, alpha_actor 0.25, alpha_baseline 0.5, gamma 0.5.
+    The episode: a bump at 0 (action x), 0 -> 1 (action R), 1 -> 2 (action R, terminal).  Newest to oldest, from the rules:
+      (1, R, 10): G = 10; delta = 10; V[1] = 5; g = 2.5; pi = 1/4 each; H[1] = -0.625 everywhere, 1.875 at R.
+      (0, R, -1): G = -1 + 0.5 * 10 = 4; delta = 4; V[0] = 2; g = 1; pi = 1/4 each; H[0] = -0.25 everywhere, 0.75 at R.
+      (0, x, -1): G = -1 + 0.5 * 4 = 1; delta = 1 - 2 = -1; V[0] = 2 - 0.5 = 1.5; g = -0.25; H[0] is no longer flat (the
+                  repeated state compounds): e = exp(-1) off R and 1 at R, Z = 1 + 3 exp(-1), so
+                  H[0][R] = 0.75 + 0.25 / Z, H[0][x] = -0.25 - 0.25 (1 - exp(-1) / Z), the other two -0.25 + 0.25 exp(-1) / Z.
+    exp(-1) comes from math.exp here; the build's exp is within one ulp of it, hence the 1e-15."""
+    grid = C.Grid.from_lists(3, 1, goals=[2], starts=[0])
+    o = R.ReinforceOracle(grid, 1, 256)
+    o.reset()
+    w = [O.words(1, o.env_ids, np.full(256, t, np.uint64)) >> 30 for t in range(3)]  # zero preferences: a = w >> 30
+    out = o.reinforce(3, 8, 0.25, 0.5, 0.5)
+    hit = np.flatnonzero((out['obs'].T == [0, 1, 2]).all(axis=1))
+    assert len(hit) >= 3
+    e1 = math.exp(-1.0)
+    Z = 1.0 + 3.0 * e1
+    for e in hit:
+        x, r1, r2 = int(w[0][e]), int(w[1][e]), int(w[2][e])
+        assert r1 == r2 != x
+        assert out['reward'][:, e].tolist() == [-1, -1, 10] and out['done'][:, e].tolist() == [0, 0, 1]
+        assert o.v[e].tolist() == [1.5, 5.0, 0.0]
+        h1 = np.full(4, -0.625)
+        h1[r1] = 1.875
+        assert o.h[e, 1].tolist() == h1.tolist() and not o.h[e, 2].any()
+        h0 = np.full(4, -0.25 + 0.25 * e1 / Z)
+        h0[r1] = 0.75 + 0.25 / Z
+        h0[x] = -0.25 - 0.25 * (1.0 - e1 / Z)
+        assert np.allclose(o.h[e, 0], h0, rtol=1e-15, atol=1e-15), (o.h[e, 0], h0)
+        assert o.buf_cnt[e] == 0 and (o.buf_sa[e] == -1).all()
+    # a learner still in its episode keeps its three transitions and has learned nothing
+    going = np.flatnonzero(out['done'].sum(axis=0) == 0)
+    assert len(going) and (o.buf_cnt[going] == 3).all() and not o.h[going].any() and not o.v[going].any()
+
+
+def test_truncation_bootstraps_on_the_baseline_and_does_not_reset():
+    """L = 3 on the 4x4 grid (no episode ends within 3 steps of the start): the pass runs after 3 steps with G starting from
+    V[s'], the env stays where it is, the buffer ends empty.  alpha_actor = 0 keeps the policy uniform, so V alone moves and is
+    recomputed here with scalar floats."""
+    grid = C.Grid.from_lists(4, 4, goals=[15])
+    n, gamma, ab = 64, 0.9, 0.5
+    v0 = np.random.default_rng(0).normal(0, 2, (n, 16))
+    o = R.ReinforceOracle(grid, 2, n)
+    o.set_ac(v=v0)
+    start = o.reset().copy()
+    episode = o.state.episode.copy()
+    out = o.reinforce(3, 3, 0.0, ab, gamma)
+    assert not out['done'].any()
+    assert not o.state.done.any() and np.array_equal(o.state.episode, episode)  # not reset
+    assert np.array_equal(o.state.pos, out['obs'][2])
+    assert not o.buf_cnt.any() and (o.buf_sa == -1).all()
+    assert not o.h.any()
+    for e in range(n):
+        states = [int(start[e]), int(out['obs'][0, e]), int(out['obs'][1, e])]
+        v = v0[e].copy()
+        g_ret = v[int(out['obs'][2, e])]  # V[s'], before any write of the pass
+        for k in (2, 1, 0):
+            g_ret = float(out['reward'][k, e]) + gamma * g_ret
+            v[states[k]] = v[states[k]] + ab * (g_ret - v[states[k]])
+        assert v.tobytes() == o.v[e].tobytes(), e
+    # the next step goes on from s', in the same episode
+    pos, t = o.state.pos.copy(), o.state.tcount.copy()
+    a = (O.words(2, o.env_ids, t) >> 30).astype(np.int32)
+    nxt, _, _ = C.look_step_ahead(grid, pos, a, True)
+    out = o.reinforce(1, 3, 0.0, ab, gamma)
+    assert np.array_equal(out['obs'][0], nxt) and np.array_equal(o.state.episode, episode)
+    assert (o.buf_cnt == 1).all() and np.array_equal(o.buf_sa[:, 0], pos * 4 + a)
+    # another L drops the pending transition
+    o.reinforce(1, 4, 0.0, ab, gamma)
+    assert (o.buf_cnt == 1).all()
+
+
+def _steps_to_shortest(grid, best, chunk=500, limit=40000):
+    """Real steps until every learner's argmax walk from the start is a shortest path (the defaults of `reinforce`: L = 256,
+    alpha_actor 0.003, alpha_baseline 0.1, gamma 0.99; seed 3, four learners)."""
+    o = R.ReinforceOracle(grid, 3, 4)
+    o.reset()
+    done = 0
+    while done < limit:
+        o.reinforce(chunk, 256, 0.003, 0.1, 0.99)
+        done += chunk
+        if all(_greedy_walk(grid, o.h[e]) == best for e in range(o.n)):
+            return done
+    return None
+
+
+def test_reinforce_learns_the_shortest_path_in_the_maze():
+    """Measured with this restatement (which the device matches byte for byte): all four learners' argmax walks are the shortest
+    24 steps after 37 000 real steps (checked every 500; the last of the four learners sets the figure).  A throwaway prototype
+    (numpy's RNG, another 11x11 maze with a 24-step path, one learner at a time) needed 12 500-24 500 at L = 256 and 9 000-14 500
+    at L = 64.  The budget is 40 000."""
+    grid = C.Grid.from_env(GridUniverseEnv(custom_world_fp=G.level_path('maze_11x11.txt')))
+    best = _shortest_from_start(grid)
+    assert best == 24
+    assert _steps_to_shortest(grid, best) == 37000
+
+
+def test_reinforce_checks_its_arguments():
+    env = GridUniverseEnv((4, 4))
+    for kw in (dict(num_learners=0), dict(num_steps=-1), dict(actor_lr=float('nan')), dict(baseline_lr=float('inf')),
+               dict(discount_factor=float('nan')), dict(max_episode_len=0), dict(max_episode_len=_lib.REINFORCE_MAX + 1)):
+        args = dict(num_steps=10)
+        args.update(kw)
+        with pytest.raises(ValueError):
+            reinforce(env, **args)
+
+
+def test_library_exports_the_reinforce_entry_points():
+    syms = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], stdout=subprocess.PIPE, check=True).stdout.decode()
+    header = open(os.path.join(ROOT, 'include', 'gu.h')).read()
+    for name in ('gu_reinforce_run', 'gu_reinforce_get_episode'):
+        assert ' T ' + name + '\n' in syms, name
+        assert name in _lib.SIGNATURES
+        assert 'int ' + name + '(' in header
+    assert '#define GU_REINFORCE_MAX {}\n'.format(_lib.REINFORCE_MAX) in header
+    assert R.REINFORCE_MAX == _lib.REINFORCE_MAX
