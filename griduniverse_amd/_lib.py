@@ -27,6 +27,7 @@ TD_Q_LEARNING, TD_SARSA = 0, 1
 NSTEP_MAX = 16  # GU_NSTEP_MAX: the largest n of gu_nstep_run
 LAMBDA_MAX = 64  # GU_LAMBDA_MAX: the largest K (trace length) of gu_lambda_run
 REINFORCE_MAX = 1024  # GU_REINFORCE_MAX: the largest L (segment length) of gu_reinforce_run
+FA_MAX_K = 8  # GU_FA_MAX_K: the most active features per state of gu_fa_init
 COMM_ID_BYTES = 128
 OPT_UNSET = -2 ** 63
 # gu_set_option / gu_get_option (include/gu.h "options"): name -> id
@@ -100,6 +101,11 @@ SIGNATURES = {
     'gu_ac_set': [_vp, _i64, _i64, _vp, _vp],
     'gu_reinforce_run': [_vp, _i64, _i32, _f64, _f64, _f64, _u32],
     'gu_reinforce_get_episode': [_vp, _i64, _i64, _vp, _vp, _vp],
+    'gu_fa_init': [_vp, _i32, _i32, _vp, _f64],
+    'gu_fa_run': [_vp, _i64, _i32, _f64, _f64, _u32, _u32],
+    'gu_fa_get_w': [_vp, _i64, _i64, _vp],
+    'gu_fa_set_w': [_vp, _i64, _i64, _vp],
+    'gu_fa_get_q': [_vp, _i64, _i64, _vp],
     'gu_vi_set': [_vp, _vp, _vp],
     'gu_vi_sweep': [_vp, _f64, _i32, _i32, _vp],
     'gu_vi_run': [_vp, _f64, _f64, _i32, _vp, _vp],

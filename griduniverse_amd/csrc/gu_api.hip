@@ -19,6 +19,7 @@ static void gu_nstep_free(gu_engine *h);  // (tabular n-step learners, below)
 static void gu_lambda_free(gu_engine *h); // (tabular lambda learners, below)
 static void gu_ac_free(gu_engine *h);     // (tabular actor-critic, below)
 static void gu_reinforce_free(gu_engine *h);  // (tabular REINFORCE, below)
+static void gu_fa_free(gu_engine *h);     // (semi-gradient learners on features, below)
 
 // ---------------------------------------------------------------------------------- errors
 static thread_local std::string g_last_error;
@@ -176,7 +177,8 @@ int gu_destroy(gu_handle h)
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
                     h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next,
-                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_lambda_w, h->d_ac_h, h->d_ac_v, h->d_rf_buf, h->d_rf_cnt};
+                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_lambda_w, h->d_ac_h, h->d_ac_v, h->d_rf_buf, h->d_rf_cnt,
+                    h->d_fa_w, h->d_fa_phi, h->d_fa_phi16, h->d_fa_next};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -256,6 +258,7 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
     }
     if (h->dyna_S && h->dyna_S != W * H) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
     if (h->ac_S && h->ac_S != W * H) gu_ac_free(h);  // ... and actor-critic tables: gu_ac_init again
+    if (h->fa_S && h->fa_S != W * H) gu_fa_free(h);  // ... and features and weights: gu_fa_init again
     h->dyna_exact = false;  // a kept model may hold outcomes of the old cells: gu_dyna_run compares every observation from now on
     h->nib_valid = false;
     if (h->d_nib) GU_HIP(hipFree(h->d_nib));
@@ -1540,6 +1543,132 @@ int gu_reinforce_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, 
         }
     if (count)
         for (int64_t e = 0; e < n; ++e) count[e] = c[e];
+    return GU_OK;
+}
+
+// ---------------------------------------------------------------------------------- semi-gradient SARSA / Q-learning on features (gu_fa.hip)
+static void gu_fa_free(gu_engine *h)
+{
+    if (h->d_fa_w) (void)hipFree(h->d_fa_w);
+    if (h->d_fa_phi) (void)hipFree(h->d_fa_phi);
+    if (h->d_fa_phi16) (void)hipFree(h->d_fa_phi16);
+    if (h->d_fa_next) (void)hipFree(h->d_fa_next);
+    h->d_fa_w = nullptr;
+    h->d_fa_phi = nullptr;
+    h->d_fa_phi16 = nullptr;
+    h->d_fa_next = nullptr;
+    h->fa_phi16_bytes = 0;
+    h->fa_S = h->fa_K = h->fa_F = 0;
+    h->fa_carry = false;
+}
+
+int gu_fa_init(gu_handle h, int32_t K, int32_t F, const int32_t *phi, double w0)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(K >= 1 && K <= GU_FA_MAX_K, GU_ERR_INVALID, "K %d out of range (1 .. %d)", K, GU_FA_MAX_K);
+    GU_REQUIRE(F >= 1 && F <= GU_FA_MAX_F, GU_ERR_INVALID, "F %d out of range (1 .. %d)", F, GU_FA_MAX_F);
+    GU_REQUIRE(phi != nullptr, GU_ERR_INVALID, "phi is NULL");
+    GU_REQUIRE(std::isfinite(w0), GU_ERR_INVALID, "w0 must be finite");
+    const size_t S = (size_t)h->S, cells = S * (size_t)K;
+    std::vector<int8_t> column((size_t)F, (int8_t)-1);  // the column each feature index occurs in
+    for (size_t i = 0; i < cells; ++i) {
+        const int32_t f = phi[i], k = (int32_t)(i % (size_t)K);
+        GU_REQUIRE(f >= 0 && f < F, GU_ERR_INVALID, "phi[%zu][%d] = %d outside 0 .. %d", i / (size_t)K, k, f, F - 1);
+        GU_REQUIRE(column[f] < 0 || column[f] == k, GU_ERR_INVALID, "feature %d occurs in columns %d and %d: a column is a slot of its own", f,
+                   (int)column[f], k);
+        column[f] = (int8_t)k;
+    }
+    gu_tabular_drop_carry(h);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!h->d_fa_w || h->fa_S != h->S || h->fa_K != K || h->fa_F != F) {
+        gu_fa_free(h);
+        const size_t bytes = (size_t)h->N * (size_t)F * 4 * sizeof(double);
+        int rc = gu_tabular_fits(h, bytes + cells * 6 + (size_t)h->N, "feature weights");
+        if (rc != GU_OK) return rc;
+        GU_HIP(hipMalloc(&h->d_fa_w, bytes));
+        GU_HIP(hipMalloc(&h->d_fa_phi, cells * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_fa_next, (size_t)h->N));
+        if (F <= 65536) {
+            h->fa_phi16_bytes = (cells * sizeof(uint16_t) + 15) & ~(size_t)15;
+            GU_HIP(hipMalloc(&h->d_fa_phi16, h->fa_phi16_bytes));
+        }
+        h->fa_S = h->S;
+        h->fa_K = K;
+        h->fa_F = F;
+    }
+    GU_HIP(hipMemcpy(h->d_fa_phi, phi, cells * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (h->d_fa_phi16) {
+        std::vector<uint16_t> p16(h->fa_phi16_bytes / sizeof(uint16_t), (uint16_t)0);
+        for (size_t i = 0; i < cells; ++i) p16[i] = (uint16_t)phi[i];
+        GU_HIP(hipMemcpy(h->d_fa_phi16, p16.data(), h->fa_phi16_bytes, hipMemcpyHostToDevice));
+    }
+    GU_HIP(hipMemsetAsync(h->d_fa_next, 0xFF, (size_t)h->N, h->stream));
+    int rc = gu_fa_fill(h, w0);
+    if (rc != GU_OK) return rc;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_fa_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_fa_w && h->fa_S == h->S, GU_ERR_STATE, "no features: call gu_fa_init first");
+    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Q-learning, 1 = SARSA", method);
+    int rc = gu_tabular_check(h, "gu_fa_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    return gu_launch_fa(h, T, method, alpha, gamma, eps_q16, flags);
+}
+
+static int gu_fa_range(gu_engine *h, int64_t env0, int64_t n, const void *p, const char *name)
+{
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_fa_w && h->fa_S == h->S, GU_ERR_STATE, "no features: call gu_fa_init first");
+    GU_REQUIRE(p != nullptr, GU_ERR_INVALID, "%s is NULL", name);
+    return gu_env_range(h, env0, n);
+}
+
+int gu_fa_get_w(gu_handle h, int64_t env0, int64_t n, double *w)
+{
+    GU_ENTER(h);
+    int rc = gu_fa_range(h, env0, n, w, "w");
+    if (rc != GU_OK) return rc;
+    const size_t row = (size_t)h->fa_F * 4;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n) GU_HIP(hipMemcpy(w, h->d_fa_w + (size_t)env0 * row, (size_t)n * row * sizeof(double), hipMemcpyDeviceToHost));
+    return GU_OK;
+}
+
+int gu_fa_set_w(gu_handle h, int64_t env0, int64_t n, const double *w)
+{
+    GU_ENTER(h);
+    int rc = gu_fa_range(h, env0, n, w, "w");
+    if (rc != GU_OK) return rc;
+    gu_tabular_drop_carry(h);
+    const size_t row = (size_t)h->fa_F * 4;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n) GU_HIP(hipMemcpy(h->d_fa_w + (size_t)env0 * row, w, (size_t)n * row * sizeof(double), hipMemcpyHostToDevice));
+    return GU_OK;
+}
+
+int gu_fa_get_q(gu_handle h, int64_t env0, int64_t n, double *q)
+{
+    GU_ENTER(h);
+    int rc = gu_fa_range(h, env0, n, q, "q");
+    if (rc != GU_OK || n == 0) return rc;
+    // folded on the device in slices of at most 64 MiB, through the engine's scratch buffer
+    const size_t row = (size_t)h->S * 4 * sizeof(double);
+    const int64_t slice = std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / row));
+    for (int64_t i = 0; i < n; i += slice) {
+        const int64_t k = std::min<int64_t>(slice, n - i);
+        rc = gu_ensure_scratch(h, (size_t)k * row);
+        if (rc != GU_OK) return rc;
+        rc = gu_fa_fold_q(h, env0 + i, k, reinterpret_cast<double *>(h->d_scratch));
+        if (rc != GU_OK) return rc;
+        GU_HIP(hipStreamSynchronize(h->stream));
+        GU_HIP(hipMemcpy(q + (size_t)i * (size_t)h->S * 4, h->d_scratch, (size_t)k * row, hipMemcpyDeviceToHost));
+    }
     return GU_OK;
 }
 

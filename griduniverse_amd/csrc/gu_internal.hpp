@@ -279,6 +279,14 @@ struct gu_engine {
     int32_t *d_rf_cnt = nullptr;  // [N] their entries
     int32_t rf_cap = 0;           // entries per env the storage holds (0: none allocated)
     int32_t rf_key = 0;           // L of the last call that touched the envs if it was a gu_reinforce_run, else 0 (buffer dropped)
+    // batched semi-gradient SARSA / Q-learning on binary features (gu_fa.hip): off until gu_fa_init; weights of its own, not d_q
+    double *d_fa_w = nullptr;         // [N][fa_F][4] one float64 weight table per env
+    int32_t *d_fa_phi = nullptr;      // [fa_S][fa_K] the feature table, shared by all envs
+    uint16_t *d_fa_phi16 = nullptr;   // ... as uint16 when fa_F <= 65536 (what the LDS kernels stage), padded to fa_phi16_bytes
+    size_t fa_phi16_bytes = 0;        // fa_S * fa_K * 2 rounded up to 16
+    int8_t *d_fa_next = nullptr;      // [N] SARSA: the action a' carried from one gu_fa_run to the next (-1: none)
+    int32_t fa_S = 0, fa_K = 0, fa_F = 0;  // states, slots and features of the tables (fa_S 0: none); a grid of another size drops them
+    bool fa_carry = false;            // the last call that touched the envs was a SARSA gu_fa_run: the next one starts from d_fa_next
     // batched tabular Dyna-Q (gu_dyna.hip): off until gu_dyna_init; learns into d_q
     uint64_t *d_dyna_model = nullptr;  // [N][dyna_S*4] one packed word per (s, a): reward | (s' | done << 31) << 32; ~0 = unobserved
     int32_t *d_dyna_list = nullptr;    // [N][dyna_S*4] observed pairs s*4+a in the order of first observation (-1 beyond count)
@@ -443,12 +451,18 @@ int gu_launch_ac(gu_engine *h, int64_t T, double alpha_actor, double alpha_criti
 // ---- batched tabular REINFORCE with baseline (gu_reinforce.hip) ------------------------
 int gu_launch_reinforce(gu_engine *h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags);
 
+// ---- batched semi-gradient SARSA / Q-learning on binary features (gu_fa.hip) ----------------
+int gu_fa_fill(gu_engine *h, double w0);  // every weight = w0 (async)
+int gu_fa_fold_q(gu_engine *h, int64_t env0, int64_t n, double *d_out);  // Q of envs env0 .. env0+n-1 into d_out [n][S][4] (async)
+int gu_launch_fa(gu_engine *h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+
 // every call that touches the envs other than the learner launches ends what the learners carry from one launch to the next:
-// gu_td_run's SARSA action, gu_nstep_run's window (its pending updates are discarded, not flushed), gu_lambda_run's window and
-// gu_reinforce_run's episode buffer (its pending transitions are discarded, not learned from)
+// gu_td_run's and gu_fa_run's SARSA actions, gu_nstep_run's window (its pending updates are discarded, not flushed), gu_lambda_run's
+// window and gu_reinforce_run's episode buffer (its pending transitions are discarded, not learned from)
 static inline void gu_tabular_drop_carry(gu_engine *h)
 {
     h->td_carry = false;
+    h->fa_carry = false;
     h->nstep_key = 0;
     h->lambda_key = 0;
     h->rf_key = 0;

@@ -1,5 +1,6 @@
 // gu_tabular.hpp -- the core of the batched tabular learners for gfx950 (gu_td.hip: Q-learning and SARSA; gu_dyna.hip: Dyna-Q;
-// gu_nstep.hip: n-step Q-learning and SARSA; gu_lambda.hip: SARSA(lambda) and Watkins's Q(lambda)).
+// gu_nstep.hip: n-step Q-learning and SARSA; gu_lambda.hip: SARSA(lambda) and Watkins's Q(lambda)); gu_fa.hip (semi-gradient
+// SARSA / Q-learning on features) uses the lane without its table.
 // N independent learners, learner e owns env e and its own float64 table Q_e[S][4], advanced T real steps per launch.  The
 // semantics are build-defined (the reference has no tabular code) and stated in include/gu.h (gu_td_run, gu_dyna_run, gu_nstep_run).
 //
@@ -95,7 +96,9 @@ __device__ __forceinline__ uint32_t gu_q_action(const QRow &q, uint32_t w, uint3
 
 // ---- the lane: state, prologue, auto-reset, move, Q[s][a] update, record, epilogue ----
 // A kernel constructs it (staging the map), runs begin .. end on live lanes and ballot on all; its own rule sits between move and step.
-template <bool LDS>
+// ROWS = false (gu_fa.hip): the lane has no table of rows of its own -- begin / reset / next_row read nothing from a.q, and the
+// kernel keeps `q` (for gu_fa.hip: the folded row of the current state) itself.
+template <bool LDS, bool ROWS = true>
 struct TabLane {
     CellMap m;
     LaneGrid lg;
@@ -121,13 +124,13 @@ struct TabLane {
         t = a.steps_taken + (uint64_t)(int64_t)(int32_t)a.tcount[e];
         // stream 4: the epoch t >> 32 hashed behind the seed, hoisted; recomputed in the step that crosses a multiple of 2^32
         prefix = gu_rng_prefix(gu_rng_seed_prefix_epoch(a.seed_prefix, (uint32_t)(t >> 32)), env);
-        qe = a.q + e * a.S * 4;
+        qe = ROWS ? a.q + e * a.S * 4 : nullptr;
         s = a.pos[e];
         r = a.reward[e];
         d = a.done[e];
         ep = a.episode[e];
         q = QRow{0.0, 0.0, 0.0, 0.0};
-        if (!d) q = gu_q_load(qe + (int64_t)s * 4);
+        if (ROWS && !d) q = gu_q_load(qe + (int64_t)s * 4);
         ret = 0;
         fin = 0;
     }
@@ -139,7 +142,7 @@ struct TabLane {
             s = lg.starts[gu_rng_start_index(start_prefix, ep, lg.n_starts)];
             ++ep;
             d = 0;
-            q = gu_q_load(qe + (int64_t)s * 4);
+            if (ROWS) q = gu_q_load(qe + (int64_t)s * 4);
         }
     }
 
@@ -161,7 +164,7 @@ struct TabLane {
     __device__ __forceinline__ QRow next_row(int32_t s2) const
     {
         QRow n = q;
-        if (!d && s2 != s) n = gu_q_load(qe + (int64_t)s2 * 4);
+        if (ROWS && !d && s2 != s) n = gu_q_load(qe + (int64_t)s2 * 4);
         return n;
     }
 

@@ -453,6 +453,57 @@ class Engine(object):
         check(self.lib.gu_reinforce_get_episode(self._h, int(env0), n, ptr(out['sa']), ptr(out['reward']), ptr(out['count'])))
         return out
 
+    # ------------------------------------------------------------------ semi-gradient SARSA / Q-learning on features (include/gu.h: gu_fa_*)
+    _fa_F = None  # features of the table installed by fa_init
+
+    def fa_init(self, phi, n_features=None, w0=0.0):
+        """Install the feature table phi int32[S, K] (K active binary features per state, 1 <= K <= FA_MAX_K, column k a slot of
+        its own) shared by all envs, and one float64 weight table [F][4] per env, every entry w0.  F = n_features, or
+        phi.max() + 1."""
+        phi = np.asarray(phi)
+        if phi.ndim == 1:
+            phi = phi[:, None]
+        if phi.ndim != 2 or phi.shape[0] != self.spec.S:
+            raise ValueError('phi must have shape ({}, K), got {}'.format(self.spec.S, phi.shape))
+        phi = _lib.as_array(phi, np.int32, None, 'phi')
+        F = (int(phi.max()) + 1 if phi.size else 0) if n_features is None else int(n_features)
+        check(self.lib.gu_fa_init(self._h, phi.shape[1], F, ptr(phi), float(w0)))
+        self._fa_F = F
+
+    def _fa_features(self):
+        if self._fa_F is None:
+            raise RuntimeError('no features: call fa_init first')
+        return self._fa_F
+
+    def fa_run(self, T, method='sarsa', alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
+        """T iterations of episodic semi-gradient SARSA / Q-learning per env in one launch, on the fa_init features.  alpha is
+        applied as given (divide by K yourself).  Rows and statistics as td_run()."""
+        check(self.lib.gu_fa_run(self._h, int(T), _TD_METHODS[method], float(alpha), float(gamma), int(eps_q16),
+                                 _learner_flags(trajectory, stats)))
+
+    def fa_get_w(self, env0=0, n=None):
+        """float64[n, F, 4]: the weights of envs env0 .. env0+n-1 (all from env0 when n is None)."""
+        n = self.N - int(env0) if n is None else int(n)
+        w = np.empty((max(n, 0), self._fa_features(), 4), np.float64)
+        check(self.lib.gu_fa_get_w(self._h, int(env0), n, ptr(w)))
+        return w
+
+    def fa_set_w(self, w, env0=0):
+        """Install weights float64[n, F, 4] (or [F, 4] for one env) for envs env0 .. env0+n-1."""
+        F = self._fa_features()
+        w = np.asarray(w, np.float64)
+        w = _lib.as_array(w.reshape((-1, F, 4)) if w.ndim == 2 else w, np.float64, None, 'w')
+        if w.ndim != 3 or w.shape[1:] != (F, 4):
+            raise ValueError('w must have shape (n, {}, 4), got {}'.format(F, w.shape))
+        check(self.lib.gu_fa_set_w(self._h, int(env0), w.shape[0], ptr(w)))
+
+    def fa_get_q(self, env0=0, n=None):
+        """float64[n, S, 4]: the action values of envs env0 .. env0+n-1, folded from the weights on the device."""
+        n = self.N - int(env0) if n is None else int(n)
+        q = np.empty((max(n, 0), self.spec.S, 4), np.float64)
+        check(self.lib.gu_fa_get_q(self._h, int(env0), n, ptr(q)))
+        return q
+
     # ------------------------------------------------------------------ state
     def get_state(self):
         pos, don = np.empty(self.N, np.int32), np.empty(self.N, np.int32)

@@ -24,6 +24,7 @@ class VecGridUniverse(object):
     _td_ready = False  # the engine holds Q tables (td_run / set_q_table allocate them on first use)
     _dyna_ready = False  # ... and Dyna-Q models (dyna_run / model allocate them on first use)
     _ac_ready = False  # ... and actor-critic tables (actor_critic_run / set_actor_critic allocate them on first use)
+    _fa_ready = False  # ... and features with their weights (set_features installs them; nothing does it implicitly)
 
     def __init__(self, num_envs, grid_shape=(4, 4), *, initial_state=0, goal_states=None, lava_states=None,
                  walls=None, custom_world_fp=None, random_maze=False, template=None, templates=None,
@@ -196,6 +197,44 @@ class VecGridUniverse(object):
     def lambda_window(self, env0=0, n=None):
         """The trace windows of envs env0 .. env0+n-1 (Engine.lambda_get_window): int32[n, 64], index = age."""
         return self.engine.lambda_get_window(env0, n)
+
+    def set_features(self, phi, n_features=None, w0=0.0):
+        """Install the feature table phi int32[S, K] (K active binary features per state, K <= 8; column k is a slot of its own,
+        as a tiling of tile coding is) shared by all envs, and give every env a weight table [F][4] of w0
+        (include/gu.h: gu_fa_init).  F = n_features, or phi.max() + 1.  See algorithms.function_approximation.tile_coding."""
+        self.engine.fa_init(phi, n_features, w0)
+        self._fa_ready = True
+
+    def _need_features(self):
+        if not self._fa_ready:
+            raise RuntimeError('no features: call set_features first')
+
+    def fa_run(self, T, method='sarsa', alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
+        """T iterations of batched episodic semi-gradient SARSA ('sarsa') or semi-gradient Q-learning ('q_learning') on the
+        features of set_features: env e learns its own weights [F][4], its action values being the sum of the K weight rows
+        active in a state, epsilon-greedy, auto-reset always on (include/gu.h: gu_fa_run).  `alpha` is applied as given: divide
+        a step size by K yourself.  Returns a dict like td_run()."""
+        self._need_features()
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.fa_run(T, method, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def weights(self, env0=0, n=None):
+        """float64[n, F, 4]: the weight tables of envs env0 .. env0+n-1 (to the end when n is None)."""
+        self._need_features()
+        return self.engine.fa_get_w(env0, n)
+
+    def set_weights(self, w, env0=0):
+        """Install weights float64[n, F, 4] (or [F, 4]) for envs env0 .. ."""
+        self._need_features()
+        self.engine.fa_set_w(w, env0)
+
+    def fa_q_table(self, env0=0, n=None):
+        """float64[n, S, 4]: the action values of envs env0 .. env0+n-1 computed from their weights on the device, in the
+        format of q_table()."""
+        self._need_features()
+        return self.engine.fa_get_q(env0, n)
 
     def _ensure_ac(self, h0=None, v0=None):
         """Actor-critic tables on the engine: zeros on first use; every entry h0 / v0 (again) when either is given."""

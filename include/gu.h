@@ -451,6 +451,43 @@ int gu_ac_set(gu_handle h, int64_t env0, int64_t n, const double *pref, const do
 int gu_reinforce_run(gu_handle h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags);
 int gu_reinforce_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count);
 
+/* ---- batched semi-gradient SARSA and Q-learning on binary features: learner e owns env e and a weight table w_e[F][4] ----
+ * (build-defined: the reference's roadmap entry "Value Approximation", for which it ships no code; Sutton & Barto 10.1;
+ * tests/_fa_oracle.py is the CPU restatement.)  The action values are computed, not stored.  The engine holds ONE feature table
+ * phi[S][K] (int32, 0 <= phi < F, 1 <= K <= GU_FA_MAX_K) shared by all envs: it depends on the state index only, so it also serves
+ * one-grid-per-env batches, whose grids share W x H.  Column k is a slot (a tiling of tile coding): no feature index occurs in two
+ * columns; one index many times in one column is aggregation.
+ *   Q_e(s)[b] = w_e[phi[s][0]][b], then + w_e[phi[s][k]][b] for k = 1 .. K-1 in this order, one rounded add each.
+ * One iteration of gu_fa_run for env e at 64-bit step count t:
+ *   1. lazy auto-reset, exactly as rule 1 of gu_td_run;
+ *   2. action: rule 2 of gu_td_run (the stream-4 word at t, eps_q16, the tie rule) applied to the row Q_e(s).  SARSA takes its
+ *      carried a' instead, under the conditions of gu_td_run's SARSA (the carry across launches is gu_fa_run's own, below);
+ *   3. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
+ *   4. n = Q_e(s') from the weights as they are before this step's update; m = max n, folded with `>` as in gu_td_run (method 0,
+ *      Q-learning) or n[a'] with a' drawn at s' by rule 2 from the word of the new t (method 1, SARSA; not drawn when d);
+ *      target = r if d else r + gamma * m; g = alpha * (target - Q_e(s)[a]); then for k = 0 .. K-1:
+ *      w_e[phi[s][k]][a] = w_e[phi[s][k]][a] + g.
+ * All float64, one rounding per operation, multiply / add / subtract only.  alpha is applied as given: dividing a step size by K
+ * is the caller's business.  With K = 1, F = S, phi[s][0] = s this is gu_td_run byte for byte, both methods, across launches.
+ * CARRY: SARSA's a' survives from one gu_fa_run to the next under the conditions of gu_td_run's carry; gu_fa_init, gu_fa_set_w and
+ * a run of any other learner end it as well, and gu_fa_run ends every other learner's carry, window and episode buffer.  A SARSA
+ * gu_td_run does not hand its action to gu_fa_run, nor the other way round.
+ * gu_fa_init  : copy phi, allocate the weights (N * F * 32 bytes; GU_ERR_NOMEM under gu_td_init's free-memory rule) and set every
+ *               entry to w0.  GU_ERR_INVALID for K outside 1 .. GU_FA_MAX_K, F outside 1 .. GU_FA_MAX_F, an index outside [0, F), an index that occurs
+ *               in two columns, a non-finite w0.  The weights are separate from the gu_td_* tables; both may exist.  A grid of
+ *               another size drops features and weights (gu_fa_init again).
+ * gu_fa_run   : T iterations per env in ONE launch (async).  method 0 = Q-learning, 1 = SARSA.  Flags, rows, statistics, the
+ *               agent trail, T = 0, the argument checks and the step counts as gu_td_run.  GU_ERR_STATE before gu_fa_init.
+ * gu_fa_get_w / gu_fa_set_w : weights of envs env0 .. env0+n-1 as w[n][F][4] on the host.
+ * gu_fa_get_q : their action values q[n][S][4], folded on the device by the rule above. */
+#define GU_FA_MAX_K 8
+#define GU_FA_MAX_F (1 << 26) /* 2 GiB of weights per learner */
+int gu_fa_init(gu_handle h, int32_t K, int32_t F, const int32_t *phi, double w0);
+int gu_fa_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+int gu_fa_get_w(gu_handle h, int64_t env0, int64_t n, double *w);
+int gu_fa_set_w(gu_handle h, int64_t env0, int64_t n, const double *w);
+int gu_fa_get_q(gu_handle h, int64_t env0, int64_t n, double *q);
+
 /* ---- look_step_ahead table queries: env:136-155 for n (state, action) pairs (grid 0 of a multi-grid engine) ---- */
 int gu_look_step_ahead(gu_handle h, int64_t n, const int32_t *states, const int32_t *actions,
                        int32_t care_about_terminal, int32_t *next, int32_t *reward, int32_t *done);

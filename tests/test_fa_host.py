@@ -1,0 +1,97 @@
+"""Semi-gradient SARSA / Q-learning on binary features, the parts that need no GPU: the CPU restatement against the tabular one,
+the restatement learning shortest paths from tile-coded features, the feature builders and the library's new symbols."""
+import subprocess
+
+import numpy as np
+import pytest
+
+from griduniverse_amd import _lib
+from griduniverse_amd.algorithms.function_approximation import one_hot, state_aggregation, tile_coding
+from oracle import c_oracle as C
+
+from . import _fa_oracle as FA
+from . import _td_oracle as O
+from .test_td_host import _bfs_lengths, _greedy_walk_lengths
+
+
+@pytest.mark.parametrize('method', [O.Q_LEARNING, O.SARSA])
+def test_identity_features_equal_the_tabular_oracle_byte_for_byte(method):
+    grid = C.Grid.from_lists(8, 8, walls=[10, 11, 19], lava=[30])
+    phi, F = one_hot(grid.S)
+    a = O.TdOracle(grid, 5, 32, q0=0.5)
+    b = FA.FaOracle(grid, 5, 32, phi, F, w0=0.5)
+    assert np.array_equal(a.reset(), b.reset())
+    for T in (200, 100):  # two launches: SARSA's action carries
+        want = a.run(T, method, 0.25, 0.9, 13107)
+        got = b.run(T, method, 0.25, 0.9, 13107)
+        for k in want:
+            assert np.array_equal(got[k], want[k]), k
+        assert b.w.tobytes() == a.q.tobytes()
+        assert b.q_tables().tobytes() == a.q.tobytes()
+
+
+@pytest.mark.parametrize('method', [O.Q_LEARNING, O.SARSA])
+def test_oracle_learns_the_shortest_paths_from_tile_coded_features(method):
+    grid = C.Grid.from_lists(8, 8)
+    phi, F = tile_coding(8, 8, 4, 4)
+    assert F == 36 and F < grid.S
+    L = 32
+    o = FA.FaOracle(grid, 5, L, phi, F)
+    o.reset()
+    o.run(6000, method, 0.2 / 4, 0.9, int(round(0.2 * 65536)))
+    dist = _bfs_lengths(grid)
+    q = o.q_tables()
+    for e in range(L):  # every learner's greedy policy walks every start cell to the goal on a shortest path
+        walk = _greedy_walk_lengths(grid, q[e])
+        assert np.array_equal(walk[grid.starts], dist[grid.starts]), (e, walk.reshape(8, 8), dist.reshape(8, 8))
+
+
+@pytest.mark.parametrize('W,H,K,B', [(8, 8, 4, 4), (32, 32, 8, 4), (32, 32, 8, 8), (7, 5, 3, 2), (11, 11, 5, 3), (9, 4, 2, 4), (6, 6, 1, 3)])
+def test_tile_coding_columns_are_disjoint_displaced_tilings(W, H, K, B):
+    phi, F = tile_coding(W, H, K, B)
+    TW, TH = (W + B - 2) // B + 1, (H + B - 2) // B + 1
+    assert phi.dtype == np.int32 and phi.shape == (W * H, K) and F == K * TW * TH
+    s = np.arange(W * H)
+    x, y = s % W, s // W
+    for k in range(K):
+        col = phi[:, k]
+        assert col.min() >= k * TW * TH and col.max() < (k + 1) * TW * TH  # column k: the index range of tiling k only
+        dx, dy = (k * B) // K, (3 * k * B // K) % B
+        tx, ty = (x + dx) // B, (y + dy) // B
+        same_tile = (tx[:, None] == tx[None, :]) & (ty[:, None] == ty[None, :])
+        assert np.array_equal(col[:, None] == col[None, :], same_tile)  # two cells share column k iff they share the displaced tile
+    assert 0 <= phi.min() and phi.max() < F
+
+
+def test_tile_coding_of_unit_tiles_is_the_identity_and_bad_arguments_raise():
+    for W, H in ((4, 4), (7, 3), (32, 32)):
+        phi, F = tile_coding(W, H, 1, 1)
+        assert F == W * H and np.array_equal(phi[:, 0], np.arange(W * H))
+    for bad in ((4, 4, 0, 2), (4, 4, 9, 2), (4, 4, 2, 0), (0, 4, 2, 2)):
+        with pytest.raises(ValueError):
+            tile_coding(*bad)
+
+
+def test_state_aggregation_and_one_hot():
+    phi, F = state_aggregation(8, 8, 4)
+    assert phi.dtype == np.int32 and phi.shape == (64, 1) and F == 4
+    assert np.array_equal(phi[:, 0].reshape(8, 8), np.kron(np.arange(4).reshape(2, 2), np.ones((4, 4), np.int64)))
+    phi, F = state_aggregation(7, 5, 3)  # ragged edges: 3 x 2 blocks
+    assert F == 6 and phi.max() == 5 and phi[6, 0] == 2 and phi[4 * 7, 0] == 3 and phi[34, 0] == 5
+    assert np.array_equal(np.unique(phi), np.arange(6))
+    phi, F = state_aggregation(5, 4, 1)
+    assert F == 20 and np.array_equal(phi[:, 0], np.arange(20))
+    phi, F = one_hot(12)
+    assert phi.dtype == np.int32 and phi.shape == (12, 1) and F == 12 and np.array_equal(phi[:, 0], np.arange(12))
+    with pytest.raises(ValueError):
+        one_hot(0)
+    with pytest.raises(ValueError):
+        state_aggregation(4, 4, 0)
+
+
+def test_library_exports_the_fa_entry_points():
+    syms = subprocess.run(['nm', '-D', '--defined-only', _lib.LIB_PATH], stdout=subprocess.PIPE, check=True).stdout.decode()
+    for name in ('gu_fa_init', 'gu_fa_run', 'gu_fa_get_w', 'gu_fa_set_w', 'gu_fa_get_q'):
+        assert ' T ' + name + '\n' in syms, name
+        assert name in _lib.SIGNATURES
+    assert _lib.FA_MAX_K == 8

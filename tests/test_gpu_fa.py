@@ -1,0 +1,344 @@
+"""Batched semi-gradient SARSA / Q-learning on binary features on the device (gu_fa_run, csrc/gu_fa.hip) against the CPU
+restatement tests/_fa_oracle.py: weights, folded action values, trajectory rows, statistics and env state compared byte for byte."""
+import numpy as np
+import pytest
+
+import griduniverse_amd as gua
+from griduniverse_amd import _lib
+from griduniverse_amd.algorithms.function_approximation import (one_hot, semi_gradient_q_learning, semi_gradient_sarsa,
+                                                                 state_aggregation, tile_coding)
+from griduniverse_amd.engine import Engine
+from oracle import c_oracle as C
+
+from . import _fa_oracle as FA
+from . import _td_oracle as O
+from ._tabular_cases import GRIDS, _eps, _grid, _random_grids, _same, _spec
+from .test_td_host import _bfs_lengths, _greedy_walk_lengths
+
+pytestmark = pytest.mark.gpu
+
+METHODS = {'q_learning': FA.Q_LEARNING, 'sarsa': FA.SARSA}
+
+# feature sets by name: (W, H) -> (phi, F); K = 1, 1, 2, 4, 8
+FEATURES = {
+    'identity': lambda W, H: one_hot(W * H),
+    'blocks2': lambda W, H: state_aggregation(W, H, 2),
+    'tiles2x2': lambda W, H: tile_coding(W, H, 2, 2),
+    'tiles4x4': lambda W, H: tile_coding(W, H, 4, 4),
+    'tiles8x4': lambda W, H: tile_coding(W, H, 8, 4),
+}
+
+
+def _pair(g, N, seed, feats, w0=0.0):
+    """A batch of N learners on grid g with the features `feats` = (phi, F) and weights of w0, and its restatement, both reset."""
+    phi, F = feats
+    vec = gua.VecGridUniverse(N, template=_spec(g), seed=seed)
+    vec.set_features(phi, F, w0)
+    o = FA.FaOracle(_grid(g), seed, N, phi, F, w0)
+    assert np.array_equal(vec.reset(), o.reset())
+    return vec, o
+
+
+def _tables(vec, o):
+    assert vec.weights().tobytes() == o.w.tobytes()
+    assert vec.fa_q_table().tobytes() == o.q_tables().tobytes()
+
+
+def _state(vec, o):
+    st = vec.get_state()
+    assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'], o.state.done)
+    assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
+
+
+@pytest.mark.parametrize('feats', sorted(FEATURES))
+@pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
+@pytest.mark.parametrize('grid', sorted(GRIDS))
+@pytest.mark.parametrize('N', [1, 63, 4096])
+def test_weights_values_rows_and_stats_equal_the_oracle(grid, method, N, feats):
+    g = GRIDS[grid]()
+    T = 300 if N < 4096 else 60
+    w0 = 0.0 if N != 63 else 0.5
+    vec, o = _pair(g, N, 3, FEATURES[feats](g['W'], g['H']), w0)
+    try:
+        for _ in range(2):  # two launches: the second starts from the first one's state (and, for SARSA, its carried action)
+            got = vec.fa_run(T, method, alpha=0.25 / o.K, discount_factor=0.9, epsilon=0.2, trajectory=True, stats=True)
+            _same(got, o.run(T, METHODS[method], 0.25 / o.K, 0.9, _eps(0.2)))
+            _tables(vec, o)
+        _state(vec, o)
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
+@pytest.mark.parametrize('K', range(1, 9))
+def test_every_number_of_slots(K, method):
+    g = GRIDS['maze11']()
+    vec, o = _pair(g, 200, 9, tile_coding(11, 11, K, 3), w0=-0.25)
+    try:
+        for T in (250, 130):
+            got = vec.fa_run(T, method, alpha=0.3 / K, discount_factor=0.95, epsilon=0.3, trajectory=True, stats=True)
+            _same(got, o.run(T, METHODS[method], 0.3 / K, 0.95, _eps(0.3)))
+            _tables(vec, o)
+        _state(vec, o)
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
+def test_identity_features_equal_td_run_on_a_twin(method):
+    g = GRIDS['test_env']()
+    S = g['W'] * g['H']
+    fa = gua.VecGridUniverse(300, template=_spec(g), seed=14)
+    td = gua.VecGridUniverse(300, template=_spec(g), seed=14)
+    try:
+        fa.set_features(*one_hot(S), w0=0.5)
+        td._ensure_q(0.5)
+        assert np.array_equal(fa.reset(), td.reset())
+        for T, alpha in ((400, 0.25), (1, 0.5), (333, 0.1)):
+            a = fa.fa_run(T, method, alpha=alpha, discount_factor=0.9, epsilon=0.15, trajectory=True, stats=True)
+            b = td.td_run(T, method, alpha=alpha, discount_factor=0.9, epsilon=0.15, trajectory=True, stats=True)
+            _same(a, b)
+            assert fa.weights().tobytes() == td.q_table().tobytes()
+            assert fa.fa_q_table().tobytes() == td.q_table().tobytes()
+    finally:
+        fa.close()
+        td.close()
+
+
+def _crowded_features(S, K, per_column, seed):
+    """Random column-disjoint phi with `per_column` distinct features per column: nearly every move keeps most of its slots."""
+    rs = np.random.RandomState(seed)
+    phi = np.stack([k * per_column + rs.randint(0, per_column, S) for k in range(K)], axis=1).astype(np.int32)
+    return phi, K * per_column
+
+
+@pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
+@pytest.mark.parametrize('K,per_column', [(1, 2), (3, 3), (4, 2), (8, 3), (2, 1), (8, 1)])  # per_column 1: F = K, all states share everything
+def test_forwarding_when_s_and_s2_share_slots(K, per_column, method):
+    g = GRIDS['maze11']()  # walls: bumps (s' == s) on top of the shared slots
+    vec, o = _pair(g, 257, 21, _crowded_features(g['W'] * g['H'], K, per_column, 100 + K), w0=0.125)
+    try:
+        for T in (300, 200):
+            got = vec.fa_run(T, method, alpha=0.2 / K, discount_factor=0.9, epsilon=0.4, trajectory=True, stats=True)
+            _same(got, o.run(T, METHODS[method], 0.2 / K, 0.9, _eps(0.4)))
+            _tables(vec, o)
+        _state(vec, o)
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
+def test_split_launches_with_changed_hyper_parameters(method):
+    g = GRIDS['test_env']()
+    vec, o = _pair(g, 130, 8, tile_coding(g['W'], g['H'], 4, 2))
+    try:
+        for alpha, gamma, eps in ((0.5 / 4, 0.95, 0.3), (0.1 / 4, 0.9, 0.05), (0.3 / 4, 0.99, 1.0), (0.2, 1.0, 0.0)):
+            got = vec.fa_run(257, method, alpha=alpha, discount_factor=gamma, epsilon=eps, trajectory=True, stats=True)
+            _same(got, o.run(257, METHODS[method], alpha, gamma, _eps(eps)))
+        _tables(vec, o)
+        _state(vec, o)
+    finally:
+        vec.close()
+
+
+def test_sarsa_carry_is_ended_by_reset_set_weights_another_learner_and_set_features():
+    g = GRIDS['open8x8']()
+    feats = tile_coding(8, 8, 4, 4)
+    vec, o = _pair(g, 200, 4, feats)
+    run = dict(alpha=0.05, discount_factor=0.9, epsilon=0.3, trajectory=True)
+    keys = ('obs', 'reward', 'done')
+    try:
+        _same(vec.fa_run(50, 'sarsa', **run), o.run(50, FA.SARSA, 0.05, 0.9, _eps(0.3)), keys)
+        _same(vec.fa_run(50, 'sarsa', **run), o.run(50, FA.SARSA, 0.05, 0.9, _eps(0.3)), keys)  # (carried)
+        assert np.array_equal(vec.reset(), o.reset())  # drops the carried action
+        _same(vec.fa_run(70, 'sarsa', **run), o.run(70, FA.SARSA, 0.05, 0.9, _eps(0.3)), keys)
+        vec.set_weights(o.w[:5] * 0.5, env0=3)  # ... and so does installing weights
+        o.set_w(o.w[:5] * 0.5, env0=3)
+        _same(vec.fa_run(70, 'sarsa', **run), o.run(70, FA.SARSA, 0.05, 0.9, _eps(0.3)), keys)
+        _tables(vec, o)
+        # ... a SARSA td_run in between: it neither takes gu_fa_run's action nor hands its own on
+        o.other_learner()
+        o.q = np.zeros((o.n, o.grid.S, 4))
+        got = vec.td_run(40, 'sarsa', alpha=0.1, discount_factor=0.9, epsilon=0.3, trajectory=True)
+        _same(got, O.TdOracle.run(o, 40, O.SARSA, 0.1, 0.9, _eps(0.3)), keys)
+        assert vec.q_table().tobytes() == o.q.tobytes()
+        o.other_learner()
+        _same(vec.fa_run(70, 'sarsa', **run), o.run(70, FA.SARSA, 0.05, 0.9, _eps(0.3)), keys)
+        _tables(vec, o)
+        # ... and set_features (here: other features, fresh weights)
+        feats = tile_coding(8, 8, 2, 3)
+        vec.set_features(*feats, w0=1.0)
+        o.set_features(*feats, w0=1.0)
+        _same(vec.fa_run(70, 'sarsa', **run), o.run(70, FA.SARSA, 0.05, 0.9, _eps(0.3)), keys)
+        _tables(vec, o)
+        _state(vec, o)
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
+@pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map and phi), one grid per env (global map and phi)
+def test_multigrid_learners_share_one_feature_table(method, n_grids, N):
+    grids = _random_grids(n_grids, 9, 9, 17)
+    phi, F = tile_coding(9, 9, 4, 3)
+    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
+    group = N // n_grids
+    oracles = [FA.FaOracle(_grid(g), 6, group, phi, F, env_id0=k * group) for k, g in enumerate(grids)]
+    try:
+        vec.set_features(phi, F)
+        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        for T in (150, 90):
+            got = vec.fa_run(T, method, alpha=0.05, discount_factor=0.9, epsilon=0.25, trajectory=True, stats=True)
+            parts = [o.run(T, METHODS[method], 0.05, 0.9, _eps(0.25)) for o in oracles]
+            _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
+        assert vec.weights().tobytes() == np.concatenate([o.w for o in oracles]).tobytes()
+        assert vec.fa_q_table().tobytes() == np.concatenate([o.q_tables() for o in oracles]).tobytes()
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
+def test_step_counts_across_the_epoch_boundary(method):
+    g = GRIDS['open8x8']()
+    N = 96
+    vec, o = _pair(g, N, 12, tile_coding(8, 8, 4, 4))
+    try:
+        tc = np.full(N, 2 ** 32 - 100, np.uint64)
+        tc[::3] += 7  # per-env counts: envs cross the boundary at different steps
+        vec.set_state(tcount=tc)
+        o.set_state(tcount=tc)
+        got = vec.fa_run(300, method, alpha=0.05, discount_factor=0.9, epsilon=0.5, trajectory=True, stats=True)
+        _same(got, o.run(300, METHODS[method], 0.05, 0.9, _eps(0.5)))
+        _tables(vec, o)
+        assert np.array_equal(vec.get_state()['tcount'], tc + np.uint64(300))
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
+@pytest.mark.parametrize('feats', ['tiles8x8', 'declared_70000'])
+def test_feature_tables_that_do_not_fit_lds_are_read_through_l2(method, feats):
+    # 64 x 64 cells: the planes take 8 KiB; K = 8 makes the uint16 table 64 KiB, and more than 65 536 features leave no uint16 table
+    W = H = 64
+    walls = [y * W + x for y in range(3, H - 2, 6) for x in range(W) if x % 7 != 3]
+    g = dict(W=W, H=H, starts=[0, W - 1], goals=[W * H - 1], lava=[W * H // 2 + 5], walls=walls)
+    phi, F = tile_coding(W, H, 8, 8) if feats == 'tiles8x8' else (tile_coding(W, H, 2, 4)[0], 70000)
+    vec, o = _pair(g, 130, 2, (phi, F), w0=0.5)
+    try:
+        for T in (200, 120):
+            got = vec.fa_run(T, method, alpha=0.03, discount_factor=0.9, epsilon=0.3, trajectory=True, stats=True)
+            _same(got, o.run(T, METHODS[method], 0.03, 0.9, _eps(0.3)))
+        _tables(vec, o)
+        _state(vec, o)
+    finally:
+        vec.close()
+
+
+def test_edges_epsilon_alpha_negative_zero_and_errors():
+    g = GRIDS['test_env']()
+    S = g['W'] * g['H']
+    feats = tile_coding(g['W'], g['H'], 3, 2)
+    vec, o = _pair(g, 64, 1, feats, w0=1.25)
+    try:
+        for eps in (0.0, 1.0):
+            got = vec.fa_run(120, 'q_learning', alpha=0.1, discount_factor=0.9, epsilon=eps, trajectory=True, stats=True)
+            _same(got, o.run(120, FA.Q_LEARNING, 0.1, 0.9, _eps(eps)))
+            _tables(vec, o)
+        before = vec.weights()
+        vec.fa_run(0, 'sarsa')  # T = 0 changes nothing
+        assert vec.weights().tobytes() == before.tobytes()
+        vec.set_features(*feats, w0=-0.0)  # three rows of -0.0 fold to -0.0: no slot adds a + 0.0
+        o.set_features(*feats, w0=-0.0)
+        assert vec.weights().tobytes() == np.full((64, feats[1], 4), -0.0).tobytes()
+        assert vec.fa_q_table().tobytes() == np.full((64, S, 4), -0.0).tobytes()
+        # alpha = 0: g is a zero, and -0.0 + (+0.0) is +0.0 -- the updated entries change sign, the others and their folds do not
+        got = vec.fa_run(200, 'sarsa', alpha=0.0, epsilon=0.4, trajectory=True, stats=True)
+        _same(got, o.run(200, FA.SARSA, 0.0, 0.99, _eps(0.4)))
+        _tables(vec, o)
+        assert np.signbit(vec.weights()).any() and not np.signbit(vec.weights()).all()
+        vec.set_features(*feats, w0=1.25)
+        vec.fa_run(200, 'sarsa', alpha=0.0, epsilon=0.4)
+        assert vec.weights().tobytes() == np.full((64, feats[1], 4), 1.25).tobytes()  # alpha = 0 on non-zero weights: w0 bit for bit
+        eng = vec.engine
+        for kw, code in ((dict(method=2), -1), (dict(eps_q16=65537), -1), (dict(alpha=float('nan')), -1), (dict(gamma=float('inf')), -1),
+                         (dict(T=-1), -1)):
+            args = dict(T=10, method=0, alpha=0.1, gamma=0.9, eps_q16=0)
+            args.update(kw)
+            with pytest.raises(gua.GuError) as err:
+                _lib.check(eng.lib.gu_fa_run(eng._h, args['T'], args['method'], args['alpha'], args['gamma'], args['eps_q16'], 0))
+            assert err.value.code == code, kw
+        with pytest.raises(gua.GuError) as err:  # a flag other than GU_F_TRAJECTORY / GU_F_STATS
+            _lib.check(eng.lib.gu_fa_run(eng._h, 10, 0, 0.1, 0.9, 0, _lib.F_AUTO_RESET))
+        assert err.value.code == -1
+        with pytest.raises(gua.GuError) as err:
+            eng.fa_get_w(60, 5)
+        assert err.value.code == -1
+        with pytest.raises(gua.GuError) as err:
+            eng.fa_get_q(60, 5)
+        assert err.value.code == -1
+        # feature tables gu_fa_init refuses; the installed one stays
+        ident = np.arange(S, dtype=np.int32)[:, None]
+        two = np.concatenate([ident, ident + S], axis=1)
+        for phi, F in ((np.zeros((S, 0), np.int32), 4), (np.zeros((S, 9), np.int32), 4), (ident, 0), (ident, S - 1), (ident - 1, S), (ident, 2 ** 26 + 1),
+                       (np.concatenate([ident, ident[::-1]], axis=1), S),  # every index in columns 0 and 1
+                       (np.where(two == S + 3, 2, two), 2 * S)):           # one index of column 0 in column 1
+            with pytest.raises(gua.GuError) as err:
+                eng.fa_init(phi, F)
+            assert err.value.code == -1, (phi.shape, F)
+        with pytest.raises(gua.GuError) as err:
+            eng.fa_init(ident, S, w0=float('inf'))
+        assert err.value.code == -1
+        assert vec.weights().shape == (64, feats[1], 4)
+        with pytest.raises(ValueError):
+            eng.fa_init(np.zeros((S + 1, 2), np.int32), 4)
+        with pytest.raises(ValueError):
+            eng.fa_set_w(np.zeros((2, feats[1] + 1, 4)))
+    finally:
+        vec.close()
+    with Engine(8, _spec(g)) as eng:
+        with pytest.raises(gua.GuError) as err:
+            _lib.check(eng.lib.gu_fa_run(eng._h, 10, 0, 0.1, 0.9, 0, 0))
+        assert err.value.code == -4
+        q = np.empty((8, S, 4))
+        with pytest.raises(gua.GuError) as err:
+            _lib.check(eng.lib.gu_fa_get_q(eng._h, 0, 8, _lib.ptr(q)))
+        assert err.value.code == -4
+        with pytest.raises(RuntimeError):
+            eng.fa_get_w()
+    vec = gua.VecGridUniverse(4, template=_spec(g))
+    try:
+        with pytest.raises(RuntimeError):
+            vec.fa_run(10)
+        with pytest.raises(RuntimeError):
+            vec.weights()
+    finally:
+        vec.close()
+
+
+def test_a_grid_of_another_size_drops_features_and_weights():
+    g = GRIDS['default4x4']()
+    vec, o = _pair(g, 16, 0, tile_coding(4, 4, 2, 2))
+    try:
+        vec.fa_run(20, 'q_learning')
+        vec.engine.set_grid(_spec(GRIDS['open8x8']()))
+        with pytest.raises(gua.GuError) as err:
+            vec.engine.fa_run(10)
+        assert err.value.code == -4
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('learn,method', [(semi_gradient_sarsa, FA.SARSA), (semi_gradient_q_learning, FA.Q_LEARNING)])
+def test_learning_end_to_end_equals_the_oracle_and_finds_the_shortest_path(learn, method):
+    env = gua.GridUniverseEnv((8, 8))
+    grid = C.Grid.from_env(env)
+    q = learn(env, 6000, alpha=0.2, discount_factor=0.9, epsilon=0.2, num_learners=32, seed=5)  # features: tile_coding(8, 8, 4, 4)
+    assert q.shape == (32, 64, 4)
+    phi, F = tile_coding(8, 8, 4, 4)
+    o = FA.FaOracle(grid, 5, 32, phi, F)
+    o.reset()
+    o.run(6000, method, 0.2 / 4, 0.9, _eps(0.2))
+    assert q.tobytes() == o.q_tables().tobytes()
+    dist = _bfs_lengths(grid)
+    for e in range(32):
+        assert np.array_equal(_greedy_walk_lengths(grid, q[e])[grid.starts], dist[grid.starts]), e
