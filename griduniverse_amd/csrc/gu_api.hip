@@ -16,6 +16,7 @@
 
 static void gu_dyna_free(gu_engine *h);  // (tabular Dyna-Q, below)
 static void gu_nstep_free(gu_engine *h);  // (tabular n-step learners, below)
+static void gu_search_free(gu_engine *h); // (rollout search, below)
 static void gu_lambda_free(gu_engine *h); // (tabular lambda learners, below)
 static void gu_ac_free(gu_engine *h);     // (tabular actor-critic, below)
 static void gu_reinforce_free(gu_engine *h);  // (tabular REINFORCE, below)
@@ -178,7 +179,7 @@ int gu_destroy(gu_handle h)
     void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
                     h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next,
                     h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_lambda_w, h->d_ac_h, h->d_ac_v, h->d_rf_buf, h->d_rf_cnt,
-                    h->d_fa_w, h->d_fa_phi, h->d_fa_phi16, h->d_fa_next};
+                    h->d_fa_w, h->d_fa_phi, h->d_fa_phi16, h->d_fa_next, h->d_search_score, h->d_search_steps};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -255,6 +256,7 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
         h->td_S = 0;
         gu_nstep_free(h);
         gu_lambda_free(h);
+        gu_search_free(h);
     }
     if (h->dyna_S && h->dyna_S != W * H) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
     if (h->ac_S && h->ac_S != W * H) gu_ac_free(h);  // ... and actor-critic tables: gu_ac_init again
@@ -1303,6 +1305,60 @@ int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32
     }
     if (list) GU_HIP(hipMemcpy(list, h->d_dyna_list + (size_t)env0 * pairs, k * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (count) GU_HIP(hipMemcpy(count, h->d_dyna_count + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return GU_OK;
+}
+
+static void gu_search_free(gu_engine *h)
+{
+    if (h->d_search_score) (void)hipFree(h->d_search_score);
+    if (h->d_search_steps) (void)hipFree(h->d_search_steps);
+    h->d_search_score = nullptr;
+    h->d_search_steps = nullptr;
+}
+
+int gu_search_run(gu_handle h, int64_t T, int32_t M, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
+                  uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(M >= 0 && M <= GU_SEARCH_MAX_M, GU_ERR_INVALID, "simulations %d out of range (0 .. %d)", M, GU_SEARCH_MAX_M);
+    GU_REQUIRE(D >= 0 && D <= GU_SEARCH_MAX_D, GU_ERR_INVALID, "depth %d out of range (0 .. %d)", D, GU_SEARCH_MAX_D);
+    GU_REQUIRE(eps_sim_q16 <= 65536u, GU_ERR_INVALID, "eps_sim_q16 %u above 65536", eps_sim_q16);
+    int rc = gu_tabular_check(h, "gu_search_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK) return rc;
+    const int64_t moves = 1 + 4 * (int64_t)M * D;  // per real step, at most
+    GU_REQUIRE(T * moves <= 100000000, GU_ERR_INVALID, "T %lld x (1 + 4 M D) = %lld moves out of range (0 .. 1e8)", (long long)T,
+               (long long)(T * moves));
+    if (T == 0) return GU_OK;
+    if (!h->d_search_score) {
+        GU_HIP(hipStreamSynchronize(h->stream));
+        rc = gu_tabular_fits(h, (size_t)h->N * (4 * sizeof(double) + sizeof(int64_t)), "search scores");
+        if (rc != GU_OK) return rc;
+        GU_HIP(hipMalloc(&h->d_search_score, (size_t)h->N * 4 * sizeof(double)));
+        GU_HIP(hipMalloc(&h->d_search_steps, (size_t)h->N * sizeof(int64_t)));
+        GU_HIP(hipMemsetAsync(h->d_search_score, 0, (size_t)h->N * 4 * sizeof(double), h->stream));
+        GU_HIP(hipMemsetAsync(h->d_search_steps, 0, (size_t)h->N * sizeof(int64_t), h->stream));
+    }
+    return gu_launch_search(h, T, M, D, alpha, gamma, eps_q16, eps_sim_q16, flags);
+}
+
+int gu_search_get(gu_handle h, int64_t env0, int64_t n, double *score, int64_t *sim_steps)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    int rc = gu_env_range(h, env0, n);
+    if (rc != GU_OK) return rc;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!n) return GU_OK;
+    if (!h->d_search_score) {  // (nothing searched yet: what the storage holds right after its allocation)
+        if (score) std::fill(score, score + (size_t)n * 4, 0.0);
+        if (sim_steps) std::fill(sim_steps, sim_steps + (size_t)n, (int64_t)0);
+        return GU_OK;
+    }
+    if (score) GU_HIP(hipMemcpy(score, h->d_search_score + (size_t)env0 * 4, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    if (sim_steps) GU_HIP(hipMemcpy(sim_steps, h->d_search_steps + env0, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
     return GU_OK;
 }
 

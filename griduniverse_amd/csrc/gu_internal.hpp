@@ -294,6 +294,9 @@ struct gu_engine {
     uint8_t *d_dyna_seen = nullptr;    // [N][dyna_S] bit a of byte s: (s, a) observed (the real step's test while dyna_exact)
     int32_t dyna_S = 0;                // states of the model (0: none allocated); a grid of another size drops it
     bool dyna_exact = false;           // every observed entry is what the current grid gives: no grid install since gu_dyna_init
+    // batched rollout search (gu_search.hip): decides and learns on d_q; allocated on first use, dropped with the tables
+    double *d_search_score = nullptr;   // [N][4] the score row of each env's most recent searched iteration
+    int64_t *d_search_steps = nullptr;  // [N] simulated moves of the last launch
 
     // agent trail (gu_trail.hip): off unless gu_trail_enable was called
     int32_t trail_cap = 0;             // entries per env (0: off)
@@ -432,6 +435,10 @@ int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, double g
 
 // ---- batched tabular Dyna-Q (gu_dyna.hip) -------------------------------------------
 int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+
+// ---- batched rollout search at decision time (gu_search.hip) --------------------------
+int gu_launch_search(gu_engine *h, int64_t T, int32_t M, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
+                     uint32_t flags);
 
 // ---- batched tabular n-step Q-learning / SARSA (gu_nstep.hip) --------------------------
 // the carry key of a gu_nstep_run (never 0): the next launch keeps the window only under the same method and n

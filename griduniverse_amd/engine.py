@@ -360,6 +360,25 @@ class Engine(object):
                                          ptr(out['list']), ptr(out['count'])))
         return out
 
+    # ------------------------------------------------------------------ rollout search at decision time (include/gu.h: gu_search_*)
+    def search_run(self, T, simulations=4, depth=16, alpha=0.1, gamma=0.99, eps_q16=6554, eps_sim_q16=65536, trajectory=False,
+                   stats=False):
+        """T real steps per env in one launch, each non-exploring one chosen by `simulations` (0 .. SEARCH_MAX_M) simulated rollouts
+        per action of `depth` (0 .. SEARCH_MAX_D) moves with the true model, under an epsilon-greedy rollout policy (eps_sim_q16;
+        65536 = uniform) on the td_init tables, which then learn from the real transition by Q-learning.  simulations = 0 is
+        td_run('q_learning').  Rows and statistics (real steps only) as td_run()."""
+        check(self.lib.gu_search_run(self._h, int(T), int(simulations), int(depth), float(alpha), float(gamma), int(eps_q16),
+                                     int(eps_sim_q16), _learner_flags(trajectory, stats)))
+
+    def search_get(self, env0=0, n=None):
+        """Of envs env0 .. env0+n-1: dict score float64[n, 4] (the summed returns per action of the env's most recent searched
+        step; zeros until there is one) and sim_steps int64[n] (simulated moves of the last launch)."""
+        n = self.N - int(env0) if n is None else int(n)
+        n0 = max(n, 0)
+        out = dict(score=np.empty((n0, 4), np.float64), sim_steps=np.empty(n0, np.int64))
+        check(self.lib.gu_search_get(self._h, int(env0), n, ptr(out['score']), ptr(out['sim_steps'])))
+        return out
+
     # ------------------------------------------------------------------ tabular n-step Q-learning / SARSA (include/gu.h: gu_nstep_*)
     def nstep_run(self, T, method='sarsa', n=4, alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
         """T iterations of n-step Q-learning / SARSA per env in one launch, into the td_init tables.  The window of pending

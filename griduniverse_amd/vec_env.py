@@ -166,6 +166,30 @@ class VecGridUniverse(object):
         self._ensure_model()
         return self.engine.dyna_get_model(env0, n)
 
+    def search_run(self, T, simulations=4, depth=16, alpha=0.1, discount_factor=0.99, epsilon=0.1, rollout_epsilon=1.0, trajectory=False,
+                   stats=False):
+        """T real steps of batched simulation-based search (Monte-Carlo rollouts at decision time): before each non-exploring
+        real move, env e simulates `simulations` (0 .. 64) rollouts of `depth` (0 .. 256) moves per action with the true model, under
+        an epsilon-greedy rollout policy on its own Q table (`rollout_epsilon`; 1.0 = uniformly random), bootstraps a truncated
+        rollout on max Q at its leaf, takes the action with the largest summed return and learns from the real transition by
+        Q-learning (include/gu.h: gu_search_run).  An exploring step (`epsilon`) simulates nothing; simulations = 0 is
+        td_run('q_learning').  The first call gives every env a table of zeros.  Rows and statistics cover the real steps, as
+        td_run()."""
+        for name, v in (('epsilon', epsilon), ('rollout_epsilon', rollout_epsilon)):
+            if not 0.0 <= float(v) <= 1.0:
+                raise ValueError('{} must lie in [0, 1]'.format(name))
+        self._ensure_q()
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.search_run(T, simulations, depth, alpha, discount_factor, int(round(float(epsilon) * 65536)),
+                               int(round(float(rollout_epsilon) * 65536)), trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def search_scores(self, env0=0, n=None):
+        """Engine.search_get: the score rows of the most recent searched steps and the simulated moves of the last search_run."""
+        self._ensure_q()
+        return self.engine.search_get(env0, n)
+
     def nstep_run(self, T, n=4, method='sarsa', alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
         """T iterations of batched tabular n-step SARSA ('sarsa') or n-step Q-learning ('q_learning'), 1 <= n <= 16: env e learns
         its own Q table [S][4] from n-step returns (include/gu.h: gu_nstep_run).  The first call gives every env a table of zeros.

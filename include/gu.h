@@ -262,7 +262,7 @@ int gu_done_indices(gu_handle h, int32_t *idx, int32_t *count);
  *      the row maximum exactly, in ascending order, the one at index (((w >> 2) & 0x3FFF) * m) >> 14.  SARSA uses the carried
  *      action a' instead -- inside a launch always, and at its start when it directly follows a SARSA gu_td_run on this engine
  *      (no gu_seed, gu_reset*, gu_step*, gu_rollout, gu_set_state, gu_set_grid(s), gu_generate_mazes, gu_td_init, gu_td_set_q, gu_dyna_run,
- *      gu_nstep_run or sweep-step call in between);
+ *      gu_nstep_run, gu_search_run or sweep-step call in between);
  *   3. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
  *   4. float64, one rounding per operation: m = max Q_e[s'] (Q-learning) or Q_e[s'][a'] with a' drawn at s' by rule 2 from the word
  *      of the new t and the pre-update row (SARSA; not drawn when d); target = r if d else r + gamma * m;
@@ -307,6 +307,47 @@ int gu_dyna_init(gu_handle h);
 int gu_dyna_run(gu_handle h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32_t *reward, int32_t *done, int32_t *list, int32_t *count);
 
+/* ---- batched simulation-based search: learner e owns env e and its table Q_e[S][4] (the gu_td_* tables) and plans at decision time ----
+ * (build-defined: the second half of the reference's roadmap entry "Integrating learning and planning (Dyna, MC/TD Tree search,
+ * Forward and Simulation-based search)", for which it ships no code; the "rollout algorithm" of Sutton & Barto 8.10, "simple
+ * Monte-Carlo search" of Silver's lecture 8; tests/_search_oracle.py is the CPU restatement.)  gu_dyna_run plans in the background
+ * from a LEARNED model; this learner plans before each real move, from the current state, with the TRUE model: the engine's move
+ * rule.  It chooses each non-exploring real action by M simulated rollouts per action, of depth D, under an epsilon-greedy rollout
+ * policy on Q_e; a truncated rollout bootstraps on max Q_e at its leaf; the real transition is learned from by Q-learning.
+ * One iteration of gu_search_run for env e at 64-bit step count t:
+ *   1. reset: lazy auto-reset, exactly as rule 1 of gu_td_run;
+ *   2. w = the stream-4 word at t (as rule 2 of gu_td_run);
+ *   3. action.  If (w >> 16) < eps_q16: a = w & 3 and NO simulation is run.  Else if M = 0: a by rule 2 of gu_td_run on Q_e[s].
+ *      Else search: for each action b = 0 .. 3 in order, (s1, r1, d1) is the move rule from (s, b) -- the env itself does not
+ *      move --, and for j = 0 .. M-1:
+ *        G = (double)r1, disc = gamma, x = s1, dn = d1;
+ *        for i = 0 .. D-1, while not dn: c = ((t * 4 + b) * M + j) * D + i (uint64, wrapping); w' = the word of RNG stream 6
+ *          with counter c & 0xFFFFFFFF and epoch c >> 32 (keyed like streams 4 and 5); u = rule 2 of gu_td_run applied to the
+ *          row Q_e[x] with w' and eps_sim_q16; (x', r', dn) = the move rule from (x, u); G = G + disc * r', then
+ *          disc = disc * gamma, then x = x';
+ *        after the loop, if not dn: G = G + disc * max Q_e[x], folded left to right with `>`;
+ *      score_b = ((G_0 + G_1) + ...) + G_{M-1} -- sums, not means: no division.  a = the tie rule of rule 2 applied to the score
+ *      row with w: the k-th (ascending) of the m exactly-maximal actions, k = (((w >> 2) & 0x3FFF) * m) >> 14.  No table entry is
+ *      written during a search;
+ *   4. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
+ *   5. the Q-learning update of rule 4 of gu_td_run, method 0, on Q_e[s][a];
+ *   6. the next iteration sees the updated table.
+ * All float64, one rounding per operation, multiply / add / subtract only.  With M = 0 this is gu_td_run, method 0, byte for byte,
+ * for any D and eps_sim_q16.  There is no carry; gu_search_run ends every other learner's carry, window and episode buffer.
+ * gu_search_run : T iterations per env in ONE launch (async).  GU_ERR_STATE before gu_td_init; GU_ERR_INVALID for M outside
+ *                 0 .. GU_SEARCH_MAX_M, D outside 0 .. GU_SEARCH_MAX_D, either epsilon above 65536, T * (1 + 4 M D) > 1e8
+ *                 (gu_dyna_run's launch bound) and everything gu_td_run rejects.  T = 0 changes nothing.  Flags, rows, statistics,
+ *                 the agent trail and the step counts as gu_td_run: the T real steps only.
+ * gu_search_get : of envs env0 .. env0+n-1 on the host: score as [n][4], the score row of each env's most recent SEARCHED
+ *                 iteration (zeros until there is one); sim_steps as [n], the simulated moves of the last launch (the inner i
+ *                 steps only, not the four first moves).  Either pointer may be NULL.  The storage (N * 40 bytes) is allocated on
+ *                 first use (GU_ERR_NOMEM under gu_td_init's free-memory rule); a grid of another size drops it with the tables. */
+#define GU_SEARCH_MAX_M 64
+#define GU_SEARCH_MAX_D 256
+int gu_search_run(gu_handle h, int64_t T, int32_t M, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
+                  uint32_t flags);
+int gu_search_get(gu_handle h, int64_t env0, int64_t n, double *score, int64_t *sim_steps);
+
 /* ---- batched tabular n-step Q-learning and n-step SARSA: learner e owns env e and its table Q_e[S][4] (the gu_td_* tables) ----
  * (build-defined: the reference lists "Temporal Difference (TD) Learning with variations" on its roadmap and ships no code;
  * Sutton & Barto ch. 7; method 0 is the uncorrected n-step Q-learning of asynchronous n-step Q-learning, Mnih et al. 2016;
@@ -326,7 +367,7 @@ int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32
  * All float64, one rounding per operation (multiply, then add).  With n = 1 this is gu_td_run, byte for byte, for both methods.
  * CARRY: the window and SARSA's a' persist from one gu_nstep_run to the next when the later call directly follows the earlier one
  * with the same method and n.  Any other call in between -- everything that ends gu_td_run's SARSA carry, gu_td_run,
- * gu_dyna_run, a gu_nstep_run with another method or n -- drops both; the pending updates are discarded, not flushed.
+ * gu_dyna_run, gu_search_run, a gu_nstep_run with another method or n -- drops both; the pending updates are discarded, not flushed.
  * gu_nstep_run ends gu_td_run's SARSA carry.
  * gu_nstep_run        : T iterations per env in ONE launch (async).  method 0 = n-step Q-learning, 1 = n-step SARSA; 1 <= n <=
  *                       GU_NSTEP_MAX.  GU_ERR_STATE before gu_td_init; GU_ERR_INVALID for a bad method or n and everything
@@ -361,7 +402,7 @@ int gu_nstep_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32
  * With K = 1 (any lambda) or lambda = 0 (any K) this is gu_td_run, byte for byte: method 0 is Q-learning, 1 is SARSA.
  * CARRY: the window and SARSA's a' persist from one gu_lambda_run to the next when the later call directly follows the earlier one
  * with the same method and K (alpha, gamma and lambda may change: the ages carry, the new c applies).  Any other call in between --
- * everything that ends gu_td_run's SARSA carry, gu_td_run, gu_dyna_run, gu_nstep_run, gu_ac_run, a gu_lambda_run with another
+ * everything that ends gu_td_run's SARSA carry, gu_td_run, gu_dyna_run, gu_nstep_run, gu_ac_run, gu_search_run, a gu_lambda_run with another
  * method or K -- drops both.  gu_lambda_run ends gu_td_run's SARSA carry and gu_nstep_run's window.
  * gu_lambda_run        : T iterations per env in ONE launch (async).  method 0 = Watkins's Q(lambda), 1 = SARSA(lambda); 1 <= K
  *                        <= GU_LAMBDA_MAX; 0 <= lambda <= 1.  GU_ERR_STATE before gu_td_init; GU_ERR_INVALID for a bad method,
@@ -434,7 +475,7 @@ int gu_ac_set(gu_handle h, int64_t env0, int64_t n, const double *pref, const do
  * With alpha_baseline = 0 and V = 0 this is plain REINFORCE.  With L = 1 it is gu_ac_run, byte for byte.
  * CARRY: the buffer persists from one gu_reinforce_run to the next when the later call directly follows the earlier one with the
  * same L (the rates and gamma may change).  Any other call in between -- everything that drops gu_lambda_run's window, and
- * gu_td_run, gu_dyna_run, gu_nstep_run, gu_lambda_run, gu_ac_run, gu_ac_init, gu_ac_set, a gu_reinforce_run with another L --
+ * gu_td_run, gu_dyna_run, gu_nstep_run, gu_lambda_run, gu_ac_run, gu_search_run, gu_ac_init, gu_ac_set, a gu_reinforce_run with another L --
  * drops it: the pending transitions are discarded, not learned from.  gu_reinforce_run ends gu_td_run's SARSA carry and the
  * windows of gu_nstep_run and gu_lambda_run.
  * gu_reinforce_run         : T iterations per env in ONE launch (async).  1 <= L <= GU_REINFORCE_MAX.  GU_ERR_STATE before
