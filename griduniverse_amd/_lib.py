@@ -29,6 +29,9 @@ LAMBDA_MAX = 64  # GU_LAMBDA_MAX: the largest K (trace length) of gu_lambda_run
 REINFORCE_MAX = 1024  # GU_REINFORCE_MAX: the largest L (segment length) of gu_reinforce_run
 SEARCH_MAX_M = 64   # GU_SEARCH_MAX_M: the most rollouts per action of gu_search_run
 SEARCH_MAX_D = 256  # GU_SEARCH_MAX_D: their largest depth
+EXPLORE_MAX_C = 4096  # GU_EXPLORE_MAX_C: the most entries of gu_explore_set_tables' U and B
+EXPLORE_COUNT_MAX = 0x3FFFFFFF  # GU_EXPLORE_COUNT_MAX: where a visit count saturates
+EXPLORE_UCB, EXPLORE_THOMPSON = 0, 1
 FA_MAX_K = 8  # GU_FA_MAX_K: the most active features per state of gu_fa_init
 COMM_ID_BYTES = 128
 OPT_UNSET = -2 ** 63
@@ -95,6 +98,11 @@ SIGNATURES = {
     'gu_dyna_get_model': [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
     'gu_search_run': [_vp, _i64, _i32, _i32, _f64, _f64, _u32, _u32, _u32],
     'gu_search_get': [_vp, _i64, _i64, _vp, _vp],
+    'gu_explore_init': [_vp],
+    'gu_explore_set_tables': [_vp, _i32, _vp, _vp],
+    'gu_explore_run': [_vp, _i64, _i32, _f64, _f64, _u32, _u32],
+    'gu_explore_get_counts': [_vp, _i64, _i64, _vp],
+    'gu_explore_set_counts': [_vp, _i64, _i64, _vp],
     'gu_nstep_run': [_vp, _i64, _i32, _i32, _f64, _f64, _u32, _u32],
     'gu_nstep_get_window': [_vp, _i64, _i64, _vp, _vp, _vp],
     'gu_lambda_run': [_vp, _i64, _i32, _i32, _f64, _f64, _f64, _u32, _u32],

@@ -17,6 +17,7 @@
 static void gu_dyna_free(gu_engine *h);  // (tabular Dyna-Q, below)
 static void gu_nstep_free(gu_engine *h);  // (tabular n-step learners, below)
 static void gu_search_free(gu_engine *h); // (rollout search, below)
+static void gu_explore_free(gu_engine *h);  // (the counts of the count-based exploration, below)
 static void gu_lambda_free(gu_engine *h); // (tabular lambda learners, below)
 static void gu_ac_free(gu_engine *h);     // (tabular actor-critic, below)
 static void gu_reinforce_free(gu_engine *h);  // (tabular REINFORCE, below)
@@ -179,7 +180,7 @@ int gu_destroy(gu_handle h)
     void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
                     h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next,
                     h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_lambda_w, h->d_ac_h, h->d_ac_v, h->d_rf_buf, h->d_rf_cnt,
-                    h->d_fa_w, h->d_fa_phi, h->d_fa_phi16, h->d_fa_next, h->d_search_score, h->d_search_steps};
+                    h->d_fa_w, h->d_fa_phi, h->d_fa_phi16, h->d_fa_next, h->d_search_score, h->d_search_steps, h->d_explore_n, h->d_explore_tab};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -258,6 +259,7 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
         gu_lambda_free(h);
         gu_search_free(h);
     }
+    if (h->explore_S && h->explore_S != W * H) gu_explore_free(h);  // ... and the visit counts: gu_explore_init again (the U and B tables stay)
     if (h->dyna_S && h->dyna_S != W * H) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
     if (h->ac_S && h->ac_S != W * H) gu_ac_free(h);  // ... and actor-critic tables: gu_ac_init again
     if (h->fa_S && h->fa_S != W * H) gu_fa_free(h);  // ... and features and weights: gu_fa_init again
@@ -1359,6 +1361,99 @@ int gu_search_get(gu_handle h, int64_t env0, int64_t n, double *score, int64_t *
     }
     if (score) GU_HIP(hipMemcpy(score, h->d_search_score + (size_t)env0 * 4, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
     if (sim_steps) GU_HIP(hipMemcpy(sim_steps, h->d_search_steps + env0, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return GU_OK;
+}
+
+static void gu_explore_free(gu_engine *h)
+{
+    if (h->d_explore_n) (void)hipFree(h->d_explore_n);
+    h->d_explore_n = nullptr;
+    h->explore_S = 0;
+}
+
+int gu_explore_init(gu_handle h)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    const size_t bytes = (size_t)h->N * (size_t)h->S * 4 * sizeof(uint32_t);
+    if (!h->d_explore_n || h->explore_S != h->S) {
+        GU_HIP(hipStreamSynchronize(h->stream));
+        gu_explore_free(h);
+        int rc = gu_tabular_fits(h, bytes, "visit counts");
+        if (rc != GU_OK) return rc;
+        GU_HIP(hipMalloc(&h->d_explore_n, bytes));
+        h->explore_S = h->S;
+    }
+    GU_HIP(hipMemsetAsync(h->d_explore_n, 0, bytes, h->stream));
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_explore_set_tables(gu_handle h, int32_t C, const double *U, const double *B)
+{
+    GU_ENTER(h);
+    GU_REQUIRE(C >= 2 && C <= GU_EXPLORE_MAX_C, GU_ERR_INVALID, "table size %d out of range (2 .. %d)", C, GU_EXPLORE_MAX_C);
+    GU_REQUIRE(U != nullptr && B != nullptr, GU_ERR_INVALID, "U or B is NULL");
+    for (int32_t k = 0; k < C; ++k)
+        GU_REQUIRE(std::isfinite(U[k]) && U[k] >= 0.0 && std::isfinite(B[k]) && B[k] >= 0.0, GU_ERR_INVALID,
+                   "entry %d (U %g, B %g): every entry must be finite and not negative", k, U[k], B[k]);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (h->explore_C != C) {
+        if (h->d_explore_tab) GU_HIP(hipFree(h->d_explore_tab));
+        h->d_explore_tab = nullptr;
+        h->explore_C = 0;
+        GU_HIP(hipMalloc(&h->d_explore_tab, (size_t)C * 2 * sizeof(double)));
+        h->explore_C = C;
+    }
+    GU_HIP(hipMemcpy(h->d_explore_tab, U, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
+    GU_HIP(hipMemcpy(h->d_explore_tab + C, B, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
+    return GU_OK;
+}
+
+int gu_explore_run(gu_handle h, int64_t T, int32_t mode, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(h->d_explore_n && h->explore_S == h->S, GU_ERR_STATE, "no visit counts: call gu_explore_init first");
+    GU_REQUIRE(h->d_explore_tab && h->explore_C >= 2, GU_ERR_STATE, "no exploration tables: call gu_explore_set_tables first");
+    GU_REQUIRE(mode == 0 || mode == 1, GU_ERR_INVALID, "mode %d: 0 = UCB, 1 = Thompson", mode);
+    int rc = gu_tabular_check(h, "gu_explore_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    return gu_launch_explore(h, T, mode, alpha, gamma, eps_q16, flags);
+}
+
+static int gu_explore_range(gu_engine *h, int64_t env0, int64_t n, const void *counts)
+{
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_explore_n && h->explore_S == h->S, GU_ERR_STATE, "no visit counts: call gu_explore_init first");
+    GU_REQUIRE(counts != nullptr, GU_ERR_INVALID, "counts is NULL");
+    return gu_env_range(h, env0, n);
+}
+
+int gu_explore_get_counts(gu_handle h, int64_t env0, int64_t n, uint32_t *counts)
+{
+    GU_ENTER(h);
+    int rc = gu_explore_range(h, env0, n, counts);
+    if (rc != GU_OK) return rc;
+    const size_t row = (size_t)h->S * 4;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n) GU_HIP(hipMemcpy(counts, h->d_explore_n + (size_t)env0 * row, (size_t)n * row * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return GU_OK;
+}
+
+int gu_explore_set_counts(gu_handle h, int64_t env0, int64_t n, const uint32_t *counts)
+{
+    GU_ENTER(h);
+    int rc = gu_explore_range(h, env0, n, counts);
+    if (rc != GU_OK) return rc;
+    const size_t row = (size_t)h->S * 4, k = (size_t)n * row;
+    for (size_t i = 0; i < k; ++i)
+        GU_REQUIRE(counts[i] <= GU_EXPLORE_COUNT_MAX, GU_ERR_INVALID, "count %u of env %lld above the cap 0x%X", counts[i],
+                   (long long)(env0 + (int64_t)(i / row)), GU_EXPLORE_COUNT_MAX);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n) GU_HIP(hipMemcpy(h->d_explore_n + (size_t)env0 * row, counts, k * sizeof(uint32_t), hipMemcpyHostToDevice));
     return GU_OK;
 }
 

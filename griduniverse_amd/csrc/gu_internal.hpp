@@ -297,6 +297,11 @@ struct gu_engine {
     // batched rollout search (gu_search.hip): decides and learns on d_q; allocated on first use, dropped with the tables
     double *d_search_score = nullptr;   // [N][4] the score row of each env's most recent searched iteration
     int64_t *d_search_steps = nullptr;  // [N] simulated moves of the last launch
+    // batched count-based exploration (gu_explore.hip): off until gu_explore_init; chooses by and learns into d_q
+    uint32_t *d_explore_n = nullptr;   // [N][explore_S][4] visit counts, saturating at GU_EXPLORE_COUNT_MAX
+    int32_t explore_S = 0;             // states of the counts (0: none allocated); a grid of another size drops them
+    double *d_explore_tab = nullptr;   // U[explore_C] | B[explore_C], shared by all envs (gu_explore_set_tables)
+    int32_t explore_C = 0;             // entries of each (0: no tables yet)
 
     // agent trail (gu_trail.hip): off unless gu_trail_enable was called
     int32_t trail_cap = 0;             // entries per env (0: off)
@@ -439,6 +444,9 @@ int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, double gamm
 // ---- batched rollout search at decision time (gu_search.hip) --------------------------
 int gu_launch_search(gu_engine *h, int64_t T, int32_t M, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
                      uint32_t flags);
+
+// ---- batched count-based exploration: UCB / Thompson Q-learning (gu_explore.hip) ---------
+int gu_launch_explore(gu_engine *h, int64_t T, int32_t mode, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 
 // ---- batched tabular n-step Q-learning / SARSA (gu_nstep.hip) --------------------------
 // the carry key of a gu_nstep_run (never 0): the next launch keeps the window only under the same method and n

@@ -14,6 +14,7 @@ from .grid import GridSpec
 
 _POLICIES = {'uniform': _lib.POLICY_UNIFORM, 'stream': _lib.POLICY_STREAM, 'greedy': _lib.POLICY_GREEDY,
              'sample': _lib.POLICY_SAMPLE}
+_EXPLORE_RULES = {'ucb': _lib.EXPLORE_UCB, 'thompson': _lib.EXPLORE_THOMPSON, 0: _lib.EXPLORE_UCB, 1: _lib.EXPLORE_THOMPSON}
 _TD_METHODS = {'q_learning': _lib.TD_Q_LEARNING, 'sarsa': _lib.TD_SARSA, 0: _lib.TD_Q_LEARNING, 1: _lib.TD_SARSA}
 
 
@@ -378,6 +379,44 @@ class Engine(object):
         out = dict(score=np.empty((n0, 4), np.float64), sim_steps=np.empty(n0, np.int64))
         check(self.lib.gu_search_get(self._h, int(env0), n, ptr(out['score']), ptr(out['sim_steps'])))
         return out
+
+    # ------------------------------------------------------------------ count-based exploration (include/gu.h: gu_explore_*)
+    def explore_init(self):
+        """Zeroed visit counts uint32 [S][4] per env; the Q tables come from td_init."""
+        check(self.lib.gu_explore_init(self._h))
+
+    def set_exploration(self, U, B):
+        """The exploration schedule: float64 U[C] and B[C], 2 <= C <= EXPLORE_MAX_C, every entry finite and >= 0.  The bonus of
+        action b in a state visited n_s times is U[min(n_s, C-1)] * B[min(n_b, C-1)] (algorithms.exploration builds both)."""
+        U, B = _lib.as_array(U, np.float64, None, 'U'), _lib.as_array(B, np.float64, None, 'B')
+        if U.ndim != 1 or U.shape != B.shape:
+            raise ValueError('U and B must be vectors of one length, got {} and {}'.format(U.shape, B.shape))
+        check(self.lib.gu_explore_set_tables(self._h, U.shape[0], ptr(U), ptr(B)))
+
+    def explore_run(self, T, rule='ucb', alpha=0.1, gamma=0.99, eps_q16=0, trajectory=False, stats=False):
+        """T Q-learning iterations per env in one launch whose non-exploring actions are greedy on Q + bonus ('ucb') or on
+        Q + bonus * noise ('thompson'), the bonus from the env's visit counts and the set_exploration tables.  With tables of
+        zeros it is td_run('q_learning').  Rows and statistics as td_run()."""
+        check(self.lib.gu_explore_run(self._h, int(T), _EXPLORE_RULES[rule], float(alpha), float(gamma), int(eps_q16),
+                                      _learner_flags(trajectory, stats)))
+
+    def explore_get_counts(self, env0=0, n=None):
+        """uint32[n, S, 4]: the visit counts of envs env0 .. env0+n-1 (all from env0 when n is None)."""
+        n = self.N - int(env0) if n is None else int(n)
+        c = np.empty((max(n, 0), self.spec.S, 4), np.uint32)
+        check(self.lib.gu_explore_get_counts(self._h, int(env0), n, ptr(c)))
+        return c
+
+    def explore_set_counts(self, counts, env0=0):
+        """Install counts uint32[n, S, 4] (or [S, 4] for one env) for envs env0 .. env0+n-1; none above EXPLORE_COUNT_MAX."""
+        c = np.asarray(counts)
+        if c.size and (c.min() < 0 or c.max() > 0xFFFFFFFF):
+            raise ValueError('counts must fit uint32')
+        c = c.astype(np.uint32)
+        c = np.ascontiguousarray(c.reshape((-1, self.spec.S, 4)) if c.ndim == 2 else c)
+        if c.ndim != 3 or c.shape[1:] != (self.spec.S, 4):
+            raise ValueError('counts must have shape (n, {}, 4), got {}'.format(self.spec.S, c.shape))
+        check(self.lib.gu_explore_set_counts(self._h, int(env0), c.shape[0], ptr(c)))
 
     # ------------------------------------------------------------------ tabular n-step Q-learning / SARSA (include/gu.h: gu_nstep_*)
     def nstep_run(self, T, method='sarsa', n=4, alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):

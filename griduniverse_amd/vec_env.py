@@ -23,6 +23,8 @@ from .grid import GridSpec
 class VecGridUniverse(object):
     _td_ready = False  # the engine holds Q tables (td_run / set_q_table allocate them on first use)
     _dyna_ready = False  # ... and Dyna-Q models (dyna_run / model allocate them on first use)
+    _explore_ready = False  # ... and visit counts (explore_run / visit_counts allocate them on first use)
+    _explore_tables = False  # set_exploration was called
     _ac_ready = False  # ... and actor-critic tables (actor_critic_run / set_actor_critic allocate them on first use)
     _fa_ready = False  # ... and features with their weights (set_features installs them; nothing does it implicitly)
 
@@ -189,6 +191,48 @@ class VecGridUniverse(object):
         """Engine.search_get: the score rows of the most recent searched steps and the simulated moves of the last search_run."""
         self._ensure_q()
         return self.engine.search_get(env0, n)
+
+    def _ensure_counts(self):
+        """Visit counts on the engine: zeroed counts on first use (and tables of zeros if the envs had no Q tables)."""
+        self._ensure_q()
+        if not self._explore_ready:
+            self.engine.explore_init()
+            self._explore_ready = True
+
+    def set_exploration(self, U, B):
+        """The exploration schedule of explore_run: float64 vectors U and B of one length C, 2 <= C <= 4096, finite and >= 0.  The
+        bonus of action b in a state visited n_s times is U[min(n_s, C-1)] * B[min(n_b, C-1)]; algorithms.exploration.ucb_tables
+        and thompson_tables build the two usual schedules."""
+        self.engine.set_exploration(U, B)
+        self._explore_tables = True
+
+    def explore_run(self, T, rule='ucb', alpha=0.1, discount_factor=0.99, epsilon=0.0, trajectory=False, stats=False):
+        """T steps of batched tabular Q-learning with count-based exploration: env e keeps visit counts [S][4] beside its Q table
+        and takes, where it does not explore by `epsilon`, the action that maximises Q + bonus ('ucb') or Q + bonus * noise
+        ('thompson': four approximate normals per step from RNG stream 7), the bonus from its counts and the set_exploration
+        tables (include/gu.h: gu_explore_run).  The update is td_run('q_learning')'s: the bonus never enters the table.  The
+        first call gives every env zeroed counts (and a table of zeros if it had none).  Rows and statistics as td_run()."""
+        if rule not in ('ucb', 'thompson'):
+            raise ValueError("rule must be 'ucb' or 'thompson'")
+        if not 0.0 <= float(epsilon) <= 1.0:
+            raise ValueError('epsilon must lie in [0, 1]')
+        if not self._explore_tables:
+            raise ValueError('no exploration schedule: call set_exploration(U, B) first')
+        self._ensure_counts()
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.explore_run(T, rule, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def visit_counts(self, env0=0, n=None):
+        """uint32[n, S, 4]: the visit counts of envs env0 .. env0+n-1 (to the end when n is None); zeros before the first explore_run."""
+        self._ensure_counts()
+        return self.engine.explore_get_counts(env0, n)
+
+    def set_visit_counts(self, counts, env0=0):
+        """Install visit counts uint32[n, S, 4] (or [S, 4]) for envs env0 ..; no value above 0x3FFFFFFF, where the counts saturate."""
+        self._ensure_counts()
+        self.engine.explore_set_counts(counts, env0)
 
     def nstep_run(self, T, n=4, method='sarsa', alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
         """T iterations of batched tabular n-step SARSA ('sarsa') or n-step Q-learning ('q_learning'), 1 <= n <= 16: env e learns

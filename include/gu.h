@@ -262,7 +262,7 @@ int gu_done_indices(gu_handle h, int32_t *idx, int32_t *count);
  *      the row maximum exactly, in ascending order, the one at index (((w >> 2) & 0x3FFF) * m) >> 14.  SARSA uses the carried
  *      action a' instead -- inside a launch always, and at its start when it directly follows a SARSA gu_td_run on this engine
  *      (no gu_seed, gu_reset*, gu_step*, gu_rollout, gu_set_state, gu_set_grid(s), gu_generate_mazes, gu_td_init, gu_td_set_q, gu_dyna_run,
- *      gu_nstep_run, gu_search_run or sweep-step call in between);
+ *      gu_nstep_run, gu_search_run, gu_explore_run or sweep-step call in between);
  *   3. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
  *   4. float64, one rounding per operation: m = max Q_e[s'] (Q-learning) or Q_e[s'][a'] with a' drawn at s' by rule 2 from the word
  *      of the new t and the pre-update row (SARSA; not drawn when d); target = r if d else r + gamma * m;
@@ -347,6 +347,51 @@ int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32
 int gu_search_run(gu_handle h, int64_t T, int32_t M, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
                   uint32_t flags);
 int gu_search_get(gu_handle h, int64_t env0, int64_t n, double *score, int64_t *sim_steps);
+
+/* ---- batched count-based exploration: learner e owns env e, its table Q_e[S][4] (the gu_td_* tables) and visit counts N_e[S][4] ----
+ * (build-defined: the last entry of the reference's roadmap, "Exploration vs Exploitation (Optimistic policy, optimistic policy
+ * with uncertainty, Thompson sampling, UCB)", for which it ships no code; Sutton & Barto 2.7 (UCB action selection), Silver's
+ * lecture 9; tests/_explore_oracle.py is the CPU restatement.  "Optimistic policy" is gu_td_init's q0.)  Tabular Q-learning whose
+ * ACTION CHOICE is driven by the learner's own counts: N_e[S][4], uint32, learner-major [N][S][4], saturating at
+ * GU_EXPLORE_COUNT_MAX.  Two float64 tables shared by all learners, U[C] and B[C], supplied by the host, turn counts into a bonus:
+ * the exploration schedule is data, and the kernel computes no log, sqrt or division.
+ * One iteration of gu_explore_run for env e at 64-bit step count t:
+ *   1. reset: lazy auto-reset, exactly as rule 1 of gu_td_run;
+ *   2. w = the stream-4 word at t (as rule 2 of gu_td_run).  If (w >> 16) < eps_q16: a = w & 3;
+ *   3. else: n_b = N_e[s][b], n_s = n_0 + n_1 + n_2 + n_3 (fits 32 bits: the counts saturate); u = U[min(n_s, C-1)];
+ *      p_b = u * B[min(n_b, C-1)];
+ *        mode 0 (UCB)      : score_b = Q_e[s][b] + p_b;
+ *        mode 1 (Thompson) : score_b = Q_e[s][b] + (p_b * z_b), z_b = the integer-valued double (byte0 + byte1 + byte2 + byte3 of
+ *                            x_b) - 510, where x_0 = the word of RNG stream 7 with counter t & 0xFFFFFFFF and epoch t >> 32 (keyed
+ *                            exactly like stream 4) and x_{b+1} = next(x_b), the bijection of stream 2 (gu_rng.hpp:
+ *                            gu_rng_sample_next).  z_b is an Irwin-Hall approximate normal of variance 21845: the host folds
+ *                            1 / sqrt(21845) into B;
+ *      a = the greedy branch of rule 2 of gu_td_run applied to the score row: the maximum folded left to right with `>`, of the m
+ *      actions whose score equals it exactly the one at index (((w >> 2) & 0x3FFF) * m) >> 14;
+ *   4. N_e[s][a] = min(N_e[s][a] + 1, GU_EXPLORE_COUNT_MAX) -- on exploring steps too, after the choice;
+ *   5. (s', r, d) by the engine's move rule; t += 1; the Q-learning update of rule 4 of gu_td_run, method 0, on Q_e[s][a].  The bonus
+ *      never enters the table.
+ * All float64, one rounding per operation, multiply and add only.  With U or B all zero either mode is gu_td_run, method 0, byte for
+ * byte (tables, rows, statistics, env state, step counts); the counts are an extra.  There is no carry; gu_explore_run ends every
+ * other learner's carry, window and episode buffer, as gu_search_run does.
+ * gu_explore_init       : allocate the counts (N * S * 16 bytes; GU_ERR_NOMEM under gu_td_init's free-memory rule) and zero them.
+ *                         GU_ERR_STATE before gu_td_init.  gu_td_init and gu_td_set_q leave the counts alone; a grid of another
+ *                         size drops them (gu_explore_init again).
+ * gu_explore_set_tables : copy U[C] and B[C] (they stay until the next call, across grids).  GU_ERR_INVALID unless
+ *                         2 <= C <= GU_EXPLORE_MAX_C and every entry is finite and >= 0.
+ * gu_explore_run        : T iterations per env in ONE launch (async).  mode 0 = UCB, 1 = Thompson.  GU_ERR_STATE before
+ *                         gu_td_init, gu_explore_init or gu_explore_set_tables; GU_ERR_INVALID for another mode and everything
+ *                         gu_td_run rejects.  T = 0 changes nothing.  Flags, rows, statistics, the agent trail and the step counts
+ *                         as gu_td_run.
+ * gu_explore_get_counts / gu_explore_set_counts : counts of envs env0 .. env0+n-1 as counts[n][S][4] on the host; set rejects a
+ *                         value above GU_EXPLORE_COUNT_MAX (GU_ERR_INVALID) before it writes anything. */
+#define GU_EXPLORE_MAX_C 4096
+#define GU_EXPLORE_COUNT_MAX 0x3FFFFFFFu
+int gu_explore_init(gu_handle h);
+int gu_explore_set_tables(gu_handle h, int32_t C, const double *U, const double *B);
+int gu_explore_run(gu_handle h, int64_t T, int32_t mode, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+int gu_explore_get_counts(gu_handle h, int64_t env0, int64_t n, uint32_t *counts);
+int gu_explore_set_counts(gu_handle h, int64_t env0, int64_t n, const uint32_t *counts);
 
 /* ---- batched tabular n-step Q-learning and n-step SARSA: learner e owns env e and its table Q_e[S][4] (the gu_td_* tables) ----
  * (build-defined: the reference lists "Temporal Difference (TD) Learning with variations" on its roadmap and ships no code;

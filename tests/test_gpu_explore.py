@@ -1,0 +1,385 @@
+"""Batched count-based exploration on the device (gu_explore_run, csrc/gu_explore.hip) against the CPU restatement
+tests/_explore_oracle.py: Q tables, visit counts, trajectory rows, statistics and env state compared byte for byte."""
+import functools
+
+import numpy as np
+import pytest
+
+import griduniverse_amd as gua
+from griduniverse_amd import _lib
+from griduniverse_amd.algorithms import exploration as X
+from griduniverse_amd.algorithms.temporal_difference import greedy_policy
+from griduniverse_amd.engine import Engine
+from oracle import c_oracle as C
+
+from . import _explore_oracle as EO
+from . import _td_oracle as TD
+from ._tabular_cases import GRIDS, _eps, _grid, _pair, _random_grids, _same, _spec
+from .test_explore_host import BEHAVIOUR, coverage
+from .test_td_host import _bfs_lengths, _greedy_walk_lengths
+
+pytestmark = pytest.mark.gpu
+
+_pair = functools.partial(_pair, EO.ExploreOracle)
+MODES = {'ucb': EO.UCB, 'thompson': EO.THOMPSON}
+CAP = EO.COUNT_MAX
+
+
+def _tables(case, rule):
+    """(U, B, epsilon) of a table case."""
+    if case == 'builder1024':  # the builders' schedules; 16 KiB of tables: staged in LDS beside a staged map
+        return (X.ucb_tables(1.0, 1024) if rule == 'ucb' else X.thompson_tables(1.0, 1024)) + (0.0,)
+    if case == 'epsilon':      # ... with uniform exploration on top
+        return (X.ucb_tables(0.5, 64) if rule == 'ucb' else X.thompson_tables(3.0, 64)) + (0.2,)
+    if case == 'four':         # C = 4: both clamps within a few steps
+        return np.array([0.0, 0.5, 1.0, 1.5]), np.array([4.0, 2.0, 1.0, 0.25]), 0.05
+    assert case == 'l2'        # 64 KiB of tables: never staged, read through L2
+    return (X.ucb_tables(1.0, 4096) if rule == 'ucb' else X.thompson_tables(2.0, 4096)) + (0.1,)
+
+
+def _install(vec, oracles, U, B):
+    vec.set_exploration(U, B)
+    for o in oracles:
+        o.set_tables(U, B)
+
+
+def _same_tables(vec, oracles):
+    assert vec.q_table().tobytes() == np.concatenate([o.q for o in oracles]).tobytes()
+    got = vec.visit_counts()
+    assert got.dtype == np.uint32 and got.tobytes() == np.concatenate([o.counts for o in oracles]).tobytes()
+
+
+def _same_state(vec, oracles):
+    st = vec.get_state()
+    for k in ('pos', 'done', 'episode', 'tcount'):
+        assert np.array_equal(st[k], np.concatenate([getattr(o.state, k) for o in oracles])), k
+
+
+def _run(vec, o, T, rule, eps, alpha=0.25, gamma=0.9):
+    got = vec.explore_run(T, rule, alpha=alpha, discount_factor=gamma, epsilon=eps, trajectory=True, stats=True)
+    _same(got, o.explore(T, MODES[rule], alpha, gamma, _eps(eps)))
+    _same_tables(vec, [o])
+
+
+@pytest.mark.parametrize('case', ['builder1024', 'epsilon', 'four', 'l2'])
+@pytest.mark.parametrize('rule', ['ucb', 'thompson'])
+@pytest.mark.parametrize('grid', sorted(GRIDS))
+def test_tables_counts_rows_stats_and_state_equal_the_oracle(grid, rule, case):
+    g = GRIDS[grid]()
+    U, B, eps = _tables(case, rule)
+    vec, o = _pair(g, 63, 3, q0=0.5 if case == 'four' else 0.0)
+    try:
+        _install(vec, [o], U, B)
+        for T in (200, 100):  # two launches: the second starts from the first one's tables and counts
+            _run(vec, o, T, rule, eps)
+        _same_state(vec, [o])
+        assert np.array_equal(o.counts.astype(np.int64).sum(axis=(1, 2)), np.full(63, 300))
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('rule', ['ucb', 'thompson'])
+def test_4096_learners_equal_the_oracle(rule):
+    g = GRIDS['lava32']()
+    U, B, _ = _tables('builder1024', rule)
+    vec, o = _pair(g, 4096, 5)
+    try:
+        _install(vec, [o], U, B)
+        _run(vec, o, 120, rule, 0.05, alpha=0.3, gamma=0.95)
+        _run(vec, o, 40, rule, 0.0, alpha=0.3, gamma=0.95)
+        _same_state(vec, [o])
+    finally:
+        vec.close()
+
+
+@pytest.mark.parametrize('rule', ['ucb', 'thompson'])
+def test_with_zero_tables_equals_td_q_learning(rule):
+    g = GRIDS['maze11']()
+    a, _ = _pair(g, 300, 7, q0=0.1)
+    b, _ = _pair(g, 300, 7, q0=0.1)
+    try:
+        steps = 0
+        for T, U, B in ((250, np.zeros(16), np.arange(16.0)), (77, np.arange(1.0, 6.0), np.zeros(5))):  # U zero, then B zero
+            a.set_exploration(U, B)
+            got = a.explore_run(T, rule, alpha=0.3, discount_factor=0.95, epsilon=0.15, trajectory=True, stats=True)
+            want = b.td_run(T, 'q_learning', alpha=0.3, discount_factor=0.95, epsilon=0.15, trajectory=True, stats=True)
+            _same(got, want)
+            assert a.q_table().tobytes() == b.q_table().tobytes()
+            steps += T
+            assert np.array_equal(a.visit_counts().astype(np.int64).sum(axis=(1, 2)), np.full(300, steps))
+        sa, sb = a.get_state(), b.get_state()
+        assert all(np.array_equal(sa[k], sb[k]) for k in ('pos', 'done', 'episode', 'tcount'))
+    finally:
+        a.close()
+        b.close()
+
+
+@pytest.mark.parametrize('rule', ['ucb', 'thompson'])
+def test_split_launch_equals_one_launch(rule):
+    g = GRIDS['test_env']()
+    U, B, _ = _tables('epsilon', rule)
+    a, o = _pair(g, 130, 8)
+    b, _ = _pair(g, 130, 8)
+    try:
+        _install(a, [o], U, B)
+        b.set_exploration(U, B)
+        T, kw = 120, dict(alpha=0.4, discount_factor=0.9, epsilon=0.1, trajectory=True, stats=True)
+        whole = a.explore_run(T, rule, **kw)
+        first = b.explore_run(1, rule, **kw)
+        rest = b.explore_run(T - 1, rule, **kw)
+        for k in ('obs', 'reward', 'done'):
+            assert np.array_equal(whole[k], np.concatenate([first[k], rest[k]])), k
+        assert np.array_equal(whole['ret'], first['ret'] + rest['ret'])
+        assert a.q_table().tobytes() == b.q_table().tobytes() and a.visit_counts().tobytes() == b.visit_counts().tobytes()
+        _same(whole, o.explore(T, MODES[rule], 0.4, 0.9, _eps(0.1)))
+        _same_tables(a, [o])
+    finally:
+        a.close()
+        b.close()
+
+
+@pytest.mark.parametrize('rule', ['ucb', 'thompson'])
+@pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
+def test_a_batch_of_distinct_mazes_equals_the_oracle(n_grids, N, rule):
+    grids = _random_grids(n_grids, 9, 9, 17)
+    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
+    group = N // n_grids
+    oracles = [EO.ExploreOracle(_grid(g), 6, group, env_id0=k * group) for k, g in enumerate(grids)]
+    try:
+        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        for case, T in (('epsilon', 60), ('l2', 30)):
+            U, B, eps = _tables(case, rule)
+            _install(vec, oracles, U, B)
+            got = vec.explore_run(T, rule, alpha=0.2, discount_factor=0.9, epsilon=eps, trajectory=True, stats=True)
+            parts = [o.explore(T, MODES[rule], 0.2, 0.9, _eps(eps)) for o in oracles]
+            _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
+        _same_tables(vec, oracles)
+        _same_state(vec, oracles)
+    finally:
+        vec.close()
+
+
+def test_device_mazes_equal_the_oracle():
+    N, W, H, maze_seed, n_grids = 256, 11, 11, 31, 4
+    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
+    group = N // n_grids
+    oracles = []
+    for k in range(n_grids):
+        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
+        oracles.append(EO.ExploreOracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]), 2, group,
+                                        env_id0=k * group))
+    try:
+        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        U, B, _ = _tables('builder1024', 'thompson')
+        _install(vec, oracles, U, B)
+        got = vec.explore_run(80, 'thompson', alpha=0.2, discount_factor=0.9, epsilon=0.0, trajectory=True, stats=True)
+        parts = [o.explore(80, EO.THOMPSON, 0.2, 0.9, 0) for o in oracles]
+        _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
+        _same_tables(vec, oracles)
+        _same_state(vec, oracles)
+    finally:
+        vec.close()
+
+
+def test_step_counts_across_the_epoch_boundary():
+    """The step count t, which keys streams 4 and 7, crosses 2^32 mid-launch."""
+    g = GRIDS['open8x8']()
+    N = 96
+    vec, o = _pair(g, N, 12)
+    try:
+        tc = np.full(N, 2 ** 32 - 30, np.uint64)
+        tc[::3] += 7  # per-env counts: envs cross at different steps
+        vec.set_state(tcount=tc)
+        o.set_state(tcount=tc)
+        U, B, _ = _tables('builder1024', 'thompson')
+        _install(vec, [o], U, B)
+        _run(vec, o, 60, 'thompson', 0.1, alpha=0.2, gamma=0.9)
+        assert np.array_equal(vec.get_state()['tcount'], tc + np.uint64(60))
+        _same_state(vec, [o])
+    finally:
+        vec.close()
+
+
+def test_counts_round_trip_and_saturate_at_the_cap():
+    g = GRIDS['default4x4']()
+    vec, o = _pair(g, 70, 4)
+    try:
+        S = g['W'] * g['H']
+        assert vec.visit_counts().shape == (70, S, 4) and not vec.visit_counts().any()
+        rs = np.random.RandomState(0)
+        c = rs.randint(0, 50, size=(70, S, 4)).astype(np.uint32)
+        c[:, :, 1] = CAP      # at the cap: stays
+        c[:, :, 3] = CAP - 1  # one below: reaches it and stays
+        vec.set_visit_counts(c)
+        o.set_counts(c)
+        assert vec.visit_counts().tobytes() == c.tobytes()
+        part = rs.randint(0, 9, size=(3, S, 4)).astype(np.uint32)
+        vec.set_visit_counts(part, env0=10)
+        o.set_counts(part, env0=10)
+        assert vec.visit_counts(10, 3).tobytes() == part.tobytes() and vec.visit_counts(9, 1).tobytes() == c[9:10].tobytes()
+        vec.set_visit_counts(c[5], env0=5)  # one env as [S, 4]
+        U, B, _ = _tables('four', 'ucb')
+        _install(vec, [o], U, B)
+        _run(vec, o, 400, 'ucb', 1.0)  # always exploring: every pair near the start again and again
+        got = vec.visit_counts()
+        assert got.max() == CAP and (got[0, :, 1] == CAP).all() and (got[0, 0, 3] == CAP)
+        with pytest.raises(gua.GuError) as err:  # one value above the cap: refused, nothing written
+            bad = got.copy()
+            bad[69, S - 1, 3] = CAP + 1
+            vec.set_visit_counts(bad)
+        assert err.value.code == -1 and vec.visit_counts().tobytes() == got.tobytes()
+    finally:
+        vec.close()
+
+
+def test_explore_run_ends_the_sarsa_carry():
+    g = GRIDS['maze11']()
+    vec, o = _pair(g, 200, 9)
+    try:
+        U, B, _ = _tables('epsilon', 'ucb')
+        _install(vec, [o], U, B)
+        kw = dict(alpha=0.3, discount_factor=0.9, epsilon=0.3, trajectory=True, stats=True)
+        _same(vec.td_run(40, 'sarsa', **kw), o.run(40, TD.SARSA, 0.3, 0.9, _eps(0.3)))
+        _run(vec, o, 10, 'ucb', 0.3, alpha=0.3, gamma=0.9)
+        assert not o.carry_valid
+        _same(vec.td_run(40, 'sarsa', **kw), o.run(40, TD.SARSA, 0.3, 0.9, _eps(0.3)))  # a' drawn afresh at the first step
+        assert vec.q_table().tobytes() == o.q.tobytes()
+    finally:
+        vec.close()
+
+
+def _code(call):
+    with pytest.raises(gua.GuError) as err:
+        call()
+    return err.value.code
+
+
+def test_edges_and_errors():
+    g = GRIDS['test_env']()
+    ok = np.ones(8)
+    with Engine(8, _spec(g)) as eng:
+        lib, h, p = eng.lib, eng._h, _lib.ptr
+        S = eng.spec.S
+        buf = np.zeros((8, S, 4), np.uint32)
+        # before gu_td_init
+        assert _code(eng.explore_init) == -4
+        assert _code(lambda: eng.explore_run(10)) == -4
+        # the tables need neither grid-sized storage nor Q tables; their checks
+        for C_, U, B in ((1, ok, ok), (4097, np.ones(4097), np.ones(4097)), (0, ok, ok), (-3, ok, ok)):
+            assert _code(lambda: _lib.check(lib.gu_explore_set_tables(h, C_, p(U), p(B)))) == -1
+        for k, v in ((0, -1e-9), (7, float('nan')), (3, float('inf')), (5, -float('inf'))):
+            for which in (0, 1):
+                t = [ok.copy(), ok.copy()]
+                t[which][k] = v
+                assert _code(lambda: eng.set_exploration(*t)) == -1
+        assert _code(lambda: _lib.check(lib.gu_explore_set_tables(h, 8, None, p(ok)))) == -1
+        assert _code(lambda: _lib.check(lib.gu_explore_set_tables(h, 8, p(ok), None))) == -1
+        with pytest.raises(ValueError):
+            eng.set_exploration(np.ones(4), np.ones(5))
+        eng.td_init(0.5)
+        assert _code(lambda: eng.explore_run(10)) == -4        # no counts
+        assert _code(lambda: eng.explore_get_counts()) == -4
+        assert _code(lambda: eng.explore_set_counts(buf)) == -4
+        eng.explore_init()
+        assert _code(lambda: eng.explore_run(10)) == -4        # no tables (every set_tables above was refused)
+        eng.set_exploration(np.zeros(2), np.zeros(2))          # the smallest; +0.0 entries are fine
+        eng.set_exploration(*X.ucb_tables(1.0, 4096))          # the largest
+        eng.reset()
+        eng.explore_run(25, 'ucb')
+        eng.explore_run(25, 'thompson', eps_q16=65536)
+        assert eng.explore_get_counts().astype(np.int64).sum() == 8 * 50
+        # gu_explore_run's argument checks
+        args = dict(T=10, mode=0, alpha=0.1, gamma=0.9, eps_q16=0, flags=0)
+        for kw in (dict(mode=2), dict(mode=-1), dict(eps_q16=65537), dict(T=-1), dict(T=100000001), dict(alpha=float('nan')),
+                   dict(gamma=float('inf')), dict(flags=_lib.F_AUTO_RESET)):
+            a = dict(args, **kw)
+            assert _code(lambda: _lib.check(lib.gu_explore_run(h, a['T'], a['mode'], a['alpha'], a['gamma'], a['eps_q16'], a['flags']))) == -1, kw
+        assert _code(lambda: eng.explore_run(10, trajectory=True)) == -4  # no trajectory buffer reserved
+        with pytest.raises(KeyError):
+            eng.explore_run(10, 'optimistic')
+        # T = 0 changes nothing
+        before, q, c = eng.get_state(), eng.td_get_q(), eng.explore_get_counts()
+        eng.explore_run(0)
+        after = eng.get_state()
+        assert all(np.array_equal(before[k], after[k]) for k in before)
+        assert eng.td_get_q().tobytes() == q.tobytes() and eng.explore_get_counts().tobytes() == c.tobytes()
+        # the count accessors
+        assert _code(lambda: eng.explore_get_counts(6, 3)) == -1
+        assert _code(lambda: eng.explore_get_counts(-1, 2)) == -1
+        assert _code(lambda: eng.explore_set_counts(buf[:3], env0=6)) == -1
+        assert _code(lambda: _lib.check(lib.gu_explore_get_counts(h, 0, 8, None))) == -1
+        assert _code(lambda: _lib.check(lib.gu_explore_set_counts(h, 0, 8, None))) == -1
+        assert eng.explore_get_counts(8, 0).shape == (0, S, 4)
+        with pytest.raises(ValueError):
+            eng.explore_set_counts(np.zeros((2, S, 3), np.uint32))
+        # gu_td_init and gu_td_set_q leave the counts alone
+        eng.td_init(0.0)
+        eng.td_set_q(np.ones((8, S, 4)))
+        assert eng.explore_get_counts().tobytes() == c.tobytes()
+        # gu_explore_init zeroes them again
+        eng.explore_init()
+        assert not eng.explore_get_counts().any()
+        # a grid of another size drops the counts with the Q tables; the U and B tables stay
+        eng.set_grid(_spec(GRIDS['default4x4']()))
+        assert _code(eng.explore_init) == -4
+        eng.td_init()
+        assert _code(lambda: eng.explore_run(10)) == -4 and _code(lambda: eng.explore_get_counts()) == -4
+        eng.explore_init()
+        eng.reset()
+        eng.explore_run(10)
+        assert eng.explore_get_counts().astype(np.int64).sum() == 8 * 10
+    vec = gua.VecGridUniverse(16, template=_spec(g), seed=1)
+    try:
+        with pytest.raises(ValueError):  # no schedule yet
+            vec.explore_run(10)
+        vec.set_exploration(*X.ucb_tables())
+        for bad in (dict(epsilon=1.5), dict(epsilon=-0.5), dict(rule='optimistic')):
+            with pytest.raises(ValueError):
+                vec.explore_run(10, **bad)
+        vec.reset()
+        out = vec.explore_run(20, stats=True)  # the first call allocates tables of zeros and zeroed counts
+        assert out['ret'].shape == (16,) and vec.visit_counts().astype(np.int64).sum() == 16 * 20
+    finally:
+        vec.close()
+
+
+def test_coverage_on_the_device_equals_the_restatement():
+    """The behaviour run of tests/test_explore_host.py on the device.  The engine's reward planes hold -1, +10 and -10 only, so
+    the sparse grids of that file (step reward 0) cannot be installed on it; this is the open 8x8 grid with the engine's
+    rewards (start 0, goal 63, -1 a step).  The device equals the restatement by construction, which is what is asserted; the
+    coverage (mean / least per learner, of 252 pairs) is printed.  With a -1 step reward a table of zeros is optimistic already,
+    so the two are expected to be close here."""
+    b = BEHAVIOUR
+    g = dict(W=8, H=8, starts=[0], goals=[63], lava=[], walls=[])
+    for name, tables, eps_q16 in (('UCB', X.ucb_tables(1.0, 1024), 0), ('epsilon-greedy', (np.zeros(2), np.zeros(2)), b['plain_eps_q16'])):
+        vec = gua.VecGridUniverse(b['N'], template=_spec(g), seed=b['seed'])
+        o = EO.ExploreOracle(_grid(g), b['seed'], b['N'])
+        try:
+            _install(vec, [o], *tables)
+            assert np.array_equal(vec.reset(), o.reset())
+            got = vec.explore_run(500, 'ucb', alpha=b['alpha'], discount_factor=b['gamma'], epsilon=eps_q16 / 65536.0, stats=True)
+            want = o.explore(500, EO.UCB, b['alpha'], b['gamma'], eps_q16)
+            _same(got, want, keys=('ret', 'episodes'))
+            cov, ref = coverage(vec.visit_counts()), coverage(o.counts)
+            print('open 8x8 on the device, 500 steps: {} coverage mean {:.1f} least {} (restatement: {:.1f} / {})'.format(
+                name, cov.mean(), cov.min(), ref.mean(), ref.min()))
+            assert np.array_equal(cov, ref)
+            _same_tables(vec, [o])
+        finally:
+            vec.close()
+
+
+def test_ucb_q_learning_finds_a_policy_that_reaches_the_goal():
+    """algorithms.ucb_q_learning on the open 8x8 grid (the engine's rewards: the sparse grid cannot be installed on the device,
+    see above), epsilon 0, 20 000 steps: the greedy policy of every learner walks from the start to the goal, on a shortest path."""
+    env = gua.GridUniverseEnv(grid_shape=(8, 8))
+    grid = C.Grid.from_env(env)
+    q = X.ucb_q_learning(env, 20000, c=1.0, num_learners=8, seed=1)
+    assert q.shape == (8, env.world.size, 4) and q.dtype == np.float64 and np.isfinite(q).all()
+    dist = _bfs_lengths(grid)
+    for e in range(8):
+        assert _greedy_walk_lengths(grid, q[e])[grid.starts[0]] == dist[grid.starts[0]], e
+        pi = greedy_policy(q[e], env)
+        assert pi.shape == (env.world.size, 4) and np.allclose(pi.sum(axis=1)[:-1], 1.0)
+    q1 = X.thompson_q_learning(env, 50, sigma=0.5, seed=1)
+    assert q1.shape == (env.world.size, 4)
