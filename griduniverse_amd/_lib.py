@@ -32,6 +32,8 @@ SEARCH_MAX_D = 256  # GU_SEARCH_MAX_D: their largest depth
 EXPLORE_MAX_C = 4096  # GU_EXPLORE_MAX_C: the most entries of gu_explore_set_tables' U and B
 EXPLORE_COUNT_MAX = 0x3FFFFFFF  # GU_EXPLORE_COUNT_MAX: where a visit count saturates
 EXPLORE_UCB, EXPLORE_THOMPSON = 0, 1
+MCTS_MAX_SIMS = 255   # GU_MCTS_MAX_SIMS: the most simulations per decision of gu_mcts_run (the pool of gu_mcts_init holds one node more)
+MCTS_MAX_DEPTH = 64   # GU_MCTS_MAX_DEPTH: the largest depth cap of its tree
 FA_MAX_K = 8  # GU_FA_MAX_K: the most active features per state of gu_fa_init
 COMM_ID_BYTES = 128
 OPT_UNSET = -2 ** 63
@@ -103,6 +105,11 @@ SIGNATURES = {
     'gu_explore_run': [_vp, _i64, _i32, _f64, _f64, _u32, _u32],
     'gu_explore_get_counts': [_vp, _i64, _i64, _vp],
     'gu_explore_set_counts': [_vp, _i64, _i64, _vp],
+    'gu_mcts_init': [_vp, _i32],
+    'gu_mcts_set_tables': [_vp, _i32, _vp, _vp, _vp],
+    'gu_mcts_run': [_vp, _i64, _i32, _i32, _i32, _f64, _f64, _u32, _u32, _u32],
+    'gu_mcts_get': [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    'gu_mcts_get_tree': [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     'gu_nstep_run': [_vp, _i64, _i32, _i32, _f64, _f64, _u32, _u32],
     'gu_nstep_get_window': [_vp, _i64, _i64, _vp, _vp, _vp],
     'gu_lambda_run': [_vp, _i64, _i32, _i32, _f64, _f64, _f64, _u32, _u32],

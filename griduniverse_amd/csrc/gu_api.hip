@@ -18,6 +18,7 @@ static void gu_dyna_free(gu_engine *h);  // (tabular Dyna-Q, below)
 static void gu_nstep_free(gu_engine *h);  // (tabular n-step learners, below)
 static void gu_search_free(gu_engine *h); // (rollout search, below)
 static void gu_explore_free(gu_engine *h);  // (the counts of the count-based exploration, below)
+static void gu_mcts_free(gu_engine *h);  // (the node pools of the tree search, below)
 static void gu_lambda_free(gu_engine *h); // (tabular lambda learners, below)
 static void gu_ac_free(gu_engine *h);     // (tabular actor-critic, below)
 static void gu_reinforce_free(gu_engine *h);  // (tabular REINFORCE, below)
@@ -180,7 +181,8 @@ int gu_destroy(gu_handle h)
     void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
                     h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next,
                     h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_lambda_w, h->d_ac_h, h->d_ac_v, h->d_rf_buf, h->d_rf_cnt,
-                    h->d_fa_w, h->d_fa_phi, h->d_fa_phi16, h->d_fa_next, h->d_search_score, h->d_search_steps, h->d_explore_n, h->d_explore_tab};
+                    h->d_fa_w, h->d_fa_phi, h->d_fa_phi16, h->d_fa_next, h->d_search_score, h->d_search_steps, h->d_explore_n, h->d_explore_tab,
+                    h->d_mcts_pool, h->d_mcts_meta, h->d_mcts_nodes, h->d_mcts_steps, h->d_mcts_tab};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -258,6 +260,7 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
         gu_nstep_free(h);
         gu_lambda_free(h);
         gu_search_free(h);
+        gu_mcts_free(h);  // (gu_mcts_init again; the U, B and I tables stay)
     }
     if (h->explore_S && h->explore_S != W * H) gu_explore_free(h);  // ... and the visit counts: gu_explore_init again (the U and B tables stay)
     if (h->dyna_S && h->dyna_S != W * H) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
@@ -1454,6 +1457,146 @@ int gu_explore_set_counts(gu_handle h, int64_t env0, int64_t n, const uint32_t *
                    (long long)(env0 + (int64_t)(i / row)), GU_EXPLORE_COUNT_MAX);
     GU_HIP(hipStreamSynchronize(h->stream));
     if (n) GU_HIP(hipMemcpy(h->d_explore_n + (size_t)env0 * row, counts, k * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return GU_OK;
+}
+
+static void gu_mcts_free(gu_engine *h)
+{
+    for (void *p : {(void *)h->d_mcts_pool, (void *)h->d_mcts_meta, (void *)h->d_mcts_nodes, (void *)h->d_mcts_steps})
+        if (p) (void)hipFree(p);
+    h->d_mcts_pool = nullptr;
+    h->d_mcts_meta = nullptr;
+    h->d_mcts_nodes = nullptr;
+    h->d_mcts_steps = nullptr;
+    h->mcts_P = 0;
+}
+
+int gu_mcts_init(gu_handle h, int32_t max_sims)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(max_sims >= 1 && max_sims <= GU_MCTS_MAX_SIMS, GU_ERR_INVALID, "max_sims %d out of range (1 .. %d)", max_sims, GU_MCTS_MAX_SIMS);
+    const int32_t P = max_sims + 1;
+    const size_t nodes = (size_t)h->N * (size_t)P;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!h->d_mcts_pool || h->mcts_P != P) {
+        gu_mcts_free(h);
+        int rc = gu_tabular_fits(h, nodes * 72 + (size_t)h->N * 12, "tree-search node pools");
+        if (rc != GU_OK) return rc;
+        GU_HIP(hipMalloc(&h->d_mcts_pool, nodes * 64));
+        GU_HIP(hipMalloc(&h->d_mcts_meta, nodes * 8));
+        GU_HIP(hipMalloc(&h->d_mcts_nodes, (size_t)h->N * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_mcts_steps, (size_t)h->N * sizeof(int64_t)));
+        h->mcts_P = P;
+    }
+    GU_HIP(hipMemsetAsync(h->d_mcts_pool, 0, nodes * 64, h->stream));  // (root rows of zeros until an iteration has been searched)
+    GU_HIP(hipMemsetAsync(h->d_mcts_meta, 0xFF, nodes * 8, h->stream));
+    GU_HIP(hipMemsetAsync(h->d_mcts_nodes, 0, (size_t)h->N * sizeof(int32_t), h->stream));
+    GU_HIP(hipMemsetAsync(h->d_mcts_steps, 0, (size_t)h->N * sizeof(int64_t), h->stream));
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_mcts_set_tables(gu_handle h, int32_t C, const double *U, const double *B, const double *I)
+{
+    GU_ENTER(h);
+    GU_REQUIRE(C >= 2 && C <= GU_EXPLORE_MAX_C, GU_ERR_INVALID, "table size %d out of range (2 .. %d)", C, GU_EXPLORE_MAX_C);
+    GU_REQUIRE(U != nullptr && B != nullptr && I != nullptr, GU_ERR_INVALID, "U, B or I is NULL");
+    for (int32_t k = 0; k < C; ++k)
+        GU_REQUIRE(std::isfinite(U[k]) && U[k] >= 0.0 && std::isfinite(B[k]) && B[k] >= 0.0 && std::isfinite(I[k]) && I[k] >= 0.0, GU_ERR_INVALID,
+                   "entry %d (U %g, B %g, I %g): every entry must be finite and not negative", k, U[k], B[k], I[k]);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (h->mcts_C != C) {
+        if (h->d_mcts_tab) GU_HIP(hipFree(h->d_mcts_tab));
+        h->d_mcts_tab = nullptr;
+        h->mcts_C = 0;
+        const size_t bytes = ((size_t)C * 3 * sizeof(double) + 15) & ~(size_t)15;  // (whole 16-byte pieces: the LDS kernels stage it so)
+        GU_HIP(hipMalloc(&h->d_mcts_tab, bytes));
+        GU_HIP(hipMemset(h->d_mcts_tab, 0, bytes));
+        h->mcts_C = C;
+    }
+    GU_HIP(hipMemcpy(h->d_mcts_tab, U, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
+    GU_HIP(hipMemcpy(h->d_mcts_tab + C, B, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
+    GU_HIP(hipMemcpy(h->d_mcts_tab + 2 * (size_t)C, I, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
+    return GU_OK;
+}
+
+int gu_mcts_run(gu_handle h, int64_t T, int32_t M, int32_t H, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
+                uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(h->d_mcts_pool && h->mcts_P >= 2, GU_ERR_STATE, "no node pools: call gu_mcts_init first");
+    GU_REQUIRE(M >= 0 && M <= h->mcts_P - 1, GU_ERR_INVALID, "simulations %d out of range (0 .. %d, gu_mcts_init's max_sims)", M, h->mcts_P - 1);
+    GU_REQUIRE(H >= 1 && H <= GU_MCTS_MAX_DEPTH, GU_ERR_INVALID, "tree depth %d out of range (1 .. %d)", H, GU_MCTS_MAX_DEPTH);
+    GU_REQUIRE(D >= 0 && D <= GU_SEARCH_MAX_D, GU_ERR_INVALID, "depth %d out of range (0 .. %d)", D, GU_SEARCH_MAX_D);
+    GU_REQUIRE(eps_sim_q16 <= 65536u, GU_ERR_INVALID, "eps_sim_q16 %u above 65536", eps_sim_q16);
+    GU_REQUIRE(M == 0 || (h->d_mcts_tab && h->mcts_C >= 2), GU_ERR_STATE, "no tree-search tables: call gu_mcts_set_tables first");
+    int rc = gu_tabular_check(h, "gu_mcts_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK) return rc;
+    const int64_t moves = 1 + (int64_t)M * (H + D);  // per real step, at most
+    GU_REQUIRE(T * moves <= 100000000, GU_ERR_INVALID, "T %lld x (1 + M (H + D)) = %lld moves out of range (0 .. 1e8)", (long long)T,
+               (long long)(T * moves));
+    if (T == 0) return GU_OK;
+    return gu_launch_mcts(h, T, M, H, D, alpha, gamma, eps_q16, eps_sim_q16, flags);
+}
+
+static int gu_mcts_range(gu_engine *h, int64_t env0, int64_t n)
+{
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(h->d_mcts_pool && h->mcts_P >= 2, GU_ERR_STATE, "no node pools: call gu_mcts_init first");
+    return gu_env_range(h, env0, n);
+}
+
+int gu_mcts_get(gu_handle h, int64_t env0, int64_t n, double *w, uint32_t *visits, int32_t *nodes, int64_t *sim_steps)
+{
+    GU_ENTER(h);
+    int rc = gu_mcts_range(h, env0, n);
+    if (rc != GU_OK) return rc;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!n) return GU_OK;
+    // the root is node 0 of each env's pool: its w row at byte 0, its visits row at byte 32
+    const size_t pitch = (size_t)h->mcts_P * 64;
+    const uint8_t *root = h->d_mcts_pool + (size_t)env0 * pitch;
+    if (w) GU_HIP(hipMemcpy2D(w, 32, root, pitch, 32, (size_t)n, hipMemcpyDeviceToHost));
+    if (visits) GU_HIP(hipMemcpy2D(visits, 16, root + 32, pitch, 16, (size_t)n, hipMemcpyDeviceToHost));
+    if (nodes) GU_HIP(hipMemcpy(nodes, h->d_mcts_nodes + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (sim_steps) GU_HIP(hipMemcpy(sim_steps, h->d_mcts_steps + env0, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+    return GU_OK;
+}
+
+int gu_mcts_get_tree(gu_handle h, int64_t env0, int64_t n, int32_t *state, int32_t *parent, int32_t *child, uint32_t *visits, double *w,
+                     int32_t *count)
+{
+    GU_ENTER(h);
+    int rc = gu_mcts_range(h, env0, n);
+    if (rc != GU_OK) return rc;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!n) return GU_OK;
+    const size_t P = (size_t)h->mcts_P, k = (size_t)n * P;
+    std::vector<uint8_t> pool(k * 64);
+    std::vector<int32_t> meta(k * 2), cnt((size_t)n);
+    GU_HIP(hipMemcpy(pool.data(), h->d_mcts_pool + (size_t)env0 * P * 64, k * 64, hipMemcpyDeviceToHost));
+    GU_HIP(hipMemcpy(meta.data(), h->d_mcts_meta + (size_t)env0 * P * 2, k * 8, hipMemcpyDeviceToHost));
+    GU_HIP(hipMemcpy(cnt.data(), h->d_mcts_nodes + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (size_t e = 0; e < (size_t)n; ++e) {
+        if (count) count[e] = cnt[e];
+        for (size_t v = 0; v < P; ++v) {
+            const size_t i = e * P + v;
+            const bool live = (int64_t)v < (int64_t)cnt[e];
+            const uint8_t *node = pool.data() + i * 64;
+            if (state) state[i] = live ? meta[i * 2] : -1;
+            if (parent) parent[i] = live ? meta[i * 2 + 1] : -1;
+            for (size_t b = 0; b < 4; ++b) {
+                if (w) w[i * 4 + b] = live ? reinterpret_cast<const double *>(node)[b] : 0.0;
+                if (visits) visits[i * 4 + b] = live ? reinterpret_cast<const uint32_t *>(node + 32)[b] : 0u;
+                if (child) child[i * 4 + b] = live ? reinterpret_cast<const int32_t *>(node + 48)[b] : -1;
+            }
+        }
+    }
     return GU_OK;
 }
 

@@ -302,6 +302,14 @@ struct gu_engine {
     int32_t explore_S = 0;             // states of the counts (0: none allocated); a grid of another size drops them
     double *d_explore_tab = nullptr;   // U[explore_C] | B[explore_C], shared by all envs (gu_explore_set_tables)
     int32_t explore_C = 0;             // entries of each (0: no tables yet)
+    // batched Monte-Carlo tree search (gu_mcts.hip): off until gu_mcts_init; decides and learns on d_q; dropped with the tables
+    uint8_t *d_mcts_pool = nullptr;    // [N][mcts_P] nodes of 64 bytes: w[4] float64 | visits[4] uint32 | child[4] int32
+    int32_t *d_mcts_meta = nullptr;    // [N][mcts_P][2] (state, parent * 4 + action; -1 for the root)
+    int32_t *d_mcts_nodes = nullptr;   // [N] nodes of each env's most recent searched iteration (0: none yet)
+    int64_t *d_mcts_steps = nullptr;   // [N] simulated moves of the last launch
+    int32_t mcts_P = 0;                // nodes per env, max_sims + 1 (0: no pool)
+    double *d_mcts_tab = nullptr;      // U[mcts_C] | B[mcts_C] | I[mcts_C], shared by all envs (gu_mcts_set_tables)
+    int32_t mcts_C = 0;                // entries of each (0: no tables yet)
 
     // agent trail (gu_trail.hip): off unless gu_trail_enable was called
     int32_t trail_cap = 0;             // entries per env (0: off)
@@ -447,6 +455,10 @@ int gu_launch_search(gu_engine *h, int64_t T, int32_t M, int32_t D, double alpha
 
 // ---- batched count-based exploration: UCB / Thompson Q-learning (gu_explore.hip) ---------
 int gu_launch_explore(gu_engine *h, int64_t T, int32_t mode, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+
+// ---- batched Monte-Carlo tree search at decision time (gu_mcts.hip) -------------------
+int gu_launch_mcts(gu_engine *h, int64_t T, int32_t M, int32_t H, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
+                   uint32_t flags);
 
 // ---- batched tabular n-step Q-learning / SARSA (gu_nstep.hip) --------------------------
 // the carry key of a gu_nstep_run (never 0): the next launch keeps the window only under the same method and n

@@ -418,6 +418,54 @@ class Engine(object):
             raise ValueError('counts must have shape (n, {}, 4), got {}'.format(self.spec.S, c.shape))
         check(self.lib.gu_explore_set_counts(self._h, int(env0), c.shape[0], ptr(c)))
 
+    # ------------------------------------------------------------------ Monte-Carlo tree search at decision time (include/gu.h: gu_mcts_*)
+    def mcts_init(self, max_sims=64):
+        """An empty pool of max_sims + 1 tree nodes per env (1 <= max_sims <= MCTS_MAX_SIMS); the Q tables come from td_init."""
+        check(self.lib.gu_mcts_init(self._h, int(max_sims)))
+        self._mcts_nodes = int(max_sims) + 1
+
+    def set_tree_tables(self, U, B, I):
+        """The schedule of the tree search: float64 U[C], B[C] and I[C], 2 <= C <= EXPLORE_MAX_C, every entry finite and >= 0.  An
+        action tried n_b times at a node visited n_s times scores w_b * I[min(n_b, C-1)] + U[min(n_s, C-1)] * B[min(n_b, C-1)]
+        (algorithms.search.uct_tables builds UCB1's)."""
+        U, B, I = (_lib.as_array(t, np.float64, None, k) for t, k in ((U, 'U'), (B, 'B'), (I, 'I')))
+        if U.ndim != 1 or U.shape != B.shape or U.shape != I.shape:
+            raise ValueError('U, B and I must be vectors of one length, got {}, {} and {}'.format(U.shape, B.shape, I.shape))
+        check(self.lib.gu_mcts_set_tables(self._h, U.shape[0], ptr(U), ptr(B), ptr(I)))
+
+    def mcts_run(self, T, simulations=64, tree_depth=8, depth=4, alpha=0.1, gamma=0.99, eps_q16=6554, eps_sim_q16=65536, trajectory=False,
+                 stats=False):
+        """T real steps per env in one launch, each non-exploring one chosen by a UCT tree of `simulations` (0 .. mcts_init's
+        max_sims) simulations with the true model: selection down to `tree_depth` (1 .. MCTS_MAX_DEPTH) levels, one new node, a
+        rollout of `depth` (0 .. SEARCH_MAX_D) moves under an epsilon-greedy policy (eps_sim_q16; 65536 = uniform) on the td_init
+        tables, which then learn from the real transition by Q-learning.  simulations = 0 is td_run('q_learning').  Rows and
+        statistics (real steps only) as td_run()."""
+        check(self.lib.gu_mcts_run(self._h, int(T), int(simulations), int(tree_depth), int(depth), float(alpha), float(gamma), int(eps_q16),
+                                   int(eps_sim_q16), _learner_flags(trajectory, stats)))
+
+    def mcts_get(self, env0=0, n=None):
+        """Of envs env0 .. env0+n-1, from each env's most recent searched step: dict w float64[n, 4] and visits uint32[n, 4] (the
+        root's return sums and visit counts; zeros until there is one), nodes int32[n] (the nodes of that tree) and sim_steps
+        int64[n] (simulated moves of the last launch)."""
+        n = self.N - int(env0) if n is None else int(n)
+        n0 = max(n, 0)
+        out = dict(w=np.empty((n0, 4), np.float64), visits=np.empty((n0, 4), np.uint32), nodes=np.empty(n0, np.int32),
+                   sim_steps=np.empty(n0, np.int64))
+        check(self.lib.gu_mcts_get(self._h, int(env0), n, ptr(out['w']), ptr(out['visits']), ptr(out['nodes']), ptr(out['sim_steps'])))
+        return out
+
+    def mcts_tree(self, env0=0, n=None):
+        """The whole tree of each env's most recent searched step, P = max_sims + 1 node slots per env in order of creation: dict
+        state int32[n, P], parent int32[n, P] (parent * 4 + action; -1 for the root), child int32[n, P, 4] (-1 = none), visits
+        uint32[n, P, 4], w float64[n, P, 4] and count int32[n]; slots beyond count hold -1 / -1 / -1 / 0 / 0.0."""
+        n = self.N - int(env0) if n is None else int(n)
+        n0, P = max(n, 0), getattr(self, '_mcts_nodes', 0)
+        out = dict(state=np.empty((n0, P), np.int32), parent=np.empty((n0, P), np.int32), child=np.empty((n0, P, 4), np.int32),
+                   visits=np.empty((n0, P, 4), np.uint32), w=np.empty((n0, P, 4), np.float64), count=np.empty(n0, np.int32))
+        check(self.lib.gu_mcts_get_tree(self._h, int(env0), n, ptr(out['state']), ptr(out['parent']), ptr(out['child']), ptr(out['visits']),
+                                        ptr(out['w']), ptr(out['count'])))
+        return out
+
     # ------------------------------------------------------------------ tabular n-step Q-learning / SARSA (include/gu.h: gu_nstep_*)
     def nstep_run(self, T, method='sarsa', n=4, alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
         """T iterations of n-step Q-learning / SARSA per env in one launch, into the td_init tables.  The window of pending

@@ -14,7 +14,7 @@ keyed by GLOBAL env id, so the union of the shards equals the single-device batc
 for byte (see `parallel.py`).
 """
 
-from . import softmax
+from . import _lib, softmax
 from .engine import Engine
 from .envs.griduniverse_env import GridUniverseEnv
 from .grid import GridSpec
@@ -25,6 +25,8 @@ class VecGridUniverse(object):
     _dyna_ready = False  # ... and Dyna-Q models (dyna_run / model allocate them on first use)
     _explore_ready = False  # ... and visit counts (explore_run / visit_counts allocate them on first use)
     _explore_tables = False  # set_exploration was called
+    _tree_sims = 0  # simulations the tree-search node pools hold (tree_search_run allocates them on first use and when it needs more)
+    _tree_tables = False  # set_tree_search was called (tree_search_run installs UCB1 tables with c = 3 otherwise)
     _ac_ready = False  # ... and actor-critic tables (actor_critic_run / set_actor_critic allocate them on first use)
     _fa_ready = False  # ... and features with their weights (set_features installs them; nothing does it implicitly)
 
@@ -191,6 +193,59 @@ class VecGridUniverse(object):
         """Engine.search_get: the score rows of the most recent searched steps and the simulated moves of the last search_run."""
         self._ensure_q()
         return self.engine.search_get(env0, n)
+
+    def set_tree_search(self, U, B, I):
+        """The schedule of tree_search_run: float64 vectors U, B and I of one length C, 2 <= C <= 4096, finite and >= 0.  At a node
+        visited n_s times, an action tried n_b times with summed returns w_b scores w_b * I[min(n_b, C-1)] + U[min(n_s, C-1)] *
+        B[min(n_b, C-1)]; algorithms.search.uct_tables builds UCB1's."""
+        self.engine.set_tree_tables(U, B, I)
+        self._tree_tables = True
+
+    def tree_search_run(self, T, simulations=64, tree_depth=8, depth=4, alpha=0.1, discount_factor=0.99, epsilon=0.1, rollout_epsilon=1.0,
+                        trajectory=False, stats=False):
+        """T real steps of batched Monte-Carlo tree search (UCT at decision time): before each non-exploring real move, env e
+        builds a search tree at its state by `simulations` (0 .. 255) simulations with the true model -- UCB1 selection down to
+        `tree_depth` (1 .. 64) levels, one new node, a rollout of `depth` (0 .. 256) moves under an epsilon-greedy policy on its own
+        Q table (`rollout_epsilon`; 1.0 = uniformly random) that bootstraps on max Q at its leaf, and a backup --, takes the root
+        action with the largest mean return and learns from the real transition by Q-learning (include/gu.h: gu_mcts_run).  An
+        exploring step (`epsilon`) simulates nothing; simulations = 0 is td_run('q_learning').  The first call gives every env a
+        table of zeros and a node pool, and installs uct_tables(3.0) unless set_tree_search was called.  Rows and statistics
+        cover the real steps, as td_run()."""
+        for name, v in (('epsilon', epsilon), ('rollout_epsilon', rollout_epsilon)):
+            if not 0.0 <= float(v) <= 1.0:
+                raise ValueError('{} must lie in [0, 1]'.format(name))
+        M = int(simulations)
+        if not 0 <= M <= _lib.MCTS_MAX_SIMS:
+            raise ValueError('simulations must lie in 0 .. {}'.format(_lib.MCTS_MAX_SIMS))
+        self._ensure_q()
+        if M > self._tree_sims or not self._tree_sims:
+            self.engine.mcts_init(max(M, 1))
+            self._tree_sims = max(M, 1)
+        if not self._tree_tables:
+            from .algorithms.search import uct_tables
+            self.set_tree_search(*uct_tables())
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.mcts_run(T, M, tree_depth, depth, alpha, discount_factor, int(round(float(epsilon) * 65536)),
+                             int(round(float(rollout_epsilon) * 65536)), trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def _ensure_tree(self):
+        self._ensure_q()
+        if not self._tree_sims:
+            self.engine.mcts_init(1)
+            self._tree_sims = 1
+
+    def tree_search_roots(self, env0=0, n=None):
+        """Engine.mcts_get: the root rows (return sums, visits) and node counts of the most recent searched steps and the simulated
+        moves of the last tree_search_run."""
+        self._ensure_tree()
+        return self.engine.mcts_get(env0, n)
+
+    def tree_search_tree(self, env0=0, n=None):
+        """Engine.mcts_tree: the whole trees of the most recent searched steps."""
+        self._ensure_tree()
+        return self.engine.mcts_tree(env0, n)
 
     def _ensure_counts(self):
         """Visit counts on the engine: zeroed counts on first use (and tables of zeros if the envs had no Q tables)."""

@@ -262,7 +262,7 @@ int gu_done_indices(gu_handle h, int32_t *idx, int32_t *count);
  *      the row maximum exactly, in ascending order, the one at index (((w >> 2) & 0x3FFF) * m) >> 14.  SARSA uses the carried
  *      action a' instead -- inside a launch always, and at its start when it directly follows a SARSA gu_td_run on this engine
  *      (no gu_seed, gu_reset*, gu_step*, gu_rollout, gu_set_state, gu_set_grid(s), gu_generate_mazes, gu_td_init, gu_td_set_q, gu_dyna_run,
- *      gu_nstep_run, gu_search_run, gu_explore_run or sweep-step call in between);
+ *      gu_nstep_run, gu_search_run, gu_explore_run, gu_mcts_run or sweep-step call in between);
  *   3. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
  *   4. float64, one rounding per operation: m = max Q_e[s'] (Q-learning) or Q_e[s'][a'] with a' drawn at s' by rule 2 from the word
  *      of the new t and the pre-update row (SARSA; not drawn when d); target = r if d else r + gamma * m;
@@ -392,6 +392,72 @@ int gu_explore_set_tables(gu_handle h, int32_t C, const double *U, const double 
 int gu_explore_run(gu_handle h, int64_t T, int32_t mode, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 int gu_explore_get_counts(gu_handle h, int64_t env0, int64_t n, uint32_t *counts);
 int gu_explore_set_counts(gu_handle h, int64_t env0, int64_t n, const uint32_t *counts);
+
+/* ---- batched Monte-Carlo tree search (UCT): learner e owns env e, its table Q_e[S][4] (the gu_td_* tables) and a pool of tree nodes ----
+ * (build-defined: the "MC/TD Tree search" half of the reference's roadmap entry "Integrating learning and planning (Dyna, MC/TD Tree
+ * search, Forward and Simulation-based search)", for which it ships no code; Kocsis & Szepesvari's UCT, Sutton & Barto 8.11;
+ * tests/_mcts_oracle.py is the CPU restatement.)  gu_search_run spends a fixed budget of rollouts on every action; this learner
+ * builds a TREE at the state it stands in, before each non-exploring real move, with the TRUE model (the engine's move rule), and
+ * spends its M simulations where the tree's own statistics point.  Node 0 is the root; nodes are numbered in order of creation;
+ * node v holds its state x_v, its parent link (parent * 4 + action; -1 for the root), child_v[4] (node index, -1 = none), visit
+ * counts n_v[4] (uint32) and return sums w_v[4] (float64).  Three float64 tables shared by all learners, U[C], B[C] and I[C],
+ * supplied by the host, every index clamped to C - 1, turn counts into the UCB1 bonus and sums into means: the kernel computes no
+ * log, sqrt or division.
+ * One iteration of gu_mcts_run for env e at 64-bit step count t:
+ *   1. reset: lazy auto-reset, exactly as rule 1 of gu_td_run;
+ *   2. w = the stream-4 word at t (as rule 2 of gu_td_run);
+ *   3. action.  If (w >> 16) < eps_q16: a = w & 3 and NO simulation is run.  Else if M = 0: a by rule 2 of gu_td_run on Q_e[s].
+ *      Else the tree is rebuilt from scratch -- node 0 = s without children, counts 0, sums 0.0; one node -- and for j = 0 .. M-1
+ *      one simulation runs.  Its draws are the words of RNG stream 8 with counter c & 0xFFFFFFFF and epoch c >> 32 (keyed like
+ *      streams 4 - 7), c = (t * M + j) * (H + D) + i (uint64, wrapping), i = the draws the simulation has made so far:
+ *        selection: v = 0, depth = 0.  At node v: n_s = n_v[0] + n_v[1] + n_v[2] + n_v[3]; score_b = +infinity if n_v[b] == 0, else
+ *          (w_v[b] * I[n_v[b]]) + (U[n_s] * B[n_v[b]]); u = the greedy branch of rule 2 of gu_td_run applied to the score row with
+ *          the next stream-8 word (the maximum folded left to right with `>`, of the m exactly-maximal actions the one at index
+ *          (((w' >> 2) & 0x3FFF) * m) >> 14); (x', r', dn) = the move rule from (x_v, u); depth += 1.  If dn: tail = 0.0 and the
+ *          simulation goes to its backup.  Else if child_v[u] >= 0 and depth < H: v = child_v[u], again.  Else: if child_v[u] < 0
+ *          a node for x' is created (no children, counts 0, sums 0.0, parent link v * 4 + u, child_v[u] = its index) -- at the
+ *          depth cap too --, and in either case a rollout starts at x';
+ *        rollout (gu_search_run's): G = 0.0, disc = 1.0, x = x'; up to D times, while not terminal: u = rule 2 of gu_td_run
+ *          applied to the row Q_e[x] with the next stream-8 word and eps_sim_q16; (x, r, dn) = the move rule from (x, u);
+ *          G = G + disc * r, then disc = disc * gamma.  After the loop, if not dn: G = G + disc * max Q_e[x], folded left to right
+ *          with `>`.  tail = G.  (D = 0: tail = 0.0 + 1.0 * max Q_e[x'], the TD-tree-search case.);
+ *        backup: G = tail; for each edge of the path, from the last one (v, u) -- its reward r' -- up to the root's:
+ *          G = r_edge + gamma * G, then w[edge] = w[edge] + G and n[edge] += 1.
+ *      After the M simulations the final row is -infinity where n_0[b] == 0, else w_0[b] * I[n_0[b]] -- the MEAN return of the root
+ *      action, not its visit count --, and a = the tie rule of rule 2 applied to that row with w.  No Q_e entry is written during
+ *      a search;
+ *   4. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
+ *   5. the Q-learning update of rule 4 of gu_td_run, method 0, on Q_e[s][a]; the next iteration sees the updated table.
+ * All float64, one rounding per operation, multiply / add / subtract only.  With M = 0 this is gu_td_run, method 0, byte for byte,
+ * for any H, D, tables and eps_sim_q16.  There is no carry; gu_mcts_run ends every other learner's carry, window and episode
+ * buffer, as gu_search_run does.  A tree lives for one decision: nothing is reused between decisions and states met twice in one
+ * tree are two nodes.
+ * gu_mcts_init       : allocate a pool of max_sims + 1 nodes per env (1 <= max_sims <= GU_MCTS_MAX_SIMS; N * (max_sims + 1) * 72
+ *                      bytes; GU_ERR_NOMEM under gu_td_init's free-memory rule) and empty it.  GU_ERR_STATE before gu_td_init.  A
+ *                      grid of another size drops the pool with the Q tables (gu_mcts_init again).
+ * gu_mcts_set_tables : copy U[C], B[C] and I[C] (they stay until the next call, across grids).  GU_ERR_INVALID unless
+ *                      2 <= C <= GU_EXPLORE_MAX_C and every entry is finite and >= 0.  UCB1 with constant k: U[n] = k sqrt(ln(n + 1)),
+ *                      B[n] = 1 / sqrt(n), I[n] = 1 / n, B[0] = I[0] = 0 (index 0 is never read: an untried action scores infinity).
+ * gu_mcts_run        : T iterations per env in ONE launch (async).  GU_ERR_STATE before gu_td_init or gu_mcts_init, and, when M > 0,
+ *                      before gu_mcts_set_tables; GU_ERR_INVALID for M outside 0 .. max_sims, H outside 1 .. GU_MCTS_MAX_DEPTH, D
+ *                      outside 0 .. GU_SEARCH_MAX_D, either epsilon above 65536, T * (1 + M (H + D)) > 1e8 (gu_dyna_run's launch
+ *                      bound) and everything gu_td_run rejects.  T = 0 changes nothing.  Flags, rows, statistics, the agent trail
+ *                      and the step counts as gu_td_run: the T real steps only.
+ * gu_mcts_get        : of envs env0 .. env0+n-1 on the host, from each env's most recent SEARCHED iteration: w as [n][4] and visits
+ *                      as [n][4], the root's rows (zeros until there is one); nodes as [n], the nodes of that tree; sim_steps as
+ *                      int64 [n], the simulated moves of the last launch, selection and rollout moves alike.  Any pointer may be NULL.
+ * gu_mcts_get_tree   : the whole tree of that iteration: state, parent as [n][max_sims + 1], child, visits, w as
+ *                      [n][max_sims + 1][4], count as [n]; entries of nodes beyond count are -1, -1, -1, 0, 0.0.  Any pointer may
+ *                      be NULL. */
+#define GU_MCTS_MAX_SIMS 255
+#define GU_MCTS_MAX_DEPTH 64
+int gu_mcts_init(gu_handle h, int32_t max_sims);
+int gu_mcts_set_tables(gu_handle h, int32_t C, const double *U, const double *B, const double *I);
+int gu_mcts_run(gu_handle h, int64_t T, int32_t M, int32_t H, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
+                uint32_t flags);
+int gu_mcts_get(gu_handle h, int64_t env0, int64_t n, double *w, uint32_t *visits, int32_t *nodes, int64_t *sim_steps);
+int gu_mcts_get_tree(gu_handle h, int64_t env0, int64_t n, int32_t *state, int32_t *parent, int32_t *child, uint32_t *visits, double *w,
+                     int32_t *count);
 
 /* ---- batched tabular n-step Q-learning and n-step SARSA: learner e owns env e and its table Q_e[S][4] (the gu_td_* tables) ----
  * (build-defined: the reference lists "Temporal Difference (TD) Learning with variations" on its roadmap and ships no code;
