@@ -27,6 +27,7 @@ TD_Q_LEARNING, TD_SARSA = 0, 1
 NSTEP_MAX = 16  # GU_NSTEP_MAX: the largest n of gu_nstep_run
 LAMBDA_MAX = 64  # GU_LAMBDA_MAX: the largest K (trace length) of gu_lambda_run
 REINFORCE_MAX = 1024  # GU_REINFORCE_MAX: the largest L (segment length) of gu_reinforce_run
+IS_MAX = 1024  # GU_IS_MAX: the largest L (segment length) of gu_is_run
 SEARCH_MAX_M = 64   # GU_SEARCH_MAX_M: the most rollouts per action of gu_search_run
 SEARCH_MAX_D = 256  # GU_SEARCH_MAX_D: their largest depth
 EXPLORE_MAX_C = 4096  # GU_EXPLORE_MAX_C: the most entries of gu_explore_set_tables' U and B
@@ -120,6 +121,11 @@ SIGNATURES = {
     'gu_ac_set': [_vp, _i64, _i64, _vp, _vp],
     'gu_reinforce_run': [_vp, _i64, _i32, _f64, _f64, _f64, _u32],
     'gu_reinforce_get_episode': [_vp, _i64, _i64, _vp, _vp, _vp],
+    'gu_is_init': [_vp],
+    'gu_is_run': [_vp, _i64, _i32, _f64, _u32, _f64, _u32],
+    'gu_is_get': [_vp, _i64, _i64, _vp],
+    'gu_is_set': [_vp, _i64, _i64, _vp],
+    'gu_is_get_episode': [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
     'gu_fa_init': [_vp, _i32, _i32, _vp, _f64],
     'gu_fa_run': [_vp, _i64, _i32, _f64, _f64, _u32, _u32],
     'gu_fa_get_w': [_vp, _i64, _i64, _vp],

@@ -19,6 +19,7 @@ static void gu_nstep_free(gu_engine *h);  // (tabular n-step learners, below)
 static void gu_search_free(gu_engine *h); // (rollout search, below)
 static void gu_explore_free(gu_engine *h);  // (the counts of the count-based exploration, below)
 static void gu_mcts_free(gu_engine *h);  // (the node pools of the tree search, below)
+static void gu_is_free(gu_engine *h);  // (the cumulative weights and episode buffers of the off-policy Monte-Carlo learner, below)
 static void gu_lambda_free(gu_engine *h); // (tabular lambda learners, below)
 static void gu_ac_free(gu_engine *h);     // (tabular actor-critic, below)
 static void gu_reinforce_free(gu_engine *h);  // (tabular REINFORCE, below)
@@ -182,7 +183,8 @@ int gu_destroy(gu_handle h)
                     h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next,
                     h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_lambda_w, h->d_ac_h, h->d_ac_v, h->d_rf_buf, h->d_rf_cnt,
                     h->d_fa_w, h->d_fa_phi, h->d_fa_phi16, h->d_fa_next, h->d_search_score, h->d_search_steps, h->d_explore_n, h->d_explore_tab,
-                    h->d_mcts_pool, h->d_mcts_meta, h->d_mcts_nodes, h->d_mcts_steps, h->d_mcts_tab};
+                    h->d_mcts_pool, h->d_mcts_meta, h->d_mcts_nodes, h->d_mcts_steps, h->d_mcts_tab,
+                    h->d_is_c, h->d_is_R, h->d_is_buf, h->d_is_cnt};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -262,6 +264,7 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
         gu_search_free(h);
         gu_mcts_free(h);  // (gu_mcts_init again; the U, B and I tables stay)
     }
+    if (h->is_S && h->is_S != W * H) gu_is_free(h);  // ... and the cumulative weights: gu_is_init again
     if (h->explore_S && h->explore_S != W * H) gu_explore_free(h);  // ... and the visit counts: gu_explore_init again (the U and B tables stay)
     if (h->dyna_S && h->dyna_S != W * H) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
     if (h->ac_S && h->ac_S != W * H) gu_ac_free(h);  // ... and actor-critic tables: gu_ac_init again
@@ -1834,6 +1837,150 @@ int gu_reinforce_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, 
             const size_t i = (size_t)e * GU_REINFORCE_MAX + j, b = ((size_t)j * n + e) * 2;
             if (sa) sa[i] = j < c[e] ? w[b] : -1;
             if (reward) reward[i] = j < c[e] ? w[b + 1] : 0;
+        }
+    if (count)
+        for (int64_t e = 0; e < n; ++e) count[e] = c[e];
+    return GU_OK;
+}
+
+// ---------------------------------------------------------------------------------- off-policy Monte-Carlo control, weighted importance sampling (gu_is.hip)
+static void gu_is_free(gu_engine *h)
+{
+    for (void *p : {(void *)h->d_is_c, (void *)h->d_is_R, (void *)h->d_is_buf, (void *)h->d_is_cnt})
+        if (p) (void)hipFree(p);
+    h->d_is_c = nullptr;
+    h->d_is_R = nullptr;
+    h->d_is_buf = nullptr;
+    h->d_is_cnt = nullptr;
+    h->is_S = 0;
+    h->is_eps = -1;
+    h->is_cap = 0;
+    h->is_key = 0;
+}
+
+int gu_is_init(gu_handle h)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    gu_tabular_drop_carry(h);
+    const size_t bytes = (size_t)h->N * (size_t)h->S * 4 * sizeof(double);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!h->d_is_c || h->is_S != h->S) {
+        gu_is_free(h);
+        int rc = gu_tabular_fits(h, bytes, "cumulative weights");
+        if (rc != GU_OK) return rc;
+        GU_HIP(hipMalloc(&h->d_is_c, bytes));
+        GU_HIP(hipMalloc(&h->d_is_R, 20 * sizeof(double)));
+        h->is_S = h->S;
+    }
+    GU_HIP(hipMemsetAsync(h->d_is_c, 0, bytes, h->stream));
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+// R[m][c] = pi(a|s) / b(a|s) for the tie-uniform greedy target (1 / m_now) and the epsilon-greedy behaviour at action time (c of the
+// row's maxima tied, the action one of them; c = 0: not one of them), laid out for the kernel as R[c * 4 + m - 1]
+static void gu_is_ratios(uint32_t eps_q16, double *R)
+{
+    const double eps = (double)eps_q16 / 65536.0;
+    for (int c = 0; c <= 4; ++c) {
+        const double b = c == 0 ? eps * 0.25 : (1.0 - eps) / (double)c + eps * 0.25;
+        for (int m = 1; m <= 4; ++m) R[c * 4 + m - 1] = b == 0.0 ? 0.0 : (1.0 / (double)m) / b;
+    }
+}
+
+int gu_is_run(gu_handle h, int64_t T, int32_t L, double gamma, uint32_t eps_q16, double w_cap, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(h->d_is_c && h->is_S == h->S, GU_ERR_STATE, "no cumulative weights: call gu_is_init first");
+    GU_REQUIRE(L >= 1 && L <= GU_IS_MAX, GU_ERR_INVALID, "L %d out of range (1 .. %d)", L, GU_IS_MAX);
+    GU_REQUIRE(w_cap >= 1.0 && w_cap <= 0x1p256, GU_ERR_INVALID, "w_cap %g outside [1, 2^256]", w_cap);
+    int rc = gu_tabular_check(h, "gu_is_run", T, -1, eps_q16, 0.0, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    if (h->is_cap < L) {  // (a call with another L drops the buffer anyway: nothing to keep)
+        const size_t slots = (size_t)h->N * (size_t)L;
+        GU_HIP(hipStreamSynchronize(h->stream));
+        rc = gu_tabular_fits(h, slots * 2 * sizeof(int32_t) + (size_t)h->N * sizeof(int32_t), "episode buffers");
+        if (rc != GU_OK) return rc;
+        for (void *p : {(void *)h->d_is_buf, (void *)h->d_is_cnt})
+            if (p) (void)hipFree(p);
+        h->d_is_buf = nullptr;
+        h->d_is_cnt = nullptr;
+        h->is_cap = 0;
+        h->is_key = 0;
+        GU_HIP(hipMalloc(&h->d_is_buf, slots * 2 * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_is_cnt, (size_t)h->N * sizeof(int32_t)));
+        h->is_cap = L;
+    }
+    if (h->is_eps != (int64_t)eps_q16) {  // (a launch still in flight reads the table of its own epsilon)
+        double R[20];
+        gu_is_ratios(eps_q16, R);
+        GU_HIP(hipStreamSynchronize(h->stream));
+        h->is_eps = -1;
+        GU_HIP(hipMemcpy(h->d_is_R, R, sizeof(R), hipMemcpyHostToDevice));
+        h->is_eps = (int64_t)eps_q16;
+    }
+    return gu_launch_is(h, T, L, gamma, eps_q16, w_cap, flags);
+}
+
+static int gu_is_range(gu_engine *h, int64_t env0, int64_t n, const void *c)
+{
+    GU_NEED_GRID(h);
+    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
+    GU_REQUIRE(h->d_is_c && h->is_S == h->S, GU_ERR_STATE, "no cumulative weights: call gu_is_init first");
+    GU_REQUIRE(c != nullptr, GU_ERR_INVALID, "c is NULL");
+    return gu_env_range(h, env0, n);
+}
+
+int gu_is_get(gu_handle h, int64_t env0, int64_t n, double *c)
+{
+    GU_ENTER(h);
+    int rc = gu_is_range(h, env0, n, c);
+    if (rc != GU_OK) return rc;
+    const size_t row = (size_t)h->S * 4;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n) GU_HIP(hipMemcpy(c, h->d_is_c + (size_t)env0 * row, (size_t)n * row * sizeof(double), hipMemcpyDeviceToHost));
+    return GU_OK;
+}
+
+int gu_is_set(gu_handle h, int64_t env0, int64_t n, const double *c)
+{
+    GU_ENTER(h);
+    int rc = gu_is_range(h, env0, n, c);
+    if (rc != GU_OK) return rc;
+    const size_t row = (size_t)h->S * 4, k = (size_t)n * row;
+    for (size_t i = 0; i < k; ++i)
+        GU_REQUIRE(std::isfinite(c[i]) && c[i] >= 0.0, GU_ERR_INVALID, "c[%zu] = %g: every entry must be finite and not negative", i, c[i]);
+    gu_tabular_drop_carry(h);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n) GU_HIP(hipMemcpy(h->d_is_c + (size_t)env0 * row, c, k * sizeof(double), hipMemcpyHostToDevice));
+    return GU_OK;
+}
+
+int gu_is_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *cls, int32_t *count)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    int rc = gu_env_range(h, env0, n);
+    if (rc != GU_OK) return rc;
+    const int32_t L = h->is_key;  // (0: the buffer was dropped and reads as empty, whatever the device copy still holds)
+    std::vector<int32_t> c(n), w((size_t)n * (size_t)L * 2);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n && L) {
+        GU_HIP(hipMemcpy(c.data(), h->d_is_cnt + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        GU_HIP(hipMemcpy2D(w.data(), (size_t)n * 8, h->d_is_buf + (size_t)env0 * 2, (size_t)h->N * 8, (size_t)n * 8, (size_t)L,
+                           hipMemcpyDeviceToHost));  // rows k = 0 .. L-1 of [L][N], columns env0 .. env0+n-1
+    }
+    for (int64_t e = 0; e < n; ++e)
+        for (int32_t j = 0; j < GU_IS_MAX; ++j) {
+            const size_t i = (size_t)e * GU_IS_MAX + j, b = ((size_t)j * n + e) * 2;
+            const bool live = j < c[e];
+            if (sa) sa[i] = live ? w[b] : -1;
+            if (reward) reward[i] = live ? w[b + 1] >> 3 : 0;
+            if (cls) cls[i] = live ? w[b + 1] & 7 : 0;
         }
     if (count)
         for (int64_t e = 0; e < n; ++e) count[e] = c[e];

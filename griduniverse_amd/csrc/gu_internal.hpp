@@ -279,6 +279,15 @@ struct gu_engine {
     int32_t *d_rf_cnt = nullptr;  // [N] their entries
     int32_t rf_cap = 0;           // entries per env the storage holds (0: none allocated)
     int32_t rf_key = 0;           // L of the last call that touched the envs if it was a gu_reinforce_run, else 0 (buffer dropped)
+    // batched off-policy Monte-Carlo control with weighted importance sampling (gu_is.hip): off until gu_is_init; learns into d_q
+    double *d_is_c = nullptr;     // [N][is_S][4] cumulative weights
+    int32_t is_S = 0;             // states of the weights (0: none allocated); a grid of another size drops them
+    double *d_is_R = nullptr;     // [5][4] the ratio table of is_eps, R[c * 4 + m - 1]
+    int64_t is_eps = -1;          // eps_q16 of the table on the device (-1: none yet)
+    int32_t *d_is_buf = nullptr;  // [is_cap][N] the episode buffers, step-major, oldest first: 8-byte entries {s*4+a, r*8+c}
+    int32_t *d_is_cnt = nullptr;  // [N] their entries
+    int32_t is_cap = 0;           // entries per env the storage holds (0: none allocated)
+    int32_t is_key = 0;           // L of the last call that touched the envs if it was a gu_is_run, else 0 (buffer dropped)
     // batched semi-gradient SARSA / Q-learning on binary features (gu_fa.hip): off until gu_fa_init; weights of its own, not d_q
     double *d_fa_w = nullptr;         // [N][fa_F][4] one float64 weight table per env
     int32_t *d_fa_phi = nullptr;      // [fa_S][fa_K] the feature table, shared by all envs
@@ -478,6 +487,9 @@ int gu_launch_ac(gu_engine *h, int64_t T, double alpha_actor, double alpha_criti
 // ---- batched tabular REINFORCE with baseline (gu_reinforce.hip) ------------------------
 int gu_launch_reinforce(gu_engine *h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags);
 
+// ---- batched off-policy Monte-Carlo control with weighted importance sampling (gu_is.hip) ----
+int gu_launch_is(gu_engine *h, int64_t T, int32_t L, double gamma, uint32_t eps_q16, double w_cap, uint32_t flags);
+
 // ---- batched semi-gradient SARSA / Q-learning on binary features (gu_fa.hip) ----------------
 int gu_fa_fill(gu_engine *h, double w0);  // every weight = w0 (async)
 int gu_fa_fold_q(gu_engine *h, int64_t env0, int64_t n, double *d_out);  // Q of envs env0 .. env0+n-1 into d_out [n][S][4] (async)
@@ -485,7 +497,7 @@ int gu_launch_fa(gu_engine *h, int64_t T, int32_t method, double alpha, double g
 
 // every call that touches the envs other than the learner launches ends what the learners carry from one launch to the next:
 // gu_td_run's and gu_fa_run's SARSA actions, gu_nstep_run's window (its pending updates are discarded, not flushed), gu_lambda_run's
-// window and gu_reinforce_run's episode buffer (its pending transitions are discarded, not learned from)
+// window and the episode buffers of gu_reinforce_run and gu_is_run (their pending transitions are discarded, not learned from)
 static inline void gu_tabular_drop_carry(gu_engine *h)
 {
     h->td_carry = false;
@@ -493,6 +505,7 @@ static inline void gu_tabular_drop_carry(gu_engine *h)
     h->nstep_key = 0;
     h->lambda_key = 0;
     h->rf_key = 0;
+    h->is_key = 0;
 }
 
 // ---- agent trail (gu_trail.hip): no-ops while the trail is off ----------------------

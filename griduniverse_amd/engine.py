@@ -559,6 +559,45 @@ class Engine(object):
         check(self.lib.gu_reinforce_get_episode(self._h, int(env0), n, ptr(out['sa']), ptr(out['reward']), ptr(out['count'])))
         return out
 
+    # ------------------------------------------------------------------ off-policy Monte-Carlo control, weighted importance sampling (include/gu.h: gu_is_*)
+    def is_init(self):
+        """One float64 table [S][4] of cumulative weights per env, all zero; the Q tables come from td_init."""
+        check(self.lib.gu_is_init(self._h))
+
+    def is_run(self, T, L=64, gamma=0.99, eps_q16=6554, w_cap=2.0 ** 64, trajectory=False, stats=False):
+        """T iterations of off-policy every-visit Monte-Carlo control with weighted importance sampling per env in one launch,
+        into the td_init tables and the is_init weights: epsilon-greedy behaviour, greedy target; the backward pass over a
+        segment runs when its episode ends or after L (1 .. IS_MAX) steps and stops at the first action that is no longer
+        greedy, or where the weight leaves [2^-256, w_cap).  The episode buffer carries into the next is_run with the same L;
+        any other call in between drops it.  Rows and statistics as td_run()."""
+        check(self.lib.gu_is_run(self._h, int(T), int(L), float(gamma), int(eps_q16), float(w_cap), _learner_flags(trajectory, stats)))
+
+    def is_get(self, env0=0, n=None):
+        """float64[n, S, 4]: the cumulative weights of envs env0 .. env0+n-1 (all from env0 when n is None)."""
+        n = self.N - int(env0) if n is None else int(n)
+        c = np.empty((max(n, 0), self.spec.S, 4), np.float64)
+        check(self.lib.gu_is_get(self._h, int(env0), n, ptr(c)))
+        return c
+
+    def is_set(self, c, env0=0):
+        """Install cumulative weights float64[n, S, 4] (or [S, 4] for one env) for envs env0 .. env0+n-1: finite, not negative."""
+        S = self.spec.S
+        c = np.asarray(c, np.float64)
+        c = _lib.as_array(c.reshape((-1, S, 4)) if c.ndim == 2 else c, np.float64, None, 'c')
+        if c.ndim != 3 or c.shape[1:] != (S, 4):
+            raise ValueError('c must have shape (n, {}, 4), got {}'.format(S, c.shape))
+        check(self.lib.gu_is_set(self._h, int(env0), c.shape[0], ptr(c)))
+
+    def is_get_episode(self, env0=0, n=None):
+        """The episode buffers of envs env0 .. env0+n-1: dict sa / reward / cls int32[n, IS_MAX] (pending s*4+a, r and the class
+        of the action, oldest first; -1 / 0 / 0 beyond count) and count int32[n] (0 once dropped)."""
+        n = self.N - int(env0) if n is None else int(n)
+        n0 = max(n, 0)
+        out = dict(sa=np.empty((n0, _lib.IS_MAX), np.int32), reward=np.empty((n0, _lib.IS_MAX), np.int32),
+                   cls=np.empty((n0, _lib.IS_MAX), np.int32), count=np.empty(n0, np.int32))
+        check(self.lib.gu_is_get_episode(self._h, int(env0), n, ptr(out['sa']), ptr(out['reward']), ptr(out['cls']), ptr(out['count'])))
+        return out
+
     # ------------------------------------------------------------------ semi-gradient SARSA / Q-learning on features (include/gu.h: gu_fa_*)
     _fa_F = None  # features of the table installed by fa_init
 

@@ -20,6 +20,16 @@ from .envs.griduniverse_env import GridUniverseEnv
 from .grid import GridSpec
 
 
+def check_off_policy_args(max_episode_len, epsilon, w_cap):
+    """The argument checks of off_policy_mc_run and algorithms.off_policy (ValueError)."""
+    if not 1 <= int(max_episode_len) <= _lib.IS_MAX:
+        raise ValueError('max_episode_len must lie in 1 .. {}'.format(_lib.IS_MAX))
+    if not 0.0 <= float(epsilon) <= 1.0:
+        raise ValueError('epsilon must lie in [0, 1]')
+    if not 1.0 <= float(w_cap) <= 2.0 ** 256:  # (NaN and infinity fail too)
+        raise ValueError('w_cap must lie in [1, 2**256]')
+
+
 class VecGridUniverse(object):
     _td_ready = False  # the engine holds Q tables (td_run / set_q_table allocate them on first use)
     _dyna_ready = False  # ... and Dyna-Q models (dyna_run / model allocate them on first use)
@@ -28,6 +38,7 @@ class VecGridUniverse(object):
     _tree_sims = 0  # simulations the tree-search node pools hold (tree_search_run allocates them on first use and when it needs more)
     _tree_tables = False  # set_tree_search was called (tree_search_run installs UCB1 tables with c = 3 otherwise)
     _ac_ready = False  # ... and actor-critic tables (actor_critic_run / set_actor_critic allocate them on first use)
+    _is_ready = False  # ... and cumulative importance weights (off_policy_mc_run / importance_weights allocate them on first use)
     _fa_ready = False  # ... and features with their weights (set_features installs them; nothing does it implicitly)
 
     def __init__(self, num_envs, grid_shape=(4, 4), *, initial_state=0, goal_states=None, lava_states=None,
@@ -392,6 +403,44 @@ class VecGridUniverse(object):
     def episode_buffer(self, env0=0, n=None):
         """The episode buffers of envs env0 .. env0+n-1 (Engine.reinforce_get_episode)."""
         return self.engine.reinforce_get_episode(env0, n)
+
+    def _ensure_is(self):
+        """Cumulative weights on the engine: zeros on first use (and tables of zeros if the envs had no Q tables)."""
+        self._ensure_q()
+        if not self._is_ready:
+            self.engine.is_init()
+            self._is_ready = True
+
+    def off_policy_mc_run(self, T, max_episode_len=64, discount_factor=0.99, epsilon=0.1, w_cap=2.0 ** 64, trajectory=False,
+                          stats=False):
+        """T iterations of batched off-policy every-visit Monte-Carlo control with weighted importance sampling (Sutton & Barto
+        5.7): env e acts epsilon-greedily on its own Q table [S][4] and, when its episode ends, walks it backwards, learning
+        the GREEDY policy's values from returns weighted by the importance ratio, up to the first action that is no longer
+        greedy; an episode still running after `max_episode_len` (1 .. 1024) steps is cut there and its return bootstraps on
+        max Q (include/gu.h: gu_is_run).  A pass also ends where its weight reaches `w_cap` (1 .. 2^256).  The Q tables are
+        td_run's; the first call gives every env tables of zeros and zeroed cumulative weights.  Consecutive calls with the same
+        max_episode_len carry the episode buffer; any other call in between drops it.  Returns a dict like td_run()."""
+        check_off_policy_args(max_episode_len, epsilon, w_cap)
+        self._ensure_is()
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.is_run(T, max_episode_len, discount_factor, int(round(float(epsilon) * 65536)), w_cap, trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def importance_weights(self, env0=0, n=None):
+        """float64[n, S, 4]: the cumulative weights C of envs env0 .. env0+n-1 (to the end when n is None); zeros before the
+        first off_policy_mc_run."""
+        self._ensure_is()
+        return self.engine.is_get(env0, n)
+
+    def set_importance_weights(self, c, env0=0):
+        """Install cumulative weights float64[n, S, 4] (or [S, 4]) for envs env0 ..: finite and not negative."""
+        self._ensure_is()
+        self.engine.is_set(c, env0)
+
+    def off_policy_episode_buffer(self, env0=0, n=None):
+        """The episode buffers of off_policy_mc_run of envs env0 .. env0+n-1 (Engine.is_get_episode)."""
+        return self.engine.is_get_episode(env0, n)
 
     def preferences(self, env0=0, n=None):
         """float64[n, S, 4]: the actor's preference tables of envs env0 .. env0+n-1 (to the end when n is None)."""

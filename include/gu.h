@@ -603,6 +603,71 @@ int gu_ac_set(gu_handle h, int64_t env0, int64_t n, const double *pref, const do
 int gu_reinforce_run(gu_handle h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags);
 int gu_reinforce_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count);
 
+/* ---- batched off-policy Monte-Carlo control with weighted importance sampling: learner e owns env e and its table Q_e[S][4] ----
+ * (build-defined: the second half of the reference's roadmap entry "Off-policy control (Q-Learning, Importance Sampling)", for
+ * which it ships no code -- gu_td_run is the first half; Sutton & Barto 5.7, every-visit, WEIGHTED importance sampling;
+ * tests/_is_oracle.py is the CPU restatement.)  The target policy is greedy on Q_e with ties shared equally, the behaviour policy is
+ * gu_td_run's epsilon-greedy on the same table.  Learner e owns env e, its gu_td_* table Q_e[S][4], a float64 table C_e[S][4] of
+ * CUMULATIVE WEIGHTS, initially 0, and an EPISODE BUFFER E_e: the entries (s_k, a_k, r_k, c_k) of its current segment, oldest
+ * first, at most L-1 of them between iterations.  All arithmetic is float64 with one rounding per operation and no contraction.
+ * THE RATIO TABLE R[m][c], m = 1..4, c = 0..4: pi(a|s) / b(a|s) for an action that is one of m maxima of its row now and was, when
+ * it was taken, one of c maxima (c = 0: none of them).  Computed on the host from eps_q16: eps = eps_q16 / 65536.0;
+ * b_0 = eps * 0.25; b_c = (1.0 - eps) / c + eps * 0.25; R[m][c] = (1.0 / m) / b_c, and 0.0 where b_c == 0 (only c = 0 at epsilon 0,
+ * a class that cannot occur).  The kernel holds these 20 doubles and computes no division for the ratio.  The tie rule's
+ * (x * m) >> 14 is exactly uniform only for m = 1, 2, 4: for m = 3 the three actions have probabilities 5462, 5461, 5461 / 16384,
+ * and the ratios are the nominal ones.
+ * RECIP(x), the correctly rounded 1 / x of a positive normal x: x = f * 2^p with f in [1, 2); the build's correctly rounded
+ * reciprocal of f (csrc/gu_softmax.hpp, gu_recip14) scaled by 2^-p, which is exact.  The restatement writes 1.0 / x.
+ * One iteration of gu_is_run for env e at 64-bit step count t:
+ *   1. reset: lazy auto-reset, exactly as rule 1 of gu_td_run (the buffer is empty here: see 5);
+ *   2. behaviour action: rule 2 of gu_td_run unchanged (the stream-4 word at t, epsilon-greedy on Q_e[s] with its tie rule; no
+ *      other RNG stream).  Its CLASS c: m, the number of entries of Q_e[s] equal to the row maximum (folded left to right with
+ *      `>`), if Q_e[s][a] equals that maximum -- an exploring draw that happens to be greedy included --, else 0;
+ *   3. (s', r, d) by the engine's move rule (absorbing terminal); t += 1; append (s, a, r, c) to E_e;
+ *   4. if not d and E_e holds fewer than L entries: the iteration ends here;
+ *   5. segment end (d, or E_e holds L entries): G = 0.0 if d, else max Q_e[s'], folded left to right with `>` and read before any
+ *      write of this pass (a truncated segment bootstraps; the env is NOT reset and goes on from s').  W = 1.0.  Then for every
+ *      entry, newest to oldest, in this order:
+ *        G = r_k + gamma * G;
+ *        C_e[s_k][a_k] = C_e[s_k][a_k] + W;
+ *        Q_e[s_k][a_k] = Q_e[s_k][a_k] + (W * RECIP(C_e[s_k][a_k])) * (G - Q_e[s_k][a_k]);
+ *        with the row Q_e[s_k] as it is now: if Q_e[s_k][a_k] is not equal to the row maximum, the pass ends and the older
+ *        entries are discarded unlearned (the target policy would not have taken a_k: their weight is 0);
+ *        otherwise W = W * R[m_now][c_k], m_now the number of maxima of the row now;
+ *        if not 2^-256 <= W < w_cap, the pass ends likewise.
+ *      E_e ends empty;
+ *   6. the next iteration sees the tables after the pass.
+ * W stays inside [2^-256, w_cap) wherever it is added to C, so a nonzero entry of C that the learner made lies in
+ * [2^-256, 2^320) and RECIP never sees a subnormal, zero or infinity (entries installed by gu_is_set above 2^320 are outside that
+ * guarantee).  w_cap, 1 <= w_cap <= 2^256, is also the knob of "truncated importance sampling": a small value ends passes early.
+ * Ordinary (unweighted) importance sampling is not offered: its estimates overflow.  With L long and few greedy actions the learner
+ * learns from the tails of its episodes only: on large open grids it is slower than gu_td_run (the textbook weakness).
+ * CARRY: as gu_reinforce_run's.  The buffer persists from one gu_is_run to the next when the later call directly follows the
+ * earlier one with the same L (gamma, epsilon and w_cap may change).  Any other call in between -- everything that drops
+ * gu_reinforce_run's buffer, gu_reinforce_run itself, gu_is_init, gu_is_set, a gu_is_run with another L -- drops it: the pending
+ * transitions are discarded, not learned from; and gu_is_run drops gu_reinforce_run's buffer, ends gu_td_run's SARSA carry and the
+ * windows of gu_nstep_run and gu_lambda_run.  C_e lives until gu_is_init or a grid of another size; gu_td_init and gu_td_set_q
+ * leave it alone (new Q tables under old weights learn slowly: call gu_is_init too).
+ * gu_is_init        : allocate the cumulative weights (N * S * 32 bytes; GU_ERR_NOMEM under gu_td_init's free-memory rule) and set
+ *                     them to 0.  GU_ERR_STATE before gu_td_init.
+ * gu_is_run         : T iterations per env in ONE launch (async).  1 <= L <= GU_IS_MAX.  GU_ERR_STATE before gu_td_init or
+ *                     gu_is_init; GU_ERR_INVALID for a bad L, w_cap outside [1, 2^256] (NaN included), eps_q16 above 65536, a
+ *                     non-finite gamma, T < 0 or T > 1e8, flags other than GU_F_TRAJECTORY | GU_F_STATS.  The buffer storage
+ *                     (N * (8 L + 4) bytes) is allocated on first use for the L of the call, and again for a larger one
+ *                     (GU_ERR_NOMEM as above); a grid of another size drops it with the weights.  T = 0 changes nothing.  Rows,
+ *                     statistics, the trajectory reservation and the agent trail as gu_td_run: the T real steps only.  The step
+ *                     counts advance by T.
+ * gu_is_get / gu_is_set : the cumulative weights of envs env0 .. env0+n-1 as c[n][S][4] on the host; set rejects a negative or
+ *                     non-finite entry (GU_ERR_INVALID) before it writes anything.
+ * gu_is_get_episode : the buffers of envs env0 .. env0+n-1 on the host: sa (s*4+a), reward and cls as [n][GU_IS_MAX], oldest
+ *                     first, (-1, 0, 0) beyond count; count as [n], 0 when the buffer has been dropped.  Any pointer may be NULL. */
+#define GU_IS_MAX 1024
+int gu_is_init(gu_handle h);
+int gu_is_run(gu_handle h, int64_t T, int32_t L, double gamma, uint32_t eps_q16, double w_cap, uint32_t flags);
+int gu_is_get(gu_handle h, int64_t env0, int64_t n, double *c);
+int gu_is_set(gu_handle h, int64_t env0, int64_t n, const double *c);
+int gu_is_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *cls, int32_t *count);
+
 /* ---- batched semi-gradient SARSA and Q-learning on binary features: learner e owns env e and a weight table w_e[F][4] ----
  * (build-defined: the reference's roadmap entry "Value Approximation", for which it ships no code; Sutton & Barto 10.1;
  * tests/_fa_oracle.py is the CPU restatement.)  The action values are computed, not stored.  The engine holds ONE feature table
