@@ -35,6 +35,8 @@ EXPLORE_COUNT_MAX = 0x3FFFFFFF  # GU_EXPLORE_COUNT_MAX: where a visit count satu
 EXPLORE_UCB, EXPLORE_THOMPSON = 0, 1
 MCTS_MAX_SIMS = 255   # GU_MCTS_MAX_SIMS: the most simulations per decision of gu_mcts_run (the pool of gu_mcts_init holds one node more)
 MCTS_MAX_DEPTH = 64   # GU_MCTS_MAX_DEPTH: the largest depth cap of its tree
+SENSE_EGO, SENSE_GRID = 0, 1
+SENSE_MAX_R = 7  # GU_SENSE_MAX_R: the largest radius of gu_sense's egocentric view
 FA_MAX_K = 8  # GU_FA_MAX_K: the most active features per state of gu_fa_init
 COMM_ID_BYTES = 128
 OPT_UNSET = -2 ** 63
@@ -151,6 +153,8 @@ SIGNATURES = {
     'gu_trail_enable': [_vp, _i32],
     'gu_trail_read': [_vp, _i64, _i64, _vp, _vp],
     'gu_render_policy_rgb': [_vp, _i32, _vp],
+    'gu_sense': [_vp, _i64, _i64, _i32, _i32, _vp],
+    'gu_sense_trajectory': [_vp, _i64, _i64, _i32, _i32, _vp],
     'gu_host_alloc': [_c.c_size_t, _c.POINTER(_vp)],
     'gu_host_free': [_vp],
     'gu_sync': [_vp],

@@ -3,8 +3,8 @@ approximation over K active binary features per state -- the reference's roadmap
 no code for it, so the semantics are this build's: include/gu.h, gu_fa_run).
 
 The action values are computed, not stored: Q(s) is the sum of the K weight rows [4] that the feature table phi[S][K] activates in
-s.  `tile_coding`, `state_aggregation` and `one_hot` build such tables; `semi_gradient_sarsa` / `semi_gradient_q_learning` run
-`num_learners` independent epsilon-greedy learners on the grid of a facade `GridUniverseEnv`, learner e in env e of a batch, each
+s.  `tile_coding`, `state_aggregation`, `one_hot` and `view_features` build such tables; `semi_gradient_sarsa` /
+`semi_gradient_q_learning` run `num_learners` independent epsilon-greedy learners on the grid of a facade `GridUniverseEnv`, learner e in env e of a batch, each
 with its own float64 weights, all advanced on the MI355X by one kernel (csrc/gu_fa.hip), and return the action values folded from
 the weights in the format of `temporal_difference.q_learning`, so `greedy_policy` applies unchanged.  With `one_hot` features they
 are `sarsa` / `q_learning`.
@@ -51,6 +51,21 @@ def one_hot(S):
     if S < 1:
         raise ValueError('S must be at least 1')
     return np.arange(S, dtype=np.int32)[:, None], S
+
+
+def view_features(env, radius):
+    """What the agent SEES as its only feature: phi[s] is the id of the egocentric view of `radius` from cell s (grid.view_table:
+    the classes of the (2 * radius + 1)^2 cells around it, 4 outside the grid), ids in order of first appearance over s = 0 .. S-1,
+    so states that look alike share one weight row -- a perceptually aliased learner on the kernel of `semi_gradient_*`.  `env`: a
+    GridUniverseEnv (or anything GridSpec.from_env reads) or a GridSpec.  Returns (phi int32[S, 1], F), F the number of distinct
+    views; for radius >= max(W, H) - 1 the border places the agent and the features are one_hot's, relabelled."""
+    from ..grid import GridSpec, view_table
+    spec = env if isinstance(env, GridSpec) else GridSpec.from_env(env)
+    views = view_table(spec, radius).reshape(spec.S, -1)
+    ids, phi = {}, np.empty((spec.S, 1), np.int32)
+    for s in range(spec.S):
+        phi[s, 0] = ids.setdefault(views[s].tobytes(), len(ids))
+    return phi, len(ids)
 
 
 def _fa(method, env, num_steps, features, alpha, discount_factor, epsilon, num_learners, seed, w0):

@@ -11,6 +11,7 @@
 // (rendering.py:287-311): which cells, which alpha, which order are the reference's (tests/golden/trail.json); the blend is the
 // integer rule stated in the kernel.
 #include "gu_internal.hpp"
+#include "gu_tile.hpp"
 
 struct RenderArgs {
     const uint8_t *cell;   // [G][flags | reward] (absorbing map: flags carry TERM / reward code / WALL)
@@ -25,15 +26,8 @@ struct RenderArgs {
     int32_t trail_cap;
 };
 
-// Which texture a cell gets is the reference's rule (core/envs/rendering.py:119-133: goal, else lava, else wall, else ground;
-// pinned by tests/golden/arrows.json "tiles"); the COLOURS stand in for its four textures and are build-defined.
-__device__ __forceinline__ uint32_t gu_tile_kind(const uint8_t *kind, uint32_t f, int64_t index)
-{
-    if (kind) return kind[index];
-    // device-generated mazes: one goal, no lava, the goal never on a wall -- the flags are unambiguous
-    return (f & GU_CELL_TERM) ? ((f & GU_CELL_RMINUS) ? 2u : 3u) : (f & GU_CELL_WALL) ? 1u : 0u;
-}
-
+// Which texture a cell gets is the reference's rule (gu_tile.hpp: gu_tile_kind, shared with the sensor); the COLOURS stand in for its
+// four textures and are build-defined.
 __device__ __forceinline__ void gu_tile_colour(uint32_t k, uint8_t &r, uint8_t &g, uint8_t &b)
 {
     if (k == 3u) { r = 40; g = 180; b = 60; }        // goal   (wbs_texture_05_resized_green.jpg)

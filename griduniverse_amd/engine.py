@@ -10,7 +10,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check, ptr
-from .grid import GridSpec
+from .grid import GridSpec, check_sense_args
 
 _POLICIES = {'uniform': _lib.POLICY_UNIFORM, 'stream': _lib.POLICY_STREAM, 'greedy': _lib.POLICY_GREEDY,
              'sample': _lib.POLICY_SAMPLE}
@@ -807,6 +807,42 @@ class Engine(object):
         out = np.empty((int(n_envs), H * cell_px, W * cell_px, 3), np.uint8)
         check(self.lib.gu_render_rgb(self._h, int(env0), int(n_envs), int(cell_px), ptr(out)))
         return out
+
+    def _view_shape(self, mode, radius):
+        return (self.spec.H, self.spec.W) if mode else (2 * radius + 1, 2 * radius + 1)
+
+    def sense(self, env0=0, n=None, radius=1, mode='ego'):
+        """uint8[n, K, K] ('ego', K = 2 * radius + 1) or uint8[n, H, W] ('grid'): what envs env0 .. env0+n-1 (to the end when n is
+        None) see from where they stand (include/gu.h: gu_sense)."""
+        m, r = check_sense_args(radius, mode)
+        n = self.N - int(env0) if n is None else int(n)
+        out = np.empty((max(n, 0),) + self._view_shape(m, r), np.uint8)
+        check(self.lib.gu_sense(self._h, int(env0), n, m, r, ptr(out)))
+        return out
+
+    def sense_trajectory(self, t0, T, radius=1, mode='ego', chunk_bytes=256 << 20):
+        """uint8[T, N, K, K] or uint8[T, N, H, W]: the views along rows t0 .. t0+T-1 of the trajectory buffer, the position
+        being each row's obs (include/gu.h: gu_sense_trajectory).  One library call per run of rows of at most `chunk_bytes`."""
+        m, r = check_sense_args(radius, mode)
+        t0, T = int(t0), int(T)
+        shape = self._view_shape(m, r)
+        out = np.empty((max(T, 0), self.N) + shape, np.uint8)
+        rows = max(1, int(chunk_bytes) // (self.N * shape[0] * shape[1]))
+        if T <= 0:  # (the library's message)
+            check(self.lib.gu_sense_trajectory(self._h, t0, T, m, r, None))
+        for r0 in range(0, T, rows):
+            nr = min(rows, T - r0)
+            check(self.lib.gu_sense_trajectory(self._h, t0 + r0, nr, m, r, ptr(out[r0:r0 + nr])))
+        return out
+
+    def sense_device(self, T=None, t0=0, radius=1, mode='ego'):
+        """The sensor kernel alone, for timing (tools/sense_rate.py): the views of the current state (T None) or of T rows stay
+        in the engine's scratch memory; nothing is copied."""
+        m, r = check_sense_args(radius, mode)
+        if T is None:
+            check(self.lib.gu_sense(self._h, 0, self.N, m, r, None))
+        else:
+            check(self.lib.gu_sense_trajectory(self._h, int(t0), int(T), m, r, None))
 
     def trail_enable(self, capacity=500):
         """Keep the reference viewer's agent trail per env (env:92-93, 182-184, 190: the cell after every step, newest `capacity`

@@ -389,6 +389,17 @@ class GridUniverseEnv(object):
             sys.stdout.write(''.join('{:<5}'.format(cell) for cell in row) + '\n')
         sys.stdout.write('\n')
 
+    def sense(self, radius=1, mode='ego'):
+        """What the agent sees from its current state (an addition of this build; the reference's roadmap asks for it):
+        mode='ego' -- uint8[K, K], K = 2 * radius + 1, radius 0 .. 7, entry [dy, dx] the class of the cell dy - radius rows and
+        dx - radius columns from the agent (0 ground, 1 wall, 2 lava, 3 goal by the viewer's tile rule, 4 outside the grid);
+        mode='grid' -- uint8[H, W], the class of every cell plus 8 on the agent's.  Computed on the host from the grid lists as
+        they are now; the rule is VecGridUniverse.sense's (include/gu.h: gu_sense)."""
+        from ..grid import check_sense_args, grid_view, view_table
+        m, r = check_sense_args(radius, mode)
+        spec = GridSpec.from_env(self)
+        return grid_view(spec, self._state) if m else view_table(spec, r)[int(self._state)].copy()
+
     def seed(self, seed=None):
         self.np_random = np.random.RandomState(None if seed is None else int(seed) % (2 ** 32))
         return [seed]

@@ -76,3 +76,46 @@ class GridSpec(object):
     def key(self):
         return (self.W, self.H, tuple(self.starts), self.wall.tobytes(), self.goal.tobytes(),
                 self.lava.tobytes(), self.reward.tobytes())
+
+
+# ---- agent sensors: the host mirror of csrc/gu_sense.hip (include/gu.h: gu_sense) ----------------------------------
+SENSE_MAX_R = 7   # GU_SENSE_MAX_R
+SENSE_OUTSIDE = 4  # class of a cell outside the grid
+SENSE_AGENT = 8    # added to the agent's cell in the whole-grid view
+
+
+def check_sense_args(radius, mode):
+    """The argument checks of every sense() (ValueError); returns (mode, radius) as the library takes them."""
+    if mode not in ('ego', 'grid'):
+        raise ValueError("mode must be 'ego' or 'grid'")
+    if mode == 'grid':
+        return 1, 0
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= SENSE_MAX_R:
+        raise ValueError('radius must be an integer in 0 .. {}'.format(SENSE_MAX_R))
+    return 0, int(radius)
+
+
+def cell_classes(spec):
+    """uint8[S]: the class of every cell by the reference viewer's tile rule (core/envs/rendering.py:119-133): goal -> 3, else
+    lava -> 2, else wall -> 1, else ground -> 0."""
+    return np.where(spec.goal, 3, np.where(spec.lava, 2, np.where(spec.wall, 1, 0))).astype(np.uint8)
+
+
+def view_table(spec, radius):
+    """uint8[S, K, K], K = 2 * radius + 1: the egocentric view from every cell (walls included): entry [s, dy, dx] is the class
+    of cell (y + dy - radius, x + dx - radius) for s = y * W + x, 4 outside the grid."""
+    _, r = check_sense_args(radius, 'ego')
+    K = 2 * r + 1
+    padded = np.pad(cell_classes(spec).reshape(spec.H, spec.W), r, mode='constant', constant_values=SENSE_OUTSIDE)
+    windows = np.lib.stride_tricks.sliding_window_view(padded, (K, K))  # [H, W, K, K]
+    return np.ascontiguousarray(windows.reshape(spec.S, K, K))
+
+
+def grid_view(spec, pos):
+    """uint8[H, W]: the whole-grid view of an agent on cell `pos`: the class of every cell, plus 8 on the agent's."""
+    pos = int(pos)
+    if not 0 <= pos < spec.S:
+        raise ValueError('position {} is outside the {}x{} grid'.format(pos, spec.W, spec.H))
+    view = cell_classes(spec)
+    view[pos] += SENSE_AGENT
+    return view.reshape(spec.H, spec.W)

@@ -463,6 +463,18 @@ class VecGridUniverse(object):
         device's (griduniverse_amd.softmax)."""
         return softmax.softmax_policy(self.preferences(env0, n))
 
+    def sense(self, radius=1, mode='ego', env0=0, n=None):
+        """What the agents see from where they stand: uint8[n, K, K] egocentric views of radius 0 .. 7 (K = 2 * radius + 1; entry
+        [dy, dx] is the class of the cell dy - radius rows and dx - radius columns from the agent: 0 ground, 1 wall, 2 lava,
+        3 goal, 4 outside the grid), or -- mode='grid' -- uint8[n, H, W], the class of every cell plus 8 on the agent's, for envs
+        env0 .. env0+n-1 (to the end when n is None).  Computed on the device (include/gu.h: gu_sense)."""
+        return self.engine.sense(env0, n, radius, mode)
+
+    def sense_trajectory(self, T, radius=1, mode='ego', t0=0):
+        """uint8[T, N, K, K] or uint8[T, N, H, W]: the same views along rows t0 .. t0+T-1 of the last rollout(trajectory=True) or
+        learner launch with trajectory=True, seen from each row's obs.  Packed rows (trajectory='packed') are refused."""
+        return self.engine.sense_trajectory(t0, T, radius, mode)
+
     def done_indices(self):
         return self.engine.done_indices()
 

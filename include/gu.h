@@ -808,6 +808,32 @@ int gu_trail_read(gu_handle h, int64_t env0, int64_t n_envs, int32_t *cells, int
  * included, the base edge excluded).  Probabilities are expected in [0, 1] (an arrow never leaves its tile then). */
 int gu_render_policy_rgb(gu_handle h, int32_t cell_px, uint8_t *rgb);
 
+/* ---- agent sensors: what every env SEES, as small uint8 views ------------------------------------------------
+ * The reference ships no sensor; its roadmap asks for "different sensor configurations for the agent so it can be defined
+ * whether the agent field of view is constrained to the current state, surrounding states or the complete grid".  The rule
+ * is build-defined:
+ *   class of a cell: the viewer's tile rule (core/envs/rendering.py:119-133, pinned by tests/golden/arrows.json "tiles"):
+ *     goal -> 3, else lava -> 2, else wall -> 1, else ground -> 0 (so goal+lava and goal+wall are goal, lava+wall is lava);
+ *     a cell outside the grid has class 4.  Device-generated mazes: the class follows from the cell's flags.
+ *   GU_SENSE_EGO, radius r in 0 .. GU_SENSE_MAX_R, K = 2r + 1: for an agent on cell s = y*W + x,
+ *     view[dy][dx] = class of cell (y + dy - r, x + dx - r), 4 where that lies outside the grid; r = 0 is the class of the
+ *     agent's own cell.  The agent is always at the centre and is not marked.
+ *   GU_SENSE_GRID: view[y][x] = class of cell y*W + x, plus 8 on the agent's cell; H x W, the radius is ignored.
+ * gu_sense: the position is the env's current one (under lazy auto-reset a finished env still stands on its terminal cell);
+ *   view[n][K][K] or [n][H][W] for envs env0 .. env0+n-1.
+ * gu_sense_trajectory: the position is the obs value of the row and env; view[T][N][K][K] or [T][N][H][W] for rows t0 .. t0+T-1
+ *   of the trajectory buffer, in either int32 layout (GU_OPT_TRAJ_LAYOUT).
+ * view == NULL: the kernel runs into the engine's scratch memory and nothing is copied (timing: gu_timer_begin / gu_timer_end).
+ * GU_ERR_STATE: no grid; rows not in the trajectory buffer or nothing written there yet; a packed buffer (GU_F_PACKED).
+ * GU_ERR_INVALID: unknown mode; radius outside 0 .. GU_SENSE_MAX_R in GU_SENSE_EGO; env range outside the batch; more than 2^32
+ *   bytes of views in one call.  Neither call touches env state, RNG streams, what the learners carry from launch to launch,
+ *   their windows and buffers, or the trajectory buffer. */
+#define GU_SENSE_EGO 0
+#define GU_SENSE_GRID 1
+#define GU_SENSE_MAX_R 7
+int gu_sense(gu_handle h, int64_t env0, int64_t n, int32_t mode, int32_t radius, uint8_t *view);
+int gu_sense_trajectory(gu_handle h, int64_t t0, int64_t T, int32_t mode, int32_t radius, uint8_t *view);
+
 /* ---- page-locked host memory -----------------------------------------------------
  * Buffers from gu_host_alloc make gu_step (with GU_F_PINNED_IO), gu_read_outputs and gu_read_trajectory copy at
  * the full PCIe rate; numpy arrays can be built on them (np.ctypeslib / np.frombuffer). */
