@@ -79,7 +79,7 @@ static void gu_ac_fill_one(gu_engine *h, double *p, size_t n, double x)
     hipLaunchKernelGGL(gu_ac_fill_kernel, dim3(blocks), dim3(256), 0, h->stream, p, n, x);
 }
 
-int gu_ac_fill(gu_engine *h, double h0, double v0)
+static int gu_ac_fill(gu_engine *h, double h0, double v0)
 {
     const size_t nv = (size_t)h->N * (size_t)h->ac_S;
     gu_ac_fill_one(h, h->d_ac_h, nv * 4, h0);
@@ -88,7 +88,7 @@ int gu_ac_fill(gu_engine *h, double h0, double v0)
     return GU_OK;
 }
 
-int gu_launch_ac(gu_engine *h, int64_t T, double alpha_actor, double alpha_critic, double gamma, uint32_t flags)
+static int gu_launch_ac(gu_engine *h, int64_t T, double alpha_actor, double alpha_critic, double gamma, uint32_t flags)
 {
     AcArgs a{};
     gu_tabular_args(h, a, T, alpha_actor, gamma, 0u, flags);
@@ -98,3 +98,75 @@ int gu_launch_ac(gu_engine *h, int64_t T, double alpha_actor, double alpha_criti
     const int rc = gu_tabular_launch(h, gu_ac_kernel<true>, gu_ac_kernel<false>, a);
     return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
 }
+
+void gu_ac_free(gu_engine *h)
+{
+    gu_release(h->d_ac_h, h->d_ac_v);
+    h->ac_S = 0;
+    gu_reinforce_free(h);
+}
+
+extern "C" {
+
+int gu_ac_init(gu_handle h, double h0, double v0)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(std::isfinite(h0) && std::isfinite(v0), GU_ERR_INVALID, "h0 and v0 must be finite");
+    gu_tabular_drop_carry(h);
+    if (!h->d_ac_h || h->ac_S != h->S) {
+        GU_HIP(hipStreamSynchronize(h->stream));
+        gu_ac_free(h);
+        const size_t states = (size_t)h->N * (size_t)h->S;
+        GU_TRY(gu_tabular_fits(h, states * 5 * sizeof(double), "actor-critic tables"));
+        GU_HIP(hipMalloc(&h->d_ac_h, states * 4 * sizeof(double)));
+        GU_HIP(hipMalloc(&h->d_ac_v, states * sizeof(double)));
+        h->ac_S = h->S;
+    }
+    GU_TRY(gu_ac_fill(h, h0, v0));  // every preference = h0, every value = v0 (async)
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_ac_run(gu_handle h, int64_t T, double alpha_actor, double alpha_critic, double gamma, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_AC(h);
+    GU_REQUIRE(std::isfinite(alpha_critic), GU_ERR_INVALID, "alpha_critic must be finite");
+    int rc = gu_tabular_check(h, "gu_ac_run", T, -1, 0u, alpha_actor, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    return gu_launch_ac(h, T, alpha_actor, alpha_critic, gamma, flags);
+}
+
+static int gu_ac_range(gu_engine *h, int64_t env0, int64_t n, const void *pref, const void *v)
+{
+    GU_NEED_GRID(h);
+    GU_NEED_AC(h);
+    GU_REQUIRE(pref != nullptr || v != nullptr, GU_ERR_INVALID, "pref and v are both NULL");
+    return gu_env_range(h, env0, n);
+}
+
+int gu_ac_get(gu_handle h, int64_t env0, int64_t n, double *pref, double *v)
+{
+    GU_ENTER(h);
+    GU_TRY(gu_ac_range(h, env0, n, pref, v));
+    GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, pref, h->d_ac_h, env0, n, (size_t)h->S * 4));
+    return gu_env_copy(h, hipMemcpyDeviceToHost, v, h->d_ac_v, env0, n, (size_t)h->S, false);
+}
+
+int gu_ac_set(gu_handle h, int64_t env0, int64_t n, const double *pref, const double *v)
+{
+    GU_ENTER(h);
+    GU_TRY(gu_ac_range(h, env0, n, pref, v));
+    const size_t S = (size_t)h->S, k = (size_t)n * S;
+    if (pref)
+        for (size_t i = 0; i < 4 * k; ++i) GU_REQUIRE(std::isfinite(pref[i]), GU_ERR_INVALID, "pref[%zu] is not finite", i);
+    if (v)
+        for (size_t i = 0; i < k; ++i) GU_REQUIRE(std::isfinite(v[i]), GU_ERR_INVALID, "v[%zu] is not finite", i);
+    gu_tabular_drop_carry(h);
+    GU_TRY(gu_env_copy(h, hipMemcpyHostToDevice, pref, h->d_ac_h, env0, n, S * 4));
+    return gu_env_copy(h, hipMemcpyHostToDevice, v, h->d_ac_v, env0, n, S, false);
+}
+
+}  // extern "C"

@@ -1,5 +1,7 @@
 // gu_api.hip -- C ABI of libgu.so (see include/gu.h for the contract and the reference
-// interfaces each entry point replaces).
+// interfaces each entry point replaces): errors, lifetime, grids, RNG, stepping, rollouts, trajectories and env state.  The other
+// modules hold their own entry points beside their kernels -- the batched learners too (gu_td.hip .. gu_fa.hip); what this file
+// knows of them is gu_learners_drop (gu_internal.hpp).
 #include "gu_internal.hpp"
 #include "gu_rng.hpp"
 
@@ -13,17 +15,6 @@
 #include <chrono>
 #include <mutex>
 #include <vector>
-
-static void gu_dyna_free(gu_engine *h);  // (tabular Dyna-Q, below)
-static void gu_nstep_free(gu_engine *h);  // (tabular n-step learners, below)
-static void gu_search_free(gu_engine *h); // (rollout search, below)
-static void gu_explore_free(gu_engine *h);  // (the counts of the count-based exploration, below)
-static void gu_mcts_free(gu_engine *h);  // (the node pools of the tree search, below)
-static void gu_is_free(gu_engine *h);  // (the cumulative weights and episode buffers of the off-policy Monte-Carlo learner, below)
-static void gu_lambda_free(gu_engine *h); // (tabular lambda learners, below)
-static void gu_ac_free(gu_engine *h);     // (tabular actor-critic, below)
-static void gu_reinforce_free(gu_engine *h);  // (tabular REINFORCE, below)
-static void gu_fa_free(gu_engine *h);     // (semi-gradient learners on features, below)
 
 // ---------------------------------------------------------------------------------- errors
 static thread_local std::string g_last_error;
@@ -69,14 +60,6 @@ int gu_ensure_scratch(gu_engine *h, size_t bytes)
     h->scratch_bytes = bytes;
     return GU_OK;
 }
-
-#define GU_ENTER(h)                                  \
-    do {                                             \
-        int _rc = gu_use_device(h);                  \
-        if (_rc != GU_OK) return _rc;                \
-    } while (0)
-
-#define GU_NEED_GRID(h) GU_REQUIRE((h)->has_grid, GU_ERR_STATE, "no grid set: call gu_set_grid first")
 
 static void gu_placement_release(gu_engine *h);  // (the registry of chosen trajectory buffers, below)
 
@@ -178,13 +161,10 @@ int gu_destroy(gu_handle h)
     gu_vi_free(h);
     gu_trail_free(h);
     gu_placement_release(h);
+    gu_learners_drop(h, 0);
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
     void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
-                    h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_q, h->d_td_next,
-                    h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen, h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt, h->d_lambda_w, h->d_ac_h, h->d_ac_v, h->d_rf_buf, h->d_rf_cnt,
-                    h->d_fa_w, h->d_fa_phi, h->d_fa_phi16, h->d_fa_next, h->d_search_score, h->d_search_steps, h->d_explore_n, h->d_explore_tab,
-                    h->d_mcts_pool, h->d_mcts_meta, h->d_mcts_nodes, h->d_mcts_steps, h->d_mcts_tab,
-                    h->d_is_c, h->d_is_R, h->d_is_buf, h->d_is_cnt};
+                    h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt};
     for (void *p : bufs)
         if (p) (void)hipFree(p);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
@@ -253,22 +233,7 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
     GU_HIP(hipStreamSynchronize(h->stream));
     h->entry_table_ok = false;  // (other cells, other flags)
     gu_tabular_drop_carry(h);
-    if (h->td_S && h->td_S != W * H) {  // Q tables of another state count belong to another grid: gu_td_init again
-        if (h->d_q) GU_HIP(hipFree(h->d_q));
-        if (h->d_td_next) GU_HIP(hipFree(h->d_td_next));
-        h->d_q = nullptr;
-        h->d_td_next = nullptr;
-        h->td_S = 0;
-        gu_nstep_free(h);
-        gu_lambda_free(h);
-        gu_search_free(h);
-        gu_mcts_free(h);  // (gu_mcts_init again; the U, B and I tables stay)
-    }
-    if (h->is_S && h->is_S != W * H) gu_is_free(h);  // ... and the cumulative weights: gu_is_init again
-    if (h->explore_S && h->explore_S != W * H) gu_explore_free(h);  // ... and the visit counts: gu_explore_init again (the U and B tables stay)
-    if (h->dyna_S && h->dyna_S != W * H) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
-    if (h->ac_S && h->ac_S != W * H) gu_ac_free(h);  // ... and actor-critic tables: gu_ac_init again
-    if (h->fa_S && h->fa_S != W * H) gu_fa_free(h);  // ... and features and weights: gu_fa_init again
+    gu_learners_drop(h, S);  // the learners' stores of another state count belong to another grid
     h->dyna_exact = false;  // a kept model may hold outcomes of the old cells: gu_dyna_run compares every observation from now on
     h->nib_valid = false;
     if (h->d_nib) GU_HIP(hipFree(h->d_nib));
@@ -1125,991 +1090,6 @@ int gu_read_stats(gu_handle h, int64_t *reward_sum, int32_t *episodes)
         for (size_t i = 0; i < n; ++i) reward_sum[i] = tmp[i];
     }
     if (episodes) GU_HIP(hipMemcpy(episodes, h->d_episodes_fin, n * 4, hipMemcpyDeviceToHost));
-    return GU_OK;
-}
-
-// ---------------------------------------------------------------------------------- tabular TD control, Dyna-Q, n-step and lambda learners
-// (gu_td.hip, gu_dyna.hip, gu_nstep.hip, gu_lambda.hip; their shared core is gu_tabular.hpp)
-
-// tables of `bytes` for the engine's envs: what is left has to hold the trajectory buffer and the scratch of other calls too, so
-// keep 1 GiB of headroom
-static int gu_tabular_fits(gu_engine *h, size_t bytes, const char *what)
-{
-    size_t free_b = 0, total_b = 0;
-    GU_HIP(hipMemGetInfo(&free_b, &total_b));
-    GU_REQUIRE(bytes + ((size_t)1 << 30) <= free_b, GU_ERR_NOMEM, "%s of %lld envs x %d states need %.2f GiB, %.2f GiB are free", what,
-               (long long)h->N, h->S, bytes / 1073741824.0, free_b / 1073741824.0);
-    return GU_OK;
-}
-
-// the checks of a learner launch of T real steps; P < 0: gu_td_run (one update per step), else gu_dyna_run (P + 1 per step)
-static int gu_tabular_check(gu_engine *h, const char *fn, int64_t T, int32_t P, uint32_t eps_q16, double alpha, double gamma, uint32_t flags)
-{
-    if (P < 0)
-        GU_REQUIRE(T >= 0 && T <= 100000000, GU_ERR_INVALID, "T %lld out of range (0 .. 1e8)", (long long)T);
-    else
-        GU_REQUIRE(T >= 0 && T <= 100000000 && T * (int64_t)(P + 1) <= 100000000, GU_ERR_INVALID,
-                   "T %lld x (P + 1) = %lld updates out of range (0 .. 1e8)", (long long)T, (long long)T * (P + 1));
-    GU_REQUIRE(eps_q16 <= 65536u, GU_ERR_INVALID, "eps_q16 %u above 65536", eps_q16);
-    GU_REQUIRE(std::isfinite(alpha) && std::isfinite(gamma), GU_ERR_INVALID, "alpha and gamma must be finite");
-    GU_REQUIRE((flags & ~(GU_F_TRAJECTORY | GU_F_STATS)) == 0, GU_ERR_INVALID, "%s accepts GU_F_TRAJECTORY and GU_F_STATS only (flags 0x%x)", fn, flags);
-    if (flags & GU_F_TRAJECTORY)
-        GU_REQUIRE(h->d_traj && T <= h->traj_T, GU_ERR_STATE, "trajectory buffer holds %lld rows, need %lld: call gu_reserve_trajectory",
-                   (long long)h->traj_T, (long long)T);
-    GU_REQUIRE(!h->trail_cap || (flags & GU_F_TRAJECTORY), GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): %s must write rows (GU_F_TRAJECTORY) to feed it", fn);
-    return GU_OK;
-}
-
-static int gu_env_range(gu_engine *h, int64_t env0, int64_t n)
-{
-    GU_REQUIRE(env0 >= 0 && n >= 0 && env0 + n <= h->N, GU_ERR_INVALID, "envs [%lld, %lld) outside 0 .. %lld", (long long)env0,
-               (long long)(env0 + n), (long long)h->N);
-    return GU_OK;
-}
-
-int gu_td_init(gu_handle h, double q0)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(std::isfinite(q0), GU_ERR_INVALID, "q0 must be finite");
-    gu_tabular_drop_carry(h);
-    const size_t bytes = (size_t)h->N * (size_t)h->S * 4 * sizeof(double);
-    if (!h->d_q || h->td_S != h->S) {
-        GU_HIP(hipStreamSynchronize(h->stream));
-        if (h->d_q) GU_HIP(hipFree(h->d_q));
-        if (h->d_td_next) GU_HIP(hipFree(h->d_td_next));
-        h->d_q = nullptr;
-        h->d_td_next = nullptr;
-        h->td_S = 0;
-        int rc = gu_tabular_fits(h, bytes, "Q tables");
-        if (rc != GU_OK) return rc;
-        GU_HIP(hipMalloc(&h->d_q, bytes));
-        GU_HIP(hipMalloc(&h->d_td_next, (size_t)h->N));
-        h->td_S = h->S;
-    }
-    GU_HIP(hipMemsetAsync(h->d_td_next, 0xFF, (size_t)h->N, h->stream));
-    int rc = gu_td_fill(h, q0);
-    if (rc != GU_OK) return rc;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    return GU_OK;
-}
-
-int gu_td_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Q-learning, 1 = SARSA", method);
-    int rc = gu_tabular_check(h, "gu_td_run", T, -1, eps_q16, alpha, gamma, flags);
-    if (rc != GU_OK || T == 0) return rc;
-    return gu_launch_td(h, T, method, alpha, gamma, eps_q16, flags);
-}
-
-static int gu_td_range(gu_engine *h, int64_t env0, int64_t n, const void *q)
-{
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(q != nullptr, GU_ERR_INVALID, "q is NULL");
-    return gu_env_range(h, env0, n);
-}
-
-int gu_td_get_q(gu_handle h, int64_t env0, int64_t n, double *q)
-{
-    GU_ENTER(h);
-    int rc = gu_td_range(h, env0, n, q);
-    if (rc != GU_OK) return rc;
-    const size_t row = (size_t)h->S * 4;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n) GU_HIP(hipMemcpy(q, h->d_q + (size_t)env0 * row, (size_t)n * row * sizeof(double), hipMemcpyDeviceToHost));
-    return GU_OK;
-}
-
-int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q)
-{
-    GU_ENTER(h);
-    int rc = gu_td_range(h, env0, n, q);
-    if (rc != GU_OK) return rc;
-    gu_tabular_drop_carry(h);
-    const size_t row = (size_t)h->S * 4;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n) GU_HIP(hipMemcpy(h->d_q + (size_t)env0 * row, q, (size_t)n * row * sizeof(double), hipMemcpyHostToDevice));
-    return GU_OK;
-}
-
-static void gu_dyna_free(gu_engine *h)
-{
-    if (h->d_dyna_model) (void)hipFree(h->d_dyna_model);
-    if (h->d_dyna_list) (void)hipFree(h->d_dyna_list);
-    if (h->d_dyna_count) (void)hipFree(h->d_dyna_count);
-    if (h->d_dyna_seen) (void)hipFree(h->d_dyna_seen);
-    h->d_dyna_model = nullptr;
-    h->d_dyna_list = nullptr;
-    h->d_dyna_count = nullptr;
-    h->d_dyna_seen = nullptr;
-    h->dyna_S = 0;
-    h->dyna_exact = false;
-}
-
-int gu_dyna_init(gu_handle h)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    gu_tabular_drop_carry(h);
-    const size_t pairs = (size_t)h->N * (size_t)h->S * 4;
-    if (!h->d_dyna_model || h->dyna_S != h->S) {
-        GU_HIP(hipStreamSynchronize(h->stream));
-        gu_dyna_free(h);
-        const size_t bytes = pairs * (sizeof(uint64_t) + sizeof(int32_t)) + (size_t)h->N * (sizeof(int32_t) + (size_t)h->S);
-        int rc = gu_tabular_fits(h, bytes, "Dyna-Q models");
-        if (rc != GU_OK) return rc;
-        GU_HIP(hipMalloc(&h->d_dyna_model, pairs * sizeof(uint64_t)));
-        GU_HIP(hipMalloc(&h->d_dyna_list, pairs * sizeof(int32_t)));
-        GU_HIP(hipMalloc(&h->d_dyna_count, (size_t)h->N * sizeof(int32_t)));
-        GU_HIP(hipMalloc(&h->d_dyna_seen, (size_t)h->N * (size_t)h->S));
-        h->dyna_S = h->S;
-    }
-    h->dyna_exact = true;
-    GU_HIP(hipMemsetAsync(h->d_dyna_model, 0xFF, pairs * sizeof(uint64_t), h->stream));
-    GU_HIP(hipMemsetAsync(h->d_dyna_list, 0xFF, pairs * sizeof(int32_t), h->stream));
-    GU_HIP(hipMemsetAsync(h->d_dyna_count, 0, (size_t)h->N * sizeof(int32_t), h->stream));
-    GU_HIP(hipMemsetAsync(h->d_dyna_seen, 0, (size_t)h->N * (size_t)h->S, h->stream));
-    GU_HIP(hipStreamSynchronize(h->stream));
-    return GU_OK;
-}
-
-int gu_dyna_run(gu_handle h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(h->d_dyna_model && h->dyna_S == h->S, GU_ERR_STATE, "no Dyna-Q model: call gu_dyna_init first");
-    GU_REQUIRE(P >= 0 && P <= 256, GU_ERR_INVALID, "planning steps %d out of range (0 .. 256)", P);
-    int rc = gu_tabular_check(h, "gu_dyna_run", T, P, eps_q16, alpha, gamma, flags);
-    if (rc != GU_OK || T == 0) return rc;
-    return gu_launch_dyna(h, T, P, alpha, gamma, eps_q16, flags);
-}
-
-int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32_t *reward, int32_t *done, int32_t *list, int32_t *count)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_dyna_model && h->dyna_S == h->S, GU_ERR_STATE, "no Dyna-Q model: call gu_dyna_init first");
-    int rc = gu_env_range(h, env0, n);
-    if (rc != GU_OK) return rc;
-    const size_t pairs = (size_t)h->S * 4, k = (size_t)n * pairs;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (!n) return GU_OK;
-    if (next || reward || done) {
-        std::vector<uint64_t> words(k);
-        GU_HIP(hipMemcpy(words.data(), h->d_dyna_model + (size_t)env0 * pairs, k * sizeof(uint64_t), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < k; ++i) {
-            const uint64_t w = words[i];
-            const bool seen = w != ~0ull;
-            const uint32_t hi = (uint32_t)(w >> 32);
-            if (next) next[i] = seen ? (int32_t)(hi & 0x7FFFFFFFu) : -1;
-            if (reward) reward[i] = seen ? (int32_t)(uint32_t)w : 0;
-            if (done) done[i] = seen ? (int32_t)(hi >> 31) : 0;
-        }
-    }
-    if (list) GU_HIP(hipMemcpy(list, h->d_dyna_list + (size_t)env0 * pairs, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (count) GU_HIP(hipMemcpy(count, h->d_dyna_count + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return GU_OK;
-}
-
-static void gu_search_free(gu_engine *h)
-{
-    if (h->d_search_score) (void)hipFree(h->d_search_score);
-    if (h->d_search_steps) (void)hipFree(h->d_search_steps);
-    h->d_search_score = nullptr;
-    h->d_search_steps = nullptr;
-}
-
-int gu_search_run(gu_handle h, int64_t T, int32_t M, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
-                  uint32_t flags)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(M >= 0 && M <= GU_SEARCH_MAX_M, GU_ERR_INVALID, "simulations %d out of range (0 .. %d)", M, GU_SEARCH_MAX_M);
-    GU_REQUIRE(D >= 0 && D <= GU_SEARCH_MAX_D, GU_ERR_INVALID, "depth %d out of range (0 .. %d)", D, GU_SEARCH_MAX_D);
-    GU_REQUIRE(eps_sim_q16 <= 65536u, GU_ERR_INVALID, "eps_sim_q16 %u above 65536", eps_sim_q16);
-    int rc = gu_tabular_check(h, "gu_search_run", T, -1, eps_q16, alpha, gamma, flags);
-    if (rc != GU_OK) return rc;
-    const int64_t moves = 1 + 4 * (int64_t)M * D;  // per real step, at most
-    GU_REQUIRE(T * moves <= 100000000, GU_ERR_INVALID, "T %lld x (1 + 4 M D) = %lld moves out of range (0 .. 1e8)", (long long)T,
-               (long long)(T * moves));
-    if (T == 0) return GU_OK;
-    if (!h->d_search_score) {
-        GU_HIP(hipStreamSynchronize(h->stream));
-        rc = gu_tabular_fits(h, (size_t)h->N * (4 * sizeof(double) + sizeof(int64_t)), "search scores");
-        if (rc != GU_OK) return rc;
-        GU_HIP(hipMalloc(&h->d_search_score, (size_t)h->N * 4 * sizeof(double)));
-        GU_HIP(hipMalloc(&h->d_search_steps, (size_t)h->N * sizeof(int64_t)));
-        GU_HIP(hipMemsetAsync(h->d_search_score, 0, (size_t)h->N * 4 * sizeof(double), h->stream));
-        GU_HIP(hipMemsetAsync(h->d_search_steps, 0, (size_t)h->N * sizeof(int64_t), h->stream));
-    }
-    return gu_launch_search(h, T, M, D, alpha, gamma, eps_q16, eps_sim_q16, flags);
-}
-
-int gu_search_get(gu_handle h, int64_t env0, int64_t n, double *score, int64_t *sim_steps)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    int rc = gu_env_range(h, env0, n);
-    if (rc != GU_OK) return rc;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (!n) return GU_OK;
-    if (!h->d_search_score) {  // (nothing searched yet: what the storage holds right after its allocation)
-        if (score) std::fill(score, score + (size_t)n * 4, 0.0);
-        if (sim_steps) std::fill(sim_steps, sim_steps + (size_t)n, (int64_t)0);
-        return GU_OK;
-    }
-    if (score) GU_HIP(hipMemcpy(score, h->d_search_score + (size_t)env0 * 4, (size_t)n * 4 * sizeof(double), hipMemcpyDeviceToHost));
-    if (sim_steps) GU_HIP(hipMemcpy(sim_steps, h->d_search_steps + env0, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return GU_OK;
-}
-
-static void gu_explore_free(gu_engine *h)
-{
-    if (h->d_explore_n) (void)hipFree(h->d_explore_n);
-    h->d_explore_n = nullptr;
-    h->explore_S = 0;
-}
-
-int gu_explore_init(gu_handle h)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    const size_t bytes = (size_t)h->N * (size_t)h->S * 4 * sizeof(uint32_t);
-    if (!h->d_explore_n || h->explore_S != h->S) {
-        GU_HIP(hipStreamSynchronize(h->stream));
-        gu_explore_free(h);
-        int rc = gu_tabular_fits(h, bytes, "visit counts");
-        if (rc != GU_OK) return rc;
-        GU_HIP(hipMalloc(&h->d_explore_n, bytes));
-        h->explore_S = h->S;
-    }
-    GU_HIP(hipMemsetAsync(h->d_explore_n, 0, bytes, h->stream));
-    GU_HIP(hipStreamSynchronize(h->stream));
-    return GU_OK;
-}
-
-int gu_explore_set_tables(gu_handle h, int32_t C, const double *U, const double *B)
-{
-    GU_ENTER(h);
-    GU_REQUIRE(C >= 2 && C <= GU_EXPLORE_MAX_C, GU_ERR_INVALID, "table size %d out of range (2 .. %d)", C, GU_EXPLORE_MAX_C);
-    GU_REQUIRE(U != nullptr && B != nullptr, GU_ERR_INVALID, "U or B is NULL");
-    for (int32_t k = 0; k < C; ++k)
-        GU_REQUIRE(std::isfinite(U[k]) && U[k] >= 0.0 && std::isfinite(B[k]) && B[k] >= 0.0, GU_ERR_INVALID,
-                   "entry %d (U %g, B %g): every entry must be finite and not negative", k, U[k], B[k]);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (h->explore_C != C) {
-        if (h->d_explore_tab) GU_HIP(hipFree(h->d_explore_tab));
-        h->d_explore_tab = nullptr;
-        h->explore_C = 0;
-        GU_HIP(hipMalloc(&h->d_explore_tab, (size_t)C * 2 * sizeof(double)));
-        h->explore_C = C;
-    }
-    GU_HIP(hipMemcpy(h->d_explore_tab, U, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
-    GU_HIP(hipMemcpy(h->d_explore_tab + C, B, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
-    return GU_OK;
-}
-
-int gu_explore_run(gu_handle h, int64_t T, int32_t mode, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(h->d_explore_n && h->explore_S == h->S, GU_ERR_STATE, "no visit counts: call gu_explore_init first");
-    GU_REQUIRE(h->d_explore_tab && h->explore_C >= 2, GU_ERR_STATE, "no exploration tables: call gu_explore_set_tables first");
-    GU_REQUIRE(mode == 0 || mode == 1, GU_ERR_INVALID, "mode %d: 0 = UCB, 1 = Thompson", mode);
-    int rc = gu_tabular_check(h, "gu_explore_run", T, -1, eps_q16, alpha, gamma, flags);
-    if (rc != GU_OK || T == 0) return rc;
-    return gu_launch_explore(h, T, mode, alpha, gamma, eps_q16, flags);
-}
-
-static int gu_explore_range(gu_engine *h, int64_t env0, int64_t n, const void *counts)
-{
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_explore_n && h->explore_S == h->S, GU_ERR_STATE, "no visit counts: call gu_explore_init first");
-    GU_REQUIRE(counts != nullptr, GU_ERR_INVALID, "counts is NULL");
-    return gu_env_range(h, env0, n);
-}
-
-int gu_explore_get_counts(gu_handle h, int64_t env0, int64_t n, uint32_t *counts)
-{
-    GU_ENTER(h);
-    int rc = gu_explore_range(h, env0, n, counts);
-    if (rc != GU_OK) return rc;
-    const size_t row = (size_t)h->S * 4;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n) GU_HIP(hipMemcpy(counts, h->d_explore_n + (size_t)env0 * row, (size_t)n * row * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    return GU_OK;
-}
-
-int gu_explore_set_counts(gu_handle h, int64_t env0, int64_t n, const uint32_t *counts)
-{
-    GU_ENTER(h);
-    int rc = gu_explore_range(h, env0, n, counts);
-    if (rc != GU_OK) return rc;
-    const size_t row = (size_t)h->S * 4, k = (size_t)n * row;
-    for (size_t i = 0; i < k; ++i)
-        GU_REQUIRE(counts[i] <= GU_EXPLORE_COUNT_MAX, GU_ERR_INVALID, "count %u of env %lld above the cap 0x%X", counts[i],
-                   (long long)(env0 + (int64_t)(i / row)), GU_EXPLORE_COUNT_MAX);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n) GU_HIP(hipMemcpy(h->d_explore_n + (size_t)env0 * row, counts, k * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return GU_OK;
-}
-
-static void gu_mcts_free(gu_engine *h)
-{
-    for (void *p : {(void *)h->d_mcts_pool, (void *)h->d_mcts_meta, (void *)h->d_mcts_nodes, (void *)h->d_mcts_steps})
-        if (p) (void)hipFree(p);
-    h->d_mcts_pool = nullptr;
-    h->d_mcts_meta = nullptr;
-    h->d_mcts_nodes = nullptr;
-    h->d_mcts_steps = nullptr;
-    h->mcts_P = 0;
-}
-
-int gu_mcts_init(gu_handle h, int32_t max_sims)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(max_sims >= 1 && max_sims <= GU_MCTS_MAX_SIMS, GU_ERR_INVALID, "max_sims %d out of range (1 .. %d)", max_sims, GU_MCTS_MAX_SIMS);
-    const int32_t P = max_sims + 1;
-    const size_t nodes = (size_t)h->N * (size_t)P;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (!h->d_mcts_pool || h->mcts_P != P) {
-        gu_mcts_free(h);
-        int rc = gu_tabular_fits(h, nodes * 72 + (size_t)h->N * 12, "tree-search node pools");
-        if (rc != GU_OK) return rc;
-        GU_HIP(hipMalloc(&h->d_mcts_pool, nodes * 64));
-        GU_HIP(hipMalloc(&h->d_mcts_meta, nodes * 8));
-        GU_HIP(hipMalloc(&h->d_mcts_nodes, (size_t)h->N * sizeof(int32_t)));
-        GU_HIP(hipMalloc(&h->d_mcts_steps, (size_t)h->N * sizeof(int64_t)));
-        h->mcts_P = P;
-    }
-    GU_HIP(hipMemsetAsync(h->d_mcts_pool, 0, nodes * 64, h->stream));  // (root rows of zeros until an iteration has been searched)
-    GU_HIP(hipMemsetAsync(h->d_mcts_meta, 0xFF, nodes * 8, h->stream));
-    GU_HIP(hipMemsetAsync(h->d_mcts_nodes, 0, (size_t)h->N * sizeof(int32_t), h->stream));
-    GU_HIP(hipMemsetAsync(h->d_mcts_steps, 0, (size_t)h->N * sizeof(int64_t), h->stream));
-    GU_HIP(hipStreamSynchronize(h->stream));
-    return GU_OK;
-}
-
-int gu_mcts_set_tables(gu_handle h, int32_t C, const double *U, const double *B, const double *I)
-{
-    GU_ENTER(h);
-    GU_REQUIRE(C >= 2 && C <= GU_EXPLORE_MAX_C, GU_ERR_INVALID, "table size %d out of range (2 .. %d)", C, GU_EXPLORE_MAX_C);
-    GU_REQUIRE(U != nullptr && B != nullptr && I != nullptr, GU_ERR_INVALID, "U, B or I is NULL");
-    for (int32_t k = 0; k < C; ++k)
-        GU_REQUIRE(std::isfinite(U[k]) && U[k] >= 0.0 && std::isfinite(B[k]) && B[k] >= 0.0 && std::isfinite(I[k]) && I[k] >= 0.0, GU_ERR_INVALID,
-                   "entry %d (U %g, B %g, I %g): every entry must be finite and not negative", k, U[k], B[k], I[k]);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (h->mcts_C != C) {
-        if (h->d_mcts_tab) GU_HIP(hipFree(h->d_mcts_tab));
-        h->d_mcts_tab = nullptr;
-        h->mcts_C = 0;
-        const size_t bytes = ((size_t)C * 3 * sizeof(double) + 15) & ~(size_t)15;  // (whole 16-byte pieces: the LDS kernels stage it so)
-        GU_HIP(hipMalloc(&h->d_mcts_tab, bytes));
-        GU_HIP(hipMemset(h->d_mcts_tab, 0, bytes));
-        h->mcts_C = C;
-    }
-    GU_HIP(hipMemcpy(h->d_mcts_tab, U, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
-    GU_HIP(hipMemcpy(h->d_mcts_tab + C, B, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
-    GU_HIP(hipMemcpy(h->d_mcts_tab + 2 * (size_t)C, I, (size_t)C * sizeof(double), hipMemcpyHostToDevice));
-    return GU_OK;
-}
-
-int gu_mcts_run(gu_handle h, int64_t T, int32_t M, int32_t H, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
-                uint32_t flags)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(h->d_mcts_pool && h->mcts_P >= 2, GU_ERR_STATE, "no node pools: call gu_mcts_init first");
-    GU_REQUIRE(M >= 0 && M <= h->mcts_P - 1, GU_ERR_INVALID, "simulations %d out of range (0 .. %d, gu_mcts_init's max_sims)", M, h->mcts_P - 1);
-    GU_REQUIRE(H >= 1 && H <= GU_MCTS_MAX_DEPTH, GU_ERR_INVALID, "tree depth %d out of range (1 .. %d)", H, GU_MCTS_MAX_DEPTH);
-    GU_REQUIRE(D >= 0 && D <= GU_SEARCH_MAX_D, GU_ERR_INVALID, "depth %d out of range (0 .. %d)", D, GU_SEARCH_MAX_D);
-    GU_REQUIRE(eps_sim_q16 <= 65536u, GU_ERR_INVALID, "eps_sim_q16 %u above 65536", eps_sim_q16);
-    GU_REQUIRE(M == 0 || (h->d_mcts_tab && h->mcts_C >= 2), GU_ERR_STATE, "no tree-search tables: call gu_mcts_set_tables first");
-    int rc = gu_tabular_check(h, "gu_mcts_run", T, -1, eps_q16, alpha, gamma, flags);
-    if (rc != GU_OK) return rc;
-    const int64_t moves = 1 + (int64_t)M * (H + D);  // per real step, at most
-    GU_REQUIRE(T * moves <= 100000000, GU_ERR_INVALID, "T %lld x (1 + M (H + D)) = %lld moves out of range (0 .. 1e8)", (long long)T,
-               (long long)(T * moves));
-    if (T == 0) return GU_OK;
-    return gu_launch_mcts(h, T, M, H, D, alpha, gamma, eps_q16, eps_sim_q16, flags);
-}
-
-static int gu_mcts_range(gu_engine *h, int64_t env0, int64_t n)
-{
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(h->d_mcts_pool && h->mcts_P >= 2, GU_ERR_STATE, "no node pools: call gu_mcts_init first");
-    return gu_env_range(h, env0, n);
-}
-
-int gu_mcts_get(gu_handle h, int64_t env0, int64_t n, double *w, uint32_t *visits, int32_t *nodes, int64_t *sim_steps)
-{
-    GU_ENTER(h);
-    int rc = gu_mcts_range(h, env0, n);
-    if (rc != GU_OK) return rc;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (!n) return GU_OK;
-    // the root is node 0 of each env's pool: its w row at byte 0, its visits row at byte 32
-    const size_t pitch = (size_t)h->mcts_P * 64;
-    const uint8_t *root = h->d_mcts_pool + (size_t)env0 * pitch;
-    if (w) GU_HIP(hipMemcpy2D(w, 32, root, pitch, 32, (size_t)n, hipMemcpyDeviceToHost));
-    if (visits) GU_HIP(hipMemcpy2D(visits, 16, root + 32, pitch, 16, (size_t)n, hipMemcpyDeviceToHost));
-    if (nodes) GU_HIP(hipMemcpy(nodes, h->d_mcts_nodes + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (sim_steps) GU_HIP(hipMemcpy(sim_steps, h->d_mcts_steps + env0, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
-    return GU_OK;
-}
-
-int gu_mcts_get_tree(gu_handle h, int64_t env0, int64_t n, int32_t *state, int32_t *parent, int32_t *child, uint32_t *visits, double *w,
-                     int32_t *count)
-{
-    GU_ENTER(h);
-    int rc = gu_mcts_range(h, env0, n);
-    if (rc != GU_OK) return rc;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (!n) return GU_OK;
-    const size_t P = (size_t)h->mcts_P, k = (size_t)n * P;
-    std::vector<uint8_t> pool(k * 64);
-    std::vector<int32_t> meta(k * 2), cnt((size_t)n);
-    GU_HIP(hipMemcpy(pool.data(), h->d_mcts_pool + (size_t)env0 * P * 64, k * 64, hipMemcpyDeviceToHost));
-    GU_HIP(hipMemcpy(meta.data(), h->d_mcts_meta + (size_t)env0 * P * 2, k * 8, hipMemcpyDeviceToHost));
-    GU_HIP(hipMemcpy(cnt.data(), h->d_mcts_nodes + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (size_t e = 0; e < (size_t)n; ++e) {
-        if (count) count[e] = cnt[e];
-        for (size_t v = 0; v < P; ++v) {
-            const size_t i = e * P + v;
-            const bool live = (int64_t)v < (int64_t)cnt[e];
-            const uint8_t *node = pool.data() + i * 64;
-            if (state) state[i] = live ? meta[i * 2] : -1;
-            if (parent) parent[i] = live ? meta[i * 2 + 1] : -1;
-            for (size_t b = 0; b < 4; ++b) {
-                if (w) w[i * 4 + b] = live ? reinterpret_cast<const double *>(node)[b] : 0.0;
-                if (visits) visits[i * 4 + b] = live ? reinterpret_cast<const uint32_t *>(node + 32)[b] : 0u;
-                if (child) child[i * 4 + b] = live ? reinterpret_cast<const int32_t *>(node + 48)[b] : -1;
-            }
-        }
-    }
-    return GU_OK;
-}
-
-static void gu_nstep_free(gu_engine *h)
-{
-    if (h->d_nstep_sa) (void)hipFree(h->d_nstep_sa);
-    if (h->d_nstep_r) (void)hipFree(h->d_nstep_r);
-    if (h->d_nstep_cnt) (void)hipFree(h->d_nstep_cnt);
-    h->d_nstep_sa = nullptr;
-    h->d_nstep_r = nullptr;
-    h->d_nstep_cnt = nullptr;
-    h->nstep_key = 0;
-}
-
-int gu_nstep_run(gu_handle h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = n-step Q-learning, 1 = n-step SARSA", method);
-    GU_REQUIRE(n >= 1 && n <= GU_NSTEP_MAX, GU_ERR_INVALID, "n %d out of range (1 .. %d)", n, GU_NSTEP_MAX);
-    int rc = gu_tabular_check(h, "gu_nstep_run", T, -1, eps_q16, alpha, gamma, flags);
-    if (rc != GU_OK || T == 0) return rc;
-    if (!h->d_nstep_sa) {
-        const size_t slots = (size_t)h->N * GU_NSTEP_MAX;
-        GU_HIP(hipStreamSynchronize(h->stream));
-        rc = gu_tabular_fits(h, 2 * slots * sizeof(int32_t) + (size_t)h->N * sizeof(int32_t), "n-step windows");
-        if (rc != GU_OK) return rc;
-        GU_HIP(hipMalloc(&h->d_nstep_sa, slots * sizeof(int32_t)));
-        GU_HIP(hipMalloc(&h->d_nstep_r, slots * sizeof(int32_t)));
-        GU_HIP(hipMalloc(&h->d_nstep_cnt, (size_t)h->N * sizeof(int32_t)));
-        h->nstep_key = 0;
-    }
-    return gu_launch_nstep(h, T, method, n, alpha, gamma, eps_q16, flags);
-}
-
-int gu_nstep_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    int rc = gu_env_range(h, env0, n);
-    if (rc != GU_OK) return rc;
-    const size_t k = (size_t)n * GU_NSTEP_MAX;
-    std::vector<int32_t> c(n), w_sa(k), w_r(k);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n && h->nstep_key) {  // (a dropped window reads as empty, whatever the device copy still holds)
-        GU_HIP(hipMemcpy(c.data(), h->d_nstep_cnt + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        GU_HIP(hipMemcpy(w_sa.data(), h->d_nstep_sa + (size_t)env0 * GU_NSTEP_MAX, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-        GU_HIP(hipMemcpy(w_r.data(), h->d_nstep_r + (size_t)env0 * GU_NSTEP_MAX, k * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    for (int64_t e = 0; e < n; ++e)
-        for (int32_t j = 0; j < GU_NSTEP_MAX; ++j) {
-            const size_t i = (size_t)e * GU_NSTEP_MAX + j;
-            if (sa) sa[i] = j < c[e] ? w_sa[i] : -1;
-            if (reward) reward[i] = j < c[e] ? w_r[i] : 0;
-        }
-    if (count)
-        for (int64_t e = 0; e < n; ++e) count[e] = c[e];
-    return GU_OK;
-}
-
-static void gu_lambda_free(gu_engine *h)
-{
-    if (h->d_lambda_w) (void)hipFree(h->d_lambda_w);
-    h->d_lambda_w = nullptr;
-    h->lambda_key = 0;
-}
-
-int gu_lambda_run(gu_handle h, int64_t T, int32_t method, int32_t K, double alpha, double gamma, double lambda, uint32_t eps_q16,
-                  uint32_t flags)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Watkins's Q(lambda), 1 = SARSA(lambda)", method);
-    GU_REQUIRE(K >= 1 && K <= GU_LAMBDA_MAX, GU_ERR_INVALID, "K %d out of range (1 .. %d)", K, GU_LAMBDA_MAX);
-    GU_REQUIRE(lambda >= 0.0 && lambda <= 1.0, GU_ERR_INVALID, "lambda %g outside [0, 1]", lambda);
-    int rc = gu_tabular_check(h, "gu_lambda_run", T, -1, eps_q16, alpha, gamma, flags);
-    if (rc != GU_OK || T == 0) return rc;
-    if (!h->d_lambda_w) {
-        const size_t slots = (size_t)h->N * GU_LAMBDA_MAX;
-        GU_HIP(hipStreamSynchronize(h->stream));
-        rc = gu_tabular_fits(h, slots * sizeof(int32_t), "trace windows");
-        if (rc != GU_OK) return rc;
-        GU_HIP(hipMalloc(&h->d_lambda_w, slots * sizeof(int32_t)));
-        h->lambda_key = 0;
-    }
-    return gu_launch_lambda(h, T, method, K, alpha, gamma, lambda, eps_q16, flags);
-}
-
-int gu_lambda_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    int rc = gu_env_range(h, env0, n);
-    if (rc != GU_OK) return rc;
-    GU_REQUIRE(sa != nullptr || n == 0, GU_ERR_INVALID, "sa is NULL");
-    const int32_t K = h->lambda_key ? (h->lambda_key - 1) / 2 : 0;  // (gu_lambda_key; 0: the window was dropped)
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n && K)
-        GU_HIP(hipMemcpy(sa, h->d_lambda_w + (size_t)env0 * GU_LAMBDA_MAX, (size_t)n * GU_LAMBDA_MAX * sizeof(int32_t), hipMemcpyDeviceToHost));
-    for (int64_t e = 0; e < n; ++e)  // (a dropped window reads as empty, whatever the device copy still holds; ages >= K are not written)
-        for (int32_t j = K; j < GU_LAMBDA_MAX; ++j) sa[(size_t)e * GU_LAMBDA_MAX + j] = -1;
-    return GU_OK;
-}
-
-static void gu_ac_free(gu_engine *h)
-{
-    if (h->d_ac_h) (void)hipFree(h->d_ac_h);
-    if (h->d_ac_v) (void)hipFree(h->d_ac_v);
-    h->d_ac_h = nullptr;
-    h->d_ac_v = nullptr;
-    h->ac_S = 0;
-    gu_reinforce_free(h);
-}
-
-int gu_ac_init(gu_handle h, double h0, double v0)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(std::isfinite(h0) && std::isfinite(v0), GU_ERR_INVALID, "h0 and v0 must be finite");
-    gu_tabular_drop_carry(h);
-    if (!h->d_ac_h || h->ac_S != h->S) {
-        GU_HIP(hipStreamSynchronize(h->stream));
-        gu_ac_free(h);
-        const size_t states = (size_t)h->N * (size_t)h->S;
-        int rc = gu_tabular_fits(h, states * 5 * sizeof(double), "actor-critic tables");
-        if (rc != GU_OK) return rc;
-        GU_HIP(hipMalloc(&h->d_ac_h, states * 4 * sizeof(double)));
-        GU_HIP(hipMalloc(&h->d_ac_v, states * sizeof(double)));
-        h->ac_S = h->S;
-    }
-    int rc = gu_ac_fill(h, h0, v0);
-    if (rc != GU_OK) return rc;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    return GU_OK;
-}
-
-int gu_ac_run(gu_handle h, int64_t T, double alpha_actor, double alpha_critic, double gamma, uint32_t flags)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_ac_h && h->ac_S == h->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first");
-    GU_REQUIRE(std::isfinite(alpha_critic), GU_ERR_INVALID, "alpha_critic must be finite");
-    int rc = gu_tabular_check(h, "gu_ac_run", T, -1, 0u, alpha_actor, gamma, flags);
-    if (rc != GU_OK || T == 0) return rc;
-    return gu_launch_ac(h, T, alpha_actor, alpha_critic, gamma, flags);
-}
-
-static int gu_ac_range(gu_engine *h, int64_t env0, int64_t n, const void *pref, const void *v)
-{
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_ac_h && h->ac_S == h->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first");
-    GU_REQUIRE(pref != nullptr || v != nullptr, GU_ERR_INVALID, "pref and v are both NULL");
-    return gu_env_range(h, env0, n);
-}
-
-int gu_ac_get(gu_handle h, int64_t env0, int64_t n, double *pref, double *v)
-{
-    GU_ENTER(h);
-    int rc = gu_ac_range(h, env0, n, pref, v);
-    if (rc != GU_OK) return rc;
-    const size_t S = (size_t)h->S;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n && pref) GU_HIP(hipMemcpy(pref, h->d_ac_h + (size_t)env0 * S * 4, (size_t)n * S * 4 * sizeof(double), hipMemcpyDeviceToHost));
-    if (n && v) GU_HIP(hipMemcpy(v, h->d_ac_v + (size_t)env0 * S, (size_t)n * S * sizeof(double), hipMemcpyDeviceToHost));
-    return GU_OK;
-}
-
-int gu_ac_set(gu_handle h, int64_t env0, int64_t n, const double *pref, const double *v)
-{
-    GU_ENTER(h);
-    int rc = gu_ac_range(h, env0, n, pref, v);
-    if (rc != GU_OK) return rc;
-    const size_t S = (size_t)h->S, k = (size_t)n * S;
-    if (pref)
-        for (size_t i = 0; i < 4 * k; ++i) GU_REQUIRE(std::isfinite(pref[i]), GU_ERR_INVALID, "pref[%zu] is not finite", i);
-    if (v)
-        for (size_t i = 0; i < k; ++i) GU_REQUIRE(std::isfinite(v[i]), GU_ERR_INVALID, "v[%zu] is not finite", i);
-    gu_tabular_drop_carry(h);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n && pref) GU_HIP(hipMemcpy(h->d_ac_h + (size_t)env0 * S * 4, pref, 4 * k * sizeof(double), hipMemcpyHostToDevice));
-    if (n && v) GU_HIP(hipMemcpy(h->d_ac_v + (size_t)env0 * S, v, k * sizeof(double), hipMemcpyHostToDevice));
-    return GU_OK;
-}
-
-static void gu_reinforce_free(gu_engine *h)
-{
-    if (h->d_rf_buf) (void)hipFree(h->d_rf_buf);
-    if (h->d_rf_cnt) (void)hipFree(h->d_rf_cnt);
-    h->d_rf_buf = nullptr;
-    h->d_rf_cnt = nullptr;
-    h->rf_cap = 0;
-    h->rf_key = 0;
-}
-
-int gu_reinforce_run(gu_handle h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_ac_h && h->ac_S == h->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first");
-    GU_REQUIRE(L >= 1 && L <= GU_REINFORCE_MAX, GU_ERR_INVALID, "L %d out of range (1 .. %d)", L, GU_REINFORCE_MAX);
-    GU_REQUIRE(std::isfinite(alpha_baseline), GU_ERR_INVALID, "alpha_baseline must be finite");
-    int rc = gu_tabular_check(h, "gu_reinforce_run", T, -1, 0u, alpha_actor, gamma, flags);
-    if (rc != GU_OK || T == 0) return rc;
-    if (h->rf_cap < L) {  // (a call with another L drops the buffer anyway: nothing to keep)
-        const size_t slots = (size_t)h->N * (size_t)L;
-        GU_HIP(hipStreamSynchronize(h->stream));
-        rc = gu_tabular_fits(h, slots * 2 * sizeof(int32_t) + (size_t)h->N * sizeof(int32_t), "episode buffers");
-        if (rc != GU_OK) return rc;
-        gu_reinforce_free(h);
-        GU_HIP(hipMalloc(&h->d_rf_buf, slots * 2 * sizeof(int32_t)));
-        GU_HIP(hipMalloc(&h->d_rf_cnt, (size_t)h->N * sizeof(int32_t)));
-        h->rf_cap = L;
-    }
-    return gu_launch_reinforce(h, T, L, alpha_actor, alpha_baseline, gamma, flags);
-}
-
-int gu_reinforce_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    int rc = gu_env_range(h, env0, n);
-    if (rc != GU_OK) return rc;
-    const int32_t L = h->rf_key;  // (0: the buffer was dropped and reads as empty, whatever the device copy still holds)
-    std::vector<int32_t> c(n), w((size_t)n * (size_t)L * 2);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n && L) {
-        GU_HIP(hipMemcpy(c.data(), h->d_rf_cnt + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        GU_HIP(hipMemcpy2D(w.data(), (size_t)n * 8, h->d_rf_buf + (size_t)env0 * 2, (size_t)h->N * 8, (size_t)n * 8, (size_t)L,
-                           hipMemcpyDeviceToHost));  // rows k = 0 .. L-1 of [L][N], columns env0 .. env0+n-1
-    }
-    for (int64_t e = 0; e < n; ++e)
-        for (int32_t j = 0; j < GU_REINFORCE_MAX; ++j) {
-            const size_t i = (size_t)e * GU_REINFORCE_MAX + j, b = ((size_t)j * n + e) * 2;
-            if (sa) sa[i] = j < c[e] ? w[b] : -1;
-            if (reward) reward[i] = j < c[e] ? w[b + 1] : 0;
-        }
-    if (count)
-        for (int64_t e = 0; e < n; ++e) count[e] = c[e];
-    return GU_OK;
-}
-
-// ---------------------------------------------------------------------------------- off-policy Monte-Carlo control, weighted importance sampling (gu_is.hip)
-static void gu_is_free(gu_engine *h)
-{
-    for (void *p : {(void *)h->d_is_c, (void *)h->d_is_R, (void *)h->d_is_buf, (void *)h->d_is_cnt})
-        if (p) (void)hipFree(p);
-    h->d_is_c = nullptr;
-    h->d_is_R = nullptr;
-    h->d_is_buf = nullptr;
-    h->d_is_cnt = nullptr;
-    h->is_S = 0;
-    h->is_eps = -1;
-    h->is_cap = 0;
-    h->is_key = 0;
-}
-
-int gu_is_init(gu_handle h)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    gu_tabular_drop_carry(h);
-    const size_t bytes = (size_t)h->N * (size_t)h->S * 4 * sizeof(double);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (!h->d_is_c || h->is_S != h->S) {
-        gu_is_free(h);
-        int rc = gu_tabular_fits(h, bytes, "cumulative weights");
-        if (rc != GU_OK) return rc;
-        GU_HIP(hipMalloc(&h->d_is_c, bytes));
-        GU_HIP(hipMalloc(&h->d_is_R, 20 * sizeof(double)));
-        h->is_S = h->S;
-    }
-    GU_HIP(hipMemsetAsync(h->d_is_c, 0, bytes, h->stream));
-    GU_HIP(hipStreamSynchronize(h->stream));
-    return GU_OK;
-}
-
-// R[m][c] = pi(a|s) / b(a|s) for the tie-uniform greedy target (1 / m_now) and the epsilon-greedy behaviour at action time (c of the
-// row's maxima tied, the action one of them; c = 0: not one of them), laid out for the kernel as R[c * 4 + m - 1]
-static void gu_is_ratios(uint32_t eps_q16, double *R)
-{
-    const double eps = (double)eps_q16 / 65536.0;
-    for (int c = 0; c <= 4; ++c) {
-        const double b = c == 0 ? eps * 0.25 : (1.0 - eps) / (double)c + eps * 0.25;
-        for (int m = 1; m <= 4; ++m) R[c * 4 + m - 1] = b == 0.0 ? 0.0 : (1.0 / (double)m) / b;
-    }
-}
-
-int gu_is_run(gu_handle h, int64_t T, int32_t L, double gamma, uint32_t eps_q16, double w_cap, uint32_t flags)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(h->d_is_c && h->is_S == h->S, GU_ERR_STATE, "no cumulative weights: call gu_is_init first");
-    GU_REQUIRE(L >= 1 && L <= GU_IS_MAX, GU_ERR_INVALID, "L %d out of range (1 .. %d)", L, GU_IS_MAX);
-    GU_REQUIRE(w_cap >= 1.0 && w_cap <= 0x1p256, GU_ERR_INVALID, "w_cap %g outside [1, 2^256]", w_cap);
-    int rc = gu_tabular_check(h, "gu_is_run", T, -1, eps_q16, 0.0, gamma, flags);
-    if (rc != GU_OK || T == 0) return rc;
-    if (h->is_cap < L) {  // (a call with another L drops the buffer anyway: nothing to keep)
-        const size_t slots = (size_t)h->N * (size_t)L;
-        GU_HIP(hipStreamSynchronize(h->stream));
-        rc = gu_tabular_fits(h, slots * 2 * sizeof(int32_t) + (size_t)h->N * sizeof(int32_t), "episode buffers");
-        if (rc != GU_OK) return rc;
-        for (void *p : {(void *)h->d_is_buf, (void *)h->d_is_cnt})
-            if (p) (void)hipFree(p);
-        h->d_is_buf = nullptr;
-        h->d_is_cnt = nullptr;
-        h->is_cap = 0;
-        h->is_key = 0;
-        GU_HIP(hipMalloc(&h->d_is_buf, slots * 2 * sizeof(int32_t)));
-        GU_HIP(hipMalloc(&h->d_is_cnt, (size_t)h->N * sizeof(int32_t)));
-        h->is_cap = L;
-    }
-    if (h->is_eps != (int64_t)eps_q16) {  // (a launch still in flight reads the table of its own epsilon)
-        double R[20];
-        gu_is_ratios(eps_q16, R);
-        GU_HIP(hipStreamSynchronize(h->stream));
-        h->is_eps = -1;
-        GU_HIP(hipMemcpy(h->d_is_R, R, sizeof(R), hipMemcpyHostToDevice));
-        h->is_eps = (int64_t)eps_q16;
-    }
-    return gu_launch_is(h, T, L, gamma, eps_q16, w_cap, flags);
-}
-
-static int gu_is_range(gu_engine *h, int64_t env0, int64_t n, const void *c)
-{
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_q && h->td_S == h->S, GU_ERR_STATE, "no Q tables: call gu_td_init first");
-    GU_REQUIRE(h->d_is_c && h->is_S == h->S, GU_ERR_STATE, "no cumulative weights: call gu_is_init first");
-    GU_REQUIRE(c != nullptr, GU_ERR_INVALID, "c is NULL");
-    return gu_env_range(h, env0, n);
-}
-
-int gu_is_get(gu_handle h, int64_t env0, int64_t n, double *c)
-{
-    GU_ENTER(h);
-    int rc = gu_is_range(h, env0, n, c);
-    if (rc != GU_OK) return rc;
-    const size_t row = (size_t)h->S * 4;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n) GU_HIP(hipMemcpy(c, h->d_is_c + (size_t)env0 * row, (size_t)n * row * sizeof(double), hipMemcpyDeviceToHost));
-    return GU_OK;
-}
-
-int gu_is_set(gu_handle h, int64_t env0, int64_t n, const double *c)
-{
-    GU_ENTER(h);
-    int rc = gu_is_range(h, env0, n, c);
-    if (rc != GU_OK) return rc;
-    const size_t row = (size_t)h->S * 4, k = (size_t)n * row;
-    for (size_t i = 0; i < k; ++i)
-        GU_REQUIRE(std::isfinite(c[i]) && c[i] >= 0.0, GU_ERR_INVALID, "c[%zu] = %g: every entry must be finite and not negative", i, c[i]);
-    gu_tabular_drop_carry(h);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n) GU_HIP(hipMemcpy(h->d_is_c + (size_t)env0 * row, c, k * sizeof(double), hipMemcpyHostToDevice));
-    return GU_OK;
-}
-
-int gu_is_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *cls, int32_t *count)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    int rc = gu_env_range(h, env0, n);
-    if (rc != GU_OK) return rc;
-    const int32_t L = h->is_key;  // (0: the buffer was dropped and reads as empty, whatever the device copy still holds)
-    std::vector<int32_t> c(n), w((size_t)n * (size_t)L * 2);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n && L) {
-        GU_HIP(hipMemcpy(c.data(), h->d_is_cnt + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-        GU_HIP(hipMemcpy2D(w.data(), (size_t)n * 8, h->d_is_buf + (size_t)env0 * 2, (size_t)h->N * 8, (size_t)n * 8, (size_t)L,
-                           hipMemcpyDeviceToHost));  // rows k = 0 .. L-1 of [L][N], columns env0 .. env0+n-1
-    }
-    for (int64_t e = 0; e < n; ++e)
-        for (int32_t j = 0; j < GU_IS_MAX; ++j) {
-            const size_t i = (size_t)e * GU_IS_MAX + j, b = ((size_t)j * n + e) * 2;
-            const bool live = j < c[e];
-            if (sa) sa[i] = live ? w[b] : -1;
-            if (reward) reward[i] = live ? w[b + 1] >> 3 : 0;
-            if (cls) cls[i] = live ? w[b + 1] & 7 : 0;
-        }
-    if (count)
-        for (int64_t e = 0; e < n; ++e) count[e] = c[e];
-    return GU_OK;
-}
-
-// ---------------------------------------------------------------------------------- semi-gradient SARSA / Q-learning on features (gu_fa.hip)
-static void gu_fa_free(gu_engine *h)
-{
-    if (h->d_fa_w) (void)hipFree(h->d_fa_w);
-    if (h->d_fa_phi) (void)hipFree(h->d_fa_phi);
-    if (h->d_fa_phi16) (void)hipFree(h->d_fa_phi16);
-    if (h->d_fa_next) (void)hipFree(h->d_fa_next);
-    h->d_fa_w = nullptr;
-    h->d_fa_phi = nullptr;
-    h->d_fa_phi16 = nullptr;
-    h->d_fa_next = nullptr;
-    h->fa_phi16_bytes = 0;
-    h->fa_S = h->fa_K = h->fa_F = 0;
-    h->fa_carry = false;
-}
-
-int gu_fa_init(gu_handle h, int32_t K, int32_t F, const int32_t *phi, double w0)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(K >= 1 && K <= GU_FA_MAX_K, GU_ERR_INVALID, "K %d out of range (1 .. %d)", K, GU_FA_MAX_K);
-    GU_REQUIRE(F >= 1 && F <= GU_FA_MAX_F, GU_ERR_INVALID, "F %d out of range (1 .. %d)", F, GU_FA_MAX_F);
-    GU_REQUIRE(phi != nullptr, GU_ERR_INVALID, "phi is NULL");
-    GU_REQUIRE(std::isfinite(w0), GU_ERR_INVALID, "w0 must be finite");
-    const size_t S = (size_t)h->S, cells = S * (size_t)K;
-    std::vector<int8_t> column((size_t)F, (int8_t)-1);  // the column each feature index occurs in
-    for (size_t i = 0; i < cells; ++i) {
-        const int32_t f = phi[i], k = (int32_t)(i % (size_t)K);
-        GU_REQUIRE(f >= 0 && f < F, GU_ERR_INVALID, "phi[%zu][%d] = %d outside 0 .. %d", i / (size_t)K, k, f, F - 1);
-        GU_REQUIRE(column[f] < 0 || column[f] == k, GU_ERR_INVALID, "feature %d occurs in columns %d and %d: a column is a slot of its own", f,
-                   (int)column[f], k);
-        column[f] = (int8_t)k;
-    }
-    gu_tabular_drop_carry(h);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (!h->d_fa_w || h->fa_S != h->S || h->fa_K != K || h->fa_F != F) {
-        gu_fa_free(h);
-        const size_t bytes = (size_t)h->N * (size_t)F * 4 * sizeof(double);
-        int rc = gu_tabular_fits(h, bytes + cells * 6 + (size_t)h->N, "feature weights");
-        if (rc != GU_OK) return rc;
-        GU_HIP(hipMalloc(&h->d_fa_w, bytes));
-        GU_HIP(hipMalloc(&h->d_fa_phi, cells * sizeof(int32_t)));
-        GU_HIP(hipMalloc(&h->d_fa_next, (size_t)h->N));
-        if (F <= 65536) {
-            h->fa_phi16_bytes = (cells * sizeof(uint16_t) + 15) & ~(size_t)15;
-            GU_HIP(hipMalloc(&h->d_fa_phi16, h->fa_phi16_bytes));
-        }
-        h->fa_S = h->S;
-        h->fa_K = K;
-        h->fa_F = F;
-    }
-    GU_HIP(hipMemcpy(h->d_fa_phi, phi, cells * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (h->d_fa_phi16) {
-        std::vector<uint16_t> p16(h->fa_phi16_bytes / sizeof(uint16_t), (uint16_t)0);
-        for (size_t i = 0; i < cells; ++i) p16[i] = (uint16_t)phi[i];
-        GU_HIP(hipMemcpy(h->d_fa_phi16, p16.data(), h->fa_phi16_bytes, hipMemcpyHostToDevice));
-    }
-    GU_HIP(hipMemsetAsync(h->d_fa_next, 0xFF, (size_t)h->N, h->stream));
-    int rc = gu_fa_fill(h, w0);
-    if (rc != GU_OK) return rc;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    return GU_OK;
-}
-
-int gu_fa_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
-{
-    GU_ENTER(h);
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_fa_w && h->fa_S == h->S, GU_ERR_STATE, "no features: call gu_fa_init first");
-    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Q-learning, 1 = SARSA", method);
-    int rc = gu_tabular_check(h, "gu_fa_run", T, -1, eps_q16, alpha, gamma, flags);
-    if (rc != GU_OK || T == 0) return rc;
-    return gu_launch_fa(h, T, method, alpha, gamma, eps_q16, flags);
-}
-
-static int gu_fa_range(gu_engine *h, int64_t env0, int64_t n, const void *p, const char *name)
-{
-    GU_NEED_GRID(h);
-    GU_REQUIRE(h->d_fa_w && h->fa_S == h->S, GU_ERR_STATE, "no features: call gu_fa_init first");
-    GU_REQUIRE(p != nullptr, GU_ERR_INVALID, "%s is NULL", name);
-    return gu_env_range(h, env0, n);
-}
-
-int gu_fa_get_w(gu_handle h, int64_t env0, int64_t n, double *w)
-{
-    GU_ENTER(h);
-    int rc = gu_fa_range(h, env0, n, w, "w");
-    if (rc != GU_OK) return rc;
-    const size_t row = (size_t)h->fa_F * 4;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n) GU_HIP(hipMemcpy(w, h->d_fa_w + (size_t)env0 * row, (size_t)n * row * sizeof(double), hipMemcpyDeviceToHost));
-    return GU_OK;
-}
-
-int gu_fa_set_w(gu_handle h, int64_t env0, int64_t n, const double *w)
-{
-    GU_ENTER(h);
-    int rc = gu_fa_range(h, env0, n, w, "w");
-    if (rc != GU_OK) return rc;
-    gu_tabular_drop_carry(h);
-    const size_t row = (size_t)h->fa_F * 4;
-    GU_HIP(hipStreamSynchronize(h->stream));
-    if (n) GU_HIP(hipMemcpy(h->d_fa_w + (size_t)env0 * row, w, (size_t)n * row * sizeof(double), hipMemcpyHostToDevice));
-    return GU_OK;
-}
-
-int gu_fa_get_q(gu_handle h, int64_t env0, int64_t n, double *q)
-{
-    GU_ENTER(h);
-    int rc = gu_fa_range(h, env0, n, q, "q");
-    if (rc != GU_OK || n == 0) return rc;
-    // folded on the device in slices of at most 64 MiB, through the engine's scratch buffer
-    const size_t row = (size_t)h->S * 4 * sizeof(double);
-    const int64_t slice = std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / row));
-    for (int64_t i = 0; i < n; i += slice) {
-        const int64_t k = std::min<int64_t>(slice, n - i);
-        rc = gu_ensure_scratch(h, (size_t)k * row);
-        if (rc != GU_OK) return rc;
-        rc = gu_fa_fold_q(h, env0 + i, k, reinterpret_cast<double *>(h->d_scratch));
-        if (rc != GU_OK) return rc;
-        GU_HIP(hipStreamSynchronize(h->stream));
-        GU_HIP(hipMemcpy(q + (size_t)i * (size_t)h->S * 4, h->d_scratch, (size_t)k * row, hipMemcpyDeviceToHost));
-    }
     return GU_OK;
 }
 

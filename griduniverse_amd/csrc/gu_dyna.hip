@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_dyna_kernel(const DynaArgs a)
     L.ballot(a);
 }
 
-int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+static int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
 {
     DynaArgs a{};
     gu_tabular_args(h, a, T, alpha, gamma, eps_q16, flags);
@@ -151,3 +151,79 @@ int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, double gamm
                          : gu_tabular_launch(h, gu_dyna_kernel<false, true>, gu_dyna_kernel<false, false>, a);
     return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
 }
+
+void gu_dyna_free(gu_engine *h)
+{
+    gu_release(h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen);
+    h->dyna_S = 0;
+    h->dyna_exact = false;
+}
+
+#define GU_NEED_DYNA(h) GU_REQUIRE((h)->d_dyna_model && (h)->dyna_S == (h)->S, GU_ERR_STATE, "no Dyna-Q model: call gu_dyna_init first")
+
+extern "C" {
+
+int gu_dyna_init(gu_handle h)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    gu_tabular_drop_carry(h);
+    const size_t pairs = (size_t)h->N * (size_t)h->S * 4;
+    if (!h->d_dyna_model || h->dyna_S != h->S) {
+        GU_HIP(hipStreamSynchronize(h->stream));
+        gu_dyna_free(h);
+        const size_t bytes = pairs * (sizeof(uint64_t) + sizeof(int32_t)) + (size_t)h->N * (sizeof(int32_t) + (size_t)h->S);
+        GU_TRY(gu_tabular_fits(h, bytes, "Dyna-Q models"));
+        GU_HIP(hipMalloc(&h->d_dyna_model, pairs * sizeof(uint64_t)));
+        GU_HIP(hipMalloc(&h->d_dyna_list, pairs * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_dyna_count, (size_t)h->N * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_dyna_seen, (size_t)h->N * (size_t)h->S));
+        h->dyna_S = h->S;
+    }
+    h->dyna_exact = true;
+    GU_HIP(hipMemsetAsync(h->d_dyna_model, 0xFF, pairs * sizeof(uint64_t), h->stream));
+    GU_HIP(hipMemsetAsync(h->d_dyna_list, 0xFF, pairs * sizeof(int32_t), h->stream));
+    GU_HIP(hipMemsetAsync(h->d_dyna_count, 0, (size_t)h->N * sizeof(int32_t), h->stream));
+    GU_HIP(hipMemsetAsync(h->d_dyna_seen, 0, (size_t)h->N * (size_t)h->S, h->stream));
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_dyna_run(gu_handle h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_NEED_DYNA(h);
+    GU_REQUIRE(P >= 0 && P <= 256, GU_ERR_INVALID, "planning steps %d out of range (0 .. 256)", P);
+    int rc = gu_tabular_check(h, "gu_dyna_run", T, P, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    return gu_launch_dyna(h, T, P, alpha, gamma, eps_q16, flags);
+}
+
+int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32_t *reward, int32_t *done, int32_t *list, int32_t *count)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_DYNA(h);
+    GU_TRY(gu_env_range(h, env0, n));
+    const size_t pairs = (size_t)h->S * 4, k = (size_t)n * pairs;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!n) return GU_OK;
+    if (next || reward || done) {
+        std::vector<uint64_t> words(k);
+        GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, words.data(), h->d_dyna_model, env0, n, pairs, false));
+        for (size_t i = 0; i < k; ++i) {
+            const uint64_t w = words[i];
+            const bool seen = w != ~0ull;
+            const uint32_t hi = (uint32_t)(w >> 32);
+            if (next) next[i] = seen ? (int32_t)(hi & 0x7FFFFFFFu) : -1;
+            if (reward) reward[i] = seen ? (int32_t)(uint32_t)w : 0;
+            if (done) done[i] = seen ? (int32_t)(hi >> 31) : 0;
+        }
+    }
+    GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, list, h->d_dyna_list, env0, n, pairs, false));
+    return gu_env_copy(h, hipMemcpyDeviceToHost, count, h->d_dyna_count, env0, n, 1, false);
+}
+
+}  // extern "C"

@@ -127,7 +127,7 @@ static int gu_explore_launch(gu_engine *h, ExploreArgs &a)
     return GU_OK;
 }
 
-int gu_launch_explore(gu_engine *h, int64_t T, int32_t mode, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+static int gu_launch_explore(gu_engine *h, int64_t T, int32_t mode, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
 {
     ExploreArgs a{};
     gu_tabular_args(h, a, T, alpha, gamma, eps_q16, flags);
@@ -137,3 +137,79 @@ int gu_launch_explore(gu_engine *h, int64_t T, int32_t mode, double alpha, doubl
     const int rc = mode == 1 ? gu_explore_launch<1>(h, a) : gu_explore_launch<0>(h, a);
     return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
 }
+
+void gu_explore_free(gu_engine *h)
+{
+    gu_release(h->d_explore_n);
+    h->explore_S = 0;
+}
+
+#define GU_NEED_COUNTS(h) GU_REQUIRE((h)->d_explore_n && (h)->explore_S == (h)->S, GU_ERR_STATE, "no visit counts: call gu_explore_init first")
+
+extern "C" {
+
+int gu_explore_init(gu_handle h)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    const size_t bytes = (size_t)h->N * (size_t)h->S * 4 * sizeof(uint32_t);
+    if (!h->d_explore_n || h->explore_S != h->S) {
+        GU_HIP(hipStreamSynchronize(h->stream));
+        gu_explore_free(h);
+        GU_TRY(gu_tabular_fits(h, bytes, "visit counts"));
+        GU_HIP(hipMalloc(&h->d_explore_n, bytes));
+        h->explore_S = h->S;
+    }
+    GU_HIP(hipMemsetAsync(h->d_explore_n, 0, bytes, h->stream));
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_explore_set_tables(gu_handle h, int32_t C, const double *U, const double *B)
+{
+    GU_ENTER(h);
+    const double *v[] = {U, B};
+    return gu_schedule_upload(h, h->d_explore_tab, h->explore_C, C, v, 2);
+}
+
+int gu_explore_run(gu_handle h, int64_t T, int32_t mode, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_NEED_COUNTS(h);
+    GU_REQUIRE(h->d_explore_tab && h->explore_C >= 2, GU_ERR_STATE, "no exploration tables: call gu_explore_set_tables first");
+    GU_REQUIRE(mode == 0 || mode == 1, GU_ERR_INVALID, "mode %d: 0 = UCB, 1 = Thompson", mode);
+    int rc = gu_tabular_check(h, "gu_explore_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    return gu_launch_explore(h, T, mode, alpha, gamma, eps_q16, flags);
+}
+
+static int gu_explore_range(gu_engine *h, int64_t env0, int64_t n, const void *counts)
+{
+    GU_NEED_GRID(h);
+    GU_NEED_COUNTS(h);
+    GU_REQUIRE(counts != nullptr, GU_ERR_INVALID, "counts is NULL");
+    return gu_env_range(h, env0, n);
+}
+
+int gu_explore_get_counts(gu_handle h, int64_t env0, int64_t n, uint32_t *counts)
+{
+    GU_ENTER(h);
+    GU_TRY(gu_explore_range(h, env0, n, counts));
+    return gu_env_copy(h, hipMemcpyDeviceToHost, counts, h->d_explore_n, env0, n, (size_t)h->S * 4);
+}
+
+int gu_explore_set_counts(gu_handle h, int64_t env0, int64_t n, const uint32_t *counts)
+{
+    GU_ENTER(h);
+    GU_TRY(gu_explore_range(h, env0, n, counts));
+    const size_t row = (size_t)h->S * 4, k = (size_t)n * row;
+    for (size_t i = 0; i < k; ++i)
+        GU_REQUIRE(counts[i] <= GU_EXPLORE_COUNT_MAX, GU_ERR_INVALID, "count %u of env %lld above the cap 0x%X", counts[i],
+                   (long long)(env0 + (int64_t)(i / row)), GU_EXPLORE_COUNT_MAX);
+    return gu_env_copy(h, hipMemcpyHostToDevice, counts, h->d_explore_n, env0, n, row);
+}
+
+}  // extern "C"

@@ -177,7 +177,7 @@ __global__ void __launch_bounds__(256) gu_fa_fill_kernel(double *__restrict__ w,
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) w[i] = v;
 }
 
-int gu_fa_fill(gu_engine *h, double w0)
+static int gu_fa_fill(gu_engine *h, double w0)
 {
     const size_t n = (size_t)h->N * (size_t)h->fa_F * 4;
     const unsigned blocks = (unsigned)std::max<size_t>(1, std::min<size_t>((n + 255) / 256, (size_t)h->n_cu * 16));
@@ -210,7 +210,7 @@ __global__ void __launch_bounds__(256) gu_fa_q_kernel(const double *__restrict__
 }
 
 // the folded tables of envs env0 .. env0+n-1 into d_out [n][S][4] (async)
-int gu_fa_fold_q(gu_engine *h, int64_t env0, int64_t n, double *d_out)
+static int gu_fa_fold_q(gu_engine *h, int64_t env0, int64_t n, double *d_out)
 {
     const int64_t rows = n * (int64_t)h->S;
     if (rows == 0) return GU_OK;
@@ -242,7 +242,7 @@ static int gu_fa_launch_k(gu_engine *h, FaArgs &a, int32_t method)
     return method == 1 ? gu_fa_launch<K, true>(h, a) : gu_fa_launch<K, false>(h, a);
 }
 
-int gu_launch_fa(gu_engine *h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+static int gu_launch_fa(gu_engine *h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
 {
     FaArgs a{};
     gu_tabular_args(h, a, T, alpha, gamma, eps_q16, flags);
@@ -269,3 +269,115 @@ int gu_launch_fa(gu_engine *h, int64_t T, int32_t method, double alpha, double g
     h->fa_carry = method == 1;
     return rc;
 }
+
+void gu_fa_free(gu_engine *h)
+{
+    gu_release(h->d_fa_w, h->d_fa_phi, h->d_fa_phi16, h->d_fa_next);
+    h->fa_phi16_bytes = 0;
+    h->fa_S = h->fa_K = h->fa_F = 0;
+    h->fa_carry = false;
+}
+
+#define GU_NEED_FA(h) GU_REQUIRE((h)->d_fa_w && (h)->fa_S == (h)->S, GU_ERR_STATE, "no features: call gu_fa_init first")
+
+extern "C" {
+
+int gu_fa_init(gu_handle h, int32_t K, int32_t F, const int32_t *phi, double w0)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(K >= 1 && K <= GU_FA_MAX_K, GU_ERR_INVALID, "K %d out of range (1 .. %d)", K, GU_FA_MAX_K);
+    GU_REQUIRE(F >= 1 && F <= GU_FA_MAX_F, GU_ERR_INVALID, "F %d out of range (1 .. %d)", F, GU_FA_MAX_F);
+    GU_REQUIRE(phi != nullptr, GU_ERR_INVALID, "phi is NULL");
+    GU_REQUIRE(std::isfinite(w0), GU_ERR_INVALID, "w0 must be finite");
+    const size_t S = (size_t)h->S, cells = S * (size_t)K;
+    std::vector<int8_t> column((size_t)F, (int8_t)-1);  // the column each feature index occurs in
+    for (size_t i = 0; i < cells; ++i) {
+        const int32_t f = phi[i], k = (int32_t)(i % (size_t)K);
+        GU_REQUIRE(f >= 0 && f < F, GU_ERR_INVALID, "phi[%zu][%d] = %d outside 0 .. %d", i / (size_t)K, k, f, F - 1);
+        GU_REQUIRE(column[f] < 0 || column[f] == k, GU_ERR_INVALID, "feature %d occurs in columns %d and %d: a column is a slot of its own", f,
+                   (int)column[f], k);
+        column[f] = (int8_t)k;
+    }
+    gu_tabular_drop_carry(h);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!h->d_fa_w || h->fa_S != h->S || h->fa_K != K || h->fa_F != F) {
+        gu_fa_free(h);
+        const size_t bytes = (size_t)h->N * (size_t)F * 4 * sizeof(double);
+        GU_TRY(gu_tabular_fits(h, bytes + cells * 6 + (size_t)h->N, "feature weights"));
+        GU_HIP(hipMalloc(&h->d_fa_w, bytes));
+        GU_HIP(hipMalloc(&h->d_fa_phi, cells * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_fa_next, (size_t)h->N));
+        if (F <= 65536) {
+            h->fa_phi16_bytes = (cells * sizeof(uint16_t) + 15) & ~(size_t)15;
+            GU_HIP(hipMalloc(&h->d_fa_phi16, h->fa_phi16_bytes));
+        }
+        h->fa_S = h->S;
+        h->fa_K = K;
+        h->fa_F = F;
+    }
+    GU_HIP(hipMemcpy(h->d_fa_phi, phi, cells * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (h->d_fa_phi16) {
+        std::vector<uint16_t> p16(h->fa_phi16_bytes / sizeof(uint16_t), (uint16_t)0);
+        for (size_t i = 0; i < cells; ++i) p16[i] = (uint16_t)phi[i];
+        GU_HIP(hipMemcpy(h->d_fa_phi16, p16.data(), h->fa_phi16_bytes, hipMemcpyHostToDevice));
+    }
+    GU_HIP(hipMemsetAsync(h->d_fa_next, 0xFF, (size_t)h->N, h->stream));
+    GU_TRY(gu_fa_fill(h, w0));  // every weight = w0 (async)
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_fa_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_FA(h);
+    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Q-learning, 1 = SARSA", method);
+    int rc = gu_tabular_check(h, "gu_fa_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    return gu_launch_fa(h, T, method, alpha, gamma, eps_q16, flags);
+}
+
+static int gu_fa_range(gu_engine *h, int64_t env0, int64_t n, const void *p, const char *name)
+{
+    GU_NEED_GRID(h);
+    GU_NEED_FA(h);
+    GU_REQUIRE(p != nullptr, GU_ERR_INVALID, "%s is NULL", name);
+    return gu_env_range(h, env0, n);
+}
+
+int gu_fa_get_w(gu_handle h, int64_t env0, int64_t n, double *w)
+{
+    GU_ENTER(h);
+    GU_TRY(gu_fa_range(h, env0, n, w, "w"));
+    return gu_env_copy(h, hipMemcpyDeviceToHost, w, h->d_fa_w, env0, n, (size_t)h->fa_F * 4);
+}
+
+int gu_fa_set_w(gu_handle h, int64_t env0, int64_t n, const double *w)
+{
+    GU_ENTER(h);
+    GU_TRY(gu_fa_range(h, env0, n, w, "w"));
+    gu_tabular_drop_carry(h);
+    return gu_env_copy(h, hipMemcpyHostToDevice, w, h->d_fa_w, env0, n, (size_t)h->fa_F * 4);
+}
+
+int gu_fa_get_q(gu_handle h, int64_t env0, int64_t n, double *q)
+{
+    GU_ENTER(h);
+    int rc = gu_fa_range(h, env0, n, q, "q");
+    if (rc != GU_OK || n == 0) return rc;
+    // folded on the device in slices of at most 64 MiB, through the engine's scratch buffer
+    const size_t row = (size_t)h->S * 4 * sizeof(double);
+    const int64_t slice = std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / row));
+    for (int64_t i = 0; i < n; i += slice) {
+        const int64_t k = std::min<int64_t>(slice, n - i);
+        GU_TRY(gu_ensure_scratch(h, (size_t)k * row));
+        GU_TRY(gu_fa_fold_q(h, env0 + i, k, reinterpret_cast<double *>(h->d_scratch)));
+        GU_HIP(hipStreamSynchronize(h->stream));
+        GU_HIP(hipMemcpy(q + (size_t)i * (size_t)h->S * 4, h->d_scratch, (size_t)k * row, hipMemcpyDeviceToHost));
+    }
+    return GU_OK;
+}
+
+}  // extern "C"

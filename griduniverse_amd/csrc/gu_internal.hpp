@@ -372,6 +372,16 @@ int gu_fail(int code, const char *fmt, ...);
 int gu_use_device(gu_engine *h);
 int gu_ensure_scratch(gu_engine *h, size_t bytes);
 
+#define GU_TRY(call)                                 \
+    do {                                             \
+        int _rc = (call);                            \
+        if (_rc != GU_OK) return _rc;                \
+    } while (0)
+
+#define GU_ENTER(h) GU_TRY(gu_use_device(h))
+
+#define GU_NEED_GRID(h) GU_REQUIRE((h)->has_grid, GU_ERR_STATE, "no grid set: call gu_set_grid first")
+
 // ---- options (gu_options.hip) ----------------------------------------------------
 // The value in force for `option`: the engine's own, else the process default, else the built-in one.  A few loads; called
 // per launch.  (A -DGU_EXPERIMENTS build also consults the environment variable of the same name on every call, for the
@@ -451,49 +461,26 @@ int gu_vi_xcd_fused_run(gu_engine *h, const GuXcdPlan &xp, double gamma, int32_t
 int gu_vi_xcd_dp_run(gu_engine *h, double gamma, double threshold, bool use_threshold, bool greedy, int32_t max_rounds, int32_t *rounds_done,
                      double *deltas);
 
-// ---- batched tabular TD control (gu_td.hip) ----------------------------------------
-int gu_td_fill(gu_engine *h, double q0);  // every entry of every table = q0 (async)
-int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
-
-// ---- batched tabular Dyna-Q (gu_dyna.hip) -------------------------------------------
-int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
-
-// ---- batched rollout search at decision time (gu_search.hip) --------------------------
-int gu_launch_search(gu_engine *h, int64_t T, int32_t M, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
-                     uint32_t flags);
-
-// ---- batched count-based exploration: UCB / Thompson Q-learning (gu_explore.hip) ---------
-int gu_launch_explore(gu_engine *h, int64_t T, int32_t mode, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
-
-// ---- batched Monte-Carlo tree search at decision time (gu_mcts.hip) -------------------
-int gu_launch_mcts(gu_engine *h, int64_t T, int32_t M, int32_t H, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
-                   uint32_t flags);
-
-// ---- batched tabular n-step Q-learning / SARSA (gu_nstep.hip) --------------------------
-// the carry key of a gu_nstep_run (never 0): the next launch keeps the window only under the same method and n
-static inline int32_t gu_nstep_key(int32_t method, int32_t n) { return 1 + method + 2 * n; }
-int gu_launch_nstep(gu_engine *h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
-
-// ---- batched tabular SARSA(lambda) / Watkins's Q(lambda) (gu_lambda.hip) ----------------
-// the carry key of a gu_lambda_run (never 0): the next launch keeps the window only under the same method and K
-static inline int32_t gu_lambda_key(int32_t method, int32_t K) { return 1 + method + 2 * K; }
-int gu_launch_lambda(gu_engine *h, int64_t T, int32_t method, int32_t K, double alpha, double gamma, double lambda, uint32_t eps_q16,
-                     uint32_t flags);
-
-// ---- batched tabular softmax actor-critic (gu_ac.hip) ----------------------------------
-int gu_ac_fill(gu_engine *h, double h0, double v0);  // every preference = h0, every value = v0 (async)
-int gu_launch_ac(gu_engine *h, int64_t T, double alpha_actor, double alpha_critic, double gamma, uint32_t flags);
-
-// ---- batched tabular REINFORCE with baseline (gu_reinforce.hip) ------------------------
-int gu_launch_reinforce(gu_engine *h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags);
-
-// ---- batched off-policy Monte-Carlo control with weighted importance sampling (gu_is.hip) ----
-int gu_launch_is(gu_engine *h, int64_t T, int32_t L, double gamma, uint32_t eps_q16, double w_cap, uint32_t flags);
-
-// ---- batched semi-gradient SARSA / Q-learning on binary features (gu_fa.hip) ----------------
-int gu_fa_fill(gu_engine *h, double w0);  // every weight = w0 (async)
-int gu_fa_fold_q(gu_engine *h, int64_t env0, int64_t n, double *d_out);  // Q of envs env0 .. env0+n-1 into d_out [n][S][4] (async)
-int gu_launch_fa(gu_engine *h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+// ---- the batched learners ------------------------------------------------------------
+// gu_td.hip (Q-learning, SARSA), gu_dyna.hip (Dyna-Q), gu_nstep.hip, gu_lambda.hip, gu_search.hip (rollout search), gu_explore.hip
+// (UCB / Thompson), gu_mcts.hip (tree search), gu_is.hip (off-policy Monte-Carlo), gu_ac.hip (actor-critic), gu_reinforce.hip and
+// gu_fa.hip (semi-gradient learners on features) each hold their kernels, their launch code and their extern "C" functions
+// (include/gu.h); the host helpers they share are in gu_tabular.hpp.  What they export to each other is their gu_*_free: the device
+// buffers of the module and the fields that describe them, back to "none".
+void gu_dyna_free(gu_engine *h);
+void gu_nstep_free(gu_engine *h);
+void gu_lambda_free(gu_engine *h);
+void gu_search_free(gu_engine *h);
+void gu_explore_free(gu_engine *h);    // (the visit counts; the U and B tables stay)
+void gu_mcts_free(gu_engine *h);       // (the node pools; the U, B and I tables stay)
+void gu_is_free(gu_engine *h);
+void gu_ac_free(gu_engine *h);         // (takes gu_reinforce_free along: REINFORCE learns into the actor-critic tables)
+void gu_reinforce_free(gu_engine *h);
+void gu_fa_free(gu_engine *h);
+// The one place that knows every learner's stores (gu_td.hip).  S > 0: a grid of S states is being installed -- Q tables of another
+// state count go and take what hangs on them along (the SARSA actions, the n-step and lambda windows, the search scores, the node
+// pools), and so does every other store sized by another state count.  S == 0: the engine is being destroyed -- everything goes.
+void gu_learners_drop(gu_engine *h, int32_t S);
 
 // every call that touches the envs other than the learner launches ends what the learners carry from one launch to the next:
 // gu_td_run's and gu_fa_run's SARSA actions, gu_nstep_run's window (its pending updates are discarded, not flushed), gu_lambda_run's

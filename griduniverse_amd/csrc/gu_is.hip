@@ -136,7 +136,7 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_is_kernel(const IsArgs a)
     L.ballot(a);
 }
 
-int gu_launch_is(gu_engine *h, int64_t T, int32_t L, double gamma, uint32_t eps_q16, double w_cap, uint32_t flags)
+static int gu_launch_is(gu_engine *h, int64_t T, int32_t L, double gamma, uint32_t eps_q16, double w_cap, uint32_t flags)
 {
     IsArgs a{};
     gu_tabular_args(h, a, T, 0.0, gamma, eps_q16, flags);
@@ -153,3 +153,106 @@ int gu_launch_is(gu_engine *h, int64_t T, int32_t L, double gamma, uint32_t eps_
     h->is_key = L;
     return rc2;
 }
+
+void gu_is_free(gu_engine *h)
+{
+    gu_release(h->d_is_c, h->d_is_R, h->d_is_buf, h->d_is_cnt);
+    h->is_S = 0;
+    h->is_eps = -1;
+    h->is_cap = 0;
+    h->is_key = 0;
+}
+
+// R[m][c] = pi(a|s) / b(a|s) for the tie-uniform greedy target (1 / m_now) and the epsilon-greedy behaviour at action time (c of the
+// row's maxima tied, the action one of them; c = 0: not one of them), laid out for the kernel as R[c * 4 + m - 1]
+static void gu_is_ratios(uint32_t eps_q16, double *R)
+{
+    const double eps = (double)eps_q16 / 65536.0;
+    for (int c = 0; c <= 4; ++c) {
+        const double b = c == 0 ? eps * 0.25 : (1.0 - eps) / (double)c + eps * 0.25;
+        for (int m = 1; m <= 4; ++m) R[c * 4 + m - 1] = b == 0.0 ? 0.0 : (1.0 / (double)m) / b;
+    }
+}
+
+#define GU_NEED_WEIGHTS(h) GU_REQUIRE((h)->d_is_c && (h)->is_S == (h)->S, GU_ERR_STATE, "no cumulative weights: call gu_is_init first")
+
+extern "C" {
+
+int gu_is_init(gu_handle h)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    gu_tabular_drop_carry(h);
+    const size_t bytes = (size_t)h->N * (size_t)h->S * 4 * sizeof(double);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!h->d_is_c || h->is_S != h->S) {
+        gu_is_free(h);
+        GU_TRY(gu_tabular_fits(h, bytes, "cumulative weights"));
+        GU_HIP(hipMalloc(&h->d_is_c, bytes));
+        GU_HIP(hipMalloc(&h->d_is_R, 20 * sizeof(double)));
+        h->is_S = h->S;
+    }
+    GU_HIP(hipMemsetAsync(h->d_is_c, 0, bytes, h->stream));
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_is_run(gu_handle h, int64_t T, int32_t L, double gamma, uint32_t eps_q16, double w_cap, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_NEED_WEIGHTS(h);
+    GU_REQUIRE(L >= 1 && L <= GU_IS_MAX, GU_ERR_INVALID, "L %d out of range (1 .. %d)", L, GU_IS_MAX);
+    GU_REQUIRE(w_cap >= 1.0 && w_cap <= 0x1p256, GU_ERR_INVALID, "w_cap %g outside [1, 2^256]", w_cap);
+    int rc = gu_tabular_check(h, "gu_is_run", T, -1, eps_q16, 0.0, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    GU_TRY(gu_episode_reserve(h, h->d_is_buf, h->d_is_cnt, h->is_cap, h->is_key, L));
+    if (h->is_eps != (int64_t)eps_q16) {  // (a launch still in flight reads the table of its own epsilon)
+        double R[20];
+        gu_is_ratios(eps_q16, R);
+        GU_HIP(hipStreamSynchronize(h->stream));
+        h->is_eps = -1;
+        GU_HIP(hipMemcpy(h->d_is_R, R, sizeof(R), hipMemcpyHostToDevice));
+        h->is_eps = (int64_t)eps_q16;
+    }
+    return gu_launch_is(h, T, L, gamma, eps_q16, w_cap, flags);
+}
+
+static int gu_is_range(gu_engine *h, int64_t env0, int64_t n, const void *c)
+{
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_NEED_WEIGHTS(h);
+    GU_REQUIRE(c != nullptr, GU_ERR_INVALID, "c is NULL");
+    return gu_env_range(h, env0, n);
+}
+
+int gu_is_get(gu_handle h, int64_t env0, int64_t n, double *c)
+{
+    GU_ENTER(h);
+    GU_TRY(gu_is_range(h, env0, n, c));
+    return gu_env_copy(h, hipMemcpyDeviceToHost, c, h->d_is_c, env0, n, (size_t)h->S * 4);
+}
+
+int gu_is_set(gu_handle h, int64_t env0, int64_t n, const double *c)
+{
+    GU_ENTER(h);
+    GU_TRY(gu_is_range(h, env0, n, c));
+    const size_t row = (size_t)h->S * 4, k = (size_t)n * row;
+    for (size_t i = 0; i < k; ++i)
+        GU_REQUIRE(std::isfinite(c[i]) && c[i] >= 0.0, GU_ERR_INVALID, "c[%zu] = %g: every entry must be finite and not negative", i, c[i]);
+    gu_tabular_drop_carry(h);
+    return gu_env_copy(h, hipMemcpyHostToDevice, c, h->d_is_c, env0, n, row);
+}
+
+int gu_is_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *cls, int32_t *count)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_TRY(gu_env_range(h, env0, n));
+    return gu_episode_read(h, h->d_is_buf, h->d_is_cnt, h->is_key, GU_IS_MAX, env0, n, sa, reward, cls, true, count);
+}
+
+}  // extern "C"

@@ -156,7 +156,10 @@ static int gu_lambda_launch_m(gu_engine *h, const LambdaArgs &a)
                        : gu_lambda_launch_c<SARSA, GU_LAMBDA_MAX>(h, a);
 }
 
-int gu_launch_lambda(gu_engine *h, int64_t T, int32_t method, int32_t K, double alpha, double gamma, double lambda, uint32_t eps_q16,
+// the carry key of a gu_lambda_run (never 0): the next launch keeps the window only under the same method and K
+static inline int32_t gu_lambda_key(int32_t method, int32_t K) { return 1 + method + 2 * K; }
+
+static int gu_launch_lambda(gu_engine *h, int64_t T, int32_t method, int32_t K, double alpha, double gamma, double lambda, uint32_t eps_q16,
                      uint32_t flags)
 {
     LambdaArgs a{};
@@ -180,3 +183,48 @@ int gu_launch_lambda(gu_engine *h, int64_t T, int32_t method, int32_t K, double 
     h->lambda_key = key;
     return rc2;
 }
+
+void gu_lambda_free(gu_engine *h)
+{
+    gu_release(h->d_lambda_w);
+    h->lambda_key = 0;
+}
+
+extern "C" {
+
+int gu_lambda_run(gu_handle h, int64_t T, int32_t method, int32_t K, double alpha, double gamma, double lambda, uint32_t eps_q16,
+                  uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Watkins's Q(lambda), 1 = SARSA(lambda)", method);
+    GU_REQUIRE(K >= 1 && K <= GU_LAMBDA_MAX, GU_ERR_INVALID, "K %d out of range (1 .. %d)", K, GU_LAMBDA_MAX);
+    GU_REQUIRE(lambda >= 0.0 && lambda <= 1.0, GU_ERR_INVALID, "lambda %g outside [0, 1]", lambda);
+    int rc = gu_tabular_check(h, "gu_lambda_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    if (!h->d_lambda_w) {
+        const size_t slots = (size_t)h->N * GU_LAMBDA_MAX;
+        GU_HIP(hipStreamSynchronize(h->stream));
+        GU_TRY(gu_tabular_fits(h, slots * sizeof(int32_t), "trace windows"));
+        GU_HIP(hipMalloc(&h->d_lambda_w, slots * sizeof(int32_t)));
+        h->lambda_key = 0;
+    }
+    return gu_launch_lambda(h, T, method, K, alpha, gamma, lambda, eps_q16, flags);
+}
+
+int gu_lambda_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_TRY(gu_env_range(h, env0, n));
+    GU_REQUIRE(sa != nullptr || n == 0, GU_ERR_INVALID, "sa is NULL");
+    const int32_t K = h->lambda_key ? (h->lambda_key - 1) / 2 : 0;  // (gu_lambda_key; 0: the window was dropped)
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (K) GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, sa, h->d_lambda_w, env0, n, GU_LAMBDA_MAX, false));
+    for (int64_t e = 0; e < n; ++e)  // (a dropped window reads as empty, whatever the device copy still holds; ages >= K are not written)
+        for (int32_t j = K; j < GU_LAMBDA_MAX; ++j) sa[(size_t)e * GU_LAMBDA_MAX + j] = -1;
+    return GU_OK;
+}
+
+}  // extern "C"

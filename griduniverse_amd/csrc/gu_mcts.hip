@@ -296,7 +296,7 @@ static int gu_mcts_launch(gu_engine *h, MctsArgs &a)
     return GU_OK;
 }
 
-int gu_launch_mcts(gu_engine *h, int64_t T, int32_t M, int32_t H, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
+static int gu_launch_mcts(gu_engine *h, int64_t T, int32_t M, int32_t H, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
                    uint32_t flags)
 {
     MctsArgs a{};
@@ -315,3 +315,120 @@ int gu_launch_mcts(gu_engine *h, int64_t T, int32_t M, int32_t H, int32_t D, dou
     const int rc = eps_sim_q16 == 65536u ? gu_mcts_launch<true>(h, a) : gu_mcts_launch<false>(h, a);
     return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
 }
+
+void gu_mcts_free(gu_engine *h)
+{
+    gu_release(h->d_mcts_pool, h->d_mcts_meta, h->d_mcts_nodes, h->d_mcts_steps);
+    h->mcts_P = 0;
+}
+
+#define GU_NEED_POOLS(h) GU_REQUIRE((h)->d_mcts_pool && (h)->mcts_P >= 2, GU_ERR_STATE, "no node pools: call gu_mcts_init first")
+
+extern "C" {
+
+int gu_mcts_init(gu_handle h, int32_t max_sims)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_REQUIRE(max_sims >= 1 && max_sims <= GU_MCTS_MAX_SIMS, GU_ERR_INVALID, "max_sims %d out of range (1 .. %d)", max_sims, GU_MCTS_MAX_SIMS);
+    const int32_t P = max_sims + 1;
+    const size_t nodes = (size_t)h->N * (size_t)P;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!h->d_mcts_pool || h->mcts_P != P) {
+        gu_mcts_free(h);
+        GU_TRY(gu_tabular_fits(h, nodes * 72 + (size_t)h->N * 12, "tree-search node pools"));
+        GU_HIP(hipMalloc(&h->d_mcts_pool, nodes * 64));
+        GU_HIP(hipMalloc(&h->d_mcts_meta, nodes * 8));
+        GU_HIP(hipMalloc(&h->d_mcts_nodes, (size_t)h->N * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_mcts_steps, (size_t)h->N * sizeof(int64_t)));
+        h->mcts_P = P;
+    }
+    GU_HIP(hipMemsetAsync(h->d_mcts_pool, 0, nodes * 64, h->stream));  // (root rows of zeros until an iteration has been searched)
+    GU_HIP(hipMemsetAsync(h->d_mcts_meta, 0xFF, nodes * 8, h->stream));
+    GU_HIP(hipMemsetAsync(h->d_mcts_nodes, 0, (size_t)h->N * sizeof(int32_t), h->stream));
+    GU_HIP(hipMemsetAsync(h->d_mcts_steps, 0, (size_t)h->N * sizeof(int64_t), h->stream));
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_mcts_set_tables(gu_handle h, int32_t C, const double *U, const double *B, const double *I)
+{
+    GU_ENTER(h);
+    const double *v[] = {U, B, I};
+    return gu_schedule_upload(h, h->d_mcts_tab, h->mcts_C, C, v, 3);
+}
+
+int gu_mcts_run(gu_handle h, int64_t T, int32_t M, int32_t H, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
+                uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_NEED_POOLS(h);
+    GU_REQUIRE(M >= 0 && M <= h->mcts_P - 1, GU_ERR_INVALID, "simulations %d out of range (0 .. %d, gu_mcts_init's max_sims)", M, h->mcts_P - 1);
+    GU_REQUIRE(H >= 1 && H <= GU_MCTS_MAX_DEPTH, GU_ERR_INVALID, "tree depth %d out of range (1 .. %d)", H, GU_MCTS_MAX_DEPTH);
+    GU_REQUIRE(D >= 0 && D <= GU_SEARCH_MAX_D, GU_ERR_INVALID, "depth %d out of range (0 .. %d)", D, GU_SEARCH_MAX_D);
+    GU_REQUIRE(eps_sim_q16 <= 65536u, GU_ERR_INVALID, "eps_sim_q16 %u above 65536", eps_sim_q16);
+    GU_REQUIRE(M == 0 || (h->d_mcts_tab && h->mcts_C >= 2), GU_ERR_STATE, "no tree-search tables: call gu_mcts_set_tables first");
+    GU_TRY(gu_tabular_check(h, "gu_mcts_run", T, -1, eps_q16, alpha, gamma, flags));
+    GU_TRY(gu_move_budget(T, 1 + (int64_t)M * (H + D), "1 + M (H + D)"));  // per real step, at most
+    if (T == 0) return GU_OK;
+    return gu_launch_mcts(h, T, M, H, D, alpha, gamma, eps_q16, eps_sim_q16, flags);
+}
+
+static int gu_mcts_range(gu_engine *h, int64_t env0, int64_t n)
+{
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_NEED_POOLS(h);
+    return gu_env_range(h, env0, n);
+}
+
+int gu_mcts_get(gu_handle h, int64_t env0, int64_t n, double *w, uint32_t *visits, int32_t *nodes, int64_t *sim_steps)
+{
+    GU_ENTER(h);
+    GU_TRY(gu_mcts_range(h, env0, n));
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!n) return GU_OK;
+    // the root is node 0 of each env's pool: its w row at byte 0, its visits row at byte 32
+    const size_t pitch = (size_t)h->mcts_P * 64;
+    const uint8_t *root = h->d_mcts_pool + (size_t)env0 * pitch;
+    if (w) GU_HIP(hipMemcpy2D(w, 32, root, pitch, 32, (size_t)n, hipMemcpyDeviceToHost));
+    if (visits) GU_HIP(hipMemcpy2D(visits, 16, root + 32, pitch, 16, (size_t)n, hipMemcpyDeviceToHost));
+    GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, nodes, h->d_mcts_nodes, env0, n, 1, false));
+    return gu_env_copy(h, hipMemcpyDeviceToHost, sim_steps, h->d_mcts_steps, env0, n, 1, false);
+}
+
+int gu_mcts_get_tree(gu_handle h, int64_t env0, int64_t n, int32_t *state, int32_t *parent, int32_t *child, uint32_t *visits, double *w,
+                     int32_t *count)
+{
+    GU_ENTER(h);
+    GU_TRY(gu_mcts_range(h, env0, n));
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!n) return GU_OK;
+    const size_t P = (size_t)h->mcts_P, k = (size_t)n * P;
+    std::vector<uint8_t> pool(k * 64);
+    std::vector<int32_t> meta(k * 2), cnt((size_t)n);
+    GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, pool.data(), h->d_mcts_pool, env0, n, P * 64, false));
+    GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, meta.data(), h->d_mcts_meta, env0, n, P * 2, false));
+    GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, cnt.data(), h->d_mcts_nodes, env0, n, 1, false));
+    for (size_t e = 0; e < (size_t)n; ++e) {
+        if (count) count[e] = cnt[e];
+        for (size_t v = 0; v < P; ++v) {
+            const size_t i = e * P + v;
+            const bool live = (int64_t)v < (int64_t)cnt[e];
+            const uint8_t *node = pool.data() + i * 64;
+            if (state) state[i] = live ? meta[i * 2] : -1;
+            if (parent) parent[i] = live ? meta[i * 2 + 1] : -1;
+            for (size_t b = 0; b < 4; ++b) {
+                if (w) w[i * 4 + b] = live ? reinterpret_cast<const double *>(node)[b] : 0.0;
+                if (visits) visits[i * 4 + b] = live ? reinterpret_cast<const uint32_t *>(node + 32)[b] : 0u;
+                if (child) child[i * 4 + b] = live ? reinterpret_cast<const int32_t *>(node + 48)[b] : -1;
+            }
+        }
+    }
+    return GU_OK;
+}
+
+}  // extern "C"

@@ -144,7 +144,10 @@ static int gu_nstep_launch_m(gu_engine *h, const NstepArgs &a)
     return a.n == 1 ? gu_nstep_launch_c<SARSA, 1>(h, a) : a.n <= 4 ? gu_nstep_launch_c<SARSA, 4>(h, a) : gu_nstep_launch_c<SARSA, GU_NSTEP_MAX>(h, a);
 }
 
-int gu_launch_nstep(gu_engine *h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+// the carry key of a gu_nstep_run (never 0): the next launch keeps the window only under the same method and n
+static inline int32_t gu_nstep_key(int32_t method, int32_t n) { return 1 + method + 2 * n; }
+
+static int gu_launch_nstep(gu_engine *h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
 {
     NstepArgs a{};
     gu_tabular_args(h, a, T, alpha, gamma, eps_q16, flags);
@@ -161,3 +164,58 @@ int gu_launch_nstep(gu_engine *h, int64_t T, int32_t method, int32_t n, double a
     h->nstep_key = key;
     return rc2;
 }
+
+void gu_nstep_free(gu_engine *h)
+{
+    gu_release(h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt);
+    h->nstep_key = 0;
+}
+
+extern "C" {
+
+int gu_nstep_run(gu_handle h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = n-step Q-learning, 1 = n-step SARSA", method);
+    GU_REQUIRE(n >= 1 && n <= GU_NSTEP_MAX, GU_ERR_INVALID, "n %d out of range (1 .. %d)", n, GU_NSTEP_MAX);
+    int rc = gu_tabular_check(h, "gu_nstep_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    if (!h->d_nstep_sa) {
+        const size_t slots = (size_t)h->N * GU_NSTEP_MAX;
+        GU_HIP(hipStreamSynchronize(h->stream));
+        GU_TRY(gu_tabular_fits(h, 2 * slots * sizeof(int32_t) + (size_t)h->N * sizeof(int32_t), "n-step windows"));
+        GU_HIP(hipMalloc(&h->d_nstep_sa, slots * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_nstep_r, slots * sizeof(int32_t)));
+        GU_HIP(hipMalloc(&h->d_nstep_cnt, (size_t)h->N * sizeof(int32_t)));
+        h->nstep_key = 0;
+    }
+    return gu_launch_nstep(h, T, method, n, alpha, gamma, eps_q16, flags);
+}
+
+int gu_nstep_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_TRY(gu_env_range(h, env0, n));
+    const size_t k = (size_t)n * GU_NSTEP_MAX;
+    std::vector<int32_t> c(n), w_sa(k), w_r(k);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (h->nstep_key) {  // (a dropped window reads as empty, whatever the device copy still holds)
+        GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, c.data(), h->d_nstep_cnt, env0, n, 1, false));
+        GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, w_sa.data(), h->d_nstep_sa, env0, n, GU_NSTEP_MAX, false));
+        GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, w_r.data(), h->d_nstep_r, env0, n, GU_NSTEP_MAX, false));
+    }
+    for (int64_t e = 0; e < n; ++e)
+        for (int32_t j = 0; j < GU_NSTEP_MAX; ++j) {
+            const size_t i = (size_t)e * GU_NSTEP_MAX + j;
+            if (sa) sa[i] = j < c[e] ? w_sa[i] : -1;
+            if (reward) reward[i] = j < c[e] ? w_r[i] : 0;
+        }
+    if (count)
+        for (int64_t e = 0; e < n; ++e) count[e] = c[e];
+    return GU_OK;
+}
+
+}  // extern "C"

@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_reinforce_kernel(const RfArgs a)
     L.ballot(a);
 }
 
-int gu_launch_reinforce(gu_engine *h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags)
+static int gu_launch_reinforce(gu_engine *h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags)
 {
     RfArgs a{};
     gu_tabular_args(h, a, T, alpha_actor, gamma, 0u, flags);
@@ -132,3 +132,35 @@ int gu_launch_reinforce(gu_engine *h, int64_t T, int32_t L, double alpha_actor, 
     h->rf_key = L;
     return rc2;
 }
+
+void gu_reinforce_free(gu_engine *h)
+{
+    gu_release(h->d_rf_buf, h->d_rf_cnt);
+    h->rf_cap = 0;
+    h->rf_key = 0;
+}
+
+extern "C" {
+
+int gu_reinforce_run(gu_handle h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_AC(h);
+    GU_REQUIRE(L >= 1 && L <= GU_REINFORCE_MAX, GU_ERR_INVALID, "L %d out of range (1 .. %d)", L, GU_REINFORCE_MAX);
+    GU_REQUIRE(std::isfinite(alpha_baseline), GU_ERR_INVALID, "alpha_baseline must be finite");
+    int rc = gu_tabular_check(h, "gu_reinforce_run", T, -1, 0u, alpha_actor, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    GU_TRY(gu_episode_reserve(h, h->d_rf_buf, h->d_rf_cnt, h->rf_cap, h->rf_key, L));
+    return gu_launch_reinforce(h, T, L, alpha_actor, alpha_baseline, gamma, flags);
+}
+
+int gu_reinforce_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t *reward, int32_t *count)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_TRY(gu_env_range(h, env0, n));
+    return gu_episode_read(h, h->d_rf_buf, h->d_rf_cnt, h->rf_key, GU_REINFORCE_MAX, env0, n, sa, reward, nullptr, false, count);
+}
+
+}  // extern "C"

@@ -179,7 +179,7 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_search_kernel(const SearchArgs a)
     L.ballot(a);
 }
 
-int gu_launch_search(gu_engine *h, int64_t T, int32_t M, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
+static int gu_launch_search(gu_engine *h, int64_t T, int32_t M, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
                      uint32_t flags)
 {
     SearchArgs a{};
@@ -193,3 +193,49 @@ int gu_launch_search(gu_engine *h, int64_t T, int32_t M, int32_t D, double alpha
                                          : gu_tabular_launch(h, gu_search_kernel<false, true>, gu_search_kernel<false, false>, a);
     return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
 }
+
+void gu_search_free(gu_engine *h) { gu_release(h->d_search_score, h->d_search_steps); }
+
+extern "C" {
+
+int gu_search_run(gu_handle h, int64_t T, int32_t M, int32_t D, double alpha, double gamma, uint32_t eps_q16, uint32_t eps_sim_q16,
+                  uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_REQUIRE(M >= 0 && M <= GU_SEARCH_MAX_M, GU_ERR_INVALID, "simulations %d out of range (0 .. %d)", M, GU_SEARCH_MAX_M);
+    GU_REQUIRE(D >= 0 && D <= GU_SEARCH_MAX_D, GU_ERR_INVALID, "depth %d out of range (0 .. %d)", D, GU_SEARCH_MAX_D);
+    GU_REQUIRE(eps_sim_q16 <= 65536u, GU_ERR_INVALID, "eps_sim_q16 %u above 65536", eps_sim_q16);
+    GU_TRY(gu_tabular_check(h, "gu_search_run", T, -1, eps_q16, alpha, gamma, flags));
+    GU_TRY(gu_move_budget(T, 1 + 4 * (int64_t)M * D, "1 + 4 M D"));  // per real step, at most
+    if (T == 0) return GU_OK;
+    if (!h->d_search_score) {
+        GU_HIP(hipStreamSynchronize(h->stream));
+        GU_TRY(gu_tabular_fits(h, (size_t)h->N * (4 * sizeof(double) + sizeof(int64_t)), "search scores"));
+        GU_HIP(hipMalloc(&h->d_search_score, (size_t)h->N * 4 * sizeof(double)));
+        GU_HIP(hipMalloc(&h->d_search_steps, (size_t)h->N * sizeof(int64_t)));
+        GU_HIP(hipMemsetAsync(h->d_search_score, 0, (size_t)h->N * 4 * sizeof(double), h->stream));
+        GU_HIP(hipMemsetAsync(h->d_search_steps, 0, (size_t)h->N * sizeof(int64_t), h->stream));
+    }
+    return gu_launch_search(h, T, M, D, alpha, gamma, eps_q16, eps_sim_q16, flags);
+}
+
+int gu_search_get(gu_handle h, int64_t env0, int64_t n, double *score, int64_t *sim_steps)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_TRY(gu_env_range(h, env0, n));
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (!n) return GU_OK;
+    if (!h->d_search_score) {  // (nothing searched yet: what the storage holds right after its allocation)
+        if (score) std::fill(score, score + (size_t)n * 4, 0.0);
+        if (sim_steps) std::fill(sim_steps, sim_steps + (size_t)n, (int64_t)0);
+        return GU_OK;
+    }
+    GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, score, h->d_search_score, env0, n, 4, false));
+    return gu_env_copy(h, hipMemcpyDeviceToHost, sim_steps, h->d_search_steps, env0, n, 1, false);
+}
+
+}  // extern "C"

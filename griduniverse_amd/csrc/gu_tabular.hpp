@@ -20,6 +20,8 @@
 #pragma once
 #include "gu_rollout.hpp"  // (gu_map.hpp, gu_blocks, gu_lds_block)
 
+#include <cmath>
+
 // ---- the fields both kernels read (gu_tabular_args fills them) ----
 struct TabArgs {
     const uint8_t *cell;
@@ -213,6 +215,152 @@ struct TabLane {
 };
 
 // ---- host side ----
+// What the learners' entry points share: gu_td.hip, gu_dyna.hip, gu_nstep.hip, gu_lambda.hip, gu_search.hip, gu_explore.hip,
+// gu_mcts.hip, gu_is.hip, gu_ac.hip, gu_reinforce.hip and gu_fa.hip each hold their own extern "C" functions and their gu_*_free;
+// the checks, copies and stores they have in common are here.
+
+// frees device buffers and forgets them (hipFree's status is not looked at)
+template <class... P>
+static inline void gu_release(P *&...p)
+{
+    ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...);
+}
+
+// the tables that more than one learner's entry points need, present and of this grid's size
+#define GU_NEED_Q(h) GU_REQUIRE((h)->d_q && (h)->td_S == (h)->S, GU_ERR_STATE, "no Q tables: call gu_td_init first")
+#define GU_NEED_AC(h) GU_REQUIRE((h)->d_ac_h && (h)->ac_S == (h)->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first")
+
+// tables of `bytes` for the engine's envs: what is left has to hold the trajectory buffer and the scratch of other calls too, so
+// keep 1 GiB of headroom
+static inline int gu_tabular_fits(gu_engine *h, size_t bytes, const char *what)
+{
+    size_t free_b = 0, total_b = 0;
+    GU_HIP(hipMemGetInfo(&free_b, &total_b));
+    GU_REQUIRE(bytes + ((size_t)1 << 30) <= free_b, GU_ERR_NOMEM, "%s of %lld envs x %d states need %.2f GiB, %.2f GiB are free", what,
+               (long long)h->N, h->S, bytes / 1073741824.0, free_b / 1073741824.0);
+    return GU_OK;
+}
+
+// the checks of a learner launch of T real steps; P < 0: one update per step, else gu_dyna_run (P + 1 per step)
+static inline int gu_tabular_check(gu_engine *h, const char *fn, int64_t T, int32_t P, uint32_t eps_q16, double alpha, double gamma, uint32_t flags)
+{
+    if (P < 0)
+        GU_REQUIRE(T >= 0 && T <= 100000000, GU_ERR_INVALID, "T %lld out of range (0 .. 1e8)", (long long)T);
+    else
+        GU_REQUIRE(T >= 0 && T <= 100000000 && T * (int64_t)(P + 1) <= 100000000, GU_ERR_INVALID,
+                   "T %lld x (P + 1) = %lld updates out of range (0 .. 1e8)", (long long)T, (long long)T * (P + 1));
+    GU_REQUIRE(eps_q16 <= 65536u, GU_ERR_INVALID, "eps_q16 %u above 65536", eps_q16);
+    GU_REQUIRE(std::isfinite(alpha) && std::isfinite(gamma), GU_ERR_INVALID, "alpha and gamma must be finite");
+    GU_REQUIRE((flags & ~(GU_F_TRAJECTORY | GU_F_STATS)) == 0, GU_ERR_INVALID, "%s accepts GU_F_TRAJECTORY and GU_F_STATS only (flags 0x%x)", fn, flags);
+    if (flags & GU_F_TRAJECTORY)
+        GU_REQUIRE(h->d_traj && T <= h->traj_T, GU_ERR_STATE, "trajectory buffer holds %lld rows, need %lld: call gu_reserve_trajectory",
+                   (long long)h->traj_T, (long long)T);
+    GU_REQUIRE(!h->trail_cap || (flags & GU_F_TRAJECTORY), GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): %s must write rows (GU_F_TRAJECTORY) to feed it", fn);
+    return GU_OK;
+}
+
+// the budget of a searching launch (gu_search_run, gu_mcts_run): T real steps of at most `moves` moves each, `formula` says which
+static inline int gu_move_budget(int64_t T, int64_t moves, const char *formula)
+{
+    GU_REQUIRE(T * moves <= 100000000, GU_ERR_INVALID, "T %lld x (%s) = %lld moves out of range (0 .. 1e8)", (long long)T, formula,
+               (long long)(T * moves));
+    return GU_OK;
+}
+
+static inline int gu_env_range(gu_engine *h, int64_t env0, int64_t n)
+{
+    GU_REQUIRE(env0 >= 0 && n >= 0 && env0 + n <= h->N, GU_ERR_INVALID, "envs [%lld, %lld) outside 0 .. %lld", (long long)env0,
+               (long long)(env0 + n), (long long)h->N);
+    return GU_OK;
+}
+
+// Envs env0 .. env0+n-1 of a device array of `row` elements per env, to the host (hipMemcpyDeviceToHost) or from it, behind everything
+// queued on the engine's stream (sync = false: the caller has waited already).  Copies nothing for n == 0 or a NULL host pointer.
+template <class T>
+static int gu_env_copy(gu_engine *h, hipMemcpyKind dir, const T *host, T *dev, int64_t env0, int64_t n, size_t row, bool sync = true)
+{
+    if (sync) GU_HIP(hipStreamSynchronize(h->stream));
+    if (!n || !host) return GU_OK;
+    T *at = dev + (size_t)env0 * row;
+    const size_t bytes = (size_t)n * row * sizeof(T);
+    if (dir == hipMemcpyDeviceToHost)
+        GU_HIP(hipMemcpy(const_cast<T *>(host), at, bytes, hipMemcpyDeviceToHost));
+    else
+        GU_HIP(hipMemcpy(at, host, bytes, hipMemcpyHostToDevice));
+    return GU_OK;
+}
+
+// ---- episode buffers (gu_reinforce.hip, gu_is.hip): step-major [cap][N] entries of 8 bytes {s*4+a, word} and [N] counts ----
+// storage for L entries per env, allocated on first use (a call with another L drops the buffer anyway: nothing to keep)
+static int gu_episode_reserve(gu_engine *h, int32_t *&buf, int32_t *&cnt, int32_t &cap, int32_t &key, int32_t L)
+{
+    if (cap >= L) return GU_OK;
+    const size_t slots = (size_t)h->N * (size_t)L;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    const int rc = gu_tabular_fits(h, slots * 2 * sizeof(int32_t) + (size_t)h->N * sizeof(int32_t), "episode buffers");
+    if (rc != GU_OK) return rc;
+    gu_release(buf, cnt);
+    cap = 0;
+    key = 0;
+    GU_HIP(hipMalloc(&buf, slots * 2 * sizeof(int32_t)));
+    GU_HIP(hipMalloc(&cnt, (size_t)h->N * sizeof(int32_t)));
+    cap = L;
+    return GU_OK;
+}
+
+// The buffers of envs env0 .. env0+n-1 as [n][pitch] rows, entries behind an env's count as -1 / 0.  L entries per env are live
+// (0: the buffer was dropped and reads as empty, whatever the device copy still holds).  The entry's word is the reward, or, `packed`,
+// reward * 8 + class.
+static int gu_episode_read(gu_engine *h, const int32_t *buf, const int32_t *cnt, int32_t L, int32_t pitch, int64_t env0, int64_t n,
+                           int32_t *sa, int32_t *reward, int32_t *cls, bool packed, int32_t *count)
+{
+    std::vector<int32_t> c(n), w((size_t)n * (size_t)L * 2);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (n && L) {
+        GU_HIP(hipMemcpy(c.data(), cnt + env0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+        GU_HIP(hipMemcpy2D(w.data(), (size_t)n * 8, buf + (size_t)env0 * 2, (size_t)h->N * 8, (size_t)n * 8, (size_t)L,
+                           hipMemcpyDeviceToHost));  // rows k = 0 .. L-1 of [L][N], columns env0 .. env0+n-1
+    }
+    for (int64_t e = 0; e < n; ++e)
+        for (int32_t j = 0; j < pitch; ++j) {
+            const size_t i = (size_t)e * pitch + j, b = ((size_t)j * n + e) * 2;
+            const bool live = j < c[e];
+            if (sa) sa[i] = live ? w[b] : -1;
+            if (reward) reward[i] = live ? (packed ? w[b + 1] >> 3 : w[b + 1]) : 0;
+            if (cls) cls[i] = live ? w[b + 1] & 7 : 0;
+        }
+    if (count)
+        for (int64_t e = 0; e < n; ++e) count[e] = c[e];
+    return GU_OK;
+}
+
+// ---- schedule tables (gu_explore_set_tables: U | B; gu_mcts_set_tables: U | B | I): nv vectors of C entries, one after the other
+// in one device array of whole 16-byte pieces (the LDS kernels stage it so), zero behind the last entry ----
+static int gu_schedule_upload(gu_engine *h, double *&tab, int32_t &tab_C, int32_t C, const double *const *v, int nv)
+{
+    GU_REQUIRE(C >= 2 && C <= GU_EXPLORE_MAX_C, GU_ERR_INVALID, "table size %d out of range (2 .. %d)", C, GU_EXPLORE_MAX_C);
+    GU_REQUIRE(v[0] != nullptr && v[1] != nullptr && (nv < 3 || v[2] != nullptr), GU_ERR_INVALID, "%s is NULL", nv < 3 ? "U or B" : "U, B or I");
+    for (int32_t k = 0; k < C; ++k) {
+        bool ok = true;
+        for (int i = 0; i < nv; ++i) ok = ok && std::isfinite(v[i][k]) && v[i][k] >= 0.0;
+        if (nv < 3)
+            GU_REQUIRE(ok, GU_ERR_INVALID, "entry %d (U %g, B %g): every entry must be finite and not negative", k, v[0][k], v[1][k]);
+        else
+            GU_REQUIRE(ok, GU_ERR_INVALID, "entry %d (U %g, B %g, I %g): every entry must be finite and not negative", k, v[0][k], v[1][k], v[2][k]);
+    }
+    GU_HIP(hipStreamSynchronize(h->stream));
+    if (tab_C != C) {
+        gu_release(tab);
+        tab_C = 0;
+        const size_t bytes = ((size_t)C * nv * sizeof(double) + 15) & ~(size_t)15;
+        GU_HIP(hipMalloc(&tab, bytes));
+        GU_HIP(hipMemset(tab, 0, bytes));
+        tab_C = C;
+    }
+    for (int i = 0; i < nv; ++i) GU_HIP(hipMemcpy(tab + (size_t)i * C, v[i], (size_t)C * sizeof(double), hipMemcpyHostToDevice));
+    return GU_OK;
+}
+
 static inline void gu_tabular_args(gu_engine *h, TabArgs &a, int64_t T, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
 {
     const bool traj = flags & GU_F_TRAJECTORY, stats = flags & GU_F_STATS;

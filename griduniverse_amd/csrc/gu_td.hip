@@ -52,7 +52,7 @@ __global__ void __launch_bounds__(256) gu_td_fill_kernel(double *__restrict__ q,
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) q[i] = v;
 }
 
-int gu_td_fill(gu_engine *h, double q0)
+static int gu_td_fill(gu_engine *h, double q0)  // every entry of every table = q0 (async)
 {
     const size_t n = (size_t)h->N * (size_t)h->td_S * 4;
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, (size_t)h->n_cu * 16);
@@ -61,7 +61,7 @@ int gu_td_fill(gu_engine *h, double q0)
     return GU_OK;
 }
 
-int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+static int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
 {
     TdArgs a{};
     gu_tabular_args(h, a, T, alpha, gamma, eps_q16, flags);
@@ -71,3 +71,93 @@ int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, double g
                                : gu_tabular_launch(h, gu_td_kernel<false, true>, gu_td_kernel<false, false>, a);
     return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, method == 1);
 }
+
+static void gu_td_free(gu_engine *h)
+{
+    gu_release(h->d_q, h->d_td_next);
+    h->td_S = 0;
+}
+
+void gu_learners_drop(gu_engine *h, int32_t S)
+{
+    const bool all = S == 0;
+    if (all || (h->td_S && h->td_S != S)) {  // Q tables of another state count belong to another grid: gu_td_init again
+        gu_td_free(h);
+        gu_nstep_free(h);
+        gu_lambda_free(h);
+        gu_search_free(h);
+        gu_mcts_free(h);  // (gu_mcts_init again)
+    }
+    if (all || (h->is_S && h->is_S != S)) gu_is_free(h);  // ... and the cumulative weights: gu_is_init again
+    if (all || (h->explore_S && h->explore_S != S)) gu_explore_free(h);  // ... and the visit counts: gu_explore_init again
+    if (all || (h->dyna_S && h->dyna_S != S)) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
+    if (all || (h->ac_S && h->ac_S != S)) gu_ac_free(h);  // ... and actor-critic tables (with the REINFORCE buffers): gu_ac_init again
+    if (all || (h->fa_S && h->fa_S != S)) gu_fa_free(h);  // ... and features and weights: gu_fa_init again
+    if (all) {  // the schedule tables outlive every grid
+        gu_release(h->d_explore_tab, h->d_mcts_tab);
+        h->explore_C = h->mcts_C = 0;
+    }
+}
+
+extern "C" {
+
+int gu_td_init(gu_handle h, double q0)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_REQUIRE(std::isfinite(q0), GU_ERR_INVALID, "q0 must be finite");
+    gu_tabular_drop_carry(h);
+    const size_t bytes = (size_t)h->N * (size_t)h->S * 4 * sizeof(double);
+    if (!h->d_q || h->td_S != h->S) {
+        GU_HIP(hipStreamSynchronize(h->stream));
+        gu_td_free(h);
+        int rc = gu_tabular_fits(h, bytes, "Q tables");
+        if (rc != GU_OK) return rc;
+        GU_HIP(hipMalloc(&h->d_q, bytes));
+        GU_HIP(hipMalloc(&h->d_td_next, (size_t)h->N));
+        h->td_S = h->S;
+    }
+    GU_HIP(hipMemsetAsync(h->d_td_next, 0xFF, (size_t)h->N, h->stream));
+    int rc = gu_td_fill(h, q0);
+    if (rc != GU_OK) return rc;
+    GU_HIP(hipStreamSynchronize(h->stream));
+    return GU_OK;
+}
+
+int gu_td_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Q-learning, 1 = SARSA", method);
+    int rc = gu_tabular_check(h, "gu_td_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    return gu_launch_td(h, T, method, alpha, gamma, eps_q16, flags);
+}
+
+static int gu_td_range(gu_engine *h, int64_t env0, int64_t n, const void *q)
+{
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    GU_REQUIRE(q != nullptr, GU_ERR_INVALID, "q is NULL");
+    return gu_env_range(h, env0, n);
+}
+
+int gu_td_get_q(gu_handle h, int64_t env0, int64_t n, double *q)
+{
+    GU_ENTER(h);
+    int rc = gu_td_range(h, env0, n, q);
+    if (rc != GU_OK) return rc;
+    return gu_env_copy(h, hipMemcpyDeviceToHost, q, h->d_q, env0, n, (size_t)h->S * 4);
+}
+
+int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q)
+{
+    GU_ENTER(h);
+    int rc = gu_td_range(h, env0, n, q);
+    if (rc != GU_OK) return rc;
+    gu_tabular_drop_carry(h);
+    return gu_env_copy(h, hipMemcpyHostToDevice, q, h->d_q, env0, n, (size_t)h->S * 4);
+}
+
+}  // extern "C"

@@ -23,6 +23,15 @@ def _learner_flags(trajectory, stats):
     return (_lib.F_TRAJECTORY if trajectory else 0) | (_lib.F_STATS if stats else 0)
 
 
+def _tables(x, row, name, dtype=np.float64):
+    """`x` as a contiguous `dtype` array [n, *row]; an array of shape `row` is the table of one env."""
+    x = np.asarray(x, dtype)
+    x = _lib.as_array(x.reshape((-1,) + row) if x.ndim == len(row) else x, dtype, None, name)
+    if x.ndim != len(row) + 1 or x.shape[1:] != row:
+        raise ValueError('{} must have shape (n, {}), got {}'.format(name, ', '.join(str(k) for k in row), x.shape))
+    return x
+
+
 class Engine(object):
     def __init__(self, num_envs, spec, device=0, env_id0=0, seed=0):
         if not isinstance(spec, GridSpec):
@@ -313,6 +322,12 @@ class Engine(object):
         check(self.lib.gu_read_stats(self._h, ptr(ret), ptr(eps)))
         return ret, eps
 
+    def _env_range(self, env0, n):
+        """env0 and n as the library takes them (n None: all from env0), and the rows of the result."""
+        env0 = int(env0)
+        n = self.N - env0 if n is None else int(n)
+        return env0, n, max(n, 0)
+
     # ------------------------------------------------------------------ tabular TD control (include/gu.h: gu_td_*)
     def td_init(self, q0=0.0):
         """One float64 Q table [S][4] per env, every entry q0."""
@@ -326,17 +341,14 @@ class Engine(object):
 
     def td_get_q(self, env0=0, n=None):
         """float64[n, S, 4]: the tables of envs env0 .. env0+n-1 (all from env0 when n is None)."""
-        n = self.N - int(env0) if n is None else int(n)
-        q = np.empty((max(n, 0), self.spec.S, 4), np.float64)
-        check(self.lib.gu_td_get_q(self._h, int(env0), n, ptr(q)))
+        env0, n, n0 = self._env_range(env0, n)
+        q = np.empty((n0, self.spec.S, 4), np.float64)
+        check(self.lib.gu_td_get_q(self._h, env0, n, ptr(q)))
         return q
 
     def td_set_q(self, q, env0=0):
         """Install tables float64[n, S, 4] (or [S, 4] for one env) for envs env0 .. env0+n-1."""
-        q = np.asarray(q, np.float64)
-        q = _lib.as_array(q.reshape((-1, self.spec.S, 4)) if q.ndim == 2 else q, np.float64, None, 'q')
-        if q.ndim != 3 or q.shape[1:] != (self.spec.S, 4):
-            raise ValueError('q must have shape (n, {}, 4), got {}'.format(self.spec.S, q.shape))
+        q = _tables(q, (self.spec.S, 4), 'q')
         check(self.lib.gu_td_set_q(self._h, int(env0), q.shape[0], ptr(q)))
 
     # ------------------------------------------------------------------ tabular Dyna-Q (include/gu.h: gu_dyna_*)
@@ -353,11 +365,11 @@ class Engine(object):
     def dyna_get_model(self, env0=0, n=None):
         """The models of envs env0 .. env0+n-1: dict next / reward / done int32[n, S, 4] (unobserved: -1 / 0 / 0),
         list int32[n, 4S] (observed pairs s*4+a in first-observation order, -1 beyond count) and count int32[n]."""
-        n = self.N - int(env0) if n is None else int(n)
-        n0, S = max(n, 0), self.spec.S
+        env0, n, n0 = self._env_range(env0, n)
+        S = self.spec.S
         out = dict(next=np.empty((n0, S, 4), np.int32), reward=np.empty((n0, S, 4), np.int32), done=np.empty((n0, S, 4), np.int32),
                    list=np.empty((n0, 4 * S), np.int32), count=np.empty(n0, np.int32))
-        check(self.lib.gu_dyna_get_model(self._h, int(env0), n, ptr(out['next']), ptr(out['reward']), ptr(out['done']),
+        check(self.lib.gu_dyna_get_model(self._h, env0, n, ptr(out['next']), ptr(out['reward']), ptr(out['done']),
                                          ptr(out['list']), ptr(out['count'])))
         return out
 
@@ -374,10 +386,9 @@ class Engine(object):
     def search_get(self, env0=0, n=None):
         """Of envs env0 .. env0+n-1: dict score float64[n, 4] (the summed returns per action of the env's most recent searched
         step; zeros until there is one) and sim_steps int64[n] (simulated moves of the last launch)."""
-        n = self.N - int(env0) if n is None else int(n)
-        n0 = max(n, 0)
+        env0, n, n0 = self._env_range(env0, n)
         out = dict(score=np.empty((n0, 4), np.float64), sim_steps=np.empty(n0, np.int64))
-        check(self.lib.gu_search_get(self._h, int(env0), n, ptr(out['score']), ptr(out['sim_steps'])))
+        check(self.lib.gu_search_get(self._h, env0, n, ptr(out['score']), ptr(out['sim_steps'])))
         return out
 
     # ------------------------------------------------------------------ count-based exploration (include/gu.h: gu_explore_*)
@@ -402,9 +413,9 @@ class Engine(object):
 
     def explore_get_counts(self, env0=0, n=None):
         """uint32[n, S, 4]: the visit counts of envs env0 .. env0+n-1 (all from env0 when n is None)."""
-        n = self.N - int(env0) if n is None else int(n)
-        c = np.empty((max(n, 0), self.spec.S, 4), np.uint32)
-        check(self.lib.gu_explore_get_counts(self._h, int(env0), n, ptr(c)))
+        env0, n, n0 = self._env_range(env0, n)
+        c = np.empty((n0, self.spec.S, 4), np.uint32)
+        check(self.lib.gu_explore_get_counts(self._h, env0, n, ptr(c)))
         return c
 
     def explore_set_counts(self, counts, env0=0):
@@ -412,10 +423,7 @@ class Engine(object):
         c = np.asarray(counts)
         if c.size and (c.min() < 0 or c.max() > 0xFFFFFFFF):
             raise ValueError('counts must fit uint32')
-        c = c.astype(np.uint32)
-        c = np.ascontiguousarray(c.reshape((-1, self.spec.S, 4)) if c.ndim == 2 else c)
-        if c.ndim != 3 or c.shape[1:] != (self.spec.S, 4):
-            raise ValueError('counts must have shape (n, {}, 4), got {}'.format(self.spec.S, c.shape))
+        c = _tables(c.astype(np.uint32), (self.spec.S, 4), 'counts', np.uint32)
         check(self.lib.gu_explore_set_counts(self._h, int(env0), c.shape[0], ptr(c)))
 
     # ------------------------------------------------------------------ Monte-Carlo tree search at decision time (include/gu.h: gu_mcts_*)
@@ -447,22 +455,21 @@ class Engine(object):
         """Of envs env0 .. env0+n-1, from each env's most recent searched step: dict w float64[n, 4] and visits uint32[n, 4] (the
         root's return sums and visit counts; zeros until there is one), nodes int32[n] (the nodes of that tree) and sim_steps
         int64[n] (simulated moves of the last launch)."""
-        n = self.N - int(env0) if n is None else int(n)
-        n0 = max(n, 0)
+        env0, n, n0 = self._env_range(env0, n)
         out = dict(w=np.empty((n0, 4), np.float64), visits=np.empty((n0, 4), np.uint32), nodes=np.empty(n0, np.int32),
                    sim_steps=np.empty(n0, np.int64))
-        check(self.lib.gu_mcts_get(self._h, int(env0), n, ptr(out['w']), ptr(out['visits']), ptr(out['nodes']), ptr(out['sim_steps'])))
+        check(self.lib.gu_mcts_get(self._h, env0, n, ptr(out['w']), ptr(out['visits']), ptr(out['nodes']), ptr(out['sim_steps'])))
         return out
 
     def mcts_tree(self, env0=0, n=None):
         """The whole tree of each env's most recent searched step, P = max_sims + 1 node slots per env in order of creation: dict
         state int32[n, P], parent int32[n, P] (parent * 4 + action; -1 for the root), child int32[n, P, 4] (-1 = none), visits
         uint32[n, P, 4], w float64[n, P, 4] and count int32[n]; slots beyond count hold -1 / -1 / -1 / 0 / 0.0."""
-        n = self.N - int(env0) if n is None else int(n)
-        n0, P = max(n, 0), getattr(self, '_mcts_nodes', 0)
+        env0, n, n0 = self._env_range(env0, n)
+        P = getattr(self, '_mcts_nodes', 0)
         out = dict(state=np.empty((n0, P), np.int32), parent=np.empty((n0, P), np.int32), child=np.empty((n0, P, 4), np.int32),
                    visits=np.empty((n0, P, 4), np.uint32), w=np.empty((n0, P, 4), np.float64), count=np.empty(n0, np.int32))
-        check(self.lib.gu_mcts_get_tree(self._h, int(env0), n, ptr(out['state']), ptr(out['parent']), ptr(out['child']), ptr(out['visits']),
+        check(self.lib.gu_mcts_get_tree(self._h, env0, n, ptr(out['state']), ptr(out['parent']), ptr(out['child']), ptr(out['visits']),
                                         ptr(out['w']), ptr(out['count'])))
         return out
 
@@ -477,11 +484,10 @@ class Engine(object):
     def nstep_get_window(self, env0=0, n=None):
         """The windows of envs env0 .. env0+n-1: dict sa / reward int32[n, NSTEP_MAX] (pending s*4+a and r, oldest first;
         -1 / 0 beyond count) and count int32[n] (0 once dropped)."""
-        n = self.N - int(env0) if n is None else int(n)
-        n0 = max(n, 0)
+        env0, n, n0 = self._env_range(env0, n)
         out = dict(sa=np.empty((n0, _lib.NSTEP_MAX), np.int32), reward=np.empty((n0, _lib.NSTEP_MAX), np.int32),
                    count=np.empty(n0, np.int32))
-        check(self.lib.gu_nstep_get_window(self._h, int(env0), n, ptr(out['sa']), ptr(out['reward']), ptr(out['count'])))
+        check(self.lib.gu_nstep_get_window(self._h, env0, n, ptr(out['sa']), ptr(out['reward']), ptr(out['count'])))
         return out
 
     # ------------------------------------------------------------------ tabular SARSA(lambda) / Watkins's Q(lambda) (include/gu.h: gu_lambda_*)
@@ -495,9 +501,9 @@ class Engine(object):
     def lambda_get_window(self, env0=0, n=None):
         """int32[n, LAMBDA_MAX]: the trace windows of envs env0 .. env0+n-1, index = age (the pair s*4+a, -1 for none; all -1
         once dropped)."""
-        n = self.N - int(env0) if n is None else int(n)
-        sa = np.empty((max(n, 0), _lib.LAMBDA_MAX), np.int32)
-        check(self.lib.gu_lambda_get_window(self._h, int(env0), n, ptr(sa)))
+        env0, n, n0 = self._env_range(env0, n)
+        sa = np.empty((n0, _lib.LAMBDA_MAX), np.int32)
+        check(self.lib.gu_lambda_get_window(self._h, env0, n, ptr(sa)))
         return sa
 
     # ------------------------------------------------------------------ tabular softmax actor-critic (include/gu.h: gu_ac_*)
@@ -513,10 +519,10 @@ class Engine(object):
 
     def ac_get(self, env0=0, n=None):
         """(preferences float64[n, S, 4], values float64[n, S]) of envs env0 .. env0+n-1 (all from env0 when n is None)."""
-        n = self.N - int(env0) if n is None else int(n)
+        env0, n, n0 = self._env_range(env0, n)
         S = self.spec.S
-        h, v = np.empty((max(n, 0), S, 4), np.float64), np.empty((max(n, 0), S), np.float64)
-        check(self.lib.gu_ac_get(self._h, int(env0), n, ptr(h), ptr(v)))
+        h, v = np.empty((n0, S, 4), np.float64), np.empty((n0, S), np.float64)
+        check(self.lib.gu_ac_get(self._h, env0, n, ptr(h), ptr(v)))
         return h, v
 
     def ac_set(self, h=None, v=None, env0=0):
@@ -524,16 +530,10 @@ class Engine(object):
         are given they must cover the same envs."""
         S, n = self.spec.S, None
         if h is not None:
-            h = np.asarray(h, np.float64)
-            h = _lib.as_array(h.reshape((-1, S, 4)) if h.ndim == 2 else h, np.float64, None, 'h')
-            if h.ndim != 3 or h.shape[1:] != (S, 4):
-                raise ValueError('h must have shape (n, {}, 4), got {}'.format(S, h.shape))
+            h = _tables(h, (S, 4), 'h')
             n = h.shape[0]
         if v is not None:
-            v = np.asarray(v, np.float64)
-            v = _lib.as_array(v.reshape((-1, S)) if v.ndim == 1 else v, np.float64, None, 'v')
-            if v.ndim != 2 or v.shape[1] != S:
-                raise ValueError('v must have shape (n, {}), got {}'.format(S, v.shape))
+            v = _tables(v, (S,), 'v')
             if n is not None and v.shape[0] != n:
                 raise ValueError('h and v cover {} and {} envs'.format(n, v.shape[0]))
             n = v.shape[0]
@@ -552,11 +552,10 @@ class Engine(object):
     def reinforce_get_episode(self, env0=0, n=None):
         """The episode buffers of envs env0 .. env0+n-1: dict sa / reward int32[n, REINFORCE_MAX] (pending s*4+a and r, oldest
         first; -1 / 0 beyond count) and count int32[n] (0 once dropped)."""
-        n = self.N - int(env0) if n is None else int(n)
-        n0 = max(n, 0)
+        env0, n, n0 = self._env_range(env0, n)
         out = dict(sa=np.empty((n0, _lib.REINFORCE_MAX), np.int32), reward=np.empty((n0, _lib.REINFORCE_MAX), np.int32),
                    count=np.empty(n0, np.int32))
-        check(self.lib.gu_reinforce_get_episode(self._h, int(env0), n, ptr(out['sa']), ptr(out['reward']), ptr(out['count'])))
+        check(self.lib.gu_reinforce_get_episode(self._h, env0, n, ptr(out['sa']), ptr(out['reward']), ptr(out['count'])))
         return out
 
     # ------------------------------------------------------------------ off-policy Monte-Carlo control, weighted importance sampling (include/gu.h: gu_is_*)
@@ -574,28 +573,23 @@ class Engine(object):
 
     def is_get(self, env0=0, n=None):
         """float64[n, S, 4]: the cumulative weights of envs env0 .. env0+n-1 (all from env0 when n is None)."""
-        n = self.N - int(env0) if n is None else int(n)
-        c = np.empty((max(n, 0), self.spec.S, 4), np.float64)
-        check(self.lib.gu_is_get(self._h, int(env0), n, ptr(c)))
+        env0, n, n0 = self._env_range(env0, n)
+        c = np.empty((n0, self.spec.S, 4), np.float64)
+        check(self.lib.gu_is_get(self._h, env0, n, ptr(c)))
         return c
 
     def is_set(self, c, env0=0):
         """Install cumulative weights float64[n, S, 4] (or [S, 4] for one env) for envs env0 .. env0+n-1: finite, not negative."""
-        S = self.spec.S
-        c = np.asarray(c, np.float64)
-        c = _lib.as_array(c.reshape((-1, S, 4)) if c.ndim == 2 else c, np.float64, None, 'c')
-        if c.ndim != 3 or c.shape[1:] != (S, 4):
-            raise ValueError('c must have shape (n, {}, 4), got {}'.format(S, c.shape))
+        c = _tables(c, (self.spec.S, 4), 'c')
         check(self.lib.gu_is_set(self._h, int(env0), c.shape[0], ptr(c)))
 
     def is_get_episode(self, env0=0, n=None):
         """The episode buffers of envs env0 .. env0+n-1: dict sa / reward / cls int32[n, IS_MAX] (pending s*4+a, r and the class
         of the action, oldest first; -1 / 0 / 0 beyond count) and count int32[n] (0 once dropped)."""
-        n = self.N - int(env0) if n is None else int(n)
-        n0 = max(n, 0)
+        env0, n, n0 = self._env_range(env0, n)
         out = dict(sa=np.empty((n0, _lib.IS_MAX), np.int32), reward=np.empty((n0, _lib.IS_MAX), np.int32),
                    cls=np.empty((n0, _lib.IS_MAX), np.int32), count=np.empty(n0, np.int32))
-        check(self.lib.gu_is_get_episode(self._h, int(env0), n, ptr(out['sa']), ptr(out['reward']), ptr(out['cls']), ptr(out['count'])))
+        check(self.lib.gu_is_get_episode(self._h, env0, n, ptr(out['sa']), ptr(out['reward']), ptr(out['cls']), ptr(out['count'])))
         return out
 
     # ------------------------------------------------------------------ semi-gradient SARSA / Q-learning on features (include/gu.h: gu_fa_*)
@@ -628,25 +622,21 @@ class Engine(object):
 
     def fa_get_w(self, env0=0, n=None):
         """float64[n, F, 4]: the weights of envs env0 .. env0+n-1 (all from env0 when n is None)."""
-        n = self.N - int(env0) if n is None else int(n)
-        w = np.empty((max(n, 0), self._fa_features(), 4), np.float64)
-        check(self.lib.gu_fa_get_w(self._h, int(env0), n, ptr(w)))
+        env0, n, n0 = self._env_range(env0, n)
+        w = np.empty((n0, self._fa_features(), 4), np.float64)
+        check(self.lib.gu_fa_get_w(self._h, env0, n, ptr(w)))
         return w
 
     def fa_set_w(self, w, env0=0):
         """Install weights float64[n, F, 4] (or [F, 4] for one env) for envs env0 .. env0+n-1."""
-        F = self._fa_features()
-        w = np.asarray(w, np.float64)
-        w = _lib.as_array(w.reshape((-1, F, 4)) if w.ndim == 2 else w, np.float64, None, 'w')
-        if w.ndim != 3 or w.shape[1:] != (F, 4):
-            raise ValueError('w must have shape (n, {}, 4), got {}'.format(F, w.shape))
+        w = _tables(w, (self._fa_features(), 4), 'w')
         check(self.lib.gu_fa_set_w(self._h, int(env0), w.shape[0], ptr(w)))
 
     def fa_get_q(self, env0=0, n=None):
         """float64[n, S, 4]: the action values of envs env0 .. env0+n-1, folded from the weights on the device."""
-        n = self.N - int(env0) if n is None else int(n)
-        q = np.empty((max(n, 0), self.spec.S, 4), np.float64)
-        check(self.lib.gu_fa_get_q(self._h, int(env0), n, ptr(q)))
+        env0, n, n0 = self._env_range(env0, n)
+        q = np.empty((n0, self.spec.S, 4), np.float64)
+        check(self.lib.gu_fa_get_q(self._h, env0, n, ptr(q)))
         return q
 
     # ------------------------------------------------------------------ state
@@ -815,9 +805,9 @@ class Engine(object):
         """uint8[n, K, K] ('ego', K = 2 * radius + 1) or uint8[n, H, W] ('grid'): what envs env0 .. env0+n-1 (to the end when n is
         None) see from where they stand (include/gu.h: gu_sense)."""
         m, r = check_sense_args(radius, mode)
-        n = self.N - int(env0) if n is None else int(n)
-        out = np.empty((max(n, 0),) + self._view_shape(m, r), np.uint8)
-        check(self.lib.gu_sense(self._h, int(env0), n, m, r, ptr(out)))
+        env0, n, n0 = self._env_range(env0, n)
+        out = np.empty((n0,) + self._view_shape(m, r), np.uint8)
+        check(self.lib.gu_sense(self._h, env0, n, m, r, ptr(out)))
         return out
 
     def sense_trajectory(self, t0, T, radius=1, mode='ego', chunk_bytes=256 << 20):
