@@ -382,6 +382,13 @@ int gu_ensure_scratch(gu_engine *h, size_t bytes);
 
 #define GU_NEED_GRID(h) GU_REQUIRE((h)->has_grid, GU_ERR_STATE, "no grid set: call gu_set_grid first")
 
+// frees device buffers and forgets them (hipFree's status is not looked at)
+template <class... P>
+static inline void gu_release(P *&...p)
+{
+    ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...);
+}
+
 // ---- options (gu_options.hip) ----------------------------------------------------
 // The value in force for `option`: the engine's own, else the process default, else the built-in one.  A few loads; called
 // per launch.  (A -DGU_EXPERIMENTS build also consults the environment variable of the same name on every call, for the
@@ -448,14 +455,10 @@ struct GuXcdPlan {
     int block = 0, K = 0, NB = 1;  // threads per workgroup, states per thread at most, 16-byte exchange loads per thread (1 or 4)
     unsigned G = 0;            // workgroups
     uint32_t values = 0;       // doubles of a workgroup's value window in LDS
-    size_t lds = 0, slots_bytes = 0, work_bytes = 0;  // dynamic LDS; scratch: delta-key slots (all XCCs), granule buffers (per XCC)
+    size_t lds = 0, slots_bytes = 0, work_bytes = 0;  // dynamic LDS; the launches' own buffers: delta-key slots (all XCCs), granule buffers (per XCC)
 };
-struct ViStepXcdArgs;
 #define GU_VI_FALLBACK 1  /* internal: a one-launch DP form did not apply or gave up, the tables are as they were -- take the next form */
 bool gu_vi_xcd_plan(const gu_engine *h, bool agents, GuXcdPlan *plan);
-int gu_vi_xcd_launch(gu_engine *h, const GuXcdPlan &plan, const ViStepXcdArgs &a, bool agents, bool greedy);
-int gu_vi_xcd_buffers(gu_engine *h, const GuXcdPlan &xp);  // the per-XCD launches' own buffers, wiped when they must be
-uint32_t gu_vi_xcd_tag0(const gu_engine *h);                // the launch's number, where its tags carry it
 void gu_vi_xcd_free(gu_engine *h);
 int gu_vi_xcd_fused_run(gu_engine *h, const GuXcdPlan &xp, double gamma, int32_t iters, uint32_t flags, double *deltas);
 int gu_vi_xcd_dp_run(gu_engine *h, double gamma, double threshold, bool use_threshold, bool greedy, int32_t max_rounds, int32_t *rounds_done,

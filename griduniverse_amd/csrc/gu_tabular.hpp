@@ -219,13 +219,6 @@ struct TabLane {
 // gu_mcts.hip, gu_is.hip, gu_ac.hip, gu_reinforce.hip and gu_fa.hip each hold their own extern "C" functions and their gu_*_free;
 // the checks, copies and stores they have in common are here.
 
-// frees device buffers and forgets them (hipFree's status is not looked at)
-template <class... P>
-static inline void gu_release(P *&...p)
-{
-    ((p ? (void)hipFree(p) : (void)0, p = nullptr), ...);
-}
-
 // the tables that more than one learner's entry points need, present and of this grid's size
 #define GU_NEED_Q(h) GU_REQUIRE((h)->d_q && (h)->td_S == (h)->S, GU_ERR_STATE, "no Q tables: call gu_td_init first")
 #define GU_NEED_AC(h) GU_REQUIRE((h)->d_ac_h && (h)->ac_S == (h)->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first")

@@ -602,15 +602,7 @@ int gu_vi_alloc(gu_engine *h)
 
 void gu_vi_free(gu_engine *h)
 {
-    for (int k = 0; k < 2; ++k) {
-        if (h->d_v[k]) (void)hipFree(h->d_v[k]);
-        if (h->d_pi[k]) (void)hipFree(h->d_pi[k]);
-        h->d_v[k] = h->d_pi[k] = nullptr;
-    }
-    if (h->d_pi_thr) (void)hipFree(h->d_pi_thr);
-    h->d_pi_thr = nullptr;
-    if (h->d_delta) (void)hipFree(h->d_delta);
-    h->d_delta = nullptr;
+    gu_release(h->d_v[0], h->d_pi[0], h->d_v[1], h->d_pi[1], h->d_pi_thr, h->d_delta);
     gu_vi_xcd_free(h);
     h->has_vi = false;
     h->greedy_valid = false;
@@ -624,12 +616,32 @@ int gu_launch_greedy_table(gu_engine *h)
     return GU_OK;
 }
 
-static double vi_unkey(unsigned long long k)
+#define GU_NEED_VI(h) GU_REQUIRE((h)->has_vi, GU_ERR_STATE, "no value/policy tables: call gu_vi_set first")
+
+// A call that may write the tables withdraws the host's copy of them (gu_vi_xcd.hip: h_tables); the per-XCD launch of the tables
+// alone renews it.
+static inline void vi_withdraw_host_tables(gu_engine *h) { h->h_tables_valid = false; }
+
+// One launch of a per-round kernel, one lane per state or env: the instantiation that stages the cell planes in LDS where they
+// fit, else the one that reads them from L2.
+template <class A>
+static void vi_launch_round(gu_engine *h, void (*lds)(const A), void (*l2)(const A), int64_t lanes, const A &a)
 {
-    unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-    double x;
-    memcpy(&x, &b, sizeof x);
-    return x;
+    const dim3 grid(vi_blocks(lanes)), block(VI_BLOCK);
+    if (h->S <= GU_MAX_LDS_CELLS)
+        hipLaunchKernelGGL(lds, grid, block, 2 * (size_t)h->cell_bytes, h->stream, a);
+    else
+        hipLaunchKernelGGL(l2, grid, block, 0, h->stream, a);
+}
+
+// the deltas of the first n rounds of a one-launch form, from its keys on the device (the launch has been waited for)
+static int vi_fetch_deltas(const unsigned long long *keys_d, int32_t n, double *deltas)
+{
+    if (!deltas || n <= 0) return GU_OK;
+    std::vector<unsigned long long> keys((size_t)n);
+    GU_HIP(hipMemcpy(keys.data(), keys_d, keys.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    vi_unkey_n(keys.data(), keys.size(), deltas);
+    return GU_OK;
 }
 
 static ViArgs vi_args(gu_engine *h, double gamma, unsigned long long *delta_key)
@@ -659,9 +671,8 @@ static ViArgs vi_args(gu_engine *h, double gamma, unsigned long long *delta_key)
 // hundred at 32x32, against 46 and 240 of the single-workgroup kernel (profiles/archive/r04z_dp_calls.txt).  It is taken first on every
 // grid it fits; the other paths are what it falls back to (a grid that does not fit a workgroup's LDS, workgroups that cannot all
 // be resident, GU_OPT_VI_PATH).
-static bool vi_xcd_preferred(const gu_engine *h, int32_t rounds)
+static bool vi_xcd_preferred(const gu_engine *h)
 {
-    (void)rounds;
     const int64_t path = gu_opt(h, GU_OPT_VI_PATH);
     return path == 0 || path == 5 || path == 6;
 }
@@ -677,8 +688,7 @@ static int vi_block_run(gu_engine *h, double gamma, double threshold, bool use_t
     *rounds_done = 0;
     if (max_rounds <= 0) return GU_OK;
     const size_t key_bytes = (size_t)max_rounds * sizeof(unsigned long long);
-    int rc = gu_ensure_scratch(h, key_bytes + 16);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_ensure_scratch(h, key_bytes + 16));
     unsigned long long *keys_d = (unsigned long long *)h->d_scratch;
     int32_t *done_d = (int32_t *)((char *)h->d_scratch + key_bytes);
     ViBlockArgs a{h->d_cell, h->cell_bytes, h->W, h->S, gamma, threshold, h->d_v[h->vi_cur], h->d_pi[h->vi_cur], keys_d, done_d,
@@ -700,15 +710,8 @@ static int vi_block_run(gu_engine *h, double gamma, double threshold, bool use_t
     hipLaunchKernelGGL(kern, dim3(1), dim3(VI_PB_THREADS), smem, h->stream, a);
     GU_HIP(hipGetLastError());
     int32_t done = 0;
-    {
-        const int rb = gu_read_back(h, &done, done_d, sizeof done);
-        if (rb != GU_OK) return rb;
-    }
-    if (deltas && done > 0) {
-        std::vector<unsigned long long> keys((size_t)done);
-        GU_HIP(hipMemcpy(keys.data(), keys_d, (size_t)done * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (int32_t i = 0; i < done; ++i) deltas[i] = vi_unkey(keys[(size_t)i]);
-    }
+    GU_TRY(gu_read_back(h, &done, done_d, sizeof done));
+    GU_TRY(vi_fetch_deltas(keys_d, done, deltas));
     *rounds_done = done;
     h->greedy_valid = false;
     return GU_OK;
@@ -751,8 +754,7 @@ static int vi_cluster_run(gu_engine *h, double gamma, double threshold, bool use
     const size_t snap_off = (16 + key_bytes + 15) & ~(size_t)15;
     const size_t v_bytes = (size_t)h->S * sizeof(double);
     const size_t total = snap_off + 5 * v_bytes;
-    int rc = gu_ensure_scratch(h, total);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_ensure_scratch(h, total));
     uint32_t *sync_d = (uint32_t *)h->d_scratch;
     int32_t *done_d = (int32_t *)h->d_scratch + 2;
     unsigned long long *keys_d = (unsigned long long *)((char *)h->d_scratch + 16);
@@ -761,8 +763,8 @@ static int vi_cluster_run(gu_engine *h, double gamma, double threshold, bool use
     // A barrier that times out (the workgroups were not resident together: another process on the device, a CU mask) leaves v
     // written halfway through a round and the policy rows of some states updated: the launch works on a snapshot's ORIGINAL,
     // and a timeout restores it (40 bytes per state, device to device) and hands the loop to the one-launch-per-round path.
-    if ((rc = gu_device_copy(h, snap, h->d_v[h->vi_cur], v_bytes)) != GU_OK) return rc;
-    if ((rc = gu_device_copy(h, snap + v_bytes, h->d_pi[h->vi_cur], 4 * v_bytes)) != GU_OK) return rc;
+    GU_TRY(gu_device_copy(h, snap, h->d_v[h->vi_cur], v_bytes));
+    GU_TRY(gu_device_copy(h, snap + v_bytes, h->d_pi[h->vi_cur], 4 * v_bytes));
     if (gu_opt(h, GU_OPT_VI_PATH) == 3) GU_HIP(hipMemsetD32Async((hipDeviceptr_t)(sync_d + 1), 1, 1, h->stream));  // tests: an injected timeout
     ViClusterArgs a{h->d_cell, h->cell_bytes, h->W, h->S, gamma, threshold, h->d_v[h->vi_cur], h->d_v[h->vi_cur ^ 1],
                     h->d_pi[h->vi_cur], keys_d, sync_d, done_d, max_rounds, use_threshold ? 1 : 0};
@@ -781,45 +783,55 @@ static int vi_cluster_run(gu_engine *h, double gamma, double threshold, bool use
     // rounds_done is written by ONE workgroup, and a timeout need not be unanimous (the workgroup that arrives last finds the
     // counter complete and goes on while the others have given up): the timeout word, raised by whoever gives up, decides.
     int32_t ctl[4] = {0, 0, 0, 0};  // [arrival counter, timeout word, rounds_done, pad]
-    {
-        const int rb = gu_read_back(h, ctl, h->d_scratch, sizeof ctl);
-        if (rb != GU_OK) return rb;
-    }
+    GU_TRY(gu_read_back(h, ctl, h->d_scratch, sizeof ctl));
     const int32_t done = ctl[1] ? -1 : ctl[2];
     if (done < 0) {
-        if ((rc = gu_device_copy(h, h->d_v[h->vi_cur], snap, v_bytes)) != GU_OK) return rc;
-        if ((rc = gu_device_copy(h, h->d_pi[h->vi_cur], snap + v_bytes, 4 * v_bytes)) != GU_OK) return rc;
+        GU_TRY(gu_device_copy(h, h->d_v[h->vi_cur], snap, v_bytes));
+        GU_TRY(gu_device_copy(h, h->d_pi[h->vi_cur], snap + v_bytes, 4 * v_bytes));
         GU_HIP(hipStreamSynchronize(h->stream));
         if (gu_debug()) fprintf(stderr, "[gu] DP cluster kernel: grid barrier timed out (%u workgroups not resident together); tables restored, one launch per round instead\n", G);
         return GU_VI_FALLBACK;
     }
-    if (deltas && done > 0) {
-        std::vector<unsigned long long> keys((size_t)done);
-        GU_HIP(hipMemcpy(keys.data(), keys_d, (size_t)done * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (int32_t i = 0; i < done; ++i) deltas[i] = vi_unkey(keys[(size_t)i]);
-    }
-    if (done & 1) {  // the value table ended in the other buffer; the policy stayed where it was
-        double *t = h->d_v[0];
-        h->d_v[0] = h->d_v[1];
-        h->d_v[1] = t;
-    }
+    GU_TRY(vi_fetch_deltas(keys_d, done, deltas));
+    if (done & 1) std::swap(h->d_v[0], h->d_v[1]);  // the value table ended in the other buffer; the policy stayed where it was
     *rounds_done = done;
     h->greedy_valid = false;
     return GU_OK;
+}
+
+// The one-launch forms of gu_vi_sweep / gu_vi_run / gu_vi_eval_run, fastest first: one XCD's workgroups, one workgroup, the
+// chip-wide cluster.  A form that does not apply or gives up leaves the tables as they were and hands on to the next one;
+// GU_VI_FALLBACK: none of them took the call, the caller runs its own one launch per round.
+static int vi_dp_run(gu_engine *h, double gamma, double threshold, bool use_threshold, bool greedy, int32_t max_rounds,
+                     int32_t *rounds_done, double *deltas)
+{
+    if (vi_xcd_preferred(h)) {  // one launch of one XCD's workgroups, nothing leaves that XCD's L2 (gu_vi_xcd.hip)
+        const int rc = gu_vi_xcd_dp_run(h, gamma, threshold, use_threshold, greedy, max_rounds, rounds_done, deltas);
+        h->vi_dp_form = 1;
+        if (rc != GU_VI_FALLBACK) return rc;
+    }
+    if (vi_block_eligible(h)) {
+        h->vi_dp_form = 2;
+        return vi_block_run(h, gamma, threshold, use_threshold, greedy, max_rounds, rounds_done, deltas);
+    }
+    if (vi_cluster_eligible(h)) {
+        const int rc = vi_cluster_run(h, gamma, threshold, use_threshold, greedy, max_rounds, rounds_done, deltas);
+        h->vi_dp_form = 3;
+        if (rc != GU_VI_FALLBACK) return rc;
+    }
+    return GU_VI_FALLBACK;
 }
 
 extern "C" {
 
 int gu_vi_set(gu_handle h, const double *v, const double *pi)
 {
-    int rc = gu_use_device(h);
-    if (rc != GU_OK) return rc;
-    h->h_tables_valid = false;  // (the call may write the tables: the host's copy of them, gu_vi_xcd.hip, is withdrawn; the per-XCD launch of the tables alone renews it)
-    GU_REQUIRE(h->has_grid, GU_ERR_STATE, "no grid set: call gu_set_grid first");
+    GU_ENTER(h);
+    vi_withdraw_host_tables(h);
+    GU_NEED_GRID(h);
     GU_REQUIRE(h->n_grids == 1, GU_ERR_UNSUPPORTED, "value / policy tables need a single-grid engine");
     GU_REQUIRE(v && pi, GU_ERR_INVALID, "v or pi is NULL");
-    rc = gu_vi_alloc(h);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_vi_alloc(h));
     const size_t vb = (size_t)h->S * sizeof(double);
     if (h->h_up && 5 * vb <= GU_UP_BYTES) {
         // through the page-locked staging area: two DMAs the stream orders in front of whatever is launched next, no wait (36 -> ~8 us
@@ -831,7 +843,7 @@ int gu_vi_set(gu_handle h, const double *v, const double *pi)
         GuSegments up;  // ONE launch reads both tables out of the page-locked area (it is mapped into the device's address space)
         up.add(h->d_v[h->vi_cur], h->h_up, vb);
         up.add(h->d_pi[h->vi_cur], h->h_up + vb, 4 * vb);
-        if ((rc = gu_device_segments(h, up)) != GU_OK) return rc;
+        GU_TRY(gu_device_segments(h, up));
     } else {
         GU_HIP(hipStreamSynchronize(h->stream));
         GU_HIP(hipMemcpy(h->d_v[h->vi_cur], v, vb, hipMemcpyHostToDevice));
@@ -844,9 +856,8 @@ int gu_vi_set(gu_handle h, const double *v, const double *pi)
 
 int gu_vi_get(gu_handle h, double *v, double *pi)
 {
-    int rc = gu_use_device(h);
-    if (rc != GU_OK) return rc;
-    GU_REQUIRE(h->has_vi, GU_ERR_STATE, "no value/policy tables: call gu_vi_set first");
+    GU_ENTER(h);
+    GU_NEED_VI(h);
     const size_t vb = (size_t)h->S * sizeof(double);
     if (h->h_tables_valid && h->h_tables) {  // the launch that wrote the tables last left a copy on the host (and has been waited for)
         if (v) memcpy(v, h->h_tables, vb);
@@ -858,100 +869,58 @@ int gu_vi_get(gu_handle h, double *v, double *pi)
         GuSegments down;  // ONE launch writes both tables into the page-locked landing area, one wait
         down.add(land, h->d_v[h->vi_cur], vb);
         down.add(land + vb, h->d_pi[h->vi_cur], 4 * vb);
-        if ((rc = gu_device_segments(h, down)) != GU_OK) return rc;
+        GU_TRY(gu_device_segments(h, down));
         GU_HIP(hipStreamSynchronize(h->stream));
         memcpy(v, land, vb);
         memcpy(pi, land + vb, 4 * vb);
         return GU_OK;
     }
-    if (v && (rc = gu_read_back(h, v, h->d_v[h->vi_cur], vb)) != GU_OK) return rc;
-    if (pi && (rc = gu_read_back(h, pi, h->d_pi[h->vi_cur], 4 * vb)) != GU_OK) return rc;
+    if (v) GU_TRY(gu_read_back(h, v, h->d_v[h->vi_cur], vb));
+    if (pi) GU_TRY(gu_read_back(h, pi, h->d_pi[h->vi_cur], 4 * vb));
     if (!v && !pi) GU_HIP(hipStreamSynchronize(h->stream));
     return GU_OK;
 }
 
 int gu_vi_sweep(gu_handle h, double gamma, int32_t iters, int32_t greedy_update, double *deltas)
 {
-    int rc = gu_use_device(h);
-    if (rc != GU_OK) return rc;
-    h->h_tables_valid = false;  // (the call may write the tables: the host's copy of them, gu_vi_xcd.hip, is withdrawn; the per-XCD launch of the tables alone renews it)
-    GU_REQUIRE(h->has_vi, GU_ERR_STATE, "no value/policy tables: call gu_vi_set first");
+    GU_ENTER(h);
+    vi_withdraw_host_tables(h);
+    GU_NEED_VI(h);
     GU_REQUIRE(iters > 0 && iters <= 4096, GU_ERR_INVALID, "iters must be in 1..4096 per call");
-    if (vi_xcd_preferred(h, iters)) {  // one launch of one XCD's workgroups, nothing leaves that XCD's L2 (gu_vi_xcd.hip)
-        int32_t done = 0;
-        rc = gu_vi_xcd_dp_run(h, gamma, 0.0, false, greedy_update != 0, iters, &done, deltas);
-        h->vi_dp_form = 1;
-        if (rc != GU_VI_FALLBACK) return rc;
-    }
-    if (vi_block_eligible(h)) {
-        int32_t done = 0;
-        h->vi_dp_form = 2;
-        return vi_block_run(h, gamma, 0.0, false, greedy_update != 0, iters, &done, deltas);
-    }
-    if (vi_cluster_eligible(h)) {
-        int32_t done = 0;
-        rc = vi_cluster_run(h, gamma, 0.0, false, greedy_update != 0, iters, &done, deltas);
-        h->vi_dp_form = 3;
-        if (rc != GU_VI_FALLBACK) return rc;
-    }
+    int32_t done = 0;
+    const int rc = vi_dp_run(h, gamma, 0.0, false, greedy_update != 0, iters, &done, deltas);
+    if (rc != GU_VI_FALLBACK) return rc;
     h->vi_dp_form = 4;
     GU_HIP(hipMemsetAsync(h->d_delta, 0, (size_t)iters * sizeof(unsigned long long), h->stream));
-    const dim3 grid(vi_blocks(h->S)), block(VI_BLOCK);
-    const bool lds = h->S <= GU_MAX_LDS_CELLS;
-    const size_t smem = lds ? 2 * (size_t)h->cell_bytes : 0;
     for (int32_t i = 0; i < iters; ++i) {
-        ViArgs a = vi_args(h, gamma, (unsigned long long *)h->d_delta + i);
+        const ViArgs a = vi_args(h, gamma, (unsigned long long *)h->d_delta + i);
         if (greedy_update) {
-            if (lds) hipLaunchKernelGGL(gu_vi_round_kernel<true>, grid, block, smem, h->stream, a);
-            else hipLaunchKernelGGL(gu_vi_round_kernel<false>, grid, block, 0, h->stream, a);
+            vi_launch_round(h, gu_vi_round_kernel<true>, gu_vi_round_kernel<false>, h->S, a);
             h->vi_cur ^= 1;  // both tables advanced
         } else {
-            if (lds) hipLaunchKernelGGL(gu_vi_eval_kernel<true>, grid, block, smem, h->stream, a);
-            else hipLaunchKernelGGL(gu_vi_eval_kernel<false>, grid, block, 0, h->stream, a);
-            // policy unchanged: only v advances; keep pi where it is by swapping v buffers only
-            double *t = h->d_v[0];
-            h->d_v[0] = h->d_v[1];
-            h->d_v[1] = t;
+            vi_launch_round(h, gu_vi_eval_kernel<true>, gu_vi_eval_kernel<false>, h->S, a);
+            std::swap(h->d_v[0], h->d_v[1]);  // policy unchanged: only v advances; pi stays where it is
         }
     }
     GU_HIP(hipGetLastError());
     h->greedy_valid = false;
     if (deltas) {
         std::vector<unsigned long long> keys((size_t)iters);
-        {
-            const int rb = gu_read_back(h, keys.data(), h->d_delta, (size_t)iters * sizeof(unsigned long long));
-            if (rb != GU_OK) return rb;
-        }
-        for (int32_t i = 0; i < iters; ++i) deltas[i] = vi_unkey(keys[(size_t)i]);
+        GU_TRY(gu_read_back(h, keys.data(), h->d_delta, keys.size() * sizeof(unsigned long long)));
+        vi_unkey_n(keys.data(), keys.size(), deltas);
     }
     return GU_OK;
 }
 
 int gu_vi_run(gu_handle h, double gamma, double threshold, int32_t max_steps, int32_t *steps_done, double *deltas)
 {
-    int rc = gu_use_device(h);
-    if (rc != GU_OK) return rc;
-    h->h_tables_valid = false;  // (the call may write the tables: the host's copy of them, gu_vi_xcd.hip, is withdrawn; the per-XCD launch of the tables alone renews it)
-    GU_REQUIRE(h->has_vi, GU_ERR_STATE, "no value/policy tables: call gu_vi_set first");
+    GU_ENTER(h);
+    vi_withdraw_host_tables(h);
+    GU_NEED_VI(h);
     GU_REQUIRE(max_steps >= 0 && steps_done, GU_ERR_INVALID, "max_steps < 0 or steps_done is NULL");
-    if (vi_xcd_preferred(h, max_steps)) {
-        rc = gu_vi_xcd_dp_run(h, gamma, threshold, true, true, max_steps, steps_done, deltas);
-        h->vi_dp_form = 1;
-        if (rc != GU_VI_FALLBACK) return rc;
-    }
-    if (vi_block_eligible(h)) {
-        h->vi_dp_form = 2;
-        return vi_block_run(h, gamma, threshold, true, true, max_steps, steps_done, deltas);
-    }
-    if (vi_cluster_eligible(h)) {
-        rc = vi_cluster_run(h, gamma, threshold, true, true, max_steps, steps_done, deltas);
-        h->vi_dp_form = 3;
-        if (rc != GU_VI_FALLBACK) return rc;
-    }
+    const int rc = vi_dp_run(h, gamma, threshold, true, true, max_steps, steps_done, deltas);
+    if (rc != GU_VI_FALLBACK) return rc;
     h->vi_dp_form = 4;
-    const dim3 grid(vi_blocks(h->S)), block(VI_BLOCK);
-    const bool lds = h->S <= GU_MAX_LDS_CELLS;
-    const size_t smem = lds ? 2 * (size_t)h->cell_bytes : 0;
     int32_t *ctl = (int32_t *)(h->d_delta + 4000);  // past the delta slots a batch uses
     GU_HIP(hipMemsetAsync(ctl, 0, 8, h->stream));
     int32_t done_total = 0, stop = 0;
@@ -972,22 +941,17 @@ int gu_vi_run(gu_handle h, double gamma, double threshold, int32_t max_steps, in
             a.ctl = ctl;
             a.prev_delta_key = i ? (const unsigned long long *)h->d_delta + i - 1 : nullptr;  // the host checked the last batch
             a.threshold = threshold;
-            if (lds) hipLaunchKernelGGL(gu_vi_round_kernel<true>, grid, block, smem, h->stream, a);
-            else hipLaunchKernelGGL(gu_vi_round_kernel<false>, grid, block, 0, h->stream, a);
+            vi_launch_round(h, gu_vi_round_kernel<true>, gu_vi_round_kernel<false>, h->S, a);
         }
         return GU_OK;
     };
     std::vector<unsigned long long> keys(VI_RUN_BATCH);
     for (int32_t base = 0; base < max_steps && !stop; base += VI_RUN_BATCH) {
         const int32_t n = max_steps - base < VI_RUN_BATCH ? max_steps - base : VI_RUN_BATCH;
-        rc = enqueue(n);
-        if (rc != GU_OK) return rc;
+        GU_TRY(enqueue(n));
         h->vi_cur ^= n & 1;
         GU_HIP(hipGetLastError());
-        {
-            const int rb = gu_read_back(h, keys.data(), h->d_delta, (size_t)n * sizeof(unsigned long long));
-            if (rb != GU_OK) return rb;
-        }
+        GU_TRY(gu_read_back(h, keys.data(), h->d_delta, (size_t)n * sizeof(unsigned long long)));
         // rounds of this batch that ran: up to and including the first one whose delta met the threshold (:22-23)
         for (int32_t i = 0; i < n && !stop; ++i) {
             const double delta = vi_unkey(keys[(size_t)i]);
@@ -1004,30 +968,14 @@ int gu_vi_run(gu_handle h, double gamma, double threshold, int32_t max_steps, in
 
 int gu_vi_eval_run(gu_handle h, double gamma, double threshold, int32_t max_steps, int32_t *steps_done, double *deltas)
 {
-    int rc = gu_use_device(h);
-    if (rc != GU_OK) return rc;
-    h->h_tables_valid = false;  // (the call may write the tables: the host's copy of them, gu_vi_xcd.hip, is withdrawn; the per-XCD launch of the tables alone renews it)
-    GU_REQUIRE(h->has_vi, GU_ERR_STATE, "no value/policy tables: call gu_vi_set first");
+    GU_ENTER(h);
+    vi_withdraw_host_tables(h);
+    GU_NEED_VI(h);
     GU_REQUIRE(max_steps >= 0 && steps_done, GU_ERR_INVALID, "max_steps < 0 or steps_done is NULL");
-    if (vi_xcd_preferred(h, max_steps)) {
-        rc = gu_vi_xcd_dp_run(h, gamma, threshold, true, false, max_steps, steps_done, deltas);
-        h->vi_dp_form = 1;
-        if (rc != GU_VI_FALLBACK) return rc;
-    }
-    if (vi_block_eligible(h)) {
-        h->vi_dp_form = 2;
-        return vi_block_run(h, gamma, threshold, true, false, max_steps, steps_done, deltas);
-    }
-    if (vi_cluster_eligible(h)) {
-        rc = vi_cluster_run(h, gamma, threshold, true, false, max_steps, steps_done, deltas);
-        h->vi_dp_form = 3;
-        if (rc != GU_VI_FALLBACK) return rc;
-    }
+    const int rc = vi_dp_run(h, gamma, threshold, true, false, max_steps, steps_done, deltas);
+    if (rc != GU_VI_FALLBACK) return rc;
     h->vi_dp_form = 4;
     // larger grids: one evaluation launch per sweep, the host looks at the deltas once per batch
-    const dim3 grid(vi_blocks(h->S)), block(VI_BLOCK);
-    const bool lds = h->S <= GU_MAX_LDS_CELLS;
-    const size_t smem = lds ? 2 * (size_t)h->cell_bytes : 0;
     std::vector<unsigned long long> keys(VI_RUN_BATCH);
     int32_t done_total = 0;
     bool stop = false;
@@ -1035,28 +983,20 @@ int gu_vi_eval_run(gu_handle h, double gamma, double threshold, int32_t max_step
         // a sweep past the converged one would change v: snapshot v, queue one batch, find the first converged sweep,
         // and if the batch overshot it restore the snapshot and replay exactly that many sweeps
         const int32_t n = std::min<int32_t>(VI_RUN_BATCH, max_steps - done_total);
-        rc = gu_ensure_scratch(h, (size_t)h->S * sizeof(double));
-        if (rc != GU_OK) return rc;
+        GU_TRY(gu_ensure_scratch(h, (size_t)h->S * sizeof(double)));
         GU_HIP(hipMemcpyAsync(h->d_scratch, h->d_v[h->vi_cur], (size_t)h->S * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         auto sweeps = [&](int32_t count) {
             GU_HIP(hipMemsetAsync(h->d_delta, 0, (size_t)count * sizeof(unsigned long long), h->stream));
             for (int32_t i = 0; i < count; ++i) {
-                ViArgs a = vi_args(h, gamma, (unsigned long long *)h->d_delta + i);
-                if (lds) hipLaunchKernelGGL(gu_vi_eval_kernel<true>, grid, block, smem, h->stream, a);
-                else hipLaunchKernelGGL(gu_vi_eval_kernel<false>, grid, block, 0, h->stream, a);
-                double *t = h->d_v[0];  // policy unchanged: only v advances
-                h->d_v[0] = h->d_v[1];
-                h->d_v[1] = t;
+                const ViArgs a = vi_args(h, gamma, (unsigned long long *)h->d_delta + i);
+                vi_launch_round(h, gu_vi_eval_kernel<true>, gu_vi_eval_kernel<false>, h->S, a);
+                std::swap(h->d_v[0], h->d_v[1]);  // policy unchanged: only v advances
             }
             GU_HIP(hipGetLastError());
             return GU_OK;
         };
-        rc = sweeps(n);
-        if (rc != GU_OK) return rc;
-        {
-            const int rb = gu_read_back(h, keys.data(), h->d_delta, (size_t)n * sizeof(unsigned long long));
-            if (rb != GU_OK) return rb;
-        }
+        GU_TRY(sweeps(n));
+        GU_TRY(gu_read_back(h, keys.data(), h->d_delta, (size_t)n * sizeof(unsigned long long)));
         int32_t ran = n;
         for (int32_t i = 0; i < n; ++i) {
             const double delta = vi_unkey(keys[(size_t)i]);
@@ -1069,8 +1009,7 @@ int gu_vi_eval_run(gu_handle h, double gamma, double threshold, int32_t max_step
         }
         if (ran < n) {  // overshot: back to the snapshot, replay the sweeps up to the converged one
             GU_HIP(hipMemcpyAsync(h->d_v[h->vi_cur], h->d_scratch, (size_t)h->S * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            rc = sweeps(ran);
-            if (rc != GU_OK) return rc;
+            GU_TRY(sweeps(ran));
         }
         done_total += ran;
     }
@@ -1081,54 +1020,31 @@ int gu_vi_eval_run(gu_handle h, double gamma, double threshold, int32_t max_step
 
 int gu_vi_greedy(gu_handle h, double gamma)
 {
-    int rc = gu_use_device(h);
-    if (rc != GU_OK) return rc;
-    h->h_tables_valid = false;  // (the call may write the tables: the host's copy of them, gu_vi_xcd.hip, is withdrawn; the per-XCD launch of the tables alone renews it)
-    GU_REQUIRE(h->has_vi, GU_ERR_STATE, "no value/policy tables: call gu_vi_set first");
+    GU_ENTER(h);
+    vi_withdraw_host_tables(h);
+    GU_NEED_VI(h);
     ViArgs a = vi_args(h, gamma, nullptr);
     a.v_new = h->d_v[h->vi_cur];  // V2 reads the CURRENT value table ...
-    const dim3 grid(vi_blocks(h->S)), block(VI_BLOCK);
-    if (h->S <= GU_MAX_LDS_CELLS)
-        hipLaunchKernelGGL(gu_vi_greedy_kernel<true>, grid, block, 2 * (size_t)h->cell_bytes, h->stream, a);
-    else
-        hipLaunchKernelGGL(gu_vi_greedy_kernel<false>, grid, block, 0, h->stream, a);
+    vi_launch_round(h, gu_vi_greedy_kernel<true>, gu_vi_greedy_kernel<false>, h->S, a);
     GU_HIP(hipGetLastError());
-    double *t = h->d_pi[0];  // ... and only the policy table advances
-    h->d_pi[0] = h->d_pi[1];
-    h->d_pi[1] = t;
+    std::swap(h->d_pi[0], h->d_pi[1]);  // ... and only the policy table advances
     h->greedy_valid = false;
     return GU_OK;
 }
 
 int gu_vi_sweep_step(gu_handle h, double gamma, uint32_t flags, double *delta)
 {
-    int rc = gu_use_device(h);
-    if (rc != GU_OK) return rc;
-    h->h_tables_valid = false;  // (the call may write the tables: the host's copy of them, gu_vi_xcd.hip, is withdrawn; the per-XCD launch of the tables alone renews it)
+    GU_ENTER(h);
+    vi_withdraw_host_tables(h);
     h->entry_table_ok = false;  // (the fused launches step the envs: their state is consistent too, but only rollouts vouch for it)
-    GU_REQUIRE(h->has_vi, GU_ERR_STATE, "no value/policy tables: call gu_vi_set first");
+    GU_NEED_VI(h);
     GU_REQUIRE((flags & ~GU_F_AUTO_RESET) == 0, GU_ERR_INVALID, "gu_vi_sweep_step accepts only GU_F_AUTO_RESET");
     GU_REQUIRE(!h->trail_cap, GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): the fused sweep + step launches do not feed it");
     GU_HIP(hipMemsetAsync(h->d_delta, 0, sizeof(unsigned long long), h->stream));
     ViStepArgs a{};
     a.vi = vi_args(h, gamma, (unsigned long long *)h->d_delta);
-    a.pos = h->pos();
-    a.reward = h->reward();
-    a.done = h->done();
-    a.episode = h->d_episode;
-    a.starts = h->d_starts;
-    a.n_starts = (uint32_t)h->n_starts;
-    a.seed_prefix = h->seed_prefix;
-    a.env_id0 = (uint32_t)h->env_id0;
-    a.N = h->N;
-    a.flags = flags;
-    a.done_bits = h->d_done_bits;
-    const int64_t threads = h->N > h->S ? h->N : h->S;
-    const dim3 grid(vi_blocks(threads)), block(VI_BLOCK);
-    if (h->S <= GU_MAX_LDS_CELLS)
-        hipLaunchKernelGGL(gu_vi_sweep_step_kernel<true>, grid, block, 2 * (size_t)h->cell_bytes, h->stream, a);
-    else
-        hipLaunchKernelGGL(gu_vi_sweep_step_kernel<false>, grid, block, 0, h->stream, a);
+    vi_env_args(h, flags, a);
+    vi_launch_round(h, gu_vi_sweep_step_kernel<true>, gu_vi_sweep_step_kernel<false>, h->N > h->S ? h->N : (int64_t)h->S, a);
     GU_HIP(hipGetLastError());
     h->vi_cur ^= 1;
     h->greedy_valid = false;
@@ -1136,7 +1052,7 @@ int gu_vi_sweep_step(gu_handle h, double gamma, uint32_t flags, double *delta)
     gu_tabular_drop_carry(h);
     if (delta) {
         unsigned long long key = 0;
-        if ((rc = gu_read_back(h, &key, h->d_delta, sizeof key)) != GU_OK) return rc;
+        GU_TRY(gu_read_back(h, &key, h->d_delta, sizeof key));
         *delta = vi_unkey(key);
     }
     return GU_OK;
@@ -1144,11 +1060,10 @@ int gu_vi_sweep_step(gu_handle h, double gamma, uint32_t flags, double *delta)
 
 int gu_vi_sweep_step_run(gu_handle h, double gamma, int32_t iters, uint32_t flags, double *deltas)
 {
-    int rc = gu_use_device(h);
-    if (rc != GU_OK) return rc;
-    h->h_tables_valid = false;  // (the call may write the tables: the host's copy of them, gu_vi_xcd.hip, is withdrawn; the per-XCD launch of the tables alone renews it)
+    GU_ENTER(h);
+    vi_withdraw_host_tables(h);
     h->entry_table_ok = false;
-    GU_REQUIRE(h->has_vi, GU_ERR_STATE, "no value/policy tables: call gu_vi_set first");
+    GU_NEED_VI(h);
     GU_REQUIRE((flags & ~GU_F_AUTO_RESET) == 0, GU_ERR_INVALID, "gu_vi_sweep_step_run accepts only GU_F_AUTO_RESET");
     GU_REQUIRE(!h->trail_cap, GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): the fused sweep + step launches do not feed it");
     GU_REQUIRE(iters > 0 && iters <= 1000000, GU_ERR_INVALID, "iters must be in 1..1000000");
@@ -1156,8 +1071,8 @@ int gu_vi_sweep_step_run(gu_handle h, double gamma, int32_t iters, uint32_t flag
     const int64_t G = (threads + VI_CL_THREADS - 1) / VI_CL_THREADS;
     const int64_t path = gu_opt(h, GU_OPT_VI_PATH);
     // Three forms, fastest first: ONE launch synchronised per XCD (gu_vi_xcd.hip), ONE launch with a chip-wide barrier per round,
-    // one launch per round.  The one-launch forms work on a snapshot's ORIGINAL: a form that gives up (every spin in them is bounded)
-    // leaves half-advanced state, which is put back before the next form runs.
+    // one launch per round.  A one-launch form that gives up (every spin in them is bounded) leaves everything as it was for the
+    // next form: the per-XCD one writes its results beside the state, the chip-wide one works on a snapshot's ORIGINAL.
     GuXcdPlan xp{};
     // (a call of ONE round: the one-launch forms cost ~10 us more to start -- the registration wait, the snapshot, the zeroed
     // exchange buffers -- than they save; profiles/archive/r04z_c5_forms.json, xcd_default_us_per_call_by_rounds.  GU_OPT_VI_PATH = 6: always)
@@ -1166,106 +1081,63 @@ int gu_vi_sweep_step_run(gu_handle h, double gamma, int32_t iters, uint32_t flag
     const bool try_cluster = h->n_grids == 1 && h->S <= GU_MAX_LDS_CELLS && G <= (h->n_cu < VI_CL_MAX_WGS ? h->n_cu : VI_CL_MAX_WGS) &&
                              !short_call && (path == 0 || path == 3 || path == 4 || path == 5 || path == 6);
     if (try_xcd) {  // ONE launch per up to 4096 rounds, results into the other halves of the double buffers (gu_vi_xcd.hip)
-        rc = gu_vi_xcd_fused_run(h, xp, gamma, iters, flags, deltas);
+        const int rc = gu_vi_xcd_fused_run(h, xp, gamma, iters, flags, deltas);
         if (rc == GU_OK) h->vi_run_form = 1;
         if (rc != GU_VI_FALLBACK) return rc;
     }
     if (try_cluster) {
-        // scratch: header (64 B) | delta keys [iters] | delta-key slots of the per-XCD form | snapshot | the per-XCD granule buffers
+        // scratch: header (64 B) | delta keys [iters] | snapshot
         const size_t key_bytes = (size_t)iters * sizeof(unsigned long long);
-        const size_t slots_off = (64 + key_bytes + 255) & ~(size_t)255;
-        const size_t snap_off = slots_off + (try_xcd ? xp.slots_bytes : 0);
+        const size_t snap_off = (64 + key_bytes + 255) & ~(size_t)255;
         const size_t v_bytes = (size_t)h->S * sizeof(double), n4 = (size_t)h->N * 4, bits_bytes = (((size_t)h->N + 63) / 64) * 8;
         const size_t snap_bytes = (5 * v_bytes + 4 * n4 + bits_bytes + 255) & ~(size_t)255;
-        rc = gu_ensure_scratch(h, snap_off + snap_bytes + (try_xcd ? 8 * xp.work_bytes : 0));
-        if (rc != GU_OK) return rc;
+        GU_TRY(gu_ensure_scratch(h, snap_off + snap_bytes));
         uint32_t *hdr_d = (uint32_t *)h->d_scratch;
         int32_t *done_d = (int32_t *)h->d_scratch + 2;
         unsigned long long *keys_d = (unsigned long long *)((char *)h->d_scratch + 64);
         char *snap = (char *)h->d_scratch + snap_off;
-        // what a form that gives up would leave half-advanced -- tables, positions, rewards, done flags and their ballots,
+        // what a launch that gives up would leave half-advanced -- tables, positions, rewards, done flags and their ballots,
         // episode counters -- is snapshot first (device to device)
         void *live[5] = {h->d_v[h->vi_cur], h->d_pi[h->vi_cur], h->d_out3, h->d_episode, h->d_done_bits};
         const size_t size[5] = {v_bytes, 4 * v_bytes, 3 * n4, n4, bits_bytes};
+        // ONE launch: the snapshot, and every polled word zeroed
+        GuSegments seg;
         size_t off = 0;
-        bool snapped = false;
-        for (int form = 1; form < 2; ++form) {  // (0: per XCD -- handled above since round 5), 1: chip-wide
-            if (!try_cluster) continue;
-            // ONE launch: the snapshot (first form tried only), every polled word zeroed (before every launch), and for the per-XCD
-            // form its exchange buffers zeroed -- every word that crosses workgroups there is tagged with its round, no tag of an
-            // earlier launch may be left
-            GuSegments seg;
-            off = 0;
-            for (int k = 0; k < 5 && !snapped; off += size[k], ++k) seg.add(snap + off, live[k], size[k]);
-            snapped = true;
-            seg.add(h->d_scratch, nullptr, form == 0 ? snap_off : slots_off);
-            if (form == 0) seg.add(snap + snap_bytes, nullptr, 8 * xp.work_bytes);
-            if ((rc = gu_device_segments(h, seg)) != GU_OK) return rc;
-            ViStepXcdArgs a{};
-            a.vi = ViClusterArgs{h->d_cell, h->cell_bytes, h->W, h->S, gamma, 0.0, h->d_v[h->vi_cur], h->d_v[h->vi_cur ^ 1],
-                                 h->d_pi[h->vi_cur], keys_d, hdr_d, done_d, iters, 0};
-            a.pos = h->pos();
-            a.reward = h->reward();
-            a.done = h->done();
-            a.episode = h->d_episode;
-            a.starts = h->d_starts;
-            a.n_starts = (uint32_t)h->n_starts;
-            a.seed_prefix = h->seed_prefix;
-            a.env_id0 = (uint32_t)h->env_id0;
-            a.N = h->N;
-            a.flags = flags;
-            a.done_bits = h->d_done_bits;
-            if (form == 0) {
-                a.slots = (vi_u64 *)((char *)h->d_scratch + slots_off);
-                a.gx = (uint8_t *)(snap + snap_bytes);
-                a.work_bytes = (uint32_t)xp.work_bytes;
-                a.inject_failure = path == 5;  // tests: the per-XCD form gives up
-                if ((rc = gu_vi_xcd_launch(h, xp, a, true, true)) != GU_OK) return rc;
-            } else {
-                if (path == 3) GU_HIP(hipMemsetD32Async((hipDeviceptr_t)(hdr_d + 1), 1, 1, h->stream));  // tests: an injected timeout
-                hipLaunchKernelGGL(gu_vi_sweep_step_cluster_kernel, dim3((unsigned)G), dim3(VI_CL_THREADS), 2 * (size_t)h->cell_bytes, h->stream,
-                                   static_cast<const ViStepClusterArgs &>(a));
-                GU_HIP(hipGetLastError());
-            }
-            // rounds_done is written by ONE workgroup, and giving up need not be unanimous: the fallback word, raised by whoever
-            // gives up, decides (see vi_cluster_run)
-            // (header and delta keys lie side by side: ONE copy back, one wait)
-            std::vector<unsigned long long> back(8 + (deltas ? (size_t)iters : 0));
-            if ((rc = gu_read_back(h, back.data(), h->d_scratch, back.size() * sizeof(unsigned long long))) != GU_OK) return rc;
-            int32_t ctl[4];  // [arrival counter (chip-wide form), fallback word, rounds_done, -]
-            memcpy(ctl, back.data(), sizeof ctl);
-            if (form == 0) {  // the per-XCD form's registration word: eight 7-bit counts of workgroups per HW_REG_XCC_ID (gu_vi_xcd.hip)
-                for (int k = 0; k < 8; ++k) h->vi_xcd_members[k] = (int32_t)((back[2] >> (7 * k)) & 0x7Full);
-                h->vi_xcd_torn += (int64_t)(back[4] & 0xFFFFFFFFull);  // (hdr[8]: counted by a -DGU_VI_XCD_TORN build only)
-            }
-            if (!ctl[1] && ctl[2] == iters) {
-                for (int32_t i = 0; deltas && i < iters; ++i) deltas[i] = vi_unkey(back[8 + (size_t)i]);
-                if (iters & 1) {
-                    double *t = h->d_v[0];
-                    h->d_v[0] = h->d_v[1];
-                    h->d_v[1] = t;
-                }
-                h->greedy_valid = false;
-                h->steps_taken += (uint64_t)iters;
-                gu_tabular_drop_carry(h);
-                h->vi_run_form = form == 0 ? 1 : 2;
-                return GU_OK;
-            }
-            off = 0;
-            for (int k = 0; k < 5; off += size[k], ++k)
-                if ((rc = gu_device_copy(h, live[k], snap + off, size[k])) != GU_OK) return rc;
-            GU_HIP(hipStreamSynchronize(h->stream));
-            if (gu_debug())
-                fprintf(stderr, "[gu] sweep-step %s kernel gave up (workgroups not resident together, or clusters too uneven); state restored, next form\n",
-                        form == 0 ? "per-XCD" : "chip-wide cluster");
+        for (int k = 0; k < 5; off += size[k], ++k) seg.add(snap + off, live[k], size[k]);
+        seg.add(h->d_scratch, nullptr, snap_off);
+        GU_TRY(gu_device_segments(h, seg));
+        ViStepClusterArgs a{};
+        a.vi = ViClusterArgs{h->d_cell, h->cell_bytes, h->W, h->S, gamma, 0.0, h->d_v[h->vi_cur], h->d_v[h->vi_cur ^ 1],
+                             h->d_pi[h->vi_cur], keys_d, hdr_d, done_d, iters, 0};
+        vi_env_args(h, flags, a);
+        if (path == 3) GU_HIP(hipMemsetD32Async((hipDeviceptr_t)(hdr_d + 1), 1, 1, h->stream));  // tests: an injected timeout
+        hipLaunchKernelGGL(gu_vi_sweep_step_cluster_kernel, dim3((unsigned)G), dim3(VI_CL_THREADS), 2 * (size_t)h->cell_bytes, h->stream, a);
+        GU_HIP(hipGetLastError());
+        // rounds_done is written by ONE workgroup, and giving up need not be unanimous: the fallback word, raised by whoever
+        // gives up, decides (see vi_cluster_run)
+        // (header and delta keys lie side by side: ONE copy back, one wait)
+        std::vector<unsigned long long> back(8 + (deltas ? (size_t)iters : 0));
+        GU_TRY(gu_read_back(h, back.data(), h->d_scratch, back.size() * sizeof(unsigned long long)));
+        int32_t ctl[4];  // [arrival counter, fallback word, rounds_done, -]
+        memcpy(ctl, back.data(), sizeof ctl);
+        if (!ctl[1] && ctl[2] == iters) {
+            if (deltas) vi_unkey_n(back.data() + 8, (size_t)iters, deltas);
+            if (iters & 1) std::swap(h->d_v[0], h->d_v[1]);
+            h->greedy_valid = false;
+            h->steps_taken += (uint64_t)iters;
+            gu_tabular_drop_carry(h);
+            h->vi_run_form = 2;
+            return GU_OK;
         }
+        off = 0;
+        for (int k = 0; k < 5; off += size[k], ++k) GU_TRY(gu_device_copy(h, live[k], snap + off, size[k]));
+        GU_HIP(hipStreamSynchronize(h->stream));
+        if (gu_debug())
+            fprintf(stderr, "[gu] sweep-step chip-wide cluster kernel gave up (workgroups not resident together, or clusters too uneven); state restored, next form\n");
     }
     // one fused launch per round; the deltas are collected once at the end
     std::vector<double> one((size_t)iters);
-    for (int32_t i = 0; i < iters; ++i) {
-        rc = gu_vi_sweep_step(h, gamma, flags, deltas ? &one[(size_t)i] : nullptr);
-        if (rc != GU_OK) return rc;
-    }
+    for (int32_t i = 0; i < iters; ++i) GU_TRY(gu_vi_sweep_step(h, gamma, flags, deltas ? &one[(size_t)i] : nullptr));
     if (deltas) memcpy(deltas, one.data(), (size_t)iters * sizeof(double));
     h->vi_run_form = 3;
     return GU_OK;

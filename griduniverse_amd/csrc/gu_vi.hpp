@@ -1,12 +1,12 @@
 // gu_vi.hpp -- device helpers shared by the tabular-DP kernels (gu_vi.hip, gu_vi_xcd.hip): the float64 restatement of
 //   core/algorithms/utils.py:15-27   single_step_policy_evaluation        (V1)
 //   core/algorithms/utils.py:55-72   greedy_policy_from_value_function    (V2)
-// for ONE state, in the reference's operation order (see the header of gu_vi.hip).
+// for ONE state, in the reference's operation order (see the header of gu_vi.hip) -- and the host helpers both files' launch code uses.
 #pragma once
 #include "gu_internal.hpp"
+#include <cstring>
 
 typedef unsigned long long vi_u64;
-
 
 struct ViMap {
     const uint8_t *f;  // flags plane (OPEN bits 0..3, TERM bit 4)
@@ -113,6 +113,20 @@ __device__ __forceinline__ double vi_unkey_dev(unsigned long long k)
     return __longlong_as_double((long long)b);
 }
 
+// ... and on the host, where the keys of a call's rounds are read back: one key, and n of them into the caller's deltas
+static inline double vi_unkey(unsigned long long k)
+{
+    const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+    double x;
+    memcpy(&x, &b, sizeof x);
+    return x;
+}
+
+static inline void vi_unkey_n(const unsigned long long *keys, size_t n, double *deltas)
+{
+    for (size_t i = 0; i < n; ++i) deltas[i] = vi_unkey(keys[i]);
+}
+
 __device__ __forceinline__ double vi_ld_agent(const double *p)
 {
     return __longlong_as_double((long long)__hip_atomic_load(reinterpret_cast<const vi_u64 *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -163,6 +177,23 @@ struct ViStepClusterArgs {
     uint64_t *done_bits;
 };
 
+// the env fields of a fused sweep + step launch, from the engine: ViStepArgs (gu_vi.hip), ViStepClusterArgs and ViStepXcdArgs
+// name them alike
+template <class A>
+static inline void vi_env_args(const gu_engine *h, uint32_t flags, A &a)
+{
+    a.pos = h->pos();
+    a.reward = h->reward();
+    a.done = h->done();
+    a.episode = h->d_episode;
+    a.starts = h->d_starts;
+    a.n_starts = (uint32_t)h->n_starts;
+    a.seed_prefix = h->seed_prefix;
+    a.env_id0 = (uint32_t)h->env_id0;
+    a.N = h->N;
+    a.flags = flags;
+    a.done_bits = h->d_done_bits;
+}
 
 // gu_vi_sweep_step_xcd_kernel (gu_vi_xcd.hip): the same rounds synchronised per XCD.  `vi.sync` = the launch header, zeroed
 // before the launch: [0] workgroups registered, [1] fallback word, [2] rounds done, [3] 1 + XCC id of workgroup 0,

@@ -787,7 +787,7 @@ bool gu_vi_xcd_plan(const gu_engine *h, bool agents, GuXcdPlan *plan)
 }
 
 // agents: config 5.  Otherwise the tables alone, with (`greedy`) or without the policy update.
-int gu_vi_xcd_launch(gu_engine *h, const GuXcdPlan &plan, const ViStepXcdArgs &args, bool agents, bool greedy)
+static int gu_vi_xcd_launch(gu_engine *h, const GuXcdPlan &plan, const ViStepXcdArgs &args, bool agents, bool greedy)
 {
     ViStepXcdArgs a = args;
     a.lds_values = plan.values;
@@ -813,21 +813,19 @@ int gu_vi_xcd_launch(gu_engine *h, const GuXcdPlan &plan, const ViStepXcdArgs &a
 // they are (re)allocated and when the launch number is about to repeat.
 #define VI_XCD_CTL_KEYS 1024u                       /* bytes of the sixteen launch headers in front of the delta keys */
 #define VI_XCD_CTL_SLOTS (VI_XCD_CTL_KEYS + 4096u * 8u) /* the delta-key slots behind 4096 keys */
-int gu_vi_xcd_buffers(gu_engine *h, const GuXcdPlan &xp)
+static int gu_vi_xcd_buffers(gu_engine *h, const GuXcdPlan &xp)
 {
     const size_t ctl_bytes = VI_XCD_CTL_SLOTS + xp.slots_bytes, work_bytes = 8 * xp.work_bytes;
     bool wipe = (h->vi_xcd_epoch & 0x7FFFFu) == 0u;  // (the tags hold 19 bits of it)
     if (wipe) h->vi_xcd_epoch += 1u;
     if (!h->d_vi_xcd_ctl || h->vi_xcd_ctl_bytes < ctl_bytes) {
-        if (h->d_vi_xcd_ctl) (void)hipFree(h->d_vi_xcd_ctl);
-        h->d_vi_xcd_ctl = nullptr;
+        gu_release(h->d_vi_xcd_ctl);
         GU_HIP(hipMalloc(&h->d_vi_xcd_ctl, ctl_bytes));
         h->vi_xcd_ctl_bytes = ctl_bytes;
         wipe = true;
     }
     if (!h->d_vi_xcd_work || h->vi_xcd_work_bytes < work_bytes) {
-        if (h->d_vi_xcd_work) (void)hipFree(h->d_vi_xcd_work);
-        h->d_vi_xcd_work = nullptr;
+        gu_release(h->d_vi_xcd_work);
         GU_HIP(hipMalloc(&h->d_vi_xcd_work, work_bytes));
         h->vi_xcd_work_bytes = work_bytes;
         wipe = true;
@@ -842,7 +840,8 @@ int gu_vi_xcd_buffers(gu_engine *h, const GuXcdPlan &xp)
     return GU_OK;
 }
 
-uint32_t gu_vi_xcd_tag0(const gu_engine *h)
+// the launch's number, where its tags carry it
+static uint32_t gu_vi_xcd_tag0(const gu_engine *h)
 {
 #ifdef GU_VI_XCD_TORN
     (void)h;
@@ -854,10 +853,71 @@ uint32_t gu_vi_xcd_tag0(const gu_engine *h)
 
 void gu_vi_xcd_free(gu_engine *h)
 {
-    if (h->d_vi_xcd_ctl) (void)hipFree(h->d_vi_xcd_ctl);
-    if (h->d_vi_xcd_work) (void)hipFree(h->d_vi_xcd_work);
-    h->d_vi_xcd_ctl = h->d_vi_xcd_work = nullptr;
+    gu_release(h->d_vi_xcd_ctl, h->d_vi_xcd_work);
     h->vi_xcd_ctl_bytes = h->vi_xcd_work_bytes = 0;
+}
+
+// The place of the next per-XCD launch in the engine's OWN buffers (nothing else ever writes them -- the scratch area is shared
+// with every other call):
+//   ctl  = a ring of sixteen 64-byte launch headers | delta keys [4096] | delta-key slots
+//   work = the clusters' granule buffers
+// Every tag in them carries this launch's number above the round (ViStepXcdArgs::tag0), the kernel clears the NEXT launch's
+// header when it is done, and the final state goes to the other halves of the double buffers: ONE launch per call, nothing
+// zeroed, nothing snapshot, nothing to restore.  (Until round 4: a launch of copies and zero fills in front of every call, ~6 us.)
+// Fills the launch's header, delta keys and rounds_done in a.vi and the ring-slot fields of `a`; *slot = its header's place in the ring.
+static int vi_xcd_ring_slot(gu_engine *h, const GuXcdPlan &xp, ViStepXcdArgs &a, uint32_t *slot)
+{
+    GU_TRY(gu_vi_xcd_buffers(h, xp));
+    char *ctl = (char *)h->d_vi_xcd_ctl;
+    const uint32_t slot_i = h->vi_xcd_epoch & 15u;
+    uint32_t *hdr = (uint32_t *)(ctl + 64 * (size_t)slot_i);
+    a.vi.sync = hdr;
+    a.vi.delta_key = (vi_u64 *)(ctl + VI_XCD_CTL_KEYS);
+    a.vi.rounds_done = (int32_t *)hdr + 2;
+    a.slots = (vi_u64 *)(ctl + VI_XCD_CTL_SLOTS);
+    a.gx = (uint8_t *)h->d_vi_xcd_work;
+    a.work_bytes = (uint32_t)xp.work_bytes;
+    a.inject_failure = gu_opt(h, GU_OPT_VI_PATH) == 5;  // tests: the per-XCD form gives up
+    a.tag0 = gu_vi_xcd_tag0(h);
+    a.hdr_next = (uint32_t *)(ctl + 64 * (size_t)((slot_i + 1u) & 15u));
+    *slot = slot_i;
+    return GU_OK;
+}
+
+// What a launch of n rounds left in the ring: the sixteen headers and the first delta keys lie side by side -- ONE copy back
+// and one wait.
+struct ViXcdRing {
+    std::vector<unsigned long long> back;  // the sixteen headers (128 words) | the first delta keys
+    size_t first_keys = 0;                 // delta keys that came back with the headers (none when the caller wants no deltas)
+    int32_t ctl[4] = {0, 0, 0, 0};         // the launch's header: [-, fallback word, rounds_done, -]
+    unsigned long long members = 0;        // ... and its registration word: eight 7-bit counts of workgroups per HW_REG_XCC_ID
+};
+
+static int vi_xcd_read_ring(gu_engine *h, uint32_t slot, int32_t n, bool keys, ViXcdRing &r)
+{
+    r.first_keys = keys ? (size_t)(n < 3968 ? n : 3968) : 0;
+    r.back.resize(128 + r.first_keys);
+    GU_TRY(gu_read_back(h, r.back.data(), h->d_vi_xcd_ctl, r.back.size() * sizeof(unsigned long long)));
+    const unsigned long long *hdr = r.back.data() + 8 * (size_t)slot;
+    memcpy(r.ctl, hdr, sizeof r.ctl);
+    r.members = hdr[2];
+    h->vi_xcd_torn += (int64_t)(hdr[4] & 0xFFFFFFFFull);  // (hdr[8]: counted by a -DGU_VI_XCD_TORN build only)
+    return GU_OK;
+}
+
+// ... and the deltas of its first n rounds: from the keys that came back with the headers, the rest (calls of more than 3968
+// rounds) in a second copy
+static int vi_xcd_ring_deltas(gu_engine *h, const ViXcdRing &r, int32_t n, double *deltas)
+{
+    const size_t count = (size_t)n;
+    vi_unkey_n(r.back.data() + 128, count < r.first_keys ? count : r.first_keys, deltas);
+    if (count > r.first_keys) {
+        std::vector<unsigned long long> rest(count - r.first_keys);
+        const vi_u64 *keys = (const vi_u64 *)((const char *)h->d_vi_xcd_ctl + VI_XCD_CTL_KEYS);
+        GU_HIP(hipMemcpy(rest.data(), keys + r.first_keys, rest.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        vi_unkey_n(rest.data(), rest.size(), deltas + r.first_keys);
+    }
+    return GU_OK;
 }
 
 // gu_vi_sweep / gu_vi_run / gu_vi_eval_run as ONE launch of one XCD's workgroups (see the kernel, !AGENTS).  Runs up to max_rounds
@@ -870,28 +930,12 @@ static int vi_xcd_dp_launch(gu_engine *h, double gamma, double threshold, bool u
     const int64_t path = gu_opt(h, GU_OPT_VI_PATH);
     GuXcdPlan xp{};
     if (!(path == 0 || path == 5 || path == 6) || !gu_vi_xcd_plan(h, false, &xp)) return GU_VI_FALLBACK;
-    // The engine's OWN buffers (nothing else ever writes them -- the scratch area is shared with every other call):
-    //   ctl  = a ring of sixteen 64-byte launch headers | delta keys [4096] | delta-key slots
-    //   work = the clusters' granule buffers
-    // Every tag in them carries this launch's number above the round (ViStepXcdArgs::tag0), the kernel clears the NEXT launch's
-    // header when it is done, and the final tables go to the other halves of the double buffers: ONE launch per call, nothing
-    // zeroed, nothing snapshot, nothing to restore.  (Until round 4: a launch of copies and zero fills in front of every call, ~6 us.)
-    int rc = gu_vi_xcd_buffers(h, xp);
-    if (rc != GU_OK) return rc;
-    char *ctl = (char *)h->d_vi_xcd_ctl;
-    const uint32_t slot_i = h->vi_xcd_epoch & 15u;
-    uint32_t *hdr = (uint32_t *)(ctl + 64 * (size_t)slot_i);
-    vi_u64 *keys = (vi_u64 *)(ctl + VI_XCD_CTL_KEYS);
     ViStepXcdArgs a{};
     a.vi = ViClusterArgs{h->d_cell, h->cell_bytes, h->W, h->S, gamma, threshold, h->d_v[h->vi_cur], h->d_v[h->vi_cur ^ 1], h->d_pi[h->vi_cur],
-                         keys, hdr, (int32_t *)hdr + 2, max_rounds, use_threshold ? 1 : 0};
+                         nullptr, nullptr, nullptr, max_rounds, use_threshold ? 1 : 0};  // (delta keys, header, rounds_done: the ring slot's)
+    uint32_t slot = 0;
+    GU_TRY(vi_xcd_ring_slot(h, xp, a, &slot));
     a.N = 0;
-    a.slots = (vi_u64 *)(ctl + VI_XCD_CTL_SLOTS);
-    a.gx = (uint8_t *)h->d_vi_xcd_work;
-    a.work_bytes = (uint32_t)xp.work_bytes;
-    a.inject_failure = path == 5;
-    a.tag0 = gu_vi_xcd_tag0(h);
-    a.hdr_next = (uint32_t *)(ctl + 64 * (size_t)((slot_i + 1u) & 15u));
     a.v_out = h->d_v[h->vi_cur ^ 1];
     a.pi_out = greedy ? h->d_pi[h->vi_cur ^ 1] : nullptr;
     // the final tables also land in a page-locked copy on the host (40 KB at 32 x 32: a few us of stores at the end of the launch),
@@ -909,33 +953,17 @@ static int vi_xcd_dp_launch(gu_engine *h, double gamma, double threshold, bool u
     h->h_tables_valid = false;
     a.v_host = h->h_tables;
     a.pi_host = h->h_tables ? h->h_tables + h->S : nullptr;
-    if ((rc = gu_vi_xcd_launch(h, xp, a, false, greedy)) != GU_OK) return rc;
+    GU_TRY(gu_vi_xcd_launch(h, xp, a, false, greedy));
     ++h->vi_xcd_epoch;
-    // (the sixteen headers and the first delta keys lie side by side: ONE copy back and one wait)
-    const size_t first_keys = deltas ? (size_t)(max_rounds < 3968 ? max_rounds : 3968) : 0;
-    std::vector<unsigned long long> back(128 + first_keys);
-    if ((rc = gu_read_back(h, back.data(), ctl, back.size() * sizeof(unsigned long long))) != GU_OK) return rc;
-    int32_t ctlw[4];  // [workgroups registered, fallback word, rounds_done, -]
-    memcpy(ctlw, back.data() + 8 * (size_t)slot_i, sizeof ctlw);
-    h->vi_xcd_torn += (int64_t)(back[8 * (size_t)slot_i + 4] & 0xFFFFFFFFull);  // (hdr[8]: counted by a -DGU_VI_XCD_TORN build only)
-    const int32_t done = ctlw[1] ? -1 : ctlw[2];
+    ViXcdRing ring;
+    GU_TRY(vi_xcd_read_ring(h, slot, max_rounds, deltas != nullptr, ring));
+    const int32_t done = ring.ctl[1] ? -1 : ring.ctl[2];
     if (done < 0) {  // the input tables are as they were; the ring is wiped (who knows which header this launch left how)
-        GU_HIP(hipMemsetAsync(ctl, 0, VI_XCD_CTL_KEYS, h->stream));
+        GU_HIP(hipMemsetAsync(h->d_vi_xcd_ctl, 0, VI_XCD_CTL_KEYS, h->stream));
         if (gu_debug()) fprintf(stderr, "[gu] DP per-XCD kernel gave up (workgroups not resident together, or clusters too uneven); next form\n");
         return GU_VI_FALLBACK;
     }
-    if (deltas && done > 0) {
-        std::vector<unsigned long long> rest;
-        if ((size_t)done > first_keys) {
-            rest.resize((size_t)done - first_keys);
-            GU_HIP(hipMemcpy(rest.data(), keys + first_keys, rest.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        }
-        for (int32_t i = 0; i < done; ++i) {
-            const unsigned long long k = (size_t)i < first_keys ? back[128 + (size_t)i] : rest[(size_t)i - first_keys];
-            const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-            memcpy(&deltas[i], &b, sizeof(double));
-        }
-    }
+    if (deltas && done > 0) GU_TRY(vi_xcd_ring_deltas(h, ring, done, deltas));
     if (done > 0) {  // the results are in the other halves of the double buffers: they become the current ones
         std::swap(h->d_v[0], h->d_v[1]);
         if (greedy) std::swap(h->d_pi[0], h->d_pi[1]);
@@ -952,7 +980,6 @@ static int vi_xcd_dp_launch(gu_engine *h, double gamma, double threshold, bool u
 // GU_VI_FALLBACK: the launch gave up (or does not apply), everything is as it was.
 int gu_vi_xcd_fused_run(gu_engine *h, const GuXcdPlan &xp, double gamma, int32_t iters, uint32_t flags, double *deltas)
 {
-    const int64_t path = gu_opt(h, GU_OPT_VI_PATH);
     const size_t n4 = (size_t)h->N * 4, bits_bytes = (((size_t)h->N + 63) / 64) * 8;
     if (!h->d_out3_alt) {  // all three or none: a half-made set would make the launch write two of them in place
         int32_t *out3 = nullptr;
@@ -973,32 +1000,12 @@ int gu_vi_xcd_fused_run(gu_engine *h, const GuXcdPlan &xp, double gamma, int32_t
     int32_t total = 0;
     while (total < iters) {
         const int32_t n = iters - total < 4096 ? iters - total : 4096;
-        int rc = gu_vi_xcd_buffers(h, xp);
-        if (rc != GU_OK) return rc;
-        char *ctl = (char *)h->d_vi_xcd_ctl;
-        const uint32_t slot_i = h->vi_xcd_epoch & 15u;
-        uint32_t *hdr = (uint32_t *)(ctl + 64 * (size_t)slot_i);
-        vi_u64 *keys = (vi_u64 *)(ctl + VI_XCD_CTL_KEYS);
         ViStepXcdArgs a{};
         a.vi = ViClusterArgs{h->d_cell, h->cell_bytes, h->W, h->S, gamma, 0.0, h->d_v[h->vi_cur], h->d_v[h->vi_cur ^ 1], h->d_pi[h->vi_cur],
-                             keys, hdr, (int32_t *)hdr + 2, n, 0};
-        a.pos = h->pos();
-        a.reward = h->reward();
-        a.done = h->done();
-        a.episode = h->d_episode;
-        a.starts = h->d_starts;
-        a.n_starts = (uint32_t)h->n_starts;
-        a.seed_prefix = h->seed_prefix;
-        a.env_id0 = (uint32_t)h->env_id0;
-        a.N = h->N;
-        a.flags = flags;
-        a.done_bits = h->d_done_bits;
-        a.slots = (vi_u64 *)(ctl + VI_XCD_CTL_SLOTS);
-        a.gx = (uint8_t *)h->d_vi_xcd_work;
-        a.work_bytes = (uint32_t)xp.work_bytes;
-        a.inject_failure = path == 5;
-        a.tag0 = gu_vi_xcd_tag0(h);
-        a.hdr_next = (uint32_t *)(ctl + 64 * (size_t)((slot_i + 1u) & 15u));
+                             nullptr, nullptr, nullptr, n, 0};  // (delta keys, header, rounds_done: the ring slot's)
+        uint32_t slot = 0;
+        GU_TRY(vi_xcd_ring_slot(h, xp, a, &slot));
+        vi_env_args(h, flags, a);
         a.v_out = h->d_v[h->vi_cur ^ 1];
         a.pi_out = h->d_pi[h->vi_cur ^ 1];
         a.pos_out = h->d_out3_alt;
@@ -1006,33 +1013,18 @@ int gu_vi_xcd_fused_run(gu_engine *h, const GuXcdPlan &xp, double gamma, int32_t
         a.done_out = h->d_out3_alt + 2 * h->N;
         a.episode_out = h->d_episode_alt;
         a.done_bits_out = h->d_done_bits_alt;
-        if ((rc = gu_vi_xcd_launch(h, xp, a, true, true)) != GU_OK) return rc;
+        GU_TRY(gu_vi_xcd_launch(h, xp, a, true, true));
         ++h->vi_xcd_epoch;
-        const size_t first_keys = deltas ? (size_t)(n < 3968 ? n : 3968) : 0;
-        std::vector<unsigned long long> back(128 + first_keys);
-        if ((rc = gu_read_back(h, back.data(), ctl, back.size() * sizeof(unsigned long long))) != GU_OK) return rc;
-        int32_t ctlw[4];  // [-, fallback word, rounds_done, -]
-        memcpy(ctlw, back.data() + 8 * (size_t)slot_i, sizeof ctlw);
-        for (int k = 0; k < 8; ++k) h->vi_xcd_members[k] = (int32_t)((back[8 * (size_t)slot_i + 2] >> (7 * k)) & 0x7Full);  // the registration word
-        h->vi_xcd_torn += (int64_t)(back[8 * (size_t)slot_i + 4] & 0xFFFFFFFFull);
-        if (ctlw[1] || ctlw[2] != n) {
-            GU_HIP(hipMemsetAsync(ctl, 0, VI_XCD_CTL_KEYS, h->stream));
+        ViXcdRing ring;
+        GU_TRY(vi_xcd_read_ring(h, slot, n, deltas != nullptr, ring));
+        for (int k = 0; k < 8; ++k) h->vi_xcd_members[k] = (int32_t)((ring.members >> (7 * k)) & 0x7Full);
+        if (ring.ctl[1] || ring.ctl[2] != n) {
+            GU_HIP(hipMemsetAsync(h->d_vi_xcd_ctl, 0, VI_XCD_CTL_KEYS, h->stream));
             if (gu_debug()) fprintf(stderr, "[gu] sweep-step per-XCD kernel gave up (workgroups not resident together, or clusters too uneven); next form\n");
             if (total > 0) return gu_fail(GU_ERR_HIP, "the per-XCD sweep + step launch gave up %d rounds into a call", total);
             return GU_VI_FALLBACK;
         }
-        if (deltas) {
-            std::vector<unsigned long long> rest;
-            if ((size_t)n > first_keys) {
-                rest.resize((size_t)n - first_keys);
-                GU_HIP(hipMemcpy(rest.data(), keys + first_keys, rest.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-            }
-            for (int32_t i = 0; i < n; ++i) {
-                const unsigned long long k = (size_t)i < first_keys ? back[128 + (size_t)i] : rest[(size_t)i - first_keys];
-                const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-                memcpy(&deltas[total + i], &b, sizeof(double));
-            }
-        }
+        if (deltas) GU_TRY(vi_xcd_ring_deltas(h, ring, n, deltas + total));
         // the results become the current state
         std::swap(h->d_v[0], h->d_v[1]);
         std::swap(h->d_pi[0], h->d_pi[1]);
@@ -1052,9 +1044,11 @@ int gu_vi_xcd_fused_run(gu_engine *h, const GuXcdPlan &xp, double gamma, int32_t
     return GU_OK;
 }
 
-// gu_vi_sweep / gu_vi_run / gu_vi_eval_run on the per-XCD kernel: launches of up to 4096 rounds (the tags keep 13 bits for the round,
-// the engine's buffer 4096 delta keys), one after the other while the stopping rule has not fired -- a call of up to 4096 rounds
-// is ONE launch.  The tables pass from launch to launch in memory, exactly as between two calls.
+// The first form vi_dp_run (gu_vi.hip) tries for gu_vi_sweep / gu_vi_run / gu_vi_eval_run: the per-XCD kernel, in launches of up
+// to 4096 rounds (the tags keep 13 bits for the round, the engine's buffer 4096 delta keys), one after the other while the
+// stopping rule has not fired -- a call of up to 4096 rounds is ONE launch.  The tables pass from launch to launch in memory,
+// exactly as between two calls.  GU_VI_FALLBACK (from the first launch only): the form does not apply here or gave up, the
+// tables are as they were and vi_dp_run goes on to the next form.
 int gu_vi_xcd_dp_run(gu_engine *h, double gamma, double threshold, bool use_threshold, bool greedy, int32_t max_rounds, int32_t *rounds_done,
                      double *deltas)
 {

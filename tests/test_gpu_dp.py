@@ -437,6 +437,28 @@ def test_the_tables_alone_take_the_per_xcd_launch_wherever_it_fits(W, H, vi_path
         assert eng.vi_last_dp_form() == 1
 
 
+@pytest.mark.parametrize('W,H', [(8, 8), (70, 70)])
+def test_the_four_dp_calls_choose_their_form_by_one_rule(W, H, vi_path):
+    """vi_sweep without and with the greedy update, vi_run and vi_eval_run go down the same ladder of forms (csrc/gu_vi.hip:
+    vi_dp_run): from the same starting tables all four report the same vi_last_dp_form().  One launch per round (vi_path = 2)
+    is form 4 on every grid; without the per-XCD form (vi_path = 4) 8x8 takes the one-workgroup kernel, form 2 -- 70x70 has 4900
+    states, just above that kernel's 4096."""
+    S = W * H
+    v0, pi0 = np.zeros(S), np.ones((S, 4)) / 4
+    forms = []
+    with Engine(64, GridSpec(W, H, [0], [S - 1], [S // 2], [])) as eng:
+        for call in (lambda: eng.vi_sweep(0.9, 3, greedy_update=False), lambda: eng.vi_sweep(0.9, 3, greedy_update=True),
+                     lambda: eng.vi_run(0.9, 1e-3, 5), lambda: eng.vi_eval_run(0.9, 1e-3, 5)):
+            eng.vi_set(v0, pi0)
+            call()
+            forms.append(eng.vi_last_dp_form())
+    assert len(set(forms)) == 1, forms
+    if vi_path == 'launch_per_round':
+        assert forms[0] == 4
+    if vi_path == 'no_per_xcd_form' and S <= 4096:
+        assert forms[0] == 2
+
+
 @pytest.mark.parametrize('W,H', [(32, 32), (64, 64), (100, 40), (7, 3)])
 def test_the_tables_a_dp_call_leaves_on_the_host_are_the_tables_on_the_device(W, H):
     """The per-XCD launch of gu_vi_run / gu_vi_sweep / gu_vi_eval_run writes its final tables to a page-locked copy on the host as well,
