@@ -69,6 +69,8 @@ SIGNATURES = {
     'gu_set_grids': [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32],
     'gu_generate_mazes': [_vp, _i32, _i32, _i32, _u64],
     'gu_get_cells': [_vp, _i32, _vp, _vp, _vp, _vp],
+    'gu_set_wind': [_vp, _vp, _u32],
+    'gu_get_wind': [_vp, _vp, _vp, _vp],
     'gu_seed': [_vp, _u64],
     'gu_reset': [_vp, _vp, _vp, _vp],
     'gu_reset_done': [_vp],

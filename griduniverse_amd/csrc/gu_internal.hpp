@@ -130,6 +130,9 @@ struct gu_engine {
     int32_t cell_bytes = 0;          // S rounded up to 16
     uint8_t *d_cell = nullptr;       // absorbing-aware planes    [2 * cell_bytes]
     uint8_t *d_cell_raw = nullptr;   // care_about_terminal=False [2 * cell_bytes]
+    uint8_t *d_wind_cell = nullptr;  // wind (gu_set_wind, gu_wind.hip; single-grid engines): [3 * cell_bytes] the planes of d_cell with the
+                                     // wind plane behind them -- what the windy kernels stage in one piece; nullptr: calm
+    uint32_t gust_q16 = 0;           // ... and its gust probability in 1/65536
     uint8_t *d_kind = nullptr;       // [n_grids][cell_bytes] texture class of every cell as the reference's viewer picks it
                                      // (rendering.py:119-133: goal, else lava, else wall, else ground = 3, 2, 1, 0) -- the flags
                                      // cannot tell a goal+lava cell from a lava cell; nullptr for device-generated mazes (no
@@ -382,6 +385,10 @@ int gu_ensure_scratch(gu_engine *h, size_t bytes);
 
 #define GU_NEED_GRID(h) GU_REQUIRE((h)->has_grid, GU_ERR_STATE, "no grid set: call gu_set_grid first")
 
+// every call that moves envs or reads the move rule and has no windy form refuses while wind is set (include/gu.h: gu_set_wind)
+#define GU_NO_WIND(h, fn) \
+    GU_REQUIRE(!(h)->d_wind_cell, GU_ERR_UNSUPPORTED, "%s knows no wind: the engine has wind set (gu_set_wind; NULL calms it again)", fn)
+
 // frees device buffers and forgets them (hipFree's status is not looked at)
 template <class... P>
 static inline void gu_release(P *&...p)
@@ -497,6 +504,13 @@ static inline void gu_tabular_drop_carry(gu_engine *h)
     h->rf_key = 0;
     h->is_key = 0;
 }
+
+// ---- wind (gu_wind.hip): the launches that gu_launch_step / gu_launch_rollout hand over while wind is set ----
+struct RolloutArgs;
+int gu_wind_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward, int32_t *host_done,
+                        uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
+int gu_wind_launch_rollout(gu_engine *h, const RolloutArgs &a, int64_t T, int32_t policy, uint32_t flags);
+void gu_wind_free(gu_engine *h);
 
 // ---- agent trail (gu_trail.hip): no-ops while the trail is off ----------------------
 int gu_trail_after_step(gu_engine *h, uint32_t flags);

@@ -327,6 +327,7 @@ int gu_launch_reset(gu_engine *h, const uint8_t *d_mask, const int32_t *d_choice
 int gu_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward,
                    int32_t *host_done, uint32_t *host_seq, uint32_t seq, uint32_t *host_err)
 {
+    if (h->d_wind_cell) return gu_wind_launch_step(h, d_actions_row, flags, host_obs, host_reward, host_done, host_seq, seq, host_err);  // gu_wind.hip
     h->entry_table_ok = false;
     StepArgs a{h->d_cell, h->cell_bytes, h->W, h->delta_lut, d_actions_row, h->pos(), h->reward(), h->done(),
                h->d_episode, h->d_tcount, h->d_starts, (uint32_t)h->n_starts, h->seed_prefix, (uint32_t)h->env_id0, h->N, flags,
@@ -551,8 +552,9 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
     // profiles/archive/r05m_half_sizes.txt) --, beyond it the planes win.  So: triples for the uniform policy on the transition-row
     // kernel with pair tables, up to n_cu / 4 workgroups of 256 (half waves for the upper half of that range).  Batches of more than 2^24 envs (lane offset + 15 rows must stay
     // below 2^32 bytes) and engines with the agent trail on always keep the planes.
+    GU_REQUIRE(!(h->d_wind_cell && (flags & GU_F_PACKED)), GU_ERR_UNSUPPORTED, "a rollout under wind (gu_set_wind) writes int32 rows only: GU_F_PACKED is refused");
     int traj = (flags & GU_F_PACKED) ? 2 : ((flags & GU_F_TRAJECTORY) ? 1 : 0);
-    if (traj == 1 && h->N <= ((int64_t)1 << 24) && !h->trail_cap) {
+    if (traj == 1 && h->N <= ((int64_t)1 << 24) && !h->trail_cap && !h->d_wind_cell) {
         const int64_t layout = gu_opt(h, GU_OPT_TRAJ_LAYOUT);
         if (layout == 1 || (layout == -1 && policy == GU_POLICY_UNIFORM && gu_rows_pairs_fit(h) && (int64_t)gu_blocks(h->N, 256) * 4 <= h->n_cu)) traj = 3;
     }
@@ -633,6 +635,7 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
     a.xcd_remap = gu_opt(h, GU_OPT_ROLLOUT_XCD) != 0 && h->n_grids == 1;  // XCD-aware env-block order (see gu_env_block; measured slower, off)
     if (policy == GU_POLICY_SAMPLE)
         hipLaunchKernelGGL(gu_pi_threshold_kernel, dim3(gu_blocks(h->S, 256)), dim3(256), 0, h->stream, h->d_pi[h->vi_cur], h->S, h->d_pi_thr);
+    if (h->d_wind_cell) return gu_wind_launch_rollout(h, a, T, policy, flags);  // wind is set: the windy kernel serves every shape (gu_wind.hip)
     if (!a.straddle && gu_rollout_multi(h, a, policy, auto_mode, traj, stats)) {
         GU_HIP(hipGetLastError());
         h->steps_taken += (uint64_t)T;

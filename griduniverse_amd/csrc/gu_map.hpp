@@ -1,5 +1,5 @@
 // gu_map.hpp -- device helpers shared by the step / rollout / look-ahead kernels: the per-cell record map (global,
-// block-shared LDS or private LDS), the action -> delta LUT and the branch-free move.
+// block-shared LDS or private LDS), the action -> delta LUT, the branch-free move and the wind's pushes.
 #pragma once
 #include "gu_internal.hpp"
 #include "gu_rng.hpp"
@@ -84,4 +84,33 @@ __device__ __forceinline__ int32_t gu_reward_packed(uint32_t flags)
 __device__ __forceinline__ int32_t gu_move(int32_t s, uint32_t flags, uint32_t a, int32_t delta)
 {
     return __mul24((int32_t)__builtin_amdgcn_ubfe(flags, a, 1), delta) + s;  // v_bfe_u32 + v_mad_i32_i24
+}
+
+// ------------------------------------------------------------------------------------
+// wind (include/gu.h: gu_set_wind): one byte per cell behind the two cell planes, bits 0..1 the direction, bits 2..3 the strength
+// ------------------------------------------------------------------------------------
+#define GU_WIND_STRENGTH(c) (((c) >> 2) & 3u)
+
+// the strength after the gust test on the stream-9 word w of the step: k > 0 becomes k + 1 or k - 1 where (w >> 16) < gust_q16
+__device__ __forceinline__ uint32_t gu_wind_gust(uint32_t k, uint32_t w, uint32_t gust_q16)
+{
+    const uint32_t moved = (w & 1u) ? k + 1u : k - 1u;
+    return (k > 0u && (w >> 16) < gust_q16) ? moved : k;
+}
+
+// k pushes of the cell's wind from s (where the action left the agent), each one move of the engine's rule: the OPEN bit of the
+// cell stood on.  A WAVE-UNIFORM loop with an early exit: it runs while some lane of the wave still has pushes left, so a wave
+// over calm cells pays one ballot and one untaken scalar branch, and a lane that a wall, the border or a terminal cell has stopped
+// leaves the count at once (the same push from the same cell would fail again).  Every trip is one dependent read of the flags plane.
+template <bool LUT>
+__device__ __forceinline__ int32_t gu_wind_push(const uint8_t *f, int32_t s, uint32_t c, uint32_t k, uint64_t lut, int32_t W)
+{
+    const uint32_t dir = c & 3u;
+    const int32_t delta = gu_delta<LUT>(dir, lut, W);
+    while (__builtin_amdgcn_ballot_w64(k > 0u) != 0ull) {
+        const uint32_t go = k > 0u ? __builtin_amdgcn_ubfe((uint32_t)f[s], dir, 1) : 0u;
+        s += __mul24((int32_t)go, delta);
+        k = go ? k - 1u : 0u;
+    }
+    return s;
 }

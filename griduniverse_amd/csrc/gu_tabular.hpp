@@ -100,9 +100,14 @@ __device__ __forceinline__ uint32_t gu_q_action(const QRow &q, uint32_t w, uint3
 // A kernel constructs it (staging the map), runs begin .. end on live lanes and ballot on all; its own rule sits between move and step.
 // ROWS = false (gu_fa.hip): the lane has no table of rows of its own -- begin / reset / next_row read nothing from a.q, and the
 // kernel keeps `q` (for gu_fa.hip: the folded row of the current state) itself.
-template <bool LDS, bool ROWS = true>
+// WIND (include/gu.h: gu_set_wind; 0 = calm, 1 = wind without gusts, 2 = with gusts): a.cell then carries the wind plane behind the two
+// cell planes (gu_engine::d_wind_cell; staged with them), the kernel sets `gust_q16` (its own arguments hold it: TabArgs does not),
+// and move() pushes the agent behind its action.  The calm instantiations hold none of it.
+template <bool LDS, bool ROWS = true, int WIND = 0>
 struct TabLane {
     CellMap m;
+    const uint8_t *wd;  // WIND: the wind plane
+    uint32_t gust_q16;  // WIND == 2
     LaneGrid lg;
     int64_t e;
     uint32_t env, start_prefix, prefix, ep;
@@ -113,7 +118,8 @@ struct TabLane {
 
     __device__ __forceinline__ TabLane(const TabArgs &a, uint8_t *smem)
     {
-        m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs);
+        m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, WIND ? 3 : 2);
+        if (WIND) wd = m.f + 2 * a.cell_bytes;
         e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         d = 0;
     }
@@ -154,7 +160,13 @@ struct TabLane {
     // take action ua from s: sets r and d, advances t (re-keying stream 4 where t crosses a multiple of 2^32), returns s'
     __device__ __forceinline__ int32_t move(const TabArgs &a, uint32_t ua)
     {
-        const int32_t s2 = gu_move(s, m.f[s], ua, gu_delta<LDS>(ua, a.lut, a.W));
+        int32_t s2 = gu_move(s, m.f[s], ua, gu_delta<LDS>(ua, a.lut, a.W));
+        if (WIND) {  // the wind of the cell the agent leaves, gusting on the stream-9 word of step t (hashed only where some lane stands in wind)
+            const uint32_t c = wd[s];
+            uint32_t k = GU_WIND_STRENGTH(c);
+            if (WIND == 2 && __builtin_amdgcn_ballot_w64(k > 0u) != 0ull) k = gu_wind_gust(k, gu_rng_word(prefix, GU_RNG_STREAM_WIND, (uint32_t)t), gust_q16);
+            s2 = gu_wind_push<LDS>(m.f, s2, c, k, a.lut, a.W);
+        }
         r = m.r[s2];
         d = (m.f[s2] >> GU_CELL_TERM_BIT) & 1;
         ++t;
@@ -390,12 +402,13 @@ static inline void gu_tabular_args(gu_engine *h, TabArgs &a, int64_t T, double a
 
 // launch the LDS instantiation where every block uses one grid whose planes fit, else the L2 one; blocks of at most `bs` lanes,
 // and `lane_lds` bytes of dynamic LDS per lane after the planes (gu_lambda.hip's ring; none for the other learners)
+// (`planes`: 3 for the windy instantiations, whose a.cell carries the wind plane behind the two cell planes)
 template <class A>
-static int gu_tabular_launch(gu_engine *h, void (*lds)(A), void (*l2)(A), const A &a, int bs = GU_BLOCK, size_t lane_lds = 0)
+static int gu_tabular_launch(gu_engine *h, void (*lds)(A), void (*l2)(A), const A &a, int bs = GU_BLOCK, size_t lane_lds = 0, int planes = 2)
 {
-    const int lds_bs = gu_lds_block(h, bs, 2);
+    const int lds_bs = gu_lds_block(h, bs, planes);
     if (lds_bs) {
-        const size_t bytes = 2 * (size_t)h->cell_bytes + lane_lds * (size_t)lds_bs;
+        const size_t bytes = (size_t)planes * (size_t)h->cell_bytes + lane_lds * (size_t)lds_bs;
         if (bytes > 64 * 1024) GU_HIP(hipFuncSetAttribute((const void *)lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
         hipLaunchKernelGGL(lds, dim3(gu_blocks(h->N, lds_bs)), dim3(lds_bs), bytes, h->stream, a);
     } else {

@@ -9,13 +9,16 @@
 struct TdArgs : TabArgs {
     int8_t *next_a;  // [N] SARSA: the action carried to the next launch (-1: none)
     int32_t carry;   // 1: this launch directly follows a SARSA launch on the same engine -- start with next_a
+    uint32_t gust_q16;  // the windy instantiations: the engine's gust probability (gu_set_wind); a.cell then holds three planes
 };
 
-template <bool SARSA, bool LDS>
+// WIND: 0 = calm, 1 = wind without gusts (no stream-9 hash in the code), 2 = with gusts (gu_tabular.hpp: TabLane)
+template <bool SARSA, bool LDS, int WIND = 0>
 __global__ void __launch_bounds__(GU_BLOCK) gu_td_kernel(const TdArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    TabLane<LDS> L(a, smem);
+    TabLane<LDS, true, WIND> L(a, smem);
+    if (WIND == 2) L.gust_q16 = a.gust_q16;
     if (L.e < a.N) {
         L.begin(a);
         int32_t act = (SARSA && a.carry) ? (int32_t)a.next_a[L.e] : -1;
@@ -67,8 +70,20 @@ static int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, d
     gu_tabular_args(h, a, T, alpha, gamma, eps_q16, flags);
     a.next_a = h->d_td_next;
     a.carry = (method == 1 && h->td_carry) ? 1 : 0;
-    const int rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true>, gu_td_kernel<true, false>, a)
-                               : gu_tabular_launch(h, gu_td_kernel<false, true>, gu_td_kernel<false, false>, a);
+    a.gust_q16 = h->gust_q16;
+    int rc;
+    if (h->d_wind_cell) {  // the windy instantiations, on the three planes
+        a.cell = h->d_wind_cell;
+        if (h->gust_q16)
+            rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 2>, gu_td_kernel<true, false, 2>, a, GU_BLOCK, 0, 3)
+                             : gu_tabular_launch(h, gu_td_kernel<false, true, 2>, gu_td_kernel<false, false, 2>, a, GU_BLOCK, 0, 3);
+        else
+            rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 1>, gu_td_kernel<true, false, 1>, a, GU_BLOCK, 0, 3)
+                             : gu_tabular_launch(h, gu_td_kernel<false, true, 1>, gu_td_kernel<false, false, 1>, a, GU_BLOCK, 0, 3);
+    } else {
+        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true>, gu_td_kernel<true, false>, a)
+                         : gu_tabular_launch(h, gu_td_kernel<false, true>, gu_td_kernel<false, false>, a);
+    }
     return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, method == 1);
 }
 

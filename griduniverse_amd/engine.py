@@ -137,6 +137,19 @@ class Engine(object):
         check(self.lib.gu_get_cells(self._h, int(grid_index), ptr(flags), ptr(reward), ptr(starts), ctypes.byref(n)))
         return flags, reward, starts[:n.value].copy()
 
+    def set_wind(self, wind, gust_q16=0):
+        """Install the wind plane uint8[S] (grid.wind_plane) and the gust probability in 1/65536; None calms the engine again
+        (gu_set_wind)."""
+        w = None if wind is None else _lib.as_array(wind, np.uint8, (self.spec.S,), 'wind')
+        check(self.lib.gu_set_wind(self._h, ptr(w), int(gust_q16)))
+
+    def get_wind(self):
+        """(wind uint8[S], gust_q16), or None while the engine is calm (gu_get_wind)."""
+        wind = np.empty(self.spec.S, np.uint8)
+        gust, present = ctypes.c_uint32(0), ctypes.c_int32(0)
+        check(self.lib.gu_get_wind(self._h, ptr(wind), ctypes.byref(gust), ctypes.byref(present)))
+        return (wind, gust.value) if present.value else None
+
     def seed(self, seed):
         self.seed_value = int(seed) & 0xFFFFFFFFFFFFFFFF
         check(self.lib.gu_seed(self._h, self.seed_value))

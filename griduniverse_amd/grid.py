@@ -119,3 +119,41 @@ def grid_view(spec, pos):
     view = cell_classes(spec)
     view[pos] += SENSE_AGENT
     return view.reshape(spec.H, spec.W)
+
+
+# ---- wind: the per-cell plane of include/gu.h, gu_set_wind ---------------------------------------------------------
+WIND_DIRECTIONS = {'up': 0, 'right': 1, 'down': 2, 'left': 3}  # the action codes
+
+
+def _wind_field(x, W, H, name):
+    """An int array [H, W], or [W] meaning per column, as int64[H, W]; a scalar fills the grid."""
+    a = np.asarray(x)
+    if a.dtype == bool or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError('{} must hold integers'.format(name))
+    if a.shape == ():
+        return np.full((H, W), int(a), np.int64)
+    if a.shape == (W,):
+        return np.broadcast_to(a.astype(np.int64)[None, :], (H, W)).copy()
+    if a.shape == (H, W):
+        return a.astype(np.int64)
+    raise ValueError('{} must have shape ({}, {}) or ({},), got {}'.format(name, H, W, W, a.shape))
+
+
+def wind_plane(W, H, strength, direction='up'):
+    """uint8[S]: the wind plane of a W x H grid as gu_set_wind takes it -- bits 0..1 of cell s = y * W + x the direction (the action
+    codes UP, RIGHT, DOWN, LEFT), bits 2..3 the strength.  `strength`: an int array [H, W], or [W] meaning per column, of values
+    0 .. 3.  `direction`: a name ('up', 'right', 'down', 'left'), a code 0 .. 3, or an array of codes of the same shapes."""
+    W, H = int(W), int(H)
+    if isinstance(strength, (bool, np.bool_)) or np.ndim(strength) == 0:
+        raise ValueError('strength must be an array of shape ({}, {}) or ({},)'.format(H, W, W))
+    k = _wind_field(strength, W, H, 'strength')
+    if k.min() < 0 or k.max() > 3:
+        raise ValueError('strength must lie in 0 .. 3')
+    if isinstance(direction, str):
+        if direction not in WIND_DIRECTIONS:
+            raise ValueError("direction must be one of 'up', 'right', 'down', 'left', or a code 0 .. 3")
+        direction = WIND_DIRECTIONS[direction]
+    d = _wind_field(direction, W, H, 'direction')
+    if d.min() < 0 or d.max() > 3:
+        raise ValueError('direction codes must lie in 0 .. 3')
+    return np.ascontiguousarray((d | (k << 2)).astype(np.uint8).reshape(W * H))

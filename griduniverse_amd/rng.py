@@ -12,6 +12,8 @@ one, keyed by (seed, GLOBAL env id, stream, counter):
     stream 4  TD control      : one word per step of gu_td_run, counter t & 0xFFFFFFFF, epoch t >> 32 (hashed right behind the
                                 seed when it is not zero, as for streams 0 and 2); explore iff (word >> 16) < eps_q16, explore action
                                 word & 3, greedy tie index (((word >> 2) & 0x3FFF) * ties) >> 14
+    stream 9  gusts of wind   : one word per step taken from a cell with wind while gust_q16 > 0 (gu_set_wind), counter and epoch
+                                as stream 4; the strength k changes iff (word >> 16) < gust_q16, to k + 1 if word & 1 else k - 1
 
 These helpers let a caller reproduce on the host exactly what a `policy='uniform'` rollout did on the device -- e.g.
 to replay the same (grid, seed, action) sequence through the reference's own `step()`.
@@ -74,3 +76,10 @@ def epsilon_greedy_words(seed, env_ids, t0, T):
     t = np.arange(T, dtype=np.uint64)[:, None] + np.asarray(t0, dtype=np.uint64)
     env = np.asarray(env_ids, dtype=np.uint64)[None, :]
     return words(seed, env, 4, t & _M32, t >> np.uint64(32))
+
+
+def wind_words(seed, env_ids, t):
+    """uint32: the stream-9 words behind the gusts of the steps at 64-bit step counts `t` of global env ids `env_ids` (the two
+    broadcast against each other); see gu_set_wind in include/gu.h."""
+    t = np.asarray(t, dtype=np.uint64)
+    return words(seed, np.asarray(env_ids, dtype=np.uint64), 9, t & _M32, t >> np.uint64(32))

@@ -17,7 +17,7 @@ for byte (see `parallel.py`).
 from . import _lib, softmax
 from .engine import Engine
 from .envs.griduniverse_env import GridUniverseEnv
-from .grid import GridSpec
+from .grid import GridSpec, wind_plane
 
 
 def check_off_policy_args(max_episode_len, epsilon, w_cap):
@@ -125,6 +125,29 @@ class VecGridUniverse(object):
         if stats:
             out['ret'], out['episodes'] = self.engine.read_stats()
         return out
+
+    def set_wind(self, strength, direction='up', gust=0.0):
+        """Wind on the engine's grid (single-grid engines; include/gu.h: gu_set_wind): every step, the agent is pushed behind its
+        action by the wind of the cell it leaves -- `strength` (0 .. 3) moves in `direction`, each by the engine's move rule, so walls
+        and the border stop a push and an agent blown onto a goal or lava cell stays there.  With probability `gust` (0 .. 1) a
+        strength above 0 is one more or one less for that step (2/3: one third each for k - 1, k, k + 1).  `strength` and
+        `direction` as grid.wind_plane takes them; set_wind(None) calms the engine.  step, rollout and td_run follow the wind;
+        the other learners, the DP and look-ahead calls, the path search and the trail are refused while it is set."""
+        gust = float(gust)
+        if not 0.0 <= gust <= 1.0:  # (NaN fails too)
+            raise ValueError('gust must lie in [0, 1]')
+        if strength is None:
+            self.engine.set_wind(None)
+            return
+        self.engine.set_wind(wind_plane(self.spec.W, self.spec.H, strength, direction), int(round(gust * 65536)))
+
+    def wind(self):
+        """None while the engine is calm, else dict(strength=uint8[H, W], direction=uint8[H, W], gust=float)."""
+        got = self.engine.get_wind()
+        if got is None:
+            return None
+        plane = got[0].reshape(self.spec.H, self.spec.W)
+        return dict(strength=(plane >> 2) & 3, direction=plane & 3, gust=got[1] / 65536.0)
 
     def _ensure_q(self, q0=None):
         """Q tables on the engine: tables of zeros on first use; every entry q0 (again) when q0 is given."""

@@ -174,6 +174,37 @@ int gu_generate_mazes(gu_handle h, int32_t n_grids, int32_t W, int32_t H, uint64
  * reward[S] (int8), and its start table (any pointer may be NULL). */
 int gu_get_cells(gu_handle h, int32_t grid_index, uint8_t *flags, int8_t *reward, int32_t *starts, int32_t *n_starts);
 
+/* ---- wind: per-cell pushes with gusts (Sutton & Barto's windy gridworld, Example 6.5, and its stochastic form, Exercise 6.10) ----
+ * Build-defined (the reference has no wind; restated on the CPU by tests/_wind_oracle.py).  Wind is a property of a SINGLE-GRID
+ * engine: one byte per cell, wind[s] bits 0..1 the direction (the action codes UP, RIGHT, DOWN, LEFT), bits 2..3 the strength k
+ * (0 .. 3), bits 4..7 zero, and an engine-wide gust probability gust_q16 in 0 .. 65536 (gust_q16 = round(gust * 65536); gust = 2/3,
+ * 43691, is Exercise 6.10's one third each for k - 1, k and k + 1).
+ * One step of env e at 64-bit step count t, from cell s (after the lazy reset, where there is one), with a valid action a:
+ *   1. c = wind[s], the wind of the cell the agent LEAVES; k = (c >> 2) & 3, dir = c & 3.
+ *   2. If k > 0 and gust_q16 > 0: w = the word of RNG stream 9 with counter t & 0xFFFFFFFF and epoch t >> 32 (keyed exactly like
+ *      stream 4); if (w >> 16) < gust_q16 then k += (w & 1) ? +1 : -1.  So k ends in 0 .. 4.
+ *   3. s1 = move(s, a); then k times s1 = move(s1, dir).
+ *   4. move is the engine's rule as it stands: the OPEN bit of the cell's flags, with the absorbing terminal.  A wall or the border
+ *      stops a push, and an agent blown ONTO a goal or lava cell stays there (its OPEN bits are zero).
+ *   5. reward and done come from the final cell; then t += 1.
+ * An action that gu_step rejects moves nothing and draws nothing; a launch with gust_q16 == 0 hashes no word; wind of strength 0
+ * everywhere gives the bytes of the calm engine.  This differs from Sutton & Barto's vector-sum rule in one point -- an agent
+ * cannot be blown ACROSS a terminal cell: on the book's 10 x 7 grid (column strengths 0 0 0 1 1 1 2 2 1 0 upward, start (0, 3), goal
+ * (7, 3)) the shortest path has 10 moves (15 under the book's rule) and 62 of the 70 cells can be reached.
+ * While wind is set, gu_step, gu_step_device, gu_rollout (all four policies; GU_F_PACKED is refused) and gu_td_run (both methods)
+ * run their windy kernels (csrc/gu_wind.hip, csrc/gu_td.hip); every other call that moves envs or reads the move rule --
+ * gu_step_graph, the other learners' gu_*_run, gu_look_step_ahead, gu_vi_sweep / _run / _eval_run / _greedy / _sweep_step /
+ * _sweep_step_run, gu_mc_walk_lengths / _episodes, gu_shortest_paths -- returns GU_ERR_UNSUPPORTED.  Calls that read rows or state
+ * only (gu_vi_set / _get, gu_mc_evaluate, sense, render, state, reset, seed, the tables' getters and setters) are unaffected.
+ * gu_set_wind: wind[S], or NULL = calm again (the calm kernels run as before).  GU_ERR_STATE without a grid; GU_ERR_UNSUPPORTED on a
+ *              multi-grid engine and while the agent trail is on (gu_trail_enable refuses while wind is set); GU_ERR_INVALID for a
+ *              byte with bits 4..7 set or gust_q16 > 65536.  Ends what the learners carry from launch to launch (SARSA actions,
+ *              windows, episode buffers); keeps tables, env state and step counts.  gu_set_grid, gu_set_grids and
+ *              gu_generate_mazes drop the wind.
+ * gu_get_wind: the plane (zeros when calm), the gust probability and whether wind is set; any pointer may be NULL. */
+int gu_set_wind(gu_handle h, const uint8_t *wind /* [S], NULL = calm again */, uint32_t gust_q16);
+int gu_get_wind(gu_handle h, uint8_t *wind /* [S], may be NULL */, uint32_t *gust_q16, int32_t *present);
+
 /* ---- RNG ---------------------------------------------------------------------
  * Keys the per-env counter RNG (MurmurHash3 of seed, global env id, stream,
  * counter -- 32-bit counters, no stream repeats before 2^32 draws; host view:
