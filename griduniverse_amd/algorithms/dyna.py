@@ -5,10 +5,17 @@ and plans"; it ships no code for it, so the semantics are this build's: include/
 `dyna_q` runs `num_learners` independent learners on the grid of a facade `GridUniverseEnv`, learner e in env e of a batch, each
 with its own float64 Q table and its own model, all advanced on the MI355X by one kernel (csrc/gu_dyna.hip).  Its result has the
 shape of `q_learning`'s and feeds `greedy_policy` the same way.
+
+`prioritized_sweeping` (Sutton & Barto 8.4; include/gu.h, gu_sweep_run; csrc/gu_sweep.hip) keeps the same model and spends its
+planning updates where they change something: every learner has a priority queue of observed pairs, ordered by the size of the
+update waiting for them, takes its planning updates from the top and queues the predecessors of what it updated.
 """
+import math
+
 from .temporal_difference import _learn
 
 MAX_PLANNING_STEPS = 256
+MAX_SWEEP_STATES = 16384  # the queue's keys hold the pair index s*4+a in 16 bits
 _UPDATES = 1000000  # real steps x (planning steps + 1) per launch (the launch limit is 1e8; shorter launches keep the device responsive)
 
 
@@ -27,3 +34,28 @@ def dyna_q(env, num_steps, planning_steps=10, alpha=0.1, discount_factor=0.99, e
         raise ValueError('num_steps must not be negative')
     return _learn(env, L, seed, q0, num_steps, max(1, _UPDATES // (P + 1)),
                   lambda vec, T: vec.dyna_run(T, P, alpha, discount_factor, epsilon), model=True)
+
+
+def prioritized_sweeping(env, num_steps, planning_steps=10, theta=1e-4, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0,
+                         q0=0.0):
+    """Epsilon-greedy prioritized sweeping, `num_steps` real env steps per learner (episodes restart at a start cell when they end).
+    A real step queues its pair when its |TD error| exceeds `theta` (finite, not negative) and is followed by up to `planning_steps`
+    (0 .. 256) updates from the top of the learner's priority queue, each of which queues the predecessors of its pair; a real step
+    updates nothing by itself.  Returns Q float64[S][4], or [L][S][4] for L = num_learners > 1."""
+    L, P, theta = int(num_learners), int(planning_steps), float(theta)
+    if L < 1:
+        raise ValueError('num_learners must be at least 1')
+    if not 0 <= P <= MAX_PLANNING_STEPS:
+        raise ValueError('planning_steps must lie in 0 .. {}'.format(MAX_PLANNING_STEPS))
+    if not 0.0 <= float(epsilon) <= 1.0:
+        raise ValueError('epsilon must lie in [0, 1]')
+    if not (math.isfinite(theta) and theta >= 0.0):
+        raise ValueError('theta must be finite and not negative')
+    if int(num_steps) < 0:
+        raise ValueError('num_steps must not be negative')
+    if int(env.world.size) > MAX_SWEEP_STATES:
+        raise ValueError('prioritized sweeping takes grids of at most {} states'.format(MAX_SWEEP_STATES))
+
+    def launch(vec, T):
+        vec.sweep_run(T, P, theta, alpha, discount_factor, epsilon)
+    return _learn(env, L, seed, q0, num_steps, max(1, _UPDATES // (P + 1)), launch)

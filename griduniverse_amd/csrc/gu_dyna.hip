@@ -23,8 +23,6 @@
 // its action from the table after planning.
 #include "gu_tabular.hpp"
 
-#define GU_DYNA_UNSEEN (~0ull)
-
 struct DynaArgs : TabArgs {
     int32_t P;
     uint64_t *model;  // [N][S*4]
@@ -33,11 +31,6 @@ struct DynaArgs : TabArgs {
     uint8_t *seen;    // [N][S] bit a of byte s: (s, a) observed
     int32_t exact;    // 1: the model holds only outcomes of the current cells (the seen bits decide); 0: compare every word
 };
-
-__device__ __forceinline__ uint64_t gu_dyna_pack(int32_t s2, int32_t r, int32_t d)
-{
-    return (uint64_t)(uint32_t)r | ((uint64_t)((uint32_t)s2 | ((uint32_t)d << 31)) << 32);
-}
 
 // stream-5 prefix of planning draw c (epoch c >> 32 hashed behind the seed, then the env)
 __device__ __forceinline__ uint32_t gu_dyna_prefix(uint32_t seed_prefix, uint32_t env, uint64_t c)
@@ -155,6 +148,7 @@ static int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, doub
 void gu_dyna_free(gu_engine *h)
 {
     gu_release(h->d_dyna_model, h->d_dyna_list, h->d_dyna_count, h->d_dyna_seen);
+    gu_release(h->d_sweep_heap, h->d_sweep_pos, h->d_sweep_size);  // gu_sweep.hip's queues hold pairs of this model
     h->dyna_S = 0;
     h->dyna_exact = false;
 }
@@ -185,6 +179,7 @@ int gu_dyna_init(gu_handle h)
     GU_HIP(hipMemsetAsync(h->d_dyna_list, 0xFF, pairs * sizeof(int32_t), h->stream));
     GU_HIP(hipMemsetAsync(h->d_dyna_count, 0, (size_t)h->N * sizeof(int32_t), h->stream));
     GU_HIP(hipMemsetAsync(h->d_dyna_seen, 0, (size_t)h->N * (size_t)h->S, h->stream));
+    GU_TRY(gu_sweep_clear(h));  // a queued pair must not outlive its model entry
     GU_HIP(hipStreamSynchronize(h->stream));
     return GU_OK;
 }

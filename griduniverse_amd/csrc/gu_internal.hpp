@@ -306,6 +306,11 @@ struct gu_engine {
     uint8_t *d_dyna_seen = nullptr;    // [N][dyna_S] bit a of byte s: (s, a) observed (the real step's test while dyna_exact)
     int32_t dyna_S = 0;                // states of the model (0: none allocated); a grid of another size drops it
     bool dyna_exact = false;           // every observed entry is what the current grid gives: no grid install since gu_dyna_init
+    // batched prioritized sweeping (gu_sweep.hip): off until gu_sweep_init; learns into d_q from the Dyna-Q model above, with which
+    // the queues are cleared (gu_dyna_init) and dropped (gu_dyna_free): they are sized by dyna_S
+    uint64_t *d_sweep_heap = nullptr;  // [N][dyna_S*4+2] 1-based binary max-heap of keys (priority pattern | pair); slot 0: pops | inserts << 32
+    int32_t *d_sweep_pos = nullptr;    // [N][dyna_S*4] the heap slot of each pair (-1: not queued)
+    int32_t *d_sweep_size = nullptr;   // [N] keys in the heap
     // batched rollout search (gu_search.hip): decides and learns on d_q; allocated on first use, dropped with the tables
     double *d_search_score = nullptr;   // [N][4] the score row of each env's most recent searched iteration
     int64_t *d_search_steps = nullptr;  // [N] simulated moves of the last launch
@@ -472,12 +477,13 @@ int gu_vi_xcd_dp_run(gu_engine *h, double gamma, double threshold, bool use_thre
                      double *deltas);
 
 // ---- the batched learners ------------------------------------------------------------
-// gu_td.hip (Q-learning, SARSA), gu_dyna.hip (Dyna-Q), gu_nstep.hip, gu_lambda.hip, gu_search.hip (rollout search), gu_explore.hip
+// gu_td.hip (Q-learning, SARSA), gu_dyna.hip (Dyna-Q), gu_sweep.hip (prioritized sweeping), gu_nstep.hip, gu_lambda.hip, gu_search.hip (rollout search), gu_explore.hip
 // (UCB / Thompson), gu_mcts.hip (tree search), gu_is.hip (off-policy Monte-Carlo), gu_ac.hip (actor-critic), gu_reinforce.hip and
 // gu_fa.hip (semi-gradient learners on features) each hold their kernels, their launch code and their extern "C" functions
 // (include/gu.h); the host helpers they share are in gu_tabular.hpp.  What they export to each other is their gu_*_free: the device
 // buffers of the module and the fields that describe them, back to "none".
-void gu_dyna_free(gu_engine *h);
+void gu_dyna_free(gu_engine *h);        // (takes gu_sweep.hip's queues along)
+int gu_sweep_clear(gu_engine *h);       // gu_sweep.hip: empty queues, queued on the stream (gu_dyna_init clears them with the model)
 void gu_nstep_free(gu_engine *h);
 void gu_lambda_free(gu_engine *h);
 void gu_search_free(gu_engine *h);

@@ -1,4 +1,4 @@
-// gu_tabular.hpp -- the core of the batched tabular learners for gfx950 (gu_td.hip: Q-learning and SARSA; gu_dyna.hip: Dyna-Q;
+// gu_tabular.hpp -- the core of the batched tabular learners for gfx950 (gu_td.hip: Q-learning and SARSA; gu_dyna.hip: Dyna-Q; gu_sweep.hip: prioritized sweeping;
 // gu_nstep.hip: n-step Q-learning and SARSA; gu_lambda.hip: SARSA(lambda) and Watkins's Q(lambda)); gu_fa.hip (semi-gradient
 // SARSA / Q-learning on features) uses the lane without its table.
 // N independent learners, learner e owns env e and its own float64 table Q_e[S][4], advanced T real steps per launch.  The
@@ -94,6 +94,15 @@ __device__ __forceinline__ uint32_t gu_q_action(const QRow &q, uint32_t w, uint3
     a = (e2 && k == e0 + e1) ? 2u : a;
     a = (e3 && k == e0 + e1 + e2) ? 3u : a;
     return (w >> 16) < eps_q16 ? (w & 3u) : a;
+}
+
+// ---- the Dyna-Q model word of one (s, a) (gu_dyna.hip records and replays it, gu_sweep.hip sweeps over it): low half the reward
+// (int32), high half s' | done << 31; all ones = never observed ----
+#define GU_DYNA_UNSEEN (~0ull)
+
+__device__ __forceinline__ uint64_t gu_dyna_pack(int32_t s2, int32_t r, int32_t d)
+{
+    return (uint64_t)(uint32_t)r | ((uint64_t)((uint32_t)s2 | ((uint32_t)d << 31)) << 32);
 }
 
 // ---- the lane: state, prologue, auto-reset, move, Q[s][a] update, record, epilogue ----
@@ -227,7 +236,7 @@ struct TabLane {
 };
 
 // ---- host side ----
-// What the learners' entry points share: gu_td.hip, gu_dyna.hip, gu_nstep.hip, gu_lambda.hip, gu_search.hip, gu_explore.hip,
+// What the learners' entry points share: gu_td.hip, gu_dyna.hip, gu_sweep.hip, gu_nstep.hip, gu_lambda.hip, gu_search.hip, gu_explore.hip,
 // gu_mcts.hip, gu_is.hip, gu_ac.hip, gu_reinforce.hip and gu_fa.hip each hold their own extern "C" functions and their gu_*_free;
 // the checks, copies and stores they have in common are here.
 

@@ -386,6 +386,34 @@ class Engine(object):
                                          ptr(out['list']), ptr(out['count'])))
         return out
 
+    # ------------------------------------------------------------------ prioritized sweeping (include/gu.h: gu_sweep_*)
+    def sweep_init(self):
+        """dyna_init plus an empty priority queue per env (a grid of more than 16 384 states: GU_ERR_INVALID)."""
+        check(self.lib.gu_sweep_init(self._h))
+
+    def sweep_run(self, T, planning_steps=10, theta=1e-4, alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
+        """T real steps per env in one launch; each records its outcome in the env's model, queues its pair under |TD error| (above
+        `theta`) and is followed by up to `planning_steps` updates of the pair with the largest priority, whose predecessors are
+        queued in turn.  Rows and statistics (real steps only) as td_run()."""
+        check(self.lib.gu_sweep_run(self._h, int(T), int(planning_steps), float(theta), float(alpha), float(gamma), int(eps_q16),
+                                    _learner_flags(trajectory, stats)))
+
+    def sweep_get_queue(self, env0=0, n=None):
+        """The queues of envs env0 .. env0+n-1: dict key uint64[n, S, 4] (0 = not queued) and size int32[n]."""
+        env0, n, n0 = self._env_range(env0, n)
+        out = dict(key=np.empty((n0, self.spec.S, 4), np.uint64), size=np.empty(n0, np.int32))
+        check(self.lib.gu_sweep_get_queue(self._h, env0, n, ptr(out['key']), ptr(out['size'])))
+        return out
+
+    def diag_sweep_heap(self, env0=0, n=None):
+        """The device's raw form of those queues: dict heap uint64[n, 4S+2] (a 1-based binary max-heap in slots 1 .. size; slot 0:
+        pops | inserts << 32 since sweep_init) and pos int32[n, 4S] (the slot of each queued pair, -1 elsewhere)."""
+        env0, n, n0 = self._env_range(env0, n)
+        S = self.spec.S
+        out = dict(heap=np.empty((n0, 4 * S + 2), np.uint64), pos=np.empty((n0, 4 * S), np.int32))
+        check(self.lib.gu_diag_sweep_heap(self._h, env0, n, ptr(out['heap']), ptr(out['pos'])))
+        return out
+
     # ------------------------------------------------------------------ rollout search at decision time (include/gu.h: gu_search_*)
     def search_run(self, T, simulations=4, depth=16, alpha=0.1, gamma=0.99, eps_q16=6554, eps_sim_q16=65536, trajectory=False,
                    stats=False):

@@ -14,6 +14,8 @@ keyed by GLOBAL env id, so the union of the shards equals the single-device batc
 for byte (see `parallel.py`).
 """
 
+import numpy as np
+
 from . import _lib, softmax
 from .engine import Engine
 from .envs.griduniverse_env import GridUniverseEnv
@@ -33,6 +35,7 @@ def check_off_policy_args(max_episode_len, epsilon, w_cap):
 class VecGridUniverse(object):
     _td_ready = False  # the engine holds Q tables (td_run / set_q_table allocate them on first use)
     _dyna_ready = False  # ... and Dyna-Q models (dyna_run / model allocate them on first use)
+    _sweep_ready = False  # ... and priority queues (sweep_run / priority_queue allocate them, with the models, on first use)
     _explore_ready = False  # ... and visit counts (explore_run / visit_counts allocate them on first use)
     _explore_tables = False  # set_exploration was called
     _tree_sims = 0  # simulations the tree-search node pools hold (tree_search_run allocates them on first use and when it needs more)
@@ -203,6 +206,33 @@ class VecGridUniverse(object):
         """The Dyna-Q models of envs env0 .. env0+n-1 (Engine.dyna_get_model); an empty model is allocated on first use."""
         self._ensure_model()
         return self.engine.dyna_get_model(env0, n)
+
+    def _ensure_queue(self):
+        """Priority queues (and Dyna-Q models) on the engine: empty ones on first use."""
+        if not self._sweep_ready:
+            self.engine.sweep_init()
+            self._sweep_ready = self._dyna_ready = True
+
+    def sweep_run(self, T, planning_steps=10, theta=1e-4, alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
+        """T real steps of batched tabular prioritized sweeping (Sutton & Barto 8.4): env e keeps its own Q table, its own model of
+        the env (dyna_run's) and its own priority queue.  A real step learns nothing by itself: its pair is queued under its
+        |TD error| when that exceeds `theta`, and up to `planning_steps` times the pair with the largest priority is updated from the
+        model and its predecessors are queued (include/gu.h: gu_sweep_run).  The first call gives every env a table of zeros (if
+        it had none), an empty model and an empty queue.  Rows and statistics cover the real steps, as td_run()."""
+        self._ensure_q()
+        self._ensure_queue()
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.sweep_run(T, planning_steps, theta, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def priority_queue(self, env0=0, n=None):
+        """The priority queues of envs env0 .. env0+n-1: dict key uint64[n, S, 4] (0 = not queued), priority float64[n, S, 4] (the
+        key with its low 16 bits, the pair index, cleared; 0.0 where the pair is not queued) and size int32[n]."""
+        self._ensure_queue()
+        out = self.engine.sweep_get_queue(env0, n)
+        out['priority'] = (out['key'] & ~np.uint64(0xFFFF)).view(np.float64)
+        return out
 
     def search_run(self, T, simulations=4, depth=16, alpha=0.1, discount_factor=0.99, epsilon=0.1, rollout_epsilon=1.0, trajectory=False,
                    stats=False):

@@ -293,7 +293,7 @@ int gu_done_indices(gu_handle h, int32_t *idx, int32_t *count);
  *      the row maximum exactly, in ascending order, the one at index (((w >> 2) & 0x3FFF) * m) >> 14.  SARSA uses the carried
  *      action a' instead -- inside a launch always, and at its start when it directly follows a SARSA gu_td_run on this engine
  *      (no gu_seed, gu_reset*, gu_step*, gu_rollout, gu_set_state, gu_set_grid(s), gu_generate_mazes, gu_td_init, gu_td_set_q, gu_dyna_run,
- *      gu_nstep_run, gu_search_run, gu_explore_run, gu_mcts_run or sweep-step call in between);
+ *      gu_sweep_run, gu_nstep_run, gu_search_run, gu_explore_run, gu_mcts_run or sweep-step call in between);
  *   3. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
  *   4. float64, one rounding per operation: m = max Q_e[s'] (Q-learning) or Q_e[s'][a'] with a' drawn at s' by rule 2 from the word
  *      of the new t and the pre-update row (SARSA; not drawn when d); target = r if d else r + gamma * m;
@@ -337,6 +337,51 @@ int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q);
 int gu_dyna_init(gu_handle h);
 int gu_dyna_run(gu_handle h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 int gu_dyna_get_model(gu_handle h, int64_t env0, int64_t n, int32_t *next, int32_t *reward, int32_t *done, int32_t *list, int32_t *count);
+
+/* ---- batched prioritized sweeping: learner e owns env e, its table Q_e[S][4] (the gu_td_* tables), its Dyna-Q model and a queue ----
+ * (build-defined: the reference ships no code for it; Sutton & Barto 8.4; tests/_sweep_oracle.py is the CPU restatement.)  The model
+ * is the one gu_dyna_run fills (next / reward / done / list / count above, the same buffers).  The queue of learner e is a set of
+ * observed pairs p = s*4+a, each under a 64-bit key:
+ *   key(p, x) = ((bits(x) >> 16) << 16) | p for a float64 priority x > 0, bits(x) its pattern: the priority truncated to 36 mantissa
+ *   bits, ties broken by the larger pair index.  The pair index has 16 bits, so the queue needs 4 * S <= 65 536 (S <= 16 384: a
+ *   128 x 128 grid fits).  Key 0 = not queued.  Keys are ordered as uint64, a total order: what a pop returns does not depend on how
+ *   the device stores the queue.
+ *   insert(p, x): only if x > theta and (bits(x) >> 16) != 0 (a NaN x fails the first test); then key_e[p] = max(key_e[p], key(p, x)) --
+ *   a pair that is queued keeps the larger priority.
+ * One iteration of gu_sweep_run for env e at 64-bit step count t:
+ *   1. real step: rules 1-3 of gu_td_run, method 0 (lazy auto-reset, the stream-4 word at count t, epsilon-greedy with its tie rule, the
+ *      move, t += 1) -- and NO update of Q_e[s][a]: all learning goes through the queue;
+ *   2. model: rule 2 of gu_dyna_run, unchanged;
+ *   3. priority of the real pair: target = r if d, else r + gamma * max Q_e[s'] (folded left to right with `>`); x = |target -
+ *      Q_e[s][a]|, float64, one rounding per operation; insert(s*4+a, x);
+ *   4. planning: up to P times, ending early when the queue is empty: remove the pair p with the largest key, S = p >> 2, A = p & 3,
+ *      (S', R, D) from the model; tgt = R if D, else R + gamma * max Q_e[S'] over the row as it is now; Q_e[S][A] += alpha * (tgt -
+ *      Q_e[S][A]); then for every candidate cell c of {S, S - W, S + 1, S + W, S - 1} with 0 <= c < S_cells (W = the current grid's
+ *      width) and every action b of 0 .. 3 whose pair (c, b) is observed with next_e[c][b] == S: with (R', D') of that pair,
+ *      x' = |(R' if D' else R' + gamma * max Q_e[S]) - Q_e[c][b]|, insert(c*4+b, x').  (Inserts commute and Q is only read, so the
+ *      order of the candidates does not matter.  A move displaces the agent by at most one cell and nothing wraps, so on a model
+ *      recorded under the current grid these 20 candidates are ALL predecessors of S; the rule is geometric so that it stays
+ *      defined on a model kept across a grid install of equal S and another W.)
+ *   5. the next iteration chooses its action from the table after planning.
+ * Trajectory rows and GU_F_STATS cover the real steps only.  The step counts advance by T.  Planning draws nothing: no RNG stream.
+ * gu_sweep_init      : gu_dyna_init (allocate the model if need be, clear it), plus the queue: allocated if need be (N * (S * 48 + 20)
+ *                      bytes under gu_td_init's free-memory rule) and emptied.  GU_ERR_INVALID if 4 * S > 65 536.  gu_dyna_init
+ *                      empties an existing queue with the model (a queued pair never outlives its model entry); a grid of another
+ *                      size drops the queue with the model.
+ * gu_sweep_run       : T iterations per env with up to P planning updates each, in ONE launch (async).  GU_ERR_STATE without Q tables
+ *                      (gu_td_init) or without a queue for the current S; GU_ERR_INVALID for P < 0 or P > 256, theta negative or not
+ *                      finite, T * (P + 1) > 1e8, and everything gu_dyna_run rejects.  T = 0 changes nothing.  Flags as gu_td_run.
+ *                      Refused while wind is set, as gu_dyna_run; ends the other learners' carries as gu_dyna_run does.
+ * gu_sweep_get_queue : the queues of envs env0 .. env0+n-1 on the host: key as [n][S][4] (0 = not queued), size as [n]; either
+ *                      pointer may be NULL.
+ * gu_diag_sweep_heap : introspection -- the device's raw form of those queues, one binary max-heap per env: heap as [n][4S+2]
+ *                      (slots 1 .. size hold the keys, every parent i >= its children 2i and 2i+1; slot 0 holds two counters since
+ *                      gu_sweep_init, pops in the low half and inserts that changed the queue in the high half, each modulo 2^32; the
+ *                      other slots are stale), pos as [n][4S] (the slot of each queued pair, -1 elsewhere); either may be NULL. */
+int gu_sweep_init(gu_handle h);
+int gu_sweep_run(gu_handle h, int64_t T, int32_t P, double theta, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+int gu_sweep_get_queue(gu_handle h, int64_t env0, int64_t n, uint64_t *key, int32_t *size);
+int gu_diag_sweep_heap(gu_handle h, int64_t env0, int64_t n, uint64_t *heap, int32_t *pos);
 
 /* ---- batched simulation-based search: learner e owns env e and its table Q_e[S][4] (the gu_td_* tables) and plans at decision time ----
  * (build-defined: the second half of the reference's roadmap entry "Integrating learning and planning (Dyna, MC/TD Tree search,
@@ -509,7 +554,7 @@ int gu_mcts_get_tree(gu_handle h, int64_t env0, int64_t n, int32_t *state, int32
  * All float64, one rounding per operation (multiply, then add).  With n = 1 this is gu_td_run, byte for byte, for both methods.
  * CARRY: the window and SARSA's a' persist from one gu_nstep_run to the next when the later call directly follows the earlier one
  * with the same method and n.  Any other call in between -- everything that ends gu_td_run's SARSA carry, gu_td_run,
- * gu_dyna_run, gu_search_run, a gu_nstep_run with another method or n -- drops both; the pending updates are discarded, not flushed.
+ * gu_dyna_run, gu_sweep_run, gu_search_run, a gu_nstep_run with another method or n -- drops both; the pending updates are discarded, not flushed.
  * gu_nstep_run ends gu_td_run's SARSA carry.
  * gu_nstep_run        : T iterations per env in ONE launch (async).  method 0 = n-step Q-learning, 1 = n-step SARSA; 1 <= n <=
  *                       GU_NSTEP_MAX.  GU_ERR_STATE before gu_td_init; GU_ERR_INVALID for a bad method or n and everything
@@ -544,7 +589,7 @@ int gu_nstep_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32
  * With K = 1 (any lambda) or lambda = 0 (any K) this is gu_td_run, byte for byte: method 0 is Q-learning, 1 is SARSA.
  * CARRY: the window and SARSA's a' persist from one gu_lambda_run to the next when the later call directly follows the earlier one
  * with the same method and K (alpha, gamma and lambda may change: the ages carry, the new c applies).  Any other call in between --
- * everything that ends gu_td_run's SARSA carry, gu_td_run, gu_dyna_run, gu_nstep_run, gu_ac_run, gu_search_run, a gu_lambda_run with another
+ * everything that ends gu_td_run's SARSA carry, gu_td_run, gu_dyna_run, gu_sweep_run, gu_nstep_run, gu_ac_run, gu_search_run, a gu_lambda_run with another
  * method or K -- drops both.  gu_lambda_run ends gu_td_run's SARSA carry and gu_nstep_run's window.
  * gu_lambda_run        : T iterations per env in ONE launch (async).  method 0 = Watkins's Q(lambda), 1 = SARSA(lambda); 1 <= K
  *                        <= GU_LAMBDA_MAX; 0 <= lambda <= 1.  GU_ERR_STATE before gu_td_init; GU_ERR_INVALID for a bad method,
@@ -617,7 +662,7 @@ int gu_ac_set(gu_handle h, int64_t env0, int64_t n, const double *pref, const do
  * With alpha_baseline = 0 and V = 0 this is plain REINFORCE.  With L = 1 it is gu_ac_run, byte for byte.
  * CARRY: the buffer persists from one gu_reinforce_run to the next when the later call directly follows the earlier one with the
  * same L (the rates and gamma may change).  Any other call in between -- everything that drops gu_lambda_run's window, and
- * gu_td_run, gu_dyna_run, gu_nstep_run, gu_lambda_run, gu_ac_run, gu_search_run, gu_ac_init, gu_ac_set, a gu_reinforce_run with another L --
+ * gu_td_run, gu_dyna_run, gu_sweep_run, gu_nstep_run, gu_lambda_run, gu_ac_run, gu_search_run, gu_ac_init, gu_ac_set, a gu_reinforce_run with another L --
  * drops it: the pending transitions are discarded, not learned from.  gu_reinforce_run ends gu_td_run's SARSA carry and the
  * windows of gu_nstep_run and gu_lambda_run.
  * gu_reinforce_run         : T iterations per env in ONE launch (async).  1 <= L <= GU_REINFORCE_MAX.  GU_ERR_STATE before
