@@ -107,6 +107,7 @@ SIGNATURES = {
     'gu_sweep_run': [_vp, _i64, _i32, _f64, _f64, _f64, _u32, _u32],
     'gu_sweep_get_queue': [_vp, _i64, _i64, _vp, _vp],
     'gu_diag_sweep_heap': [_vp, _i64, _i64, _vp, _vp],
+    'gu_diag_rollout_form': [_vp, _vp, _i32, _vp],
     'gu_search_run': [_vp, _i64, _i32, _i32, _f64, _f64, _u32, _u32, _u32],
     'gu_search_get': [_vp, _i64, _i64, _vp, _vp],
     'gu_explore_init': [_vp],

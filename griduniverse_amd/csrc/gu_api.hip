@@ -4,6 +4,7 @@
 // knows of them is gu_learners_drop (gu_internal.hpp).
 #include "gu_internal.hpp"
 #include "gu_rng.hpp"
+#include "gu_rollout_plan.hpp"
 
 #include <atomic>
 #include <cmath>
@@ -175,8 +176,6 @@ int gu_destroy(gu_handle h)
     if (h->h_up) (void)hipHostFree(h->h_up);
     if (h->d_blocks_done) (void)hipFree(h->d_blocks_done);
     for (hipEvent_t ev : h->ev_marks) (void)hipEventDestroy(ev);
-    for (hipEvent_t ev : h->ev_cal)
-        if (ev) (void)hipEventDestroy(ev);
     if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
     if (h->ev_end) (void)hipEventDestroy(h->ev_end);
     if (h->ev_sync) (void)hipEventDestroy(h->ev_sync);
@@ -937,6 +936,18 @@ int gu_rollout(gu_handle h, int64_t T, int32_t policy_kind, uint32_t flags)
     return rc;
 }
 
+int gu_diag_rollout_form(gu_handle h, int32_t *form, int32_t capacity, int32_t *count)
+{
+    GU_ENTER(h);
+    const int32_t n = (int32_t)(sizeof h->rollout_form / sizeof h->rollout_form[0]);
+    if (count) *count = n;
+    if (form) {
+        GU_REQUIRE(capacity >= n, GU_ERR_INVALID, "room for %d words, the form has %d", capacity, n);
+        std::copy(h->rollout_form, h->rollout_form + n, form);
+    }
+    return GU_OK;
+}
+
 int gu_rollout_calibrate(gu_handle h, int64_t T, int32_t policy_kind, uint32_t flags)
 {
     // (rounds 3 and 4: gu_rollout with the pacing search made now.  There is no search any more -- the launches of a kind choose
@@ -948,15 +959,13 @@ int gu_rollout_calibrate(gu_handle h, int64_t T, int32_t policy_kind, uint32_t f
 static int gu_pace_slot_in_use(gu_engine *h, int32_t policy_kind, uint32_t flags)
 {
     const int auto_mode = (flags & GU_F_AUTO_RESET) ? (h->all_single_start ? 1 : 2) : 0;
-    if (flags & GU_F_PACKED) {  // packed rows: the transition-row kernel's ring of its own
-        const int slot = 24 + policy_kind * 3 + auto_mode;
-        return h->pace[slot].active && h->pace[slot].seq && h->pace[slot].buffer == (const void *)h->d_traj ? slot : -1;
-    }
     int found = -1;
     uint32_t most = 0;
-    for (int base : {0, 12}) {
-        const gu_engine::PaceKind &k = h->pace[base + policy_kind * 3 + auto_mode];
-        if (k.active && k.seq > most && k.buffer == (const void *)h->d_traj) found = base + policy_kind * 3 + auto_mode, most = k.seq;
+    for (const bool row_kernel : {false, true}) {
+        if ((flags & GU_F_PACKED) && !row_kernel) continue;  // packed rows: the transition-row kernel's ring of its own
+        const int slot = gu_pace_slot(row_kernel, (flags & GU_F_PACKED) ? 2 : 1, policy_kind, auto_mode);
+        const gu_engine::PaceKind &k = h->pace[slot];
+        if (k.active && k.seq > most && k.buffer == (const void *)h->d_traj) found = slot, most = k.seq;
     }
     return found;
 }

@@ -42,6 +42,7 @@
 #define GU_ACTION_OK(raw) ((uint32_t)((int32_t)(raw) + 4) < 8u)
 #define GU_CELL_WALL 0x80u  /* the cell itself is a wall (only the path search needs it: wall nodes have no edges) */
 
+#define GU_BLOCK 256 /* workgroup of every kernel that has no reason for another size */
 #define GU_MAX_LDS_CELLS 32767 /* both planes of grids up to 32 767 cells (64 KiB) are LDS-resident; larger read L2 */
 
 #define GU_HOST_ERR_WORD 4
@@ -184,7 +185,7 @@ struct gu_engine {
     bool traj_registered = false;               // counted in the per-device registry of chosen buffers
 
     // store pacing of the launches that write rows (gu_rollout.hpp: GuPacer): one ring of launch records per launch kind
-    // [policy * 3 + auto mode] for the general kernel, + 12 for the transition-row kernel's int32 rows, + 24 for its packed rows
+    // (gu_rollout_plan.hpp: gu_pace_slot -- policy x auto mode for the general kernel, the transition-row kernel's int32 and packed rows)
     struct PaceKind {
         bool active = false;           // the kind's ring is in use
         const void *buffer = nullptr;  // the launch shape the ring belongs to: trajectory buffer, workgroups, launch length (within
@@ -198,7 +199,7 @@ struct gu_engine {
     GuPaceEntry *d_pace_ring = nullptr;  // [36][GU_PACE_RING]
     uint64_t *d_pace_slots = nullptr;    // [36][2][pace_slot_stride] the waves' reports (allocated with the ring)
     int64_t pace_slot_stride = 0;
-    hipEvent_t ev_cal[2] = {nullptr, nullptr};
+    int32_t rollout_form[12] = {};       // what the last rollout launch ran on (include/gu.h: gu_diag_rollout_form); zeros: none yet
 
     // transition-row tables of the latency-bound rollout (gu_rollout_rows.hip): [0] absorbing, [1] auto-reset folded in
     uint32_t *d_rows[2] = {nullptr, nullptr};
@@ -425,7 +426,6 @@ int gu_launch_reset(gu_engine *h, const uint8_t *d_mask, const int32_t *d_choice
 int gu_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs = nullptr,
                    int32_t *host_reward = nullptr, int32_t *host_done = nullptr, uint32_t *host_seq = nullptr, uint32_t seq = 0,
                    uint32_t *host_err = nullptr);
-int gu_launch_validate_actions(gu_engine *h, const int32_t *d_actions, int64_t count);
 int gu_launch_pack_actions(gu_engine *h, int64_t T);  // validates h->d_actions[0 .. T) and fills h->d_actions_packed
 int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags);
 int gu_launch_lookahead(gu_engine *h, int64_t n, const int32_t *d_states, const int32_t *d_actions, bool care,
@@ -433,9 +433,9 @@ int gu_launch_lookahead(gu_engine *h, int64_t n, const int32_t *d_states, const 
 int gu_launch_done_compact(gu_engine *h);
 int gu_launch_deinterleave(gu_engine *h, const int32_t *triples, int32_t *planes, int64_t count);  // [count][3] -> [3][count]
 int gu_probe_trajectory_buffer(gu_engine *h, int32_t *buf, int64_t T, float *ms);  // one timed full write, rollout store shape
-// Device-to-device copy by a kernel on the engine's stream (bytes a multiple of 4): the snapshots that the pace calibration and the
-// DP cluster launches take of the engine's state, and put back, stay on the kernel path (ordered with the launches around them,
-// no copy-engine round trip for a few hundred KB).
+// Device-to-device copy by a kernel on the engine's stream (bytes a multiple of 4): the snapshots that the DP cluster launches take
+// of the engine's state, and put back, stay on the kernel path (ordered with the launches around them, no copy-engine round trip
+// for a few hundred KB).
 int gu_device_copy(gu_engine *h, void *dst, const void *src, size_t bytes);
 #define GU_MAX_SEGMENTS 8
 struct GuSegments {  // gu_device_segments: copies (src != nullptr) and fills with zero (src == nullptr) of whole 32-bit words, one launch
@@ -513,9 +513,10 @@ static inline void gu_tabular_drop_carry(gu_engine *h)
 
 // ---- wind (gu_wind.hip): the launches that gu_launch_step / gu_launch_rollout hand over while wind is set ----
 struct RolloutArgs;
+struct GuRolloutPlan;
 int gu_wind_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward, int32_t *host_done,
                         uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
-int gu_wind_launch_rollout(gu_engine *h, const RolloutArgs &a, int64_t T, int32_t policy, uint32_t flags);
+void gu_wind_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);  // (the launch alone: gu_launch_rollout checks and completes it)
 void gu_wind_free(gu_engine *h);
 
 // ---- agent trail (gu_trail.hip): no-ops while the trail is off ----------------------

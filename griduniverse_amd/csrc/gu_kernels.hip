@@ -22,16 +22,11 @@
 // every step for no gain.
 #include "gu_rollout.hpp"
 
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 
 #include <algorithm>
 #include <cstring>
-#include <functional>
-#include <map>
-#include <mutex>
-#include <tuple>
 #include <vector>
 
 // ------------------------------------------------------------------------------------
@@ -168,16 +163,6 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_step_kernel(const StepArgs a)
             }
         }
     }
-}
-
-// Validation of a caller-supplied action stream on the device (gu_upload_actions): any value outside -4..3 raises the
-// page-locked error word.  Replaces a serial host loop over T x N values.
-__global__ void __launch_bounds__(256) gu_validate_actions_kernel(const int32_t *__restrict__ actions, int64_t count, uint32_t *host_err)
-{
-    bool bad = false;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x)
-        bad |= !GU_ACTION_OK(actions[i]);
-    if (__ballot(bad) && (threadIdx.x & 63) == 0) __hip_atomic_store(host_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // The uploaded stream as the rollout kernels read it: word [k][env] holds the two-bit actions of steps 16 k .. 16 k + 15 of
@@ -343,9 +328,6 @@ int gu_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, i
     return gu_trail_after_step(h, flags);
 }
 
-static double gu_wall_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-static double g_last_rollout_ms[64];  // per device: when this process last launched a rollout there (is the device at its working clocks?)
-
 __global__ void __launch_bounds__(256) gu_copy_kernel(uint32_t *__restrict__ dst, const uint32_t *__restrict__ src, size_t words)
 {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) dst[i] = src[i];
@@ -406,25 +388,11 @@ int gu_read_back(gu_engine *h, void *dst, const void *src, size_t bytes)
     return GU_OK;
 }
 
-static void gu_rollout_general(gu_engine *h, const RolloutArgs &a, int32_t policy, int auto_mode, int traj, bool stats, int bs)
-{
-    switch (policy) {
-    case GU_POLICY_UNIFORM: gu_rollout_uniform(h, a, auto_mode, traj, stats, bs); break;
-    case GU_POLICY_STREAM: gu_rollout_stream(h, a, auto_mode, traj, stats, bs); break;
-    case GU_POLICY_GREEDY: gu_rollout_greedy(h, a, auto_mode, traj, stats, bs); break;
-    default: gu_rollout_sample(h, a, auto_mode, traj, stats, bs); break;
-    }
-}
-
-// The schedule of this launch.  `slot` = policy * 3 + auto mode (+ 12 for the transition-row kernel's int32 rows, + 24 for its packed
-// rows, `row_bytes` = 12 / 4 per env-step).  (The open-loop period search of rounds 3 and 4 is gone from the library: docs/HISTORY.md.)
+// The schedule of this launch: the plan names the kind's slot (gu_pace_slot), the bytes per env-step and whether the launch can be
+// bound by the HBM write path (gu_pace_eligible).  (The open-loop period search of rounds 3 and 4 is gone from the library: docs/HISTORY.md.)
 //   GU_OPT_ROLLOUT_PACE = 0: no limiter.  n > 0: that period, fixed.  -1 (the default): the launches of a kind choose their period
 //   themselves, closed loop, from the first one on (GuPacer / gu_pace_next): no search, no dedicated launch, nothing on the host.
-// Launches that cannot be bound by the HBM write path (less than 128 MB of rows, or fewer workgroups than half the CUs), launches of
-// fewer than 64 steps (fewer than four groups to schedule) and batches of more than four waves per SIMD (524 288 envs and more on
-// 256 CUs: a per-wave schedule found nothing to gain there, 0.96 .. 0.98 ms = 6.4 .. 6.6 TB/s with and without, and a batch that does
-// not fit the device at once is not on one schedule anyway; profiles/archive/r03n_batch_sizes.txt) keep no schedule and no record --
-// a fixed period applies to them all the same.  A kind's ring belongs to one launch SHAPE (trajectory buffer, workgroups, length
+// Launches that are not eligible keep no schedule and no record -- a fixed period applies to them all the same.  A kind's ring belongs to one launch SHAPE (trajectory buffer, workgroups, length
 // within a factor of two, row bytes): another shape starts it over from the model, the rows of 16 steps at GU_OPT_PACE_TARGET GB/s
 // (7200; the cliff sits at 7.4 .. 7.5 TB/s on the allocations measured in rounds 3 and 4).
 static int gu_pace_ring_for(gu_engine *h, int slot, int64_t T, unsigned blocks, int block_size, int row_bytes, GuPaceArgs *pace)
@@ -478,22 +446,14 @@ static int gu_pace_ring_for(gu_engine *h, int slot, int64_t T, unsigned blocks, 
     return GU_OK;
 }
 
-static bool gu_pace_eligible(const gu_engine *h, int64_t T, unsigned blocks, int row_bytes)
-{
-    return !((double)h->N * (double)T * (double)row_bytes < 128e6 || (int64_t)blocks * 2 < h->n_cu || T < 64 || h->N > (int64_t)h->n_cu * 1024);
-}
-
-int gu_pace_for(gu_engine *h, int slot, int64_t T, unsigned blocks, int block_size, int row_bytes, GuPaceArgs *pace)
+int gu_pace_for(gu_engine *h, const GuRolloutPlan &p, int64_t T, GuPaceArgs *pace)
 {
     *pace = GuPaceArgs{};
     const int64_t opt = gu_opt(h, GU_OPT_ROLLOUT_PACE);
     if (opt == 0) return GU_OK;
-    const bool eligible = gu_pace_eligible(h, T, blocks, row_bytes);
-    if (eligible && !(opt > 0 && gu_opt(h, GU_OPT_PACE_RECORD) == 0)) {
-        const int rc = gu_pace_ring_for(h, slot, T, blocks, block_size, row_bytes, pace);
-        if (rc != GU_OK) return rc;
+    if (p.pace_eligible && !(opt > 0 && gu_opt(h, GU_OPT_PACE_RECORD) == 0)) {
+        GU_TRY(gu_pace_ring_for(h, p.pace_slot, T, p.pace_blocks, p.pace_block, p.row_bytes, pace));
         if (opt > 0) pace->period = (uint32_t)opt, pace->fixed = 1;  // fixed, and recorded all the same
-        if (h->device >= 0 && h->device < 64) g_last_rollout_ms[h->device] = gu_wall_ms();
         return GU_OK;
     }
     if (opt > 0) pace->period = (uint32_t)opt;
@@ -538,137 +498,97 @@ int gu_nibble_planes(gu_engine *h)
     return GU_OK;
 }
 
+// Whether some env passes a multiple of 2^32 steps during a launch of T steps that draws from RNG streams 0 or 2 (csrc/gu_rng.hpp: their
+// epoch is the step count >> 32).  *epoch_lo: the epoch the launch begins in.  May read the envs' offsets once.
+static int gu_rollout_straddles(gu_engine *h, int64_t T, int32_t policy, bool *straddle, uint32_t *epoch_lo)
+{
+    const bool draws = policy == GU_POLICY_UNIFORM || policy == GU_POLICY_SAMPLE;  // (the stream and greedy policies draw nothing from those streams)
+    int64_t lo = std::max<int64_t>((int64_t)h->steps_taken + h->off_lo, 0), hi = (int64_t)h->steps_taken + h->off_hi + T - 1;
+    if (draws && (lo >> 32) != (hi >> 32) && !h->off_exact) {
+        // the bounds are only bounds (envs were held back by rejected actions since the host last knew): read the offsets once,
+        // so that launches do not take the slow path for longer than the envs really are on both sides of the boundary
+        std::vector<int32_t> off((size_t)h->N);
+        GU_HIP(hipMemcpyAsync(off.data(), h->d_tcount, (size_t)h->N * 4, hipMemcpyDeviceToHost, h->stream));
+        GU_HIP(hipStreamSynchronize(h->stream));
+        const auto mm = std::minmax_element(off.begin(), off.end());
+        h->off_lo = *mm.first, h->off_hi = *mm.second, h->off_exact = true;
+        lo = std::max<int64_t>((int64_t)h->steps_taken + h->off_lo, 0), hi = (int64_t)h->steps_taken + h->off_hi + T - 1;
+    }
+    *straddle = draws && (lo >> 32) != (hi >> 32);
+    *epoch_lo = (uint32_t)(lo >> 32);
+    return GU_OK;
+}
+
+// Checks, the straddle test, the plan (gu_rollout_plan.hpp), what the plan needs, the arguments, the schedule, the launch, the completion.
 int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
 {
-    // int32 rows: three planes [T][N], or one plane of (obs, reward, done) triples [T][N][3] -- the same words, one 12-byte store
-    // per lane and step (gu_rollout.hpp: TRAJ == 3; the readers take them apart again: gu_read_trajectory, gu_mc_evaluate).
-    // GU_OPT_TRAJ_LAYOUT: 0 = planes, 1 = triples wherever possible, -1 (default) = triples where they are faster.  Measured
-    // (profiles/archive/r05b_layout_ab.txt, r05c_layout_sizes.txt, five variants interleaved in one process): a launch bound by the HBM write path is
-    // SLOWER with triples -- 65 536 envs: 117 against 112 us, a config-4 shard of 32 768: 68 against 63 -- and so is every table
-    // policy; a launch of a few waves, bound by the ISSUE of its stores (~25 clocks per 256-byte store of a wave that has its SIMD
-    // alone), gains little from the triple alone (config 2, 4096 envs: 49.4 against 49.9 us) but 25 % together with the pair tables
-    // (two steps per LDS round trip, two stores per pair instead of six: 37.3 us), up to 8192 envs = one workgroup per eight
-    // CUs; at 16 384 the two are level -- unless the batch is spread over twice the waves (32 envs each: 43.6 against 53.3 us,
-    // profiles/archive/r05m_half_sizes.txt) --, beyond it the planes win.  So: triples for the uniform policy on the transition-row
-    // kernel with pair tables, up to n_cu / 4 workgroups of 256 (half waves for the upper half of that range).  Batches of more than 2^24 envs (lane offset + 15 rows must stay
-    // below 2^32 bytes) and engines with the agent trail on always keep the planes.
     GU_REQUIRE(!(h->d_wind_cell && (flags & GU_F_PACKED)), GU_ERR_UNSUPPORTED, "a rollout under wind (gu_set_wind) writes int32 rows only: GU_F_PACKED is refused");
-    int traj = (flags & GU_F_PACKED) ? 2 : ((flags & GU_F_TRAJECTORY) ? 1 : 0);
-    if (traj == 1 && h->N <= ((int64_t)1 << 24) && !h->trail_cap && !h->d_wind_cell) {
-        const int64_t layout = gu_opt(h, GU_OPT_TRAJ_LAYOUT);
-        if (layout == 1 || (layout == -1 && policy == GU_POLICY_UNIFORM && gu_rows_pairs_fit(h) && (int64_t)gu_blocks(h->N, 256) * 4 <= h->n_cu)) traj = 3;
+    GU_REQUIRE(!h->trail_cap || (flags & (GU_F_TRAJECTORY | GU_F_PACKED)), GU_ERR_UNSUPPORTED,
+               "the agent trail is on (gu_trail_enable): a rollout must write rows (GU_F_TRAJECTORY or GU_F_PACKED) to feed it");
+    GU_REQUIRE(policy >= GU_POLICY_UNIFORM && policy <= GU_POLICY_SAMPLE, GU_ERR_INVALID, "unknown policy kind %d", policy);
+    bool straddle = false;
+    uint32_t epoch_lo = 0;
+    GU_TRY(gu_rollout_straddles(h, T, policy, &straddle, &epoch_lo));
+
+    // the plan, and what it needs.  A table that cannot be allocated takes its form out of the next plan.
+    unsigned exclude = 0;
+    GuRolloutPlan p = gu_rollout_plan(h, T, policy, flags, straddle, exclude);
+    h->traj_written = p.traj;
+    if (p.need_nib) GU_TRY(gu_nibble_planes(h));
+    if (policy == GU_POLICY_SAMPLE)
+        hipLaunchKernelGGL(gu_pi_threshold_kernel, dim3(gu_blocks(h->S, 256)), dim3(256), 0, h->stream, h->d_pi[h->vi_cur], h->S, h->d_pi_thr);
+    for (bool no_pairs = false; !(p.family == GU_PLAN_KSTEP ? gu_kstep_ensure(h, p) : p.family == GU_PLAN_ROWS ? gu_rows_ensure(h, p, &no_pairs) : true);) {
+        exclude |= no_pairs ? GU_PLAN_NO_PAIRS : 1u << p.family;
+        p = gu_rollout_plan(h, T, policy, flags, straddle, exclude);
     }
-    h->traj_written = traj;
-    const bool stats = flags & GU_F_STATS;
-    const int auto_mode = (flags & GU_F_AUTO_RESET) ? (h->all_single_start ? 1 : 2) : 0;
-    const int64_t rows = traj ? h->traj_T * h->N : 0;
-    GU_REQUIRE(!h->trail_cap || traj, GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): a rollout must write rows (GU_F_TRAJECTORY or GU_F_PACKED) to feed it");
+
     RolloutArgs a{};
-    a.cell = h->d_cell;
-    a.greedy = h->d_greedy;
-    a.pi_thr = h->d_pi_thr;
-    a.S = h->S;
-    a.pi_lds = 0;
-    a.cell_bytes = h->cell_bytes;
-    a.W = h->W;
-    a.lut = h->delta_lut;
-    a.pos = h->pos();
-    a.reward = h->reward();
-    a.done = h->done();
-    a.episode = h->d_episode;
-    a.tcount = h->d_tcount;
-    a.starts = h->d_starts;
-    a.actions = h->d_actions_packed;
-    a.tr_obs = h->d_traj;
-    a.tr_reward = h->d_traj ? h->d_traj + rows : nullptr;
-    a.tr_done = h->d_traj ? h->d_traj + 2 * rows : nullptr;
-    a.ret = h->d_ret;
-    a.episodes_fin = h->d_episodes_fin;
-    a.done_bits = h->d_done_bits;
-    a.n_starts = (uint32_t)h->n_starts;
-    a.env_id0 = (uint32_t)h->env_id0;
-    a.steps_taken = (uint32_t)h->steps_taken;
-    a.steps_hi = (uint32_t)(h->steps_taken >> 32);
-    a.seed_prefix0 = h->seed_prefix;
-    {   // The epoch (step count >> 32) of RNG streams 0 and 2, csrc/gu_rng.hpp: folded into the seed prefix when every env stays in
-        // ONE epoch for the whole launch (the kernels then count in 32 bits, as ever); else -- once in 2^32 steps -- the launch goes
-        // to the general kernel, which asks per lane and step.  The stream and greedy policies draw nothing from those streams.
-        const bool draws = policy == GU_POLICY_UNIFORM || policy == GU_POLICY_SAMPLE;
-        int64_t lo = std::max<int64_t>((int64_t)h->steps_taken + h->off_lo, 0), hi = (int64_t)h->steps_taken + h->off_hi + T - 1;
-        if (draws && (lo >> 32) != (hi >> 32) && !h->off_exact) {
-            // the bounds are only bounds (envs were held back by rejected actions since the host last knew): read the offsets once,
-            // so that launches do not take the slow path for longer than the envs really are on both sides of the boundary
-            std::vector<int32_t> off((size_t)h->N);
-            GU_HIP(hipMemcpyAsync(off.data(), h->d_tcount, (size_t)h->N * 4, hipMemcpyDeviceToHost, h->stream));
-            GU_HIP(hipStreamSynchronize(h->stream));
-            const auto mm = std::minmax_element(off.begin(), off.end());
-            h->off_lo = *mm.first, h->off_hi = *mm.second, h->off_exact = true;
-            lo = std::max<int64_t>((int64_t)h->steps_taken + h->off_lo, 0), hi = (int64_t)h->steps_taken + h->off_hi + T - 1;
-        }
-        a.straddle = draws && (lo >> 32) != (hi >> 32) ? 1 : 0;
-        a.seed_prefix = a.straddle ? h->seed_prefix : gu_rng_seed_prefix_epoch(h->seed_prefix, (uint32_t)(lo >> 32));
-    }
-    a.N = h->N;
-    a.T = T;
-    a.gs = gu_grid_sel(h);
-    a.rows = nullptr;
-    a.rows2 = nullptr;
-    a.row_shift = 0;
-    a.stream_lds_off = 0;
-    a.stream_lds_words = 0;
-    a.half_waves = 0;
-    a.entry_table = (h->entry_table_ok && gu_opt(h, GU_OPT_ROLLOUT_ENTRY) != 0) ? 1 : 0;
-    const int bs = gu_rollout_block(h);
-    a.nib = nullptr;
-    a.nib_dwords = 0;
-    if (h->n_grids > 1 && (policy == GU_POLICY_UNIFORM || policy == GU_POLICY_STREAM) && !gu_lds_block(h, bs, 2) && h->W <= 1022 &&
-        gu_nibble_bytes_per_wave(h) <= (size_t)h->lds_per_cu - 512) {  // groups that do not align with blocks (one maze per env): MAP 5
-        const int rc = gu_nibble_planes(h);
-        if (rc != GU_OK) return rc;
-        a.nib = h->d_nib;
-        a.nib_dwords = gu_nibble_dwords(h);
+    const int64_t rows = p.traj ? h->traj_T * h->N : 0;
+    a.cell = h->d_cell, a.cell_bytes = h->cell_bytes, a.S = h->S, a.W = h->W, a.lut = h->delta_lut, a.gs = gu_grid_sel(h);
+    a.greedy = h->d_greedy, a.pi_thr = h->d_pi_thr, a.actions = h->d_actions_packed;
+    a.pos = h->pos(), a.reward = h->reward(), a.done = h->done(), a.episode = h->d_episode, a.tcount = h->d_tcount, a.done_bits = h->d_done_bits;
+    a.starts = h->d_starts, a.n_starts = (uint32_t)h->n_starts, a.env_id0 = (uint32_t)h->env_id0;
+    a.tr_obs = h->d_traj, a.tr_reward = h->d_traj ? h->d_traj + rows : nullptr, a.tr_done = h->d_traj ? h->d_traj + 2 * rows : nullptr;
+    a.ret = h->d_ret, a.episodes_fin = h->d_episodes_fin;
+    a.N = h->N, a.T = T, a.steps_taken = (uint32_t)h->steps_taken, a.steps_hi = (uint32_t)(h->steps_taken >> 32);
+    // The epoch of RNG streams 0 and 2 is folded into the seed prefix when every env stays in ONE epoch for the whole launch (the kernels
+    // then count in 32 bits, as ever); else -- once in 2^32 steps -- the general kernel asks per lane and step.
+    a.straddle = straddle ? 1 : 0;
+    a.seed_prefix0 = h->seed_prefix, a.seed_prefix = straddle ? h->seed_prefix : gu_rng_seed_prefix_epoch(h->seed_prefix, epoch_lo);
+    // what the plan decided
+    a.gs.per_wave = p.per_wave, a.pi_lds = p.pi_lds, a.stream_lds_off = p.stream_lds_off, a.stream_lds_words = p.stream_lds_words;
+    a.half_waves = p.half, a.entry_table = p.entry_table, a.xcd_remap = p.xcd_remap;
+    if (p.family == GU_PLAN_ROWS) a.rows = p.table_policy ? h->d_prow : h->d_rows[p.which], a.rows2 = p.pair ? h->d_rows2[p.which] : nullptr, a.row_shift = p.row_shift;
+    if (p.family == GU_PLAN_KSTEP) a.rows = h->d_mrows[p.which];
+    if (p.need_nib) {
+        a.nib = h->d_nib, a.nib_dwords = gu_nibble_dwords(h);
         // (cells of the padded image times 32: W <= 1022 keeps a row's step inside an int16)
         const uint64_t wp = (uint64_t)(uint16_t)(int16_t)((h->W + 1) * 32), mwp = (uint64_t)(uint16_t)(int16_t)(-(h->W + 1) * 32);
         a.lut_p = mwp | (32ull << 16) | (wp << 32) | ((uint64_t)(uint16_t)(int16_t)-32 << 48);
     }
-    a.pace = GuPaceArgs{};
-    a.xcd_remap = gu_opt(h, GU_OPT_ROLLOUT_XCD) != 0 && h->n_grids == 1;  // XCD-aware env-block order (see gu_env_block; measured slower, off)
-    if (policy == GU_POLICY_SAMPLE)
-        hipLaunchKernelGGL(gu_pi_threshold_kernel, dim3(gu_blocks(h->S, 256)), dim3(256), 0, h->stream, h->d_pi[h->vi_cur], h->S, h->d_pi_thr);
-    if (h->d_wind_cell) return gu_wind_launch_rollout(h, a, T, policy, flags);  // wind is set: the windy kernel serves every shape (gu_wind.hip)
-    if (!a.straddle && gu_rollout_multi(h, a, policy, auto_mode, traj, stats)) {
-        GU_HIP(hipGetLastError());
-        h->steps_taken += (uint64_t)T;
-        gu_tabular_drop_carry(h);
-        h->entry_table_ok = true;
-        return gu_trail_after_rollout(h, T, traj, auto_mode != 0);
-    }
-    {
-        int rows_rc = GU_OK;
-        if (!a.straddle && gu_rollout_rows(h, a, policy, auto_mode, traj, stats, &rows_rc)) {
-            if (rows_rc != GU_OK) return rows_rc;
-            GU_HIP(hipGetLastError());
-            h->steps_taken += (uint64_t)T;
-            gu_tabular_drop_carry(h);
-            h->entry_table_ok = true;
-            if (h->device >= 0 && h->device < 64) g_last_rollout_ms[h->device] = gu_wall_ms();
-            return gu_trail_after_rollout(h, T, traj, auto_mode != 0);
+    if (p.pace_slot >= 0) GU_TRY(gu_pace_for(h, p, T, &a.pace));
+
+    switch (p.family) {
+    case GU_PLAN_WIND: gu_wind_launch_rollout(h, p, a); break;
+    case GU_PLAN_KSTEP: gu_kstep_launch(h, p, a); break;
+    case GU_PLAN_ROWS:
+        if (!gu_rows_launch(h, p, a)) return gu_fail(GU_ERR_HIP, "gu_rollout_rows_kernel reports static LDS: its table must start at LDS address 0");
+        break;
+    default: {
+        auto launch = policy == GU_POLICY_UNIFORM ? gu_rollout_uniform : policy == GU_POLICY_STREAM ? gu_rollout_stream : policy == GU_POLICY_GREEDY ? gu_rollout_greedy : gu_rollout_sample;
+        if (!launch(h, p, a)) {  // MAP 5 whose images would not start at LDS address 0: the launch reads the records from L2 instead
+            p = gu_rollout_plan(h, T, policy, flags, straddle, exclude | GU_PLAN_NO_MAP5);
+            a.xcd_remap = p.xcd_remap ? 1 : 0;
+            launch(h, p, a);
         }
     }
-    if (policy < GU_POLICY_UNIFORM || policy > GU_POLICY_SAMPLE) return gu_fail(GU_ERR_INVALID, "unknown policy kind %d", policy);
-    if (traj == 1 || traj == 3) {  // int32 rows on the general kernel: the store stream is rate-limited (gu_rollout.hpp: GuPacer)
-        int rc = gu_pace_for(h, policy * 3 + auto_mode, T, gu_blocks(h->N, bs), bs, 12, &a.pace);
-        if (rc != GU_OK) return rc;
-        gu_rollout_general(h, a, policy, auto_mode, traj, stats, bs);
-    } else {
-        gu_rollout_general(h, a, policy, auto_mode, traj, stats, bs);
     }
-    if (h->device >= 0 && h->device < 64) g_last_rollout_ms[h->device] = gu_wall_ms();
     GU_HIP(hipGetLastError());
+    gu_rollout_plan_form(p, h->rollout_form);
     h->steps_taken += (uint64_t)T;
     gu_tabular_drop_carry(h);
-    h->entry_table_ok = true;
-    return gu_trail_after_rollout(h, T, traj, auto_mode != 0);
+    h->entry_table_ok = p.family != GU_PLAN_WIND;
+    return gu_trail_after_rollout(h, T, p.traj, p.auto_mode != 0);
 }
 
 int gu_launch_lookahead(gu_engine *h, int64_t n, const int32_t *d_states, const int32_t *d_actions, bool care,
@@ -681,14 +601,6 @@ int gu_launch_lookahead(gu_engine *h, int64_t n, const int32_t *d_states, const 
         hipLaunchKernelGGL(gu_lookahead_kernel<true>, grid, block, 2 * (size_t)h->cell_bytes, h->stream, a);
     else
         hipLaunchKernelGGL(gu_lookahead_kernel<false>, grid, block, 0, h->stream, a);
-    GU_HIP(hipGetLastError());
-    return GU_OK;
-}
-
-int gu_launch_validate_actions(gu_engine *h, const int32_t *d_actions, int64_t count)
-{
-    const unsigned blocks = (unsigned)std::min<int64_t>((count + 255) / 256, 4096);
-    hipLaunchKernelGGL(gu_validate_actions_kernel, dim3(blocks), dim3(256), 0, h->stream, d_actions, count, h->h_seq + GU_HOST_ERR_WORD);
     GU_HIP(hipGetLastError());
     return GU_OK;
 }

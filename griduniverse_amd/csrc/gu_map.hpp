@@ -4,8 +4,6 @@
 #include "gu_internal.hpp"
 #include "gu_rng.hpp"
 
-#define GU_BLOCK 256
-
 // ------------------------------------------------------------------------------------
 // helpers
 // ------------------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 // compiles in parallel; gu_kernels.hip only sees the four entry points declared at the end.
 #pragma once
 #include "gu_map.hpp"
+#include "gu_rollout_plan.hpp"
 
 #include <cstdlib>
 #include <functional>
@@ -465,7 +466,6 @@ __device__ __forceinline__ void gu_stream_run(const char *pa, int64_t row, uint3
 #ifndef GU_STORE_AUX_PACKED
 #define GU_STORE_AUX_PACKED 16
 #endif
-#define GU_MAX_BLOCK 1024
 typedef uint32_t gu_v3u __attribute__((ext_vector_type(3)));
 // TRAJ: 0 = no trajectory; 1 = int32 obs / reward / done rows (12 B per env-step), three planes [T][N]; 3 = the same int32 words as
 //       ONE plane of triples [T][N][3] (one 12-byte store per lane and step instead of three 4-byte ones);
@@ -889,139 +889,65 @@ __global__ void __launch_bounds__(GU_MAX_BLOCK) gu_rollout_kernel(const RolloutA
 }
 
 // ------------------------------------------------------------------------------------
-// launch helpers
+// launching: gu_rollout_plan.hpp decides, gu_launch_rollout (gu_kernels.hip) executes; what is here and in the per-family files only
+// turns the plan's run-time values into template arguments (gu_pick) and launches
 // ------------------------------------------------------------------------------------
-static inline unsigned gu_blocks(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
-
-// Largest block size <= preferred for which every block uses one grid (0 = none: use the L2 variant)
-static inline int gu_lds_block(const gu_engine *h, int preferred, int planes)
+// Launch KERN with `lds` bytes of dynamic LDS.  Raises the instantiation's dynamic-LDS limit once per device (gu_allow_lds; to the
+// whole LDS of a CU, so that a larger grid later in the process is not refused).  BASE_ZERO: the kernel addresses its dynamic LDS
+// from 0 -- asked once per instantiation: has it no static LDS in front?  false: it has, and nothing was launched.
+template <auto KERN, bool BASE_ZERO, class... A>
+static bool gu_lds_launch(const gu_engine *h, unsigned blocks, int block, size_t lds, const A &...args)
 {
-    if (h->S > GU_MAX_LDS_CELLS || (size_t)planes * h->cell_bytes > 65536) return 0;
-    if (h->n_grids == 1) return preferred;
-    for (int bs = preferred; bs >= 64; bs >>= 1)
-        if (h->group % bs == 0) return bs;
-    return 0;
+    static std::atomic<uint64_t> raised{0};
+    gu_allow_lds(KERN, raised, h->device, lds, (size_t)h->lds_per_cu);
+    if (BASE_ZERO) {
+        static std::atomic<int> base_zero{0};  // 1: no static LDS, the dynamic block starts at address 0
+        if (!base_zero.load(std::memory_order_relaxed)) {
+            hipFuncAttributes fa{};
+            const bool got = hipFuncGetAttributes(&fa, (const void *)KERN) == hipSuccess;
+            base_zero.store(got && fa.sharedSizeBytes == 0 ? 1 : 2, std::memory_order_relaxed);
+        }
+        if (base_zero.load(std::memory_order_relaxed) != 1) return false;
+    }
+    hipLaunchKernelGGL(KERN, dim3(blocks), dim3(block), lds, h->stream, args...);
+    return true;
 }
 
-static inline int gu_rollout_block(const gu_engine *h) { return (int)gu_opt(h, GU_OPT_ROLLOUT_BLOCK); }
-
-// MAP 5: dwords per env of the padded four-bits-per-cell image (eight cells per dword, rounded up to whole uint4 per lane), bytes per wave
-static inline int32_t gu_nibble_cells(const gu_engine *h) { return (h->H + 2) * (h->W + 1) + 1; }
-static inline int32_t gu_nibble_dwords(const gu_engine *h) { return (((gu_nibble_cells(h) + 7) / 8) + 3) & ~3; }
-static inline size_t gu_nibble_bytes_per_wave(const gu_engine *h) { return (size_t)gu_nibble_dwords(h) * 256u; }
-int gu_nibble_planes(gu_engine *h);  // builds h->d_nib if the installed grids have none yet (gu_kernels.hip)
-
-template <int POLICY, int AUTO, int TRAJ, bool STATS>
-static void gu_rollout_launch(gu_engine *h, const RolloutArgs &a_in, int bs)
-{
-    RolloutArgs a = a_in;
-    auto blocks_ok = [&](int block) { return gu_blocks(h->N, block) % 8 == 0; };
-    auto n_blocks = [&](int block) { return gu_blocks(h->N, block); };
-    const int planes = POLICY == GU_POLICY_GREEDY ? 3 : 2;
-    int lds_bs = gu_lds_block(h, bs, planes);
-    // Groups of 64 .. 192 envs (a multiple of 64, smaller than the workgroup): every wave stages its own grid's planes, so the launch
-    // keeps the workgroup size of the shared-grid launch -- whose store stream the memory takes at a shorter period than that of
-    // one-wave workgroups (profiles/r06m_multigrid_ab.txt).  Uniform and stream policies (the table policies keep one grid anyway).
-    bool per_wave = false;
-    if ((POLICY == GU_POLICY_UNIFORM || POLICY == GU_POLICY_STREAM) && lds_bs && lds_bs < bs && h->n_grids > 1 && h->group % 64 == 0 &&
-        (size_t)(bs / 64) * planes * h->cell_bytes <= 32768)
-        per_wave = true, lds_bs = bs;
-    if (lds_bs) {
-        size_t lds = (size_t)planes * h->cell_bytes * (per_wave ? (size_t)(bs / 64) : 1);
-        RolloutArgs b = a;
-        b.gs.per_wave = per_wave ? 1 : 0;
-        b.xcd_remap = a.xcd_remap && blocks_ok(lds_bs);
-        if (POLICY == GU_POLICY_SAMPLE && lds + (size_t)h->S * sizeof(uint4) <= 65536) {
-            b.pi_lds = 1;
-            lds += (size_t)h->S * sizeof(uint4);
-        }
-        auto kern = gu_rollout_kernel<POLICY, AUTO, TRAJ, STATS, 1>;
-        if (POLICY == GU_POLICY_STREAM && TRAJ != 0) {
-            // staged action words: as many per lane as the LDS share of a block admits at the occupancy this batch needs
-            const int64_t per_cu = std::min<int64_t>(8, std::max<int64_t>(1, ((int64_t)n_blocks(lds_bs) + h->n_cu - 1) / h->n_cu));
-            const int64_t room = h->lds_per_cu / per_cu - (int64_t)lds - 512;
-            int64_t kw = std::min<int64_t>({room / ((int64_t)lds_bs * 4), (int64_t)64, (a.T + 15) / 16});
-            if (kw >= 4) {
-                b.stream_lds_off = (int32_t)lds;
-                b.stream_lds_words = (int32_t)kw;
-                lds += (size_t)kw * lds_bs * 4;
-            }
-        }
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_per_cu);
-        hipLaunchKernelGGL(kern, dim3(n_blocks(lds_bs)), dim3(lds_bs), lds, h->stream, b);
-        return;
-    }
-    if constexpr (POLICY == GU_POLICY_UNIFORM || POLICY == GU_POLICY_STREAM) {
-        // one grid too big for two planes in 64 KiB: its flags plane alone, up to the whole 160 KB of a CU
-        if (h->n_grids == 1 && h->W <= 32767 && (int64_t)h->cell_bytes <= h->lds_per_cu - 512) {
-            a.xcd_remap = a.xcd_remap && blocks_ok(bs);
-            auto kern = gu_rollout_kernel<POLICY, AUTO, TRAJ, STATS, 3>;
-            if (h->cell_bytes > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->cell_bytes);
-            hipLaunchKernelGGL(kern, dim3(n_blocks(bs)), dim3(bs), (size_t)h->cell_bytes, h->stream, a);
-            return;
-        }
-        // misaligned multi-grid engine (e.g. one maze per env): every lane's grid at four bits per cell in LDS, if a wave's 64 fit
-        if (h->n_grids > 1 && h->W <= 1022 && gu_nibble_bytes_per_wave(h) <= (size_t)h->lds_per_cu - 512 && a.nib) {
-            // workgroups of four waves where four images fit a CU's LDS (32 x 32: 144 KB): the launch shape of the shared-grid kernel,
-            // whose store stream the memory takes at a shorter period than that of 1024 one-wave workgroups (profiles/r06m_multigrid_ab.txt)
-            int mbs = 256;
-            while (mbs > 64 && (size_t)(mbs / 64) * gu_nibble_bytes_per_wave(h) > (size_t)h->lds_per_cu - 512) mbs >>= 1;
-            const size_t lds = (size_t)(mbs / 64) * gu_nibble_bytes_per_wave(h);
-            auto kern = gu_rollout_kernel<POLICY, AUTO, TRAJ, STATS, 5>;
-            static std::atomic<int> base_zero{0};  // 1: no static LDS, the image starts at LDS address 0 (the kernel relies on it)
-            if (!base_zero.load(std::memory_order_relaxed)) {
-                hipFuncAttributes fa{};
-                const bool got = hipFuncGetAttributes(&fa, (const void *)kern) == hipSuccess;
-                base_zero.store(got && fa.sharedSizeBytes == 0 ? 1 : 2, std::memory_order_relaxed);
-            }
-            if (base_zero.load(std::memory_order_relaxed) == 1) {
-                if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                hipLaunchKernelGGL(kern, dim3(gu_blocks(h->N, mbs)), dim3(mbs), lds, h->stream, a);
-                return;
-            }
-        }
-    }
-    a.xcd_remap = a.xcd_remap && h->n_grids == 1 && blocks_ok(bs);
-    hipLaunchKernelGGL((gu_rollout_kernel<POLICY, AUTO, TRAJ, STATS, 0>), dim3(n_blocks(bs)), dim3(bs), 0, h->stream, a);
-}
-
-template <int POLICY, int AUTO>
-static void gu_rollout_dispatch2(gu_engine *h, const RolloutArgs &a, int traj, bool stats, int bs)
-{
-    if (traj == 1) {
-        if (stats) gu_rollout_launch<POLICY, AUTO, 1, true>(h, a, bs);
-        else gu_rollout_launch<POLICY, AUTO, 1, false>(h, a, bs);
-    } else if (traj == 2) {
-        if (stats) gu_rollout_launch<POLICY, AUTO, 2, true>(h, a, bs);
-        else gu_rollout_launch<POLICY, AUTO, 2, false>(h, a, bs);
-    } else if (traj == 3) {
-        if (stats) gu_rollout_launch<POLICY, AUTO, 3, true>(h, a, bs);
-        else gu_rollout_launch<POLICY, AUTO, 3, false>(h, a, bs);
-    } else {
-        if (stats) gu_rollout_launch<POLICY, AUTO, 0, true>(h, a, bs);
-        else gu_rollout_launch<POLICY, AUTO, 0, false>(h, a, bs);
-    }
-}
-
+// the general kernel's instantiation for a plan; false: MAP 5 found static LDS in front of its images (the launcher plans again without)
 template <int POLICY>
-static void gu_rollout_dispatch(gu_engine *h, const RolloutArgs &a, int auto_mode, int traj, bool stats, int bs)
+static bool gu_rollout_general(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a)
 {
-    switch (auto_mode) {
-    case 0: gu_rollout_dispatch2<POLICY, 0>(h, a, traj, stats, bs); break;
-    case 1: gu_rollout_dispatch2<POLICY, 1>(h, a, traj, stats, bs); break;
-    default: gu_rollout_dispatch2<POLICY, 2>(h, a, traj, stats, bs); break;
-    }
+    bool ok = false;
+    gu_pick<2, 1, 0>(p.auto_mode, [&](auto auto_c) {
+        gu_pick<0, 3, 2, 1>(p.traj, [&](auto traj_c) {
+            gu_pick<0, 1>(p.stats, [&](auto stats_c) {
+                gu_pick<0, 5, 3, 1>(p.map, [&](auto map_c) {  // (the lists run backwards so that the kernels keep their order in the code
+                                                              // object: an unchanged binary is how a change here is checked)
+                    constexpr int AUTO = decltype(auto_c)::value, TRAJ = decltype(traj_c)::value, MAP = decltype(map_c)::value;
+                    constexpr bool STATS = decltype(stats_c)::value != 0;
+                    // (MAP 3 and 5 exist for the policies that move without a table)
+                    if constexpr (MAP < 3 || POLICY == GU_POLICY_UNIFORM || POLICY == GU_POLICY_STREAM)
+                        ok = gu_lds_launch<gu_rollout_kernel<POLICY, AUTO, TRAJ, STATS, MAP>, MAP == 5>(h, p.blocks, p.block, p.lds, a);
+                });
+            });
+        });
+    });
+    return ok;
 }
 
 // one per policy kind, each in its own translation unit
-void gu_rollout_uniform(gu_engine *h, const RolloutArgs &a, int auto_mode, int traj, bool stats, int bs);
-void gu_rollout_stream(gu_engine *h, const RolloutArgs &a, int auto_mode, int traj, bool stats, int bs);
-void gu_rollout_greedy(gu_engine *h, const RolloutArgs &a, int auto_mode, int traj, bool stats, int bs);
-void gu_rollout_sample(gu_engine *h, const RolloutArgs &a, int auto_mode, int traj, bool stats, int bs);
-// the transition-row kernel (gu_rollout_rows.hip): true when it took the launch (*rc: what its pace calibration returned)
-bool gu_rollout_rows(gu_engine *h, RolloutArgs a, int32_t policy, int auto_mode, int traj, bool stats, int *rc);
-bool gu_rows_pairs_fit(const gu_engine *h);  // its pair tables fit this engine's grid (and GU_OPT_ROLLOUT_ROWS does not forbid them)
+bool gu_rollout_uniform(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);
+bool gu_rollout_stream(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);
+bool gu_rollout_greedy(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);
+bool gu_rollout_sample(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);
+// the transition-row kernel (gu_rollout_rows.hip): builds the tables the plan names (false: one could not be allocated -- *no_pairs: it
+// was a pair table), launches (false: static LDS in front of its table)
+bool gu_rows_ensure(gu_engine *h, const GuRolloutPlan &p, bool *no_pairs);
+bool gu_rows_launch(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);
+// the K-step kernel (gu_rollout_multi.hip; uniform policy and streams, no trajectory)
+bool gu_kstep_ensure(gu_engine *h, const GuRolloutPlan &p);
+void gu_kstep_launch(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);
+// the four-bit images of MAP 5: builds h->d_nib if the installed grids have none yet (gu_kernels.hip)
+int gu_nibble_planes(gu_engine *h);
 // store pacing (gu_kernels.hip): the schedule of a launch that writes rows -- the launch kind's ring of records, or a fixed period
-int gu_pace_for(gu_engine *h, int slot, int64_t T, unsigned blocks, int block_size, int row_bytes, GuPaceArgs *pace);
-// the K-step kernel (gu_rollout_multi.hip; uniform policy, no trajectory): true when it took the launch
-bool gu_rollout_multi(gu_engine *h, RolloutArgs a, int32_t policy, int auto_mode, int traj, bool stats);
+int gu_pace_for(gu_engine *h, const GuRolloutPlan &p, int64_t T, GuPaceArgs *pace);

@@ -245,82 +245,40 @@ __global__ void __launch_bounds__(GU_MAX_BLOCK) gu_rollout_multi_kernel(const Ro
 }
 
 // ------------------------------------------------------------------------------------ host side
-static int multi_mode(const gu_engine *h) { return (int)gu_opt(h, GU_OPT_ROLLOUT_MULTI); }
-
-// (K, workgroup size, copies) or false: (4^K * 4 * copies + 16) bytes per cell and workgroup, as many workgroups per CU as the
-// batch needs on 256 CUs
-static bool multi_shape(const gu_engine *h, int *K, int *block, int *copies)
+// (when this kernel takes a launch, and in which shape: gu_rollout_plan.hpp, gu_plan_kstep)
+// The K-step table and the one-step table that goes with it, rebuilt when they are not what the plan wants.  false: no memory for them.
+bool gu_kstep_ensure(gu_engine *h, const GuRolloutPlan &p)
 {
-    // diagnostics: force K, replicate the table (a second copy across the banks buys nothing: profiles/archive/r02h_multi_ab.txt)
-    const int only = (int)gu_opt(h, GU_OPT_ROLLOUT_MULTI_K), max_copies = gu_opt(h, GU_OPT_ROLLOUT_MULTI_COPIES) == 2 ? 2 : 1;
-    for (int bs = 256; bs <= GU_MAX_BLOCK; bs <<= 1) {
-        const int64_t blocks = (h->N + bs - 1) / bs, per_cu = (blocks + h->n_cu - 1) / h->n_cu;
-        for (int k = 4; k >= 2; k -= 2) {
-            if (only && only != k) continue;
-            const int64_t row = (int64_t)4 << (2 * k);
-            for (int c = max_copies; c >= 1; c >>= 1) {
-                if (((int64_t)h->S * (row * c + 16)) * per_cu <= h->lds_per_cu - 2048) {
-                    *K = k, *block = bs, *copies = c;
-                    return true;
-                }
-            }
-        }
-    }
-    return false;
-}
-
-// Returns true when the launch was taken by the K-step kernel.
-bool gu_rollout_multi(gu_engine *h, RolloutArgs a, int32_t policy, int auto_mode, int traj, bool stats)
-{
-    if ((policy != GU_POLICY_UNIFORM && policy != GU_POLICY_STREAM) || traj != 0 || auto_mode == 2 || h->n_grids != 1) return false;
-    const int mode = multi_mode(h);
-    if (mode == 0 || (mode != 1 && a.T < 64)) return false;  // (short launches: the second table's staging is not worth it)
-    int K = 0, bs = 0, copies = 0;
-    if (!multi_shape(h, &K, &bs, &copies)) return false;
-    const int row_log2 = 2 * K + 2;
-    const int shift = row_log2 + (copies == 2 ? 1 : 0);
-    const int which = auto_mode ? 1 : 0;
-    if (h->mrows_K[which] != K || h->mrows_shift[which] != shift) {
-        for (uint32_t **p : {&h->d_mrows[which], &h->d_mrows1[which]}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-        }
+    const int which = p.which, K = p.K;
+    if (h->mrows_K[which] != K || h->mrows_shift[which] != p.row_shift) {
+        gu_release(h->d_mrows[which], h->d_mrows1[which]);
         h->mrows_K[which] = 0;
-        if (hipMalloc(&h->d_mrows[which], ((size_t)h->S << row_log2)) != hipSuccess || hipMalloc(&h->d_mrows1[which], (size_t)h->S * 16) != hipSuccess) {
+        if (hipMalloc(&h->d_mrows[which], (size_t)h->S << (2 * K + 2)) != hipSuccess || hipMalloc(&h->d_mrows1[which], (size_t)h->S * 16) != hipSuccess) {
             (void)hipGetLastError();
             return false;
         }
-        BuildMultiArgs bK{h->d_cell, h->cell_bytes, h->S, h->W, h->start0, which, shift, h->d_mrows[which]};
+        BuildMultiArgs bK{h->d_cell, h->cell_bytes, h->S, h->W, h->start0, which, p.row_shift, h->d_mrows[which]};
         const unsigned nK = (unsigned)(((int64_t)h->S << (2 * K)) + 255) / 256;
         if (K == 4) hipLaunchKernelGGL(gu_build_multi_rows_kernel<4>, dim3(nK), dim3(256), 0, h->stream, bK);
         else hipLaunchKernelGGL(gu_build_multi_rows_kernel<2>, dim3(nK), dim3(256), 0, h->stream, bK);
         BuildMultiArgs b1{h->d_cell, h->cell_bytes, h->S, h->W, h->start0, which, 4, h->d_mrows1[which]};
         hipLaunchKernelGGL(gu_build_multi_rows_kernel<1>, dim3((unsigned)(((int64_t)h->S * 4 + 255) / 256)), dim3(256), 0, h->stream, b1);
         h->mrows_K[which] = K;
-        h->mrows_shift[which] = shift;
+        h->mrows_shift[which] = p.row_shift;
     }
-    a.rows = h->d_mrows[which];
-    const size_t lds = ((size_t)h->S << shift) + (size_t)h->S * 16;
-    const dim3 grid(gu_blocks(h->N, bs)), block(bs);
-    a.xcd_remap = a.xcd_remap && grid.x % 8 == 0;
-#define GU_MULTI_LAUNCH_P(PP, KK, ST)                                                                                        \
-    do {                                                                                                                     \
-        auto kern = gu_rollout_multi_kernel<PP, KK, ST>;                                                                     \
-        static std::atomic<uint64_t> raised{0}; /* per instantiation AND per device (gu_allow_lds) */                        \
-        gu_allow_lds(kern, raised, h->device, lds, (size_t)h->lds_per_cu);                                                   \
-        hipLaunchKernelGGL(kern, grid, block, lds, h->stream, a, which, h->d_mrows1[which], shift);                          \
-    } while (0)
-#define GU_MULTI_LAUNCH(KK, ST)                                                          \
-    do {                                                                                 \
-        if (policy == GU_POLICY_STREAM) GU_MULTI_LAUNCH_P(GU_POLICY_STREAM, KK, ST);     \
-        else GU_MULTI_LAUNCH_P(GU_POLICY_UNIFORM, KK, ST);                               \
-    } while (0)
-    if (K == 4) {
-        if (stats) GU_MULTI_LAUNCH(4, true); else GU_MULTI_LAUNCH(4, false);
-    } else {
-        if (stats) GU_MULTI_LAUNCH(2, true); else GU_MULTI_LAUNCH(2, false);
-    }
-#undef GU_MULTI_LAUNCH
-#undef GU_MULTI_LAUNCH_P
     return true;
+}
+
+// (the lists run backwards so that the kernels keep their order in the code object: an unchanged binary is how a change here is checked)
+void gu_kstep_launch(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a)
+{
+    gu_pick<2, 4>(p.K, [&](auto k_c) {
+        gu_pick<0, 1>(p.stats, [&](auto stats_c) {
+            gu_pick<GU_POLICY_UNIFORM, GU_POLICY_STREAM>(p.policy, [&](auto policy_c) {
+                constexpr int POLICY = decltype(policy_c)::value, K = decltype(k_c)::value;
+                constexpr bool STATS = decltype(stats_c)::value != 0;
+                gu_lds_launch<gu_rollout_multi_kernel<POLICY, K, STATS>, false>(h, p.blocks, p.block, p.lds, a, (int)p.which, (const uint32_t *)h->d_mrows1[p.which], (int)p.row_shift);
+            });
+        });
+    });
 }

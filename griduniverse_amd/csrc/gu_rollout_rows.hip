@@ -36,7 +36,6 @@
 // picks this one where it is faster (profiles/archive/r02b_map_ab.txt, profiles/archive/r02d_rows_crossover.txt).
 #include "gu_rollout.hpp"
 
-#define GU_ROW_ADDR_MASK 0xFFFFFu
 #define GU_ROW_DONE_BIT 23
 
 struct BuildRowsArgs {
@@ -131,7 +130,6 @@ struct BuildPairRowsArgs {
     uint32_t *rows2;  // [S][16][2] pair records, then [S][4] one-step records (row_shift 7)
 };
 
-#define GU_PAIR_SHIFT 7
 
 __global__ void __launch_bounds__(256) gu_build_pair_rows_kernel(const BuildPairRowsArgs a)
 {
@@ -163,7 +161,6 @@ struct RowBytes {
 #define GU_CHAIN_FENCE() __builtin_amdgcn_sched_barrier(0)
 // (workgroups of up to 512 lanes, i.e. 256 registers: the staging below keeps up to twelve 16-byte rows per lane in flight beside the
 // 32 registers of the first wave's pacing slots)
-#define GU_ROWS_MAX_BLOCK 512
 template <int POLICY, int TRAJ, bool STATS, bool PAIR = false>
 __global__ void __launch_bounds__(GU_ROWS_MAX_BLOCK) gu_rollout_rows_kernel(const RolloutArgs a, const int32_t auto_reset)
 {
@@ -177,7 +174,7 @@ __global__ void __launch_bounds__(GU_ROWS_MAX_BLOCK) gu_rollout_rows_kernel(cons
     // address bits ARE the ds_read address -- no base is added on the dependent chain.  (Until late in round 5 the block's address
     // was folded into every record; the compiler cannot know that it is 0 -- a link-time constant to it -- and spent one vector
     // instruction per emitted record on `rec - base`, a seventh of config 2's per-step vector work.  The launcher checks it:
-    // rows_dispatch refuses an instantiation that reports static LDS.)
+    // gu_lds_launch refuses an instantiation that reports static LDS.)
     constexpr uint32_t lds_base = 0u;
     // ---- The launch's fixed cost (round 5: 8.6 us of a 60 us config-4 shard, profiles/archive/r05r_rows_intercept.txt) is LATENCY: the table
     // came in through four dependent rounds of global loads (every copy of a row fetched separately, eight loads in flight), and
@@ -601,214 +598,73 @@ __global__ void __launch_bounds__(GU_ROWS_MAX_BLOCK) gu_rollout_rows_kernel(cons
 }
 
 // ------------------------------------------------------------------------------------ host side
-// (block size, copies) for the row table, or false when it does not fit: row_bytes * copies bytes per cell and block, one table
-// shared by all waves of a block; the batch must fit in (blocks per CU the LDS admits) x 256 CUs blocks.
-static bool rows_shape(const gu_engine *h, int row_bytes, int max_copies, int *block, int *copies)
+// (when this kernel takes a launch, and in which shape: gu_rollout_plan.hpp, gu_plan_rows)
+// The tables the plan names: allocated on first use, built when they are not what the plan wants.  false: no memory for one
+// (*no_pairs: for the pair tables; the one-step table would do).
+bool gu_rows_ensure(gu_engine *h, const GuRolloutPlan &p, bool *no_pairs)
 {
-    if (h->n_grids != 1) return false;
-    // the smallest workgroup that fits, with as many copies as its LDS share admits (the copy count matters little once the
-    // table is staged with wide, pipelined stores; the workgroup size does: profiles/archive/r02e_rows_copies.txt)
-    // (128- and 64-thread workgroups, which spread a 32 768-env launch over all CUs instead of half of them, are no faster: 70 .. 72 us
-    // either way, profiles/archive/r03h_rows_block.txt)
-    for (int bs = 256; bs <= GU_ROWS_MAX_BLOCK; bs <<= 1) {
-        const int64_t blocks = (h->N + bs - 1) / bs, per_cu = (blocks + h->n_cu - 1) / h->n_cu;
-        for (int c = max_copies; c >= 1; c >>= 1) {
-            if ((int64_t)h->S * row_bytes * c * per_cu <= h->lds_per_cu - 2048) {
-                *block = bs;
-                *copies = c;
-                return true;
-            }
-        }
-    }
-    return false;
-}
-
-// copies of every row across the LDS banks: up to 8 (uniform / stream), 16 (greedy), 4 (sampled); GU_ROWS_COPIES overrides
-// (a power of two; diagnostics)
-static int rows_max_copies(const gu_engine *h, int32_t policy)
-{
-    const int v = (int)gu_opt(h, GU_OPT_ROWS_COPIES);
-    if (v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32) return v;
-    return policy == GU_POLICY_GREEDY ? 16 : policy == GU_POLICY_SAMPLE ? 4 : 8;
-}
-
-static int rows_mode(const gu_engine *h) { return (int)gu_opt(h, GU_OPT_ROLLOUT_ROWS); }
-
-template <int POLICY, bool PAIR = false>
-static bool rows_dispatch(const gu_engine *h, const RolloutArgs &a, int traj, bool stats, int auto_reset, dim3 grid, dim3 block, size_t lds, hipStream_t stream)
-{
-#define GU_ROWS_LAUNCH(TR, ST)                                                                                           \
-    do {                                                                                                                 \
-        auto kern = gu_rollout_rows_kernel<POLICY, TR, ST, PAIR>;                                                        \
-        static std::atomic<uint64_t> raised{0}; /* per instantiation and per device: raise the dynamic-LDS limit once */ \
-        gu_allow_lds(kern, raised, h->device, lds, (size_t)h->lds_per_cu);                                               \
-        static std::atomic<int> base_zero{0}; /* 1: no static LDS, the dynamic block starts at 0 (the kernel relies on it) */ \
-        if (!base_zero.load(std::memory_order_relaxed)) {                                                                \
-            hipFuncAttributes fa{};                                                                                      \
-            const bool got = hipFuncGetAttributes(&fa, (const void *)kern) == hipSuccess;                                \
-            base_zero.store(got && fa.sharedSizeBytes == 0 ? 1 : 2, std::memory_order_relaxed);                          \
-        }                                                                                                                \
-        if (base_zero.load(std::memory_order_relaxed) != 1) return false;                                                \
-        hipLaunchKernelGGL(kern, grid, block, lds, stream, a, auto_reset);                                               \
-    } while (0)
-    if (traj == 1) {
-        if (stats) GU_ROWS_LAUNCH(1, true); else GU_ROWS_LAUNCH(1, false);
-    } else if (traj == 2) {
-        if (stats) GU_ROWS_LAUNCH(2, true); else GU_ROWS_LAUNCH(2, false);
-    } else if (traj == 3) {
-        if (stats) GU_ROWS_LAUNCH(3, true); else GU_ROWS_LAUNCH(3, false);
-    } else {
-        if (stats) GU_ROWS_LAUNCH(0, true); else GU_ROWS_LAUNCH(0, false);
-    }
-    return true;
-#undef GU_ROWS_LAUNCH
-}
-
-// the pair tables fit this engine's grid: one grid, one start cell (or no auto-reset), 144 bytes of LDS per cell in one workgroup's share
-bool gu_rows_pairs_fit(const gu_engine *h)
-{
-    return h->n_grids == 1 && (int64_t)h->S * 144 <= h->lds_per_cu - 2048 && ((int64_t)h->S << GU_PAIR_SHIFT) <= (int64_t)GU_ROW_ADDR_MASK && rows_mode(h) != 0 &&
-           rows_mode(h) != 2;
-}
-
-// Returns true when the launch was taken by the row-table kernel.
-bool gu_rollout_rows(gu_engine *h, RolloutArgs a, int32_t policy, int auto_mode, int traj, bool stats, int *rc)
-{
-    *rc = GU_OK;
-    if (policy < GU_POLICY_UNIFORM || policy > GU_POLICY_SAMPLE) return false;
-    if (auto_mode == 2) return false;  // several start cells: the reset draws from the RNG, it cannot be tabulated
-    const int mode = rows_mode(h);
-    // Default policy (profiles/archive/r02b_map_ab.txt, profiles/archive/r02d_rows_crossover.txt, profiles/archive/r02e_policy_rows.txt; interleaved
-    // A/B in one process): every launch that is bound by the dependent chain rather than by the HBM write path --
-    //   stats only           : every batch size (uniform: 62 -> 40 us at 65 536 envs, 68 -> 35 us at 262 144)
-    //   packed rows (4 B)    : up to one 256-env workgroup per CU (83 -> 51 us at 65 536 envs; 103 against 111 us at 131 072)
-    //   int32 rows (12 B)    : uniform / stream / greedy up to 32 768 envs (80 -> 59 us at 4096..16 384 envs, 84 -> 74 us at
-    //                          32 768 -- config 2, and a config-4 shard; beyond that the general kernel's store timing is the
-    //                          better one: 124 against 133 us at 65 536 envs); sampled up to one workgroup per CU
-    //   sampled policy       : only with auto-reset (122 against 141 us stats only, 148 against 168 us int32 rows at 65 536
-    //                          envs); without it the general kernel's shorter step wins (107 against 122 us) -- a sampled step
-    //                          is bound by its ~45 vector instructions, half of them the MurmurHash3 of its RNG word, not by
-    //                          the LDS round trips the row table saves
-    if (mode == 0) return false;
-    if (mode != 1 && mode != 2 && mode != 3) {
-        const unsigned blocks = gu_blocks(h->N, 256);
-        // (a caller-supplied stream with int32 rows: the row-table kernel reads its action words straight from HBM, and a load
-        // among streaming stores waits for all of them -- beyond 16 384 envs the general kernel, which stages the words in LDS,
-        // is the quicker one: 88 against 116 us at 32 768 envs, profiles/archive/r02j_stream_crossover.txt)
-        // (measured on the 256 CUs of an MI355X; stated relative to the CU count: one workgroup per CU, a quarter, half of them)
-        const unsigned cus = (unsigned)h->n_cu;
-        // (round 3, under the schedule limiter, 65 536 envs with int32 rows, profiles/archive/r03s_rows_vs_general.txt: greedy with auto-reset
-        // 108 .. 111 us here against 119 .. 120 on the general kernel, whose step then has two dependent LDS reads; sampled without
-        // auto-reset 135 against 142; uniform / stream / greedy without auto-reset: the same on both, they stay where they were)
-        // (the whole table, 8192 .. 65 536 envs x four policy kinds x int32 / packed rows on both kernels: profiles/archive/r03s_rows_crossover.txt.
-        // A caller-supplied stream with int32 rows used to leave this kernel at 16 384 envs -- its action words are read straight
-        // from HBM among the streaming stores --; with sc1 + nt stores it is the quicker one up to 32 768 like the uniform policy:
-        // 60 .. 61 against 66 .. 71 us)
-        const unsigned int32_limit = (policy == GU_POLICY_SAMPLE || (policy == GU_POLICY_GREEDY && auto_mode == 1)) ? cus : cus / 2;
-        if (((traj == 1 || traj == 3) && blocks > int32_limit) || (traj == 2 && blocks > cus)) return false;
-        if (policy == GU_POLICY_SAMPLE && auto_mode != 1 && traj == 0) return false;
-    }
-    const bool table_policy = policy == GU_POLICY_GREEDY || policy == GU_POLICY_SAMPLE;
-    const int row_log2 = policy == GU_POLICY_GREEDY ? 2 : policy == GU_POLICY_SAMPLE ? 5 : 4;
-    int bs = 0, copies = 0;
-    if (!rows_shape(h, 1 << row_log2, rows_max_copies(h, policy), &bs, &copies)) return false;
-    int shift = row_log2;
-    while ((1 << (shift - row_log2)) < copies) ++shift;
-    const int which = auto_mode ? 1 : 0;
-    if (table_policy) {
+    const int which = p.which;
+    const unsigned s_blocks = (unsigned)((h->S + 255) / 256);
+    auto alloc = [](uint32_t **table, size_t bytes) {
+        if (*table || hipMalloc(table, bytes) == hipSuccess) return true;
+        (void)hipGetLastError();
+        return false;
+    };
+    *no_pairs = false;
+    if (p.table_policy) {
         // policy-dependent rows: rebuilt by every launch (one tiny kernel), like the threshold table itself
-        if (!h->d_prow) {
-            if (hipMalloc(&h->d_prow, (size_t)h->S * 32) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;
-            }
-        }
-        BuildPolicyRowsArgs b{h->d_cell, h->d_greedy, policy == GU_POLICY_SAMPLE ? h->d_pi_thr : nullptr, h->cell_bytes, h->S, h->W,
-                              h->start0, which, shift, h->d_prow};
-        hipLaunchKernelGGL(gu_build_policy_rows_kernel, dim3((unsigned)((h->S + 255) / 256)), dim3(256), 0, h->stream, b);
-        a.rows = h->d_prow;
+        if (!alloc(&h->d_prow, (size_t)h->S * 32)) return false;
+        BuildPolicyRowsArgs b{h->d_cell, h->d_greedy, p.policy == GU_POLICY_SAMPLE ? h->d_pi_thr : nullptr, h->cell_bytes, h->S, h->W,
+                              h->start0, which, p.table_shift, h->d_prow};
+        hipLaunchKernelGGL(gu_build_policy_rows_kernel, dim3(s_blocks), dim3(256), 0, h->stream, b);
     } else {
-        if (!h->d_rows[which]) {
-            if (hipMalloc(&h->d_rows[which], (size_t)h->S * 4 * sizeof(uint32_t)) != hipSuccess) {
-                (void)hipGetLastError();
-                return false;
-            }
-            h->rows_shift[which] = -1;
+        if (!h->d_rows[which]) h->rows_shift[which] = -1;
+        if (!alloc(&h->d_rows[which], (size_t)h->S * 4 * sizeof(uint32_t))) return false;
+        if (h->rows_shift[which] != p.table_shift) {
+            BuildRowsArgs b{h->d_cell, h->cell_bytes, h->S, h->W, h->start0, which, p.table_shift, h->d_rows[which]};
+            hipLaunchKernelGGL(gu_build_rows_kernel, dim3(s_blocks), dim3(256), 0, h->stream, b);
+            h->rows_shift[which] = p.table_shift;
         }
-        if (h->rows_shift[which] != shift) {
-            BuildRowsArgs b{h->d_cell, h->cell_bytes, h->S, h->W, h->start0, which, shift, h->d_rows[which]};
-            hipLaunchKernelGGL(gu_build_rows_kernel, dim3((unsigned)((h->S + 255) / 256)), dim3(256), 0, h->stream, b);
-            h->rows_shift[which] = shift;
-        }
-        a.rows = h->d_rows[which];
     }
-    // Pair tables (two steps per LDS round trip) where they pay: state-independent actions, PACKED rows (int32 rows are as fast or
-    // faster on the one-step table -- 58 .. 61 against 65 us at 32 768 envs, 110 against 115 at 65 536: six stores and two records'
-    // worth of unpacking per round trip cost what the shorter chain saves, and those launches are close to the write path's rate
-    // anyway -- round 4, forced for int32 rows again, the chain fenced (GU_CHAIN_FENCE): 43.8 against 44.6 ns per step at config 2's
-    // 4096 envs, slower at 32 768 and 65 536.  What bounds a wave that has its SIMD alone is the ISSUE of its stores, ~25 clocks per
-    // 256-byte buffer_store_dword: 107 clocks per step with three of them, 143 per packed pair with two, 210 per int32 pair with six
-    // (slopes over T = 2000 .. 4000); without rows the K-step kernel of gu_rollout_multi.hip is the tool), one 256-lane workgroup per CU at most (144 bytes
-    // of LDS per cell).  GU_OPT_ROLLOUT_ROWS = 2 keeps the one-step table (A/B, tests).  profiles/archive/r03r_pair_rows.txt
-    // (int32 TRIPLES, round 5: two 12-byte stores per pair instead of six 4-byte ones -- 37 against 50 us at config 2's 4096 envs, 39 at
-    // 8192, level with the one-step table at 16 384, slower beyond; the launcher hands triples to this kernel only where they pay,
-    // GU_OPT_ROLLOUT_ROWS = 3 forces the pairs for every triples launch)
-    bool pair = !table_policy && (traj == 2 || (traj == 3 && (mode == 3 || policy == GU_POLICY_UNIFORM) && (mode == 3 || (int64_t)gu_blocks(h->N, 256) * 4 <= h->n_cu))) &&
-                mode != 2 && gu_blocks(h->N, 256) <= (unsigned)h->n_cu && gu_rows_pairs_fit(h);
-    if (pair) {
-        if (!h->d_rows2[which]) {
-            if (hipMalloc(&h->d_rows2[which], (size_t)h->S * 144) != hipSuccess) {
-                (void)hipGetLastError();
-                pair = false;
-            }
-            h->rows2_built[which] = false;
+    if (p.pair) {
+        if (!h->d_rows2[which]) h->rows2_built[which] = false;
+        if (!alloc(&h->d_rows2[which], (size_t)h->S * 144)) {
+            *no_pairs = true;
+            return false;
         }
-        if (pair && !h->rows2_built[which]) {
+        if (!h->rows2_built[which]) {
             BuildPairRowsArgs b2{h->d_cell, h->cell_bytes, h->S, h->W, h->start0, which, h->d_rows2[which]};
             hipLaunchKernelGGL(gu_build_pair_rows_kernel, dim3((unsigned)((h->S * 16 + 255) / 256)), dim3(256), 0, h->stream, b2);
             BuildRowsArgs b1{h->d_cell, h->cell_bytes, h->S, h->W, h->start0, which, GU_PAIR_SHIFT, h->d_rows2[which] + (size_t)h->S * 32};
-            hipLaunchKernelGGL(gu_build_rows_kernel, dim3((unsigned)((h->S + 255) / 256)), dim3(256), 0, h->stream, b1);
+            hipLaunchKernelGGL(gu_build_rows_kernel, dim3(s_blocks), dim3(256), 0, h->stream, b1);
             h->rows2_built[which] = true;
         }
-        if (pair) {
-            a.rows2 = h->d_rows2[which];
-            bs = 256;
-            shift = GU_PAIR_SHIFT;
-        }
     }
-    a.row_shift = shift;
-    const size_t lds = pair ? (size_t)h->S * 144 : ((size_t)h->S << row_log2) << (shift - row_log2);
-    // Half waves (see the kernel).  Measured (profiles/archive/r05m_half_sizes.txt, r05m_half_ab.txt): the stores of a wave do NOT get cheaper
-    // with fewer lanes -- planes at 4096 .. 8192 envs: 52.3 us either way, 55.4 against 53.3 at 16 384, and 223 against 126 us
-    // where two half waves share a SIMD -- so this is no cure for the issue-bound launches.  It pays in ONE place: triples with
-    // the pair tables between 8192 and 16 384 envs (43.6 against 47.6 us; the planes: 53.3), where a workgroup per four CUs
-    // becomes one per two.  That is the default; GU_OPT_ROLLOUT_HALF_WAVES = 1 / 0 forces / forbids it.
-    const int64_t half_opt = gu_opt(h, GU_OPT_ROLLOUT_HALF_WAVES);
-    const bool half = traj != 0 && h->N % 32 == 0 &&
-                      (half_opt == 1 || (half_opt == -1 && traj == 3 && pair && (int64_t)gu_blocks(h->N, 256) * 8 > h->n_cu && (int64_t)gu_blocks(h->N, 256) * 4 <= h->n_cu));
-    a.half_waves = half ? 1 : 0;
-    const dim3 grid(gu_blocks(h->N, half ? bs / 2 : bs)), block(bs);
-    a.xcd_remap = a.xcd_remap && grid.x % 8 == 0;
-    bool launched = true;  // (false: an instantiation with static LDS below its table -- not this build; the launch fails loudly)
-    auto launch = [&](const RolloutArgs &args) {
-        switch (policy) {
-        case GU_POLICY_UNIFORM:
-            launched = pair ? rows_dispatch<GU_POLICY_UNIFORM, true>(h, args, traj, stats, which, grid, block, lds, h->stream)
-                            : rows_dispatch<GU_POLICY_UNIFORM>(h, args, traj, stats, which, grid, block, lds, h->stream);
-            break;
-        case GU_POLICY_STREAM:
-            launched = pair ? rows_dispatch<GU_POLICY_STREAM, true>(h, args, traj, stats, which, grid, block, lds, h->stream)
-                            : rows_dispatch<GU_POLICY_STREAM>(h, args, traj, stats, which, grid, block, lds, h->stream);
-            break;
-        case GU_POLICY_GREEDY: launched = rows_dispatch<GU_POLICY_GREEDY>(h, args, traj, stats, which, grid, block, lds, h->stream); break;
-        default: launched = rows_dispatch<GU_POLICY_SAMPLE>(h, args, traj, stats, which, grid, block, lds, h->stream); break;
-        }
-    };
-    if (traj) {  // rows to write: the store stream is rate-limited here too (gu_rollout.hpp: GuPacer)
-        *rc = gu_pace_for(h, (traj != 2 ? 12 : 24) + policy * 3 + auto_mode, a.T, grid.x, bs, traj != 2 ? 12 : 4, &a.pace);
-        if (*rc != GU_OK) return true;
-    }
-    launch(a);
-    if (!launched) *rc = gu_fail(GU_ERR_HIP, "gu_rollout_rows_kernel reports static LDS: its table must start at LDS address 0");
     return true;
+}
+
+// false: an instantiation with static LDS below its table -- not this build; the launch fails loudly
+// (the lists run backwards so that the kernels keep their order in the code object: an unchanged binary is how a change here is checked)
+template <int POLICY, bool PAIR>
+static bool rows_launch(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a)
+{
+    bool ok = false;
+    gu_pick<0, 3, 2, 1>(p.traj, [&](auto traj_c) {
+        gu_pick<0, 1>(p.stats, [&](auto stats_c) {
+            constexpr int TRAJ = decltype(traj_c)::value;
+            constexpr bool STATS = decltype(stats_c)::value != 0;
+            ok = gu_lds_launch<gu_rollout_rows_kernel<POLICY, TRAJ, STATS, PAIR>, true>(h, p.blocks, p.block, p.lds, a, (int32_t)p.which);
+        });
+    });
+    return ok;
+}
+
+bool gu_rows_launch(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a)
+{
+    switch (p.policy) {
+    case GU_POLICY_UNIFORM: return p.pair ? rows_launch<GU_POLICY_UNIFORM, true>(h, p, a) : rows_launch<GU_POLICY_UNIFORM, false>(h, p, a);
+    case GU_POLICY_STREAM: return p.pair ? rows_launch<GU_POLICY_STREAM, true>(h, p, a) : rows_launch<GU_POLICY_STREAM, false>(h, p, a);
+    case GU_POLICY_GREEDY: return rows_launch<GU_POLICY_GREEDY, false>(h, p, a);
+    default: return rows_launch<GU_POLICY_SAMPLE, false>(h, p, a);
+    }
 }

@@ -239,67 +239,27 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_wind_rollout_kernel(const WindRol
     if ((threadIdx.x & 63) == 0 && live) a.done_bits[e >> 6] = bits;
 }
 
-template <int POLICY>
-static int gu_wind_rollout_launch(gu_engine *h, const WindRolloutArgs &a)
-{
-    const int lds_bs = gu_lds_block(h, GU_BLOCK, 3);
-    const dim3 grid(gu_blocks(h->N, GU_BLOCK)), block(GU_BLOCK);
-    const size_t lds = lds_bs ? 3 * (size_t)h->cell_bytes : 0;
-    if (lds_bs && h->gust_q16) hipLaunchKernelGGL((gu_wind_rollout_kernel<POLICY, true, true>), grid, block, lds, h->stream, a);
-    else if (lds_bs) hipLaunchKernelGGL((gu_wind_rollout_kernel<POLICY, true, false>), grid, block, lds, h->stream, a);
-    else if (h->gust_q16) hipLaunchKernelGGL((gu_wind_rollout_kernel<POLICY, false, true>), grid, block, 0, h->stream, a);
-    else hipLaunchKernelGGL((gu_wind_rollout_kernel<POLICY, false, false>), grid, block, 0, h->stream, a);
-    GU_HIP(hipGetLastError());
-    return GU_OK;
-}
-
 // gu_launch_rollout hands a launch over here while wind is set: `r` is what it has filled in (state, tables, rows, streams)
-int gu_wind_launch_rollout(gu_engine *h, const RolloutArgs &r, int64_t T, int32_t policy, uint32_t flags)
+// (the lists run backwards so that the kernels keep their order in the code object: an unchanged binary is how a change here is checked)
+void gu_wind_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &r)
 {
-    GU_REQUIRE(policy >= GU_POLICY_UNIFORM && policy <= GU_POLICY_SAMPLE, GU_ERR_INVALID, "unknown policy kind %d", policy);
-    const bool traj = flags & GU_F_TRAJECTORY, stats = flags & GU_F_STATS;
     WindRolloutArgs a{};
-    a.cell = h->d_wind_cell;
-    a.greedy = r.greedy;
-    a.pi_thr = r.pi_thr;
-    a.cell_bytes = h->cell_bytes;
-    a.W = h->W;
-    a.lut = h->delta_lut;
-    a.pos = r.pos;
-    a.reward = r.reward;
-    a.done = r.done;
-    a.episode = r.episode;
-    a.tcount = r.tcount;
-    a.starts = r.starts;
-    a.actions = r.actions;
-    a.tr_obs = traj ? r.tr_obs : nullptr;
-    a.tr_reward = traj ? r.tr_reward : nullptr;
-    a.tr_done = traj ? r.tr_done : nullptr;
-    a.ret = stats ? r.ret : nullptr;
-    a.episodes_fin = stats ? r.episodes_fin : nullptr;
-    a.done_bits = r.done_bits;
-    a.n_starts = r.n_starts;
-    a.seed_prefix = h->seed_prefix;
-    a.env_id0 = r.env_id0;
-    a.gust_q16 = h->gust_q16;
-    a.steps_taken = h->steps_taken;
-    a.N = h->N;
-    a.T = T;
-    a.auto_reset = (flags & GU_F_AUTO_RESET) ? 1 : 0;
-    a.gs = r.gs;
-    int rc;
-    switch (policy) {
-    case GU_POLICY_UNIFORM: rc = gu_wind_rollout_launch<GU_POLICY_UNIFORM>(h, a); break;
-    case GU_POLICY_STREAM: rc = gu_wind_rollout_launch<GU_POLICY_STREAM>(h, a); break;
-    case GU_POLICY_GREEDY: rc = gu_wind_rollout_launch<GU_POLICY_GREEDY>(h, a); break;
-    default: rc = gu_wind_rollout_launch<GU_POLICY_SAMPLE>(h, a); break;
-    }
-    if (rc != GU_OK) return rc;
-    h->steps_taken += (uint64_t)T;
-    gu_tabular_drop_carry(h);
-    h->entry_table_ok = false;
-    h->traj_written = traj ? 1 : 0;
-    return gu_trail_after_rollout(h, T, traj ? 1 : 0, (flags & GU_F_AUTO_RESET) != 0);
+    a.cell = h->d_wind_cell, a.cell_bytes = h->cell_bytes, a.W = h->W, a.lut = h->delta_lut, a.gs = r.gs, a.gust_q16 = h->gust_q16;
+    a.greedy = r.greedy, a.pi_thr = r.pi_thr, a.actions = r.actions;
+    a.pos = r.pos, a.reward = r.reward, a.done = r.done, a.episode = r.episode, a.tcount = r.tcount, a.done_bits = r.done_bits;
+    a.starts = r.starts, a.n_starts = r.n_starts, a.env_id0 = r.env_id0, a.seed_prefix = h->seed_prefix;
+    a.tr_obs = p.traj ? r.tr_obs : nullptr, a.tr_reward = p.traj ? r.tr_reward : nullptr, a.tr_done = p.traj ? r.tr_done : nullptr;
+    a.ret = p.stats ? r.ret : nullptr, a.episodes_fin = p.stats ? r.episodes_fin : nullptr;
+    a.N = h->N, a.T = r.T, a.steps_taken = h->steps_taken, a.auto_reset = p.auto_mode ? 1 : 0;
+    gu_pick<3, 2, 1, 0>(p.policy, [&](auto policy_c) {
+        gu_pick<0, 1>(p.lds != 0, [&](auto lds_c) {
+            gu_pick<0, 1>(h->gust_q16 != 0, [&](auto gust_c) {
+                constexpr int POLICY = decltype(policy_c)::value;
+                constexpr bool LDS = decltype(lds_c)::value != 0, GUST = decltype(gust_c)::value != 0;
+                gu_lds_launch<gu_wind_rollout_kernel<POLICY, LDS, GUST>, false>(h, p.blocks, p.block, p.lds, a);
+            });
+        });
+    });
 }
 
 void gu_wind_free(gu_engine *h)

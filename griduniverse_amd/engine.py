@@ -250,6 +250,23 @@ class Engine(object):
         flags = (_lib.F_AUTO_RESET if auto_reset else 0) | tflag | (_lib.F_STATS if stats else 0)
         check(self.lib.gu_rollout(self._h, int(T), _POLICIES[policy], flags))
 
+    ROLLOUT_FORM = ('family', 'layout', 'map', 'block', 'workgroups', 'lds_bytes', 'flags', 'K', 'row_shift', 'stream_words', 'pace_slot', 'pace_mode')
+    ROLLOUT_FAMILIES = {0: None, 1: 'general', 2: 'rows', 3: 'kstep', 4: 'wind'}
+    ROLLOUT_FLAG_BITS = ('pair', 'half', 'per_wave', 'pi_lds', 'straddle', 'entry_table', 'xcd_remap')
+
+    def rollout_last_form(self):
+        """What the last rollout of this engine ran on (gu_diag_rollout_form): dict with the twelve form words under the names of
+        ROLLOUT_FORM ('family' as a name: 'general', 'rows', 'kstep', 'wind'; None before the first rollout), each flag bit as a
+        bool under its name in ROLLOUT_FLAG_BITS, and the raw words as 'words'."""
+        words = np.zeros(len(self.ROLLOUT_FORM), np.int32)
+        n = ctypes.c_int32(0)
+        check(self.lib.gu_diag_rollout_form(self._h, ptr(words), words.size, ctypes.byref(n)))
+        out = dict(zip(self.ROLLOUT_FORM, (int(w) for w in words)))
+        out.update((name, bool(out['flags'] >> bit & 1)) for bit, name in enumerate(self.ROLLOUT_FLAG_BITS))
+        out['family'] = self.ROLLOUT_FAMILIES[out['family']]
+        out['words'] = [int(w) for w in words]
+        return out
+
     def calibrate_rollout(self, T, policy='uniform', auto_reset=True, trajectory=True, stats=False):
         """= rollout(...).  Rounds 3 and 4 searched the store-pacing period here; the launches choose it themselves now
         (include/gu.h: gu_rollout_calibrate), so nothing is left to ask for."""

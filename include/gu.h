@@ -382,6 +382,14 @@ int gu_sweep_init(gu_handle h);
 int gu_sweep_run(gu_handle h, int64_t T, int32_t P, double theta, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 int gu_sweep_get_queue(gu_handle h, int64_t env0, int64_t n, uint64_t *key, int32_t *size);
 int gu_diag_sweep_heap(gu_handle h, int64_t env0, int64_t n, uint64_t *heap, int32_t *pos);
+/* gu_diag_rollout_form : introspection -- what the last gu_rollout of this engine ran on, as the launcher planned it
+ *                      (csrc/gu_rollout_plan.hpp; DESIGN.md "Rollout dispatch").  *count = 12 words; with `form`, capacity >= 12:
+ *                      kernel family (1 general, 2 transition-row, 3 K-step, 4 windy); row layout (0 none, 1 planes, 2 packed, 3 triples);
+ *                      MAP of the general kernel (0 / 1 / 3 / 5), else -1; workgroup size; workgroups; dynamic LDS bytes; flag bits (1 pair
+ *                      tables, 2 half waves, 4 per-wave grids, 8 thresholds in LDS, 16 straddles a 2^32-step boundary, 32 first step on the
+ *                      table, 64 XCD-aware block order); K of the K-step kernel; log2 of the table's row pitch; staged action words per lane;
+ *                      the store-pacing slot (-1 none); 0 unpaced / 1 closed loop / 2 fixed period.  All zeros before the first rollout. */
+int gu_diag_rollout_form(gu_handle h, int32_t *form, int32_t capacity, int32_t *count);
 
 /* ---- batched simulation-based search: learner e owns env e and its table Q_e[S][4] (the gu_td_* tables) and plans at decision time ----
  * (build-defined: the second half of the reference's roadmap entry "Integrating learning and planning (Dyna, MC/TD Tree search,

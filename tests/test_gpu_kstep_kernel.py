@@ -49,6 +49,9 @@ def test_k_step_kernel_equals_the_oracle(gu_option, name, force_k):
                             acts = rs.randint(0, 4, (T, N)).astype(np.int32)
                             eng.upload_actions(acts)
                         eng.rollout(T, policy, auto, False, stats=stats)
+                        if force_k and (single_start or not auto):
+                            form = eng.rollout_last_form()
+                            assert (form['family'], form['K']) == ('kstep', int(force_k.split()[0])), (name, N, auto, T, form)
                         want = C.rollout(grid, 33, st, T, auto, actions=acts, stats=True)
                         if stats:
                             ret, eps = eng.read_stats()

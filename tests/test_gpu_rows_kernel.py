@@ -31,10 +31,12 @@ def _oracle_and_engine(meta, N, seed, env_id0=0):
 
 
 @pytest.mark.parametrize('name', ['c3_maze32', 'c4_lava32', 'c2_open8x8', 'c5_maze64', 'grid1x1', 'grid9x1', 'rect25x30_busy'])
-def test_rows_kernel_equals_the_oracle(force_rows, name):
+def test_rows_kernel_equals_the_oracle(force_rows, gu_option, name):
     """Every launch form of the transition-row kernel against the C oracle: uniform / stream actions, auto-reset on and
     off, int32 / packed / no trajectory + stats, launches of 1, 2, 15, 16, 17, 33 and 200 steps chained (resumability:
-    head / body / tail of the 16-actions-per-word schedule), ragged batch sizes."""
+    head / body / tail of the 16-actions-per-word schedule), ragged batch sizes.  The K-step kernel, which is asked first for
+    launches of 64 steps and more that keep statistics only, is switched off: every launch must REPORT the row kernel."""
+    gu_option('rollout_multi', 0)
     meta, _ = G.load_traj(name)
     single_start = len(meta['starts']) == 1
     for N in (1, 65, 1000):
@@ -50,6 +52,8 @@ def test_rows_kernel_equals_the_oracle(force_rows, name):
                             eng.upload_actions(acts)
                         for traj in (True, 'packed', False):
                             eng.rollout(T, policy, auto, traj, stats=True)
+                            # (several start cells with auto-reset: the reset draws, the general kernel takes the launch)
+                            assert eng.rollout_last_form()['family'] == ('rows' if single_start or not auto else 'general'), (name, N, auto, T, policy, traj)
                             want = C.rollout(grid, 21, st, T, auto, actions=acts, stats=True)
                             if traj is True:
                                 got = eng.read_trajectory(0, T)
@@ -209,6 +213,7 @@ def test_rows_kernel_on_a_single_device_generated_maze(force_rows):
         eng.reserve_trajectory(T)
         for traj in (True, False):
             eng.rollout(T, 'uniform', True, traj, stats=True)
+            assert eng.rollout_last_form()['family'] == ('rows' if traj else 'kstep')  # (statistics only, 300 steps: the K-step kernel is asked first)
             want = C.rollout(grid, 4, st, T, True, stats=True)
             if traj:
                 got = eng.read_trajectory(0, T)
@@ -306,13 +311,17 @@ def test_pair_tables_leave_the_same_rows_as_the_one_step_table_and_the_general_k
                         if acts is not None:
                             eng.upload_actions(acts)
                         eng.rollout(T, policy, auto, trajectory=traj, stats=True)
+                        form = eng.rollout_last_form()
+                        assert form['family'] == ('rows' if rows else 'general'), (N, T, policy, auto, traj, rows)
+                        # pair tables: packed rows, and the int32 triples that the default layout gives the uniform policy at these sizes
+                        assert form['pair'] == (rows == 1 and (traj == 'packed' or policy == 'uniform')), (N, T, policy, auto, traj, rows, form)
                         tr = eng.read_trajectory(0, T) if traj is True else eng.read_trajectory_packed(0, T)
                         st = eng.get_state()
                         outs[rows] = [tr[k] for k in sorted(tr)] + [st[k] for k in sorted(st)] + list(eng.read_stats()) + [eng.done_indices()]
                 for rows in (1, 2):
                     assert all(np.array_equal(a, b) for a, b in zip(outs[0], outs[rows])), (N, T, policy, auto, traj, rows)
     gu_option('rollout_rows', None)
-    # the default dispatch at a config-4 shard (32 768 envs, int32 rows) and for packed rows at 65 536 envs is the pair path: oracle
+    # the default dispatch at a config-4 shard (32 768 envs, int32 rows) and for packed rows at 65 536 envs : the row kernel on its one-step table and on its pair tables; against the oracle
     grid = C.Grid.from_lists(**meta)
     for N, traj in ((32768, True), (65536, 'packed')):
         T = 200
@@ -320,6 +329,8 @@ def test_pair_tables_leave_the_same_rows_as_the_one_step_table_and_the_general_k
             eng.reset()
             eng.reserve_trajectory(T)
             eng.rollout(T, 'uniform', True, trajectory=traj)
+            form = eng.rollout_last_form()
+            assert form['family'] == 'rows' and form['pair'] == (traj == 'packed'), form  # (32 768 envs with int32 rows: planes, the one-step table)
             got = eng.read_trajectory(0, T) if traj is True else eng.read_trajectory_packed(0, T, unpack=True)
         st = C.State(2048, N - 2048)
         C.reset(grid, 4, st)

@@ -39,6 +39,10 @@ def test_rows_are_the_same_bytes_under_every_layout_and_kernel(name, N, T, polic
             if policy == 'stream':
                 eng.upload_actions(np.random.RandomState(3).randint(0, 4, (T, N)).astype(np.int32))
             eng.rollout(T, policy, True, True, stats=True)
+            # what the launcher reports is what read_trajectory decodes below: planes under layout 0, triples under 1, one of the two by default
+            form = eng.rollout_last_form()
+            assert form['layout'] == {0: 1, 1: 3}.get(layout, form['layout']) and form['layout'] in (1, 3), (layout, rows, form)
+            assert rows != 0 or form['family'] == 'general'
             b = eng.read_trajectory(0, T)
             part = eng.read_trajectory(T // 2, T - T // 2)  # rows from the middle of the buffer
             st = eng.get_state()
