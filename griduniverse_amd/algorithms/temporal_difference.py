@@ -19,16 +19,19 @@ from ..vec_env import VecGridUniverse
 _CHUNK = 100000  # steps per launch (the launch limit is 1e8; shorter launches keep the device responsive)
 
 
-def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, wind=None, gust=0.0):
+def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, wind=None, gust=0.0, fruit=None):
     """The learner batch of q_learning / sarsa / n_step_* / *_lambda / dyna_q: L learners on the grid of `env`, tables of q0 (and empty models when
     `model`), `num_steps` real steps each in launches `launch(vec, T)` of at most `chunk` steps.  Returns Q [S][4] or [L][S][4].
-    `wind`: a strength array or a (strength, direction) pair for VecGridUniverse.set_wind, with `gust`."""
+    `wind`: a strength array or a (strength, direction) pair for VecGridUniverse.set_wind, with `gust`.  `fruit`: (cells, kinds,
+    values) for VecGridUniverse.set_fruit; the tables then have S << F rows."""
     L = int(num_learners)
     vec = VecGridUniverse(L, template=env, seed=seed)
     try:
         if wind is not None:
             strength, direction = wind if isinstance(wind, tuple) else (wind, 'up')
             vec.set_wind(strength, direction, gust)
+        if fruit is not None:
+            vec.set_fruit(*fruit)
         vec._ensure_q(q0)
         if model:
             vec._ensure_model()
@@ -44,27 +47,34 @@ def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, w
     return q[0] if L == 1 else q
 
 
-def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind=None, gust=0.0):
+def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind=None, gust=0.0, fruit=None):
     if int(num_learners) < 1:
         raise ValueError('num_learners must be at least 1')
     if not 0.0 <= float(epsilon) <= 1.0:
         raise ValueError('epsilon must lie in [0, 1]')
     if not 0.0 <= float(gust) <= 1.0:
         raise ValueError('gust must lie in [0, 1]')
+    if fruit is not None:
+        if wind is not None:
+            raise ValueError('wind and fruit exclude each other')
+        if not isinstance(fruit, (tuple, list)) or len(fruit) != 3:
+            raise ValueError('fruit must be (cells, kinds, values)')
     return _learn(env, num_learners, seed, q0, num_steps, _CHUNK,
-                  lambda vec, T: vec.td_run(T, method, alpha, discount_factor, epsilon), wind=wind, gust=gust)
+                  lambda vec, T: vec.td_run(T, method, alpha, discount_factor, epsilon), wind=wind, gust=gust, fruit=fruit)
 
 
-def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0):
+def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None):
     """Epsilon-greedy Q-learning, `num_steps` env steps per learner (episodes restart at a start cell when they end).  Returns
     Q float64[S][4], or [L][S][4] for L = num_learners > 1.  `wind`: a strength array ([H, W], or [W] per column; blowing up) or a
-    (strength, direction) pair as VecGridUniverse.set_wind takes them, gusting with probability `gust`; None: the calm grid."""
-    return _td('q_learning', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust)
+    (strength, direction) pair as VecGridUniverse.set_wind takes them, gusting with probability `gust`; None: the calm grid.  `fruit`: (cells, kinds, values)
+    as VecGridUniverse.set_fruit takes them -- the result then has S << F rows, row eaten * S + s for cell s with the mask `eaten` of
+    eaten fruit; not together with `wind`."""
+    return _td('q_learning', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit)
 
 
-def sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0):
+def sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None):
     """Epsilon-greedy SARSA; arguments and result as `q_learning`."""
-    return _td('sarsa', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust)
+    return _td('sarsa', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit)
 
 
 def _nstep(method, env, num_steps, n, alpha, discount_factor, epsilon, num_learners, seed, q0):

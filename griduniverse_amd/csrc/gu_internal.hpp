@@ -134,6 +134,12 @@ struct gu_engine {
     uint8_t *d_wind_cell = nullptr;  // wind (gu_set_wind, gu_wind.hip; single-grid engines): [3 * cell_bytes] the planes of d_cell with the
                                      // wind plane behind them -- what the windy kernels stage in one piece; nullptr: calm
     uint32_t gust_q16 = 0;           // ... and its gust probability in 1/65536
+    uint8_t *d_fruit_cell = nullptr; // fruit (gu_set_fruit, gu_fruit.hip; single-grid engines): [3 * cell_bytes] the planes of d_cell with the
+                                     // fruit plane behind them; nullptr: no fruit
+    uint32_t *d_eaten = nullptr;     // ... [N] the envs' masks of eaten fruit (bit = slot), cleared by every reset
+    int32_t n_fruit = 0;             // ... F, the number of fruit cells (1 .. 32; 0: no fruit); gu_td_run's tables then have S << F rows
+    uint32_t fruit_values = 0;       // ... the three kinds' values as int8 bytes 1 .. 3 (byte 0 zero), as the kernels take them
+    int32_t fruit_value[3] = {0, 0, 0};
     uint8_t *d_kind = nullptr;       // [n_grids][cell_bytes] texture class of every cell as the reference's viewer picks it
                                      // (rendering.py:119-133: goal, else lava, else wall, else ground = 3, 2, 1, 0) -- the flags
                                      // cannot tell a goal+lava cell from a lava cell; nullptr for device-generated mazes (no
@@ -395,6 +401,10 @@ int gu_ensure_scratch(gu_engine *h, size_t bytes);
 #define GU_NO_WIND(h, fn) \
     GU_REQUIRE(!(h)->d_wind_cell, GU_ERR_UNSUPPORTED, "%s knows no wind: the engine has wind set (gu_set_wind; NULL calms it again)", fn)
 
+// ... and so does every such call without a form that eats fruit while fruit is set (include/gu.h: gu_set_fruit)
+#define GU_NO_FRUIT(h, fn) \
+    GU_REQUIRE(!(h)->n_fruit, GU_ERR_UNSUPPORTED, "%s knows no fruit: the engine has fruit set (gu_set_fruit; NULL takes it away again)", fn)
+
 // frees device buffers and forgets them (hipFree's status is not looked at)
 template <class... P>
 static inline void gu_release(P *&...p)
@@ -518,6 +528,15 @@ int gu_wind_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t fla
                         uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
 void gu_wind_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);  // (the launch alone: gu_launch_rollout checks and completes it)
 void gu_wind_free(gu_engine *h);
+
+// ---- fruit (gu_fruit.hip): the launches that gu_launch_step / gu_launch_rollout hand over while fruit is set ----
+int gu_fruit_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward, int32_t *host_done,
+                         uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
+void gu_fruit_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);  // (the launch alone, as gu_wind_launch_rollout)
+int gu_fruit_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done);  // clears the masks of the envs a reset is about to take; no-op without fruit
+void gu_fruit_free(gu_engine *h);
+// gu_td.hip: the fruit count becomes F (0: none) -- Q tables whose row count is not S << F go, with what hangs on them
+void gu_td_rows_changed(gu_engine *h, int32_t F);
 
 // ---- agent trail (gu_trail.hip): no-ops while the trail is off ----------------------
 int gu_trail_after_step(gu_engine *h, uint32_t flags);

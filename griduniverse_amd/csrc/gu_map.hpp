@@ -112,3 +112,19 @@ __device__ __forceinline__ int32_t gu_wind_push(const uint8_t *f, int32_t s, uin
     }
     return s;
 }
+
+// ------------------------------------------------------------------------------------
+// fruit (include/gu.h: gu_set_fruit): one byte per cell behind the two cell planes, bits 0..4 the slot, bits 5..6 the kind (0: none)
+// ------------------------------------------------------------------------------------
+// What the fruit byte c of the cell just reached adds to the step's reward, and its slot into the env's mask.  `values` holds the
+// three kinds' values as int8 bytes 1 .. 3 (byte 0, "no fruit", is zero), so the pick is one v_bfe_i32 on kind * 8 and nothing
+// branches: a shift (an UNSIGNED 1: slot 31 is in range), an and-not for "not eaten yet" and an or.
+__device__ __forceinline__ int32_t gu_fruit_eat(uint32_t c, uint32_t values, uint32_t &eaten)
+{
+    const uint32_t kind = (c >> 5) & 3u;
+    const uint32_t bit = (kind ? 1u : 0u) << (c & 31u);
+    const int32_t v = __builtin_amdgcn_sbfe((int32_t)values, kind << 3, 8);
+    const int32_t gain = (bit & ~eaten) ? v : 0;
+    eaten |= bit;
+    return gain;
+}

@@ -112,11 +112,18 @@ __device__ __forceinline__ uint64_t gu_dyna_pack(int32_t s2, int32_t r, int32_t 
 // WIND (include/gu.h: gu_set_wind; 0 = calm, 1 = wind without gusts, 2 = with gusts): a.cell then carries the wind plane behind the two
 // cell planes (gu_engine::d_wind_cell; staged with them), the kernel sets `gust_q16` (its own arguments hold it: TabArgs does not),
 // and move() pushes the agent behind its action.  The calm instantiations hold none of it.
-template <bool LDS, bool ROWS = true, int WIND = 0>
+// FRUIT (include/gu.h: gu_set_fruit): a.cell carries the fruit plane behind the two cell planes (gu_engine::d_fruit_cell), the kernel
+// sets `fvalues`, `rows` and `eaten` before begin() and stores `eaten` behind end() (its own arguments hold them), and the table has S << F
+// rows: the lane stands on row eaten * S + s.  move() leaves the mask behind the step in `eaten2`, step() makes it current.  A wall
+// bump onto an uneaten fruit keeps the cell and changes the row, so next_row() and update() compare ROWS, not cells.  The
+// instantiations without fruit hold none of it (row() is s there).
+template <bool LDS, bool ROWS = true, int WIND = 0, bool FRUIT = false>
 struct TabLane {
     CellMap m;
-    const uint8_t *wd;  // WIND: the wind plane
+    const uint8_t *wd;  // WIND: the wind plane; FRUIT: the fruit plane
     uint32_t gust_q16;  // WIND == 2
+    uint32_t fvalues, eaten, eaten2;  // FRUIT
+    int32_t S, rows;                  // FRUIT: states, and rows of one learner's table (S << F)
     LaneGrid lg;
     int64_t e;
     uint32_t env, start_prefix, prefix, ep;
@@ -127,8 +134,9 @@ struct TabLane {
 
     __device__ __forceinline__ TabLane(const TabArgs &a, uint8_t *smem)
     {
-        m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, WIND ? 3 : 2);
-        if (WIND) wd = m.f + 2 * a.cell_bytes;
+        m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, (WIND || FRUIT) ? 3 : 2);
+        if (WIND || FRUIT) wd = m.f + 2 * a.cell_bytes;
+        if (FRUIT) S = a.S;
         e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         d = 0;
     }
@@ -141,13 +149,14 @@ struct TabLane {
         t = a.steps_taken + (uint64_t)(int64_t)(int32_t)a.tcount[e];
         // stream 4: the epoch t >> 32 hashed behind the seed, hoisted; recomputed in the step that crosses a multiple of 2^32
         prefix = gu_rng_prefix(gu_rng_seed_prefix_epoch(a.seed_prefix, (uint32_t)(t >> 32)), env);
-        qe = ROWS ? a.q + e * a.S * 4 : nullptr;
+        qe = ROWS ? a.q + (FRUIT ? e * rows : e * a.S) * 4 : nullptr;
+        if (FRUIT) eaten2 = eaten;
         s = a.pos[e];
         r = a.reward[e];
         d = a.done[e];
         ep = a.episode[e];
         q = QRow{0.0, 0.0, 0.0, 0.0};
-        if (ROWS && !d) q = gu_q_load(qe + (int64_t)s * 4);
+        if (ROWS && !d) q = gu_q_load(qe + row() * 4);
         ret = 0;
         fin = 0;
     }
@@ -159,9 +168,14 @@ struct TabLane {
             s = lg.starts[gu_rng_start_index(start_prefix, ep, lg.n_starts)];
             ++ep;
             d = 0;
-            if (ROWS) q = gu_q_load(qe + (int64_t)s * 4);
+            if (FRUIT) eaten = eaten2 = 0u;  // the fruit grows back
+            if (ROWS) q = gu_q_load(qe + row() * 4);
         }
     }
+
+    // the table row the lane stands on, and the one it stands on behind move()
+    __device__ __forceinline__ int64_t row() const { return FRUIT ? (int64_t)eaten * S + s : (int64_t)s; }
+    __device__ __forceinline__ int64_t row2(int32_t s2) const { return FRUIT ? (int64_t)eaten2 * S + s2 : (int64_t)s2; }
 
     // the stream-4 word of step t
     __device__ __forceinline__ uint32_t word() const { return gu_rng_word(prefix, GU_RNG_STREAM_TD, (uint32_t)t); }
@@ -177,6 +191,7 @@ struct TabLane {
             s2 = gu_wind_push<LDS>(m.f, s2, c, k, a.lut, a.W);
         }
         r = m.r[s2];
+        if (FRUIT) r += gu_fruit_eat(wd[s2], fvalues, eaten2);  // (read beside the flags and the reward byte of s': the chain does not grow)
         d = (m.f[s2] >> GU_CELL_TERM_BIT) & 1;
         ++t;
         if ((uint32_t)t == 0u) prefix = gu_rng_prefix(gu_rng_seed_prefix_epoch(a.seed_prefix, (uint32_t)(t >> 32)), env);
@@ -187,7 +202,7 @@ struct TabLane {
     __device__ __forceinline__ QRow next_row(int32_t s2) const
     {
         QRow n = q;
-        if (ROWS && !d && s2 != s) n = gu_q_load(qe + (int64_t)s2 * 4);
+        if (ROWS && !d && (FRUIT ? row2(s2) != row() : s2 != s)) n = gu_q_load(qe + row2(s2) * 4);
         return n;
     }
 
@@ -197,7 +212,7 @@ struct TabLane {
         double qa = gu_q_get(q, ua);
         qa = __dadd_rn(qa, __dmul_rn(a.alpha, __dsub_rn(target, qa)));
         qe[sa] = qa;
-        if (s2 == s) gu_q_put(n, ua, qa);
+        if (FRUIT ? row2(s2) == row() : s2 == s) gu_q_put(n, ua, qa);
     }
 
     // the lane stands in s' with row n: the trajectory row and the statistics of step i
@@ -205,6 +220,7 @@ struct TabLane {
     {
         q = n;
         s = s2;
+        if (FRUIT) eaten = eaten2;
         if (a.tr_obs) {
             const int64_t row = (int64_t)i * a.N + e;
             a.tr_obs[row] = s2;
@@ -242,6 +258,9 @@ struct TabLane {
 
 // the tables that more than one learner's entry points need, present and of this grid's size
 #define GU_NEED_Q(h) GU_REQUIRE((h)->d_q && (h)->td_S == (h)->S, GU_ERR_STATE, "no Q tables: call gu_td_init first")
+// ... gu_td_run and the table copies alone know fruit: S << F rows (include/gu.h: gu_set_fruit)
+#define GU_TD_ROWS(h) ((int64_t)(h)->S << (h)->n_fruit)  /* (64 bits: F runs to 32; gu_td_init keeps it below 2^31) */
+#define GU_NEED_TD_Q(h) GU_REQUIRE((h)->d_q && (int64_t)(h)->td_S == GU_TD_ROWS(h), GU_ERR_STATE, "no Q tables: call gu_td_init first")
 #define GU_NEED_AC(h) GU_REQUIRE((h)->d_ac_h && (h)->ac_S == (h)->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first")
 
 // tables of `bytes` for the engine's envs: what is left has to hold the trajectory buffer and the scratch of other calls too, so

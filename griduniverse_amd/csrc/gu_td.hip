@@ -10,16 +10,22 @@ struct TdArgs : TabArgs {
     int8_t *next_a;  // [N] SARSA: the action carried to the next launch (-1: none)
     int32_t carry;   // 1: this launch directly follows a SARSA launch on the same engine -- start with next_a
     uint32_t gust_q16;  // the windy instantiations: the engine's gust probability (gu_set_wind); a.cell then holds three planes
+    // the fruit instantiations (gu_set_fruit; a.cell holds three planes): the kinds' values, the envs' masks, the rows of one table (S << F)
+    uint32_t fruit_values;
+    int32_t rows;
+    uint32_t *eaten;
 };
 
 // WIND: 0 = calm, 1 = wind without gusts (no stream-9 hash in the code), 2 = with gusts (gu_tabular.hpp: TabLane)
-template <bool SARSA, bool LDS, int WIND = 0>
+// FRUIT: the table has S << F rows and the lane learns on row eaten * S + s (TabLane); never together with WIND
+template <bool SARSA, bool LDS, int WIND = 0, bool FRUIT = false>
 __global__ void __launch_bounds__(GU_BLOCK) gu_td_kernel(const TdArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    TabLane<LDS, true, WIND> L(a, smem);
+    TabLane<LDS, true, WIND, FRUIT> L(a, smem);
     if (WIND == 2) L.gust_q16 = a.gust_q16;
     if (L.e < a.N) {
+        if (FRUIT) L.fvalues = a.fruit_values, L.rows = a.rows, L.eaten = a.eaten[L.e];
         L.begin(a);
         int32_t act = (SARSA && a.carry) ? (int32_t)a.next_a[L.e] : -1;
         for (int32_t i = 0; i < a.T; ++i) {
@@ -40,11 +46,12 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_td_kernel(const TdArgs a)
                 mval = gu_q_max(n);
             }
             const double target = L.d ? (double)L.r : __dadd_rn((double)L.r, __dmul_rn(a.gamma, mval));
-            L.update(a, (int64_t)L.s * 4 + ua, ua, s2, n, target);
+            L.update(a, L.row() * 4 + ua, ua, s2, n, target);
             act = a2;
             L.step(a, i, s2, n);
         }
         L.end(a);
+        if (FRUIT) a.eaten[L.e] = L.eaten;
         if (SARSA) a.next_a[L.e] = (int8_t)act;
     }
     L.ballot(a);
@@ -71,8 +78,13 @@ static int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, d
     a.next_a = h->d_td_next;
     a.carry = (method == 1 && h->td_carry) ? 1 : 0;
     a.gust_q16 = h->gust_q16;
+    a.fruit_values = h->fruit_values, a.rows = h->td_S, a.eaten = h->d_eaten;
     int rc;
-    if (h->d_wind_cell) {  // the windy instantiations, on the three planes
+    if (h->n_fruit) {  // the fruit instantiations, on the three planes and S << F rows
+        a.cell = h->d_fruit_cell;
+        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 0, true>, gu_td_kernel<true, false, 0, true>, a, GU_BLOCK, 0, 3)
+                         : gu_tabular_launch(h, gu_td_kernel<false, true, 0, true>, gu_td_kernel<false, false, 0, true>, a, GU_BLOCK, 0, 3);
+    } else if (h->d_wind_cell) {  // the windy instantiations, on the three planes
         a.cell = h->d_wind_cell;
         if (h->gust_q16)
             rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 2>, gu_td_kernel<true, false, 2>, a, GU_BLOCK, 0, 3)
@@ -93,15 +105,25 @@ static void gu_td_free(gu_engine *h)
     h->td_S = 0;
 }
 
+static void gu_td_drop(gu_engine *h)  // the Q tables and what hangs on them
+{
+    gu_td_free(h);
+    gu_nstep_free(h);
+    gu_lambda_free(h);
+    gu_search_free(h);
+    gu_mcts_free(h);  // (gu_mcts_init again)
+}
+
+void gu_td_rows_changed(gu_engine *h, int32_t F)
+{
+    if (h->td_S && (int64_t)h->td_S != ((int64_t)h->S << F)) gu_td_drop(h);
+}
+
 void gu_learners_drop(gu_engine *h, int32_t S)
 {
     const bool all = S == 0;
     if (all || (h->td_S && h->td_S != S)) {  // Q tables of another state count belong to another grid: gu_td_init again
-        gu_td_free(h);
-        gu_nstep_free(h);
-        gu_lambda_free(h);
-        gu_search_free(h);
-        gu_mcts_free(h);  // (gu_mcts_init again)
+        gu_td_drop(h);
     }
     if (all || (h->is_S && h->is_S != S)) gu_is_free(h);  // ... and the cumulative weights: gu_is_init again
     if (all || (h->explore_S && h->explore_S != S)) gu_explore_free(h);  // ... and the visit counts: gu_explore_init again
@@ -122,15 +144,19 @@ int gu_td_init(gu_handle h, double q0)
     GU_NEED_GRID(h);
     GU_REQUIRE(std::isfinite(q0), GU_ERR_INVALID, "q0 must be finite");
     gu_tabular_drop_carry(h);
-    const size_t bytes = (size_t)h->N * (size_t)h->S * 4 * sizeof(double);
-    if (!h->d_q || h->td_S != h->S) {
+    // under fruit a table has a row per (cell, mask): S << F of them (gu_set_fruit), which ten fruits multiply by 1024
+    GU_REQUIRE(h->n_fruit <= 10, GU_ERR_INVALID, "%d fruits: gu_td_init learns on S << F rows and takes at most 10 fruits", h->n_fruit);
+    GU_REQUIRE(((int64_t)h->S << h->n_fruit) <= 0x7FFFFFFF, GU_ERR_INVALID, "%d states x 2^%d masks: more than 2^31 - 1 rows", h->S, h->n_fruit);
+    const int32_t rows = (int32_t)GU_TD_ROWS(h);
+    const size_t bytes = (size_t)h->N * (size_t)rows * 4 * sizeof(double);
+    if (!h->d_q || h->td_S != rows) {
         GU_HIP(hipStreamSynchronize(h->stream));
         gu_td_free(h);
         int rc = gu_tabular_fits(h, bytes, "Q tables");
         if (rc != GU_OK) return rc;
         GU_HIP(hipMalloc(&h->d_q, bytes));
         GU_HIP(hipMalloc(&h->d_td_next, (size_t)h->N));
-        h->td_S = h->S;
+        h->td_S = rows;
     }
     GU_HIP(hipMemsetAsync(h->d_td_next, 0xFF, (size_t)h->N, h->stream));
     int rc = gu_td_fill(h, q0);
@@ -143,7 +169,7 @@ int gu_td_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma
 {
     GU_ENTER(h);
     GU_NEED_GRID(h);
-    GU_NEED_Q(h);
+    GU_NEED_TD_Q(h);
     GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Q-learning, 1 = SARSA", method);
     int rc = gu_tabular_check(h, "gu_td_run", T, -1, eps_q16, alpha, gamma, flags);
     if (rc != GU_OK || T == 0) return rc;
@@ -153,7 +179,7 @@ int gu_td_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma
 static int gu_td_range(gu_engine *h, int64_t env0, int64_t n, const void *q)
 {
     GU_NEED_GRID(h);
-    GU_NEED_Q(h);
+    GU_NEED_TD_Q(h);
     GU_REQUIRE(q != nullptr, GU_ERR_INVALID, "q is NULL");
     return gu_env_range(h, env0, n);
 }
@@ -163,7 +189,7 @@ int gu_td_get_q(gu_handle h, int64_t env0, int64_t n, double *q)
     GU_ENTER(h);
     int rc = gu_td_range(h, env0, n, q);
     if (rc != GU_OK) return rc;
-    return gu_env_copy(h, hipMemcpyDeviceToHost, q, h->d_q, env0, n, (size_t)h->S * 4);
+    return gu_env_copy(h, hipMemcpyDeviceToHost, q, h->d_q, env0, n, (size_t)h->td_S * 4);
 }
 
 int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q)
@@ -172,7 +198,7 @@ int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q)
     int rc = gu_td_range(h, env0, n, q);
     if (rc != GU_OK) return rc;
     gu_tabular_drop_carry(h);
-    return gu_env_copy(h, hipMemcpyHostToDevice, q, h->d_q, env0, n, (size_t)h->S * 4);
+    return gu_env_copy(h, hipMemcpyHostToDevice, q, h->d_q, env0, n, (size_t)h->td_S * 4);
 }
 
 }  // extern "C"

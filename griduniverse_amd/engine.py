@@ -98,6 +98,7 @@ class Engine(object):
                                    ptr(p['lava']), ptr(p['rplus']), ptr(p['rminus']), ptr(starts), len(starts)))
         self.spec = spec
         self._n_grids = 1
+        self._n_fruit = 0  # (a new grid drops the fruit)
 
     def set_grids(self, specs):
         """Several distinct grids of one shape: env e uses specs[e // (N // len(specs))]."""
@@ -119,6 +120,7 @@ class Engine(object):
         self.spec = specs[0]
         self.specs = list(specs)
         self._n_grids = len(specs)
+        self._n_fruit = 0
 
     def generate_mazes(self, n_grids, W, H, maze_seed):
         """n_grids random mazes carved on the device (one per env group of N // n_grids envs)."""
@@ -126,6 +128,7 @@ class Engine(object):
         self.spec = GridSpec(W, H, [0], [W * H - 1], [], [])  # shape holder; the real grids live on the device
         self.specs = None
         self._n_grids = int(n_grids)
+        self._n_fruit = 0
 
     def get_cells(self, grid_index=0):
         """(flags uint8[S], reward int8[S], starts int32[n]) of one grid as compiled on the device."""
@@ -149,6 +152,38 @@ class Engine(object):
         gust, present = ctypes.c_uint32(0), ctypes.c_int32(0)
         check(self.lib.gu_get_wind(self._h, ptr(wind), ctypes.byref(gust), ctypes.byref(present)))
         return (wind, gust.value) if present.value else None
+
+    def set_fruit(self, fruit, values=(0, 0, 0)):
+        """Install the fruit plane uint8[S] (grid.fruit_plane) and the three kinds' values (each -16 .. 16); None takes the fruit
+        away again (gu_set_fruit).  Clears every env's mask of eaten fruit."""
+        f = None if fruit is None else _lib.as_array(fruit, np.uint8, (self.spec.S,), 'fruit')
+        v = _lib.as_array(values, np.int32, (3,), 'values')
+        check(self.lib.gu_set_fruit(self._h, ptr(f), ptr(v)))
+        self._n_fruit = 0 if f is None else int(np.count_nonzero(f))
+
+    def get_fruit(self):
+        """(fruit uint8[S], values int32[3]), or None while no fruit is set (gu_get_fruit)."""
+        fruit, values = np.empty(self.spec.S, np.uint8), np.empty(3, np.int32)
+        n = ctypes.c_int32(0)
+        check(self.lib.gu_get_fruit(self._h, ptr(fruit), ptr(values), ctypes.byref(n)))
+        return (fruit, values) if n.value else None
+
+    def get_fruit_state(self, env0=0, n=None):
+        """uint32[n]: the masks of eaten fruit (bit = slot) of envs env0 .. env0+n-1 (gu_get_fruit_state)."""
+        env0, n, n0 = self._env_range(env0, n)
+        eaten = np.empty(n0, np.uint32)
+        check(self.lib.gu_get_fruit_state(self._h, env0, n, ptr(eaten)))
+        return eaten
+
+    def set_fruit_state(self, eaten, env0=0):
+        """Install the masks uint32[n] of envs env0 .. env0+n-1 (gu_set_fruit_state)."""
+        e = _lib.as_array(eaten, np.uint32, None, 'eaten')
+        check(self.lib.gu_set_fruit_state(self._h, int(env0), e.size, ptr(e)))
+
+    @property
+    def td_rows(self):
+        """Rows of one env's Q table: S, or S << F while F fruits are set (include/gu.h: gu_set_fruit)."""
+        return self.spec.S << self._n_fruit
 
     def seed(self, seed):
         self.seed_value = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -251,12 +286,12 @@ class Engine(object):
         check(self.lib.gu_rollout(self._h, int(T), _POLICIES[policy], flags))
 
     ROLLOUT_FORM = ('family', 'layout', 'map', 'block', 'workgroups', 'lds_bytes', 'flags', 'K', 'row_shift', 'stream_words', 'pace_slot', 'pace_mode')
-    ROLLOUT_FAMILIES = {0: None, 1: 'general', 2: 'rows', 3: 'kstep', 4: 'wind'}
+    ROLLOUT_FAMILIES = {0: None, 1: 'general', 2: 'rows', 3: 'kstep', 4: 'wind', 5: 'fruit'}
     ROLLOUT_FLAG_BITS = ('pair', 'half', 'per_wave', 'pi_lds', 'straddle', 'entry_table', 'xcd_remap')
 
     def rollout_last_form(self):
         """What the last rollout of this engine ran on (gu_diag_rollout_form): dict with the twelve form words under the names of
-        ROLLOUT_FORM ('family' as a name: 'general', 'rows', 'kstep', 'wind'; None before the first rollout), each flag bit as a
+        ROLLOUT_FORM ('family' as a name: 'general', 'rows', 'kstep', 'wind', 'fruit'; None before the first rollout), each flag bit as a
         bool under its name in ROLLOUT_FLAG_BITS, and the raw words as 'words'."""
         words = np.zeros(len(self.ROLLOUT_FORM), np.int32)
         n = ctypes.c_int32(0)
@@ -370,15 +405,15 @@ class Engine(object):
                                  _learner_flags(trajectory, stats)))
 
     def td_get_q(self, env0=0, n=None):
-        """float64[n, S, 4]: the tables of envs env0 .. env0+n-1 (all from env0 when n is None)."""
+        """float64[n, S, 4]: the tables of envs env0 .. env0+n-1 (all from env0 when n is None); S << F rows under fruit."""
         env0, n, n0 = self._env_range(env0, n)
-        q = np.empty((n0, self.spec.S, 4), np.float64)
+        q = np.empty((n0, self.td_rows, 4), np.float64)
         check(self.lib.gu_td_get_q(self._h, env0, n, ptr(q)))
         return q
 
     def td_set_q(self, q, env0=0):
         """Install tables float64[n, S, 4] (or [S, 4] for one env) for envs env0 .. env0+n-1."""
-        q = _tables(q, (self.spec.S, 4), 'q')
+        q = _tables(q, (self.td_rows, 4), 'q')
         check(self.lib.gu_td_set_q(self._h, int(env0), q.shape[0], ptr(q)))
 
     # ------------------------------------------------------------------ tabular Dyna-Q (include/gu.h: gu_dyna_*)

@@ -157,3 +157,43 @@ def wind_plane(W, H, strength, direction='up'):
     if d.min() < 0 or d.max() > 3:
         raise ValueError('direction codes must lie in 0 .. 3')
     return np.ascontiguousarray((d | (k << 2)).astype(np.uint8).reshape(W * H))
+
+
+# ---- fruit: the per-cell plane of include/gu.h, gu_set_fruit -------------------------------------------------------
+FRUIT_KINDS = {'apple': 1, 'lemon': 2, 'melon': 3}  # the kind codes (0: no fruit)
+FRUIT_MAX = 32  # fruits per grid: one bit each in an env's uint32 mask
+
+
+def fruit_plane(W, H, cells, kinds='apple'):
+    """uint8[S]: the fruit plane of a W x H grid as gu_set_fruit takes it -- bits 0..4 of a fruit cell its slot, bits 5..6 its kind,
+    every other cell 0.  `cells`: 1 .. 32 distinct cell indices; the slots go by ascending cell index.  `kinds`: one name ('apple',
+    'lemon', 'melon') or code 1 .. 3 for all, or one per cell, in the order of `cells`."""
+    W, H = int(W), int(H)
+    S = W * H
+    c = np.asarray(cells)
+    if c.ndim != 1 or c.dtype == bool or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError('cells must be a list of cell indices')
+    if not 1 <= c.size <= FRUIT_MAX:
+        raise ValueError('1 .. {} fruit cells, got {}'.format(FRUIT_MAX, c.size))
+    if c.min() < 0 or c.max() >= S:
+        raise ValueError('fruit cells must lie in 0 .. {}'.format(S - 1))
+    if np.unique(c).size != c.size:
+        raise ValueError('a cell holds at most one fruit')
+    many = not isinstance(kinds, (str, bytes)) and np.ndim(kinds) == 1
+    ks = list(kinds) if many else [kinds] * c.size
+    if len(ks) != c.size:
+        raise ValueError('kinds must be one kind or one per cell ({}), got {}'.format(c.size, len(ks)))
+    codes = []
+    for k in ks:
+        if isinstance(k, str):
+            if k not in FRUIT_KINDS:
+                raise ValueError("a kind is one of 'apple', 'lemon', 'melon', or a code 1 .. 3")
+            k = FRUIT_KINDS[k]
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 3:
+            raise ValueError("a kind is one of 'apple', 'lemon', 'melon', or a code 1 .. 3")
+        codes.append(int(k))
+    plane = np.zeros(S, np.uint8)
+    order = np.argsort(c, kind='stable')
+    for slot, i in enumerate(order):
+        plane[int(c[i])] = slot | (codes[i] << 5)
+    return plane

@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib, softmax
 from .engine import Engine
 from .envs.griduniverse_env import GridUniverseEnv
-from .grid import GridSpec, wind_plane
+from .grid import FRUIT_KINDS, GridSpec, fruit_plane, wind_plane
 
 
 def check_off_policy_args(max_episode_len, epsilon, w_cap):
@@ -33,6 +33,7 @@ def check_off_policy_args(max_episode_len, epsilon, w_cap):
 
 
 class VecGridUniverse(object):
+    _n_fruit = 0  # fruits set (set_fruit): the Q tables have S << F rows
     _td_ready = False  # the engine holds Q tables (td_run / set_q_table allocate them on first use)
     _dyna_ready = False  # ... and Dyna-Q models (dyna_run / model allocate them on first use)
     _sweep_ready = False  # ... and priority queues (sweep_run / priority_queue allocate them, with the models, on first use)
@@ -152,6 +153,52 @@ class VecGridUniverse(object):
         plane = got[0].reshape(self.spec.H, self.spec.W)
         return dict(strength=(plane >> 2) & 3, direction=plane & 3, gust=got[1] / 65536.0)
 
+    def set_fruit(self, cells, kinds='apple', values=(1, 5, -5)):
+        """Fruit on the engine's grid (single-grid engines; include/gu.h: gu_set_fruit): the first step of an episode that ends on
+        a fruit cell adds the value of the fruit's kind to the step's reward; every reset grows the fruit back.  `cells` and `kinds`
+        as grid.fruit_plane takes them (1 .. 32 cells, none on a wall, goal or lava cell); `values`: what an 'apple', a 'lemon' and
+        a 'melon' pay, integers in -16 .. 16.  set_fruit(None) takes the fruit away.  step, rollout and td_run follow the fruit
+        (td_run learns on S << F rows, one per cell and mask of eaten fruit, at most 10 fruits); the other learners, the DP and
+        look-ahead calls, the path search, the trail and wind are refused while it is set.  sense and render do not show fruit."""
+        if cells is None:
+            self.engine.set_fruit(None)
+            F = 0
+        else:
+            v = np.asarray(values)
+            if v.shape != (3,) or v.dtype == bool or not np.issubdtype(v.dtype, np.integer) or v.min() < -16 or v.max() > 16:
+                raise ValueError('values must be three integers in -16 .. 16 (apple, lemon, melon)')
+            plane = fruit_plane(self.spec.W, self.spec.H, cells, kinds)
+            blocked = (self.spec.wall | self.spec.goal | self.spec.lava) & (plane != 0)
+            if blocked.any():
+                raise ValueError('fruit on cell {}, which is a wall or a goal or lava cell'.format(int(np.flatnonzero(blocked)[0])))
+            self.engine.set_fruit(plane, v.astype(np.int32))
+            F = int(np.count_nonzero(plane))
+        if F != self._n_fruit:  # (the library dropped tables of another row count, and the tree search's node pools with them)
+            self._td_ready = False
+            self._tree_sims = 0
+        self._n_fruit = F
+
+    def fruit(self):
+        """None while no fruit is set, else dict(cells=int64[F] ascending (index = slot), kinds=list of names, values=int32[3])."""
+        got = self.engine.get_fruit()
+        if got is None:
+            return None
+        cells = np.flatnonzero(got[0])
+        names = {code: name for name, code in FRUIT_KINDS.items()}
+        return dict(cells=cells, kinds=[names[int(c) >> 5] for c in got[0][cells]], values=got[1])
+
+    def fruit_eaten(self, env0=0, n=None):
+        """uint32[n]: the masks of eaten fruit of envs env0 .. env0+n-1 (to the end when n is None); bit k: the fruit of slot k
+        (the k-th fruit cell in ascending order) has been eaten in the env's current episode."""
+        return self.engine.get_fruit_state(env0, n)
+
+    def set_fruit_eaten(self, eaten, env0=0):
+        """Install masks uint32[n] (or one number) for envs env0 ..; no bit at or above the number of fruits."""
+        e = np.atleast_1d(np.asarray(eaten))
+        if e.ndim != 1 or e.dtype == bool or not np.issubdtype(e.dtype, np.integer) or (e.size and (e.min() < 0 or e.max() >> max(self._n_fruit, 1) != 0)):
+            raise ValueError('eaten must hold masks of the {} fruits set'.format(self._n_fruit))
+        self.engine.set_fruit_state(e.astype(np.uint32), env0)
+
     def _ensure_q(self, q0=None):
         """Q tables on the engine: tables of zeros on first use; every entry q0 (again) when q0 is given."""
         if q0 is not None or not self._td_ready:
@@ -183,11 +230,13 @@ class VecGridUniverse(object):
         return self._learner_out(T, trajectory, stats)
 
     def q_table(self, env0=0, n=None):
-        """float64[n, S, 4]: the Q tables of envs env0 .. env0+n-1 (to the end when n is None)."""
+        """float64[n, S, 4]: the Q tables of envs env0 .. env0+n-1 (to the end when n is None).  While F fruits are set
+        (set_fruit) the tables have S << F rows: row eaten * S + s belongs to cell s with the mask `eaten`."""
         return self.engine.td_get_q(env0, n)
 
     def set_q_table(self, q, env0=0):
-        """Install Q tables float64[n, S, 4] (or [S, 4]) for envs env0 ..; the other envs get tables of zeros if they had none."""
+        """Install Q tables float64[n, S, 4] (or [S, 4]) for envs env0 ..; the other envs get tables of zeros if they had none.
+        S << F rows while F fruits are set, as q_table()."""
         self._ensure_q()
         self.engine.td_set_q(q, env0)
 

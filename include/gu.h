@@ -205,6 +205,57 @@ int gu_get_cells(gu_handle h, int32_t grid_index, uint8_t *flags, int8_t *reward
 int gu_set_wind(gu_handle h, const uint8_t *wind /* [S], NULL = calm again */, uint32_t gust_q16);
 int gu_get_wind(gu_handle h, uint8_t *wind /* [S], may be NULL */, uint32_t *gust_q16, int32_t *present);
 
+/* ---- fruit: collectable rewards, each eaten once per episode ------------------------------------------------
+ * Build-defined (the reference has no fruit; restated on the CPU by tests/_fruit_oracle.py).  Fruit is a property of a SINGLE-GRID
+ * engine.  It consists of one byte per cell, fruit[s] -- bits 0..4 the slot (0 .. 31), bits 5..6 the kind (0 = no fruit, 1 / 2 / 3 =
+ * the three kinds; the Python names are apple, lemon, melon), bit 7 zero, and kind 0 requires the whole byte to be 0 --, three
+ * engine-wide values value[3], one per kind, each in -16 .. +16, and one uint32 eaten[e] per env.  F is the number of fruit cells,
+ * 1 .. 32; their slots are exactly 0 .. F-1, each used once.  A fruit may not lie on a wall or on a goal or lava cell; it may lie on a
+ * start cell.
+ * One step of env e from cell s with a valid action:
+ *   1. the lazy auto-reset, where the call has one, sets eaten[e] = 0 together with the position;
+ *   2. s', r, d come from the engine's move rule exactly as without fruit: fruit never changes a move and never ends an episode;
+ *   3. c = fruit[s'].  If (c >> 5) & 3 != 0 and bit c & 31 of eaten[e] is clear, then r += value[kind - 1] and that bit is set;
+ *   4. t += 1.
+ * So a reset does not eat the fruit of the start cell; a later step that ends there does, and so does a wall bump that leaves the
+ * agent on it.  A rejected action (outside -4 .. 3) eats nothing.  No RNG stream is added and none is drawn differently: the obs and
+ * done rows of gu_step and of a rollout (any policy) are byte for byte those of the engine without fruit, and the reward rows differ
+ * by value[kind - 1] exactly at each fruit's first visit of an episode.
+ * The bound on the values keeps a launch's int32 reward sum in range at the existing T <= 1e8: a step ends on one cell, so it eats
+ * at most one fruit; a fruit is eaten at most once per episode and cannot lie on a terminal cell, so the step that eats it pays
+ * the cell's -1 beside the value (|r| <= 17), and an episode that eats k fruits has at least k + 1 steps, the last one a terminal step
+ * of |r| <= 10.  No step pays more than 17 in absolute value, and 1e8 * 17 < 2^31.  (Reward planes that put +-10 on a cell that is not
+ * terminal can take such a step to 26; 8.2e7 steps are safe for those.)
+ * Every path that resets an env clears its mask: gu_reset (masked envs only), gu_reset_done, and the lazy resets inside the kernels.
+ * gu_set_fruit clears the masks of all envs; gu_set_state and gu_seed leave them alone.
+ * While fruit is set, gu_step (pinned I/O and the completion word included), gu_step_device, gu_rollout (all four policies,
+ * GU_F_TRAJECTORY / GU_F_STATS; GU_F_PACKED returns GU_ERR_UNSUPPORTED; rows are the three [T][N] planes, never triples) and gu_td_run
+ * (both methods) run their fruit kernels (csrc/gu_fruit.hip, csrc/gu_td.hip); every other call that moves envs or reads the move or
+ * reward rule -- gu_step_graph, the other learners' gu_*_run, gu_look_step_ahead, gu_vi_sweep / _run / _eval_run / _greedy /
+ * _sweep_step / _sweep_step_run, gu_mc_walk_lengths / _episodes, gu_shortest_paths -- returns GU_ERR_UNSUPPORTED.  Calls that read
+ * rows or state only (gu_mc_evaluate, sense, render, the getters, gu_read_*) are unaffected; they do not show fruit.
+ * THE LEARNERS' TABLES: a problem with fruit is Markov only on (cell, eaten), so while fruit is set a gu_td_run table has S << F
+ * rows and row eaten * S + s belongs to cell s with mask eaten.  Rules 1-4 of gu_td_run hold with "row of s" read as "row of
+ * (s, eaten)": the action is drawn on the row of (s, eaten), the bootstrap uses the pre-update row of (s', eaten'), the update goes to
+ * the row of (s, eaten); the arithmetic, the tie rule, the SARSA carry and the stream-4 words are as they are.  gu_td_init under
+ * fruit returns GU_ERR_INVALID for F > 10, else allocates N * (S << F) * 32 bytes under its free-memory rule; gu_td_get_q / gu_td_set_q
+ * move q[n][S << F][4].  No other learner ever sees such a table: they are refused while fruit is set.
+ * gu_set_fruit: fruit[S] and value[3], or fruit = NULL = no fruit again (the kernels without fruit run as before).  GU_ERR_STATE without
+ *              a grid; GU_ERR_UNSUPPORTED on a multi-grid engine, while wind is set (gu_set_wind refuses while fruit is set) and
+ *              while the agent trail is on (gu_trail_enable refuses while fruit is set); GU_ERR_INVALID for a malformed byte, a
+ *              repeated or missing slot, more than 32 fruits, a fruit on a wall or terminal cell, or a value outside -16 .. 16.
+ *              Ends what the learners carry from launch to launch, destroys a captured step graph, and drops the Q tables (as a grid
+ *              of another size does: gu_td_run returns GU_ERR_STATE until gu_td_init) whenever it changes their row count -- it keeps
+ *              them when the row count stays; clearing fruit goes back to S rows the same way.  Keeps positions and step counts.
+ *              gu_set_grid, gu_set_grids and gu_generate_mazes drop the fruit.
+ * gu_get_fruit: the plane (zeros when none), the values and F (0 = none set); any pointer may be NULL.
+ * gu_get_fruit_state / gu_set_fruit_state: the masks of envs env0 .. env0+n-1; GU_ERR_STATE while no fruit is set; setting a bit at or
+ *              above F is GU_ERR_INVALID.  Setting masks ends the learners' carries (a carried SARSA action belongs to the old row). */
+int gu_set_fruit(gu_handle h, const uint8_t *fruit /* [S], NULL = no fruit again */, const int32_t value[3]);
+int gu_get_fruit(gu_handle h, uint8_t *fruit /* zeros when none */, int32_t value[3], int32_t *n_fruit /* 0 = none set */);
+int gu_get_fruit_state(gu_handle h, int64_t env0, int64_t n, uint32_t *eaten);
+int gu_set_fruit_state(gu_handle h, int64_t env0, int64_t n, const uint32_t *eaten);  /* a bit at or above F: GU_ERR_INVALID */
+
 /* ---- RNG ---------------------------------------------------------------------
  * Keys the per-env counter RNG (MurmurHash3 of seed, global env id, stream,
  * counter -- 32-bit counters, no stream repeats before 2^32 draws; host view:
@@ -384,7 +435,7 @@ int gu_sweep_get_queue(gu_handle h, int64_t env0, int64_t n, uint64_t *key, int3
 int gu_diag_sweep_heap(gu_handle h, int64_t env0, int64_t n, uint64_t *heap, int32_t *pos);
 /* gu_diag_rollout_form : introspection -- what the last gu_rollout of this engine ran on, as the launcher planned it
  *                      (csrc/gu_rollout_plan.hpp; DESIGN.md "Rollout dispatch").  *count = 12 words; with `form`, capacity >= 12:
- *                      kernel family (1 general, 2 transition-row, 3 K-step, 4 windy); row layout (0 none, 1 planes, 2 packed, 3 triples);
+ *                      kernel family (1 general, 2 transition-row, 3 K-step, 4 windy, 5 fruit); row layout (0 none, 1 planes, 2 packed, 3 triples);
  *                      MAP of the general kernel (0 / 1 / 3 / 5), else -1; workgroup size; workgroups; dynamic LDS bytes; flag bits (1 pair
  *                      tables, 2 half waves, 4 per-wave grids, 8 thresholds in LDS, 16 straddles a 2^32-step boundary, 32 first step on the
  *                      table, 64 XCD-aware block order); K of the K-step kernel; log2 of the table's row pitch; staged action words per lane;

@@ -1,0 +1,535 @@
+"""Fruit on the device (gu_set_fruit; csrc/gu_fruit.hip and the fruit gu_td_kernel instantiations) against the CPU restatement
+tests/_fruit_oracle.py: step, rollout and td_run compared byte for byte -- rows, statistics, positions, masks, tables --, every reset
+path, every refusal, and the engine after the fruit has been taken away against one that never had any."""
+import functools
+
+import numpy as np
+import pytest
+
+import griduniverse_amd as gua
+from griduniverse_amd.algorithms.exploration import ucb_tables
+from griduniverse_amd.algorithms.temporal_difference import q_learning
+from griduniverse_amd.grid import fruit_plane, wind_plane
+
+from . import _fruit_oracle as O
+from ._tabular_cases import GRIDS, _eps, _grid, _same, _spec
+
+pytestmark = pytest.mark.gpu
+
+METHODS = {'q_learning': O.Q_LEARNING, 'sarsa': O.SARSA}
+VALUES = (3, -7, 16)
+
+
+@functools.lru_cache(maxsize=None)
+def _case(name):
+    """(grid dict, fruit plane uint8[S]).  'default4x4': fruit on the corner start cell 0 (a wall bump there eats it: the cell stays,
+    the row changes) and on cell 14 before the goal.  'maze11': one fruit of each kind.  'open150': 150 x 150 cells without walls --
+    two planes fit 64 KiB of LDS there and three (67 536 bytes) do not: the L2 kernels -- with four fruits near the start.  'full8x8':
+    an open 8 x 8 grid with 32 fruits: slot 31."""
+    if name == 'default4x4':
+        g = GRIDS['default4x4']()
+        return g, fruit_plane(4, 4, [0, 14], ['apple', 'lemon'])
+    if name == 'maze11':
+        g = GRIDS['maze11']()
+        taken = set(g['walls']) | set(g['goals']) | set(g['lava'])
+        free = [s for s in range(121) if s not in taken]
+        return g, fruit_plane(11, 11, [free[3], free[len(free) // 2], free[-4]], ['apple', 'lemon', 'melon'])
+    if name == 'open150':
+        W = H = 150
+        S = W * H
+        g = dict(W=W, H=H, starts=[0], goals=[S - 1, 3 * W + 3], lava=[2 * W + 5], walls=[])
+        assert 2 * ((S + 15) & ~15) <= 65536 < 3 * ((S + 15) & ~15) == 67536
+        return g, fruit_plane(W, H, [1, W, W + 1, 2], ['apple', 'lemon', 'melon', 'melon'])
+    g = dict(W=8, H=8, starts=[0], goals=[63], lava=[], walls=[])
+    return g, fruit_plane(8, 8, list(range(1, 33)), [1 + k % 3 for k in range(32)])
+
+
+def _scatter(g, N):
+    taken = set(g['walls']) | set(g['goals']) | set(g['lava'])
+    free = np.array([s for s in range(g['W'] * g['H']) if s not in taken], np.int32)
+    return free[np.random.RandomState(N).randint(0, len(free), N)]
+
+
+def _pair(name, N, seed, q0=None, scatter=True, values=VALUES):
+    """A batch of N envs on the case's grid under its fruit and the oracle of it, both reset (and then scattered over the grid)."""
+    g, plane = _case(name)
+    vec = gua.VecGridUniverse(N, template=_spec(g), seed=seed)
+    o = O.FruitOracle(_grid(g), seed, N, plane, values, q0=q0)
+    cells = np.flatnonzero(plane)
+    vec.set_fruit(cells, [int(c) >> 5 for c in plane[cells]], values)
+    if q0 is not None:
+        vec._ensure_q(q0)
+    assert np.array_equal(vec.reset(), o.reset())
+    if scatter:
+        vec.set_state(pos=_scatter(g, N))
+        o.state.pos[:] = _scatter(g, N)
+    return vec, o
+
+
+def _same_state(vec, o):
+    st = vec.get_state()
+    assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'] != 0, o.state.done != 0)
+    assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
+    assert np.array_equal(vec.fruit_eaten(), o.eaten)
+
+
+# ---- 1: round trip and errors ----
+def test_set_fruit_round_trip_and_errors():
+    g, plane = _case('maze11')
+    cells = np.flatnonzero(plane)
+    vec = gua.VecGridUniverse(8, template=_spec(g))
+    try:
+        eng = vec.engine
+        assert vec.fruit() is None and eng.get_fruit() is None
+        for call in (lambda: vec.fruit_eaten(), lambda: eng.set_fruit_state(np.zeros(8, np.uint32))):
+            with pytest.raises(gua.GuError) as err:  # GU_ERR_STATE while no fruit is set
+                call()
+            assert err.value.code == -4
+        vec.set_fruit(cells[::-1], ['melon', 'lemon', 'apple'], VALUES)
+        got = vec.fruit()
+        assert np.array_equal(got['cells'], cells) and got['kinds'] == ['apple', 'lemon', 'melon'] and tuple(got['values']) == VALUES
+        assert np.array_equal(eng.get_fruit()[0], plane)
+        assert np.array_equal(vec.fruit_eaten(), np.zeros(8, np.uint32)) and vec.fruit_eaten(2, 3).shape == (3,)
+        vec.set_fruit_eaten([5, 7, 1], env0=2)
+        assert np.array_equal(vec.fruit_eaten(), np.array([0, 0, 5, 7, 1, 0, 0, 0], np.uint32))
+        with pytest.raises(gua.GuError) as err:  # a bit at or above F
+            eng.set_fruit_state(np.array([8], np.uint32), 0)
+        assert err.value.code == -1
+        wall, goal = g['walls'][0], g['goals'][0]
+
+        def with_byte(cell, byte, base=plane):
+            p = base.copy()
+            p[cell] = byte
+            return p
+        bad_planes = [with_byte(cells[0], plane[cells[0]] | 128), with_byte(cells[0], 5),  # bit 7; kind 0 with a slot
+                      with_byte(cells[1], plane[cells[0]]), with_byte(cells[2], 32 | 3),  # a slot twice; slot 2 missing (0, 1, 3)
+                      with_byte(wall, 32 | 3), with_byte(goal, 32 | 3), np.zeros(121, np.uint8)]
+        many = np.zeros(121, np.uint8)
+        taken = set(g['walls']) | set(g['goals']) | set(g['lava'])
+        free = [s for s in range(121) if s not in taken]
+        many[free[:33]] = 32 | (np.arange(33) & 31)  # 33 fruits
+        for bad in bad_planes + [many]:
+            with pytest.raises(gua.GuError) as err:
+                eng.set_fruit(bad, VALUES)
+            assert err.value.code == -1
+        for values in ((17, 0, 0), (0, 0, -17)):
+            with pytest.raises(gua.GuError) as err:
+                eng.set_fruit(plane, values)
+            assert err.value.code == -1
+        assert np.array_equal(eng.get_fruit()[0], plane) and np.array_equal(vec.fruit_eaten()[2:5], [5, 7, 1])  # a refused call changes nothing
+        vec.set_fruit(cells, 'apple', (1, 5, -5))  # set_fruit clears every mask
+        assert not vec.fruit_eaten().any()
+        vec.set_fruit(None)
+        assert vec.fruit() is None
+    finally:
+        vec.close()
+
+
+# ---- 2: step and step_device ----
+@pytest.mark.parametrize('N', [1, 63, 256])
+@pytest.mark.parametrize('auto', [True, False])
+@pytest.mark.parametrize('case', ['default4x4', 'maze11'])
+def test_step_and_step_device_equal_the_oracle(case, auto, N):
+    T = 60
+    vec, o = _pair(case, N, 4, scatter=False)
+    try:
+        g, plane = _case(case)
+        vec.auto_reset = auto
+        acts = np.random.RandomState(11).randint(-4, 4, (T, N)).astype(np.int32)
+        ate = 0
+        for i in range(T):
+            a = acts[i].copy()
+            if i == 10:
+                # env 0 is put next to a fruit it has not eaten and given a rejected action: it does not step and eats nothing
+                cell = int(np.flatnonzero(plane)[-1])
+                beside = cell - 1 if case == 'default4x4' else next(c for c in (cell - 1, cell + 1, cell - 11, cell + 11) if c not in g['walls'])
+                pos = vec.get_state()['pos']
+                pos[0] = beside
+                vec.set_state(pos=pos, done=np.zeros(N, np.int32))
+                o.state.pos[:], o.state.done[:] = pos, 0
+                vec.set_fruit_eaten(np.zeros(N, np.uint32))
+                o.set_eaten(np.zeros(N, np.uint32))
+                a[0] = 7
+                with pytest.raises(gua.GuError) as err:
+                    vec.step(a)
+                assert err.value.code == -1
+                o.step(a, auto)
+                _same_state(vec, o)
+                assert vec.fruit_eaten(0, 1)[0] == 0 and vec.get_state()['pos'][0] == beside
+                continue
+            obs, rew, don, _ = vec.step(a, zero_copy=(i % 2 == 1))
+            w_obs, w_rew, w_don, rejected = o.step(a, auto)
+            assert not rejected.any()
+            assert np.array_equal(obs, w_obs) and np.array_equal(rew, w_rew) and np.array_equal(don, w_don != 0), i
+            ate += int((o.eaten != 0).any())
+        assert ate > 0
+        _same_state(vec, o)
+        # the same rows from the device-resident stream
+        vec.seed(4)
+        o2 = O.FruitOracle(o.grid, 4, N, o.fruit, VALUES, q0=None)
+        assert np.array_equal(vec.reset(), o2.reset())
+        assert not vec.fruit_eaten().any()
+        vec.engine.upload_actions(acts)
+        for i in range(T):
+            vec.engine.step_device(i, auto)
+            obs, rew, don = vec.engine.read_outputs()
+            w_obs, w_rew, w_don, _ = o2.step(acts[i], auto)
+            assert np.array_equal(obs, w_obs) and np.array_equal(rew, w_rew) and np.array_equal(don != 0, w_don != 0), i
+        _same_state(vec, o2)
+    finally:
+        vec.close()
+
+
+# ---- 3: rollout ----
+def _policy_table(S):
+    pi = np.random.RandomState(1).dirichlet(np.ones(4), S)
+    pi[::7] = np.eye(4)[np.arange(len(pi[::7])) % 4]  # one-hot rows: thresholds that no word reaches
+    return pi
+
+
+@pytest.mark.parametrize('N', [200, 1])
+@pytest.mark.parametrize('auto', [True, False])
+@pytest.mark.parametrize('policy', ['uniform', 'stream', 'greedy', 'sample'])
+@pytest.mark.parametrize('case', ['default4x4', 'maze11'])
+def test_rollout_equals_the_oracle_and_a_twin_without_fruit(case, policy, auto, N):
+    T = 50
+    vec, o = _pair(case, N, 6)
+    g = _case(case)[0]
+    twin = gua.VecGridUniverse(N, template=_spec(g), seed=6)  # the engine without fruit
+    try:
+        S = o.grid.S
+        pi = _policy_table(S) if policy in ('greedy', 'sample') else None
+        acts = np.random.RandomState(2).randint(0, 4, (T, N)).astype(np.int32) if policy == 'stream' else None
+        twin.reset()
+        twin.set_state(pos=_scatter(g, N))
+        for v in (vec, twin):
+            if pi is not None:
+                v.engine.vi_set(np.zeros(S), pi)
+        want = o.rollout(T, policy, auto, actions=acts, pi=pi)
+        # two launches of 25 ...
+        halves = [vec.rollout(25, policy, actions=None if acts is None else acts[k * 25:(k + 1) * 25], auto_reset=auto, stats=True) for k in range(2)]
+        assert vec.engine.rollout_last_form()['family'] == 'fruit'
+        for k in ('obs', 'reward', 'done'):
+            assert np.array_equal(np.concatenate([h[k] for h in halves]), want[k]), k
+        assert np.array_equal(halves[0]['ret'] + halves[1]['ret'], want['ret'])
+        assert np.array_equal(halves[0]['episodes'] + halves[1]['episodes'], want['episodes'])
+        _same_state(vec, o)
+        # ... equal one of 50
+        vec.seed(6)
+        vec.reset()
+        vec.set_state(pos=_scatter(g, N))
+        got = vec.rollout(T, policy, actions=acts, auto_reset=auto, stats=True)
+        _same(got, want)
+        _same_state(vec, o)
+        # fruit never changes a move: obs and done are the twin's
+        calm = twin.rollout(T, policy, actions=acts, auto_reset=auto)
+        assert np.array_equal(got['obs'], calm['obs']) and np.array_equal(got['done'], calm['done'])
+        if N > 1 and policy == 'uniform':
+            assert (got['reward'] != calm['reward']).any()
+        # statistics alone
+        vec.seed(6)
+        vec.reset()
+        vec.set_state(pos=_scatter(g, N))
+        only = vec.rollout(T, policy, actions=acts, auto_reset=auto, trajectory=False, stats=True)
+        assert np.array_equal(only['ret'], want['ret']) and np.array_equal(only['episodes'], want['episodes'])
+        _same_state(vec, o)
+    finally:
+        vec.close()
+        twin.close()
+
+
+# ---- 4: the L2 path ----
+def test_three_planes_that_do_not_fit_lds_rollout_and_td_run():
+    N, T = 64, 30
+    vec, o = _pair('open150', N, 3, q0=0.0, scatter=False)
+    try:
+        got = vec.rollout(T, 'uniform', auto_reset=True, stats=True)
+        form = vec.engine.rollout_last_form()
+        assert form['family'] == 'fruit' and form['lds_bytes'] == 0
+        _same(got, o.rollout(T, 'uniform', True))
+        assert (o.eaten != 0).sum() > N // 2
+        _same_state(vec, o)
+        vec.reset()
+        o.reset()
+        for method in ('q_learning', 'sarsa'):
+            got = vec.td_run(T, method, alpha=0.25, discount_factor=0.9, epsilon=0.3, trajectory=True, stats=True)
+            _same(got, o.td_run(T, METHODS[method], 0.25, 0.9, _eps(0.3)))
+        assert vec.q_table().shape == (N, 22500 << 4, 4) and vec.q_table().tobytes() == o.q.tobytes()
+        _same_state(vec, o)
+    finally:
+        vec.close()
+
+
+# ---- 5: slot 31 ----
+def test_thirty_two_fruits_reach_slot_31():
+    N, T = 64, 300
+    vec, o = _pair('full8x8', N, 5, scatter=False)
+    try:
+        _same(vec.rollout(T, 'uniform', auto_reset=False, stats=True), o.rollout(T, 'uniform', False))
+        _same_state(vec, o)
+        assert (o.eaten >> 31).any() and (o.eaten >> 16 & 0xFF).any()  # the high slots are eaten, and slot 31 with an unsigned shift
+        top = np.full(N, 0x80000001, np.uint32)
+        vec.set_fruit_eaten(top)  # bit 31 is a valid slot of 32 fruits
+        assert np.array_equal(vec.fruit_eaten(), top)
+        with pytest.raises(gua.GuError) as err:  # learners take at most 10 fruits
+            vec.engine.td_init(0.0)
+        assert err.value.code == -1
+    finally:
+        vec.close()
+
+
+# ---- 6: td_run ----
+@pytest.mark.parametrize('N', [1, 63, 256])
+@pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
+@pytest.mark.parametrize('case', ['default4x4', 'maze11'])
+def test_td_run_tables_rows_and_stats_equal_the_oracle(case, method, N):
+    T = 200
+    vec, o = _pair(case, N, 3, q0=0.0 if N != 63 else 0.5, scatter=case != 'default4x4')
+    try:
+        S, F = o.grid.S, o.F
+        if N == 256:  # tables of [n, S << F, 4] through set_q_table / q_table
+            q = np.random.RandomState(7).uniform(-1, 1, (N, S << F, 4))
+            vec.set_q_table(q)
+            o.q[:] = q
+            assert vec.q_table(3, 2).tobytes() == q[3:5].tobytes()
+        want = o.td_run(T, METHODS[method], 0.25, 0.9, _eps(0.3))
+        got = vec.td_run(T, method, alpha=0.25, discount_factor=0.9, epsilon=0.3, trajectory=True, stats=True)
+        _same(got, want)
+        assert vec.q_table().shape == (N, S << F, 4) and vec.q_table().tobytes() == o.q.tobytes()
+        _same_state(vec, o)
+        if case == 'default4x4' and N > 1:
+            # the hazard: a wall bump on the corner start cell as the first step of an episode (a reset eats nothing) eats its fruit --
+            # s' == s and the row changes
+            fresh = np.concatenate([np.ones((1, N), bool), want['done'][:-1] != 0])
+            bump = fresh & (want['obs'] == 0) & (want['reward'] == -1 + VALUES[0])
+            assert bump.any()
+    finally:
+        vec.close()
+
+
+# ---- 7: the SARSA carry ----
+def test_sarsa_split_in_two_carries_its_action_and_set_fruit_and_set_fruit_eaten_drop_it():
+    vec, o = _pair('maze11', 130, 8, q0=0.0)
+    twin, o1 = _pair('maze11', 130, 8, q0=0.0)
+    try:
+        kw = dict(alpha=0.5, discount_factor=0.95, epsilon=0.3, trajectory=True, stats=True)
+        for T in (100, 100):  # the second launch starts with the first one's a'
+            _same(vec.td_run(T, 'sarsa', **kw), o.td_run(T, O.SARSA, 0.5, 0.95, _eps(0.3)))
+        assert o.carry_valid and (o.carry >= 0).any()
+        _same(twin.td_run(200, 'sarsa', **kw), o1.td_run(200, O.SARSA, 0.5, 0.95, _eps(0.3)))  # ... and equals one launch
+        assert vec.q_table().tobytes() == twin.q_table().tobytes() == o.q.tobytes()
+        masks = o.eaten.copy()
+        vec.set_fruit_eaten(masks)  # the same masks again: the carry goes
+        o.set_eaten(masks)
+        _same(vec.td_run(50, 'sarsa', **kw), o.td_run(50, O.SARSA, 0.5, 0.95, _eps(0.3)))
+        assert o.carry_valid
+        vec.engine.set_fruit(o.fruit, VALUES)  # the same fruit again: tables, positions and counts stay, the masks and the carry go
+        q = o.q.copy()
+        o.set_fruit(o.fruit, VALUES)
+        assert o.q.tobytes() == q.tobytes()
+        _same(vec.td_run(50, 'sarsa', **kw), o.td_run(50, O.SARSA, 0.5, 0.95, _eps(0.3)))
+        assert vec.q_table().tobytes() == o.q.tobytes()
+        _same_state(vec, o)
+    finally:
+        vec.close()
+        twin.close()
+
+
+# ---- 8: reset paths ----
+def test_every_reset_path_clears_the_masks_of_the_envs_it_resets():
+    N = 130
+    vec, o = _pair('default4x4', N, 2, scatter=False)
+    try:
+        _same(vec.rollout(40, 'uniform', auto_reset=False, stats=True), o.rollout(40, 'uniform', False))
+        assert (o.eaten != 0).sum() > N // 2 and (o.state.done != 0).any() and (o.state.done == 0).any()
+        _same_state(vec, o)
+        before = o.eaten.copy()
+        vec.set_state(pos=o.state.pos)  # set_state and seed leave the masks alone
+        vec.seed(2)
+        o.state.episode[:] = 0
+        o.state.tcount[:] = 0
+        assert np.array_equal(vec.fruit_eaten(), before)
+        vec.engine.reset_done()  # the done envs only
+        d = o.reset_done()
+        assert d.any() and not o.eaten[d].any() and np.array_equal(o.eaten[~d], before[~d])
+        _same_state(vec, o)
+        mask = (np.arange(N) % 3 == 0).astype(np.uint8)
+        assert np.array_equal(vec.reset(mask), o.reset(mask))  # the masked envs only
+        assert (o.eaten[mask == 0] != 0).any()
+        _same_state(vec, o)
+        _same(vec.rollout(60, 'uniform', auto_reset=True, stats=True), o.rollout(60, 'uniform', True))  # the lazy reset
+        _same_state(vec, o)
+        assert np.array_equal(vec.reset(), o.reset()) and not vec.fruit_eaten().any()
+    finally:
+        vec.close()
+
+
+# ---- 9: refusals ----
+def test_calls_without_a_fruit_form_are_refused_while_fruit_is_set():
+    g, plane = _case('maze11')
+    N, S = 64, 121
+    vec = gua.VecGridUniverse(N, template=_spec(g), seed=1)
+    try:
+        eng = vec.engine
+        vec.reset()
+        eng.upload_actions(np.zeros((4, N), np.int32))
+        eng.vi_set(np.zeros(S), np.full((S, 4), 0.25))
+        eng.reserve_trajectory(8)
+        vec.set_exploration(*ucb_tables(1.0, 16))
+        vec.set_features(np.arange(S, dtype=np.int32)[:, None])
+        cdf = np.tile(np.array([0.25, 0.5, 0.75, 1.0]), (S, 1))
+        u = np.random.RandomState(0).rand(256)
+        start = g['starts'][0]
+        calls = {
+            'gu_step_graph': lambda: eng.step_graph(0, 4),
+            'gu_dyna_run': lambda: vec.dyna_run(5, planning_steps=2),
+            'gu_sweep_run': lambda: vec.sweep_run(5),
+            'gu_search_run': lambda: vec.search_run(3, simulations=1, depth=2),
+            'gu_explore_run': lambda: vec.explore_run(5),
+            'gu_mcts_run': lambda: vec.tree_search_run(3, simulations=1, tree_depth=2, depth=2),  # (one simulation: the pool _ensure_tree made)
+            'gu_nstep_run': lambda: vec.nstep_run(5),
+            'gu_lambda_run': lambda: vec.lambda_run(5),
+            'gu_ac_run': lambda: vec.actor_critic_run(5),
+            'gu_reinforce_run': lambda: vec.reinforce_run(5),
+            'gu_is_run': lambda: vec.off_policy_mc_run(5),
+            'gu_fa_run': lambda: vec.fa_run(5),
+            'gu_look_step_ahead': lambda: eng.look_step_ahead([start], [1]),
+            'gu_vi_sweep': lambda: eng.vi_sweep(0.9, 1),
+            'gu_vi_run': lambda: eng.vi_run(0.9, 1e-3, 3),
+            'gu_vi_eval_run': lambda: eng.vi_eval_run(0.9, 1e-3, 3),
+            'gu_vi_greedy': lambda: eng.vi_greedy(0.9),
+            'gu_vi_sweep_step': lambda: eng.vi_sweep_step(0.9),
+            'gu_vi_sweep_step_run': lambda: eng.vi_sweep_step_run(0.9, 2),
+            'gu_mc_walk_lengths': lambda: eng.mc_walk_lengths(u, 8, [start], 16, cdf),
+            'gu_mc_walk_episodes': lambda: eng.mc_walk_episodes(u, cdf, np.zeros(N, np.int64), np.full(N, start, np.int32), 16, 8),
+            'gu_shortest_paths': lambda: eng.shortest_paths(),
+        }
+        # the tables the learners need exist before the fruit is set (the inits are not refused either way)
+        vec._ensure_q()
+        vec._ensure_model()
+        vec._ensure_queue()
+        vec._ensure_counts()
+        vec._ensure_tree()
+        vec._ensure_ac()
+        vec._ensure_is()
+        eng.set_fruit(plane, VALUES)
+        for name, call in calls.items():
+            with pytest.raises(gua.GuError) as err:
+                call()
+            assert err.value.code == -6 and 'fruit' in str(err.value), name
+        with pytest.raises(gua.GuError) as err:  # packed rows
+            eng.rollout(8, 'uniform', True, 'packed')
+        assert err.value.code == -6 and 'fruit' in str(err.value)
+        with pytest.raises(gua.GuError) as err:  # the trail refuses while fruit is set
+            eng.trail_enable(16)
+        assert err.value.code == -6 and 'fruit' in str(err.value)
+        with pytest.raises(gua.GuError) as err:  # fruit, then wind
+            eng.set_wind(wind_plane(11, 11, np.ones(11, int)), 0)
+        assert err.value.code == -6 and 'fruit' in str(err.value)
+        # what reads rows or state only is unaffected
+        vec.rollout(8, 'uniform', auto_reset=True)
+        eng.mc_evaluate(8, np.full(N, start, np.int32), 0.9 ** np.arange(8), np.ones(8, bool))
+        eng.vi_get()
+        vec.sense(radius=1)
+        vec.get_state()
+        vec.set_fruit(None)
+        vec._td_ready, vec._tree_sims = False, 0  # (the tables went when the fruit changed their row count, the node pools with them)
+        vec._ensure_tree()
+        for name, call in calls.items():  # the same calls succeed once the fruit is gone
+            call()
+        eng.set_wind(wind_plane(11, 11, np.ones(11, int)), 0)  # wind, then fruit
+        with pytest.raises(gua.GuError) as err:
+            eng.set_fruit(plane, VALUES)
+        assert err.value.code == -6 and 'wind' in str(err.value)
+        eng.set_wind(None)
+        eng.trail_enable(16)  # the trail, then fruit
+        with pytest.raises(gua.GuError) as err:
+            eng.set_fruit(plane, VALUES)
+        assert err.value.code == -6 and 'trail' in str(err.value)
+        eng.trail_enable(0)
+        eng.set_fruit(plane, VALUES)
+        assert eng.get_fruit() is not None
+        eng.set_grid(_spec(g))  # a new grid drops the fruit
+        assert eng.get_fruit() is None
+        eng.look_step_ahead([start], [1])
+    finally:
+        vec.close()
+    grids = [_spec(g), _spec(g)]
+    multi = gua.VecGridUniverse(N, templates=grids, seed=1)
+    try:
+        with pytest.raises(gua.GuError) as err:  # fruit is a property of a single-grid engine
+            multi.engine.set_fruit(plane, VALUES)
+        assert err.value.code == -6 and 'fruit' in str(err.value)
+        multi.engine.set_grid(_spec(g))
+        multi.engine.set_fruit(plane, VALUES)
+        multi.engine.set_grids(grids)  # ... and several grids drop it
+        assert multi.engine.get_fruit() is None
+        multi.engine.set_grid(_spec(g))
+        multi.engine.set_fruit(plane, VALUES)
+        multi.engine.generate_mazes(2, 11, 11, 5)  # ... as device mazes do
+        assert multi.engine.get_fruit() is None
+    finally:
+        multi.close()
+
+
+# ---- 10: clearing fruit ----
+def test_an_engine_without_its_fruit_again_is_the_engine_that_never_had_any():
+    g, plane = _case('maze11')
+    N, seed = 200, 9
+    vec = gua.VecGridUniverse(N, template=_spec(g), seed=seed)
+    ref = gua.VecGridUniverse(N, template=_spec(g), seed=seed)
+    try:
+        vec.set_fruit(np.flatnonzero(plane), ['apple', 'lemon', 'melon'], VALUES)
+        vec.reset()
+        vec.td_run(20, 'q_learning')
+        vec.rollout(20, 'uniform', auto_reset=True)
+        assert vec.engine.rollout_last_form()['family'] == 'fruit'
+        vec.set_fruit(None)
+        with pytest.raises(gua.GuError) as err:  # the tables of S << 3 rows went with the fruit
+            vec.engine.td_run(5)
+        assert err.value.code == -4
+        with pytest.raises(gua.GuError) as err:  # ... for the other learners too
+            vec.engine.nstep_run(5)
+        assert err.value.code == -4
+        vec.seed(seed)
+        assert np.array_equal(vec.reset(), ref.reset())
+        for auto in (True, False):
+            _same(vec.rollout(100, 'uniform', auto_reset=auto, stats=True), ref.rollout(100, 'uniform', auto_reset=auto, stats=True))
+            a, b = vec.engine.rollout_last_form(), ref.engine.rollout_last_form()
+            assert a['family'] == b['family'] != 'fruit' and a['words'] == b['words']
+        acts = np.random.RandomState(3).randint(0, 4, (8, N)).astype(np.int32)
+        for i in range(8):
+            a, b = vec.step(acts[i]), ref.step(acts[i])
+            assert all(np.array_equal(x, y) for x, y in zip(a[:3], b[:3]))
+        for method in ('q_learning', 'sarsa'):
+            kw = dict(alpha=0.3, discount_factor=0.9, epsilon=0.2, trajectory=True, stats=True)
+            _same(vec.td_run(120, method, **kw), ref.td_run(120, method, **kw))
+            assert vec.q_table().shape == (N, 121, 4) and vec.q_table().tobytes() == ref.q_table().tobytes()
+        a, b = vec.get_state(), ref.get_state()
+        assert all(np.array_equal(a[k], b[k]) for k in ('pos', 'done', 'episode', 'tcount'))
+        # fruit whose values are zero: the calm learner's rows, on the rows of the masks
+        vec.set_fruit(np.flatnonzero(plane), 'apple', (0, 0, 0))
+        for v in (vec, ref):
+            v.seed(seed)
+            v.reset()
+        _same(vec.rollout(100, 'uniform', auto_reset=True, stats=True), ref.rollout(100, 'uniform', auto_reset=True, stats=True))
+    finally:
+        vec.close()
+        ref.close()
+
+
+# ---- 11: the learning claim ----
+def test_q_learning_end_to_end_finds_the_melon_walk():
+    """64 learners, O.CLAIM_STEPS steps, alpha 0.5, gamma 0.95, epsilon 0.1 on the 5 x 3 grid of tests/test_fruit_host.py: the tables
+    equal the restatement's byte for byte, so every greedy walk eats the melon, avoids the lemon and returns 13."""
+    L, seed = O.CLAIM_LEARNERS, 1
+    env = gua.GridUniverseEnv(grid_shape=(O.CLAIM_W, O.CLAIM_H), initial_state=O.CLAIM['starts'][0], goal_states=O.CLAIM['goals'])
+    q = q_learning(env, O.CLAIM_STEPS, alpha=O.CLAIM_ALPHA, discount_factor=O.CLAIM_GAMMA, epsilon=0.1, num_learners=L, seed=seed,
+                   fruit=(O.CLAIM_CELLS, O.CLAIM_KINDS, O.CLAIM_VALUES))
+    grid, plane = _grid(O.CLAIM), fruit_plane(O.CLAIM_W, O.CLAIM_H, O.CLAIM_CELLS, O.CLAIM_KINDS)
+    o = O.FruitOracle(grid, seed, L, plane, O.CLAIM_VALUES, q0=0.0)
+    o.reset()
+    o.td_run(O.CLAIM_STEPS, O.Q_LEARNING, O.CLAIM_ALPHA, O.CLAIM_GAMMA, O.CLAIM_EPS_Q16)
+    assert q.shape == (L, 15 << 2, 4) and q.tobytes() == o.q.tobytes()
+    returns = [O.greedy_walk(grid, plane, O.CLAIM_VALUES, q[e]) for e in range(L)]
+    assert returns == [O.CLAIM_RETURN] * L, returns
