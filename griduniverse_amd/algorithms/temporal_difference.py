@@ -19,11 +19,12 @@ from ..vec_env import VecGridUniverse
 _CHUNK = 100000  # steps per launch (the launch limit is 1e8; shorter launches keep the device responsive)
 
 
-def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, wind=None, gust=0.0, fruit=None):
+def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, wind=None, gust=0.0, fruit=None, doors=None):
     """The learner batch of q_learning / sarsa / n_step_* / *_lambda / dyna_q: L learners on the grid of `env`, tables of q0 (and empty models when
     `model`), `num_steps` real steps each in launches `launch(vec, T)` of at most `chunk` steps.  Returns Q [S][4] or [L][S][4].
     `wind`: a strength array or a (strength, direction) pair for VecGridUniverse.set_wind, with `gust`.  `fruit`: (cells, kinds,
-    values) for VecGridUniverse.set_fruit; the tables then have S << F rows."""
+    values) for VecGridUniverse.set_fruit; the tables then have S << F rows.  `doors`: dict(doors=, keys=, levers=) for
+    VecGridUniverse.set_doors; the tables then have S << D rows."""
     L = int(num_learners)
     vec = VecGridUniverse(L, template=env, seed=seed)
     try:
@@ -32,6 +33,8 @@ def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, w
             vec.set_wind(strength, direction, gust)
         if fruit is not None:
             vec.set_fruit(*fruit)
+        if doors is not None:
+            vec.set_doors(doors['doors'], doors.get('keys'), doors.get('levers'))
         vec._ensure_q(q0)
         if model:
             vec._ensure_model()
@@ -47,7 +50,7 @@ def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, w
     return q[0] if L == 1 else q
 
 
-def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind=None, gust=0.0, fruit=None):
+def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind=None, gust=0.0, fruit=None, doors=None):
     if int(num_learners) < 1:
         raise ValueError('num_learners must be at least 1')
     if not 0.0 <= float(epsilon) <= 1.0:
@@ -59,22 +62,28 @@ def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, s
             raise ValueError('wind and fruit exclude each other')
         if not isinstance(fruit, (tuple, list)) or len(fruit) != 3:
             raise ValueError('fruit must be (cells, kinds, values)')
+    if doors is not None:
+        if wind is not None or fruit is not None:
+            raise ValueError('doors exclude wind and fruit')
+        if not isinstance(doors, dict) or 'doors' not in doors or set(doors) - {'doors', 'keys', 'levers'}:
+            raise ValueError('doors must be dict(doors=, keys=, levers=)')
     return _learn(env, num_learners, seed, q0, num_steps, _CHUNK,
-                  lambda vec, T: vec.td_run(T, method, alpha, discount_factor, epsilon), wind=wind, gust=gust, fruit=fruit)
+                  lambda vec, T: vec.td_run(T, method, alpha, discount_factor, epsilon), wind=wind, gust=gust, fruit=fruit, doors=doors)
 
 
-def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None):
+def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None):
     """Epsilon-greedy Q-learning, `num_steps` env steps per learner (episodes restart at a start cell when they end).  Returns
     Q float64[S][4], or [L][S][4] for L = num_learners > 1.  `wind`: a strength array ([H, W], or [W] per column; blowing up) or a
     (strength, direction) pair as VecGridUniverse.set_wind takes them, gusting with probability `gust`; None: the calm grid.  `fruit`: (cells, kinds, values)
     as VecGridUniverse.set_fruit takes them -- the result then has S << F rows, row eaten * S + s for cell s with the mask `eaten` of
-    eaten fruit; not together with `wind`."""
-    return _td('q_learning', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit)
+    eaten fruit; not together with `wind`.  `doors`: dict(doors=, keys=, levers=) as VecGridUniverse.set_doors takes them -- the result
+    then has S << D rows, row open * S + s for cell s under the mask `open` of open slots; not together with `wind` or `fruit`."""
+    return _td('q_learning', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit, doors)
 
 
-def sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None):
+def sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None):
     """Epsilon-greedy SARSA; arguments and result as `q_learning`."""
-    return _td('sarsa', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit)
+    return _td('sarsa', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit, doors)
 
 
 def _nstep(method, env, num_steps, n, alpha, discount_factor, epsilon, num_learners, seed, q0):

@@ -178,6 +178,7 @@ int gu_explore_run(gu_handle h, int64_t T, int32_t mode, double alpha, double ga
     GU_ENTER(h);
     GU_NO_WIND(h, "gu_explore_run");
     GU_NO_FRUIT(h, "gu_explore_run");
+    GU_NO_DOORS(h, "gu_explore_run");
     GU_NEED_GRID(h);
     GU_NEED_Q(h);
     GU_NEED_COUNTS(h);

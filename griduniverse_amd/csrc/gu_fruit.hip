@@ -270,6 +270,7 @@ int gu_set_fruit(gu_handle h, const uint8_t *fruit, const int32_t value[3])
     GU_NEED_GRID(h);
     GU_REQUIRE(h->n_grids == 1, GU_ERR_UNSUPPORTED, "fruit is a property of a single-grid engine (this one holds %d grids)", h->n_grids);
     GU_REQUIRE(!h->d_wind_cell, GU_ERR_UNSUPPORTED, "fruit and wind exclude each other: the engine has wind set (gu_set_wind; NULL calms it again)");
+    GU_REQUIRE(!h->n_doors, GU_ERR_UNSUPPORTED, "fruit and doors exclude each other: the engine has doors set (gu_set_doors; NULL takes them away again)");
     GU_REQUIRE(!h->trail_cap, GU_ERR_UNSUPPORTED, "fruit and the agent trail exclude each other: the trail is on (gu_trail_enable(h, 0) turns it off)");
     int32_t F = 0;
     std::vector<uint8_t> flags;

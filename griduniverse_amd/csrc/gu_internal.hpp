@@ -140,6 +140,10 @@ struct gu_engine {
     int32_t n_fruit = 0;             // ... F, the number of fruit cells (1 .. 32; 0: no fruit); gu_td_run's tables then have S << F rows
     uint32_t fruit_values = 0;       // ... the three kinds' values as int8 bytes 1 .. 3 (byte 0 zero), as the kernels take them
     int32_t fruit_value[3] = {0, 0, 0};
+    uint8_t *d_door_cell = nullptr;  // doors (gu_set_doors, gu_doors.hip; single-grid engines): [3 * cell_bytes] the planes of d_cell with the
+                                     // door plane behind them; nullptr: no doors
+    uint32_t *d_open = nullptr;      // ... [N] the envs' masks of open slots (bit = slot), cleared by every reset
+    int32_t n_doors = 0;             // ... D, the number of slots in use (1 .. 8; 0: no doors); gu_td_run's tables then have S << D rows
     uint8_t *d_kind = nullptr;       // [n_grids][cell_bytes] texture class of every cell as the reference's viewer picks it
                                      // (rendering.py:119-133: goal, else lava, else wall, else ground = 3, 2, 1, 0) -- the flags
                                      // cannot tell a goal+lava cell from a lava cell; nullptr for device-generated mazes (no
@@ -405,6 +409,10 @@ int gu_ensure_scratch(gu_engine *h, size_t bytes);
 #define GU_NO_FRUIT(h, fn) \
     GU_REQUIRE(!(h)->n_fruit, GU_ERR_UNSUPPORTED, "%s knows no fruit: the engine has fruit set (gu_set_fruit; NULL takes it away again)", fn)
 
+// ... and without a form that stops at closed doors while doors are set (include/gu.h: gu_set_doors)
+#define GU_NO_DOORS(h, fn) \
+    GU_REQUIRE(!(h)->n_doors, GU_ERR_UNSUPPORTED, "%s knows no doors: the engine has doors set (gu_set_doors; NULL takes them away again)", fn)
+
 // frees device buffers and forgets them (hipFree's status is not looked at)
 template <class... P>
 static inline void gu_release(P *&...p)
@@ -537,6 +545,13 @@ int gu_fruit_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done); 
 void gu_fruit_free(gu_engine *h);
 // gu_td.hip: the fruit count becomes F (0: none) -- Q tables whose row count is not S << F go, with what hangs on them
 void gu_td_rows_changed(gu_engine *h, int32_t F);
+
+// ---- doors (gu_doors.hip): the same hand-overs while doors are set (gu_td_rows_changed then takes D, the slots in use) ----
+int gu_doors_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward, int32_t *host_done,
+                         uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
+void gu_doors_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);  // (the launch alone, as gu_wind_launch_rollout)
+int gu_doors_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done);  // clears the masks of the envs a reset is about to take; no-op without doors
+void gu_doors_free(gu_engine *h);
 
 // ---- agent trail (gu_trail.hip): no-ops while the trail is off ----------------------
 int gu_trail_after_step(gu_engine *h, uint32_t flags);

@@ -303,6 +303,7 @@ int gu_launch_reset(gu_engine *h, const uint8_t *d_mask, const int32_t *d_choice
     int trail_rc = gu_trail_before_reset(h, d_mask, only_done);  // (reads the done flags the reset is about to clear)
     if (trail_rc != GU_OK) return trail_rc;
     GU_TRY(gu_fruit_before_reset(h, d_mask, only_done));  // gu_fruit.hip (nothing without fruit)
+    GU_TRY(gu_doors_before_reset(h, d_mask, only_done));  // gu_doors.hip (nothing without doors)
     ResetArgs a{h->pos(), h->done(), h->d_episode, h->d_starts, d_mask, d_choice, h->d_done_bits,
                 (uint32_t)h->n_starts, h->seed_prefix, (uint32_t)h->env_id0, h->N, only_done ? 1 : 0, gu_grid_sel(h)};
     hipLaunchKernelGGL(gu_reset_kernel, dim3(gu_blocks(h->N, GU_BLOCK)), dim3(GU_BLOCK), 0, h->stream, a);
@@ -315,6 +316,7 @@ int gu_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, i
 {
     if (h->d_wind_cell) return gu_wind_launch_step(h, d_actions_row, flags, host_obs, host_reward, host_done, host_seq, seq, host_err);  // gu_wind.hip
     if (h->n_fruit) return gu_fruit_launch_step(h, d_actions_row, flags, host_obs, host_reward, host_done, host_seq, seq, host_err);  // gu_fruit.hip
+    if (h->n_doors) return gu_doors_launch_step(h, d_actions_row, flags, host_obs, host_reward, host_done, host_seq, seq, host_err);  // gu_doors.hip
     h->entry_table_ok = false;
     StepArgs a{h->d_cell, h->cell_bytes, h->W, h->delta_lut, d_actions_row, h->pos(), h->reward(), h->done(),
                h->d_episode, h->d_tcount, h->d_starts, (uint32_t)h->n_starts, h->seed_prefix, (uint32_t)h->env_id0, h->N, flags,
@@ -526,6 +528,7 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
 {
     GU_REQUIRE(!(h->d_wind_cell && (flags & GU_F_PACKED)), GU_ERR_UNSUPPORTED, "a rollout under wind (gu_set_wind) writes int32 rows only: GU_F_PACKED is refused");
     GU_REQUIRE(!(h->n_fruit && (flags & GU_F_PACKED)), GU_ERR_UNSUPPORTED, "a rollout under fruit (gu_set_fruit) writes int32 rows only: GU_F_PACKED is refused");
+    GU_REQUIRE(!(h->n_doors && (flags & GU_F_PACKED)), GU_ERR_UNSUPPORTED, "a rollout under doors (gu_set_doors) writes int32 rows only: GU_F_PACKED is refused");
     GU_REQUIRE(!h->trail_cap || (flags & (GU_F_TRAJECTORY | GU_F_PACKED)), GU_ERR_UNSUPPORTED,
                "the agent trail is on (gu_trail_enable): a rollout must write rows (GU_F_TRAJECTORY or GU_F_PACKED) to feed it");
     GU_REQUIRE(policy >= GU_POLICY_UNIFORM && policy <= GU_POLICY_SAMPLE, GU_ERR_INVALID, "unknown policy kind %d", policy);
@@ -574,6 +577,7 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
     switch (p.family) {
     case GU_PLAN_WIND: gu_wind_launch_rollout(h, p, a); break;
     case GU_PLAN_FRUIT: gu_fruit_launch_rollout(h, p, a); break;
+    case GU_PLAN_DOORS: gu_doors_launch_rollout(h, p, a); break;
     case GU_PLAN_KSTEP: gu_kstep_launch(h, p, a); break;
     case GU_PLAN_ROWS:
         if (!gu_rows_launch(h, p, a)) return gu_fail(GU_ERR_HIP, "gu_rollout_rows_kernel reports static LDS: its table must start at LDS address 0");
@@ -591,7 +595,7 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
     gu_rollout_plan_form(p, h->rollout_form);
     h->steps_taken += (uint64_t)T;
     gu_tabular_drop_carry(h);
-    h->entry_table_ok = p.family != GU_PLAN_WIND && p.family != GU_PLAN_FRUIT;
+    h->entry_table_ok = p.family != GU_PLAN_WIND && p.family != GU_PLAN_FRUIT && p.family != GU_PLAN_DOORS;
     return gu_trail_after_rollout(h, T, p.traj, p.auto_mode != 0);
 }
 

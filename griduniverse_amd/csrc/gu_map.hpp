@@ -128,3 +128,22 @@ __device__ __forceinline__ int32_t gu_fruit_eat(uint32_t c, uint32_t values, uin
     eaten |= bit;
     return gain;
 }
+
+// ------------------------------------------------------------------------------------
+// doors (include/gu.h: gu_set_doors): one byte per cell behind the two cell planes, bits 0..2 the slot, bits 4..5 the kind (0: nothing,
+// 1: door, 2: key, 3: lever)
+// ------------------------------------------------------------------------------------
+// Does the door byte c of the candidate cell refuse entry under the mask `open`?  (kind 1 and the slot's bit clear)
+__device__ __forceinline__ bool gu_door_closed(uint32_t c, uint32_t open)
+{
+    return ((c >> 4) & 3u) == 1u && !((open >> (c & 7u)) & 1u);
+}
+
+// The mask behind a step that ENTERED the cell of door byte c (`entered`: s' != s): a key sets its slot's bit, a lever flips it;
+// standing still touches nothing.  Nothing branches: the bit is zero for the other kinds, and a key's or-in is a flip of a clear bit.
+__device__ __forceinline__ uint32_t gu_door_touch(uint32_t c, uint32_t open, bool entered)
+{
+    const uint32_t kind = (c >> 4) & 3u;
+    const uint32_t bit = ((entered && kind >= 2u) ? 1u : 0u) << (c & 7u);
+    return kind == 3u ? open ^ bit : open | bit;
+}

@@ -9,7 +9,7 @@
 #include <algorithm>
 #include <type_traits>
 
-enum { GU_PLAN_GENERAL = 1, GU_PLAN_ROWS = 2, GU_PLAN_KSTEP = 3, GU_PLAN_WIND = 4, GU_PLAN_FRUIT = 5 };  // kernel families (gu_diag_rollout_form, word 1)
+enum { GU_PLAN_GENERAL = 1, GU_PLAN_ROWS = 2, GU_PLAN_KSTEP = 3, GU_PLAN_WIND = 4, GU_PLAN_FRUIT = 5, GU_PLAN_DOORS = 6 };  // kernel families (gu_diag_rollout_form, word 1)
 // `exclude`: families (1u << family) and forms that the executor found it cannot run -- a table that could not be allocated, dynamic LDS
 // that does not start at address 0 -- and plans again without
 #define GU_PLAN_NO_PAIRS (1u << 8)  /* the transition-row kernel's pair tables */
@@ -314,7 +314,7 @@ inline GuRolloutPlan gu_rollout_plan(const gu_engine *h, int64_t T, int32_t poli
     // below 2^32 bytes) and engines with the agent trail on or wind set always keep the planes.
     // (AS IT STANDS the default does not ask the auto mode: with several start cells the triples go to the general kernel.  DESIGN.md 4.0)
     p.traj = (flags & GU_F_PACKED) ? 2 : ((flags & GU_F_TRAJECTORY) ? 1 : 0);
-    if (p.traj == 1 && h->N <= ((int64_t)1 << 24) && !h->trail_cap && !h->d_wind_cell && !h->n_fruit) {
+    if (p.traj == 1 && h->N <= ((int64_t)1 << 24) && !h->trail_cap && !h->d_wind_cell && !h->n_fruit && !h->n_doors) {
         const int64_t layout = gu_opt(h, GU_OPT_TRAJ_LAYOUT);
         if (layout == 1 || (layout == -1 && policy == GU_POLICY_UNIFORM && gu_rows_pairs_fit(h) && (int64_t)gu_blocks(h->N, 256) * 4 <= h->n_cu)) p.traj = 3;
     }
@@ -332,6 +332,9 @@ inline GuRolloutPlan gu_rollout_plan(const gu_engine *h, int64_t T, int32_t poli
     } else if (h->n_fruit) {  // the fruit kernel (gu_fruit.hip), likewise: [flags | reward | fruit] in LDS where they fit, int32 planes only
         p.family = GU_PLAN_FRUIT, p.block = GU_BLOCK, p.blocks = gu_blocks(h->N, GU_BLOCK), p.lds = gu_lds_block(h, GU_BLOCK, 3) ? 3 * (size_t)h->cell_bytes : 0;
         p.straddle = p.entry_table = false;  // (64-bit step count in the kernel, as the windy one)
+    } else if (h->n_doors) {  // the door kernel (gu_doors.hip), likewise: [flags | reward | door] in LDS where they fit, int32 planes only
+        p.family = GU_PLAN_DOORS, p.block = GU_BLOCK, p.blocks = gu_blocks(h->N, GU_BLOCK), p.lds = gu_lds_block(h, GU_BLOCK, 3) ? 3 * (size_t)h->cell_bytes : 0;
+        p.straddle = p.entry_table = false;
     } else if (!straddle && !(exclude & (1u << GU_PLAN_KSTEP)) && gu_plan_kstep(h, T, xcd, &p)) {}
     else if (!straddle && !(exclude & (1u << GU_PLAN_ROWS)) && gu_plan_rows(h, exclude, xcd, &p)) {}
     else gu_plan_general(h, T, exclude, xcd, &p);

@@ -320,6 +320,7 @@ int gu_sweep_run(gu_handle h, int64_t T, int32_t P, double theta, double alpha, 
     GU_ENTER(h);
     GU_NO_WIND(h, "gu_sweep_run");
     GU_NO_FRUIT(h, "gu_sweep_run");
+    GU_NO_DOORS(h, "gu_sweep_run");
     GU_NEED_GRID(h);
     GU_NEED_Q(h);
     GU_NEED_SWEEP(h);

@@ -117,13 +117,21 @@ __device__ __forceinline__ uint64_t gu_dyna_pack(int32_t s2, int32_t r, int32_t 
 // rows: the lane stands on row eaten * S + s.  move() leaves the mask behind the step in `eaten2`, step() makes it current.  A wall
 // bump onto an uneaten fruit keeps the cell and changes the row, so next_row() and update() compare ROWS, not cells.  The
 // instantiations without fruit hold none of it (row() is s there).
-template <bool LDS, bool ROWS = true, int WIND = 0, bool FRUIT = false>
+// DOORS (include/gu.h: gu_set_doors; never with WIND or FRUIT): a.cell carries the door plane behind the two cell planes
+// (gu_engine::d_door_cell) and the table has S << D rows.  The env's mask of open slots lives where fruit keeps its mask of eaten
+// fruit -- `eaten` is the mask the lane stands under, `eaten2` the one behind move() --, so the rows and their comparisons are
+// fruit's: the kernel sets `rows` and `eaten` before begin() and stores `eaten` behind end().  move() turns the candidate cell back
+// at a closed door and lets a key or lever of the cell ENTERED change `eaten2`; it reads the candidate's three bytes together and
+// picks behind the gate (the head of gu_doors.hip), so the gate adds no dependent read to a step.
+template <bool LDS, bool ROWS = true, int WIND = 0, bool FRUIT = false, bool DOORS = false>
 struct TabLane {
+    static constexpr bool MASKED = FRUIT || DOORS;  // the table has a row per (cell, mask)
     CellMap m;
-    const uint8_t *wd;  // WIND: the wind plane; FRUIT: the fruit plane
+    const uint8_t *wd;  // WIND: the wind plane; FRUIT: the fruit plane; DOORS: the door plane
     uint32_t gust_q16;  // WIND == 2
-    uint32_t fvalues, eaten, eaten2;  // FRUIT
-    int32_t S, rows;                  // FRUIT: states, and rows of one learner's table (S << F)
+    uint32_t fvalues;   // FRUIT
+    uint32_t eaten, eaten2;  // MASKED: the env's mask (eaten fruit / open slots), and the one behind move()
+    int32_t S, rows;         // MASKED: states, and rows of one learner's table (S << F, S << D)
     LaneGrid lg;
     int64_t e;
     uint32_t env, start_prefix, prefix, ep;
@@ -134,9 +142,9 @@ struct TabLane {
 
     __device__ __forceinline__ TabLane(const TabArgs &a, uint8_t *smem)
     {
-        m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, (WIND || FRUIT) ? 3 : 2);
-        if (WIND || FRUIT) wd = m.f + 2 * a.cell_bytes;
-        if (FRUIT) S = a.S;
+        m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, (WIND || MASKED) ? 3 : 2);
+        if (WIND || MASKED) wd = m.f + 2 * a.cell_bytes;
+        if (MASKED) S = a.S;
         e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         d = 0;
     }
@@ -149,8 +157,8 @@ struct TabLane {
         t = a.steps_taken + (uint64_t)(int64_t)(int32_t)a.tcount[e];
         // stream 4: the epoch t >> 32 hashed behind the seed, hoisted; recomputed in the step that crosses a multiple of 2^32
         prefix = gu_rng_prefix(gu_rng_seed_prefix_epoch(a.seed_prefix, (uint32_t)(t >> 32)), env);
-        qe = ROWS ? a.q + (FRUIT ? e * rows : e * a.S) * 4 : nullptr;
-        if (FRUIT) eaten2 = eaten;
+        qe = ROWS ? a.q + (MASKED ? e * rows : e * a.S) * 4 : nullptr;
+        if (MASKED) eaten2 = eaten;
         s = a.pos[e];
         r = a.reward[e];
         d = a.done[e];
@@ -168,14 +176,14 @@ struct TabLane {
             s = lg.starts[gu_rng_start_index(start_prefix, ep, lg.n_starts)];
             ++ep;
             d = 0;
-            if (FRUIT) eaten = eaten2 = 0u;  // the fruit grows back
+            if (MASKED) eaten = eaten2 = 0u;  // the fruit grows back; the doors are shut again
             if (ROWS) q = gu_q_load(qe + row() * 4);
         }
     }
 
     // the table row the lane stands on, and the one it stands on behind move()
-    __device__ __forceinline__ int64_t row() const { return FRUIT ? (int64_t)eaten * S + s : (int64_t)s; }
-    __device__ __forceinline__ int64_t row2(int32_t s2) const { return FRUIT ? (int64_t)eaten2 * S + s2 : (int64_t)s2; }
+    __device__ __forceinline__ int64_t row() const { return MASKED ? (int64_t)eaten * S + s : (int64_t)s; }
+    __device__ __forceinline__ int64_t row2(int32_t s2) const { return MASKED ? (int64_t)eaten2 * S + s2 : (int64_t)s2; }
 
     // the stream-4 word of step t
     __device__ __forceinline__ uint32_t word() const { return gu_rng_word(prefix, GU_RNG_STREAM_TD, (uint32_t)t); }
@@ -190,9 +198,21 @@ struct TabLane {
             if (WIND == 2 && __builtin_amdgcn_ballot_w64(k > 0u) != 0ull) k = gu_wind_gust(k, gu_rng_word(prefix, GU_RNG_STREAM_WIND, (uint32_t)t), gust_q16);
             s2 = gu_wind_push<LDS>(m.f, s2, c, k, a.lut, a.W);
         }
-        r = m.r[s2];
-        if (FRUIT) r += gu_fruit_eat(wd[s2], fvalues, eaten2);  // (read beside the flags and the reward byte of s': the chain does not grow)
-        d = (m.f[s2] >> GU_CELL_TERM_BIT) & 1;
+        if (DOORS) {
+            // A closed door refuses entry as a wall does; the key or lever of a cell entered changes the mask behind the step.  The door
+            // byte of the candidate is read BESIDE its flags and reward byte, and the gate picks between them and the bytes of s (its
+            // reward byte is read beside its flags): two rounds of reads on the chain, as without doors.
+            const uint32_t c = wd[s2];
+            const bool shut = gu_door_closed(c, eaten);
+            eaten2 = gu_door_touch(c, eaten, !shut && s2 != s);
+            r = shut ? m.r[s] : m.r[s2];
+            d = ((shut ? m.f[s] : m.f[s2]) >> GU_CELL_TERM_BIT) & 1;
+            s2 = shut ? s : s2;
+        } else {
+            r = m.r[s2];
+            if (FRUIT) r += gu_fruit_eat(wd[s2], fvalues, eaten2);  // (read beside the flags and the reward byte of s': the chain does not grow)
+            d = (m.f[s2] >> GU_CELL_TERM_BIT) & 1;
+        }
         ++t;
         if ((uint32_t)t == 0u) prefix = gu_rng_prefix(gu_rng_seed_prefix_epoch(a.seed_prefix, (uint32_t)(t >> 32)), env);
         return s2;
@@ -202,7 +222,7 @@ struct TabLane {
     __device__ __forceinline__ QRow next_row(int32_t s2) const
     {
         QRow n = q;
-        if (ROWS && !d && (FRUIT ? row2(s2) != row() : s2 != s)) n = gu_q_load(qe + row2(s2) * 4);
+        if (ROWS && !d && (MASKED ? row2(s2) != row() : s2 != s)) n = gu_q_load(qe + row2(s2) * 4);
         return n;
     }
 
@@ -212,7 +232,7 @@ struct TabLane {
         double qa = gu_q_get(q, ua);
         qa = __dadd_rn(qa, __dmul_rn(a.alpha, __dsub_rn(target, qa)));
         qe[sa] = qa;
-        if (FRUIT ? row2(s2) == row() : s2 == s) gu_q_put(n, ua, qa);
+        if (MASKED ? row2(s2) == row() : s2 == s) gu_q_put(n, ua, qa);
     }
 
     // the lane stands in s' with row n: the trajectory row and the statistics of step i
@@ -220,7 +240,7 @@ struct TabLane {
     {
         q = n;
         s = s2;
-        if (FRUIT) eaten = eaten2;
+        if (MASKED) eaten = eaten2;
         if (a.tr_obs) {
             const int64_t row = (int64_t)i * a.N + e;
             a.tr_obs[row] = s2;
@@ -259,7 +279,8 @@ struct TabLane {
 // the tables that more than one learner's entry points need, present and of this grid's size
 #define GU_NEED_Q(h) GU_REQUIRE((h)->d_q && (h)->td_S == (h)->S, GU_ERR_STATE, "no Q tables: call gu_td_init first")
 // ... gu_td_run and the table copies alone know fruit: S << F rows (include/gu.h: gu_set_fruit)
-#define GU_TD_ROWS(h) ((int64_t)(h)->S << (h)->n_fruit)  /* (64 bits: F runs to 32; gu_td_init keeps it below 2^31) */
+// ... and doors: S << D rows (include/gu.h: gu_set_doors); the two exclude each other, so one of the counts is zero
+#define GU_TD_ROWS(h) ((int64_t)(h)->S << ((h)->n_fruit + (h)->n_doors))  /* (64 bits: F runs to 32; gu_td_init keeps it below 2^31) */
 #define GU_NEED_TD_Q(h) GU_REQUIRE((h)->d_q && (int64_t)(h)->td_S == GU_TD_ROWS(h), GU_ERR_STATE, "no Q tables: call gu_td_init first")
 #define GU_NEED_AC(h) GU_REQUIRE((h)->d_ac_h && (h)->ac_S == (h)->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first")
 

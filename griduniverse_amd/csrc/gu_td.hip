@@ -13,19 +13,21 @@ struct TdArgs : TabArgs {
     // the fruit instantiations (gu_set_fruit; a.cell holds three planes): the kinds' values, the envs' masks, the rows of one table (S << F)
     uint32_t fruit_values;
     int32_t rows;
-    uint32_t *eaten;
+    uint32_t *eaten;  // (the door instantiations, gu_set_doors: the envs' masks of open slots, and rows = S << D)
 };
 
 // WIND: 0 = calm, 1 = wind without gusts (no stream-9 hash in the code), 2 = with gusts (gu_tabular.hpp: TabLane)
 // FRUIT: the table has S << F rows and the lane learns on row eaten * S + s (TabLane); never together with WIND
-template <bool SARSA, bool LDS, int WIND = 0, bool FRUIT = false>
+// DOORS: the table has S << D rows and the lane learns on row open * S + s; never together with WIND or FRUIT
+template <bool SARSA, bool LDS, int WIND = 0, bool FRUIT = false, bool DOORS = false>
 __global__ void __launch_bounds__(GU_BLOCK) gu_td_kernel(const TdArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    TabLane<LDS, true, WIND, FRUIT> L(a, smem);
+    TabLane<LDS, true, WIND, FRUIT, DOORS> L(a, smem);
     if (WIND == 2) L.gust_q16 = a.gust_q16;
     if (L.e < a.N) {
-        if (FRUIT) L.fvalues = a.fruit_values, L.rows = a.rows, L.eaten = a.eaten[L.e];
+        if (FRUIT) L.fvalues = a.fruit_values;
+        if (FRUIT || DOORS) L.rows = a.rows, L.eaten = a.eaten[L.e];
         L.begin(a);
         int32_t act = (SARSA && a.carry) ? (int32_t)a.next_a[L.e] : -1;
         for (int32_t i = 0; i < a.T; ++i) {
@@ -51,7 +53,7 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_td_kernel(const TdArgs a)
             L.step(a, i, s2, n);
         }
         L.end(a);
-        if (FRUIT) a.eaten[L.e] = L.eaten;
+        if (FRUIT || DOORS) a.eaten[L.e] = L.eaten;
         if (SARSA) a.next_a[L.e] = (int8_t)act;
     }
     L.ballot(a);
@@ -80,7 +82,11 @@ static int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, d
     a.gust_q16 = h->gust_q16;
     a.fruit_values = h->fruit_values, a.rows = h->td_S, a.eaten = h->d_eaten;
     int rc;
-    if (h->n_fruit) {  // the fruit instantiations, on the three planes and S << F rows
+    if (h->n_doors) {  // the door instantiations, on [flags | reward | door] and S << D rows
+        a.cell = h->d_door_cell, a.eaten = h->d_open;
+        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 0, false, true>, gu_td_kernel<true, false, 0, false, true>, a, GU_BLOCK, 0, 3)
+                         : gu_tabular_launch(h, gu_td_kernel<false, true, 0, false, true>, gu_td_kernel<false, false, 0, false, true>, a, GU_BLOCK, 0, 3);
+    } else if (h->n_fruit) {  // the fruit instantiations, on the three planes and S << F rows
         a.cell = h->d_fruit_cell;
         rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 0, true>, gu_td_kernel<true, false, 0, true>, a, GU_BLOCK, 0, 3)
                          : gu_tabular_launch(h, gu_td_kernel<false, true, 0, true>, gu_td_kernel<false, false, 0, true>, a, GU_BLOCK, 0, 3);
@@ -146,7 +152,7 @@ int gu_td_init(gu_handle h, double q0)
     gu_tabular_drop_carry(h);
     // under fruit a table has a row per (cell, mask): S << F of them (gu_set_fruit), which ten fruits multiply by 1024
     GU_REQUIRE(h->n_fruit <= 10, GU_ERR_INVALID, "%d fruits: gu_td_init learns on S << F rows and takes at most 10 fruits", h->n_fruit);
-    GU_REQUIRE(((int64_t)h->S << h->n_fruit) <= 0x7FFFFFFF, GU_ERR_INVALID, "%d states x 2^%d masks: more than 2^31 - 1 rows", h->S, h->n_fruit);
+    GU_REQUIRE(GU_TD_ROWS(h) <= 0x7FFFFFFF, GU_ERR_INVALID, "%d states x 2^%d masks: more than 2^31 - 1 rows", h->S, h->n_fruit + h->n_doors);
     const int32_t rows = (int32_t)GU_TD_ROWS(h);
     const size_t bytes = (size_t)h->N * (size_t)rows * 4 * sizeof(double);
     if (!h->d_q || h->td_S != rows) {

@@ -280,6 +280,7 @@ int gu_set_wind(gu_handle h, const uint8_t *wind, uint32_t gust_q16)
     GU_REQUIRE(h->n_grids == 1, GU_ERR_UNSUPPORTED, "wind is a property of a single-grid engine (this one holds %d grids)", h->n_grids);
     GU_REQUIRE(!h->trail_cap, GU_ERR_UNSUPPORTED, "wind and the agent trail exclude each other: the trail is on (gu_trail_enable(h, 0) turns it off)");
     GU_REQUIRE(!h->n_fruit, GU_ERR_UNSUPPORTED, "wind and fruit exclude each other: the engine has fruit set (gu_set_fruit; NULL takes it away again)");
+    GU_REQUIRE(!h->n_doors, GU_ERR_UNSUPPORTED, "wind and doors exclude each other: the engine has doors set (gu_set_doors; NULL takes them away again)");
     GU_REQUIRE(gust_q16 <= 65536u, GU_ERR_INVALID, "gust_q16 %u above 65536", gust_q16);
     if (wind)
         for (int32_t s = 0; s < h->S; ++s)

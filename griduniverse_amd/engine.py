@@ -99,6 +99,7 @@ class Engine(object):
         self.spec = spec
         self._n_grids = 1
         self._n_fruit = 0  # (a new grid drops the fruit)
+        self._n_doors = 0  # (... and the doors)
 
     def set_grids(self, specs):
         """Several distinct grids of one shape: env e uses specs[e // (N // len(specs))]."""
@@ -121,6 +122,7 @@ class Engine(object):
         self.specs = list(specs)
         self._n_grids = len(specs)
         self._n_fruit = 0
+        self._n_doors = 0
 
     def generate_mazes(self, n_grids, W, H, maze_seed):
         """n_grids random mazes carved on the device (one per env group of N // n_grids envs)."""
@@ -129,6 +131,7 @@ class Engine(object):
         self.specs = None
         self._n_grids = int(n_grids)
         self._n_fruit = 0
+        self._n_doors = 0
 
     def get_cells(self, grid_index=0):
         """(flags uint8[S], reward int8[S], starts int32[n]) of one grid as compiled on the device."""
@@ -180,10 +183,37 @@ class Engine(object):
         e = _lib.as_array(eaten, np.uint32, None, 'eaten')
         check(self.lib.gu_set_fruit_state(self._h, int(env0), e.size, ptr(e)))
 
+    def set_doors(self, door):
+        """Install the door plane uint8[S] (grid.door_plane); None takes the doors away again (gu_set_doors).  Clears every env's
+        mask of open slots."""
+        d = None if door is None else _lib.as_array(door, np.uint8, (self.spec.S,), 'door')
+        check(self.lib.gu_set_doors(self._h, ptr(d)))
+        self._n_doors = 0 if d is None else int(np.unique(d[d != 0] & 7).size)
+
+    def get_doors(self):
+        """door uint8[S], or None while no doors are set (gu_get_doors)."""
+        door = np.empty(self.spec.S, np.uint8)
+        n = ctypes.c_int32(0)
+        check(self.lib.gu_get_doors(self._h, ptr(door), ctypes.byref(n)))
+        return door if n.value else None
+
+    def get_doors_state(self, env0=0, n=None):
+        """uint32[n]: the masks of open slots (bit = slot) of envs env0 .. env0+n-1 (gu_get_doors_state)."""
+        env0, n, n0 = self._env_range(env0, n)
+        mask = np.empty(n0, np.uint32)
+        check(self.lib.gu_get_doors_state(self._h, env0, n, ptr(mask)))
+        return mask
+
+    def set_doors_state(self, mask, env0=0):
+        """Install the masks uint32[n] of envs env0 .. env0+n-1 (gu_set_doors_state)."""
+        m = _lib.as_array(mask, np.uint32, None, 'mask')
+        check(self.lib.gu_set_doors_state(self._h, int(env0), m.size, ptr(m)))
+
     @property
     def td_rows(self):
-        """Rows of one env's Q table: S, or S << F while F fruits are set (include/gu.h: gu_set_fruit)."""
-        return self.spec.S << self._n_fruit
+        """Rows of one env's Q table: S, or S << F while F fruits are set (include/gu.h: gu_set_fruit), or S << D while doors with
+        D slots are set (gu_set_doors)."""
+        return self.spec.S << (self._n_fruit + self._n_doors)
 
     def seed(self, seed):
         self.seed_value = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -286,12 +316,12 @@ class Engine(object):
         check(self.lib.gu_rollout(self._h, int(T), _POLICIES[policy], flags))
 
     ROLLOUT_FORM = ('family', 'layout', 'map', 'block', 'workgroups', 'lds_bytes', 'flags', 'K', 'row_shift', 'stream_words', 'pace_slot', 'pace_mode')
-    ROLLOUT_FAMILIES = {0: None, 1: 'general', 2: 'rows', 3: 'kstep', 4: 'wind', 5: 'fruit'}
+    ROLLOUT_FAMILIES = {0: None, 1: 'general', 2: 'rows', 3: 'kstep', 4: 'wind', 5: 'fruit', 6: 'doors'}
     ROLLOUT_FLAG_BITS = ('pair', 'half', 'per_wave', 'pi_lds', 'straddle', 'entry_table', 'xcd_remap')
 
     def rollout_last_form(self):
         """What the last rollout of this engine ran on (gu_diag_rollout_form): dict with the twelve form words under the names of
-        ROLLOUT_FORM ('family' as a name: 'general', 'rows', 'kstep', 'wind', 'fruit'; None before the first rollout), each flag bit as a
+        ROLLOUT_FORM ('family' as a name: 'general', 'rows', 'kstep', 'wind', 'fruit', 'doors'; None before the first rollout), each flag bit as a
         bool under its name in ROLLOUT_FLAG_BITS, and the raw words as 'words'."""
         words = np.zeros(len(self.ROLLOUT_FORM), np.int32)
         n = ctypes.c_int32(0)
@@ -405,7 +435,7 @@ class Engine(object):
                                  _learner_flags(trajectory, stats)))
 
     def td_get_q(self, env0=0, n=None):
-        """float64[n, S, 4]: the tables of envs env0 .. env0+n-1 (all from env0 when n is None); S << F rows under fruit."""
+        """float64[n, S, 4]: the tables of envs env0 .. env0+n-1 (all from env0 when n is None); S << F rows under fruit, S << D under doors."""
         env0, n, n0 = self._env_range(env0, n)
         q = np.empty((n0, self.td_rows, 4), np.float64)
         check(self.lib.gu_td_get_q(self._h, env0, n, ptr(q)))

@@ -162,6 +162,8 @@ def wind_plane(W, H, strength, direction='up'):
 # ---- fruit: the per-cell plane of include/gu.h, gu_set_fruit -------------------------------------------------------
 FRUIT_KINDS = {'apple': 1, 'lemon': 2, 'melon': 3}  # the kind codes (0: no fruit)
 FRUIT_MAX = 32  # fruits per grid: one bit each in an env's uint32 mask
+DOOR_KINDS = {'door': 1, 'key': 2, 'lever': 3}  # the kind codes of include/gu.h, gu_set_doors (0: nothing)
+DOOR_SLOTS_MAX = 8  # slots per grid: one bit each in an env's mask of open slots
 
 
 def fruit_plane(W, H, cells, kinds='apple'):
@@ -196,4 +198,51 @@ def fruit_plane(W, H, cells, kinds='apple'):
     order = np.argsort(c, kind='stable')
     for slot, i in enumerate(order):
         plane[int(c[i])] = slot | (codes[i] << 5)
+    return plane
+
+
+# ---- doors, keys and levers: the per-cell plane of include/gu.h, gu_set_doors ---------------------------------------
+def _slot_cells(what, mapping, S):
+    """{slot: sorted list of cells} of one argument of door_plane: a mapping slot -> cell or list of cells (None: empty)."""
+    out = {}
+    if mapping is None:
+        return out
+    if not hasattr(mapping, 'items'):
+        raise ValueError('{} must be a mapping slot -> cell or list of cells'.format(what))
+    for slot, cells in mapping.items():
+        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < DOOR_SLOTS_MAX:
+            raise ValueError('{}: a slot is an integer in 0 .. {}, got {!r}'.format(what, DOOR_SLOTS_MAX - 1, slot))
+        c = np.atleast_1d(np.asarray(cells))
+        if c.ndim != 1 or c.size == 0 or c.dtype == bool or not np.issubdtype(c.dtype, np.integer):
+            raise ValueError('{}: slot {} needs a cell index or a list of them'.format(what, slot))
+        if c.min() < 0 or c.max() >= S:
+            raise ValueError('{}: the cells of slot {} must lie in 0 .. {}'.format(what, slot, S - 1))
+        out[int(slot)] = sorted(int(x) for x in c)
+    return out
+
+
+def door_plane(W, H, doors, keys=None, levers=None):
+    """uint8[S]: the door plane of a W x H grid as gu_set_doors takes it -- bits 0..2 of a cell its slot, bits 4..5 its kind (1 door,
+    2 key, 3 lever), every other cell 0.  `doors`, `keys`, `levers`: mappings slot -> cell or list of cells (None: empty).  The slots
+    in use must be 0 .. D-1 without a gap, each with at least one door and at least one key or lever; no cell is named twice."""
+    W, H = int(W), int(H)
+    S = W * H
+    parts = [(name, _slot_cells(name, m, S)) for name, m in (('doors', doors), ('keys', keys), ('levers', levers))]
+    used = sorted(set().union(*[set(p) for _, p in parts]))
+    if not used:
+        raise ValueError('no door, key or lever given')
+    if used != list(range(len(used))):
+        raise ValueError('the slots in use must be 0 .. D-1 without a gap, got {}'.format(used))
+    for slot in used:
+        if slot not in parts[0][1]:
+            raise ValueError('slot {} has no door'.format(slot))
+        if slot not in parts[1][1] and slot not in parts[2][1]:
+            raise ValueError('slot {} has neither a key nor a lever'.format(slot))
+    plane = np.zeros(S, np.uint8)
+    for name, p in parts:
+        for slot, cells in p.items():
+            for c in cells:
+                if plane[c]:
+                    raise ValueError('cell {} is named twice'.format(c))
+                plane[c] = slot | (DOOR_KINDS[name[:-1]] << 4)
     return plane

@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib, softmax
 from .engine import Engine
 from .envs.griduniverse_env import GridUniverseEnv
-from .grid import FRUIT_KINDS, GridSpec, fruit_plane, wind_plane
+from .grid import DOOR_KINDS, FRUIT_KINDS, GridSpec, door_plane, fruit_plane, wind_plane
 
 
 def check_off_policy_args(max_episode_len, epsilon, w_cap):
@@ -34,6 +34,7 @@ def check_off_policy_args(max_episode_len, epsilon, w_cap):
 
 class VecGridUniverse(object):
     _n_fruit = 0  # fruits set (set_fruit): the Q tables have S << F rows
+    _n_doors = 0  # door slots set (set_doors): the Q tables have S << D rows
     _td_ready = False  # the engine holds Q tables (td_run / set_q_table allocate them on first use)
     _dyna_ready = False  # ... and Dyna-Q models (dyna_run / model allocate them on first use)
     _sweep_ready = False  # ... and priority queues (sweep_run / priority_queue allocate them, with the models, on first use)
@@ -199,6 +200,54 @@ class VecGridUniverse(object):
             raise ValueError('eaten must hold masks of the {} fruits set'.format(self._n_fruit))
         self.engine.set_fruit_state(e.astype(np.uint32), env0)
 
+    def set_doors(self, doors, keys=None, levers=None):
+        """Doors, keys and levers on the engine's grid (single-grid engines; include/gu.h: gu_set_doors): a door of slot k refuses
+        entry as a wall does while bit k of the env's mask is clear; entering a key cell of slot k sets the bit, entering a lever
+        cell flips it; every reset shuts the doors again.  `doors`, `keys`, `levers` as grid.door_plane takes them (mappings slot ->
+        cell or cells, slots 0 .. D-1 with D <= 8, none on a wall, goal or lava cell).  set_doors(None) takes them away.  step,
+        rollout and td_run follow the doors (td_run learns on S << D rows, one per cell and mask); the other learners, the DP and
+        look-ahead calls, the path search, the trail, wind and fruit are refused while they are set.  sense and render show door,
+        key and lever cells as free cells."""
+        if doors is None:
+            if keys is not None or levers is not None:
+                raise ValueError('set_doors(None) takes the doors away: keys and levers must be None too')
+            self.engine.set_doors(None)
+            D = 0
+        else:
+            plane = door_plane(self.spec.W, self.spec.H, doors, keys, levers)
+            blocked = (self.spec.wall | self.spec.goal | self.spec.lava) & (plane != 0)
+            if blocked.any():
+                raise ValueError('a door, key or lever on cell {}, which is a wall or a goal or lava cell'.format(int(np.flatnonzero(blocked)[0])))
+            self.engine.set_doors(plane)
+            D = int(np.unique(plane[plane != 0] & 7).size)
+        if D != self._n_doors:  # (the library dropped tables of another row count, and the tree search's node pools with them)
+            self._td_ready = False
+            self._tree_sims = 0
+        self._n_doors = D
+
+    def doors(self):
+        """None while no doors are set, else dict(doors=, keys=, levers=): mappings slot -> int64 array of ascending cells."""
+        plane = self.engine.get_doors()
+        if plane is None:
+            return None
+        out = {}
+        for name, code in DOOR_KINDS.items():
+            cells = np.flatnonzero((plane >> 4) == code)
+            out[name + 's'] = {int(k): cells[(plane[cells] & 7) == k] for k in np.unique(plane[cells] & 7)}
+        return out
+
+    def doors_open(self, env0=0, n=None):
+        """uint32[n]: the masks of open slots of envs env0 .. env0+n-1 (to the end when n is None); bit k: the doors of slot k are
+        open for the env in its current episode."""
+        return self.engine.get_doors_state(env0, n)
+
+    def set_doors_open(self, mask, env0=0):
+        """Install masks uint32[n] (or one number) for envs env0 ..; no bit at or above the number of slots in use."""
+        m = np.atleast_1d(np.asarray(mask))
+        if m.ndim != 1 or m.dtype == bool or not np.issubdtype(m.dtype, np.integer) or (m.size and (m.min() < 0 or m.max() >> max(self._n_doors, 1) != 0)):
+            raise ValueError('mask must hold masks of the {} door slots set'.format(self._n_doors))
+        self.engine.set_doors_state(m.astype(np.uint32), env0)
+
     def _ensure_q(self, q0=None):
         """Q tables on the engine: tables of zeros on first use; every entry q0 (again) when q0 is given."""
         if q0 is not None or not self._td_ready:
@@ -231,12 +280,13 @@ class VecGridUniverse(object):
 
     def q_table(self, env0=0, n=None):
         """float64[n, S, 4]: the Q tables of envs env0 .. env0+n-1 (to the end when n is None).  While F fruits are set
-        (set_fruit) the tables have S << F rows: row eaten * S + s belongs to cell s with the mask `eaten`."""
+        (set_fruit) the tables have S << F rows: row eaten * S + s belongs to cell s with the mask `eaten`.  While doors with D slots
+        are set (set_doors) they have S << D rows: row open * S + s belongs to cell s under the mask `open`."""
         return self.engine.td_get_q(env0, n)
 
     def set_q_table(self, q, env0=0):
         """Install Q tables float64[n, S, 4] (or [S, 4]) for envs env0 ..; the other envs get tables of zeros if they had none.
-        S << F rows while F fruits are set, as q_table()."""
+        S << F rows while F fruits are set and S << D rows while doors with D slots are set, as q_table()."""
         self._ensure_q()
         self.engine.td_set_q(q, env0)
 

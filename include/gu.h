@@ -256,6 +256,55 @@ int gu_get_fruit(gu_handle h, uint8_t *fruit /* zeros when none */, int32_t valu
 int gu_get_fruit_state(gu_handle h, int64_t env0, int64_t n, uint32_t *eaten);
 int gu_set_fruit_state(gu_handle h, int64_t env0, int64_t n, const uint32_t *eaten);  /* a bit at or above F: GU_ERR_INVALID */
 
+/* ---- doors, keys and levers: walls that an env opens for itself ----------------------------------------------
+ * Build-defined (the reference has no doors; restated on the CPU by tests/_doors_oracle.py).  Doors are a property of a SINGLE-GRID
+ * engine.  They consist of one byte per cell, door[s] -- bits 0..2 the slot (0 .. 7), bits 4..5 the kind (0 = nothing, 1 = door,
+ * 2 = key, 3 = lever), bits 3, 6 and 7 zero, and kind 0 requires the whole byte to be 0 --, and one uint32 open[e] per env: bit k set
+ * means the doors of slot k are open for env e.  D is the number of slots in use, 1 .. 8; the slots in use are exactly 0 .. D-1, and
+ * every one of them has at least one door cell and at least one key or lever cell.  Several cells may share a slot (one key can open
+ * two doors).  None of the three kinds may lie on a wall or on a goal or lava cell; they may lie on start cells.
+ * One step of env e from cell s with a valid action a:
+ *   1. the lazy auto-reset, where the call has one, sets open[e] = 0 together with the position: doors are shut again, keys are back;
+ *   2. c is the candidate cell, from the engine's move rule exactly as without doors (door, key and lever cells are free cells for it);
+ *   3. if door[c] is a door of slot k and bit k of open[e] is clear, the move is refused as a wall refuses it: s' = s; else s' = c.
+ *      A closed door refuses ENTRY only: an agent standing on a door cell (at a start, or after gu_set_state) leaves it like any cell;
+ *   4. r and d are the engine's for s': a bump on a closed door pays what a wall bump from s pays;
+ *   5. if s' != s and door[s'] is a key of slot k, then open[e] |= 1 << k; if it is a lever of slot k, then open[e] ^= 1 << k.
+ *      Standing still on a lever (wall bump, door bump) does not pull it again, and a reset onto a key or lever cell does not touch
+ *      the mask;
+ *   6. t += 1.
+ * A rejected action (outside -4 .. 3) moves nothing and changes no mask.  No RNG stream is added and none is drawn differently.
+ * Every path that resets an env clears its mask: gu_reset (masked envs only), gu_reset_done, and the lazy resets inside the kernels.
+ * gu_set_doors clears the masks of all envs; gu_set_state and gu_seed leave them alone.
+ * While doors are set, gu_step (pinned I/O and the completion word included), gu_step_device, gu_rollout (all four policies,
+ * GU_F_TRAJECTORY / GU_F_STATS; GU_F_PACKED returns GU_ERR_UNSUPPORTED; rows are the three [T][N] planes, never triples) and gu_td_run
+ * (both methods) run their door kernels (csrc/gu_doors.hip, csrc/gu_td.hip); every other call that moves envs or reads the move
+ * rule -- gu_step_graph, the other learners' gu_*_run, gu_look_step_ahead, gu_vi_sweep / _run / _eval_run / _greedy / _sweep_step /
+ * _sweep_step_run, gu_mc_walk_lengths / _episodes, gu_shortest_paths -- returns GU_ERR_UNSUPPORTED.  Calls that read rows or state only
+ * (gu_mc_evaluate, sense, render, the getters, gu_read_*) are unaffected; they show door, key and lever cells as free cells.
+ * THE LEARNERS' TABLES: a problem with doors is Markov only on (cell, open), so while doors are set a gu_td_run table has S << D rows
+ * and row open * S + s belongs to cell s under the mask open.  Rules 1-4 of gu_td_run hold with "row of s" read as "row of (s, open)":
+ * the action is drawn on the row of (s, open), the bootstrap uses the pre-update row of (s', open'), the update goes to the row of
+ * (s, open); the arithmetic, the tie rule, the SARSA carry and the stream-4 words are as they are.  gu_td_init under doors allocates
+ * N * (S << D) * 32 bytes under its free-memory rule (and its bound of 2^31 - 1 rows); gu_td_get_q / gu_td_set_q move q[n][S << D][4].
+ * No other learner ever sees such a table: they are refused while doors are set.
+ * gu_set_doors: door[S], or NULL = no doors again (the kernels without doors run as before).  GU_ERR_STATE without a grid;
+ *              GU_ERR_UNSUPPORTED on a multi-grid engine, while wind or fruit is set (gu_set_wind and gu_set_fruit refuse while doors
+ *              are set) and while the agent trail is on (gu_trail_enable refuses while doors are set); GU_ERR_INVALID for a malformed
+ *              byte (a set bit 3 is a ninth slot), a missing slot, a slot without a door, a slot without a key or lever, or a door,
+ *              key or lever on a wall or terminal cell.  A refused call leaves the engine as it was.  Ends what the learners carry
+ *              from launch to launch, destroys a captured step graph, and drops the Q tables (gu_td_run returns GU_ERR_STATE until
+ *              gu_td_init) whenever it changes their row count -- it keeps them when the row count stays; clearing the doors goes
+ *              back to S rows the same way.  Keeps positions and step counts.  gu_set_grid, gu_set_grids and gu_generate_mazes drop
+ *              the doors.
+ * gu_get_doors: the plane (zeros when none) and D (0 = none set); either pointer may be NULL.
+ * gu_get_doors_state / gu_set_doors_state: the masks of envs env0 .. env0+n-1; GU_ERR_STATE while no doors are set; setting a bit at
+ *              or above D is GU_ERR_INVALID.  Setting masks ends the learners' carries (a carried SARSA action belongs to the old row). */
+int gu_set_doors(gu_handle h, const uint8_t *door /* [S], NULL = no doors again */);
+int gu_get_doors(gu_handle h, uint8_t *door /* zeros when none */, int32_t *n_slots /* 0 = none set */);
+int gu_get_doors_state(gu_handle h, int64_t env0, int64_t n, uint32_t *open);
+int gu_set_doors_state(gu_handle h, int64_t env0, int64_t n, const uint32_t *open);  /* a bit at or above D: GU_ERR_INVALID */
+
 /* ---- RNG ---------------------------------------------------------------------
  * Keys the per-env counter RNG (MurmurHash3 of seed, global env id, stream,
  * counter -- 32-bit counters, no stream repeats before 2^32 draws; host view:
@@ -435,7 +484,7 @@ int gu_sweep_get_queue(gu_handle h, int64_t env0, int64_t n, uint64_t *key, int3
 int gu_diag_sweep_heap(gu_handle h, int64_t env0, int64_t n, uint64_t *heap, int32_t *pos);
 /* gu_diag_rollout_form : introspection -- what the last gu_rollout of this engine ran on, as the launcher planned it
  *                      (csrc/gu_rollout_plan.hpp; DESIGN.md "Rollout dispatch").  *count = 12 words; with `form`, capacity >= 12:
- *                      kernel family (1 general, 2 transition-row, 3 K-step, 4 windy, 5 fruit); row layout (0 none, 1 planes, 2 packed, 3 triples);
+ *                      kernel family (1 general, 2 transition-row, 3 K-step, 4 windy, 5 fruit, 6 doors); row layout (0 none, 1 planes, 2 packed, 3 triples);
  *                      MAP of the general kernel (0 / 1 / 3 / 5), else -1; workgroup size; workgroups; dynamic LDS bytes; flag bits (1 pair
  *                      tables, 2 half waves, 4 per-wave grids, 8 thresholds in LDS, 16 straddles a 2^32-step boundary, 32 first step on the
  *                      table, 64 XCD-aware block order); K of the K-step kernel; log2 of the table's row pitch; staged action words per lane;
