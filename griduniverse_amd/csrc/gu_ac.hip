@@ -131,9 +131,7 @@ int gu_ac_init(gu_handle h, double h0, double v0)
 int gu_ac_run(gu_handle h, int64_t T, double alpha_actor, double alpha_critic, double gamma, uint32_t flags)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_ac_run");
-    GU_NO_FRUIT(h, "gu_ac_run");
-    GU_NO_DOORS(h, "gu_ac_run");
+    GU_NO_OVERLAY(h, "gu_ac_run");
     GU_NEED_GRID(h);
     GU_NEED_AC(h);
     GU_REQUIRE(std::isfinite(alpha_critic), GU_ERR_INVALID, "alpha_critic must be finite");

@@ -161,9 +161,7 @@ int gu_destroy(gu_handle h)
     gu_comm_free(h);
     gu_vi_free(h);
     gu_trail_free(h);
-    gu_wind_free(h);
-    gu_fruit_free(h);
-    gu_doors_free(h);
+    gu_overlay_free(h);
     gu_placement_release(h);
     gu_learners_drop(h, 0);
     if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
@@ -235,17 +233,10 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
     GU_HIP(hipStreamSynchronize(h->stream));
     h->entry_table_ok = false;  // (other cells, other flags)
     gu_tabular_drop_carry(h);
-    if (h->n_fruit) {  // the fruit belonged to the old grid's cells, and tables of S << F rows to the fruit
-        gu_td_rows_changed(h, 0);
-        gu_fruit_free(h);
-    }
-    if (h->n_doors) {  // ... and so did the doors, with their tables of S << D rows
-        gu_td_rows_changed(h, 0);
-        gu_doors_free(h);
-    }
+    gu_td_rows_changed(h, 0);  // an overlay belonged to the old grid's cells, and tables of S << bits rows to its masks
+    gu_overlay_free(h);
     gu_learners_drop(h, S);  // the learners' stores of another state count belong to another grid
     h->dyna_exact = false;  // a kept model may hold outcomes of the old cells: gu_dyna_run compares every observation from now on
-    gu_wind_free(h);  // the wind belonged to the old grid's cells
     h->nib_valid = false;
     if (h->d_nib) GU_HIP(hipFree(h->d_nib));
     h->d_nib = nullptr;
@@ -628,9 +619,7 @@ int gu_step_device(gu_handle h, int64_t t, uint32_t flags)
 int gu_step_graph(gu_handle h, int64_t t0, int64_t T, uint32_t flags)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_step_graph");
-    GU_NO_FRUIT(h, "gu_step_graph");
-    GU_NO_DOORS(h, "gu_step_graph");
+    GU_NO_OVERLAY(h, "gu_step_graph");
     h->entry_table_ok = false;
     GU_NEED_GRID(h);
     GU_REQUIRE(h->d_actions && t0 >= 0 && T > 0 && t0 + T <= h->actions_T, GU_ERR_STATE, "rows [%lld,%lld) not in the uploaded action stream",
@@ -1198,9 +1187,7 @@ int gu_look_step_ahead(gu_handle h, int64_t n, const int32_t *states, const int3
                        int32_t *next, int32_t *reward, int32_t *done)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_look_step_ahead");
-    GU_NO_FRUIT(h, "gu_look_step_ahead");
-    GU_NO_DOORS(h, "gu_look_step_ahead");
+    GU_NO_OVERLAY(h, "gu_look_step_ahead");
     GU_NEED_GRID(h);
     GU_REQUIRE(n > 0 && states && actions, GU_ERR_INVALID, "n <= 0 or NULL inputs");
     const size_t bytes = (size_t)n * 4;

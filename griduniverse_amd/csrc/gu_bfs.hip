@@ -71,9 +71,7 @@ extern "C" int gu_shortest_paths(gu_handle h, int32_t max_path, int8_t *path, in
 {
     int rc = gu_use_device(h);
     if (rc != GU_OK) return rc;
-    GU_NO_WIND(h, "gu_shortest_paths");
-    GU_NO_FRUIT(h, "gu_shortest_paths");
-    GU_NO_DOORS(h, "gu_shortest_paths");
+    GU_NO_OVERLAY(h, "gu_shortest_paths");
     GU_REQUIRE(h->has_grid, GU_ERR_STATE, "no grid set");
     GU_REQUIRE(h->S <= 65534, GU_ERR_UNSUPPORTED, "shortest paths are limited to grids of 65534 cells");
     GU_REQUIRE(max_path > 0 && path && path_len, GU_ERR_INVALID, "max_path <= 0 or NULL output");

@@ -187,9 +187,7 @@ int gu_dyna_init(gu_handle h)
 int gu_dyna_run(gu_handle h, int64_t T, int32_t P, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_dyna_run");
-    GU_NO_FRUIT(h, "gu_dyna_run");
-    GU_NO_DOORS(h, "gu_dyna_run");
+    GU_NO_OVERLAY(h, "gu_dyna_run");
     GU_NEED_GRID(h);
     GU_NEED_Q(h);
     GU_NEED_DYNA(h);

@@ -176,9 +176,7 @@ int gu_explore_set_tables(gu_handle h, int32_t C, const double *U, const double 
 int gu_explore_run(gu_handle h, int64_t T, int32_t mode, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_explore_run");
-    GU_NO_FRUIT(h, "gu_explore_run");
-    GU_NO_DOORS(h, "gu_explore_run");
+    GU_NO_OVERLAY(h, "gu_explore_run");
     GU_NEED_GRID(h);
     GU_NEED_Q(h);
     GU_NEED_COUNTS(h);

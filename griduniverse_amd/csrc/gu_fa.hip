@@ -331,9 +331,7 @@ int gu_fa_init(gu_handle h, int32_t K, int32_t F, const int32_t *phi, double w0)
 int gu_fa_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_fa_run");
-    GU_NO_FRUIT(h, "gu_fa_run");
-    GU_NO_DOORS(h, "gu_fa_run");
+    GU_NO_OVERLAY(h, "gu_fa_run");
     GU_NEED_GRID(h);
     GU_NEED_FA(h);
     GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Q-learning, 1 = SARSA", method);

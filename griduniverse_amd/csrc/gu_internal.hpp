@@ -110,6 +110,8 @@ struct GuPaceArgs {
     uint32_t adapt;         // 1: the slow loop moves the rule's aim (dec_q) by what the launches' start-to-start time says
 };
 
+enum { GU_OVERLAY_NONE = 0, GU_OVERLAY_WIND, GU_OVERLAY_FRUIT, GU_OVERLAY_DOORS };  // gu_engine::overlay
+
 struct gu_engine {
     int device = -1;
     int n_cu = 256;                  // compute units of the device (hipDeviceAttributeMultiprocessorCount)
@@ -131,19 +133,18 @@ struct gu_engine {
     int32_t cell_bytes = 0;          // S rounded up to 16
     uint8_t *d_cell = nullptr;       // absorbing-aware planes    [2 * cell_bytes]
     uint8_t *d_cell_raw = nullptr;   // care_about_terminal=False [2 * cell_bytes]
-    uint8_t *d_wind_cell = nullptr;  // wind (gu_set_wind, gu_wind.hip; single-grid engines): [3 * cell_bytes] the planes of d_cell with the
-                                     // wind plane behind them -- what the windy kernels stage in one piece; nullptr: calm
-    uint32_t gust_q16 = 0;           // ... and its gust probability in 1/65536
-    uint8_t *d_fruit_cell = nullptr; // fruit (gu_set_fruit, gu_fruit.hip; single-grid engines): [3 * cell_bytes] the planes of d_cell with the
-                                     // fruit plane behind them; nullptr: no fruit
-    uint32_t *d_eaten = nullptr;     // ... [N] the envs' masks of eaten fruit (bit = slot), cleared by every reset
-    int32_t n_fruit = 0;             // ... F, the number of fruit cells (1 .. 32; 0: no fruit); gu_td_run's tables then have S << F rows
-    uint32_t fruit_values = 0;       // ... the three kinds' values as int8 bytes 1 .. 3 (byte 0 zero), as the kernels take them
-    int32_t fruit_value[3] = {0, 0, 0};
-    uint8_t *d_door_cell = nullptr;  // doors (gu_set_doors, gu_doors.hip; single-grid engines): [3 * cell_bytes] the planes of d_cell with the
-                                     // door plane behind them; nullptr: no doors
-    uint32_t *d_open = nullptr;      // ... [N] the envs' masks of open slots (bit = slot), cleared by every reset
-    int32_t n_doors = 0;             // ... D, the number of slots in use (1 .. 8; 0: no doors); gu_td_run's tables then have S << D rows
+    // the overlay slot (gu_overlay.hip; DESIGN.md "Overlays"): wind, fruit or doors -- a third byte plane behind the two cell planes
+    // of a single-grid engine and, for fruit and doors, one uint32 mask per env; at most one of them at a time
+    int overlay = GU_OVERLAY_NONE;       // which one is set (GU_OVERLAY_*)
+    uint8_t *d_overlay_cell = nullptr;   // [3 * cell_bytes] the planes of d_cell with the overlay's plane behind them -- what its kernels
+                                         // stage in one piece; nullptr: none
+    uint32_t *d_overlay_mask = nullptr;  // [N] fruit: the envs' masks of eaten fruit, doors: of open slots (bit = slot), cleared by every
+                                         // reset; nullptr under wind
+    int32_t overlay_bits = 0;            // bits of a mask in use: F fruit cells (1 .. 32), D door slots (1 .. 8), 0 under wind;
+                                         // gu_td_run's tables have S << overlay_bits rows
+    uint32_t overlay_param = 0;          // wind: gust_q16, the gust probability in 1/65536; fruit: the three kinds' values as int8 bytes
+                                         // 1 .. 3 (byte 0 zero), as the kernels take them
+    int32_t fruit_value[3] = {0, 0, 0};  // ... and as gu_get_fruit hands them back
     uint8_t *d_kind = nullptr;       // [n_grids][cell_bytes] texture class of every cell as the reference's viewer picks it
                                      // (rendering.py:119-133: goal, else lava, else wall, else ground = 3, 2, 1, 0) -- the flags
                                      // cannot tell a goal+lava cell from a lava cell; nullptr for device-generated mazes (no
@@ -401,17 +402,16 @@ int gu_ensure_scratch(gu_engine *h, size_t bytes);
 
 #define GU_NEED_GRID(h) GU_REQUIRE((h)->has_grid, GU_ERR_STATE, "no grid set: call gu_set_grid first")
 
-// every call that moves envs or reads the move rule and has no windy form refuses while wind is set (include/gu.h: gu_set_wind)
-#define GU_NO_WIND(h, fn) \
-    GU_REQUIRE(!(h)->d_wind_cell, GU_ERR_UNSUPPORTED, "%s knows no wind: the engine has wind set (gu_set_wind; NULL calms it again)", fn)
+// What the messages call an overlay, and how they tell the caller that it is set and which call takes it away (index: GU_OVERLAY_*)
+static const char *const GU_OVERLAY_NAME[4] = {"none", "wind", "fruit", "doors"};
+static const char *const GU_OVERLAY_IS_SET[4] = {"", "the engine has wind set (gu_set_wind; NULL calms it again)",
+                                                 "the engine has fruit set (gu_set_fruit; NULL takes it away again)",
+                                                 "the engine has doors set (gu_set_doors; NULL takes them away again)"};
 
-// ... and so does every such call without a form that eats fruit while fruit is set (include/gu.h: gu_set_fruit)
-#define GU_NO_FRUIT(h, fn) \
-    GU_REQUIRE(!(h)->n_fruit, GU_ERR_UNSUPPORTED, "%s knows no fruit: the engine has fruit set (gu_set_fruit; NULL takes it away again)", fn)
-
-// ... and without a form that stops at closed doors while doors are set (include/gu.h: gu_set_doors)
-#define GU_NO_DOORS(h, fn) \
-    GU_REQUIRE(!(h)->n_doors, GU_ERR_UNSUPPORTED, "%s knows no doors: the engine has doors set (gu_set_doors; NULL takes them away again)", fn)
+// every call that moves envs or reads the move or reward rule and has no form for overlays refuses while one is set (include/gu.h:
+// gu_set_wind, gu_set_fruit, gu_set_doors)
+#define GU_NO_OVERLAY(h, fn) \
+    GU_REQUIRE(!(h)->overlay, GU_ERR_UNSUPPORTED, "%s knows no %s: %s", fn, GU_OVERLAY_NAME[(h)->overlay], GU_OVERLAY_IS_SET[(h)->overlay])
 
 // frees device buffers and forgets them (hipFree's status is not looked at)
 template <class... P>
@@ -529,29 +529,34 @@ static inline void gu_tabular_drop_carry(gu_engine *h)
     h->is_key = 0;
 }
 
-// ---- wind (gu_wind.hip): the launches that gu_launch_step / gu_launch_rollout hand over while wind is set ----
+// ---- overlays (gu_overlay.hip: the slot, its install path, getters, reset and launches; gu_overlay.hpp: what its kernels share) ----
 struct RolloutArgs;
 struct GuRolloutPlan;
-int gu_wind_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward, int32_t *host_done,
-                        uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
-void gu_wind_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);  // (the launch alone: gu_launch_rollout checks and completes it)
-void gu_wind_free(gu_engine *h);
-
-// ---- fruit (gu_fruit.hip): the launches that gu_launch_step / gu_launch_rollout hand over while fruit is set ----
-int gu_fruit_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward, int32_t *host_done,
-                         uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
-void gu_fruit_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);  // (the launch alone, as gu_wind_launch_rollout)
-int gu_fruit_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done);  // clears the masks of the envs a reset is about to take; no-op without fruit
-void gu_fruit_free(gu_engine *h);
-// gu_td.hip: the fruit count becomes F (0: none) -- Q tables whose row count is not S << F go, with what hangs on them
-void gu_td_rows_changed(gu_engine *h, int32_t F);
-
-// ---- doors (gu_doors.hip): the same hand-overs while doors are set (gu_td_rows_changed then takes D, the slots in use) ----
-int gu_doors_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward, int32_t *host_done,
-                         uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
-void gu_doors_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &a);  // (the launch alone, as gu_wind_launch_rollout)
-int gu_doors_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done);  // clears the masks of the envs a reset is about to take; no-op without doors
-void gu_doors_free(gu_engine *h);
+struct OverlayStepArgs;
+struct OverlayRolloutArgs;
+// GU_ERR_UNSUPPORTED unless the engine can take an overlay of `kind`: one grid, no trail, no overlay of another kind
+int gu_overlay_admits(gu_engine *h, int kind);
+// Puts `kind` into the slot: `plane` [S] is the feature's plane, validated by its entry point, `bits` the mask bits in use (0: no
+// masks), `param` the kernels' parameter word.  plane == nullptr takes the overlay away.  A refused call leaves the engine as it was.
+int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bits, uint32_t param);
+void gu_overlay_free(gu_engine *h);
+int gu_overlay_get_plane(gu_engine *h, int kind, uint8_t *plane);  // [S]; zeros while `kind` is not set
+int gu_overlay_get_masks(gu_engine *h, int kind, int64_t env0, int64_t n, uint32_t *masks, const char *what);
+int gu_overlay_set_masks(gu_engine *h, int kind, int64_t env0, int64_t n, const uint32_t *masks, const char *what);
+int gu_overlay_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done);  // clears the masks of the envs a reset is about to take; no-op without masks
+// the launches that gu_launch_step / gu_launch_rollout hand over while an overlay is set
+int gu_overlay_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward, int32_t *host_done,
+                           uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
+void gu_overlay_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &r);  // (the launch alone: gu_launch_rollout checks and completes it)
+// ... and what each feature keeps of them: the ladder from the launch's shape to its kernel's instantiation (gu_wind.hip, gu_fruit.hip, gu_doors.hip)
+void gu_wind_step(gu_engine *h, bool lds, const OverlayStepArgs &a);
+void gu_fruit_step(gu_engine *h, bool lds, const OverlayStepArgs &a);
+void gu_doors_step(gu_engine *h, bool lds, const OverlayStepArgs &a);
+void gu_wind_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a);
+void gu_fruit_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a);
+void gu_doors_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a);
+// gu_td.hip: the mask bits in use become `bits` (0: none) -- Q tables whose row count is not S << bits go, with what hangs on them
+void gu_td_rows_changed(gu_engine *h, int32_t bits);
 
 // ---- agent trail (gu_trail.hip): no-ops while the trail is off ----------------------
 int gu_trail_after_step(gu_engine *h, uint32_t flags);

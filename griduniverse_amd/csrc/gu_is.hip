@@ -201,9 +201,7 @@ int gu_is_init(gu_handle h)
 int gu_is_run(gu_handle h, int64_t T, int32_t L, double gamma, uint32_t eps_q16, double w_cap, uint32_t flags)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_is_run");
-    GU_NO_FRUIT(h, "gu_is_run");
-    GU_NO_DOORS(h, "gu_is_run");
+    GU_NO_OVERLAY(h, "gu_is_run");
     GU_NEED_GRID(h);
     GU_NEED_Q(h);
     GU_NEED_WEIGHTS(h);

@@ -20,7 +20,7 @@
 // The action -> delta LUT is four int16 lanes of one 64-bit scalar register (v_lshrrev_b64 +
 // v_bfe_i32): staging a 4-entry table in LDS instead would put a second, dependent ds_read on
 // every step for no gain.
-#include "gu_rollout.hpp"
+#include "gu_overlay.hpp"  // (gu_rollout.hpp; gu_step_publish)
 
 #include <cstdio>
 #include <cstdlib>
@@ -148,21 +148,7 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_step_kernel(const StepArgs a)
     // episode-done compaction, first half: one 64-bit ballot word per wave (every workgroup size used is a multiple of 64)
     const uint64_t bits = __ballot(d != 0);
     if ((threadIdx.x & 63) == 0 && e < a.N) a.done_bits[e >> 6] = bits;
-    if (a.host_seq) {
-        // Completion word: the host spins on a sequence number in page-locked memory instead of going through the
-        // runtime's completion path (no interrupt, no runtime call).  Every block makes its mirror stores visible to the
-        // host, then counts itself; the block that completes the count publishes the number (and re-arms the counter).
-        __threadfence_system();
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const uint32_t arrived = atomicAdd(a.blocks_done, 1u);
-            if (arrived == gridDim.x - 1) {
-                *a.blocks_done = 0u;
-                __threadfence_system();
-                __hip_atomic_store(a.host_seq, a.seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
+    gu_step_publish(a.host_seq, a.seq, a.blocks_done);  // the completion word (gu_overlay.hpp)
 }
 
 // The uploaded stream as the rollout kernels read it: word [k][env] holds the two-bit actions of steps 16 k .. 16 k + 15 of
@@ -302,8 +288,7 @@ int gu_launch_reset(gu_engine *h, const uint8_t *d_mask, const int32_t *d_choice
     gu_tabular_drop_carry(h);
     int trail_rc = gu_trail_before_reset(h, d_mask, only_done);  // (reads the done flags the reset is about to clear)
     if (trail_rc != GU_OK) return trail_rc;
-    GU_TRY(gu_fruit_before_reset(h, d_mask, only_done));  // gu_fruit.hip (nothing without fruit)
-    GU_TRY(gu_doors_before_reset(h, d_mask, only_done));  // gu_doors.hip (nothing without doors)
+    GU_TRY(gu_overlay_before_reset(h, d_mask, only_done));  // gu_overlay.hip (nothing without masks)
     ResetArgs a{h->pos(), h->done(), h->d_episode, h->d_starts, d_mask, d_choice, h->d_done_bits,
                 (uint32_t)h->n_starts, h->seed_prefix, (uint32_t)h->env_id0, h->N, only_done ? 1 : 0, gu_grid_sel(h)};
     hipLaunchKernelGGL(gu_reset_kernel, dim3(gu_blocks(h->N, GU_BLOCK)), dim3(GU_BLOCK), 0, h->stream, a);
@@ -314,9 +299,7 @@ int gu_launch_reset(gu_engine *h, const uint8_t *d_mask, const int32_t *d_choice
 int gu_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward,
                    int32_t *host_done, uint32_t *host_seq, uint32_t seq, uint32_t *host_err)
 {
-    if (h->d_wind_cell) return gu_wind_launch_step(h, d_actions_row, flags, host_obs, host_reward, host_done, host_seq, seq, host_err);  // gu_wind.hip
-    if (h->n_fruit) return gu_fruit_launch_step(h, d_actions_row, flags, host_obs, host_reward, host_done, host_seq, seq, host_err);  // gu_fruit.hip
-    if (h->n_doors) return gu_doors_launch_step(h, d_actions_row, flags, host_obs, host_reward, host_done, host_seq, seq, host_err);  // gu_doors.hip
+    if (h->overlay) return gu_overlay_launch_step(h, d_actions_row, flags, host_obs, host_reward, host_done, host_seq, seq, host_err);  // gu_overlay.hip
     h->entry_table_ok = false;
     StepArgs a{h->d_cell, h->cell_bytes, h->W, h->delta_lut, d_actions_row, h->pos(), h->reward(), h->done(),
                h->d_episode, h->d_tcount, h->d_starts, (uint32_t)h->n_starts, h->seed_prefix, (uint32_t)h->env_id0, h->N, flags,
@@ -526,9 +509,8 @@ static int gu_rollout_straddles(gu_engine *h, int64_t T, int32_t policy, bool *s
 // Checks, the straddle test, the plan (gu_rollout_plan.hpp), what the plan needs, the arguments, the schedule, the launch, the completion.
 int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
 {
-    GU_REQUIRE(!(h->d_wind_cell && (flags & GU_F_PACKED)), GU_ERR_UNSUPPORTED, "a rollout under wind (gu_set_wind) writes int32 rows only: GU_F_PACKED is refused");
-    GU_REQUIRE(!(h->n_fruit && (flags & GU_F_PACKED)), GU_ERR_UNSUPPORTED, "a rollout under fruit (gu_set_fruit) writes int32 rows only: GU_F_PACKED is refused");
-    GU_REQUIRE(!(h->n_doors && (flags & GU_F_PACKED)), GU_ERR_UNSUPPORTED, "a rollout under doors (gu_set_doors) writes int32 rows only: GU_F_PACKED is refused");
+    GU_REQUIRE(!(h->overlay && (flags & GU_F_PACKED)), GU_ERR_UNSUPPORTED, "a rollout under %s (gu_set_%s) writes int32 rows only: GU_F_PACKED is refused",
+               GU_OVERLAY_NAME[h->overlay], GU_OVERLAY_NAME[h->overlay]);
     GU_REQUIRE(!h->trail_cap || (flags & (GU_F_TRAJECTORY | GU_F_PACKED)), GU_ERR_UNSUPPORTED,
                "the agent trail is on (gu_trail_enable): a rollout must write rows (GU_F_TRAJECTORY or GU_F_PACKED) to feed it");
     GU_REQUIRE(policy >= GU_POLICY_UNIFORM && policy <= GU_POLICY_SAMPLE, GU_ERR_INVALID, "unknown policy kind %d", policy);
@@ -575,9 +557,9 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
     if (p.pace_slot >= 0) GU_TRY(gu_pace_for(h, p, T, &a.pace));
 
     switch (p.family) {
-    case GU_PLAN_WIND: gu_wind_launch_rollout(h, p, a); break;
-    case GU_PLAN_FRUIT: gu_fruit_launch_rollout(h, p, a); break;
-    case GU_PLAN_DOORS: gu_doors_launch_rollout(h, p, a); break;
+    case GU_PLAN_WIND:
+    case GU_PLAN_FRUIT:
+    case GU_PLAN_DOORS: gu_overlay_launch_rollout(h, p, a); break;
     case GU_PLAN_KSTEP: gu_kstep_launch(h, p, a); break;
     case GU_PLAN_ROWS:
         if (!gu_rows_launch(h, p, a)) return gu_fail(GU_ERR_HIP, "gu_rollout_rows_kernel reports static LDS: its table must start at LDS address 0");
@@ -595,7 +577,7 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
     gu_rollout_plan_form(p, h->rollout_form);
     h->steps_taken += (uint64_t)T;
     gu_tabular_drop_carry(h);
-    h->entry_table_ok = p.family != GU_PLAN_WIND && p.family != GU_PLAN_FRUIT && p.family != GU_PLAN_DOORS;
+    h->entry_table_ok = !h->overlay;  // (an overlay's state is not what the entry table assumes)
     return gu_trail_after_rollout(h, T, p.traj, p.auto_mode != 0);
 }
 

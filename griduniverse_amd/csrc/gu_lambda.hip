@@ -196,9 +196,7 @@ int gu_lambda_run(gu_handle h, int64_t T, int32_t method, int32_t K, double alph
                   uint32_t flags)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_lambda_run");
-    GU_NO_FRUIT(h, "gu_lambda_run");
-    GU_NO_DOORS(h, "gu_lambda_run");
+    GU_NO_OVERLAY(h, "gu_lambda_run");
     GU_NEED_GRID(h);
     GU_NEED_Q(h);
     GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = Watkins's Q(lambda), 1 = SARSA(lambda)", method);

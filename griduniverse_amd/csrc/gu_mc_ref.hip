@@ -133,9 +133,7 @@ extern "C" int gu_mc_walk_lengths(gu_handle h, int64_t K, const double *u, int64
 {
     int rc = gu_use_device(h);
     if (rc != GU_OK) return rc;
-    GU_NO_WIND(h, "gu_mc_walk_lengths");
-    GU_NO_FRUIT(h, "gu_mc_walk_lengths");
-    GU_NO_DOORS(h, "gu_mc_walk_lengths");
+    GU_NO_OVERLAY(h, "gu_mc_walk_lengths");
     GU_REQUIRE(h->has_grid && h->n_grids == 1, GU_ERR_STATE, "gu_mc_walk_lengths needs a single-grid engine");
     GU_REQUIRE(K > 0 && u && n_offsets > 0 && n_offsets <= K && n_starts > 0 && n_starts <= 65535 && start_states && cdf && lengths, GU_ERR_INVALID, "bad arguments");
     GU_REQUIRE(cap > 0 && cap <= 65534, GU_ERR_UNSUPPORTED, "episodes of up to 65534 steps");
@@ -166,9 +164,7 @@ extern "C" int gu_mc_walk_episodes(gu_handle h, int64_t K, const double *u, cons
 {
     int rc = gu_use_device(h);
     if (rc != GU_OK) return rc;
-    GU_NO_WIND(h, "gu_mc_walk_episodes");
-    GU_NO_FRUIT(h, "gu_mc_walk_episodes");
-    GU_NO_DOORS(h, "gu_mc_walk_episodes");
+    GU_NO_OVERLAY(h, "gu_mc_walk_episodes");
     GU_REQUIRE(h->has_grid && h->n_grids == 1, GU_ERR_STATE, "gu_mc_walk_episodes needs a single-grid engine");
     GU_REQUIRE(K >= 0 && u && cdf && offsets && first_state && cap > 0 && cap <= 65534, GU_ERR_INVALID, "bad arguments");
     GU_REQUIRE(h->d_traj && T > 0 && T <= h->traj_T, GU_ERR_STATE, "trajectory buffer does not hold %lld rows: call gu_reserve_trajectory", (long long)T);

@@ -363,9 +363,7 @@ int gu_mcts_run(gu_handle h, int64_t T, int32_t M, int32_t H, int32_t D, double 
                 uint32_t flags)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_mcts_run");
-    GU_NO_FRUIT(h, "gu_mcts_run");
-    GU_NO_DOORS(h, "gu_mcts_run");
+    GU_NO_OVERLAY(h, "gu_mcts_run");
     GU_NEED_GRID(h);
     GU_NEED_Q(h);
     GU_NEED_POOLS(h);

@@ -176,9 +176,7 @@ extern "C" {
 int gu_nstep_run(gu_handle h, int64_t T, int32_t method, int32_t n, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_nstep_run");
-    GU_NO_FRUIT(h, "gu_nstep_run");
-    GU_NO_DOORS(h, "gu_nstep_run");
+    GU_NO_OVERLAY(h, "gu_nstep_run");
     GU_NEED_GRID(h);
     GU_NEED_Q(h);
     GU_REQUIRE(method == 0 || method == 1, GU_ERR_INVALID, "method %d: 0 = n-step Q-learning, 1 = n-step SARSA", method);

@@ -145,9 +145,7 @@ extern "C" {
 int gu_reinforce_run(gu_handle h, int64_t T, int32_t L, double alpha_actor, double alpha_baseline, double gamma, uint32_t flags)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_reinforce_run");
-    GU_NO_FRUIT(h, "gu_reinforce_run");
-    GU_NO_DOORS(h, "gu_reinforce_run");
+    GU_NO_OVERLAY(h, "gu_reinforce_run");
     GU_NEED_GRID(h);
     GU_NEED_AC(h);
     GU_REQUIRE(L >= 1 && L <= GU_REINFORCE_MAX, GU_ERR_INVALID, "L %d out of range (1 .. %d)", L, GU_REINFORCE_MAX);

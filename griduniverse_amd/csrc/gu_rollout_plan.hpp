@@ -1,7 +1,7 @@
 // gu_rollout_plan.hpp -- which kernel a gu_rollout call runs on, and in which shape: ONE pure function (DESIGN.md "Rollout dispatch").
 //
 // gu_rollout_plan() makes no HIP call and allocates nothing: engine fields and gu_opt() in, everything that is decided about a launch
-// out, asked in the order layout, wind, K-step, rows, general; every threshold keeps its measurement beside it.  gu_launch_rollout
+// out, asked in the order layout, overlay, K-step, rows, general; every threshold keeps its measurement beside it.  gu_launch_rollout
 // (gu_kernels.hip) executes and records the plan; tests/test_rollout_plan.py runs it against tests/golden/rollout_plan.json, no device.
 #pragma once
 #include "gu_internal.hpp"
@@ -10,6 +10,7 @@
 #include <type_traits>
 
 enum { GU_PLAN_GENERAL = 1, GU_PLAN_ROWS = 2, GU_PLAN_KSTEP = 3, GU_PLAN_WIND = 4, GU_PLAN_FRUIT = 5, GU_PLAN_DOORS = 6 };  // kernel families (gu_diag_rollout_form, word 1)
+static_assert(GU_PLAN_FRUIT - GU_PLAN_WIND == GU_OVERLAY_FRUIT - GU_OVERLAY_WIND && GU_PLAN_DOORS - GU_PLAN_WIND == GU_OVERLAY_DOORS - GU_OVERLAY_WIND, "an overlay's family is GU_PLAN_WIND + its kind - GU_OVERLAY_WIND");
 // `exclude`: families (1u << family) and forms that the executor found it cannot run -- a table that could not be allocated, dynamic LDS
 // that does not start at address 0 -- and plans again without
 #define GU_PLAN_NO_PAIRS (1u << 8)  /* the transition-row kernel's pair tables */
@@ -311,10 +312,10 @@ inline GuRolloutPlan gu_rollout_plan(const gu_engine *h, int64_t T, int32_t poli
     // CUs; at 16 384 the two are level -- unless the batch is spread over twice the waves (32 envs each: 43.6 against 53.3 us,
     // profiles/archive/r05m_half_sizes.txt) --, beyond it the planes win.  So: triples for the uniform policy where the pair tables fit,
     // up to n_cu / 4 workgroups of 256 (half waves for the upper half of that range).  Batches of more than 2^24 envs (lane offset + 15 rows must stay
-    // below 2^32 bytes) and engines with the agent trail on or wind set always keep the planes.
+    // below 2^32 bytes) and engines with the agent trail on or an overlay set always keep the planes.
     // (AS IT STANDS the default does not ask the auto mode: with several start cells the triples go to the general kernel.  DESIGN.md 4.0)
     p.traj = (flags & GU_F_PACKED) ? 2 : ((flags & GU_F_TRAJECTORY) ? 1 : 0);
-    if (p.traj == 1 && h->N <= ((int64_t)1 << 24) && !h->trail_cap && !h->d_wind_cell && !h->n_fruit && !h->n_doors) {
+    if (p.traj == 1 && h->N <= ((int64_t)1 << 24) && !h->trail_cap && !h->overlay) {
         const int64_t layout = gu_opt(h, GU_OPT_TRAJ_LAYOUT);
         if (layout == 1 || (layout == -1 && policy == GU_POLICY_UNIFORM && gu_rows_pairs_fit(h) && (int64_t)gu_blocks(h->N, 256) * 4 <= h->n_cu)) p.traj = 3;
     }
@@ -324,17 +325,12 @@ inline GuRolloutPlan gu_rollout_plan(const gu_engine *h, int64_t T, int32_t poli
     p.need_nib = h->n_grids > 1 && (policy == GU_POLICY_UNIFORM || policy == GU_POLICY_STREAM) && !gu_lds_block(h, gu_rollout_block(h), 2) && h->W <= 1022 &&
                  gu_nibble_bytes_per_wave(h) <= (size_t)h->lds_per_cu - 512;
     const bool xcd = gu_opt(h, GU_OPT_ROLLOUT_XCD) != 0 && h->n_grids == 1;  // XCD-aware env-block order (see gu_env_block; measured slower, off)
-    // ---- wind, K-step, rows, general.  A launch during which an env passes a multiple of 2^32 steps goes to the general kernel,
+    // ---- overlay, K-step, rows, general.  A launch during which an env passes a multiple of 2^32 steps goes to the general kernel,
     // which asks the RNG's epoch per lane and step.
-    if (h->d_wind_cell) {  // the windy kernel (gu_wind.hip) serves every shape: three planes in LDS where they fit, int32 planes only
-        p.family = GU_PLAN_WIND, p.block = GU_BLOCK, p.blocks = gu_blocks(h->N, GU_BLOCK), p.lds = gu_lds_block(h, GU_BLOCK, 3) ? 3 * (size_t)h->cell_bytes : 0;
-        p.straddle = p.entry_table = false;  // (its kernel reads neither: the RNG's epoch is asked per step there)
-    } else if (h->n_fruit) {  // the fruit kernel (gu_fruit.hip), likewise: [flags | reward | fruit] in LDS where they fit, int32 planes only
-        p.family = GU_PLAN_FRUIT, p.block = GU_BLOCK, p.blocks = gu_blocks(h->N, GU_BLOCK), p.lds = gu_lds_block(h, GU_BLOCK, 3) ? 3 * (size_t)h->cell_bytes : 0;
-        p.straddle = p.entry_table = false;  // (64-bit step count in the kernel, as the windy one)
-    } else if (h->n_doors) {  // the door kernel (gu_doors.hip), likewise: [flags | reward | door] in LDS where they fit, int32 planes only
-        p.family = GU_PLAN_DOORS, p.block = GU_BLOCK, p.blocks = gu_blocks(h->N, GU_BLOCK), p.lds = gu_lds_block(h, GU_BLOCK, 3) ? 3 * (size_t)h->cell_bytes : 0;
-        p.straddle = p.entry_table = false;
+    if (h->overlay) {  // an overlay's kernel (gu_wind.hip, gu_fruit.hip, gu_doors.hip) serves every shape: three planes in LDS where they fit, int32 planes only
+        p.family = GU_PLAN_WIND + h->overlay - GU_OVERLAY_WIND, p.block = GU_BLOCK, p.blocks = gu_blocks(h->N, GU_BLOCK);
+        p.lds = gu_lds_block(h, GU_BLOCK, 3) ? 3 * (size_t)h->cell_bytes : 0;
+        p.straddle = p.entry_table = false;  // (its kernel reads neither: it counts steps in 64 bits and asks the RNG's epoch per step)
     } else if (!straddle && !(exclude & (1u << GU_PLAN_KSTEP)) && gu_plan_kstep(h, T, xcd, &p)) {}
     else if (!straddle && !(exclude & (1u << GU_PLAN_ROWS)) && gu_plan_rows(h, exclude, xcd, &p)) {}
     else gu_plan_general(h, T, exclude, xcd, &p);

@@ -202,9 +202,7 @@ int gu_search_run(gu_handle h, int64_t T, int32_t M, int32_t D, double alpha, do
                   uint32_t flags)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_search_run");
-    GU_NO_FRUIT(h, "gu_search_run");
-    GU_NO_DOORS(h, "gu_search_run");
+    GU_NO_OVERLAY(h, "gu_search_run");
     GU_NEED_GRID(h);
     GU_NEED_Q(h);
     GU_REQUIRE(M >= 0 && M <= GU_SEARCH_MAX_M, GU_ERR_INVALID, "simulations %d out of range (0 .. %d)", M, GU_SEARCH_MAX_M);

@@ -110,15 +110,15 @@ __device__ __forceinline__ uint64_t gu_dyna_pack(int32_t s2, int32_t r, int32_t 
 // ROWS = false (gu_fa.hip): the lane has no table of rows of its own -- begin / reset / next_row read nothing from a.q, and the
 // kernel keeps `q` (for gu_fa.hip: the folded row of the current state) itself.
 // WIND (include/gu.h: gu_set_wind; 0 = calm, 1 = wind without gusts, 2 = with gusts): a.cell then carries the wind plane behind the two
-// cell planes (gu_engine::d_wind_cell; staged with them), the kernel sets `gust_q16` (its own arguments hold it: TabArgs does not),
+// cell planes (gu_engine::d_overlay_cell; staged with them), the kernel sets `gust_q16` (its own arguments hold it: TabArgs does not),
 // and move() pushes the agent behind its action.  The calm instantiations hold none of it.
-// FRUIT (include/gu.h: gu_set_fruit): a.cell carries the fruit plane behind the two cell planes (gu_engine::d_fruit_cell), the kernel
+// FRUIT (include/gu.h: gu_set_fruit): a.cell carries the fruit plane behind the two cell planes (gu_engine::d_overlay_cell), the kernel
 // sets `fvalues`, `rows` and `eaten` before begin() and stores `eaten` behind end() (its own arguments hold them), and the table has S << F
 // rows: the lane stands on row eaten * S + s.  move() leaves the mask behind the step in `eaten2`, step() makes it current.  A wall
 // bump onto an uneaten fruit keeps the cell and changes the row, so next_row() and update() compare ROWS, not cells.  The
 // instantiations without fruit hold none of it (row() is s there).
 // DOORS (include/gu.h: gu_set_doors; never with WIND or FRUIT): a.cell carries the door plane behind the two cell planes
-// (gu_engine::d_door_cell) and the table has S << D rows.  The env's mask of open slots lives where fruit keeps its mask of eaten
+// (gu_engine::d_overlay_cell) and the table has S << D rows.  The env's mask of open slots lives where fruit keeps its mask of eaten
 // fruit -- `eaten` is the mask the lane stands under, `eaten2` the one behind move() --, so the rows and their comparisons are
 // fruit's: the kernel sets `rows` and `eaten` before begin() and stores `eaten` behind end().  move() turns the candidate cell back
 // at a closed door and lets a key or lever of the cell ENTERED change `eaten2`; it reads the candidate's three bytes together and
@@ -278,9 +278,9 @@ struct TabLane {
 
 // the tables that more than one learner's entry points need, present and of this grid's size
 #define GU_NEED_Q(h) GU_REQUIRE((h)->d_q && (h)->td_S == (h)->S, GU_ERR_STATE, "no Q tables: call gu_td_init first")
-// ... gu_td_run and the table copies alone know fruit: S << F rows (include/gu.h: gu_set_fruit)
-// ... and doors: S << D rows (include/gu.h: gu_set_doors); the two exclude each other, so one of the counts is zero
-#define GU_TD_ROWS(h) ((int64_t)(h)->S << ((h)->n_fruit + (h)->n_doors))  /* (64 bits: F runs to 32; gu_td_init keeps it below 2^31) */
+// ... gu_td_run and the table copies alone know the overlays' masks: S << F rows under fruit, S << D under doors (include/gu.h:
+// gu_set_fruit, gu_set_doors)
+#define GU_TD_ROWS(h) ((int64_t)(h)->S << (h)->overlay_bits)  /* (64 bits: F runs to 32; gu_td_init keeps it below 2^31) */
 #define GU_NEED_TD_Q(h) GU_REQUIRE((h)->d_q && (int64_t)(h)->td_S == GU_TD_ROWS(h), GU_ERR_STATE, "no Q tables: call gu_td_init first")
 #define GU_NEED_AC(h) GU_REQUIRE((h)->d_ac_h && (h)->ac_S == (h)->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first")
 

@@ -79,20 +79,18 @@ static int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, d
     gu_tabular_args(h, a, T, alpha, gamma, eps_q16, flags);
     a.next_a = h->d_td_next;
     a.carry = (method == 1 && h->td_carry) ? 1 : 0;
-    a.gust_q16 = h->gust_q16;
-    a.fruit_values = h->fruit_values, a.rows = h->td_S, a.eaten = h->d_eaten;
+    // the overlay's instantiations, on [flags | reward | overlay]; fruit and doors learn on S << bits rows and keep the env's mask in `eaten`
+    a.gust_q16 = a.fruit_values = h->overlay_param, a.rows = h->td_S, a.eaten = h->d_overlay_mask;
+    if (h->overlay) a.cell = h->d_overlay_cell;
     int rc;
-    if (h->n_doors) {  // the door instantiations, on [flags | reward | door] and S << D rows
-        a.cell = h->d_door_cell, a.eaten = h->d_open;
+    if (h->overlay == GU_OVERLAY_DOORS) {
         rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 0, false, true>, gu_td_kernel<true, false, 0, false, true>, a, GU_BLOCK, 0, 3)
                          : gu_tabular_launch(h, gu_td_kernel<false, true, 0, false, true>, gu_td_kernel<false, false, 0, false, true>, a, GU_BLOCK, 0, 3);
-    } else if (h->n_fruit) {  // the fruit instantiations, on the three planes and S << F rows
-        a.cell = h->d_fruit_cell;
+    } else if (h->overlay == GU_OVERLAY_FRUIT) {
         rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 0, true>, gu_td_kernel<true, false, 0, true>, a, GU_BLOCK, 0, 3)
                          : gu_tabular_launch(h, gu_td_kernel<false, true, 0, true>, gu_td_kernel<false, false, 0, true>, a, GU_BLOCK, 0, 3);
-    } else if (h->d_wind_cell) {  // the windy instantiations, on the three planes
-        a.cell = h->d_wind_cell;
-        if (h->gust_q16)
+    } else if (h->overlay == GU_OVERLAY_WIND) {
+        if (h->overlay_param)  // (gusts)
             rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 2>, gu_td_kernel<true, false, 2>, a, GU_BLOCK, 0, 3)
                              : gu_tabular_launch(h, gu_td_kernel<false, true, 2>, gu_td_kernel<false, false, 2>, a, GU_BLOCK, 0, 3);
         else
@@ -120,9 +118,9 @@ static void gu_td_drop(gu_engine *h)  // the Q tables and what hangs on them
     gu_mcts_free(h);  // (gu_mcts_init again)
 }
 
-void gu_td_rows_changed(gu_engine *h, int32_t F)
+void gu_td_rows_changed(gu_engine *h, int32_t bits)
 {
-    if (h->td_S && (int64_t)h->td_S != ((int64_t)h->S << F)) gu_td_drop(h);
+    if (h->td_S && (int64_t)h->td_S != ((int64_t)h->S << bits)) gu_td_drop(h);
 }
 
 void gu_learners_drop(gu_engine *h, int32_t S)
@@ -151,8 +149,8 @@ int gu_td_init(gu_handle h, double q0)
     GU_REQUIRE(std::isfinite(q0), GU_ERR_INVALID, "q0 must be finite");
     gu_tabular_drop_carry(h);
     // under fruit a table has a row per (cell, mask): S << F of them (gu_set_fruit), which ten fruits multiply by 1024
-    GU_REQUIRE(h->n_fruit <= 10, GU_ERR_INVALID, "%d fruits: gu_td_init learns on S << F rows and takes at most 10 fruits", h->n_fruit);
-    GU_REQUIRE(GU_TD_ROWS(h) <= 0x7FFFFFFF, GU_ERR_INVALID, "%d states x 2^%d masks: more than 2^31 - 1 rows", h->S, h->n_fruit + h->n_doors);
+    GU_REQUIRE(h->overlay_bits <= 10, GU_ERR_INVALID, "%d fruits: gu_td_init learns on S << F rows and takes at most 10 fruits", h->overlay_bits);
+    GU_REQUIRE(GU_TD_ROWS(h) <= 0x7FFFFFFF, GU_ERR_INVALID, "%d states x 2^%d masks: more than 2^31 - 1 rows", h->S, h->overlay_bits);
     const int32_t rows = (int32_t)GU_TD_ROWS(h);
     const size_t bytes = (size_t)h->N * (size_t)rows * 4 * sizeof(double);
     if (!h->d_q || h->td_S != rows) {

@@ -146,9 +146,7 @@ int gu_trail_enable(gu_handle h, int32_t capacity)
     int rc = gu_use_device(h);
     if (rc != GU_OK) return rc;
     GU_REQUIRE(capacity >= 0 && capacity <= 500, GU_ERR_INVALID, "trail capacity %d outside 0 .. 500 (env:92 keeps 500 states)", capacity);
-    GU_REQUIRE(!(capacity && h->d_wind_cell), GU_ERR_UNSUPPORTED, "the agent trail and wind exclude each other: the engine has wind set (gu_set_wind; NULL calms it again)");
-    GU_REQUIRE(!(capacity && h->n_fruit), GU_ERR_UNSUPPORTED, "the agent trail and fruit exclude each other: the engine has fruit set (gu_set_fruit; NULL takes it away again)");
-    GU_REQUIRE(!(capacity && h->n_doors), GU_ERR_UNSUPPORTED, "the agent trail and doors exclude each other: the engine has doors set (gu_set_doors; NULL takes them away again)");
+    GU_REQUIRE(!(capacity && h->overlay), GU_ERR_UNSUPPORTED, "the agent trail and %s exclude each other: %s", GU_OVERLAY_NAME[h->overlay], GU_OVERLAY_IS_SET[h->overlay]);
     GU_HIP(hipStreamSynchronize(h->stream));
     gu_trail_free(h);
     if (h->graph_exec) {  // a captured step graph does not carry the trail kernels (or carries them although the trail is off now)

@@ -884,9 +884,7 @@ int gu_vi_get(gu_handle h, double *v, double *pi)
 int gu_vi_sweep(gu_handle h, double gamma, int32_t iters, int32_t greedy_update, double *deltas)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_vi_sweep");
-    GU_NO_FRUIT(h, "gu_vi_sweep");
-    GU_NO_DOORS(h, "gu_vi_sweep");
+    GU_NO_OVERLAY(h, "gu_vi_sweep");
     vi_withdraw_host_tables(h);
     GU_NEED_VI(h);
     GU_REQUIRE(iters > 0 && iters <= 4096, GU_ERR_INVALID, "iters must be in 1..4096 per call");
@@ -918,9 +916,7 @@ int gu_vi_sweep(gu_handle h, double gamma, int32_t iters, int32_t greedy_update,
 int gu_vi_run(gu_handle h, double gamma, double threshold, int32_t max_steps, int32_t *steps_done, double *deltas)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_vi_run");
-    GU_NO_FRUIT(h, "gu_vi_run");
-    GU_NO_DOORS(h, "gu_vi_run");
+    GU_NO_OVERLAY(h, "gu_vi_run");
     vi_withdraw_host_tables(h);
     GU_NEED_VI(h);
     GU_REQUIRE(max_steps >= 0 && steps_done, GU_ERR_INVALID, "max_steps < 0 or steps_done is NULL");
@@ -975,9 +971,7 @@ int gu_vi_run(gu_handle h, double gamma, double threshold, int32_t max_steps, in
 int gu_vi_eval_run(gu_handle h, double gamma, double threshold, int32_t max_steps, int32_t *steps_done, double *deltas)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_vi_eval_run");
-    GU_NO_FRUIT(h, "gu_vi_eval_run");
-    GU_NO_DOORS(h, "gu_vi_eval_run");
+    GU_NO_OVERLAY(h, "gu_vi_eval_run");
     vi_withdraw_host_tables(h);
     GU_NEED_VI(h);
     GU_REQUIRE(max_steps >= 0 && steps_done, GU_ERR_INVALID, "max_steps < 0 or steps_done is NULL");
@@ -1030,9 +1024,7 @@ int gu_vi_eval_run(gu_handle h, double gamma, double threshold, int32_t max_step
 int gu_vi_greedy(gu_handle h, double gamma)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_vi_greedy");
-    GU_NO_FRUIT(h, "gu_vi_greedy");
-    GU_NO_DOORS(h, "gu_vi_greedy");
+    GU_NO_OVERLAY(h, "gu_vi_greedy");
     vi_withdraw_host_tables(h);
     GU_NEED_VI(h);
     ViArgs a = vi_args(h, gamma, nullptr);
@@ -1047,9 +1039,7 @@ int gu_vi_greedy(gu_handle h, double gamma)
 int gu_vi_sweep_step(gu_handle h, double gamma, uint32_t flags, double *delta)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_vi_sweep_step");
-    GU_NO_FRUIT(h, "gu_vi_sweep_step");
-    GU_NO_DOORS(h, "gu_vi_sweep_step");
+    GU_NO_OVERLAY(h, "gu_vi_sweep_step");
     vi_withdraw_host_tables(h);
     h->entry_table_ok = false;  // (the fused launches step the envs: their state is consistent too, but only rollouts vouch for it)
     GU_NEED_VI(h);
@@ -1076,9 +1066,7 @@ int gu_vi_sweep_step(gu_handle h, double gamma, uint32_t flags, double *delta)
 int gu_vi_sweep_step_run(gu_handle h, double gamma, int32_t iters, uint32_t flags, double *deltas)
 {
     GU_ENTER(h);
-    GU_NO_WIND(h, "gu_vi_sweep_step_run");
-    GU_NO_FRUIT(h, "gu_vi_sweep_step_run");
-    GU_NO_DOORS(h, "gu_vi_sweep_step_run");
+    GU_NO_OVERLAY(h, "gu_vi_sweep_step_run");
     vi_withdraw_host_tables(h);
     h->entry_table_ok = false;
     GU_NEED_VI(h);

@@ -98,8 +98,7 @@ class Engine(object):
                                    ptr(p['lava']), ptr(p['rplus']), ptr(p['rminus']), ptr(starts), len(starts)))
         self.spec = spec
         self._n_grids = 1
-        self._n_fruit = 0  # (a new grid drops the fruit)
-        self._n_doors = 0  # (... and the doors)
+        self._mask_bits = 0  # (a new grid drops the fruit or the doors)
 
     def set_grids(self, specs):
         """Several distinct grids of one shape: env e uses specs[e // (N // len(specs))]."""
@@ -121,8 +120,7 @@ class Engine(object):
         self.spec = specs[0]
         self.specs = list(specs)
         self._n_grids = len(specs)
-        self._n_fruit = 0
-        self._n_doors = 0
+        self._mask_bits = 0
 
     def generate_mazes(self, n_grids, W, H, maze_seed):
         """n_grids random mazes carved on the device (one per env group of N // n_grids envs)."""
@@ -130,8 +128,7 @@ class Engine(object):
         self.spec = GridSpec(W, H, [0], [W * H - 1], [], [])  # shape holder; the real grids live on the device
         self.specs = None
         self._n_grids = int(n_grids)
-        self._n_fruit = 0
-        self._n_doors = 0
+        self._mask_bits = 0
 
     def get_cells(self, grid_index=0):
         """(flags uint8[S], reward int8[S], starts int32[n]) of one grid as compiled on the device."""
@@ -162,7 +159,7 @@ class Engine(object):
         f = None if fruit is None else _lib.as_array(fruit, np.uint8, (self.spec.S,), 'fruit')
         v = _lib.as_array(values, np.int32, (3,), 'values')
         check(self.lib.gu_set_fruit(self._h, ptr(f), ptr(v)))
-        self._n_fruit = 0 if f is None else int(np.count_nonzero(f))
+        self._mask_bits = 0 if f is None else int(np.count_nonzero(f))
 
     def get_fruit(self):
         """(fruit uint8[S], values int32[3]), or None while no fruit is set (gu_get_fruit)."""
@@ -171,24 +168,30 @@ class Engine(object):
         check(self.lib.gu_get_fruit(self._h, ptr(fruit), ptr(values), ctypes.byref(n)))
         return (fruit, values) if n.value else None
 
+    def _get_masks(self, getter, env0, n):
+        env0, n, n0 = self._env_range(env0, n)
+        masks = np.empty(n0, np.uint32)
+        check(getter(self._h, env0, n, ptr(masks)))
+        return masks
+
+    def _set_masks(self, setter, masks, env0, name):
+        m = _lib.as_array(masks, np.uint32, None, name)
+        check(setter(self._h, int(env0), m.size, ptr(m)))
+
     def get_fruit_state(self, env0=0, n=None):
         """uint32[n]: the masks of eaten fruit (bit = slot) of envs env0 .. env0+n-1 (gu_get_fruit_state)."""
-        env0, n, n0 = self._env_range(env0, n)
-        eaten = np.empty(n0, np.uint32)
-        check(self.lib.gu_get_fruit_state(self._h, env0, n, ptr(eaten)))
-        return eaten
+        return self._get_masks(self.lib.gu_get_fruit_state, env0, n)
 
     def set_fruit_state(self, eaten, env0=0):
         """Install the masks uint32[n] of envs env0 .. env0+n-1 (gu_set_fruit_state)."""
-        e = _lib.as_array(eaten, np.uint32, None, 'eaten')
-        check(self.lib.gu_set_fruit_state(self._h, int(env0), e.size, ptr(e)))
+        self._set_masks(self.lib.gu_set_fruit_state, eaten, env0, 'eaten')
 
     def set_doors(self, door):
         """Install the door plane uint8[S] (grid.door_plane); None takes the doors away again (gu_set_doors).  Clears every env's
         mask of open slots."""
         d = None if door is None else _lib.as_array(door, np.uint8, (self.spec.S,), 'door')
         check(self.lib.gu_set_doors(self._h, ptr(d)))
-        self._n_doors = 0 if d is None else int(np.unique(d[d != 0] & 7).size)
+        self._mask_bits = 0 if d is None else int(np.unique(d[d != 0] & 7).size)
 
     def get_doors(self):
         """door uint8[S], or None while no doors are set (gu_get_doors)."""
@@ -199,21 +202,17 @@ class Engine(object):
 
     def get_doors_state(self, env0=0, n=None):
         """uint32[n]: the masks of open slots (bit = slot) of envs env0 .. env0+n-1 (gu_get_doors_state)."""
-        env0, n, n0 = self._env_range(env0, n)
-        mask = np.empty(n0, np.uint32)
-        check(self.lib.gu_get_doors_state(self._h, env0, n, ptr(mask)))
-        return mask
+        return self._get_masks(self.lib.gu_get_doors_state, env0, n)
 
     def set_doors_state(self, mask, env0=0):
         """Install the masks uint32[n] of envs env0 .. env0+n-1 (gu_set_doors_state)."""
-        m = _lib.as_array(mask, np.uint32, None, 'mask')
-        check(self.lib.gu_set_doors_state(self._h, int(env0), m.size, ptr(m)))
+        self._set_masks(self.lib.gu_set_doors_state, mask, env0, 'mask')
 
     @property
     def td_rows(self):
         """Rows of one env's Q table: S, or S << F while F fruits are set (include/gu.h: gu_set_fruit), or S << D while doors with
         D slots are set (gu_set_doors)."""
-        return self.spec.S << (self._n_fruit + self._n_doors)
+        return self.spec.S << self._mask_bits
 
     def seed(self, seed):
         self.seed_value = int(seed) & 0xFFFFFFFFFFFFFFFF

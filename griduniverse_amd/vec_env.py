@@ -32,6 +32,14 @@ def check_off_policy_args(max_episode_len, epsilon, w_cap):
         raise ValueError('w_cap must lie in [1, 2**256]')
 
 
+def _masks(masks, bits, message):
+    """uint32[n] from masks (or one number) of `bits` bits each, as set_fruit_eaten and set_doors_open take them (ValueError)."""
+    m = np.atleast_1d(np.asarray(masks))
+    if m.ndim != 1 or m.dtype == bool or not np.issubdtype(m.dtype, np.integer) or (m.size and (m.min() < 0 or m.max() >> max(bits, 1) != 0)):
+        raise ValueError(message.format(bits))
+    return m.astype(np.uint32)
+
+
 class VecGridUniverse(object):
     _n_fruit = 0  # fruits set (set_fruit): the Q tables have S << F rows
     _n_doors = 0  # door slots set (set_doors): the Q tables have S << D rows
@@ -195,10 +203,7 @@ class VecGridUniverse(object):
 
     def set_fruit_eaten(self, eaten, env0=0):
         """Install masks uint32[n] (or one number) for envs env0 ..; no bit at or above the number of fruits."""
-        e = np.atleast_1d(np.asarray(eaten))
-        if e.ndim != 1 or e.dtype == bool or not np.issubdtype(e.dtype, np.integer) or (e.size and (e.min() < 0 or e.max() >> max(self._n_fruit, 1) != 0)):
-            raise ValueError('eaten must hold masks of the {} fruits set'.format(self._n_fruit))
-        self.engine.set_fruit_state(e.astype(np.uint32), env0)
+        self.engine.set_fruit_state(_masks(eaten, self._n_fruit, 'eaten must hold masks of the {} fruits set'), env0)
 
     def set_doors(self, doors, keys=None, levers=None):
         """Doors, keys and levers on the engine's grid (single-grid engines; include/gu.h: gu_set_doors): a door of slot k refuses
@@ -243,10 +248,7 @@ class VecGridUniverse(object):
 
     def set_doors_open(self, mask, env0=0):
         """Install masks uint32[n] (or one number) for envs env0 ..; no bit at or above the number of slots in use."""
-        m = np.atleast_1d(np.asarray(mask))
-        if m.ndim != 1 or m.dtype == bool or not np.issubdtype(m.dtype, np.integer) or (m.size and (m.min() < 0 or m.max() >> max(self._n_doors, 1) != 0)):
-            raise ValueError('mask must hold masks of the {} door slots set'.format(self._n_doors))
-        self.engine.set_doors_state(m.astype(np.uint32), env0)
+        self.engine.set_doors_state(_masks(mask, self._n_doors, 'mask must hold masks of the {} door slots set'), env0)
 
     def _ensure_q(self, q0=None):
         """Q tables on the engine: tables of zeros on first use; every entry q0 (again) when q0 is given."""

@@ -23,7 +23,6 @@ int main()
     enum { N, W, H, GRIDS, MULTI_START, POLICY, FLAGS, T, WIND, GUST, TRAIL, STRADDLE, ENTRY, OPT0, COLUMNS = OPT0 + sizeof option / sizeof option[0] };
     long long n_cu = 0, lds_per_cu = 0, v[COLUMNS];
     if (scanf("%lld %lld", &n_cu, &lds_per_cu) != 2) return 2;
-    uint8_t wind_plane = 0;  // (the plan only asks whether there is one)
     for (;;) {
         for (int i = 0; i < COLUMNS; ++i)
             if (scanf("%lld", &v[i]) != 1) return i == 0 ? 0 : 2;
@@ -38,8 +37,8 @@ int main()
         h.n_grids = (int32_t)v[GRIDS];
         h.group = h.N / h.n_grids;
         h.all_single_start = v[MULTI_START] == 0;
-        h.d_wind_cell = v[WIND] ? &wind_plane : nullptr;
-        h.gust_q16 = v[GUST] ? 43691u : 0u;
+        h.overlay = v[WIND] ? GU_OVERLAY_WIND : GU_OVERLAY_NONE;
+        h.overlay_param = v[GUST] ? 43691u : 0u;
         h.trail_cap = v[TRAIL] ? 8 : 0;
         h.entry_table_ok = v[ENTRY] != 0;
         for (int i = 0; i < COLUMNS - OPT0; ++i) h.opt[option[i]] = v[OPT0 + i];

@@ -102,7 +102,7 @@ def test_library_exports_the_door_entry_points_and_kernels():
         assert ' T ' + name + '\n' in syms, name
         assert name in _lib.SIGNATURES
     blob = open(_lib.LIB_PATH, 'rb').read()
-    assert b'gu_doors_step_kernel' in blob and b'gu_doors_rollout_kernel' in blob and b'gu_doors_reset_kernel' in blob
+    assert b'gu_doors_step_kernel' in blob and b'gu_doors_rollout_kernel' in blob and b'gu_overlay_reset_kernel' in blob
     assert gua.Engine.ROLLOUT_FAMILIES[6] == 'doors'
 
 

@@ -152,7 +152,7 @@ def test_library_exports_the_fruit_entry_points_and_kernels():
         assert ' T ' + name + '\n' in syms, name
         assert name in _lib.SIGNATURES
     blob = open(_lib.LIB_PATH, 'rb').read()
-    assert b'gu_fruit_step_kernel' in blob and b'gu_fruit_rollout_kernel' in blob and b'gu_fruit_reset_kernel' in blob
+    assert b'gu_fruit_step_kernel' in blob and b'gu_fruit_rollout_kernel' in blob and b'gu_overlay_reset_kernel' in blob
     assert gua.Engine.ROLLOUT_FAMILIES[5] == 'fruit'
 
 
