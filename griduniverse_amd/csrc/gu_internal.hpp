@@ -33,12 +33,16 @@
 // the store wins for the last lanes of every row of sixteen.  The compiler pads that hazard only for stores WITHOUT a scalar offset
 // (the rule of earlier chips); on gfx950 it bites with one too -- wrong first words of 12-byte rows in lanes 12 .. 15 of every
 // sixteen (tools/triples_race.py, profiles/r06t_triples_race.txt: every workgroup size but one).  Two wait states behind such a store.
+// tests/test_gpu_wide_stores.py runs both store sites against the C oracle at every workgroup size, map and wave shape; a build with
+// the pad defined away (make variant VARIANT=_nopad EXTRA="-D'GU_WIDE_STORE_PAD()='") is how that file is shown to see the hazard.
+#ifndef GU_WIDE_STORE_PAD
 #define GU_WIDE_STORE_PAD()                         \
     do {                                            \
         __builtin_amdgcn_sched_barrier(0);          \
         asm volatile("s_nop 1" ::: "memory");       \
         __builtin_amdgcn_sched_barrier(0);          \
     } while (0)
+#endif
 #define GU_ACTION_OK(raw) ((uint32_t)((int32_t)(raw) + 4) < 8u)
 #define GU_CELL_WALL 0x80u  /* the cell itself is a wall (only the path search needs it: wall nodes have no edges) */
 

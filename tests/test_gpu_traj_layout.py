@@ -1,7 +1,9 @@
 """The int32 trajectory's DEVICE layout (option traj_layout): three planes [T][N], or one plane of (obs, reward, done) triples
 [T][N][3] written with one 12-byte store per lane and step.  What a caller sees -- gu_read_trajectory, gu_mc_evaluate, the engine's
 state and statistics -- is the same bytes under both, on both rollout kernels, for every policy kind; the default (-1) takes the
-triples only where they are faster (small batches under the uniform policy, together with the pair tables)."""
+triples only where they are faster (small batches under the uniform policy, together with the pair tables).
+Everything here runs at the default workgroup of 256; the triples' 12-byte stores at the other workgroup sizes, maps and wave shapes
+(half waves, per-wave staging, held rows) live in tests/test_gpu_wide_stores.py, against the oracle."""
 import numpy as np
 import pytest
 
