@@ -28,6 +28,16 @@ GRIDS = {
 }
 
 
+def spread_grid(W, H):
+    """A grid for test_gpu_learners_at_scale.py (never one of GRIDS: those run at N = 4096): three starts, at the top, in the middle
+    and at the bottom of the index range, a goal two cells to the side of each, a lava cell in the row above the top start and in the
+    row below the middle one (above it where that is the last row; a single row: two cells to the other side of it) and two walls."""
+    S = W * H
+    mid = S // 2 + 7
+    lava = [S - 1 - W, mid + W if mid + W < S else mid - W] if H > 1 else [mid - 2]
+    return dict(W=W, H=H, starts=[S - 1, mid, 0], goals=[S - 3, mid + 2, 2], lava=lava, walls=[5, S - 7])
+
+
 def _spec(g):
     return GridSpec(g['W'], g['H'], g['starts'], g['goals'], g['lava'], g['walls'], g.get('reward'))
 
