@@ -108,6 +108,11 @@ SIGNATURES = {
     'gu_td_run': [_vp, _i64, _i32, _f64, _f64, _u32, _u32],
     'gu_td_get_q': [_vp, _i64, _i64, _vp],
     'gu_td_set_q': [_vp, _i64, _i64, _vp],
+    'gu_esarsa_run': [_vp, _i64, _f64, _f64, _u32, _u32],
+    'gu_double_init': [_vp, _f64],
+    'gu_double_run': [_vp, _i64, _f64, _f64, _u32, _u32],
+    'gu_double_get_q': [_vp, _i64, _i64, _vp],
+    'gu_double_set_q': [_vp, _i64, _i64, _vp],
     'gu_dyna_init': [_vp],
     'gu_dyna_run': [_vp, _i64, _i32, _f64, _f64, _u32, _u32],
     'gu_dyna_get_model': [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp],

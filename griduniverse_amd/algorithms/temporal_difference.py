@@ -9,7 +9,9 @@ own state is left alone.  `greedy_policy` turns a learned table into the referen
 
 `n_step_sarsa` / `n_step_q_learning` are the n-step variations (Sutton & Barto ch. 7; include/gu.h, gu_nstep_run), on the same
 tables, by csrc/gu_nstep.hip.  `sarsa_lambda` / `watkins_q_lambda` are the eligibility-trace variations (Sutton & Barto ch. 12;
-include/gu.h, gu_lambda_run), on the same tables, by csrc/gu_lambda.hip.
+include/gu.h, gu_lambda_run), on the same tables, by csrc/gu_lambda.hip.  `expected_sarsa` (Sutton & Barto 6.6; gu_esarsa_run) is a
+third rule of csrc/gu_td.hip on the same tables; `double_q_learning` (6.7; gu_double_run) keeps two tables per learner, by
+csrc/gu_double.hip.
 """
 import numpy as np
 
@@ -19,12 +21,13 @@ from ..vec_env import VecGridUniverse
 _CHUNK = 100000  # steps per launch (the launch limit is 1e8; shorter launches keep the device responsive)
 
 
-def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, wind=None, gust=0.0, fruit=None, doors=None):
+def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, wind=None, gust=0.0, fruit=None, doors=None, pairs=False):
     """The learner batch of q_learning / sarsa / n_step_* / *_lambda / dyna_q: L learners on the grid of `env`, tables of q0 (and empty models when
     `model`), `num_steps` real steps each in launches `launch(vec, T)` of at most `chunk` steps.  Returns Q [S][4] or [L][S][4].
     `wind`: a strength array or a (strength, direction) pair for VecGridUniverse.set_wind, with `gust`.  `fruit`: (cells, kinds,
     values) for VecGridUniverse.set_fruit; the tables then have S << F rows.  `doors`: dict(doors=, keys=, levers=) for
-    VecGridUniverse.set_doors; the tables then have S << D rows."""
+    VecGridUniverse.set_doors; the tables then have S << D rows.  `pairs`: the learner is Double Q-learning -- pairs of tables of q0, and
+    the result is [S][2][4] or [L][S][2][4]."""
     L = int(num_learners)
     vec = VecGridUniverse(L, template=env, seed=seed)
     try:
@@ -35,7 +38,10 @@ def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, w
             vec.set_fruit(*fruit)
         if doors is not None:
             vec.set_doors(doors['doors'], doors.get('keys'), doors.get('levers'))
-        vec._ensure_q(q0)
+        if pairs:
+            vec._ensure_pairs(q0)
+        else:
+            vec._ensure_q(q0)
         if model:
             vec._ensure_model()
         vec.reset()
@@ -44,7 +50,7 @@ def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, w
             T = min(left, chunk)
             launch(vec, T)
             left -= T
-        q = vec.q_table()
+        q = vec.double_q_tables() if pairs else vec.q_table()
     finally:
         vec.close()
     return q[0] if L == 1 else q
@@ -84,6 +90,32 @@ def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num
 def sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None):
     """Epsilon-greedy SARSA; arguments and result as `q_learning`."""
     return _td('sarsa', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit, doors)
+
+
+def expected_sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):
+    """Epsilon-greedy Expected SARSA (Sutton & Barto 6.6): acts as `q_learning` does and bootstraps on the mean of Q[s'] under the
+    epsilon-greedy policy itself, so the target has no sampling noise from the next action.  `num_steps` env steps per learner.
+    Returns Q float64[S][4], or [L][S][4] for L = num_learners > 1.  With epsilon = 0 it is `q_learning`.  The calm grid only."""
+    if int(num_learners) < 1:
+        raise ValueError('num_learners must be at least 1')
+    if not 0.0 <= float(epsilon) <= 1.0:
+        raise ValueError('epsilon must lie in [0, 1]')
+    return _learn(env, num_learners, seed, q0, num_steps, _CHUNK,
+                  lambda vec, T: vec.expected_sarsa_run(T, alpha, discount_factor, epsilon))
+
+
+def double_q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):
+    """Epsilon-greedy Double Q-learning (Sutton & Barto 6.7): two tables A and B per learner, both filled with q0; the learner acts
+    on A + B, and a coin per step picks the table that learns from the other's estimate of its own greedy action.  `num_steps` env
+    steps per learner.  Returns the MEAN of the two tables, (A + B) * 0.5, float64[S][4], or [L][S][4] for L = num_learners > 1
+    (VecGridUniverse.double_q_tables gives the two apart).  The calm grid only."""
+    if int(num_learners) < 1:
+        raise ValueError('num_learners must be at least 1')
+    if not 0.0 <= float(epsilon) <= 1.0:
+        raise ValueError('epsilon must lie in [0, 1]')
+    q = _learn(env, num_learners, seed, q0, num_steps, _CHUNK,
+               lambda vec, T: vec.double_q_run(T, alpha, discount_factor, epsilon), pairs=True)
+    return (q[..., 0, :] + q[..., 1, :]) * 0.5
 
 
 def _nstep(method, env, num_steps, n, alpha, discount_factor, epsilon, num_learners, seed, q0):

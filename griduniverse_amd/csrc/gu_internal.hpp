@@ -335,6 +335,9 @@ struct gu_engine {
     int32_t explore_S = 0;             // states of the counts (0: none allocated); a grid of another size drops them
     double *d_explore_tab = nullptr;   // U[explore_C] | B[explore_C], shared by all envs (gu_explore_set_tables)
     int32_t explore_C = 0;             // entries of each (0: no tables yet)
+    // batched Double Q-learning (gu_double.hip): off until gu_double_init; a pair of tables of its own, not d_q
+    double *d_dq = nullptr;            // [N][dq_S][2][4] the A row and the B row of a state side by side: one aligned 64-byte piece
+    int32_t dq_S = 0;                  // states of the pairs (0: none allocated); a grid of another size drops them
     // batched Monte-Carlo tree search (gu_mcts.hip): off until gu_mcts_init; decides and learns on d_q; dropped with the tables
     uint8_t *d_mcts_pool = nullptr;    // [N][mcts_P] nodes of 64 bytes: w[4] float64 | visits[4] uint32 | child[4] int32
     int32_t *d_mcts_meta = nullptr;    // [N][mcts_P][2] (state, parent * 4 + action; -1 for the root)
@@ -511,6 +514,7 @@ void gu_lambda_free(gu_engine *h);
 void gu_search_free(gu_engine *h);
 void gu_explore_free(gu_engine *h);    // (the visit counts; the U and B tables stay)
 void gu_mcts_free(gu_engine *h);       // (the node pools; the U, B and I tables stay)
+void gu_double_free(gu_engine *h);
 void gu_is_free(gu_engine *h);
 void gu_ac_free(gu_engine *h);         // (takes gu_reinforce_free along: REINFORCE learns into the actor-critic tables)
 void gu_reinforce_free(gu_engine *h);

@@ -1,7 +1,9 @@
-// gu_td.hip -- batched tabular Q-learning and SARSA for gfx950 (include/gu.h: gu_td_run; restated on the CPU by
-// tests/_td_oracle.py).  The lane, the Q-row rules, the layout and the rounding are gu_tabular.hpp's; what is here is the update
-// rule: Q-learning bootstraps on max_a Q[s'][a], SARSA draws its next action a' from Q[s'] with the next stream-4 word (unless s'
-// is terminal), bootstraps on Q[s'][a'] and takes a' in the next step -- across launches too, through next_a.
+// gu_td.hip -- batched tabular Q-learning, SARSA and Expected SARSA for gfx950 (include/gu.h: gu_td_run, gu_esarsa_run; restated on
+// the CPU by tests/_td_oracle.py and tests/_double_oracle.py).  The lane, the Q-row rules, the layout and the rounding are
+// gu_tabular.hpp's; what is here is the update rule: Q-learning bootstraps on max_a Q[s'][a], SARSA draws its next action a' from
+// Q[s'] with the next stream-4 word (unless s' is terminal), bootstraps on Q[s'][a'] and takes a' in the next step -- across launches
+// too, through next_a.  Expected SARSA acts as Q-learning does and bootstraps on the mean of Q[s'] under the epsilon-greedy policy:
+// pe * (the row's sum) + pg * (its maximum), pe = eps / 4 and pg = 1 - eps from the host -- no division, whatever the number of ties.
 #include "gu_tabular.hpp"
 
 #include <algorithm>
@@ -14,14 +16,18 @@ struct TdArgs : TabArgs {
     uint32_t fruit_values;
     int32_t rows;
     uint32_t *eaten;  // (the door instantiations, gu_set_doors: the envs' masks of open slots, and rows = S << D)
+    double pe, pg;    // TD_ESARSA: eps_q16 * 2^-18 and (65536 - eps_q16) * 2^-16, both exact
 };
+
+enum TdRule { TD_Q = 0, TD_SARSA = 1, TD_ESARSA = 2 };  // (the first two are gu_td_run's method numbers)
 
 // WIND: 0 = calm, 1 = wind without gusts (no stream-9 hash in the code), 2 = with gusts (gu_tabular.hpp: TabLane)
 // FRUIT: the table has S << F rows and the lane learns on row eaten * S + s (TabLane); never together with WIND
 // DOORS: the table has S << D rows and the lane learns on row open * S + s; never together with WIND or FRUIT
-template <bool SARSA, bool LDS, int WIND = 0, bool FRUIT = false, bool DOORS = false>
+template <TdRule RULE, bool LDS, int WIND = 0, bool FRUIT = false, bool DOORS = false>
 __global__ void __launch_bounds__(GU_BLOCK) gu_td_kernel(const TdArgs a)
 {
+    constexpr bool SARSA = RULE == TD_SARSA;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     TabLane<LDS, true, WIND, FRUIT, DOORS> L(a, smem);
     if (WIND == 2) L.gust_q16 = a.gust_q16;
@@ -44,6 +50,9 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_td_kernel(const TdArgs a)
                     a2 = (int32_t)gu_q_action(n, L.word(), a.eps_q16);
                     mval = gu_q_get(n, (uint32_t)a2);
                 }
+            } else if (RULE == TD_ESARSA) {
+                const double sum = __dadd_rn(__dadd_rn(__dadd_rn(n.v0, n.v1), n.v2), n.v3);
+                mval = __dadd_rn(__dmul_rn(a.pe, sum), __dmul_rn(a.pg, gu_q_max(n)));
             } else {
                 mval = gu_q_max(n);
             }
@@ -82,23 +91,26 @@ static int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, d
     // the overlay's instantiations, on [flags | reward | overlay]; fruit and doors learn on S << bits rows and keep the env's mask in `eaten`
     a.gust_q16 = a.fruit_values = h->overlay_param, a.rows = h->td_S, a.eaten = h->d_overlay_mask;
     if (h->overlay) a.cell = h->d_overlay_cell;
+    a.pe = (double)eps_q16 * 0x1p-18, a.pg = (double)(65536u - eps_q16) * 0x1p-16;
     int rc;
-    if (h->overlay == GU_OVERLAY_DOORS) {
-        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 0, false, true>, gu_td_kernel<true, false, 0, false, true>, a, GU_BLOCK, 0, 3)
-                         : gu_tabular_launch(h, gu_td_kernel<false, true, 0, false, true>, gu_td_kernel<false, false, 0, false, true>, a, GU_BLOCK, 0, 3);
+    if (method == TD_ESARSA) {  // (calm only: gu_esarsa_run refuses while an overlay is set)
+        rc = gu_tabular_launch(h, gu_td_kernel<TD_ESARSA, true>, gu_td_kernel<TD_ESARSA, false>, a);
+    } else if (h->overlay == GU_OVERLAY_DOORS) {
+        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 0, false, true>, gu_td_kernel<TD_SARSA, false, 0, false, true>, a, GU_BLOCK, 0, 3)
+                         : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 0, false, true>, gu_td_kernel<TD_Q, false, 0, false, true>, a, GU_BLOCK, 0, 3);
     } else if (h->overlay == GU_OVERLAY_FRUIT) {
-        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 0, true>, gu_td_kernel<true, false, 0, true>, a, GU_BLOCK, 0, 3)
-                         : gu_tabular_launch(h, gu_td_kernel<false, true, 0, true>, gu_td_kernel<false, false, 0, true>, a, GU_BLOCK, 0, 3);
+        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 0, true>, gu_td_kernel<TD_SARSA, false, 0, true>, a, GU_BLOCK, 0, 3)
+                         : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 0, true>, gu_td_kernel<TD_Q, false, 0, true>, a, GU_BLOCK, 0, 3);
     } else if (h->overlay == GU_OVERLAY_WIND) {
         if (h->overlay_param)  // (gusts)
-            rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 2>, gu_td_kernel<true, false, 2>, a, GU_BLOCK, 0, 3)
-                             : gu_tabular_launch(h, gu_td_kernel<false, true, 2>, gu_td_kernel<false, false, 2>, a, GU_BLOCK, 0, 3);
+            rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 2>, gu_td_kernel<TD_SARSA, false, 2>, a, GU_BLOCK, 0, 3)
+                             : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 2>, gu_td_kernel<TD_Q, false, 2>, a, GU_BLOCK, 0, 3);
         else
-            rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true, 1>, gu_td_kernel<true, false, 1>, a, GU_BLOCK, 0, 3)
-                             : gu_tabular_launch(h, gu_td_kernel<false, true, 1>, gu_td_kernel<false, false, 1>, a, GU_BLOCK, 0, 3);
+            rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 1>, gu_td_kernel<TD_SARSA, false, 1>, a, GU_BLOCK, 0, 3)
+                             : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 1>, gu_td_kernel<TD_Q, false, 1>, a, GU_BLOCK, 0, 3);
     } else {
-        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<true, true>, gu_td_kernel<true, false>, a)
-                         : gu_tabular_launch(h, gu_td_kernel<false, true>, gu_td_kernel<false, false>, a);
+        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true>, gu_td_kernel<TD_SARSA, false>, a)
+                         : gu_tabular_launch(h, gu_td_kernel<TD_Q, true>, gu_td_kernel<TD_Q, false>, a);
     }
     return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, method == 1);
 }
@@ -131,6 +143,7 @@ void gu_learners_drop(gu_engine *h, int32_t S)
     }
     if (all || (h->is_S && h->is_S != S)) gu_is_free(h);  // ... and the cumulative weights: gu_is_init again
     if (all || (h->explore_S && h->explore_S != S)) gu_explore_free(h);  // ... and the visit counts: gu_explore_init again
+    if (all || (h->dq_S && h->dq_S != S)) gu_double_free(h);  // ... and the pairs of Double Q-learning: gu_double_init again
     if (all || (h->dyna_S && h->dyna_S != S)) gu_dyna_free(h);  // ... and so does a Dyna-Q model: gu_dyna_init again
     if (all || (h->ac_S && h->ac_S != S)) gu_ac_free(h);  // ... and actor-critic tables (with the REINFORCE buffers): gu_ac_init again
     if (all || (h->fa_S && h->fa_S != S)) gu_fa_free(h);  // ... and features and weights: gu_fa_init again
@@ -178,6 +191,17 @@ int gu_td_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma
     int rc = gu_tabular_check(h, "gu_td_run", T, -1, eps_q16, alpha, gamma, flags);
     if (rc != GU_OK || T == 0) return rc;
     return gu_launch_td(h, T, method, alpha, gamma, eps_q16, flags);
+}
+
+int gu_esarsa_run(gu_handle h, int64_t T, double alpha, double gamma, uint32_t eps_q16, uint32_t flags)
+{
+    GU_ENTER(h);
+    GU_NO_OVERLAY(h, "gu_esarsa_run");
+    GU_NEED_GRID(h);
+    GU_NEED_Q(h);
+    int rc = gu_tabular_check(h, "gu_esarsa_run", T, -1, eps_q16, alpha, gamma, flags);
+    if (rc != GU_OK || T == 0) return rc;
+    return gu_launch_td(h, T, TD_ESARSA, alpha, gamma, eps_q16, flags);
 }
 
 static int gu_td_range(gu_engine *h, int64_t env0, int64_t n, const void *q)

@@ -445,6 +445,32 @@ class Engine(object):
         q = _tables(q, (self.td_rows, 4), 'q')
         check(self.lib.gu_td_set_q(self._h, int(env0), q.shape[0], ptr(q)))
 
+    # ------------------------------------------------------------------ Expected SARSA and Double Q-learning (include/gu.h: gu_esarsa_run, gu_double_*)
+    def esarsa_run(self, T, alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
+        """T Expected SARSA iterations per env in one launch on the td_init tables: acts as Q-learning does, bootstraps on the mean of
+        Q[s'] under the epsilon-greedy policy."""
+        check(self.lib.gu_esarsa_run(self._h, int(T), float(alpha), float(gamma), int(eps_q16), _learner_flags(trajectory, stats)))
+
+    def double_init(self, q0=0.0):
+        """A pair of float64 tables [S][2][4] per env (storage of its own, not the td_init tables), every entry q0."""
+        check(self.lib.gu_double_init(self._h, float(q0)))
+
+    def double_run(self, T, alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
+        """T Double Q-learning iterations per env in one launch: epsilon-greedy on A + B, a coin per step picks the table that learns."""
+        check(self.lib.gu_double_run(self._h, int(T), float(alpha), float(gamma), int(eps_q16), _learner_flags(trajectory, stats)))
+
+    def double_get_q(self, env0=0, n=None):
+        """float64[n, S, 2, 4]: the pairs of envs env0 .. env0+n-1 (all from env0 when n is None); [:, :, 0] is A, [:, :, 1] is B."""
+        env0, n, n0 = self._env_range(env0, n)
+        q = np.empty((n0, self.spec.S, 2, 4), np.float64)
+        check(self.lib.gu_double_get_q(self._h, env0, n, ptr(q)))
+        return q
+
+    def double_set_q(self, q, env0=0):
+        """Install pairs float64[n, S, 2, 4] (or [S, 2, 4] for one env) for envs env0 .. env0+n-1."""
+        q = _tables(q, (self.spec.S, 2, 4), 'q')
+        check(self.lib.gu_double_set_q(self._h, int(env0), q.shape[0], ptr(q)))
+
     # ------------------------------------------------------------------ tabular Dyna-Q (include/gu.h: gu_dyna_*)
     def dyna_init(self):
         """A cleared Dyna-Q model per env (count 0, every (s, a) unobserved); the Q tables come from td_init."""

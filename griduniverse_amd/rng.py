@@ -14,6 +14,8 @@ one, keyed by (seed, GLOBAL env id, stream, counter):
                                 word & 3, greedy tie index (((word >> 2) & 0x3FFF) * ties) >> 14
     stream 9  gusts of wind   : one word per step taken from a cell with wind while gust_q16 > 0 (gu_set_wind), counter and epoch
                                 as stream 4; the strength k changes iff (word >> 16) < gust_q16, to k + 1 if word & 1 else k - 1
+    stream 10 Double Q coin   : one word per step of gu_double_run, counter and epoch as stream 4 at the same step count; bit 0 picks
+                                the table that learns (0: A from B's estimate, 1: B from A's)
 
 These helpers let a caller reproduce on the host exactly what a `policy='uniform'` rollout did on the device -- e.g.
 to replay the same (grid, seed, action) sequence through the reference's own `step()`.

@@ -47,6 +47,7 @@ class VecGridUniverse(object):
     _dyna_ready = False  # ... and Dyna-Q models (dyna_run / model allocate them on first use)
     _sweep_ready = False  # ... and priority queues (sweep_run / priority_queue allocate them, with the models, on first use)
     _explore_ready = False  # ... and visit counts (explore_run / visit_counts allocate them on first use)
+    _double_ready = False  # ... and pairs of Q tables (double_q_run / double_q_tables allocate them on first use)
     _explore_tables = False  # set_exploration was called
     _tree_sims = 0  # simulations the tree-search node pools hold (tree_search_run allocates them on first use and when it needs more)
     _tree_tables = False  # set_tree_search was called (tree_search_run installs UCB1 tables with c = 3 otherwise)
@@ -291,6 +292,49 @@ class VecGridUniverse(object):
         S << F rows while F fruits are set and S << D rows while doors with D slots are set, as q_table()."""
         self._ensure_q()
         self.engine.td_set_q(q, env0)
+
+    def expected_sarsa_run(self, T, alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
+        """T iterations of batched tabular Expected SARSA (Sutton & Barto 6.6) on the tables of td_run: env e acts epsilon-greedily
+        as Q-learning does and bootstraps on the mean of Q[s'] under that same policy (include/gu.h: gu_esarsa_run); epsilon = 0
+        gives td_run('q_learning')'s bytes.  The first call gives every env a table of zeros.  Refused while wind, fruit or doors are
+        set.  Rows and statistics as td_run()."""
+        if not 0.0 <= float(epsilon) <= 1.0:
+            raise ValueError('epsilon must lie in [0, 1]')
+        self._ensure_q()
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.esarsa_run(T, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def _ensure_pairs(self, q0=None):
+        """Pairs of Q tables on the engine: two tables of zeros per env on first use; every entry q0 (again) when q0 is given."""
+        if q0 is not None or not self._double_ready:
+            self.engine.double_init(0.0 if q0 is None else q0)
+            self._double_ready = True
+
+    def double_q_run(self, T, alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
+        """T iterations of batched tabular Double Q-learning (Sutton & Barto 6.7): env e keeps two tables A and B of its own (not
+        the tables of td_run), acts epsilon-greedily on A + B, and a coin per step (RNG stream 10) picks the table that learns, from
+        the other's estimate of its own greedy action at s' (include/gu.h: gu_double_run).  The first call gives every env two
+        tables of zeros.  Refused while wind, fruit or doors are set.  Rows and statistics as td_run()."""
+        if not 0.0 <= float(epsilon) <= 1.0:
+            raise ValueError('epsilon must lie in [0, 1]')
+        self._ensure_pairs()
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        self.engine.double_run(T, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
+
+    def double_q_tables(self, env0=0, n=None):
+        """float64[n, S, 2, 4]: the pairs of envs env0 .. env0+n-1 (to the end when n is None); [:, :, 0] is A, [:, :, 1] is B; zeros
+        before the first double_q_run."""
+        self._ensure_pairs()
+        return self.engine.double_get_q(env0, n)
+
+    def set_double_q_tables(self, q, env0=0):
+        """Install pairs float64[n, S, 2, 4] (or [S, 2, 4]) for envs env0 ..; the other envs get tables of zeros if they had none."""
+        self._ensure_pairs()
+        self.engine.double_set_q(q, env0)
 
     def dyna_run(self, T, planning_steps=10, alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
         """T real steps of batched tabular Dyna-Q: env e learns its own Q table [S][4] with Q-learning and its own model of the

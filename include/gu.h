@@ -393,7 +393,8 @@ int gu_done_indices(gu_handle h, int32_t *idx, int32_t *count);
  *      the row maximum exactly, in ascending order, the one at index (((w >> 2) & 0x3FFF) * m) >> 14.  SARSA uses the carried
  *      action a' instead -- inside a launch always, and at its start when it directly follows a SARSA gu_td_run on this engine
  *      (no gu_seed, gu_reset*, gu_step*, gu_rollout, gu_set_state, gu_set_grid(s), gu_generate_mazes, gu_td_init, gu_td_set_q, gu_dyna_run,
- *      gu_sweep_run, gu_nstep_run, gu_search_run, gu_explore_run, gu_mcts_run or sweep-step call in between);
+ *      gu_sweep_run, gu_nstep_run, gu_search_run, gu_explore_run, gu_mcts_run, gu_esarsa_run, gu_double_run or sweep-step call in
+ *      between);
  *   3. (s', r, d) by the engine's move rule (absorbing terminal); t += 1;
  *   4. float64, one rounding per operation: m = max Q_e[s'] (Q-learning) or Q_e[s'][a'] with a' drawn at s' by rule 2 from the word
  *      of the new t and the pre-update row (SARSA; not drawn when d); target = r if d else r + gamma * m;
@@ -409,6 +410,43 @@ int gu_td_init(gu_handle h, double q0);
 int gu_td_run(gu_handle h, int64_t T, int32_t method, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 int gu_td_get_q(gu_handle h, int64_t env0, int64_t n, double *q);
 int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q);
+
+/* ---- batched tabular Expected SARSA (Sutton & Barto 6.6): learner e owns env e and its table Q_e[S][4] (the gu_td_* tables) ----
+ * (build-defined; tests/_double_oracle.py is the CPU restatement.)  One iteration of gu_esarsa_run for env e at step count t:
+ *   1. reset and action as gu_td_run's rules 1 and 2 for Q-learning: one word of RNG stream 4 per step, no carried action, no
+ *      second draw;
+ *   2. (s', r, d) by the engine's move rule; t += 1; n = the pre-update row Q_e[s'] (not read when d);
+ *   3. the mean of n under the epsilon-greedy policy of rule 1, float64 with one rounding per operation and no division: with
+ *      pe = eps_q16 * 2^-18 and pg = (65536 - eps_q16) * 2^-16 (both exact), sum = ((n[0] + n[1]) + n[2]) + n[3] and mx = the row
+ *      maximum, E = pe * sum + pg * mx.  (The m tied maxima all equal mx, so their mean is mx whatever m is.)
+ *   4. target = r if d else r + gamma * E;  Q_e[s][a] += alpha * (target - Q_e[s][a]).
+ * With eps_q16 = 0 (E = 0 * sum + 1 * mx) a launch gives the bytes of gu_td_run's Q-learning on finite tables without negative zeros.
+ * Launches alternate freely with gu_td_run and the other learners on the same tables; a launch ends what they carry (SARSA actions,
+ * windows, episode buffers).  Flags and errors as gu_td_run; GU_ERR_UNSUPPORTED while wind, fruit or doors are set. */
+int gu_esarsa_run(gu_handle h, int64_t T, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+
+/* ---- batched tabular Double Q-learning (Sutton & Barto 6.7): learner e owns env e and a PAIR of tables A_e[S][4], B_e[S][4] ----
+ * (build-defined; tests/_double_oracle.py is the CPU restatement.)  The pair is storage of its own, q[N][S][2][4] float64 -- the A
+ * row and the B row of a state side by side --, not the gu_td_* tables.  One iteration of gu_double_run for env e at step count t,
+ * after the lazy reset of gu_td_run's rule 1:
+ *   1. the action by gu_td_run's rule 2 (without a carried action) on the row A_e[s][.] + B_e[s][.] (one rounded add per entry), with
+ *      the word of RNG stream 4 at t;
+ *   2. the coin c = bit 0 of the word of RNG stream 10 with counter t & 0xFFFFFFFF and epoch t >> 32 (keyed exactly like stream 4),
+ *      at the same t: c = 0 updates A from B's estimate (X = A, Y = B), c = 1 updates B from A's (X = B, Y = A);
+ *   3. (s', r, d) by the engine's move rule; t += 1; the pre-update pair of s' (not read when d);
+ *   4. a* = the lowest action with X[s'][a*] equal to the maximum of row X[s'] (action 0 if none compares equal); est = Y[s'][a*];
+ *      target = r if d else r + gamma * est;  X[s][a] += alpha * (target - X[s][a]), float64, one rounding per operation;
+ *   5. that entry is the step's one store (8 bytes).
+ * gu_double_init  : allocate the pairs (N * S * 64 bytes; GU_ERR_NOMEM when free device memory cannot hold them with 1 GiB to spare)
+ *                   and set every entry of both tables to q0.  A grid of another state count drops them (gu_double_init again).
+ * gu_double_run   : T iterations per env in ONE launch (async); flags and argument errors as gu_td_run.  GU_ERR_STATE before
+ *                   gu_double_init, GU_ERR_UNSUPPORTED while wind, fruit or doors are set.  A launch ends what the other learners
+ *                   carry (SARSA actions, windows, episode buffers).  The step counts advance by T.
+ * gu_double_get_q / gu_double_set_q : pairs of envs env0 .. env0+n-1 as q[n][S][2][4] on the host. */
+int gu_double_init(gu_handle h, double q0);
+int gu_double_run(gu_handle h, int64_t T, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
+int gu_double_get_q(gu_handle h, int64_t env0, int64_t n, double *q);
+int gu_double_set_q(gu_handle h, int64_t env0, int64_t n, const double *q);
 
 /* ---- batched tabular Dyna-Q: learner e owns env e, its table Q_e[S][4] (the gu_td_* tables) and a learned model ----
  * (build-defined: the reference lists "Integrating learning and planning (Dyna, ...)" on its roadmap and ships no code; Sutton &
