@@ -96,7 +96,7 @@ static int gu_launch_ac(gu_engine *h, int64_t T, double alpha_actor, double alph
     a.v = h->d_ac_v;
     a.alpha_c = alpha_critic;
     const int rc = gu_tabular_launch(h, gu_ac_kernel<true>, gu_ac_kernel<false>, a);
-    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags);
 }
 
 void gu_ac_free(gu_engine *h)

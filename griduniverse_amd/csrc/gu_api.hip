@@ -53,8 +53,7 @@ int gu_ensure_scratch(gu_engine *h, size_t bytes)
     if (bytes <= h->scratch_bytes) return GU_OK;
     if (h->d_scratch) {
         GU_HIP(hipStreamSynchronize(h->stream));
-        GU_HIP(hipFree(h->d_scratch));
-        h->d_scratch = nullptr;
+        gu_release(h->d_scratch);
         h->scratch_bytes = 0;
     }
     GU_HIP(hipMalloc(&h->d_scratch, bytes));
@@ -63,6 +62,7 @@ int gu_ensure_scratch(gu_engine *h, size_t bytes)
 }
 
 static void gu_placement_release(gu_engine *h);  // (the registry of chosen trajectory buffers, below)
+static void gu_grid_free(gu_engine *h);          // (with gu_install_grids, below)
 
 extern "C" {
 
@@ -159,22 +159,19 @@ int gu_destroy(gu_handle h)
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     gu_comm_free(h);
-    gu_vi_free(h);
     gu_trail_free(h);
-    gu_overlay_free(h);
     gu_placement_release(h);
     gu_learners_drop(h, 0);
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    void *bufs[] = {h->d_kind, h->d_rows[0], h->d_rows[1], h->d_rows2[0], h->d_rows2[1], h->d_mrows[0], h->d_mrows[1], h->d_mrows1[0], h->d_mrows1[1], h->d_prow, h->d_cell, h->d_cell_raw, h->d_nib, h->d_starts, h->d_nstarts, h->d_out3, h->d_episode, h->d_tcount, h->d_actions, h->d_actions_packed,
-                    h->d_traj, h->d_ret, h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_greedy, h->d_pace_ring, h->d_pace_slots, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
+    gu_graph_drop(h);
+    gu_grid_free(h);  // (with the DP tables and the overlay)
+    // what belongs to the engine rather than to its grid
+    gu_release(h->d_out3, h->d_episode, h->d_tcount, h->d_out3_alt, h->d_episode_alt, h->d_done_bits_alt, h->d_actions, h->d_actions_packed, h->d_traj, h->d_ret,
+               h->d_episodes_fin, h->d_done_bits, h->d_scratch, h->d_pace_ring, h->d_pace_slots, h->d_blocks_done);
     if (h->h_pin) (void)hipHostFree(h->h_pin);
     if (h->h_seq) (void)hipHostFree(h->h_seq);
     if (h->h_ctl) (void)hipHostFree(h->h_ctl);
     if (h->h_tables) (void)hipHostFree(h->h_tables);
     if (h->h_up) (void)hipHostFree(h->h_up);
-    if (h->d_blocks_done) (void)hipFree(h->d_blocks_done);
     for (hipEvent_t ev : h->ev_marks) (void)hipEventDestroy(ev);
     if (h->ev_begin) (void)hipEventDestroy(h->ev_begin);
     if (h->ev_end) (void)hipEventDestroy(h->ev_end);
@@ -223,6 +220,24 @@ static void compile_planes(int32_t W, int32_t H, int32_t wpr, const uint32_t *wa
 
 }  // extern "C" (helpers below have C++ signatures)
 
+// What belongs to a grid goes with it: the cell planes and start tables, the nibble images, the transition-row, pair and K-step tables,
+// the policy rows, the DP tables and the overlay.  The one owner of these buffers: gu_install_grids and gu_destroy call it.
+static void gu_grid_free(gu_engine *h)
+{
+    gu_release(h->d_cell, h->d_cell_raw, h->d_kind, h->d_starts, h->d_nstarts, h->d_greedy, h->d_nib, h->d_prow);
+    h->nib_valid = false;
+    for (int k = 0; k < 2; ++k) {
+        gu_release(h->d_rows[k], h->d_rows2[k], h->d_mrows[k], h->d_mrows1[k]);
+        h->rows_shift[k] = h->mrows_shift[k] = -1;
+        h->rows2_built[k] = false;
+        h->mrows_K[k] = 0;
+    }
+    h->has_grid = false;
+    for (auto &p : h->pace) p.active = false;  // (another grid: another chain length)
+    gu_vi_free(h);
+    gu_overlay_free(h);
+}
+
 // Upload compiled planes of `n_grids` grids ([g][flags|reward]) and their start tables; resets env state.
 int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const std::vector<uint8_t> &cell,
                      const std::vector<uint8_t> &raw, const std::vector<uint8_t> &kind, const std::vector<int32_t> &starts,
@@ -231,37 +246,11 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
     const int32_t S = W * H;
     const int32_t cell_bytes = (S + 15) & ~15;
     GU_HIP(hipStreamSynchronize(h->stream));
-    h->entry_table_ok = false;  // (other cells, other flags)
-    gu_tabular_drop_carry(h);
+    gu_envs_touched(h);  // (other cells, other flags)
     gu_td_rows_changed(h, 0);  // an overlay belonged to the old grid's cells, and tables of S << bits rows to its masks
-    gu_overlay_free(h);
     gu_learners_drop(h, S);  // the learners' stores of another state count belong to another grid
     h->dyna_exact = false;  // a kept model may hold outcomes of the old cells: gu_dyna_run compares every observation from now on
-    h->nib_valid = false;
-    if (h->d_nib) GU_HIP(hipFree(h->d_nib));
-    h->d_nib = nullptr;
-    for (void *p : {(void *)h->d_cell, (void *)h->d_cell_raw, (void *)h->d_kind, (void *)h->d_starts, (void *)h->d_nstarts, (void *)h->d_greedy})
-        if (p) GU_HIP(hipFree(p));
-    h->d_cell = h->d_cell_raw = h->d_kind = h->d_greedy = nullptr;
-    h->d_starts = h->d_nstarts = nullptr;
-    for (int k = 0; k < 2; ++k) {  // the transition-row tables belong to the old grid
-        if (h->d_rows[k]) GU_HIP(hipFree(h->d_rows[k]));
-        h->d_rows[k] = nullptr;
-        h->rows_shift[k] = -1;
-        if (h->d_rows2[k]) GU_HIP(hipFree(h->d_rows2[k]));
-        h->d_rows2[k] = nullptr;
-        h->rows2_built[k] = false;
-        if (h->d_mrows[k]) GU_HIP(hipFree(h->d_mrows[k]));
-        if (h->d_mrows1[k]) GU_HIP(hipFree(h->d_mrows1[k]));
-        h->d_mrows[k] = h->d_mrows1[k] = nullptr;
-        h->mrows_K[k] = 0;
-        h->mrows_shift[k] = -1;
-    }
-    if (h->d_prow) GU_HIP(hipFree(h->d_prow));
-    h->d_prow = nullptr;
-    h->has_grid = false;
-    for (auto &p : h->pace) p.active = false;  // (another grid: another chain length)
-    gu_vi_free(h);
+    gu_grid_free(h);
     const size_t plane_bytes = 2 * (size_t)cell_bytes * n_grids;
     GU_HIP(hipMalloc(&h->d_cell, plane_bytes));
     GU_HIP(hipMalloc(&h->d_cell_raw, plane_bytes));
@@ -297,10 +286,7 @@ int gu_install_grids(gu_engine *h, int32_t n_grids, int32_t W, int32_t H, const 
     for (int32_t g = 0; g < n_grids; ++g) h->all_single_start = h->all_single_start && n_starts[(size_t)g] == 1;
     h->has_grid = true;
     h->greedy_valid = false;
-    if (h->graph_exec) {
-        (void)hipGraphExecDestroy(h->graph_exec);
-        h->graph_exec = nullptr;
-    }
+    gu_graph_drop(h);
     // every env sits on its grid's first start cell until the caller resets (pos must always be a valid cell)
     std::vector<int32_t> init((size_t)h->N);
     for (int64_t e = 0; e < h->N; ++e) init[(size_t)e] = starts[(size_t)(e / h->group) * max_starts];
@@ -381,13 +367,10 @@ int gu_seed(gu_handle h, uint64_t seed)
     h->seed = seed;
     h->seed_prefix = gu_rng_seed_prefix(seed);
     h->steps_taken = 0;
-    gu_tabular_drop_carry(h);
+    gu_envs_touched(h);
     h->off_lo = h->off_hi = 0;
     h->off_exact = true;
-    if (h->graph_exec) {  // captured step launches carry the old seed in their arguments
-        (void)hipGraphExecDestroy(h->graph_exec);
-        h->graph_exec = nullptr;
-    }
+    gu_graph_drop(h);  // captured step launches carry the old seed in their arguments
     GU_HIP(hipMemsetAsync(h->d_episode, 0, (size_t)h->N * sizeof(uint32_t), h->stream));
     GU_HIP(hipMemsetAsync(h->d_tcount, 0, (size_t)h->N * sizeof(uint32_t), h->stream));
     GU_HIP(hipStreamSynchronize(h->stream));
@@ -403,8 +386,7 @@ int gu_reset(gu_handle h, const uint8_t *mask, const int32_t *start_choice, int3
     uint8_t *d_mask = nullptr;
     int32_t *d_choice = nullptr;
     if (mask || start_choice) {
-        int rc = gu_ensure_scratch(h, n * 5 + 16);
-        if (rc != GU_OK) return rc;
+        GU_TRY(gu_ensure_scratch(h, n * 5 + 16));
         if (start_choice) {
             for (size_t i = 0; i < n; ++i)
                 if (!mask || mask[i])
@@ -418,8 +400,7 @@ int gu_reset(gu_handle h, const uint8_t *mask, const int32_t *start_choice, int3
             GU_HIP(hipMemcpyAsync(d_mask, mask, n, hipMemcpyHostToDevice, h->stream));
         }
     }
-    int rc = gu_launch_reset(h, d_mask, d_choice, false);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_launch_reset(h, d_mask, d_choice, false));
     if (obs_out) GU_HIP(hipMemcpyAsync(obs_out, h->pos(), n * 4, hipMemcpyDeviceToHost, h->stream));
     GU_HIP(hipStreamSynchronize(h->stream));
     return GU_OK;
@@ -515,18 +496,15 @@ static int gu_step_action_error(gu_engine *h, const int32_t *actions)
 // Actions are validated by the kernel itself (an error word next to the completion word), not by a host loop.
 static int gu_step_and_wait(gu_engine *h, const int32_t *actions, uint32_t flags, int32_t *obs, int32_t *reward, int32_t *done)
 {
-    int rc;
     uint32_t *err = h->h_seq + GU_HOST_ERR_WORD;
     bool finished = false;
     if (h->N <= 8192 && h->seq_since_sync < 1024 && !gu_opt(h, GU_OPT_STEP_SYNC)) {
         const uint32_t seq = ++h->seq;
-        rc = gu_launch_step(h, actions, flags, obs, reward, done, h->h_seq, seq, err);
-        if (rc != GU_OK) return rc;
+        GU_TRY(gu_launch_step(h, actions, flags, obs, reward, done, h->h_seq, seq, err));
         ++h->seq_since_sync;
         for (int spin = 0; spin < 2000000 && !finished; ++spin) finished = __atomic_load_n(h->h_seq, __ATOMIC_ACQUIRE) == seq;
     } else {
-        rc = gu_launch_step(h, actions, flags, obs, reward, done, nullptr, 0, err);
-        if (rc != GU_OK) return rc;
+        GU_TRY(gu_launch_step(h, actions, flags, obs, reward, done, nullptr, 0, err));
     }
     if (!finished) {
         GU_HIP(hipStreamSynchronize(h->stream));
@@ -545,15 +523,14 @@ int gu_step(gu_handle h, const int32_t *actions, uint32_t flags, int32_t *obs, i
     const bool direct = flags & GU_F_PINNED_IO;
     flags &= GU_F_AUTO_RESET;
     const size_t n = (size_t)h->N;
-    int rc = GU_OK;
     if (direct) {
         // The caller's buffers are page-locked (gu_host_alloc), i.e. mapped into the device's address space: the
         // kernel reads the actions from them and writes the results into them itself over PCIe -- one launch and
         // one synchronisation, no copy commands at all.  (Checked: a pageable pointer here would be a GPU fault.)
-        if ((rc = gu_require_pinned(actions, n * 4, "actions")) != GU_OK) return rc;
-        if ((rc = gu_require_pinned(obs, n * 4, "obs")) != GU_OK) return rc;
-        if ((rc = gu_require_pinned(reward, n * 4, "reward")) != GU_OK) return rc;
-        if ((rc = gu_require_pinned(done, n * 4, "done")) != GU_OK) return rc;
+        GU_TRY(gu_require_pinned(actions, n * 4, "actions"));
+        GU_TRY(gu_require_pinned(obs, n * 4, "obs"));
+        GU_TRY(gu_require_pinned(reward, n * 4, "reward"));
+        GU_TRY(gu_require_pinned(done, n * 4, "done"));
         return gu_step_and_wait(h, actions, flags, obs, reward, done);
     }
     // Ordinary (pageable) caller buffers: the engine's own page-locked staging block plays the caller's part of the
@@ -561,8 +538,7 @@ int gu_step(gu_handle h, const int32_t *actions, uint32_t flags, int32_t *obs, i
     // call is two memcpys around one launch + one sync instead of two copy commands around the launch.
     memcpy(h->h_pin, actions, n * 4);
     const bool want = obs || reward || done;
-    rc = gu_step_and_wait(h, h->h_pin, flags, want ? h->h_pin + n : nullptr, want ? h->h_pin + 2 * n : nullptr, want ? h->h_pin + 3 * n : nullptr);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_step_and_wait(h, h->h_pin, flags, want ? h->h_pin + n : nullptr, want ? h->h_pin + 2 * n : nullptr, want ? h->h_pin + 3 * n : nullptr));
     if (obs) memcpy(obs, h->h_pin + n, n * 4);
     if (reward) memcpy(reward, h->h_pin + 2 * n, n * 4);
     if (done) memcpy(done, h->h_pin + 3 * n, n * 4);
@@ -577,24 +553,17 @@ int gu_upload_actions(gu_handle h, const int32_t *actions, int64_t T)
     h->actions_T = 0;  // until the new stream has been accepted
     if (T > h->actions_cap) {
         GU_HIP(hipStreamSynchronize(h->stream));
-        if (h->d_actions) GU_HIP(hipFree(h->d_actions));
-        if (h->d_actions_packed) GU_HIP(hipFree(h->d_actions_packed));
-        h->d_actions = nullptr;
-        h->d_actions_packed = nullptr;
+        gu_release(h->d_actions, h->d_actions_packed);
         h->actions_cap = 0;
         GU_HIP(hipMalloc(&h->d_actions, count * sizeof(int32_t)));
         GU_HIP(hipMalloc(&h->d_actions_packed, (size_t)((T + 15) / 16 + GU_STREAM_PAD_WORDS) * (size_t)h->N * sizeof(uint32_t)));  // + look-ahead rows
         h->actions_cap = T;
-        if (h->graph_exec) {
-            (void)hipGraphExecDestroy(h->graph_exec);
-            h->graph_exec = nullptr;
-        }
+        gu_graph_drop(h);
     }
     GU_HIP(hipMemcpyAsync(h->d_actions, actions, count * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     // validated on the device, where the stream now is (one pass at HBM speed instead of a host loop over T x N values), and
     // packed in the same pass to the two-bit form the rollout kernels read
-    int rc = gu_launch_pack_actions(h, T);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_launch_pack_actions(h, T));
     GU_HIP(hipStreamSynchronize(h->stream));
     if (__atomic_load_n(h->h_seq + GU_HOST_ERR_WORD, __ATOMIC_ACQUIRE)) {
         __atomic_store_n(h->h_seq + GU_HOST_ERR_WORD, 0u, __ATOMIC_RELAXED);
@@ -620,16 +589,12 @@ int gu_step_graph(gu_handle h, int64_t t0, int64_t T, uint32_t flags)
 {
     GU_ENTER(h);
     GU_NO_OVERLAY(h, "gu_step_graph");
-    h->entry_table_ok = false;
     GU_NEED_GRID(h);
     GU_REQUIRE(h->d_actions && t0 >= 0 && T > 0 && t0 + T <= h->actions_T, GU_ERR_STATE, "rows [%lld,%lld) not in the uploaded action stream",
                (long long)t0, (long long)(t0 + T));
     GU_REQUIRE((flags & ~GU_F_AUTO_RESET) == 0, GU_ERR_INVALID, "gu_step_graph accepts only GU_F_AUTO_RESET");
     if (!h->graph_exec || h->graph_t0 != t0 || h->graph_T != T || h->graph_flags != flags) {
-        if (h->graph_exec) {
-            (void)hipGraphExecDestroy(h->graph_exec);
-            h->graph_exec = nullptr;
-        }
+        gu_graph_drop(h);
         const uint64_t saved = h->steps_taken;
         hipGraph_t graph = nullptr;
         GU_HIP(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
@@ -647,8 +612,7 @@ int gu_step_graph(gu_handle h, int64_t t0, int64_t T, uint32_t flags)
         h->graph_flags = flags;
     }
     GU_HIP(hipGraphLaunch(h->graph_exec, h->stream));
-    h->steps_taken += (uint64_t)T;
-    gu_tabular_drop_carry(h);
+    gu_envs_touched(h, (uint64_t)T);
     return GU_OK;
 }
 
@@ -854,12 +818,10 @@ int gu_reserve_trajectory(gu_handle h, int64_t T)
     GU_REQUIRE(T > 0, GU_ERR_INVALID, "T <= 0");
     if (h->d_traj && T <= h->traj_T) return GU_OK;  // room for AT LEAST T rows: a buffer that is large enough is kept (and so is its placement)
     GU_HIP(hipStreamSynchronize(h->stream));
-    if (h->d_traj) GU_HIP(hipFree(h->d_traj));
-    h->d_traj = nullptr;
+    gu_release(h->d_traj);
     h->traj_T = 0;
     gu_placement_release(h);
-    int rc = gu_alloc_trajectory(h, 3 * (size_t)T * (size_t)h->N * sizeof(int32_t), T, &h->d_traj);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_alloc_trajectory(h, 3 * (size_t)T * (size_t)h->N * sizeof(int32_t), T, &h->d_traj));
 #ifdef GU_EXPERIMENTS
     if (gu_opt(h, GU_OPT_X_TRAJ_POISON))  // debugging aid: nothing may depend on rows no rollout has written
         GU_HIP(hipMemsetAsync(h->d_traj, 0x5A, 3 * (size_t)T * (size_t)h->N * sizeof(int32_t), h->stream));
@@ -925,8 +887,7 @@ int gu_rollout(gu_handle h, int64_t T, int32_t policy_kind, uint32_t flags)
     if (policy_kind == GU_POLICY_GREEDY) {
         GU_REQUIRE(h->has_vi, GU_ERR_STATE, "no policy table: call gu_vi_set first");
         if (!h->greedy_valid) {
-            int rc = gu_launch_greedy_table(h);
-            if (rc != GU_OK) return rc;
+            GU_TRY(gu_launch_greedy_table(h));
         }
     }
     int rc = gu_launch_rollout(h, T, policy_kind, flags);
@@ -1042,8 +1003,7 @@ int gu_rollout_pacing(gu_handle h, int32_t policy_kind, uint32_t flags, int32_t 
     uint64_t last[8];
     int32_t n = 0;
     uint32_t launches = 0;
-    const int rc = gu_rollout_pace_log(h, policy_kind, flags, 1, last, &n, &launches);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_rollout_pace_log(h, policy_kind, flags, 1, last, &n, &launches));
     GU_REQUIRE(n == 1, GU_ERR_STATE, "no launch of this kind has been recorded yet");
     if (period) *period = (int32_t)((last[1] + 32u) >> 6);
     if (ms_unpaced) *ms_unpaced = 0.0f;  // (nothing runs without the limiter any more)
@@ -1063,11 +1023,10 @@ int gu_read_trajectory(gu_handle h, int64_t t0, int64_t T, int32_t *obs, int32_t
     int32_t *dst[3] = {obs, reward, done};
     if (h->traj_kind == 3) {  // triples [T][N][3]: taken apart on the device, a bounded number of rows at a time, then copied like planes
         const size_t chunk_rows = std::max<size_t>(1, std::min<size_t>((size_t)T, ((size_t)256 << 20) / (12 * n)));
-        int rc = gu_ensure_scratch(h, chunk_rows * n * 12);
-        if (rc != GU_OK) return rc;
+        GU_TRY(gu_ensure_scratch(h, chunk_rows * n * 12));
         for (size_t r0 = 0; r0 < (size_t)T; r0 += chunk_rows) {
             const size_t nr = std::min(chunk_rows, (size_t)T - r0), cnt = nr * n;
-            if ((rc = gu_launch_deinterleave(h, h->d_traj + ((size_t)t0 + r0) * n * 3, (int32_t *)h->d_scratch, (int64_t)cnt)) != GU_OK) return rc;
+            GU_TRY(gu_launch_deinterleave(h, h->d_traj + ((size_t)t0 + r0) * n * 3, (int32_t *)h->d_scratch, (int64_t)cnt));
             GU_HIP(hipStreamSynchronize(h->stream));
             for (int k = 0; k < 3; ++k)
                 if (dst[k]) GU_HIP(hipMemcpy(dst[k] + r0 * n, (int32_t *)h->d_scratch + k * cnt, cnt * 4, hipMemcpyDeviceToHost));
@@ -1126,8 +1085,7 @@ int gu_get_state(gu_handle h, int32_t *pos, int32_t *done, uint32_t *episode, ui
 int gu_set_state(gu_handle h, const int32_t *pos, const int32_t *done, const uint32_t *episode, const uint64_t *tcount)
 {
     GU_ENTER(h);
-    h->entry_table_ok = false;
-    gu_tabular_drop_carry(h);
+    gu_envs_touched(h);  // (even where the call is then refused)
     GU_NEED_GRID(h);
     const size_t n = (size_t)h->N;
     if (pos)
@@ -1160,10 +1118,7 @@ int gu_set_state(gu_handle h, const int32_t *pos, const int32_t *done, const uin
         h->off_lo = 0;
         h->off_hi = (int64_t)(t_max - t_min);
         h->off_exact = true;
-        if (h->graph_exec) {  // (captured rollout-free step launches carry no count, but a stale graph is not worth the doubt)
-            (void)hipGraphExecDestroy(h->graph_exec);
-            h->graph_exec = nullptr;
-        }
+        gu_graph_drop(h);  // (captured rollout-free step launches carry no count, but a stale graph is not worth the doubt)
     }
     return gu_trail_after_set_state(h, pos != nullptr, done != nullptr);
 }
@@ -1174,8 +1129,7 @@ int gu_done_indices(gu_handle h, int32_t *idx, int32_t *count)
     GU_REQUIRE(count != nullptr, GU_ERR_INVALID, "count is NULL");
     // one launch: the compaction kernel expands the ballot words (written by the step / rollout / reset kernels) into the
     // ascending index list, straight into the page-locked staging block
-    int rc = gu_launch_done_compact(h);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_launch_done_compact(h));
     GU_HIP(hipStreamSynchronize(h->stream));
     *count = (int32_t)__atomic_load_n(h->h_seq + GU_HOST_COUNT_WORD, __ATOMIC_ACQUIRE);
     if (idx && *count > 0) memcpy(idx, h->h_pin, (size_t)*count * 4);
@@ -1191,13 +1145,11 @@ int gu_look_step_ahead(gu_handle h, int64_t n, const int32_t *states, const int3
     GU_NEED_GRID(h);
     GU_REQUIRE(n > 0 && states && actions, GU_ERR_INVALID, "n <= 0 or NULL inputs");
     const size_t bytes = (size_t)n * 4;
-    int rc = gu_ensure_scratch(h, 5 * bytes);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_ensure_scratch(h, 5 * bytes));
     int32_t *d = (int32_t *)h->d_scratch;
     GU_HIP(hipMemcpyAsync(d, states, bytes, hipMemcpyHostToDevice, h->stream));
     GU_HIP(hipMemcpyAsync(d + n, actions, bytes, hipMemcpyHostToDevice, h->stream));
-    rc = gu_launch_lookahead(h, n, d, d + n, care_about_terminal != 0, d + 2 * n, d + 3 * n, d + 4 * n);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_launch_lookahead(h, n, d, d + n, care_about_terminal != 0, d + 2 * n, d + 3 * n, d + 4 * n));
     GU_HIP(hipStreamSynchronize(h->stream));
     if (__atomic_load_n(h->h_seq + GU_HOST_ERR_WORD, __ATOMIC_ACQUIRE)) {  // raised by the kernel; name the first offender
         __atomic_store_n(h->h_seq + GU_HOST_ERR_WORD, 0u, __ATOMIC_RELAXED);
@@ -1284,8 +1236,7 @@ int gu_timer_end(gu_handle h, float *milliseconds)
     GU_ENTER(h);
     GU_REQUIRE(milliseconds != nullptr, GU_ERR_INVALID, "milliseconds is NULL");
     GU_HIP(hipEventRecord(h->ev_end, h->stream));
-    int rc = gu_wait_event(h, h->ev_end);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_wait_event(h, h->ev_end));
     GU_HIP(hipEventElapsedTime(milliseconds, h->ev_begin, h->ev_end));
     return GU_OK;
 }

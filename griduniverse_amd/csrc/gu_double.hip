@@ -88,7 +88,7 @@ static int gu_launch_double(gu_engine *h, int64_t T, double alpha, double gamma,
     a.q = nullptr;
     a.dq = h->d_dq;
     const int rc = gu_tabular_launch(h, gu_double_kernel<true>, gu_double_kernel<false>, a, GU_BLOCK, 0, 2);
-    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags);
 }
 
 void gu_double_free(gu_engine *h)

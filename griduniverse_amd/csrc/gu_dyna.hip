@@ -142,7 +142,7 @@ static int gu_launch_dyna(gu_engine *h, int64_t T, int32_t P, double alpha, doub
     a.exact = h->dyna_exact ? 1 : 0;
     const int rc = P > 0 ? gu_tabular_launch(h, gu_dyna_kernel<true, true>, gu_dyna_kernel<true, false>, a)
                          : gu_tabular_launch(h, gu_dyna_kernel<false, true>, gu_dyna_kernel<false, false>, a);
-    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags);
 }
 
 void gu_dyna_free(gu_engine *h)

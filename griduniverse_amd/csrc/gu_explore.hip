@@ -135,7 +135,7 @@ static int gu_launch_explore(gu_engine *h, int64_t T, int32_t mode, double alpha
     a.tab = h->d_explore_tab;
     a.C = h->explore_C;
     const int rc = mode == 1 ? gu_explore_launch<1>(h, a) : gu_explore_launch<0>(h, a);
-    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags);
 }
 
 void gu_explore_free(gu_engine *h)

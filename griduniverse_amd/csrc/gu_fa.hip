@@ -252,7 +252,7 @@ static int gu_launch_fa(gu_engine *h, int64_t T, int32_t method, double alpha, d
     a.phi16 = h->d_fa_phi16;
     a.F = h->fa_F;
     a.next_a = h->d_fa_next;
-    a.carry = (method == 1 && h->fa_carry) ? 1 : 0;
+    a.carry = (method == 1 && gu_carry_is(h, GU_CARRY_FA_SARSA, 0)) ? 1 : 0;
     int rc = GU_ERR_INVALID;
     switch (h->fa_K) {
     case 1: rc = gu_fa_launch_k<1>(h, a, method); break;
@@ -264,10 +264,7 @@ static int gu_launch_fa(gu_engine *h, int64_t T, int32_t method, double alpha, d
     case 7: rc = gu_fa_launch_k<7>(h, a, method); break;
     case 8: rc = gu_fa_launch_k<8>(h, a, method); break;
     }
-    if (rc != GU_OK) return rc;
-    rc = gu_tabular_after(h, T, flags, false);  // (ends every other learner's carry, this one's too)
-    h->fa_carry = method == 1;
-    return rc;
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, method == 1 ? GuCarry{GU_CARRY_FA_SARSA, 0} : GuCarry{});
 }
 
 void gu_fa_free(gu_engine *h)
@@ -275,7 +272,7 @@ void gu_fa_free(gu_engine *h)
     gu_release(h->d_fa_w, h->d_fa_phi, h->d_fa_phi16, h->d_fa_next);
     h->fa_phi16_bytes = 0;
     h->fa_S = h->fa_K = h->fa_F = 0;
-    h->fa_carry = false;
+    gu_carry_release(h, GU_CARRY_FA_SARSA);
 }
 
 #define GU_NEED_FA(h) GU_REQUIRE((h)->d_fa_w && (h)->fa_S == (h)->S, GU_ERR_STATE, "no features: call gu_fa_init first")

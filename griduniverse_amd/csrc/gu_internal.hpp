@@ -116,6 +116,16 @@ struct GuPaceArgs {
 
 enum { GU_OVERLAY_NONE = 0, GU_OVERLAY_WIND, GU_OVERLAY_FRUIT, GU_OVERLAY_DOORS };  // gu_engine::overlay
 
+// What a learner carries from one launch to the next (gu_engine::carry; DESIGN.md "What the engine carries between calls"): the last
+// call that touched the envs was a launch of `owner` under `key` -- gu_td_run's and gu_fa_run's SARSA action (key 0), gu_nstep_run's
+// and gu_lambda_run's window (gu_nstep_key, gu_lambda_key), the episode buffers of gu_reinforce_run and gu_is_run (L).  The next
+// launch of the same owner and key starts from it; any other call that touches the envs or the learner's tables drops it.
+enum { GU_CARRY_NONE = 0, GU_CARRY_TD_SARSA, GU_CARRY_FA_SARSA, GU_CARRY_NSTEP, GU_CARRY_LAMBDA, GU_CARRY_REINFORCE, GU_CARRY_IS };
+struct GuCarry {
+    int owner = GU_CARRY_NONE;
+    int32_t key = 0;
+};
+
 struct gu_engine {
     int device = -1;
     int n_cu = 256;                  // compute units of the device (hipDeviceAttributeMultiprocessorCount)
@@ -276,19 +286,18 @@ struct gu_engine {
     int64_t vi_xcd_torn = 0;        // -DGU_VI_XCD_TORN builds: exchange words found with the right tag and the wrong payload, summed over the per-XCD launches
     int vi_dp_form = 0;             // ... and the last gu_vi_sweep / gu_vi_run / gu_vi_eval_run: 1 per XCD, 2 one workgroup, 3 chip-wide cluster, 4 one launch per round
 
+    GuCarry carry;  // what the last call that touched the envs left for the next launch of the same learner (none: nothing carries)
+
     // batched tabular TD control (gu_td.hip): off until gu_td_init
     double *d_q = nullptr;        // [N][td_S][4] one float64 Q table per env
     int8_t *d_td_next = nullptr;  // [N] SARSA: the action a' carried from one launch to the next (-1: none)
     int32_t td_S = 0;             // states of the tables (0: none allocated); a grid of another size drops them
-    bool td_carry = false;        // the last call that touched the envs was a SARSA gu_td_run: the next one starts from d_td_next
     // batched tabular n-step Q-learning / SARSA (gu_nstep.hip): learns into d_q; the window is allocated on first use
     int32_t *d_nstep_sa = nullptr;   // [N][GU_NSTEP_MAX] pending pairs s*4+a, oldest first
     int32_t *d_nstep_r = nullptr;    // [N][GU_NSTEP_MAX] their rewards
     int32_t *d_nstep_cnt = nullptr;  // [N] entries of the window
-    int32_t nstep_key = 0;           // gu_nstep_key of the last call that touched the envs if it was a gu_nstep_run, else 0 (window dropped)
     // batched tabular SARSA(lambda) / Watkins's Q(lambda) (gu_lambda.hip): learns into d_q; the window is allocated on first use
     int32_t *d_lambda_w = nullptr;  // [N][GU_LAMBDA_MAX] the trace window, index = age (-1: none)
-    int32_t lambda_key = 0;         // gu_lambda_key of the last call that touched the envs if it was a gu_lambda_run, else 0 (window dropped)
     // batched tabular softmax actor-critic (gu_ac.hip): off until gu_ac_init; tables of its own, not d_q
     double *d_ac_h = nullptr;  // [N][ac_S][4] preferences
     double *d_ac_v = nullptr;  // [N][ac_S] state values
@@ -297,7 +306,6 @@ struct gu_engine {
     int32_t *d_rf_buf = nullptr;  // [rf_cap][N] the episode buffers, step-major, oldest first: 8-byte entries {s*4+a, r}
     int32_t *d_rf_cnt = nullptr;  // [N] their entries
     int32_t rf_cap = 0;           // entries per env the storage holds (0: none allocated)
-    int32_t rf_key = 0;           // L of the last call that touched the envs if it was a gu_reinforce_run, else 0 (buffer dropped)
     // batched off-policy Monte-Carlo control with weighted importance sampling (gu_is.hip): off until gu_is_init; learns into d_q
     double *d_is_c = nullptr;     // [N][is_S][4] cumulative weights
     int32_t is_S = 0;             // states of the weights (0: none allocated); a grid of another size drops them
@@ -306,7 +314,6 @@ struct gu_engine {
     int32_t *d_is_buf = nullptr;  // [is_cap][N] the episode buffers, step-major, oldest first: 8-byte entries {s*4+a, r*8+c}
     int32_t *d_is_cnt = nullptr;  // [N] their entries
     int32_t is_cap = 0;           // entries per env the storage holds (0: none allocated)
-    int32_t is_key = 0;           // L of the last call that touched the envs if it was a gu_is_run, else 0 (buffer dropped)
     // batched semi-gradient SARSA / Q-learning on binary features (gu_fa.hip): off until gu_fa_init; weights of its own, not d_q
     double *d_fa_w = nullptr;         // [N][fa_F][4] one float64 weight table per env
     int32_t *d_fa_phi = nullptr;      // [fa_S][fa_K] the feature table, shared by all envs
@@ -314,7 +321,6 @@ struct gu_engine {
     size_t fa_phi16_bytes = 0;        // fa_S * fa_K * 2 rounded up to 16
     int8_t *d_fa_next = nullptr;      // [N] SARSA: the action a' carried from one gu_fa_run to the next (-1: none)
     int32_t fa_S = 0, fa_K = 0, fa_F = 0;  // states, slots and features of the tables (fa_S 0: none); a grid of another size drops them
-    bool fa_carry = false;            // the last call that touched the envs was a SARSA gu_fa_run: the next one starts from d_fa_next
     // batched tabular Dyna-Q (gu_dyna.hip): off until gu_dyna_init; learns into d_q
     uint64_t *d_dyna_model = nullptr;  // [N][dyna_S*4] one packed word per (s, a): reward | (s' | done << 31) << 32; ~0 = unobserved
     int32_t *d_dyna_list = nullptr;    // [N][dyna_S*4] observed pairs s*4+a in the order of first observation (-1 beyond count)
@@ -502,11 +508,12 @@ int gu_vi_xcd_dp_run(gu_engine *h, double gamma, double threshold, bool use_thre
                      double *deltas);
 
 // ---- the batched learners ------------------------------------------------------------
-// gu_td.hip (Q-learning, SARSA), gu_dyna.hip (Dyna-Q), gu_sweep.hip (prioritized sweeping), gu_nstep.hip, gu_lambda.hip, gu_search.hip (rollout search), gu_explore.hip
-// (UCB / Thompson), gu_mcts.hip (tree search), gu_is.hip (off-policy Monte-Carlo), gu_ac.hip (actor-critic), gu_reinforce.hip and
-// gu_fa.hip (semi-gradient learners on features) each hold their kernels, their launch code and their extern "C" functions
-// (include/gu.h); the host helpers they share are in gu_tabular.hpp.  What they export to each other is their gu_*_free: the device
-// buffers of the module and the fields that describe them, back to "none".
+// gu_td.hip (Q-learning, SARSA, Expected SARSA), gu_double.hip (Double Q-learning), gu_dyna.hip (Dyna-Q), gu_sweep.hip (prioritized
+// sweeping), gu_nstep.hip, gu_lambda.hip, gu_search.hip (rollout search), gu_explore.hip (UCB / Thompson), gu_mcts.hip (tree search),
+// gu_is.hip (off-policy Monte-Carlo), gu_ac.hip (actor-critic), gu_reinforce.hip and gu_fa.hip (semi-gradient learners on features)
+// each hold their kernels, their launch code and their extern "C" functions (include/gu.h); the host helpers they share are in
+// gu_tabular.hpp.  What they export to each other is their gu_*_free: the device buffers of the module and the fields that describe
+// them, back to "none", and the carry slot with them when the module owns it.
 void gu_dyna_free(gu_engine *h);        // (takes gu_sweep.hip's queues along)
 int gu_sweep_clear(gu_engine *h);       // gu_sweep.hip: empty queues, queued on the stream (gu_dyna_init clears them with the model)
 void gu_nstep_free(gu_engine *h);
@@ -524,17 +531,35 @@ void gu_fa_free(gu_engine *h);
 // pools), and so does every other store sized by another state count.  S == 0: the engine is being destroyed -- everything goes.
 void gu_learners_drop(gu_engine *h, int32_t S);
 
-// every call that touches the envs other than the learner launches ends what the learners carry from one launch to the next:
-// gu_td_run's and gu_fa_run's SARSA actions, gu_nstep_run's window (its pending updates are discarded, not flushed), gu_lambda_run's
-// window and the episode buffers of gu_reinforce_run and gu_is_run (their pending transitions are discarded, not learned from)
-static inline void gu_tabular_drop_carry(gu_engine *h)
+// ---- what the engine carries between calls (DESIGN.md "What the engine carries between calls") ----
+// Every call that touches the envs or a learner's tables ends what the learners carry from one launch to the next: gu_td_run's and
+// gu_fa_run's SARSA actions, gu_nstep_run's window (its pending updates are discarded, not flushed), gu_lambda_run's window and the
+// episode buffers of gu_reinforce_run and gu_is_run (their pending transitions are discarded, not learned from).  Only
+// gu_tabular_after (gu_tabular.hpp) installs a carry.
+static inline void gu_tabular_drop_carry(gu_engine *h) { h->carry = {}; }
+static inline bool gu_carry_is(const gu_engine *h, int owner, int32_t key) { return h->carry.owner == owner && h->carry.key == key; }
+// the key `owner` left if it owns the slot, else 0: its window or buffer was dropped and reads as empty
+static inline int32_t gu_carry_key(const gu_engine *h, int owner) { return h->carry.owner == owner ? h->carry.key : 0; }
+// a learner's gu_*_free: the slot goes with the stores only when they are what it points at
+static inline void gu_carry_release(gu_engine *h, int owner)
 {
-    h->td_carry = false;
-    h->fa_carry = false;
-    h->nstep_key = 0;
-    h->lambda_key = 0;
-    h->rf_key = 0;
-    h->is_key = 0;
+    if (h->carry.owner == owner) h->carry = {};
+}
+
+// The envs were touched: `steps` lock-step steps were launched (0: a reset, an installed state, seed, grid or overlay).  Whatever the
+// learners carried is gone, and only a rollout vouches for the state the entry table assumes (gu_launch_rollout says so behind this).
+static inline void gu_envs_touched(gu_engine *h, uint64_t steps = 0)
+{
+    h->steps_taken += steps;
+    gu_tabular_drop_carry(h);
+    h->entry_table_ok = false;
+}
+
+// a captured step graph holds the seed, the arrays and the launches of the moment it was captured: whoever changes one of them drops it
+static inline void gu_graph_drop(gu_engine *h)
+{
+    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
+    h->graph_exec = nullptr;
 }
 
 // ---- overlays (gu_overlay.hip: the slot, its install path, getters, reset and launches; gu_overlay.hpp: what its kernels share) ----

@@ -17,7 +17,7 @@
 // BUFFER: step-major, [L][N] entries of 8 bytes {s*4+a, r*8+c} (the class c = 0 .. 4 in the low three bits of the second word,
 // the reward, an int8, above them: one store per real step, one load per walk unit; S needs no limit of its own).  The walk
 // reads entry k-1 while it works on entry k; the newest entry is still in registers when the pass starts.  Between launches the
-// count lives in d_is_cnt; it is read only when this launch directly follows a gu_is_run with the same L (h->is_key).
+// count lives in d_is_cnt; it is read only when this launch directly follows a gu_is_run with the same L (gu_engine::carry).
 //
 // RATIOS: the 20 doubles R[m][c] come from the host, transposed to [c][m-1]: the class is known with the entry, so the walk's
 // head loads the 32-byte row of its class beside the Q row (160 bytes in all: they stay in the cache) and the tail picks by
@@ -146,12 +146,9 @@ static int gu_launch_is(gu_engine *h, int64_t T, int32_t L, double gamma, uint32
     a.buf = reinterpret_cast<int2 *>(h->d_is_buf);
     a.cnt = h->d_is_cnt;
     a.L = L;
-    a.carry = h->is_key == L ? 1 : 0;
+    a.carry = gu_carry_is(h, GU_CARRY_IS, L) ? 1 : 0;
     const int rc = gu_tabular_launch(h, gu_is_kernel<true>, gu_is_kernel<false>, a);
-    if (rc != GU_OK) return rc;
-    const int rc2 = gu_tabular_after(h, T, flags, false);
-    h->is_key = L;
-    return rc2;
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, GuCarry{GU_CARRY_IS, L});
 }
 
 void gu_is_free(gu_engine *h)
@@ -160,7 +157,7 @@ void gu_is_free(gu_engine *h)
     h->is_S = 0;
     h->is_eps = -1;
     h->is_cap = 0;
-    h->is_key = 0;
+    gu_carry_release(h, GU_CARRY_IS);
 }
 
 // R[m][c] = pi(a|s) / b(a|s) for the tie-uniform greedy target (1 / m_now) and the epsilon-greedy behaviour at action time (c of the
@@ -209,7 +206,7 @@ int gu_is_run(gu_handle h, int64_t T, int32_t L, double gamma, uint32_t eps_q16,
     GU_REQUIRE(w_cap >= 1.0 && w_cap <= 0x1p256, GU_ERR_INVALID, "w_cap %g outside [1, 2^256]", w_cap);
     int rc = gu_tabular_check(h, "gu_is_run", T, -1, eps_q16, 0.0, gamma, flags);
     if (rc != GU_OK || T == 0) return rc;
-    GU_TRY(gu_episode_reserve(h, h->d_is_buf, h->d_is_cnt, h->is_cap, h->is_key, L));
+    GU_TRY(gu_episode_reserve(h, h->d_is_buf, h->d_is_cnt, h->is_cap, GU_CARRY_IS, L));
     if (h->is_eps != (int64_t)eps_q16) {  // (a launch still in flight reads the table of its own epsilon)
         double R[20];
         gu_is_ratios(eps_q16, R);
@@ -253,7 +250,7 @@ int gu_is_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32_t
     GU_ENTER(h);
     GU_NEED_GRID(h);
     GU_TRY(gu_env_range(h, env0, n));
-    return gu_episode_read(h, h->d_is_buf, h->d_is_cnt, h->is_key, GU_IS_MAX, env0, n, sa, reward, cls, true, count);
+    return gu_episode_read(h, h->d_is_buf, h->d_is_cnt, GU_CARRY_IS, GU_IS_MAX, env0, n, sa, reward, cls, true, count);
 }
 
 }  // extern "C"

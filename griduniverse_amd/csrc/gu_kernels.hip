@@ -284,10 +284,8 @@ __global__ void __launch_bounds__(1024) gu_done_compact_kernel(const uint64_t *_
 // ------------------------------------------------------------------------------------
 int gu_launch_reset(gu_engine *h, const uint8_t *d_mask, const int32_t *d_choice, bool only_done)
 {
-    h->entry_table_ok = false;  // (a reset may land on a terminal start cell: done = 0 on a terminal cell)
-    gu_tabular_drop_carry(h);
-    int trail_rc = gu_trail_before_reset(h, d_mask, only_done);  // (reads the done flags the reset is about to clear)
-    if (trail_rc != GU_OK) return trail_rc;
+    gu_envs_touched(h);  // (a reset may land on a terminal start cell: done = 0 on a terminal cell)
+    GU_TRY(gu_trail_before_reset(h, d_mask, only_done));  // (reads the done flags the reset is about to clear)
     GU_TRY(gu_overlay_before_reset(h, d_mask, only_done));  // gu_overlay.hip (nothing without masks)
     ResetArgs a{h->pos(), h->done(), h->d_episode, h->d_starts, d_mask, d_choice, h->d_done_bits,
                 (uint32_t)h->n_starts, h->seed_prefix, (uint32_t)h->env_id0, h->N, only_done ? 1 : 0, gu_grid_sel(h)};
@@ -300,7 +298,6 @@ int gu_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, i
                    int32_t *host_done, uint32_t *host_seq, uint32_t seq, uint32_t *host_err)
 {
     if (h->overlay) return gu_overlay_launch_step(h, d_actions_row, flags, host_obs, host_reward, host_done, host_seq, seq, host_err);  // gu_overlay.hip
-    h->entry_table_ok = false;
     StepArgs a{h->d_cell, h->cell_bytes, h->W, h->delta_lut, d_actions_row, h->pos(), h->reward(), h->done(),
                h->d_episode, h->d_tcount, h->d_starts, (uint32_t)h->n_starts, h->seed_prefix, (uint32_t)h->env_id0, h->N, flags,
                gu_grid_sel(h), host_obs, host_reward, host_done, host_seq, seq, h->d_blocks_done, host_err, h->d_done_bits};
@@ -310,8 +307,7 @@ int gu_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, i
     else
         hipLaunchKernelGGL(gu_step_kernel<false>, dim3(gu_blocks(h->N, GU_BLOCK)), dim3(GU_BLOCK), 0, h->stream, a);
     GU_HIP(hipGetLastError());
-    h->steps_taken += 1;
-    gu_tabular_drop_carry(h);
+    gu_envs_touched(h, 1);
     return gu_trail_after_step(h, flags);
 }
 
@@ -575,8 +571,7 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
     }
     GU_HIP(hipGetLastError());
     gu_rollout_plan_form(p, h->rollout_form);
-    h->steps_taken += (uint64_t)T;
-    gu_tabular_drop_carry(h);
+    gu_envs_touched(h, (uint64_t)T);
     h->entry_table_ok = !h->overlay;  // (an overlay's state is not what the entry table assumes)
     return gu_trail_after_rollout(h, T, p.traj, p.auto_mode != 0);
 }

@@ -20,7 +20,7 @@
 //     entry of a 64-slot window in registers or next to its pair in LDS would cost more occupancy than the LDS ring already
 //     does (DESIGN.md §14 has the measured rates).
 // Between launches the window lives in d_lambda_w ([N][GU_LAMBDA_MAX], index = age), SARSA's a' in d_td_next; they are read
-// only when this launch directly follows one of the same method and K (h->lambda_key).
+// only when this launch directly follows one of the same method and K (gu_engine::carry).
 #include "gu_tabular.hpp"
 
 struct LambdaArgs : TabArgs {
@@ -168,7 +168,7 @@ static int gu_launch_lambda(gu_engine *h, int64_t T, int32_t method, int32_t K, 
     a.w = h->d_lambda_w;
     a.next_a = h->d_td_next;
     a.K = K;
-    a.carry = h->lambda_key == key ? 1 : 0;
+    a.carry = gu_carry_is(h, GU_CARRY_LAMBDA, key) ? 1 : 0;
     // the coefficients, one rounding per multiply (the library builds with -ffp-contract=off)
     const double c = gamma * lambda;
     a.P[0] = 1.0;
@@ -178,16 +178,13 @@ static int gu_launch_lambda(gu_engine *h, int64_t T, int32_t method, int32_t K, 
         if (a.Kp == j && a.P[j] != 0.0) a.Kp = j + 1;
     }
     const int rc = method == 1 ? gu_lambda_launch_m<true>(h, a) : gu_lambda_launch_m<false>(h, a);
-    if (rc != GU_OK) return rc;
-    const int rc2 = gu_tabular_after(h, T, flags, false);
-    h->lambda_key = key;
-    return rc2;
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, GuCarry{GU_CARRY_LAMBDA, key});
 }
 
 void gu_lambda_free(gu_engine *h)
 {
     gu_release(h->d_lambda_w);
-    h->lambda_key = 0;
+    gu_carry_release(h, GU_CARRY_LAMBDA);
 }
 
 extern "C" {
@@ -209,7 +206,6 @@ int gu_lambda_run(gu_handle h, int64_t T, int32_t method, int32_t K, double alph
         GU_HIP(hipStreamSynchronize(h->stream));
         GU_TRY(gu_tabular_fits(h, slots * sizeof(int32_t), "trace windows"));
         GU_HIP(hipMalloc(&h->d_lambda_w, slots * sizeof(int32_t)));
-        h->lambda_key = 0;
     }
     return gu_launch_lambda(h, T, method, K, alpha, gamma, lambda, eps_q16, flags);
 }
@@ -220,7 +216,7 @@ int gu_lambda_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa)
     GU_NEED_GRID(h);
     GU_TRY(gu_env_range(h, env0, n));
     GU_REQUIRE(sa != nullptr || n == 0, GU_ERR_INVALID, "sa is NULL");
-    const int32_t K = h->lambda_key ? (h->lambda_key - 1) / 2 : 0;  // (gu_lambda_key; 0: the window was dropped)
+    const int32_t key = gu_carry_key(h, GU_CARRY_LAMBDA), K = key ? (key - 1) / 2 : 0;  // (gu_lambda_key; 0: the window was dropped)
     GU_HIP(hipStreamSynchronize(h->stream));
     if (K) GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, sa, h->d_lambda_w, env0, n, GU_LAMBDA_MAX, false));
     for (int64_t e = 0; e < n; ++e)  // (a dropped window reads as empty, whatever the device copy still holds; ages >= K are not written)

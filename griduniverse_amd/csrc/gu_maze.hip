@@ -128,9 +128,7 @@ __global__ void __launch_bounds__(256) gu_init_pos_kernel(int32_t *pos, int32_t 
 
 extern "C" int gu_generate_mazes(gu_handle h, int32_t n_grids, int32_t W, int32_t H, uint64_t maze_seed)
 {
-    int rc = gu_use_device(h);
-    if (rc != GU_OK) return rc;
-    h->entry_table_ok = false;
+    GU_ENTER(h);
     GU_REQUIRE(n_grids > 0 && h->N % n_grids == 0, GU_ERR_INVALID, "n_grids=%d must divide num_envs=%lld", n_grids, (long long)h->N);
     GU_REQUIRE(W > 0 && H > 0 && (W >= 4 || H >= 4), GU_ERR_INVALID, "a %d x %d grid has no room for a corridor (need max(W,H) >= 4)", W, H);
     GU_REQUIRE((int64_t)W * H <= 65535, GU_ERR_UNSUPPORTED, "generated mazes are limited to 65535 cells");
@@ -140,12 +138,10 @@ extern "C" int gu_generate_mazes(gu_handle h, int32_t n_grids, int32_t W, int32_
     GU_REQUIRE(2 * (int64_t)cell_bytes * n_grids < (1ll << 31), GU_ERR_UNSUPPORTED, "%d grids of %d cells exceed 2 GiB of records", n_grids, S);
     std::vector<uint8_t> no_planes;  // allocate + set metadata through the common path; planes are filled on the device
     std::vector<int32_t> st((size_t)n_grids, 0), ns((size_t)n_grids, 1);
-    rc = gu_install_grids(h, n_grids, W, H, no_planes, no_planes, no_planes, st, ns, 1);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_install_grids(h, n_grids, W, H, no_planes, no_planes, no_planes, st, ns, 1));
     h->has_grid = false;
     const size_t wall_bytes = ((size_t)n_grids * S + 15) & ~(size_t)15, stack_bytes = ((size_t)n_grids * rooms_max * 2 + 15) & ~(size_t)15;
-    rc = gu_ensure_scratch(h, wall_bytes + stack_bytes + 2 * (size_t)n_grids * 4 + 16);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_ensure_scratch(h, wall_bytes + stack_bytes + 2 * (size_t)n_grids * 4 + 16));
     uint8_t *d_wall = (uint8_t *)h->d_scratch;
     uint16_t *d_stack = (uint16_t *)(d_wall + wall_bytes);
     int32_t *d_start = (int32_t *)((uint8_t *)d_stack + stack_bytes), *d_goal = d_start + n_grids, *d_status = d_goal + n_grids;

@@ -313,7 +313,7 @@ static int gu_launch_mcts(gu_engine *h, int64_t T, int32_t M, int32_t H, int32_t
     a.tab = h->d_mcts_tab;  // (nullptr while M == 0 needs none: never read then)
     a.C = h->mcts_C;
     const int rc = eps_sim_q16 == 65536u ? gu_mcts_launch<true>(h, a) : gu_mcts_launch<false>(h, a);
-    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags);
 }
 
 void gu_mcts_free(gu_engine *h)

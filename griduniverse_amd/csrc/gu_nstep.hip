@@ -18,7 +18,7 @@
 //     order), so a repeated pair compounds.  The row in registers needs no forwarding there: the next iteration resets and
 //     loads its row.
 // Between launches the window lives in d_nstep_sa / d_nstep_r ([N][GU_NSTEP_MAX]) and d_nstep_cnt, SARSA's a' in d_td_next; they
-// are read only when this launch directly follows one of the same method and n (h->nstep_key).
+// are read only when this launch directly follows one of the same method and n (gu_engine::carry).
 #include "gu_tabular.hpp"
 
 struct NstepArgs : TabArgs {
@@ -157,18 +157,15 @@ static int gu_launch_nstep(gu_engine *h, int64_t T, int32_t method, int32_t n, d
     a.w_cnt = h->d_nstep_cnt;
     a.next_a = h->d_td_next;
     a.n = n;
-    a.carry = h->nstep_key == key ? 1 : 0;
+    a.carry = gu_carry_is(h, GU_CARRY_NSTEP, key) ? 1 : 0;
     const int rc = method == 1 ? gu_nstep_launch_m<true>(h, a) : gu_nstep_launch_m<false>(h, a);
-    if (rc != GU_OK) return rc;
-    const int rc2 = gu_tabular_after(h, T, flags, false);
-    h->nstep_key = key;
-    return rc2;
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, GuCarry{GU_CARRY_NSTEP, key});
 }
 
 void gu_nstep_free(gu_engine *h)
 {
     gu_release(h->d_nstep_sa, h->d_nstep_r, h->d_nstep_cnt);
-    h->nstep_key = 0;
+    gu_carry_release(h, GU_CARRY_NSTEP);
 }
 
 extern "C" {
@@ -190,7 +187,6 @@ int gu_nstep_run(gu_handle h, int64_t T, int32_t method, int32_t n, double alpha
         GU_HIP(hipMalloc(&h->d_nstep_sa, slots * sizeof(int32_t)));
         GU_HIP(hipMalloc(&h->d_nstep_r, slots * sizeof(int32_t)));
         GU_HIP(hipMalloc(&h->d_nstep_cnt, (size_t)h->N * sizeof(int32_t)));
-        h->nstep_key = 0;
     }
     return gu_launch_nstep(h, T, method, n, alpha, gamma, eps_q16, flags);
 }
@@ -203,7 +199,7 @@ int gu_nstep_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa, int32
     const size_t k = (size_t)n * GU_NSTEP_MAX;
     std::vector<int32_t> c(n), w_sa(k), w_r(k);
     GU_HIP(hipStreamSynchronize(h->stream));
-    if (h->nstep_key) {  // (a dropped window reads as empty, whatever the device copy still holds)
+    if (gu_carry_key(h, GU_CARRY_NSTEP)) {  // (a dropped window reads as empty, whatever the device copy still holds)
         GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, c.data(), h->d_nstep_cnt, env0, n, 1, false));
         GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, w_sa.data(), h->d_nstep_sa, env0, n, GU_NSTEP_MAX, false));
         GU_TRY(gu_env_copy(h, hipMemcpyDeviceToHost, w_r.data(), h->d_nstep_r, env0, n, GU_NSTEP_MAX, false));

@@ -50,12 +50,8 @@ int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bit
             return gu_fail(e == hipErrorOutOfMemory ? GU_ERR_NOMEM : GU_ERR_HIP, "gu_set_%s: the planes and masks: %s", GU_OVERLAY_NAME[kind], hipGetErrorString(e));
         }
     }
-    gu_tabular_drop_carry(h);  // another move or reward rule: what the learners carry belongs to the old one
-    h->entry_table_ok = false;
-    if (h->graph_exec) {  // (a captured step graph holds the launches of the old rule)
-        (void)hipGraphExecDestroy(h->graph_exec);
-        h->graph_exec = nullptr;
-    }
+    gu_envs_touched(h);  // another move or reward rule: what the learners carry belongs to the old one
+    gu_graph_drop(h);    // (a captured step graph holds the launches of the old rule)
     gu_td_rows_changed(h, plane ? bits : 0);  // Q tables of another row count go (S << bits rows: gu_td_run)
     gu_overlay_free(h);
     if (!plane) return GU_OK;
@@ -102,8 +98,7 @@ int gu_overlay_set_masks(gu_engine *h, int kind, int64_t env0, int64_t n, const 
         for (int64_t i = 0; i < n; ++i)
             GU_REQUIRE((masks[i] >> h->overlay_bits) == 0u, GU_ERR_INVALID, "%s[%lld] = 0x%08x has a bit at or above the %d bits in use", what, (long long)i,
                        masks[i], h->overlay_bits);
-    gu_tabular_drop_carry(h);  // (a carried SARSA action was drawn on the row of the old mask)
-    h->entry_table_ok = false;
+    gu_envs_touched(h);  // (a carried SARSA action was drawn on the row of the old mask)
     return gu_env_copy(h, hipMemcpyHostToDevice, masks, h->d_overlay_mask, env0, n, 1);
 }
 
@@ -134,14 +129,12 @@ int gu_overlay_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t 
                            uint32_t *host_seq, uint32_t seq, uint32_t *host_err)
 {
     static void (*const step[])(gu_engine *, bool, const OverlayStepArgs &) = {nullptr, gu_wind_step, gu_fruit_step, gu_doors_step};
-    h->entry_table_ok = false;
     const OverlayStepArgs a{h->d_overlay_cell, h->cell_bytes, h->W, h->delta_lut, d_actions_row, h->pos(), h->reward(), h->done(), h->d_episode, h->d_tcount,
                             h->d_overlay_mask, h->d_starts, (uint32_t)h->n_starts, h->seed_prefix, (uint32_t)h->env_id0, h->overlay_param, h->steps_taken, h->N, flags,
                             gu_grid_sel(h), host_obs, host_reward, host_done, host_seq, seq, h->d_blocks_done, host_err, h->d_done_bits};
     step[h->overlay](h, gu_lds_block(h, GU_BLOCK, 3) != 0, a);
     GU_HIP(hipGetLastError());
-    h->steps_taken += 1;
-    gu_tabular_drop_carry(h);
+    gu_envs_touched(h, 1);
     return gu_trail_after_step(h, flags);
 }
 

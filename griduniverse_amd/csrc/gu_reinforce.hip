@@ -23,7 +23,7 @@
 // grid, ahead on the 32x32 maze for L > 1 from 65 536 learners on.  The walk reads entry k-1 while it works on entry k (the newest
 // entry is still in registers when the pass starts), which takes the entry's load out of the chain entry -> row -> softmax.
 // Between launches the count lives in d_rf_cnt; it is read only when this launch directly follows a gu_reinforce_run with the
-// same L (h->rf_key).
+// same L (gu_engine::carry).
 //
 // TabLane keeps the row of the current state in VGPRs.  A pass may rewrite it (an entry with s_k == s'), and only then: the
 // walk notes it and the next act unit reloads the row (a terminal step's reset loads its row anyway).
@@ -125,19 +125,16 @@ static int gu_launch_reinforce(gu_engine *h, int64_t T, int32_t L, double alpha_
     a.buf = reinterpret_cast<int2 *>(h->d_rf_buf);
     a.cnt = h->d_rf_cnt;
     a.L = L;
-    a.carry = h->rf_key == L ? 1 : 0;
+    a.carry = gu_carry_is(h, GU_CARRY_REINFORCE, L) ? 1 : 0;
     const int rc = gu_tabular_launch(h, gu_reinforce_kernel<true>, gu_reinforce_kernel<false>, a);
-    if (rc != GU_OK) return rc;
-    const int rc2 = gu_tabular_after(h, T, flags, false);
-    h->rf_key = L;
-    return rc2;
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, GuCarry{GU_CARRY_REINFORCE, L});
 }
 
 void gu_reinforce_free(gu_engine *h)
 {
     gu_release(h->d_rf_buf, h->d_rf_cnt);
     h->rf_cap = 0;
-    h->rf_key = 0;
+    gu_carry_release(h, GU_CARRY_REINFORCE);
 }
 
 extern "C" {
@@ -152,7 +149,7 @@ int gu_reinforce_run(gu_handle h, int64_t T, int32_t L, double alpha_actor, doub
     GU_REQUIRE(std::isfinite(alpha_baseline), GU_ERR_INVALID, "alpha_baseline must be finite");
     int rc = gu_tabular_check(h, "gu_reinforce_run", T, -1, 0u, alpha_actor, gamma, flags);
     if (rc != GU_OK || T == 0) return rc;
-    GU_TRY(gu_episode_reserve(h, h->d_rf_buf, h->d_rf_cnt, h->rf_cap, h->rf_key, L));
+    GU_TRY(gu_episode_reserve(h, h->d_rf_buf, h->d_rf_cnt, h->rf_cap, GU_CARRY_REINFORCE, L));
     return gu_launch_reinforce(h, T, L, alpha_actor, alpha_baseline, gamma, flags);
 }
 
@@ -161,7 +158,7 @@ int gu_reinforce_get_episode(gu_handle h, int64_t env0, int64_t n, int32_t *sa, 
     GU_ENTER(h);
     GU_NEED_GRID(h);
     GU_TRY(gu_env_range(h, env0, n));
-    return gu_episode_read(h, h->d_rf_buf, h->d_rf_cnt, h->rf_key, GU_REINFORCE_MAX, env0, n, sa, reward, nullptr, false, count);
+    return gu_episode_read(h, h->d_rf_buf, h->d_rf_cnt, GU_CARRY_REINFORCE, GU_REINFORCE_MAX, env0, n, sa, reward, nullptr, false, count);
 }
 
 }  // extern "C"

@@ -191,7 +191,7 @@ static int gu_launch_search(gu_engine *h, int64_t T, int32_t M, int32_t D, doubl
     a.sim_steps = h->d_search_steps;
     const int rc = eps_sim_q16 == 65536u ? gu_tabular_launch(h, gu_search_kernel<true, true>, gu_search_kernel<true, false>, a)
                                          : gu_tabular_launch(h, gu_search_kernel<false, true>, gu_search_kernel<false, false>, a);
-    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags);
 }
 
 void gu_search_free(gu_engine *h) { gu_release(h->d_search_score, h->d_search_steps); }

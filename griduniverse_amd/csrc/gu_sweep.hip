@@ -265,7 +265,7 @@ static int gu_launch_sweep(gu_engine *h, int64_t T, int32_t P, double theta, dou
     a.hpos = h->d_sweep_pos;
     a.size = h->d_sweep_size;
     const int rc = gu_tabular_launch(h, gu_sweep_kernel<true>, gu_sweep_kernel<false>, a);
-    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, false);
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags);
 }
 
 // (the queue lives and dies with the model: gu_dyna_free releases both, gu_dyna_init clears both)

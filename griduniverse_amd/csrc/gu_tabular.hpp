@@ -1,6 +1,8 @@
-// gu_tabular.hpp -- the core of the batched tabular learners for gfx950 (gu_td.hip: Q-learning and SARSA; gu_dyna.hip: Dyna-Q; gu_sweep.hip: prioritized sweeping;
-// gu_nstep.hip: n-step Q-learning and SARSA; gu_lambda.hip: SARSA(lambda) and Watkins's Q(lambda)); gu_fa.hip (semi-gradient
-// SARSA / Q-learning on features) uses the lane without its table.
+// gu_tabular.hpp -- the core of the batched tabular learners for gfx950 (gu_td.hip: Q-learning, SARSA and Expected SARSA; gu_dyna.hip:
+// Dyna-Q; gu_sweep.hip: prioritized sweeping; gu_nstep.hip: n-step Q-learning and SARSA; gu_lambda.hip: SARSA(lambda) and Watkins's
+// Q(lambda); gu_search.hip: rollout search; gu_explore.hip: UCB / Thompson; gu_mcts.hip: tree search; gu_is.hip: off-policy
+// Monte-Carlo; gu_ac.hip: actor-critic; gu_reinforce.hip: REINFORCE with baseline); gu_double.hip (Double Q-learning, on a pair of
+// tables) and gu_fa.hip (semi-gradient SARSA / Q-learning on features) use the lane without its table.
 // N independent learners, learner e owns env e and its own float64 table Q_e[S][4], advanced T real steps per launch.  The
 // semantics are build-defined (the reference has no tabular code) and stated in include/gu.h (gu_td_run, gu_dyna_run, gu_nstep_run).
 //
@@ -345,29 +347,30 @@ static int gu_env_copy(gu_engine *h, hipMemcpyKind dir, const T *host, T *dev, i
 }
 
 // ---- episode buffers (gu_reinforce.hip, gu_is.hip): step-major [cap][N] entries of 8 bytes {s*4+a, word} and [N] counts ----
-// storage for L entries per env, allocated on first use (a call with another L drops the buffer anyway: nothing to keep)
-static int gu_episode_reserve(gu_engine *h, int32_t *&buf, int32_t *&cnt, int32_t &cap, int32_t &key, int32_t L)
+// storage for L entries per env of the learner `owner` (GU_CARRY_*), allocated on first use (a call with another L drops the buffer
+// anyway: nothing to keep)
+static int gu_episode_reserve(gu_engine *h, int32_t *&buf, int32_t *&cnt, int32_t &cap, int owner, int32_t L)
 {
     if (cap >= L) return GU_OK;
     const size_t slots = (size_t)h->N * (size_t)L;
     GU_HIP(hipStreamSynchronize(h->stream));
-    const int rc = gu_tabular_fits(h, slots * 2 * sizeof(int32_t) + (size_t)h->N * sizeof(int32_t), "episode buffers");
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_tabular_fits(h, slots * 2 * sizeof(int32_t) + (size_t)h->N * sizeof(int32_t), "episode buffers"));
     gu_release(buf, cnt);
     cap = 0;
-    key = 0;
+    gu_carry_release(h, owner);
     GU_HIP(hipMalloc(&buf, slots * 2 * sizeof(int32_t)));
     GU_HIP(hipMalloc(&cnt, (size_t)h->N * sizeof(int32_t)));
     cap = L;
     return GU_OK;
 }
 
-// The buffers of envs env0 .. env0+n-1 as [n][pitch] rows, entries behind an env's count as -1 / 0.  L entries per env are live
-// (0: the buffer was dropped and reads as empty, whatever the device copy still holds).  The entry's word is the reward, or, `packed`,
-// reward * 8 + class.
-static int gu_episode_read(gu_engine *h, const int32_t *buf, const int32_t *cnt, int32_t L, int32_t pitch, int64_t env0, int64_t n,
+// The buffers of envs env0 .. env0+n-1 of the learner `owner` (GU_CARRY_*) as [n][pitch] rows, entries behind an env's count as
+// -1 / 0.  The L entries per env of its carry are live (it owns none: the buffer was dropped and reads as empty, whatever the device
+// copy still holds).  The entry's word is the reward, or, `packed`, reward * 8 + class.
+static int gu_episode_read(gu_engine *h, const int32_t *buf, const int32_t *cnt, int owner, int32_t pitch, int64_t env0, int64_t n,
                            int32_t *sa, int32_t *reward, int32_t *cls, bool packed, int32_t *count)
 {
+    const int32_t L = gu_carry_key(h, owner);
     std::vector<int32_t> c(n), w((size_t)n * (size_t)L * 2);
     GU_HIP(hipStreamSynchronize(h->stream));
     if (n && L) {
@@ -467,15 +470,13 @@ static int gu_tabular_launch(gu_engine *h, void (*lds)(A), void (*l2)(A), const 
     return GU_OK;
 }
 
-// after a launch of T steps: the engine's step count, carried SARSA action (the caller sets gu_nstep_run's window carry), rows and
-// statistics, and the agent trail
-static inline int gu_tabular_after(gu_engine *h, int64_t T, uint32_t flags, bool sarsa)
+// after a launch of T steps: the engine's step count, what the launch leaves for the next one of its kind (`leave`; nothing: every
+// carry ends here), rows and statistics, and the agent trail (an error of the trail's still leaves the carry: the launch ran)
+static inline int gu_tabular_after(gu_engine *h, int64_t T, uint32_t flags, GuCarry leave = {})
 {
     const bool traj = flags & GU_F_TRAJECTORY;
-    h->steps_taken += (uint64_t)T;
-    h->entry_table_ok = false;
-    gu_tabular_drop_carry(h);
-    h->td_carry = sarsa;
+    gu_envs_touched(h, (uint64_t)T);
+    h->carry = leave;
     if (traj) h->traj_written = 1;
     const int rc = gu_trail_after_rollout(h, T, traj ? 1 : 0, true);
     if (rc == GU_OK) {

@@ -87,7 +87,7 @@ static int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, d
     TdArgs a{};
     gu_tabular_args(h, a, T, alpha, gamma, eps_q16, flags);
     a.next_a = h->d_td_next;
-    a.carry = (method == 1 && h->td_carry) ? 1 : 0;
+    a.carry = (method == 1 && gu_carry_is(h, GU_CARRY_TD_SARSA, 0)) ? 1 : 0;
     // the overlay's instantiations, on [flags | reward | overlay]; fruit and doors learn on S << bits rows and keep the env's mask in `eaten`
     a.gust_q16 = a.fruit_values = h->overlay_param, a.rows = h->td_S, a.eaten = h->d_overlay_mask;
     if (h->overlay) a.cell = h->d_overlay_cell;
@@ -112,13 +112,14 @@ static int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, d
         rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true>, gu_td_kernel<TD_SARSA, false>, a)
                          : gu_tabular_launch(h, gu_td_kernel<TD_Q, true>, gu_td_kernel<TD_Q, false>, a);
     }
-    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, method == 1);
+    return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, method == 1 ? GuCarry{GU_CARRY_TD_SARSA, 0} : GuCarry{});
 }
 
 static void gu_td_free(gu_engine *h)
 {
     gu_release(h->d_q, h->d_td_next);
     h->td_S = 0;
+    gu_carry_release(h, GU_CARRY_TD_SARSA);
 }
 
 static void gu_td_drop(gu_engine *h)  // the Q tables and what hangs on them
@@ -169,15 +170,13 @@ int gu_td_init(gu_handle h, double q0)
     if (!h->d_q || h->td_S != rows) {
         GU_HIP(hipStreamSynchronize(h->stream));
         gu_td_free(h);
-        int rc = gu_tabular_fits(h, bytes, "Q tables");
-        if (rc != GU_OK) return rc;
+        GU_TRY(gu_tabular_fits(h, bytes, "Q tables"));
         GU_HIP(hipMalloc(&h->d_q, bytes));
         GU_HIP(hipMalloc(&h->d_td_next, (size_t)h->N));
         h->td_S = rows;
     }
     GU_HIP(hipMemsetAsync(h->d_td_next, 0xFF, (size_t)h->N, h->stream));
-    int rc = gu_td_fill(h, q0);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_td_fill(h, q0));
     GU_HIP(hipStreamSynchronize(h->stream));
     return GU_OK;
 }
@@ -215,16 +214,14 @@ static int gu_td_range(gu_engine *h, int64_t env0, int64_t n, const void *q)
 int gu_td_get_q(gu_handle h, int64_t env0, int64_t n, double *q)
 {
     GU_ENTER(h);
-    int rc = gu_td_range(h, env0, n, q);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_td_range(h, env0, n, q));
     return gu_env_copy(h, hipMemcpyDeviceToHost, q, h->d_q, env0, n, (size_t)h->td_S * 4);
 }
 
 int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q)
 {
     GU_ENTER(h);
-    int rc = gu_td_range(h, env0, n, q);
-    if (rc != GU_OK) return rc;
+    GU_TRY(gu_td_range(h, env0, n, q));
     gu_tabular_drop_carry(h);
     return gu_env_copy(h, hipMemcpyHostToDevice, q, h->d_q, env0, n, (size_t)h->td_S * 4);
 }

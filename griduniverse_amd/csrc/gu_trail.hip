@@ -129,13 +129,8 @@ int gu_trail_after_rollout(gu_engine *h, int64_t T, int traj, bool auto_reset)
 
 void gu_trail_free(gu_engine *h)
 {
-    if (h->d_trail) (void)hipFree(h->d_trail);
-    if (h->d_trail_len) (void)hipFree(h->d_trail_len);
-    if (h->d_trail_done) (void)hipFree(h->d_trail_done);
-    if (h->d_trail_alpha) (void)hipFree(h->d_trail_alpha);
-    h->d_trail = h->d_trail_len = h->d_trail_head = nullptr;
-    h->d_trail_done = nullptr;
-    h->d_trail_alpha = nullptr;
+    gu_release(h->d_trail, h->d_trail_len, h->d_trail_done, h->d_trail_alpha);
+    h->d_trail_head = nullptr;  // (lay in d_trail_len's allocation)
     h->trail_cap = 0;
 }
 
@@ -143,16 +138,12 @@ extern "C" {
 
 int gu_trail_enable(gu_handle h, int32_t capacity)
 {
-    int rc = gu_use_device(h);
-    if (rc != GU_OK) return rc;
+    GU_ENTER(h);
     GU_REQUIRE(capacity >= 0 && capacity <= 500, GU_ERR_INVALID, "trail capacity %d outside 0 .. 500 (env:92 keeps 500 states)", capacity);
     GU_REQUIRE(!(capacity && h->overlay), GU_ERR_UNSUPPORTED, "the agent trail and %s exclude each other: %s", GU_OVERLAY_NAME[h->overlay], GU_OVERLAY_IS_SET[h->overlay]);
     GU_HIP(hipStreamSynchronize(h->stream));
     gu_trail_free(h);
-    if (h->graph_exec) {  // a captured step graph does not carry the trail kernels (or carries them although the trail is off now)
-        (void)hipGraphExecDestroy(h->graph_exec);
-        h->graph_exec = nullptr;
-    }
+    gu_graph_drop(h);  // a captured step graph does not carry the trail kernels (or carries them although the trail is off now)
     if (!capacity) return GU_OK;
     const size_t n = (size_t)h->N;
     GU_HIP(hipMalloc(&h->d_trail, n * (size_t)capacity * sizeof(int32_t)));
@@ -177,8 +168,7 @@ int gu_trail_enable(gu_handle h, int32_t capacity)
 
 int gu_trail_read(gu_handle h, int64_t env0, int64_t n_envs, int32_t *cells, int32_t *length)
 {
-    int rc = gu_use_device(h);
-    if (rc != GU_OK) return rc;
+    GU_ENTER(h);
     GU_REQUIRE(h->trail_cap > 0, GU_ERR_STATE, "the trail is off: call gu_trail_enable first");
     GU_REQUIRE(cells && length && env0 >= 0 && n_envs > 0 && env0 + n_envs <= h->N, GU_ERR_INVALID, "env range [%lld,%lld) outside the batch, or a NULL pointer",
                (long long)env0, (long long)(env0 + n_envs));

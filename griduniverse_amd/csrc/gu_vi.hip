@@ -1041,7 +1041,6 @@ int gu_vi_sweep_step(gu_handle h, double gamma, uint32_t flags, double *delta)
     GU_ENTER(h);
     GU_NO_OVERLAY(h, "gu_vi_sweep_step");
     vi_withdraw_host_tables(h);
-    h->entry_table_ok = false;  // (the fused launches step the envs: their state is consistent too, but only rollouts vouch for it)
     GU_NEED_VI(h);
     GU_REQUIRE((flags & ~GU_F_AUTO_RESET) == 0, GU_ERR_INVALID, "gu_vi_sweep_step accepts only GU_F_AUTO_RESET");
     GU_REQUIRE(!h->trail_cap, GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): the fused sweep + step launches do not feed it");
@@ -1053,8 +1052,7 @@ int gu_vi_sweep_step(gu_handle h, double gamma, uint32_t flags, double *delta)
     GU_HIP(hipGetLastError());
     h->vi_cur ^= 1;
     h->greedy_valid = false;
-    h->steps_taken += 1;
-    gu_tabular_drop_carry(h);
+    gu_envs_touched(h, 1);  // (the fused launches step the envs: their state is consistent too, but only rollouts vouch for it)
     if (delta) {
         unsigned long long key = 0;
         GU_TRY(gu_read_back(h, &key, h->d_delta, sizeof key));
@@ -1068,7 +1066,6 @@ int gu_vi_sweep_step_run(gu_handle h, double gamma, int32_t iters, uint32_t flag
     GU_ENTER(h);
     GU_NO_OVERLAY(h, "gu_vi_sweep_step_run");
     vi_withdraw_host_tables(h);
-    h->entry_table_ok = false;
     GU_NEED_VI(h);
     GU_REQUIRE((flags & ~GU_F_AUTO_RESET) == 0, GU_ERR_INVALID, "gu_vi_sweep_step_run accepts only GU_F_AUTO_RESET");
     GU_REQUIRE(!h->trail_cap, GU_ERR_UNSUPPORTED, "the agent trail is on (gu_trail_enable): the fused sweep + step launches do not feed it");
@@ -1130,8 +1127,7 @@ int gu_vi_sweep_step_run(gu_handle h, double gamma, int32_t iters, uint32_t flag
             if (deltas) vi_unkey_n(back.data() + 8, (size_t)iters, deltas);
             if (iters & 1) std::swap(h->d_v[0], h->d_v[1]);
             h->greedy_valid = false;
-            h->steps_taken += (uint64_t)iters;
-            gu_tabular_drop_carry(h);
+            gu_envs_touched(h, (uint64_t)iters);
             h->vi_run_form = 2;
             return GU_OK;
         }

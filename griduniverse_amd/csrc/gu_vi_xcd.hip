@@ -1032,13 +1032,9 @@ int gu_vi_xcd_fused_run(gu_engine *h, const GuXcdPlan &xp, double gamma, int32_t
         std::swap(h->d_episode, h->d_episode_alt);
         std::swap(h->d_done_bits, h->d_done_bits_alt);
         h->done_bits_valid = true;
-        if (h->graph_exec) {  // (a captured step graph carries the old arrays in its arguments)
-            (void)hipGraphExecDestroy(h->graph_exec);
-            h->graph_exec = nullptr;
-        }
+        gu_graph_drop(h);  // (a captured step graph carries the old arrays in its arguments)
         h->greedy_valid = false;
-        h->steps_taken += (uint64_t)n;
-        gu_tabular_drop_carry(h);
+        gu_envs_touched(h, (uint64_t)n);
         total += n;
     }
     return GU_OK;
