@@ -102,6 +102,7 @@ SIGNATURES = {
     'gu_read_stats': [_vp, _vp, _vp],
     'gu_get_state': [_vp, _vp, _vp, _vp, _vp],
     'gu_set_state': [_vp, _vp, _vp, _vp, _vp],
+    'gu_get_stores': [_vp, _i32, _vp, _vp],
     'gu_done_indices': [_vp, _vp, _vp],
     'gu_look_step_ahead': [_vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
     'gu_td_init': [_vp, _f64],

@@ -12,7 +12,7 @@ update waiting for them, takes its planning updates from the top and queues the 
 """
 import math
 
-from .temporal_difference import _learn
+from ._batch import learn, need_learners, need_steps, unit
 
 MAX_PLANNING_STEPS = 256
 MAX_SWEEP_STATES = 16384  # the queue's keys hold the pair index s*4+a in 16 bits
@@ -23,17 +23,13 @@ def dyna_q(env, num_steps, planning_steps=10, alpha=0.1, discount_factor=0.99, e
     """Epsilon-greedy Dyna-Q, `num_steps` real env steps per learner (episodes restart at a start cell when they end), each
     followed by `planning_steps` model updates (0 .. 256; 0 is Q-learning).  Returns Q float64[S][4], or [L][S][4] for
     L = num_learners > 1."""
-    L, P = int(num_learners), int(planning_steps)
-    if L < 1:
-        raise ValueError('num_learners must be at least 1')
+    L, P = need_learners(num_learners), int(planning_steps)
     if not 0 <= P <= MAX_PLANNING_STEPS:
         raise ValueError('planning_steps must lie in 0 .. {}'.format(MAX_PLANNING_STEPS))
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
-    if int(num_steps) < 0:
-        raise ValueError('num_steps must not be negative')
-    return _learn(env, L, seed, q0, num_steps, max(1, _UPDATES // (P + 1)),
-                  lambda vec, T: vec.dyna_run(T, P, alpha, discount_factor, epsilon), model=True)
+    unit('epsilon', epsilon)
+    need_steps(num_steps)
+    return learn(env, L, seed, num_steps, max(1, _UPDATES // (P + 1)), lambda vec: (vec._ensure_q(q0), vec._ensure_model()),
+                 lambda vec, T: vec.dyna_run(T, P, alpha, discount_factor, epsilon))
 
 
 def prioritized_sweeping(env, num_steps, planning_steps=10, theta=1e-4, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0,
@@ -42,20 +38,14 @@ def prioritized_sweeping(env, num_steps, planning_steps=10, theta=1e-4, alpha=0.
     A real step queues its pair when its |TD error| exceeds `theta` (finite, not negative) and is followed by up to `planning_steps`
     (0 .. 256) updates from the top of the learner's priority queue, each of which queues the predecessors of its pair; a real step
     updates nothing by itself.  Returns Q float64[S][4], or [L][S][4] for L = num_learners > 1."""
-    L, P, theta = int(num_learners), int(planning_steps), float(theta)
-    if L < 1:
-        raise ValueError('num_learners must be at least 1')
+    L, P, theta = need_learners(num_learners), int(planning_steps), float(theta)
     if not 0 <= P <= MAX_PLANNING_STEPS:
         raise ValueError('planning_steps must lie in 0 .. {}'.format(MAX_PLANNING_STEPS))
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
+    unit('epsilon', epsilon)
     if not (math.isfinite(theta) and theta >= 0.0):
         raise ValueError('theta must be finite and not negative')
-    if int(num_steps) < 0:
-        raise ValueError('num_steps must not be negative')
+    need_steps(num_steps)
     if int(env.world.size) > MAX_SWEEP_STATES:
         raise ValueError('prioritized sweeping takes grids of at most {} states'.format(MAX_SWEEP_STATES))
-
-    def launch(vec, T):
-        vec.sweep_run(T, P, theta, alpha, discount_factor, epsilon)
-    return _learn(env, L, seed, q0, num_steps, max(1, _UPDATES // (P + 1)), launch)
+    return learn(env, L, seed, num_steps, max(1, _UPDATES // (P + 1)), lambda vec: vec._ensure_q(q0),
+                 lambda vec, T: vec.sweep_run(T, P, theta, alpha, discount_factor, epsilon))

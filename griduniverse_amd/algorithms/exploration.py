@@ -14,7 +14,7 @@ vectors can be installed with `VecGridUniverse.set_exploration`.  The results ha
 import numpy as np
 
 from .. import _lib
-from .temporal_difference import _CHUNK, _learn
+from ._batch import _CHUNK, learn, need_learners, need_steps, unit
 
 IRWIN_HALL_VARIANCE = 21845.0  # of the sum of four uniform bytes, 4 * (256 ** 2 - 1) / 12: the kernel's z_b before scaling
 
@@ -51,20 +51,11 @@ def thompson_tables(sigma=1.0, size=1024):
 
 
 def _explore(rule, tables, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0):
-    if int(num_learners) < 1:
-        raise ValueError('num_learners must be at least 1')
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
-    if int(num_steps) < 0:
-        raise ValueError('num_steps must not be negative')
-    U, B = tables
-
-    def launch(vec, T):
-        if not vec._explore_tables:
-            vec.set_exploration(U, B)
-        vec.explore_run(T, rule, alpha, discount_factor, epsilon)
-
-    return _learn(env, num_learners, seed, q0, num_steps, _CHUNK, launch)
+    need_learners(num_learners)
+    unit('epsilon', epsilon)
+    need_steps(num_steps)
+    return learn(env, num_learners, seed, num_steps, _CHUNK, lambda vec: (vec._ensure_q(q0), vec.set_exploration(*tables)),
+                 lambda vec, T: vec.explore_run(T, rule, alpha, discount_factor, epsilon))
 
 
 def ucb_q_learning(env, num_steps, c=1.0, table_size=1024, alpha=0.1, discount_factor=0.99, epsilon=0.0, num_learners=1, seed=0, q0=0.0):

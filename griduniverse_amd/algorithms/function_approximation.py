@@ -12,8 +12,7 @@ are `sarsa` / `q_learning`.
 import numpy as np
 
 from .. import _lib
-from ..vec_env import VecGridUniverse
-from .temporal_difference import _CHUNK
+from ._batch import _CHUNK, learn, need_learners, unit
 
 
 def tile_coding(W, H, tilings, tile):
@@ -69,29 +68,16 @@ def view_features(env, radius):
 
 
 def _fa(method, env, num_steps, features, alpha, discount_factor, epsilon, num_learners, seed, w0):
-    L = int(num_learners)
-    if L < 1:
-        raise ValueError('num_learners must be at least 1')
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
+    need_learners(num_learners)
+    unit('epsilon', epsilon)
     if features is None:
         features = tile_coding(env.x_max, env.y_max, 4, 4)
     phi, F = features
     phi = np.asarray(phi)
     K = 1 if phi.ndim == 1 else phi.shape[1]
-    vec = VecGridUniverse(L, template=env, seed=seed)
-    try:
-        vec.set_features(phi, F, w0)
-        vec.reset()
-        left = int(num_steps)
-        while left > 0:  # consecutive launches carry SARSA's next action, so chunking changes nothing
-            T = min(left, _CHUNK)
-            vec.fa_run(T, method, float(alpha) / K, discount_factor, epsilon)
-            left -= T
-        q = vec.fa_q_table()
-    finally:
-        vec.close()
-    return q[0] if L == 1 else q
+    # consecutive launches carry SARSA's next action, so chunking changes nothing
+    return learn(env, num_learners, seed, num_steps, _CHUNK, lambda vec: vec.set_features(phi, F, w0),
+                 lambda vec, T: vec.fa_run(T, method, float(alpha) / K, discount_factor, epsilon), lambda vec: vec.fa_q_table())
 
 
 def semi_gradient_sarsa(env, num_steps, features=None, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, w0=0.0):

@@ -13,18 +13,16 @@ long `max_episode_len` -- it is slower than Q-learning; that is the textbook wea
 """
 import numpy as np
 
-from ..vec_env import VecGridUniverse, check_off_policy_args
-
-_CHUNK = 100000  # steps per launch (the launch limit is 1e8; shorter launches keep the device responsive)
+from ..vec_env import _q16, check_off_policy_args
+from ._batch import _CHUNK, learn, need_finite, need_learners, need_steps, unit
 
 
 def ratio_table(epsilon):
     """float64[5, 5]: R[m][c] = pi(a|s) / b(a|s) of gu_is_run for an action that is one of m (1 .. 4) maxima of its row now and was
     one of c maxima when the epsilon-greedy behaviour took it (c = 0: none of them); row 0 is unused and zero.  The bytes are the
     ones the library computes from eps_q16 = round(epsilon * 65536) (include/gu.h)."""
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
-    eps = int(round(float(epsilon) * 65536)) / 65536.0
+    unit('epsilon', epsilon)
+    eps = _q16(epsilon) / 65536.0
     R = np.zeros((5, 5), np.float64)
     for c in range(5):
         b = eps * 0.25 if c == 0 else (1.0 - eps) / c + eps * 0.25
@@ -41,25 +39,10 @@ def off_policy_mc_control(env, num_steps, max_episode_len=64, discount_factor=0.
     its weight reaches `w_cap` (1 .. 2**256; small values give truncated importance sampling).  Transitions still in a learner's
     buffer after the last step are not learned from.  Returns Q float64[S][4], or [L][S][4] for L = num_learners > 1, as
     `q_learning` does."""
-    L = int(num_learners)
-    if L < 1:
-        raise ValueError('num_learners must be at least 1')
-    if int(num_steps) < 0:
-        raise ValueError('num_steps must not be negative')
+    need_learners(num_learners)
+    need_steps(num_steps)
     check_off_policy_args(max_episode_len, epsilon, w_cap)
-    for name, x in (('discount_factor', discount_factor), ('q0', q0)):
-        if not np.isfinite(float(x)):
-            raise ValueError('{} must be finite'.format(name))
-    vec = VecGridUniverse(L, template=env, seed=seed)
-    try:
-        vec._ensure_q(q0)
-        vec.reset()
-        left = int(num_steps)
-        while left > 0:  # (consecutive launches carry the episode buffer, so chunking changes nothing)
-            T = min(left, _CHUNK)
-            vec.off_policy_mc_run(T, max_episode_len, discount_factor, epsilon, w_cap)
-            left -= T
-        q = vec.q_table()
-    finally:
-        vec.close()
-    return q[0] if L == 1 else q
+    need_finite(discount_factor=discount_factor, q0=q0)
+    # (consecutive launches carry the episode buffer, so chunking changes nothing)
+    return learn(env, num_learners, seed, num_steps, _CHUNK, lambda vec: vec._ensure_q(q0),
+                 lambda vec, T: vec.off_policy_mc_run(T, max_episode_len, discount_factor, epsilon, w_cap))

@@ -14,39 +14,31 @@ when its episode ends, or after `max_episode_len` steps, where the return bootst
 """
 import numpy as np
 
-from ..vec_env import VecGridUniverse
+from .. import _lib
+from ._batch import _CHUNK, learn, need_finite, need_learners, need_steps
 
-_CHUNK = 100000  # steps per launch (the launch limit is 1e8; shorter launches keep the device responsive)
-_REINFORCE_MAX = 1024  # GU_REINFORCE_MAX
+
+def _softmax_learner(env, num_learners, seed, num_steps, launch):
+    """What actor_critic and reinforce share: tables of zeros, `launch` in chunks (the learners carry nothing, or their episode buffer,
+    from one launch to the next, so chunking changes nothing), and the result (policy, V) with the rows of terminal states zero."""
+    terminal = np.array([bool(env.is_terminal(s)) for s in range(env.world.size)])
+
+    def read(vec):
+        policy = vec.softmax_policy()
+        policy[:, terminal] = 0.0
+        return policy, vec.state_values()
+
+    return learn(env, num_learners, seed, num_steps, _CHUNK, lambda vec: vec._ensure_ac(0.0, 0.0), launch, read)
 
 
 def actor_critic(env, num_steps, actor_lr=0.1, critic_lr=0.1, discount_factor=0.99, num_learners=1, seed=0):
     """One-step actor-critic, `num_steps` env steps per learner (episodes restart at a start cell when they end), tables of
     zeros at the start.  Returns (policy, V): the softmax policy float64[S][4] with the rows of terminal states zero, and the
     critic's values float64[S]; [L][S][4] and [L][S] for L = num_learners > 1."""
-    L = int(num_learners)
-    if L < 1:
-        raise ValueError('num_learners must be at least 1')
-    if int(num_steps) < 0:
-        raise ValueError('num_steps must not be negative')
-    for name, x in (('actor_lr', actor_lr), ('critic_lr', critic_lr), ('discount_factor', discount_factor)):
-        if not np.isfinite(float(x)):
-            raise ValueError('{} must be finite'.format(name))
-    vec = VecGridUniverse(L, template=env, seed=seed)
-    try:
-        vec._ensure_ac(0.0, 0.0)
-        vec.reset()
-        left = int(num_steps)
-        while left > 0:  # (the learner carries nothing from one launch to the next, so chunking changes nothing)
-            T = min(left, _CHUNK)
-            vec.actor_critic_run(T, actor_lr, critic_lr, discount_factor)
-            left -= T
-        policy, v = vec.softmax_policy(), vec.state_values()
-    finally:
-        vec.close()
-    terminal = np.array([bool(env.is_terminal(s)) for s in range(env.world.size)])
-    policy[:, terminal] = 0.0
-    return (policy[0], v[0]) if L == 1 else (policy, v)
+    need_learners(num_learners)
+    need_steps(num_steps)
+    need_finite(actor_lr=actor_lr, critic_lr=critic_lr, discount_factor=discount_factor)
+    return _softmax_learner(env, num_learners, seed, num_steps, lambda vec, T: vec.actor_critic_run(T, actor_lr, critic_lr, discount_factor))
 
 
 def reinforce(env, num_steps, max_episode_len=256, actor_lr=0.003, baseline_lr=0.1, discount_factor=0.99, num_learners=1, seed=0):
@@ -54,28 +46,10 @@ def reinforce(env, num_steps, max_episode_len=256, actor_lr=0.003, baseline_lr=0
     running after `max_episode_len` steps is learned from there and goes on), tables of zeros at the start.  Transitions still
     in a learner's buffer after the last step are not learned from.  Returns (policy, V) in `actor_critic`'s format, V being the
     baseline.  The default rates are small on purpose: an update is scaled by a whole-episode return, not by a one-step error."""
-    L = int(num_learners)
-    if L < 1:
-        raise ValueError('num_learners must be at least 1')
-    if int(num_steps) < 0:
-        raise ValueError('num_steps must not be negative')
-    if not 1 <= int(max_episode_len) <= _REINFORCE_MAX:
-        raise ValueError('max_episode_len must lie in 1 .. {}'.format(_REINFORCE_MAX))
-    for name, x in (('actor_lr', actor_lr), ('baseline_lr', baseline_lr), ('discount_factor', discount_factor)):
-        if not np.isfinite(float(x)):
-            raise ValueError('{} must be finite'.format(name))
-    vec = VecGridUniverse(L, template=env, seed=seed)
-    try:
-        vec._ensure_ac(0.0, 0.0)
-        vec.reset()
-        left = int(num_steps)
-        while left > 0:  # (consecutive launches carry the episode buffer, so chunking changes nothing)
-            T = min(left, _CHUNK)
-            vec.reinforce_run(T, max_episode_len, actor_lr, baseline_lr, discount_factor)
-            left -= T
-        policy, v = vec.softmax_policy(), vec.state_values()
-    finally:
-        vec.close()
-    terminal = np.array([bool(env.is_terminal(s)) for s in range(env.world.size)])
-    policy[:, terminal] = 0.0
-    return (policy[0], v[0]) if L == 1 else (policy, v)
+    need_learners(num_learners)
+    need_steps(num_steps)
+    if not 1 <= int(max_episode_len) <= _lib.REINFORCE_MAX:
+        raise ValueError('max_episode_len must lie in 1 .. {}'.format(_lib.REINFORCE_MAX))
+    need_finite(actor_lr=actor_lr, baseline_lr=baseline_lr, discount_factor=discount_factor)
+    return _softmax_learner(env, num_learners, seed, num_steps,
+                            lambda vec, T: vec.reinforce_run(T, max_episode_len, actor_lr, baseline_lr, discount_factor))

@@ -17,7 +17,7 @@ the root action with the largest mean return.  `uct_tables` builds the UCB1 sche
 import numpy as np
 
 from .. import _lib
-from .temporal_difference import _learn
+from ._batch import learn, need_learners, need_steps, unit
 
 _MOVES = 1000000  # real steps x (1 + 4 x simulations x depth) moves per launch (the launch limit is 1e8; shorter launches keep the device responsive)
 
@@ -28,21 +28,16 @@ def rollout_search(env, num_steps, simulations=4, depth=16, alpha=0.1, discount_
     env steps per learner (episodes restart at a start cell when they end).  `simulations` (0 .. 64; 0 is `q_learning`) rollouts
     per action, `depth` (0 .. 256) simulated moves each, under an epsilon-greedy rollout policy on the learner's table
     (`rollout_epsilon`; 1.0 = uniformly random).  Returns Q float64[S][4], or [L][S][4] for L = num_learners > 1."""
-    L, M, D = int(num_learners), int(simulations), int(depth)
-    if L < 1:
-        raise ValueError('num_learners must be at least 1')
+    L, M, D = need_learners(num_learners), int(simulations), int(depth)
     if not 0 <= M <= _lib.SEARCH_MAX_M:
         raise ValueError('simulations must lie in 0 .. {}'.format(_lib.SEARCH_MAX_M))
     if not 0 <= D <= _lib.SEARCH_MAX_D:
         raise ValueError('depth must lie in 0 .. {}'.format(_lib.SEARCH_MAX_D))
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
-    if not 0.0 <= float(rollout_epsilon) <= 1.0:
-        raise ValueError('rollout_epsilon must lie in [0, 1]')
-    if int(num_steps) < 0:
-        raise ValueError('num_steps must not be negative')
-    return _learn(env, L, seed, q0, num_steps, max(1, _MOVES // (1 + 4 * M * D)),
-                  lambda vec, T: vec.search_run(T, M, D, alpha, discount_factor, epsilon, rollout_epsilon))
+    unit('epsilon', epsilon)
+    unit('rollout_epsilon', rollout_epsilon)
+    need_steps(num_steps)
+    return learn(env, L, seed, num_steps, max(1, _MOVES // (1 + 4 * M * D)), lambda vec: vec._ensure_q(q0),
+                 lambda vec, T: vec.search_run(T, M, D, alpha, discount_factor, epsilon, rollout_epsilon))
 
 
 def uct_tables(c=3.0, size=256):
@@ -71,26 +66,16 @@ def tree_search(env, num_steps, simulations=64, tree_depth=8, depth=4, c=3.0, al
     selection down to `tree_depth` (1 .. 64) levels, rollouts of `depth` (0 .. 256) moves under an epsilon-greedy policy on the
     learner's table (`rollout_epsilon`; 1.0 = uniformly random), UCB1 with constant `c`.  Returns Q float64[S][4], or [L][S][4]
     for L = num_learners > 1."""
-    L, M, H, D = int(num_learners), int(simulations), int(tree_depth), int(depth)
-    if L < 1:
-        raise ValueError('num_learners must be at least 1')
+    L, M, H, D = need_learners(num_learners), int(simulations), int(tree_depth), int(depth)
     if not 0 <= M <= _lib.MCTS_MAX_SIMS:
         raise ValueError('simulations must lie in 0 .. {}'.format(_lib.MCTS_MAX_SIMS))
     if not 1 <= H <= _lib.MCTS_MAX_DEPTH:
         raise ValueError('tree_depth must lie in 1 .. {}'.format(_lib.MCTS_MAX_DEPTH))
     if not 0 <= D <= _lib.SEARCH_MAX_D:
         raise ValueError('depth must lie in 0 .. {}'.format(_lib.SEARCH_MAX_D))
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
-    if not 0.0 <= float(rollout_epsilon) <= 1.0:
-        raise ValueError('rollout_epsilon must lie in [0, 1]')
-    if int(num_steps) < 0:
-        raise ValueError('num_steps must not be negative')
+    unit('epsilon', epsilon)
+    unit('rollout_epsilon', rollout_epsilon)
+    need_steps(num_steps)
     tables = uct_tables(c, max(256, M + 1))
-
-    def launch(vec, T):
-        if not vec._tree_tables:
-            vec.set_tree_search(*tables)
-        vec.tree_search_run(T, M, H, D, alpha, discount_factor, epsilon, rollout_epsilon)
-
-    return _learn(env, L, seed, q0, num_steps, max(1, _MOVES // (1 + M * (H + D))), launch)
+    return learn(env, L, seed, num_steps, max(1, _MOVES // (1 + M * (H + D))), lambda vec: (vec._ensure_q(q0), vec.set_tree_search(*tables)),
+                 lambda vec, T: vec.tree_search_run(T, M, H, D, alpha, discount_factor, epsilon, rollout_epsilon))

@@ -16,53 +16,13 @@ csrc/gu_double.hip.
 import numpy as np
 
 from .. import _lib
-from ..vec_env import VecGridUniverse
-
-_CHUNK = 100000  # steps per launch (the launch limit is 1e8; shorter launches keep the device responsive)
-
-
-def _learn(env, num_learners, seed, q0, num_steps, chunk, launch, model=False, wind=None, gust=0.0, fruit=None, doors=None, pairs=False):
-    """The learner batch of q_learning / sarsa / n_step_* / *_lambda / dyna_q: L learners on the grid of `env`, tables of q0 (and empty models when
-    `model`), `num_steps` real steps each in launches `launch(vec, T)` of at most `chunk` steps.  Returns Q [S][4] or [L][S][4].
-    `wind`: a strength array or a (strength, direction) pair for VecGridUniverse.set_wind, with `gust`.  `fruit`: (cells, kinds,
-    values) for VecGridUniverse.set_fruit; the tables then have S << F rows.  `doors`: dict(doors=, keys=, levers=) for
-    VecGridUniverse.set_doors; the tables then have S << D rows.  `pairs`: the learner is Double Q-learning -- pairs of tables of q0, and
-    the result is [S][2][4] or [L][S][2][4]."""
-    L = int(num_learners)
-    vec = VecGridUniverse(L, template=env, seed=seed)
-    try:
-        if wind is not None:
-            strength, direction = wind if isinstance(wind, tuple) else (wind, 'up')
-            vec.set_wind(strength, direction, gust)
-        if fruit is not None:
-            vec.set_fruit(*fruit)
-        if doors is not None:
-            vec.set_doors(doors['doors'], doors.get('keys'), doors.get('levers'))
-        if pairs:
-            vec._ensure_pairs(q0)
-        else:
-            vec._ensure_q(q0)
-        if model:
-            vec._ensure_model()
-        vec.reset()
-        left = int(num_steps)
-        while left > 0:
-            T = min(left, chunk)
-            launch(vec, T)
-            left -= T
-        q = vec.double_q_tables() if pairs else vec.q_table()
-    finally:
-        vec.close()
-    return q[0] if L == 1 else q
+from ._batch import _CHUNK, learn, need_learners, unit
 
 
 def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind=None, gust=0.0, fruit=None, doors=None):
-    if int(num_learners) < 1:
-        raise ValueError('num_learners must be at least 1')
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
-    if not 0.0 <= float(gust) <= 1.0:
-        raise ValueError('gust must lie in [0, 1]')
+    need_learners(num_learners)
+    unit('epsilon', epsilon)
+    unit('gust', gust)
     if fruit is not None:
         if wind is not None:
             raise ValueError('wind and fruit exclude each other')
@@ -73,8 +33,18 @@ def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, s
             raise ValueError('doors exclude wind and fruit')
         if not isinstance(doors, dict) or 'doors' not in doors or set(doors) - {'doors', 'keys', 'levers'}:
             raise ValueError('doors must be dict(doors=, keys=, levers=)')
-    return _learn(env, num_learners, seed, q0, num_steps, _CHUNK,
-                  lambda vec, T: vec.td_run(T, method, alpha, discount_factor, epsilon), wind=wind, gust=gust, fruit=fruit, doors=doors)
+
+    def prepare(vec):  # (the tables have S << F rows under fruit and S << D under doors: the overlay goes on before them)
+        if wind is not None:
+            strength, direction = wind if isinstance(wind, tuple) else (wind, 'up')
+            vec.set_wind(strength, direction, gust)
+        if fruit is not None:
+            vec.set_fruit(*fruit)
+        if doors is not None:
+            vec.set_doors(doors['doors'], doors.get('keys'), doors.get('levers'))
+        vec._ensure_q(q0)
+
+    return learn(env, num_learners, seed, num_steps, _CHUNK, prepare, lambda vec, T: vec.td_run(T, method, alpha, discount_factor, epsilon))
 
 
 def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None):
@@ -96,12 +66,10 @@ def expected_sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1,
     """Epsilon-greedy Expected SARSA (Sutton & Barto 6.6): acts as `q_learning` does and bootstraps on the mean of Q[s'] under the
     epsilon-greedy policy itself, so the target has no sampling noise from the next action.  `num_steps` env steps per learner.
     Returns Q float64[S][4], or [L][S][4] for L = num_learners > 1.  With epsilon = 0 it is `q_learning`.  The calm grid only."""
-    if int(num_learners) < 1:
-        raise ValueError('num_learners must be at least 1')
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
-    return _learn(env, num_learners, seed, q0, num_steps, _CHUNK,
-                  lambda vec, T: vec.expected_sarsa_run(T, alpha, discount_factor, epsilon))
+    need_learners(num_learners)
+    unit('epsilon', epsilon)
+    return learn(env, num_learners, seed, num_steps, _CHUNK, lambda vec: vec._ensure_q(q0),
+                 lambda vec, T: vec.expected_sarsa_run(T, alpha, discount_factor, epsilon))
 
 
 def double_q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):
@@ -109,25 +77,21 @@ def double_q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0
     on A + B, and a coin per step picks the table that learns from the other's estimate of its own greedy action.  `num_steps` env
     steps per learner.  Returns the MEAN of the two tables, (A + B) * 0.5, float64[S][4], or [L][S][4] for L = num_learners > 1
     (VecGridUniverse.double_q_tables gives the two apart).  The calm grid only."""
-    if int(num_learners) < 1:
-        raise ValueError('num_learners must be at least 1')
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
-    q = _learn(env, num_learners, seed, q0, num_steps, _CHUNK,
-               lambda vec, T: vec.double_q_run(T, alpha, discount_factor, epsilon), pairs=True)
+    need_learners(num_learners)
+    unit('epsilon', epsilon)
+    q = learn(env, num_learners, seed, num_steps, _CHUNK, lambda vec: vec._ensure_pairs(q0),
+              lambda vec, T: vec.double_q_run(T, alpha, discount_factor, epsilon), lambda vec: vec.double_q_tables())
     return (q[..., 0, :] + q[..., 1, :]) * 0.5
 
 
 def _nstep(method, env, num_steps, n, alpha, discount_factor, epsilon, num_learners, seed, q0):
     if not 1 <= int(n) <= _lib.NSTEP_MAX:
         raise ValueError('n must lie in 1 .. {}'.format(_lib.NSTEP_MAX))
-    if int(num_learners) < 1:
-        raise ValueError('num_learners must be at least 1')
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
+    need_learners(num_learners)
+    unit('epsilon', epsilon)
     # consecutive launches of one method and n carry the window, so chunking changes nothing
-    return _learn(env, num_learners, seed, q0, num_steps, _CHUNK,
-                  lambda vec, T: vec.nstep_run(T, n, method, alpha, discount_factor, epsilon))
+    return learn(env, num_learners, seed, num_steps, _CHUNK, lambda vec: vec._ensure_q(q0),
+                 lambda vec, T: vec.nstep_run(T, n, method, alpha, discount_factor, epsilon))
 
 
 def n_step_sarsa(env, num_steps, n=4, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):
@@ -145,17 +109,14 @@ def n_step_q_learning(env, num_steps, n=4, alpha=0.1, discount_factor=0.99, epsi
 def _lambda(method, env, num_steps, lam, trace_len, alpha, discount_factor, epsilon, num_learners, seed, q0):
     if not 1 <= int(trace_len) <= _lib.LAMBDA_MAX:
         raise ValueError('trace_len must lie in 1 .. {}'.format(_lib.LAMBDA_MAX))
-    if not 0.0 <= float(lam) <= 1.0:
-        raise ValueError('lam must lie in [0, 1]')
-    if int(num_learners) < 1:
-        raise ValueError('num_learners must be at least 1')
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
+    unit('lam', lam)
+    need_learners(num_learners)
+    unit('epsilon', epsilon)
     # a step costs up to trace_len entry updates, so launches get shorter as traces get longer; consecutive launches of one method
     # and trace_len carry the window, so chunking changes nothing
     chunk = min(_CHUNK, _CHUNK * 4 // int(trace_len))
-    return _learn(env, num_learners, seed, q0, num_steps, chunk,
-                  lambda vec, T: vec.lambda_run(T, lam, trace_len, method, alpha, discount_factor, epsilon))
+    return learn(env, num_learners, seed, num_steps, chunk, lambda vec: vec._ensure_q(q0),
+                 lambda vec, T: vec.lambda_run(T, lam, trace_len, method, alpha, discount_factor, epsilon))
 
 
 def sarsa_lambda(env, num_steps, lam=0.9, trace_len=32, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):

@@ -1082,6 +1082,33 @@ int gu_get_state(gu_handle h, int32_t *pos, int32_t *done, uint32_t *episode, ui
     return GU_OK;
 }
 
+int gu_get_stores(gu_handle h, int32_t capacity, int64_t *values, int32_t *count)
+{
+    GU_ENTER(h);
+    const int64_t w[GU_STORE_COUNT] = {
+        h->has_grid ? h->S : 0,                    // GU_STORE_S
+        h->n_grids,                                // GU_STORE_N_GRIDS
+        h->overlay,                                // GU_STORE_OVERLAY
+        h->overlay_bits,                           // GU_STORE_OVERLAY_BITS
+        GU_HAS_TD_Q(h) ? h->td_S : 0,              // GU_STORE_TD_ROWS
+        GU_HAS_PAIRS(h) ? h->dq_S : 0,             // GU_STORE_DOUBLE
+        GU_HAS_DYNA(h) ? h->dyna_S : 0,            // GU_STORE_DYNA
+        GU_HAS_SWEEP(h) ? 1 : 0,                   // GU_STORE_SWEEP
+        GU_HAS_COUNTS(h) ? h->explore_S : 0,       // GU_STORE_EXPLORE
+        GU_HAS_EXPLORE_TABLES(h) ? h->explore_C : 0,  // GU_STORE_EXPLORE_C
+        GU_HAS_POOLS(h) ? h->mcts_P : 0,           // GU_STORE_MCTS_NODES
+        GU_HAS_MCTS_TABLES(h) ? h->mcts_C : 0,     // GU_STORE_MCTS_C
+        GU_HAS_AC(h) ? h->ac_S : 0,                // GU_STORE_AC
+        GU_HAS_WEIGHTS(h) ? h->is_S : 0,           // GU_STORE_IS
+        GU_HAS_FA(h) ? h->fa_F : 0,                // GU_STORE_FA_F
+        GU_HAS_FA(h) ? h->fa_K : 0,                // GU_STORE_FA_K
+        h->trail_cap,                              // GU_STORE_TRAIL_CAP
+    };
+    if (count) *count = GU_STORE_COUNT;
+    if (values) std::copy(w, w + std::min<int32_t>(std::max<int32_t>(capacity, 0), GU_STORE_COUNT), values);
+    return GU_OK;
+}
+
 int gu_set_state(gu_handle h, const int32_t *pos, const int32_t *done, const uint32_t *episode, const uint64_t *tcount)
 {
     GU_ENTER(h);

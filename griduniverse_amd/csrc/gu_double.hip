@@ -97,7 +97,7 @@ void gu_double_free(gu_engine *h)
     h->dq_S = 0;
 }
 
-#define GU_NEED_PAIRS(h) GU_REQUIRE((h)->d_dq && (h)->dq_S == (h)->S, GU_ERR_STATE, "no pairs of Q tables: call gu_double_init first")
+#define GU_NEED_PAIRS(h) GU_REQUIRE(GU_HAS_PAIRS(h), GU_ERR_STATE, "no pairs of Q tables: call gu_double_init first")
 
 extern "C" {
 

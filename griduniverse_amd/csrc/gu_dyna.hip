@@ -153,7 +153,7 @@ void gu_dyna_free(gu_engine *h)
     h->dyna_exact = false;
 }
 
-#define GU_NEED_DYNA(h) GU_REQUIRE((h)->d_dyna_model && (h)->dyna_S == (h)->S, GU_ERR_STATE, "no Dyna-Q model: call gu_dyna_init first")
+#define GU_NEED_DYNA(h) GU_REQUIRE(GU_HAS_DYNA(h), GU_ERR_STATE, "no Dyna-Q model: call gu_dyna_init first")
 
 extern "C" {
 

@@ -144,7 +144,7 @@ void gu_explore_free(gu_engine *h)
     h->explore_S = 0;
 }
 
-#define GU_NEED_COUNTS(h) GU_REQUIRE((h)->d_explore_n && (h)->explore_S == (h)->S, GU_ERR_STATE, "no visit counts: call gu_explore_init first")
+#define GU_NEED_COUNTS(h) GU_REQUIRE(GU_HAS_COUNTS(h), GU_ERR_STATE, "no visit counts: call gu_explore_init first")
 
 extern "C" {
 
@@ -180,7 +180,7 @@ int gu_explore_run(gu_handle h, int64_t T, int32_t mode, double alpha, double ga
     GU_NEED_GRID(h);
     GU_NEED_Q(h);
     GU_NEED_COUNTS(h);
-    GU_REQUIRE(h->d_explore_tab && h->explore_C >= 2, GU_ERR_STATE, "no exploration tables: call gu_explore_set_tables first");
+    GU_REQUIRE(GU_HAS_EXPLORE_TABLES(h), GU_ERR_STATE, "no exploration tables: call gu_explore_set_tables first");
     GU_REQUIRE(mode == 0 || mode == 1, GU_ERR_INVALID, "mode %d: 0 = UCB, 1 = Thompson", mode);
     int rc = gu_tabular_check(h, "gu_explore_run", T, -1, eps_q16, alpha, gamma, flags);
     if (rc != GU_OK || T == 0) return rc;

@@ -275,7 +275,7 @@ void gu_fa_free(gu_engine *h)
     gu_carry_release(h, GU_CARRY_FA_SARSA);
 }
 
-#define GU_NEED_FA(h) GU_REQUIRE((h)->d_fa_w && (h)->fa_S == (h)->S, GU_ERR_STATE, "no features: call gu_fa_init first")
+#define GU_NEED_FA(h) GU_REQUIRE(GU_HAS_FA(h), GU_ERR_STATE, "no features: call gu_fa_init first")
 
 extern "C" {
 

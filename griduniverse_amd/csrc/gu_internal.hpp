@@ -530,6 +530,22 @@ void gu_fa_free(gu_engine *h);
 // state count go and take what hangs on them along (the SARSA actions, the n-step and lambda windows, the search scores, the node
 // pools), and so does every other store sized by another state count.  S == 0: the engine is being destroyed -- everything goes.
 void gu_learners_drop(gu_engine *h, int32_t S);
+// Whether a store is there for the grid (and, for the Q tables of gu_td_run, the mask bits) the engine has now.  The GU_NEED_* guard
+// of each module and the store's word of gu_get_stores (gu_api.hip) both ask these, so a caller that reads the word knows what the
+// guard will say.
+#define GU_TD_ROWS(h) ((int64_t)(h)->S << (h)->overlay_bits)  /* gu_td_run's rows: S << F under fruit, S << D under doors (64 bits: F runs to 32; gu_td_init keeps it below 2^31) */
+#define GU_HAS_TD_Q(h) ((h)->d_q && (int64_t)(h)->td_S == GU_TD_ROWS(h))
+#define GU_HAS_Q(h) ((h)->d_q && (h)->td_S == (h)->S)
+#define GU_HAS_PAIRS(h) ((h)->d_dq && (h)->dq_S == (h)->S)
+#define GU_HAS_DYNA(h) ((h)->d_dyna_model && (h)->dyna_S == (h)->S)
+#define GU_HAS_SWEEP(h) ((h)->d_sweep_heap && GU_HAS_DYNA(h))
+#define GU_HAS_COUNTS(h) ((h)->d_explore_n && (h)->explore_S == (h)->S)
+#define GU_HAS_EXPLORE_TABLES(h) ((h)->d_explore_tab && (h)->explore_C >= 2)
+#define GU_HAS_POOLS(h) ((h)->d_mcts_pool && (h)->mcts_P >= 2)
+#define GU_HAS_MCTS_TABLES(h) ((h)->d_mcts_tab && (h)->mcts_C >= 2)
+#define GU_HAS_AC(h) ((h)->d_ac_h && (h)->ac_S == (h)->S)
+#define GU_HAS_WEIGHTS(h) ((h)->d_is_c && (h)->is_S == (h)->S)
+#define GU_HAS_FA(h) ((h)->d_fa_w && (h)->fa_S == (h)->S)
 
 // ---- what the engine carries between calls (DESIGN.md "What the engine carries between calls") ----
 // Every call that touches the envs or a learner's tables ends what the learners carry from one launch to the next: gu_td_run's and

@@ -171,7 +171,7 @@ static void gu_is_ratios(uint32_t eps_q16, double *R)
     }
 }
 
-#define GU_NEED_WEIGHTS(h) GU_REQUIRE((h)->d_is_c && (h)->is_S == (h)->S, GU_ERR_STATE, "no cumulative weights: call gu_is_init first")
+#define GU_NEED_WEIGHTS(h) GU_REQUIRE(GU_HAS_WEIGHTS(h), GU_ERR_STATE, "no cumulative weights: call gu_is_init first")
 
 extern "C" {
 

@@ -322,7 +322,7 @@ void gu_mcts_free(gu_engine *h)
     h->mcts_P = 0;
 }
 
-#define GU_NEED_POOLS(h) GU_REQUIRE((h)->d_mcts_pool && (h)->mcts_P >= 2, GU_ERR_STATE, "no node pools: call gu_mcts_init first")
+#define GU_NEED_POOLS(h) GU_REQUIRE(GU_HAS_POOLS(h), GU_ERR_STATE, "no node pools: call gu_mcts_init first")
 
 extern "C" {
 
@@ -371,7 +371,7 @@ int gu_mcts_run(gu_handle h, int64_t T, int32_t M, int32_t H, int32_t D, double 
     GU_REQUIRE(H >= 1 && H <= GU_MCTS_MAX_DEPTH, GU_ERR_INVALID, "tree depth %d out of range (1 .. %d)", H, GU_MCTS_MAX_DEPTH);
     GU_REQUIRE(D >= 0 && D <= GU_SEARCH_MAX_D, GU_ERR_INVALID, "depth %d out of range (0 .. %d)", D, GU_SEARCH_MAX_D);
     GU_REQUIRE(eps_sim_q16 <= 65536u, GU_ERR_INVALID, "eps_sim_q16 %u above 65536", eps_sim_q16);
-    GU_REQUIRE(M == 0 || (h->d_mcts_tab && h->mcts_C >= 2), GU_ERR_STATE, "no tree-search tables: call gu_mcts_set_tables first");
+    GU_REQUIRE(M == 0 || GU_HAS_MCTS_TABLES(h), GU_ERR_STATE, "no tree-search tables: call gu_mcts_set_tables first");
     GU_TRY(gu_tabular_check(h, "gu_mcts_run", T, -1, eps_q16, alpha, gamma, flags));
     GU_TRY(gu_move_budget(T, 1 + (int64_t)M * (H + D), "1 + M (H + D)"));  // per real step, at most
     if (T == 0) return GU_OK;

@@ -270,7 +270,7 @@ static int gu_launch_sweep(gu_engine *h, int64_t T, int32_t P, double theta, dou
 
 // (the queue lives and dies with the model: gu_dyna_free releases both, gu_dyna_init clears both)
 #define GU_NEED_SWEEP(h) \
-    GU_REQUIRE((h)->d_sweep_heap && (h)->d_dyna_model && (h)->dyna_S == (h)->S, GU_ERR_STATE, "no priority queue: call gu_sweep_init first")
+    GU_REQUIRE(GU_HAS_SWEEP(h), GU_ERR_STATE, "no priority queue: call gu_sweep_init first")
 
 // empty queues, counters at zero (queued on the engine's stream; nothing to do without a queue)
 int gu_sweep_clear(gu_engine *h)

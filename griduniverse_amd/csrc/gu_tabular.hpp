@@ -279,12 +279,11 @@ struct TabLane {
 // the checks, copies and stores they have in common are here.
 
 // the tables that more than one learner's entry points need, present and of this grid's size
-#define GU_NEED_Q(h) GU_REQUIRE((h)->d_q && (h)->td_S == (h)->S, GU_ERR_STATE, "no Q tables: call gu_td_init first")
+#define GU_NEED_Q(h) GU_REQUIRE(GU_HAS_Q(h), GU_ERR_STATE, "no Q tables: call gu_td_init first")
 // ... gu_td_run and the table copies alone know the overlays' masks: S << F rows under fruit, S << D under doors (include/gu.h:
-// gu_set_fruit, gu_set_doors)
-#define GU_TD_ROWS(h) ((int64_t)(h)->S << (h)->overlay_bits)  /* (64 bits: F runs to 32; gu_td_init keeps it below 2^31) */
-#define GU_NEED_TD_Q(h) GU_REQUIRE((h)->d_q && (int64_t)(h)->td_S == GU_TD_ROWS(h), GU_ERR_STATE, "no Q tables: call gu_td_init first")
-#define GU_NEED_AC(h) GU_REQUIRE((h)->d_ac_h && (h)->ac_S == (h)->S, GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first")
+// gu_set_fruit, gu_set_doors; GU_TD_ROWS: gu_internal.hpp)
+#define GU_NEED_TD_Q(h) GU_REQUIRE(GU_HAS_TD_Q(h), GU_ERR_STATE, "no Q tables: call gu_td_init first")
+#define GU_NEED_AC(h) GU_REQUIRE(GU_HAS_AC(h), GU_ERR_STATE, "no actor-critic tables: call gu_ac_init first")
 
 // tables of `bytes` for the engine's envs: what is left has to hold the trajectory buffer and the scratch of other calls too, so
 // keep 1 GiB of headroom

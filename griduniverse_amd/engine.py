@@ -97,8 +97,6 @@ class Engine(object):
         check(self.lib.gu_set_grid(self._h, spec.W, spec.H, spec.words_per_row, ptr(p['wall']), ptr(p['goal']),
                                    ptr(p['lava']), ptr(p['rplus']), ptr(p['rminus']), ptr(starts), len(starts)))
         self.spec = spec
-        self._n_grids = 1
-        self._mask_bits = 0  # (a new grid drops the fruit or the doors)
 
     def set_grids(self, specs):
         """Several distinct grids of one shape: env e uses specs[e // (N // len(specs))]."""
@@ -119,16 +117,12 @@ class Engine(object):
                                     ptr(n_starts), max_starts))
         self.spec = specs[0]
         self.specs = list(specs)
-        self._n_grids = len(specs)
-        self._mask_bits = 0
 
     def generate_mazes(self, n_grids, W, H, maze_seed):
         """n_grids random mazes carved on the device (one per env group of N // n_grids envs)."""
         check(self.lib.gu_generate_mazes(self._h, int(n_grids), int(W), int(H), int(maze_seed) & 0xFFFFFFFFFFFFFFFF))
         self.spec = GridSpec(W, H, [0], [W * H - 1], [], [])  # shape holder; the real grids live on the device
         self.specs = None
-        self._n_grids = int(n_grids)
-        self._mask_bits = 0
 
     def get_cells(self, grid_index=0):
         """(flags uint8[S], reward int8[S], starts int32[n]) of one grid as compiled on the device."""
@@ -159,7 +153,6 @@ class Engine(object):
         f = None if fruit is None else _lib.as_array(fruit, np.uint8, (self.spec.S,), 'fruit')
         v = _lib.as_array(values, np.int32, (3,), 'values')
         check(self.lib.gu_set_fruit(self._h, ptr(f), ptr(v)))
-        self._mask_bits = 0 if f is None else int(np.count_nonzero(f))
 
     def get_fruit(self):
         """(fruit uint8[S], values int32[3]), or None while no fruit is set (gu_get_fruit)."""
@@ -191,7 +184,6 @@ class Engine(object):
         mask of open slots."""
         d = None if door is None else _lib.as_array(door, np.uint8, (self.spec.S,), 'door')
         check(self.lib.gu_set_doors(self._h, ptr(d)))
-        self._mask_bits = 0 if d is None else int(np.unique(d[d != 0] & 7).size)
 
     def get_doors(self):
         """door uint8[S], or None while no doors are set (gu_get_doors)."""
@@ -212,7 +204,7 @@ class Engine(object):
     def td_rows(self):
         """Rows of one env's Q table: S, or S << F while F fruits are set (include/gu.h: gu_set_fruit), or S << D while doors with
         D slots are set (gu_set_doors)."""
-        return self.spec.S << self._mask_bits
+        return self.spec.S << self.stores()['overlay_bits']
 
     def seed(self, seed):
         self.seed_value = int(seed) & 0xFFFFFFFFFFFFFFFF
@@ -578,7 +570,6 @@ class Engine(object):
     def mcts_init(self, max_sims=64):
         """An empty pool of max_sims + 1 tree nodes per env (1 <= max_sims <= MCTS_MAX_SIMS); the Q tables come from td_init."""
         check(self.lib.gu_mcts_init(self._h, int(max_sims)))
-        self._mcts_nodes = int(max_sims) + 1
 
     def set_tree_tables(self, U, B, I):
         """The schedule of the tree search: float64 U[C], B[C] and I[C], 2 <= C <= EXPLORE_MAX_C, every entry finite and >= 0.  An
@@ -614,7 +605,7 @@ class Engine(object):
         state int32[n, P], parent int32[n, P] (parent * 4 + action; -1 for the root), child int32[n, P, 4] (-1 = none), visits
         uint32[n, P, 4], w float64[n, P, 4] and count int32[n]; slots beyond count hold -1 / -1 / -1 / 0 / 0.0."""
         env0, n, n0 = self._env_range(env0, n)
-        P = getattr(self, '_mcts_nodes', 0)
+        P = self.stores()['mcts_nodes']
         out = dict(state=np.empty((n0, P), np.int32), parent=np.empty((n0, P), np.int32), child=np.empty((n0, P, 4), np.int32),
                    visits=np.empty((n0, P, 4), np.uint32), w=np.empty((n0, P, 4), np.float64), count=np.empty(n0, np.int32))
         check(self.lib.gu_mcts_get_tree(self._h, env0, n, ptr(out['state']), ptr(out['parent']), ptr(out['child']), ptr(out['visits']),
@@ -741,8 +732,6 @@ class Engine(object):
         return out
 
     # ------------------------------------------------------------------ semi-gradient SARSA / Q-learning on features (include/gu.h: gu_fa_*)
-    _fa_F = None  # features of the table installed by fa_init
-
     def fa_init(self, phi, n_features=None, w0=0.0):
         """Install the feature table phi int32[S, K] (K active binary features per state, 1 <= K <= FA_MAX_K, column k a slot of
         its own) shared by all envs, and one float64 weight table [F][4] per env, every entry w0.  F = n_features, or
@@ -755,12 +744,12 @@ class Engine(object):
         phi = _lib.as_array(phi, np.int32, None, 'phi')
         F = (int(phi.max()) + 1 if phi.size else 0) if n_features is None else int(n_features)
         check(self.lib.gu_fa_init(self._h, phi.shape[1], F, ptr(phi), float(w0)))
-        self._fa_F = F
 
     def _fa_features(self):
-        if self._fa_F is None:
+        F = self.stores()['fa_f']
+        if not F:  # (never made, or dropped by a grid of another size)
             raise RuntimeError('no features: call fa_init first')
-        return self._fa_F
+        return F
 
     def fa_run(self, T, method='sarsa', alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
         """T iterations of episodic semi-gradient SARSA / Q-learning per env in one launch, on the fa_init features.  alpha is
@@ -800,6 +789,18 @@ class Engine(object):
         episode = None if episode is None else _lib.as_array(episode, np.uint32, (self.N,), 'episode')
         tcount = None if tcount is None else _lib.as_array(tcount, np.uint64, (self.N,), 'tcount')
         check(self.lib.gu_set_state(self._h, ptr(pos), ptr(done), ptr(episode), ptr(tcount)))
+
+    STORES = ('s', 'n_grids', 'overlay', 'overlay_bits', 'td_rows', 'double', 'dyna', 'sweep', 'explore', 'explore_c', 'mcts_nodes', 'mcts_c', 'ac', 'is', 'fa_f',
+              'fa_k', 'trail_cap')
+
+    def stores(self):
+        """What the engine holds right now (gu_get_stores): dict of the GU_STORE_* words under the names of STORES.  A store's word is
+        non-zero exactly when the calls that need the store would find it; 'td_rows' counts only tables of the rows td_run learns on
+        now, s << overlay_bits.  A few host loads in the library: no synchronisation, nothing a learner carries is dropped.  Nothing in
+        Python keeps such a fact: whoever needs one asks here."""
+        words = (ctypes.c_int64 * len(self.STORES))()
+        check(self.lib.gu_get_stores(self._h, len(self.STORES), words, None))
+        return dict(zip(self.STORES, words))
 
     def done_indices(self):
         idx = np.empty(self.N, np.int32)
@@ -924,7 +925,7 @@ class Engine(object):
         """Breadth-first shortest path from each grid's first start cell to the first terminal state the FIFO search
         dequeues (maze_solving.py semantics).  Returns a list with one int8 action array (or None) per grid, plus the
         terminal states reached."""
-        G, S = self._n_grids, self.spec.S
+        G, S = self.stores()['n_grids'], self.spec.S
         max_path = int(max_path or S)
         path = np.zeros((G, max_path), np.int8)
         plen, term = np.zeros(G, np.int32), np.zeros(G, np.int32)
@@ -986,11 +987,10 @@ class Engine(object):
         """Keep the reference viewer's agent trail per env (env:92-93, 182-184, 190: the cell after every step, newest `capacity`
         <= 500, emptied by reset) and blend it into render_rgb frames (rendering.py:287-311); 0 switches it off again."""
         check(self.lib.gu_trail_enable(self._h, int(capacity)))
-        self._trail_cap = int(capacity)
 
     def trail_read(self, env0=0, n_envs=1):
         """The trails of envs env0 .. env0 + n_envs - 1 as lists of cells, oldest first (the reference's last_n_states as states)."""
-        cap = getattr(self, '_trail_cap', 0)
+        cap = self.stores()['trail_cap']
         cells, length = np.empty((int(n_envs), max(cap, 1)), np.int32), np.empty(int(n_envs), np.int32)
         check(self.lib.gu_trail_read(self._h, int(env0), int(n_envs), ptr(cells), ptr(length)))
         return [cells[k, :length[k]].tolist() for k in range(int(n_envs))]

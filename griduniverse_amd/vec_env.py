@@ -22,12 +22,22 @@ from .envs.griduniverse_env import GridUniverseEnv
 from .grid import DOOR_KINDS, FRUIT_KINDS, GridSpec, door_plane, fruit_plane, wind_plane
 
 
+def _q16(x):
+    """A probability as the library takes it: in 1/65536, to the nearest."""
+    return int(round(float(x) * 65536))
+
+
+def _unit(name, x):
+    """`x` lies in [0, 1] (ValueError; NaN fails too)."""
+    if not 0.0 <= float(x) <= 1.0:
+        raise ValueError('{} must lie in [0, 1]'.format(name))
+
+
 def check_off_policy_args(max_episode_len, epsilon, w_cap):
     """The argument checks of off_policy_mc_run and algorithms.off_policy (ValueError)."""
     if not 1 <= int(max_episode_len) <= _lib.IS_MAX:
         raise ValueError('max_episode_len must lie in 1 .. {}'.format(_lib.IS_MAX))
-    if not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError('epsilon must lie in [0, 1]')
+    _unit('epsilon', epsilon)
     if not 1.0 <= float(w_cap) <= 2.0 ** 256:  # (NaN and infinity fail too)
         raise ValueError('w_cap must lie in [1, 2**256]')
 
@@ -41,19 +51,12 @@ def _masks(masks, bits, message):
 
 
 class VecGridUniverse(object):
-    _n_fruit = 0  # fruits set (set_fruit): the Q tables have S << F rows
-    _n_doors = 0  # door slots set (set_doors): the Q tables have S << D rows
-    _td_ready = False  # the engine holds Q tables (td_run / set_q_table allocate them on first use)
-    _dyna_ready = False  # ... and Dyna-Q models (dyna_run / model allocate them on first use)
-    _sweep_ready = False  # ... and priority queues (sweep_run / priority_queue allocate them, with the models, on first use)
-    _explore_ready = False  # ... and visit counts (explore_run / visit_counts allocate them on first use)
-    _double_ready = False  # ... and pairs of Q tables (double_q_run / double_q_tables allocate them on first use)
-    _explore_tables = False  # set_exploration was called
-    _tree_sims = 0  # simulations the tree-search node pools hold (tree_search_run allocates them on first use and when it needs more)
-    _tree_tables = False  # set_tree_search was called (tree_search_run installs UCB1 tables with c = 3 otherwise)
-    _ac_ready = False  # ... and actor-critic tables (actor_critic_run / set_actor_critic allocate them on first use)
-    _is_ready = False  # ... and cumulative importance weights (off_policy_mc_run / importance_weights allocate them on first use)
-    _fa_ready = False  # ... and features with their weights (set_features installs them; nothing does it implicitly)
+    # A learner's store: its word of Engine.stores(), the Engine call that makes it, that call's arguments on first use, and the store it
+    # needs first.  Nothing here remembers what the engine holds: _ensure asks.
+    _STORES = {'q': ('td_rows', 'td_init', (0.0,), None), 'pairs': ('double', 'double_init', (0.0,), None),
+               'model': ('dyna', 'dyna_init', (), None), 'queue': ('sweep', 'sweep_init', (), None),
+               'counts': ('explore', 'explore_init', (), 'q'), 'weights': ('is', 'is_init', (), 'q'),
+               'ac': ('ac', 'ac_init', (0.0, 0.0), None), 'tree': ('mcts_nodes', 'mcts_init', (1,), 'q')}
 
     def __init__(self, num_envs, grid_shape=(4, 4), *, initial_state=0, goal_states=None, lava_states=None,
                  walls=None, custom_world_fp=None, random_maze=False, template=None, templates=None,
@@ -133,12 +136,8 @@ class VecGridUniverse(object):
             self.engine.reserve_trajectory(T)
         self.engine.rollout(T, policy, auto, trajectory, stats)
         if trajectory == 'packed':  # one uint32 per env-step on the device, unpacked to the same three arrays here
-            out = self.engine.read_trajectory_packed(0, T)
-        else:
-            out = self.engine.read_trajectory(0, T) if trajectory else {}
-        if stats:
-            out['ret'], out['episodes'] = self.engine.read_stats()
-        return out
+            return self._stats_into(self.engine.read_trajectory_packed(0, T), stats)
+        return self._stats_into(self.engine.read_trajectory(0, T) if trajectory else {}, stats)
 
     def set_wind(self, strength, direction='up', gust=0.0):
         """Wind on the engine's grid (single-grid engines; include/gu.h: gu_set_wind): every step, the agent is pushed behind its
@@ -147,13 +146,11 @@ class VecGridUniverse(object):
         strength above 0 is one more or one less for that step (2/3: one third each for k - 1, k, k + 1).  `strength` and
         `direction` as grid.wind_plane takes them; set_wind(None) calms the engine.  step, rollout and td_run follow the wind;
         the other learners, the DP and look-ahead calls, the path search and the trail are refused while it is set."""
-        gust = float(gust)
-        if not 0.0 <= gust <= 1.0:  # (NaN fails too)
-            raise ValueError('gust must lie in [0, 1]')
+        _unit('gust', gust)
         if strength is None:
             self.engine.set_wind(None)
             return
-        self.engine.set_wind(wind_plane(self.spec.W, self.spec.H, strength, direction), int(round(gust * 65536)))
+        self.engine.set_wind(wind_plane(self.spec.W, self.spec.H, strength, direction), _q16(gust))
 
     def wind(self):
         """None while the engine is calm, else dict(strength=uint8[H, W], direction=uint8[H, W], gust=float)."""
@@ -172,7 +169,6 @@ class VecGridUniverse(object):
         look-ahead calls, the path search, the trail and wind are refused while it is set.  sense and render do not show fruit."""
         if cells is None:
             self.engine.set_fruit(None)
-            F = 0
         else:
             v = np.asarray(values)
             if v.shape != (3,) or v.dtype == bool or not np.issubdtype(v.dtype, np.integer) or v.min() < -16 or v.max() > 16:
@@ -182,11 +178,6 @@ class VecGridUniverse(object):
             if blocked.any():
                 raise ValueError('fruit on cell {}, which is a wall or a goal or lava cell'.format(int(np.flatnonzero(blocked)[0])))
             self.engine.set_fruit(plane, v.astype(np.int32))
-            F = int(np.count_nonzero(plane))
-        if F != self._n_fruit:  # (the library dropped tables of another row count, and the tree search's node pools with them)
-            self._td_ready = False
-            self._tree_sims = 0
-        self._n_fruit = F
 
     def fruit(self):
         """None while no fruit is set, else dict(cells=int64[F] ascending (index = slot), kinds=list of names, values=int32[3])."""
@@ -204,7 +195,7 @@ class VecGridUniverse(object):
 
     def set_fruit_eaten(self, eaten, env0=0):
         """Install masks uint32[n] (or one number) for envs env0 ..; no bit at or above the number of fruits."""
-        self.engine.set_fruit_state(_masks(eaten, self._n_fruit, 'eaten must hold masks of the {} fruits set'), env0)
+        self.engine.set_fruit_state(_masks(eaten, self._mask_width(2), 'eaten must hold masks of the {} fruits set'), env0)
 
     def set_doors(self, doors, keys=None, levers=None):
         """Doors, keys and levers on the engine's grid (single-grid engines; include/gu.h: gu_set_doors): a door of slot k refuses
@@ -218,18 +209,12 @@ class VecGridUniverse(object):
             if keys is not None or levers is not None:
                 raise ValueError('set_doors(None) takes the doors away: keys and levers must be None too')
             self.engine.set_doors(None)
-            D = 0
         else:
             plane = door_plane(self.spec.W, self.spec.H, doors, keys, levers)
             blocked = (self.spec.wall | self.spec.goal | self.spec.lava) & (plane != 0)
             if blocked.any():
                 raise ValueError('a door, key or lever on cell {}, which is a wall or a goal or lava cell'.format(int(np.flatnonzero(blocked)[0])))
             self.engine.set_doors(plane)
-            D = int(np.unique(plane[plane != 0] & 7).size)
-        if D != self._n_doors:  # (the library dropped tables of another row count, and the tree search's node pools with them)
-            self._td_ready = False
-            self._tree_sims = 0
-        self._n_doors = D
 
     def doors(self):
         """None while no doors are set, else dict(doors=, keys=, levers=): mappings slot -> int64 array of ascending cells."""
@@ -249,26 +234,49 @@ class VecGridUniverse(object):
 
     def set_doors_open(self, mask, env0=0):
         """Install masks uint32[n] (or one number) for envs env0 ..; no bit at or above the number of slots in use."""
-        self.engine.set_doors_state(_masks(mask, self._n_doors, 'mask must hold masks of the {} door slots set'), env0)
+        self.engine.set_doors_state(_masks(mask, self._mask_width(3), 'mask must hold masks of the {} door slots set'), env0)
+
+    def _mask_width(self, overlay):
+        """Bits of an env's mask in use while `overlay` (2 fruit, 3 doors: include/gu.h, GU_STORE_OVERLAY) is set, else 0."""
+        st = self.engine.stores()
+        return st['overlay_bits'] if st['overlay'] == overlay else 0
+
+    def _ensure(self, st, store, *values, again=False):
+        """`store` (a key of _STORES) on the engine whose stores() are `st`: made with its first-use arguments when the library does
+        not hold it for the current grid and rows, made again when `again` or one of `values` is given (None: the first-use one)."""
+        word, init, first_use, needs = self._STORES[store]
+        if needs:
+            self._ensure(st, needs)
+        # `st` is read once and may be older than an init made since: that is safe because no init drops another store.  Without
+        # `values` the call takes its first-use arguments; a value of None stands for the first-use one at its place.
+        if again or any(v is not None for v in values) or not st[word]:
+            getattr(self.engine, init)(*[d if v is None else v for d, v in zip(first_use, values or first_use)])
 
     def _ensure_q(self, q0=None):
         """Q tables on the engine: tables of zeros on first use; every entry q0 (again) when q0 is given."""
-        if q0 is not None or not self._td_ready:
-            self.engine.td_init(0.0 if q0 is None else q0)
-            self._td_ready = True
+        self._ensure(self.engine.stores(), 'q', q0)
 
     def _ensure_model(self, clear=False):
         """Dyna-Q models on the engine: an empty model per env on first use, or when `clear`."""
-        if clear or not self._dyna_ready:
-            self.engine.dyna_init()
-            self._dyna_ready = True
+        self._ensure(self.engine.stores(), 'model', again=clear)
 
-    def _learner_out(self, T, trajectory, stats):
-        """The rows and statistics of the learner launch just made, as rollout() returns them."""
-        out = self.engine.read_trajectory(0, T) if trajectory and T > 0 else {}
+    def _stats_into(self, out, stats):
+        """`out`, the rows of the launch just made, with its statistics beside them when `stats`."""
         if stats:
             out['ret'], out['episodes'] = self.engine.read_stats()
         return out
+
+    def _learner_out(self, T, trajectory, stats):
+        """The rows and statistics of the learner launch just made, as rollout() returns them."""
+        return self._stats_into(self.engine.read_trajectory(0, T) if trajectory and T > 0 else {}, stats)
+
+    def _learner_launch(self, run, T, trajectory, stats, *args):
+        """One learner launch `run(T, *args, trajectory, stats)` of the engine, with room for its rows reserved before it and
+        its rows and statistics read behind it."""
+        if trajectory:
+            self.engine.reserve_trajectory(T)
+        run(T, *args, trajectory, stats)
+        return self._learner_out(T, trajectory, stats)
 
     def td_run(self, T, method='q_learning', alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
         """T iterations of batched tabular Q-learning ('q_learning') or SARSA ('sarsa'): env e learns its own Q table [S][4]
@@ -276,10 +284,7 @@ class VecGridUniverse(object):
         env a table of zeros.  Returns a dict like rollout(): obs/reward/done int32[T, N] when `trajectory`, ret/episodes
         when `stats`."""
         self._ensure_q()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.td_run(T, method, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        return self._learner_launch(self.engine.td_run, T, trajectory, stats, method, alpha, discount_factor, _q16(epsilon))
 
     def q_table(self, env0=0, n=None):
         """float64[n, S, 4]: the Q tables of envs env0 .. env0+n-1 (to the end when n is None).  While F fruits are set
@@ -298,32 +303,22 @@ class VecGridUniverse(object):
         as Q-learning does and bootstraps on the mean of Q[s'] under that same policy (include/gu.h: gu_esarsa_run); epsilon = 0
         gives td_run('q_learning')'s bytes.  The first call gives every env a table of zeros.  Refused while wind, fruit or doors are
         set.  Rows and statistics as td_run()."""
-        if not 0.0 <= float(epsilon) <= 1.0:
-            raise ValueError('epsilon must lie in [0, 1]')
+        _unit('epsilon', epsilon)
         self._ensure_q()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.esarsa_run(T, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        return self._learner_launch(self.engine.esarsa_run, T, trajectory, stats, alpha, discount_factor, _q16(epsilon))
 
     def _ensure_pairs(self, q0=None):
         """Pairs of Q tables on the engine: two tables of zeros per env on first use; every entry q0 (again) when q0 is given."""
-        if q0 is not None or not self._double_ready:
-            self.engine.double_init(0.0 if q0 is None else q0)
-            self._double_ready = True
+        self._ensure(self.engine.stores(), 'pairs', q0)
 
     def double_q_run(self, T, alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
         """T iterations of batched tabular Double Q-learning (Sutton & Barto 6.7): env e keeps two tables A and B of its own (not
         the tables of td_run), acts epsilon-greedily on A + B, and a coin per step (RNG stream 10) picks the table that learns, from
         the other's estimate of its own greedy action at s' (include/gu.h: gu_double_run).  The first call gives every env two
         tables of zeros.  Refused while wind, fruit or doors are set.  Rows and statistics as td_run()."""
-        if not 0.0 <= float(epsilon) <= 1.0:
-            raise ValueError('epsilon must lie in [0, 1]')
+        _unit('epsilon', epsilon)
         self._ensure_pairs()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.double_run(T, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        return self._learner_launch(self.engine.double_run, T, trajectory, stats, alpha, discount_factor, _q16(epsilon))
 
     def double_q_tables(self, env0=0, n=None):
         """float64[n, S, 2, 4]: the pairs of envs env0 .. env0+n-1 (to the end when n is None); [:, :, 0] is A, [:, :, 1] is B; zeros
@@ -340,12 +335,10 @@ class VecGridUniverse(object):
         """T real steps of batched tabular Dyna-Q: env e learns its own Q table [S][4] with Q-learning and its own model of the
         env, and replays `planning_steps` model updates after every real step (include/gu.h: gu_dyna_run).  The first call gives
         every env a table of zeros (if it had none) and an empty model.  Rows and statistics cover the real steps, as td_run()."""
-        self._ensure_q()
-        self._ensure_model()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.dyna_run(T, planning_steps, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        st = self.engine.stores()
+        self._ensure(st, 'q')
+        self._ensure(st, 'model')
+        return self._learner_launch(self.engine.dyna_run, T, trajectory, stats, planning_steps, alpha, discount_factor, _q16(epsilon))
 
     def model(self, env0=0, n=None):
         """The Dyna-Q models of envs env0 .. env0+n-1 (Engine.dyna_get_model); an empty model is allocated on first use."""
@@ -354,9 +347,7 @@ class VecGridUniverse(object):
 
     def _ensure_queue(self):
         """Priority queues (and Dyna-Q models) on the engine: empty ones on first use."""
-        if not self._sweep_ready:
-            self.engine.sweep_init()
-            self._sweep_ready = self._dyna_ready = True
+        self._ensure(self.engine.stores(), 'queue')
 
     def sweep_run(self, T, planning_steps=10, theta=1e-4, alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
         """T real steps of batched tabular prioritized sweeping (Sutton & Barto 8.4): env e keeps its own Q table, its own model of
@@ -364,12 +355,10 @@ class VecGridUniverse(object):
         |TD error| when that exceeds `theta`, and up to `planning_steps` times the pair with the largest priority is updated from the
         model and its predecessors are queued (include/gu.h: gu_sweep_run).  The first call gives every env a table of zeros (if
         it had none), an empty model and an empty queue.  Rows and statistics cover the real steps, as td_run()."""
-        self._ensure_q()
-        self._ensure_queue()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.sweep_run(T, planning_steps, theta, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        st = self.engine.stores()
+        self._ensure(st, 'q')
+        self._ensure(st, 'queue')
+        return self._learner_launch(self.engine.sweep_run, T, trajectory, stats, planning_steps, theta, alpha, discount_factor, _q16(epsilon))
 
     def priority_queue(self, env0=0, n=None):
         """The priority queues of envs env0 .. env0+n-1: dict key uint64[n, S, 4] (0 = not queued), priority float64[n, S, 4] (the
@@ -388,15 +377,11 @@ class VecGridUniverse(object):
         Q-learning (include/gu.h: gu_search_run).  An exploring step (`epsilon`) simulates nothing; simulations = 0 is
         td_run('q_learning').  The first call gives every env a table of zeros.  Rows and statistics cover the real steps, as
         td_run()."""
-        for name, v in (('epsilon', epsilon), ('rollout_epsilon', rollout_epsilon)):
-            if not 0.0 <= float(v) <= 1.0:
-                raise ValueError('{} must lie in [0, 1]'.format(name))
+        _unit('epsilon', epsilon)
+        _unit('rollout_epsilon', rollout_epsilon)
         self._ensure_q()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.search_run(T, simulations, depth, alpha, discount_factor, int(round(float(epsilon) * 65536)),
-                               int(round(float(rollout_epsilon) * 65536)), trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        return self._learner_launch(self.engine.search_run, T, trajectory, stats, simulations, depth, alpha, discount_factor, _q16(epsilon),
+                                    _q16(rollout_epsilon))
 
     def search_scores(self, env0=0, n=None):
         """Engine.search_get: the score rows of the most recent searched steps and the simulated moves of the last search_run."""
@@ -408,7 +393,6 @@ class VecGridUniverse(object):
         visited n_s times, an action tried n_b times with summed returns w_b scores w_b * I[min(n_b, C-1)] + U[min(n_s, C-1)] *
         B[min(n_b, C-1)]; algorithms.search.uct_tables builds UCB1's."""
         self.engine.set_tree_tables(U, B, I)
-        self._tree_tables = True
 
     def tree_search_run(self, T, simulations=64, tree_depth=8, depth=4, alpha=0.1, discount_factor=0.99, epsilon=0.1, rollout_epsilon=1.0,
                         trajectory=False, stats=False):
@@ -420,30 +404,25 @@ class VecGridUniverse(object):
         exploring step (`epsilon`) simulates nothing; simulations = 0 is td_run('q_learning').  The first call gives every env a
         table of zeros and a node pool, and installs uct_tables(3.0) unless set_tree_search was called.  Rows and statistics
         cover the real steps, as td_run()."""
-        for name, v in (('epsilon', epsilon), ('rollout_epsilon', rollout_epsilon)):
-            if not 0.0 <= float(v) <= 1.0:
-                raise ValueError('{} must lie in [0, 1]'.format(name))
+        _unit('epsilon', epsilon)
+        _unit('rollout_epsilon', rollout_epsilon)
         M = int(simulations)
         if not 0 <= M <= _lib.MCTS_MAX_SIMS:
             raise ValueError('simulations must lie in 0 .. {}'.format(_lib.MCTS_MAX_SIMS))
-        self._ensure_q()
-        if M > self._tree_sims or not self._tree_sims:
+        st = self.engine.stores()
+        self._ensure(st, 'q')
+        # a pool holds one node more than its simulations (no pool: 0 nodes).  Under an overlay none is made: the launch is refused, and
+        # says why, where mcts_init would only miss tables of S rows
+        if M > st['mcts_nodes'] - 1 and not st['overlay']:
             self.engine.mcts_init(max(M, 1))
-            self._tree_sims = max(M, 1)
-        if not self._tree_tables:
+        if not st['mcts_c']:
             from .algorithms.search import uct_tables
             self.set_tree_search(*uct_tables())
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.mcts_run(T, M, tree_depth, depth, alpha, discount_factor, int(round(float(epsilon) * 65536)),
-                             int(round(float(rollout_epsilon) * 65536)), trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        return self._learner_launch(self.engine.mcts_run, T, trajectory, stats, M, tree_depth, depth, alpha, discount_factor, _q16(epsilon),
+                                    _q16(rollout_epsilon))
 
     def _ensure_tree(self):
-        self._ensure_q()
-        if not self._tree_sims:
-            self.engine.mcts_init(1)
-            self._tree_sims = 1
+        self._ensure(self.engine.stores(), 'tree')
 
     def tree_search_roots(self, env0=0, n=None):
         """Engine.mcts_get: the root rows (return sums, visits) and node counts of the most recent searched steps and the simulated
@@ -458,17 +437,13 @@ class VecGridUniverse(object):
 
     def _ensure_counts(self):
         """Visit counts on the engine: zeroed counts on first use (and tables of zeros if the envs had no Q tables)."""
-        self._ensure_q()
-        if not self._explore_ready:
-            self.engine.explore_init()
-            self._explore_ready = True
+        self._ensure(self.engine.stores(), 'counts')
 
     def set_exploration(self, U, B):
         """The exploration schedule of explore_run: float64 vectors U and B of one length C, 2 <= C <= 4096, finite and >= 0.  The
         bonus of action b in a state visited n_s times is U[min(n_s, C-1)] * B[min(n_b, C-1)]; algorithms.exploration.ucb_tables
         and thompson_tables build the two usual schedules."""
         self.engine.set_exploration(U, B)
-        self._explore_tables = True
 
     def explore_run(self, T, rule='ucb', alpha=0.1, discount_factor=0.99, epsilon=0.0, trajectory=False, stats=False):
         """T steps of batched tabular Q-learning with count-based exploration: env e keeps visit counts [S][4] beside its Q table
@@ -478,15 +453,12 @@ class VecGridUniverse(object):
         first call gives every env zeroed counts (and a table of zeros if it had none).  Rows and statistics as td_run()."""
         if rule not in ('ucb', 'thompson'):
             raise ValueError("rule must be 'ucb' or 'thompson'")
-        if not 0.0 <= float(epsilon) <= 1.0:
-            raise ValueError('epsilon must lie in [0, 1]')
-        if not self._explore_tables:
+        _unit('epsilon', epsilon)
+        st = self.engine.stores()
+        if not st['explore_c']:
             raise ValueError('no exploration schedule: call set_exploration(U, B) first')
-        self._ensure_counts()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.explore_run(T, rule, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        self._ensure(st, 'counts')
+        return self._learner_launch(self.engine.explore_run, T, trajectory, stats, rule, alpha, discount_factor, _q16(epsilon))
 
     def visit_counts(self, env0=0, n=None):
         """uint32[n, S, 4]: the visit counts of envs env0 .. env0+n-1 (to the end when n is None); zeros before the first explore_run."""
@@ -504,10 +476,7 @@ class VecGridUniverse(object):
         Consecutive calls with the same method and n carry the window of pending transitions; any other call in between drops
         it.  Rows and statistics as td_run()."""
         self._ensure_q()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.nstep_run(T, method, n, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        return self._learner_launch(self.engine.nstep_run, T, trajectory, stats, method, n, alpha, discount_factor, _q16(epsilon))
 
     def nstep_window(self, env0=0, n=None):
         """The n-step windows of envs env0 .. env0+n-1 (Engine.nstep_get_window)."""
@@ -520,11 +489,7 @@ class VecGridUniverse(object):
         The first call gives every env a table of zeros.  Consecutive calls with the same method and trace_len carry the trace
         window; any other call in between drops it.  Rows and statistics as td_run()."""
         self._ensure_q()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.lambda_run(T, method, trace_len, lam, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory,
-                               stats)
-        return self._learner_out(T, trajectory, stats)
+        return self._learner_launch(self.engine.lambda_run, T, trajectory, stats, method, trace_len, lam, alpha, discount_factor, _q16(epsilon))
 
     def lambda_window(self, env0=0, n=None):
         """The trace windows of envs env0 .. env0+n-1 (Engine.lambda_get_window): int32[n, 64], index = age."""
@@ -535,10 +500,9 @@ class VecGridUniverse(object):
         as a tiling of tile coding is) shared by all envs, and give every env a weight table [F][4] of w0
         (include/gu.h: gu_fa_init).  F = n_features, or phi.max() + 1.  See algorithms.function_approximation.tile_coding."""
         self.engine.fa_init(phi, n_features, w0)
-        self._fa_ready = True
 
     def _need_features(self):
-        if not self._fa_ready:
+        if not self.engine.stores()['fa_f']:
             raise RuntimeError('no features: call set_features first')
 
     def fa_run(self, T, method='sarsa', alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
@@ -547,10 +511,7 @@ class VecGridUniverse(object):
         active in a state, epsilon-greedy, auto-reset always on (include/gu.h: gu_fa_run).  `alpha` is applied as given: divide
         a step size by K yourself.  Returns a dict like td_run()."""
         self._need_features()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.fa_run(T, method, alpha, discount_factor, int(round(float(epsilon) * 65536)), trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        return self._learner_launch(self.engine.fa_run, T, trajectory, stats, method, alpha, discount_factor, _q16(epsilon))
 
     def weights(self, env0=0, n=None):
         """float64[n, F, 4]: the weight tables of envs env0 .. env0+n-1 (to the end when n is None)."""
@@ -570,19 +531,14 @@ class VecGridUniverse(object):
 
     def _ensure_ac(self, h0=None, v0=None):
         """Actor-critic tables on the engine: zeros on first use; every entry h0 / v0 (again) when either is given."""
-        if h0 is not None or v0 is not None or not self._ac_ready:
-            self.engine.ac_init(0.0 if h0 is None else h0, 0.0 if v0 is None else v0)
-            self._ac_ready = True
+        self._ensure(self.engine.stores(), 'ac', h0, v0)
 
     def actor_critic_run(self, T, actor_lr=0.1, critic_lr=0.1, discount_factor=0.99, trajectory=False, stats=False):
         """T iterations of batched tabular one-step actor-critic: env e learns its own softmax preferences [S][4] and state
         values [S] from its own experience, acting on the softmax of its preferences, auto-reset always on (include/gu.h:
         gu_ac_run).  The first call gives every env tables of zeros.  Returns a dict like td_run()."""
         self._ensure_ac()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.ac_run(T, actor_lr, critic_lr, discount_factor, trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        return self._learner_launch(self.engine.ac_run, T, trajectory, stats, actor_lr, critic_lr, discount_factor)
 
     def reinforce_run(self, T, max_episode_len=256, actor_lr=0.003, baseline_lr=0.1, discount_factor=0.99, trajectory=False,
                       stats=False):
@@ -593,10 +549,7 @@ class VecGridUniverse(object):
         call gives every env tables of zeros.  Consecutive calls with the same max_episode_len carry the episode buffer; any
         other call in between drops it.  Returns a dict like td_run()."""
         self._ensure_ac()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.reinforce_run(T, max_episode_len, actor_lr, baseline_lr, discount_factor, trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        return self._learner_launch(self.engine.reinforce_run, T, trajectory, stats, max_episode_len, actor_lr, baseline_lr, discount_factor)
 
     def episode_buffer(self, env0=0, n=None):
         """The episode buffers of envs env0 .. env0+n-1 (Engine.reinforce_get_episode)."""
@@ -604,10 +557,7 @@ class VecGridUniverse(object):
 
     def _ensure_is(self):
         """Cumulative weights on the engine: zeros on first use (and tables of zeros if the envs had no Q tables)."""
-        self._ensure_q()
-        if not self._is_ready:
-            self.engine.is_init()
-            self._is_ready = True
+        self._ensure(self.engine.stores(), 'weights')
 
     def off_policy_mc_run(self, T, max_episode_len=64, discount_factor=0.99, epsilon=0.1, w_cap=2.0 ** 64, trajectory=False,
                           stats=False):
@@ -620,10 +570,7 @@ class VecGridUniverse(object):
         max_episode_len carry the episode buffer; any other call in between drops it.  Returns a dict like td_run()."""
         check_off_policy_args(max_episode_len, epsilon, w_cap)
         self._ensure_is()
-        if trajectory:
-            self.engine.reserve_trajectory(T)
-        self.engine.is_run(T, max_episode_len, discount_factor, int(round(float(epsilon) * 65536)), w_cap, trajectory, stats)
-        return self._learner_out(T, trajectory, stats)
+        return self._learner_launch(self.engine.is_run, T, trajectory, stats, max_episode_len, discount_factor, _q16(epsilon), w_cap)
 
     def importance_weights(self, env0=0, n=None):
         """float64[n, S, 4]: the cumulative weights C of envs env0 .. env0+n-1 (to the end when n is None); zeros before the

@@ -377,6 +377,36 @@ int gu_read_stats(gu_handle h, int64_t *reward_sum, int32_t *episodes);
 int gu_get_state(gu_handle h, int32_t *pos, int32_t *done, uint32_t *episode, uint64_t *tcount);
 int gu_set_state(gu_handle h, const int32_t *pos, const int32_t *done, const uint32_t *episode, const uint64_t *tcount);
 
+/* gu_get_stores : introspection -- what the engine holds right now, so that no caller has to keep count beside it.  *count =
+ *                 GU_STORE_COUNT; with `values`, the first min(capacity, GU_STORE_COUNT) words, indexed by GU_STORE_*.  Host fields of
+ *                 the handle only: nothing is synchronised, allocated or copied, nothing a learner carries from launch to launch is
+ *                 dropped, and the call works before a grid is set.  A store's word is non-zero exactly when the entry points that
+ *                 need the store would find it ("no ...: call gu_*_init first" otherwise): tables left over from a grid of another
+ *                 state count read 0.  GU_STORE_TD_ROWS reports the rows of the Q tables only while they are the rows gu_td_run
+ *                 learns on now, S << GU_STORE_OVERLAY_BITS; the learners that take no overlay need S rows, which is the same number
+ *                 whenever they can run at all. */
+enum {
+    GU_STORE_S = 0,         /* states of the grid; 0 without a grid */
+    GU_STORE_N_GRIDS,       /* grids installed (gu_set_grids, gu_generate_mazes) */
+    GU_STORE_OVERLAY,       /* 0 none, 1 wind, 2 fruit, 3 doors */
+    GU_STORE_OVERLAY_BITS,  /* bits of an env's mask in use: F fruits, D door slots, else 0 */
+    GU_STORE_TD_ROWS,       /* rows per env of the Q tables (gu_td_init); 0 = none for the current rows */
+    GU_STORE_DOUBLE,        /* states of the pairs of tables (gu_double_init); 0 = none */
+    GU_STORE_DYNA,          /* states of the models (gu_dyna_init); 0 = none */
+    GU_STORE_SWEEP,         /* 1 while the priority queues (gu_sweep_init) exist for the current models, else 0 */
+    GU_STORE_EXPLORE,       /* states of the visit counts (gu_explore_init); 0 = none */
+    GU_STORE_EXPLORE_C,     /* entries of the exploration schedule (gu_explore_set_tables); 0 = none */
+    GU_STORE_MCTS_NODES,    /* nodes per env of the tree search's pools (gu_mcts_init: max_sims + 1); 0 = none */
+    GU_STORE_MCTS_C,        /* entries of the tree search's schedule (gu_mcts_set_tables); 0 = none */
+    GU_STORE_AC,            /* states of the actor-critic tables (gu_ac_init); 0 = none */
+    GU_STORE_IS,            /* states of the cumulative importance weights (gu_is_init); 0 = none */
+    GU_STORE_FA_F,          /* features of the weight tables (gu_fa_init); 0 = none */
+    GU_STORE_FA_K,          /* slots per state of the feature table; 0 = none */
+    GU_STORE_TRAIL_CAP,     /* trail entries per env (gu_trail_enable); 0 = off */
+    GU_STORE_COUNT
+};
+int gu_get_stores(gu_handle h, int32_t capacity, int64_t *values, int32_t *count);
+
 /* Ascending indices of envs whose done flag is set.  Every kernel that writes done[] (step, rollout, reset,
  * sweep-step) also writes its waves' 64-bit ballot of the new flags -- 8 KB at 65 536 envs -- so this call is ONE
  * launch: a single-workgroup scan + expansion of those words straight into page-locked memory (only a done[]

@@ -41,12 +41,17 @@ class _NoEngine(object):
     """Stands in for Engine: any call on it is a library call that must not have been made."""
 
     def __init__(self, *a, **kw):
-        self.calls = []
+        self.calls, self.args, self.held = [], [], {}
 
     def __getattr__(self, name):
         def call(*a, **kw):
             self.calls.append(name)
+            self.args.append(a)
         return call
+
+    def stores(self):
+        """What the library would report (Engine.stores): the test sets `held`.  A query, so it is not recorded."""
+        return self.held
 
 
 def test_bad_arguments_are_value_errors_raised_before_any_library_call():
@@ -60,6 +65,7 @@ def test_bad_arguments_are_value_errors_raised_before_any_library_call():
             vec.set_doors(**kw)
     assert vec.engine.calls == []
     vec.set_doors({0: free[0], 1: free[1]}, keys={0: free[2]}, levers={1: free[3]})
+    vec.engine.held = dict(overlay=3, overlay_bits=2)
     for bad in ([4], [-1], [0.5], [[1]], [True]):  # two slots: bits 0 and 1
         with pytest.raises(ValueError):
             vec.set_doors_open(bad)
@@ -79,21 +85,31 @@ def test_bad_arguments_are_value_errors_raised_before_any_library_call():
                 learn(None, 10, doors=bad)
 
 
-def test_set_doors_resets_td_ready_when_the_slot_count_changes():
+def test_the_facade_asks_the_library_for_the_tables_after_set_doors():
     g = GRIDS['maze11']()
     vec = gua.VecGridUniverse(4, template=_spec(g), engine_factory=_NoEngine)
     free = O.free_cells(g)
-    vec._td_ready = True
+    # The facade keeps no flag of its own: after set_doors it asks the library, which drops tables of another row count
+    # (tests/test_gpu_stores.py checks that half) and says so in stores().
+    def inits():
+        return [(c, a) for c, a in zip(vec.engine.calls, vec.engine.args) if c != 'set_doors']
+
     vec.set_doors({0: free[0], 1: free[1]}, keys={0: free[2], 1: free[3]})
-    assert not vec._td_ready
-    vec._td_ready = True
+    vec.engine.held = dict(td_rows=0)  # another row count: the tables went
+    vec._ensure_q()
+    assert inits() == [('td_init', (0.0,))]
     vec.set_doors({0: [free[5], free[6]], 1: free[7]}, levers={0: free[8], 1: free[9]})  # two slots again: the rows stay, and so do the tables
-    assert vec._td_ready
+    vec.engine.held = dict(td_rows=121 << 2)
+    vec._ensure_q()
+    assert inits() == [('td_init', (0.0,))]
     vec.set_doors({0: free[5]}, keys={0: free[6]})
-    assert not vec._td_ready
-    vec._td_ready = True
+    vec.engine.held = dict(td_rows=0)
+    vec._ensure_q()
+    assert inits() == [('td_init', (0.0,))] * 2
     vec.set_doors(None)
-    assert not vec._td_ready
+    vec._ensure_q()
+    assert inits() == [('td_init', (0.0,))] * 3
+    assert vec.engine.calls == ['set_doors', 'td_init', 'set_doors', 'set_doors', 'td_init', 'set_doors', 'td_init']
 
 
 def test_library_exports_the_door_entry_points_and_kernels():

@@ -110,7 +110,7 @@ def test_new_entry_points_are_declared_bound_and_exported():
 
 @pytest.mark.parametrize('learn', [expected_sarsa, double_q_learning])
 def test_algorithms_check_their_arguments_before_they_touch_a_device(learn, monkeypatch):
-    from griduniverse_amd.algorithms import temporal_difference as M
+    from griduniverse_amd.algorithms import _batch as M  # (where every learner function opens its batch)
 
     def no_device(*a, **kw):
         raise AssertionError('a batch was opened before the arguments were checked')

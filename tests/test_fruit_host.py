@@ -98,12 +98,17 @@ class _NoEngine(object):
     """Stands in for Engine: any call on it is a library call that must not have been made."""
 
     def __init__(self, *a, **kw):
-        self.calls = []
+        self.calls, self.args, self.held = [], [], {}
 
     def __getattr__(self, name):
         def call(*a, **kw):
             self.calls.append(name)
+            self.args.append(a)
         return call
+
+    def stores(self):
+        """What the library would report (Engine.stores): the test sets `held`.  A query, so it is not recorded."""
+        return self.held
 
 
 def test_bad_arguments_are_value_errors_raised_before_any_library_call():
@@ -117,6 +122,7 @@ def test_bad_arguments_are_value_errors_raised_before_any_library_call():
             vec.set_fruit(**kw)
     assert vec.engine.calls == []
     vec.set_fruit(free[:3], ['apple', 'lemon', 'melon'])
+    vec.engine.held = dict(overlay=2, overlay_bits=3)
     for bad in ([8], [-1], [0.5], [[1]]):  # three fruits: bits 0 .. 2
         with pytest.raises(ValueError):
             vec.set_fruit_eaten(bad)
@@ -132,18 +138,28 @@ def test_bad_arguments_are_value_errors_raised_before_any_library_call():
             learn(None, 10, fruit=(free[:1], 'apple'))
 
 
-def test_set_fruit_resets_td_ready_when_the_row_count_changes():
+def test_the_facade_asks_the_library_for_the_tables_after_set_fruit():
     g = GRIDS['maze11']()
     vec = gua.VecGridUniverse(4, template=_spec(g), engine_factory=_NoEngine)
     free = _free(g)
-    vec._td_ready = True
+    # The facade keeps no flag of its own: after set_fruit it asks the library, which drops tables of another row count
+    # (tests/test_gpu_stores.py checks that half) and says so in stores().
+    def inits():
+        return [(c, a) for c, a in zip(vec.engine.calls, vec.engine.args) if c != 'set_fruit']
+
     vec.set_fruit(free[:2])
-    assert not vec._td_ready
-    vec._td_ready = True
+    vec.engine.held = dict(td_rows=0)  # another row count: the tables went
+    vec._ensure_q()
+    assert inits() == [('td_init', (0.0,))]
     vec.set_fruit(free[5:7], 'melon')  # two fruits again: the rows stay, and so do the tables
-    assert vec._td_ready
+    vec.engine.held = dict(td_rows=121 << 2)
+    vec._ensure_q()
+    assert inits() == [('td_init', (0.0,))]
     vec.set_fruit(None)
-    assert not vec._td_ready
+    vec.engine.held = dict(td_rows=0)
+    vec._ensure_q()
+    assert inits() == [('td_init', (0.0,))] * 2
+    assert vec.engine.calls == ['set_fruit', 'td_init', 'set_fruit', 'set_fruit', 'td_init']
 
 
 def test_library_exports_the_fruit_entry_points_and_kernels():

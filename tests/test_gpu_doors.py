@@ -588,7 +588,6 @@ def test_calls_without_a_door_form_are_refused_while_doors_are_set():
         vec.sense(radius=1)
         vec.get_state()
         vec.set_doors(None)
-        vec._td_ready, vec._tree_sims = False, 0  # (the tables went when the doors changed their row count, the node pools with them)
         vec._ensure_tree()
         for name, call in calls.items():  # the same calls succeed once the doors are gone
             call()

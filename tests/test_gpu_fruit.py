@@ -433,7 +433,6 @@ def test_calls_without_a_fruit_form_are_refused_while_fruit_is_set():
         vec.sense(radius=1)
         vec.get_state()
         vec.set_fruit(None)
-        vec._td_ready, vec._tree_sims = False, 0  # (the tables went when the fruit changed their row count, the node pools with them)
         vec._ensure_tree()
         for name, call in calls.items():  # the same calls succeed once the fruit is gone
             call()

@@ -110,8 +110,11 @@ def _drop_and_keep(N, seed):
                     lambda: eng.reinforce_run(5, L=16), lambda: eng.is_run(5, L=7), lambda: eng.fa_run(5)):
             _fails_for_want_of_a_store(run)
         for get in (eng.td_get_q, eng.explore_get_counts, eng.is_get, eng.ac_get, eng.search_get, eng.mcts_get, eng.mcts_tree, eng.dyna_get_model,
-                    eng.fa_get_w, eng.fa_get_q):
+                    eng.fa_get_q):
             _fails_for_want_of_a_store(get)
+        with pytest.raises(RuntimeError) as err:  # (the engine sizes the weights' array by what the library holds, and it holds none)
+            eng.fa_get_w()
+        assert str(err.value) == 'no features: call fa_init first'
         for get in (eng.nstep_get_window, eng.reinforce_get_episode, eng.is_get_episode):
             got = get()
             assert not got['count'].any() and (got['sa'] == -1).all() and got['sa'].shape[0] == N

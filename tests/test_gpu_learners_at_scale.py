@@ -303,7 +303,6 @@ class Mcts(Learner):
         vec._ensure_q(Q0)
         if self.max_sims:
             vec.engine.mcts_init(self.max_sims)
-            vec._tree_sims = self.max_sims
 
     def device(self, vec, T, **kw):
         return vec.tree_search_run(T, self.M, self.H, self.D, alpha=ALPHA, discount_factor=GAMMA, epsilon=EPS,
