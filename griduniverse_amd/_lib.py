@@ -37,6 +37,8 @@ MCTS_MAX_SIMS = 255   # GU_MCTS_MAX_SIMS: the most simulations per decision of g
 MCTS_MAX_DEPTH = 64   # GU_MCTS_MAX_DEPTH: the largest depth cap of its tree
 SENSE_EGO, SENSE_GRID = 0, 1
 SENSE_MAX_R = 7  # GU_SENSE_MAX_R: the largest radius of gu_sense's egocentric view
+PROBE_EXP, PROBE_RECIP14, PROBE_IS_RECIP = 0, 1, 2  # GU_PROBE_*: the ops of gu_probe_numeric (include/gu_diag.h)
+PROBE_MAX = 1 << 24  # GU_PROBE_MAX: the most items of one probe call
 FA_MAX_K = 8  # GU_FA_MAX_K: the most active features per state of gu_fa_init
 COMM_ID_BYTES = 128
 OPT_UNSET = -2 ** 63
@@ -149,6 +151,8 @@ SIGNATURES = {
     'gu_is_get': [_vp, _i64, _i64, _vp],
     'gu_is_set': [_vp, _i64, _i64, _vp],
     'gu_is_get_episode': [_vp, _i64, _i64, _vp, _vp, _vp, _vp],
+    'gu_probe_numeric': [_vp, _i32, _i64, _vp, _vp],
+    'gu_probe_numeric_softmax': [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp],
     'gu_fa_init': [_vp, _i32, _i32, _vp, _f64],
     'gu_fa_run': [_vp, _i64, _i32, _f64, _f64, _u32, _u32],
     'gu_fa_get_w': [_vp, _i64, _i64, _vp],

@@ -1,7 +1,7 @@
 // gu_is.hip -- batched off-policy every-visit Monte-Carlo control with weighted importance sampling for gfx950 (Sutton & Barto
 // 5.7; include/gu.h: gu_is_run; restated on the CPU by tests/_is_oracle.py).  The lane, its RNG word, the move, the trajectory
 // rows and the statistics are gu_tabular.hpp's; the tables are gu_td.hip's (Q [N][S][4]) plus the cumulative weights C of the same
-// shape; the reciprocal of the mantissa is gu_softmax.hpp's gu_recip14.  What is here is the episode buffer, the class of the
+// shape; RECIP is gu_softmax.hpp's gu_is_recip (gu_recip14 on the mantissa).  What is here is the episode buffer, the class of the
 // behaviour action and the backward pass at a segment's end, which stops at the first entry that is no longer greedy.
 //
 // ONE LOOP, TWO LANE MODES (gu_reinforce.hip's structure).  Every turn of the loop a lane does one unit of work:
@@ -36,16 +36,6 @@ struct IsArgs : TabArgs {
     int32_t L;         // segment length, 1 .. GU_IS_MAX
     int32_t carry;     // 1: this launch directly follows a gu_is_run with the same L -- start from cnt
 };
-
-// 1 / x correctly rounded for a positive normal x whose reciprocal is normal: gu_recip14 on the mantissa in [1, 2), the exponent
-// put back by ldexp (exact)
-__device__ __forceinline__ double gu_is_recip(double x)
-{
-    const int64_t b = __double_as_longlong(x);
-    const int ex = (int)((b >> 52) & 0x7FF) - 1023;
-    const double m = __longlong_as_double((b & 0x000FFFFFFFFFFFFFll) | 0x3FF0000000000000ll);
-    return __builtin_ldexp(gu_recip14(m), -ex);
-}
 
 template <bool LDS>
 __global__ void __launch_bounds__(GU_BLOCK) gu_is_kernel(const IsArgs a)

@@ -1,5 +1,6 @@
 // gu_softmax.hpp -- the build's float64 softmax pieces for gfx950 (include/gu.h: gu_ac_run rule 2, "the build's exp"):
-// gu_exp, a reciprocal for [1, 4] and the softmax of one preference row.  Every learner is checked byte for byte against a CPU
+// gu_exp, a reciprocal for [1, 4] (and, around it, gu_is_run's for any exponent) and the softmax of one preference row.
+// gu_probe.hip runs each of them on the caller's arrays (include/gu_diag.h) for the tests of their edges.  Every learner is checked byte for byte against a CPU
 // restatement, and neither OCML's exp nor libm's is reproducible on the other side, so both are built here from operations
 // that round once and the same way everywhere: float64 multiply and add (__dmul_rn / __dadd_rn, -ffp-contract=off), rint
 // (v_rndne_f64), ldexp (v_ldexp_f64) and integer arithmetic.
@@ -69,6 +70,16 @@ __device__ __forceinline__ double gu_recip14(double z)
         y = __longlong_as_double(b + (up ? 1 : 0) - (dn ? 1 : 0));
     }
     return y;
+}
+
+// RECIP of gu_is_run (include/gu.h): 1 / x correctly rounded for a positive normal x whose reciprocal is normal: gu_recip14 on the
+// mantissa in [1, 2), the exponent put back by ldexp (exact)
+__device__ __forceinline__ double gu_is_recip(double x)
+{
+    const int64_t b = __double_as_longlong(x);
+    const int ex = (int)((b >> 52) & 0x7FF) - 1023;
+    const double m = __longlong_as_double((b & 0x000FFFFFFFFFFFFFll) | 0x3FF0000000000000ll);
+    return __builtin_ldexp(gu_recip14(m), -ex);
 }
 
 // the softmax of one preference row h (include/gu.h, gu_ac_run rule 2): m = the row maximum folded left to right with `>`,

@@ -731,6 +731,39 @@ class Engine(object):
         check(self.lib.gu_is_get_episode(self._h, env0, n, ptr(out['sa']), ptr(out['reward']), ptr(out['cls']), ptr(out['count'])))
         return out
 
+    # ------------------------------------------------------------------ the learners' float64 building blocks (include/gu_diag.h: gu_probe_numeric*)
+    def _probe_numeric(self, op, x):
+        x = np.ascontiguousarray(x, np.float64).reshape(-1)
+        y = np.empty_like(x)
+        if x.size:
+            check(self.lib.gu_probe_numeric(self._h, op, x.size, ptr(x), ptr(y)))
+        return y
+
+    def probe_exp(self, x):
+        """float64[n]: the device's gu_exp of x[n] (x <= 0, -inf included)."""
+        return self._probe_numeric(_lib.PROBE_EXP, x)
+
+    def probe_recip14(self, z):
+        """float64[n]: the device's gu_recip14 of z[n], the correctly rounded 1 / z of z in [1, 4]."""
+        return self._probe_numeric(_lib.PROBE_RECIP14, z)
+
+    def probe_is_recip(self, x):
+        """float64[n]: the device's RECIP of gu_is_run on x[n], positive normal numbers whose reciprocals are normal."""
+        return self._probe_numeric(_lib.PROBE_IS_RECIP, x)
+
+    def probe_softmax(self, h, w):
+        """Rules 2 and 3 of gu_ac_run on the device for preference rows h float64[n, 4] and words w uint32[n]: dict e float64[n, 4],
+        Z and iz float64[n], action int32[n]."""
+        h = np.ascontiguousarray(h, np.float64)
+        w = np.ascontiguousarray(w, np.uint32).reshape(-1)
+        if h.ndim != 2 or h.shape[1] != 4 or h.shape[0] != w.size:
+            raise ValueError('h must be [n, 4] and w [n], got {} and {}'.format(h.shape, w.shape))
+        n = w.size
+        out = dict(e=np.empty((n, 4), np.float64), Z=np.empty(n, np.float64), iz=np.empty(n, np.float64), action=np.empty(n, np.int32))
+        if n:
+            check(self.lib.gu_probe_numeric_softmax(self._h, n, ptr(h), ptr(w), ptr(out['e']), ptr(out['Z']), ptr(out['iz']), ptr(out['action'])))
+        return out
+
     # ------------------------------------------------------------------ semi-gradient SARSA / Q-learning on features (include/gu.h: gu_fa_*)
     def fa_init(self, phi, n_features=None, w0=0.0):
         """Install the feature table phi int32[S, K] (K active binary features per state, 1 <= K <= FA_MAX_K, column k a slot of

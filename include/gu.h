@@ -784,8 +784,8 @@ int gu_lambda_get_window(gu_handle h, int64_t env0, int64_t n, int32_t *sa);
  * (build-defined: the reference lists "Policy Gradients (MC Policy Gradients and Actor-critic)" on its roadmap and ships no code;
  * Sutton & Barto 13.5; tests/_ac_oracle.py is the CPU restatement.)  The tables are float64 and the learner's own, not the
  * gu_td_* Q tables.  All arithmetic is float64 with one rounding per operation (multiply, add, subtract, divide).
- * THE BUILD'S EXP, gu_exp(x) for x <= 0 (non-finite x: unspecified):
- *   x < -700: 0.0.  Otherwise k = rint(x * 1.4426950408889634) (half to even);
+ * THE BUILD'S EXP, gu_exp(x) for x <= 0 (NaN: unspecified):
+ *   x < -700: 0.0, and so gu_exp(-inf) = 0.0 -- finite preferences can produce it: -1e308 - 1e308 in rule 2.  Otherwise k = rint(x * 1.4426950408889634) (half to even);
  *   r = (x - k * 6.93147180369123816490e-01) - k * 1.90821492927058770002e-10;
  *   p = 1/13!, then p = p * r + c for c = 1/12!, 1/11!, ..., 1/2!, 1, 1 in that order (multiply and add rounded separately;
  *   each 1/n! is the double nearest to it); result = ldexp(p, k) (k >= -1010 here, so the result is normal and exact).

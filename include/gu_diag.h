@@ -58,6 +58,26 @@ int gu_vi_last_clusters(gu_handle h, int32_t *members);
  * The product library returns GU_ERR_UNSUPPORTED (*count = -1). */
 int gu_vi_xcd_torn_words(gu_handle h, int64_t *count);
 
+/* ---- the learners' float64 building blocks, evaluated on the caller's arrays (csrc/gu_probe.hip) ------
+ * gu_ac_run, gu_reinforce_run and gu_is_run rest on the build's own exp, a correctly rounded reciprocal and the softmax of one row
+ * (include/gu.h: "THE BUILD'S EXP", rules 2 and 3 of gu_ac_run, RECIP of gu_is_run; csrc/gu_softmax.hpp).  These two calls run the
+ * very functions the learner kernels inline on host arrays of n items, one lane per item, so that a test can reach arguments
+ * learning never produces and compare with exact arithmetic.  They wait for the stream, use the engine's scratch only and change
+ * no table, env state or carry; they need no grid.  GU_ERR_INVALID for a NULL pointer, an unknown op, n < 0 or n > GU_PROBE_MAX;
+ * n = 0 is a no-op.
+ * gu_probe_numeric : y[i] = f(x[i]); op GU_PROBE_EXP: gu_exp (x <= 0 or -inf; NaN and x > 0 unspecified), GU_PROBE_RECIP14: the
+ *   correctly rounded 1 / x of x in [1, 4] (unspecified outside), GU_PROBE_IS_RECIP: RECIP(x) of a positive normal x whose
+ *   reciprocal is normal (unspecified otherwise).
+ * gu_probe_numeric_softmax : for row i of pref[n][4] and word w[i]: e[i][0..3] and Z[i] of rule 2, iz[i] = the reciprocal of Z[i]
+ *   as the kernels compute it, action[i] of rule 3. */
+#define GU_PROBE_EXP 0
+#define GU_PROBE_RECIP14 1
+#define GU_PROBE_IS_RECIP 2
+#define GU_PROBE_MAX (1ll << 24)
+int gu_probe_numeric(gu_handle h, int32_t op, int64_t n, const double *x, double *y);
+int gu_probe_numeric_softmax(gu_handle h, int64_t n, const double *pref, const uint32_t *w, double *e, double *Z, double *iz,
+                             int32_t *action);
+
 /* ---- timing: HIP events on the handle's own stream (torch.cuda.Event cannot see it) ----- */
 int gu_timer_begin(gu_handle h);
 int gu_timer_end(gu_handle h, float *milliseconds); /* records, waits, returns elapsed */

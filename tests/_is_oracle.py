@@ -27,7 +27,8 @@ def ratio_table(eps_q16):
 class IsOracle(TD.TdOracle):
     """TdOracle plus the cumulative weights c [n][S][4] and the episode buffers: buf_sa / buf_r / buf_c [n][IS_MAX] (s*4+a, r and
     the class of the action, oldest first; -1 / 0 / 0 beyond the count), buf_cnt [n], and buf_L, the L of the last call that
-    touched the envs if it was an `is_run`, else 0 (dropped).  walked / passes count the entries learned from and the passes."""
+    touched the envs if it was an `is_run`, else 0 (dropped).  walked / passes count the entries learned from and the passes,
+    cap_eq / cap_gt / low the passes that the weight window ended and on which side."""
 
     def __init__(self, grid, seed, n, env_id0=0, q0=0.0):
         super(IsOracle, self).__init__(grid, seed, n, env_id0, q0)
@@ -38,6 +39,7 @@ class IsOracle(TD.TdOracle):
         self.buf_cnt = np.zeros(self.n, np.int32)
         self.buf_L = 0
         self.walked = self.passes = 0
+        self.cap_eq = self.cap_gt = self.low = 0  # passes ended on a greedy entry by W == w_cap, by W > w_cap, by W < 2^-256
 
     def drop_buffer(self):
         """What every other call that touches the envs or the tables does to the buffer."""
@@ -100,7 +102,11 @@ class IsOracle(TD.TdOracle):
             m_now = (row == mx[:, None]).sum(axis=1)
             Wn = W[live] * R[m_now, cl]
             W[live] = Wn
-            alive[live] = (qa == mx) & (Wn >= W_MIN) & (Wn < w_cap)
+            greedy = qa == mx
+            self.cap_eq += int((greedy & (Wn == w_cap)).sum())
+            self.cap_gt += int((greedy & (Wn > w_cap)).sum())
+            self.low += int((greedy & (Wn < W_MIN)).sum())
+            alive[live] = greedy & (Wn >= W_MIN) & (Wn < w_cap)
         self.buf_sa[who] = -1
         self.buf_r[who] = 0
         self.buf_c[who] = 0
