@@ -125,3 +125,9 @@ class LambdaOracle(TD.TdOracle):
         self.carry_valid = False  # gu_lambda_run ends gu_td_run's SARSA carry
         self.key = (method, K)
         return dict(obs=obs, reward=rew, done=don, ret=rew.astype(np.int64).sum(axis=0), episodes=don.sum(axis=0).astype(np.int32))
+
+
+def signed_zero_table(n, S, seed=1):
+    """A table of -0.0 and 2.0 entries.  Learned with alpha = -0.0 it keeps -0.0 in pairs of the window while later steps have
+    g = +0.0, so an update by g * P_j with P_j = 0 would turn them into +0.0: only the P_j != 0 rule keeps lambda = 0 exact there."""
+    return np.where(np.random.default_rng(seed).random((n, S, 4)) < 0.5, -0.0, 2.0)

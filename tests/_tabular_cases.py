@@ -1,5 +1,9 @@
-"""Grids and helpers shared by the device tests of the tabular learners (test_gpu_td.py, test_gpu_dyna.py)."""
+"""Grids and the scaffold shared by the device tests of the learners (test_gpu_{td,nstep,lambda,dyna,sweep,double,explore,search,mcts,
+is,ac,reinforce,fa}.py), by tests/_learners.py and by the overlay and numeric-edge tests: a batch next to its CPU restatement,
+several restatements side by side as one, and step counts next to 2^32.  pytest does not rewrite the asserts of this module, so
+each one says what differed."""
 import numpy as np
+import pytest
 
 import griduniverse_amd as gua
 from griduniverse_amd.grid import GridSpec
@@ -70,3 +74,77 @@ def _random_grids(n, W, H, seed):
         wall, start, goal = C.generate_maze(seed, k, W, H)
         out.append(dict(W=W, H=H, starts=[start], goals=[goal], lava=[], walls=np.flatnonzero(wall).tolist()))
     return out
+
+
+def open_grid(W, H):
+    return dict(W=W, H=H, starts=[0], goals=[W * H - 1], lava=[], walls=[])
+
+
+def code(call):
+    """The code of the GuError that `call` must raise."""
+    with pytest.raises(gua.GuError) as err:
+        call()
+    return err.value.code
+
+
+class SideBySide(object):
+    """Several restatements, each of one group of envs, read as one batch in env order."""
+
+    def __init__(self, oracles):
+        self.oracles = list(oracles)
+
+    def reset(self):
+        return np.concatenate([o.reset() for o in self.oracles])
+
+    def run(self, call):
+        """call(o) of every restatement -- a launch that returns a dict of arrays [..., n] -- joined along the env axis."""
+        parts = [call(o) for o in self.oracles]
+        return {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]}
+
+    def cat(self, per_oracle):
+        """per_oracle(o), an array [n, ...] such as a table, of every restatement, joined along the env axis."""
+        return np.concatenate([per_oracle(o) for o in self.oracles])
+
+
+def same_env_state(vec, oracles):
+    """vec's env state against one restatement's, or against several side by side."""
+    oracles = oracles.oracles if isinstance(oracles, SideBySide) else oracles if isinstance(oracles, (list, tuple)) else [oracles]
+    st = vec.get_state()
+    for k in ('pos', 'done', 'episode', 'tcount'):
+        want = np.concatenate([getattr(o.state, k) for o in oracles])
+        assert np.array_equal(st[k], want), 'env state: %s differs in envs %s' % (k, _where(st[k], want))
+
+
+def _where(got, want):
+    return np.flatnonzero(np.asarray(got) != want)[:8].tolist() if np.shape(got) == np.shape(want) else 'all (shapes %s, %s)' % (
+        np.shape(got), np.shape(want))
+
+
+def multigrid_batch(make_oracle, n_grids, N, W=9, H=9, grids_seed=17, seed=6):
+    """N envs on n_grids distinct mazes, N // n_grids envs each, and make_oracle(grid, seed, n, env_id0) of every group."""
+    grids = _random_grids(n_grids, W, H, grids_seed)
+    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=seed)
+    group = N // n_grids
+    return vec, SideBySide(make_oracle(_grid(g), seed, group, k * group) for k, g in enumerate(grids))
+
+
+def device_maze_batch(make_oracle, n_grids, N=256, W=11, H=11, maze_seed=31, seed=2):
+    """The same on mazes that the device generates; the restatements get the host generator's."""
+    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=seed)
+    group = N // n_grids
+    oracles = []
+    for k in range(n_grids):
+        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
+        oracles.append(make_oracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]), seed, group,
+                                   k * group))
+    return vec, SideBySide(oracles)
+
+
+def counts_near_2_32(vec, o, N, t0=2 ** 32 - 100, stride=3, bump=7):
+    """Step counts of t0, and t0 + bump in every stride-th env so that envs cross the multiple of 2^32 at different steps, set on
+    the device and in the restatement; returns them."""
+    tc = np.full(N, t0, np.uint64)
+    tc[::stride] += bump
+    vec.set_state(tcount=tc)
+    o.set_state(tcount=tc)
+    return tc

@@ -16,7 +16,7 @@ from oracle import c_oracle as C
 from . import _ac_oracle as A
 from . import _golden as G
 from . import _td_oracle as O
-from .test_dyna_host import _greedy_walk, _shortest_from_start
+from . import _walks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -76,7 +76,7 @@ def _steps_to_shortest(grid, best, chunk=100, limit=10000):
     while done < limit:
         o.ac(chunk, 0.1, 0.1, 0.99)
         done += chunk
-        if all(_greedy_walk(grid, o.h[e]) == best for e in range(o.n)):
+        if all(_walks._greedy_walk(grid, o.h[e]) == best for e in range(o.n)):
             return done
     return None
 
@@ -85,7 +85,7 @@ def test_actor_critic_learns_the_shortest_path_in_the_maze():
     """Measured with this restatement (which the device matches byte for byte): all four learners' argmax walks are the shortest
     24 steps after 8000 real steps, in line with a throwaway prototype (numpy's RNG) that needed 7000-9500.  The budget is 10 000."""
     grid = C.Grid.from_env(GridUniverseEnv(custom_world_fp=G.level_path('maze_11x11.txt')))
-    best = _shortest_from_start(grid)
+    best = _walks._shortest_from_start(grid)
     assert best == 24
     assert _steps_to_shortest(grid, best) == 8000
 

@@ -15,6 +15,7 @@ from oracle import gu_rng as R
 from . import _dyna_oracle as D
 from . import _golden as G
 from . import _td_oracle as O
+from . import _walks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -61,35 +62,6 @@ def test_stream_5_words_across_the_epoch_boundary():
     assert D.planning_words(6, [1], [2 ** 32])[0] != D.planning_words(6, [1], [0])[0]
 
 
-def _shortest_from_start(grid):
-    S = grid.S
-    s = np.repeat(np.arange(S, dtype=np.int32), 4)
-    a = np.tile(np.arange(4, dtype=np.int32), S)
-    nxt = C.look_step_ahead(grid, s, a, True)[0].reshape(S, 4)
-    dist = {int(grid.starts[0]): 0}
-    frontier = [int(grid.starts[0])]
-    while frontier:
-        nf = []
-        for c in frontier:
-            if grid.goal[c] or grid.lava[c]:
-                continue
-            for b in range(4):
-                n = int(nxt[c, b])
-                if n not in dist:
-                    dist[n] = dist[c] + 1
-                    nf.append(n)
-        frontier = nf
-    return min(v for k, v in dist.items() if grid.goal[k])
-
-
-def _greedy_walk(grid, q):
-    s, n = int(grid.starts[0]), 0
-    while not (grid.goal[s] or grid.lava[s]) and n <= grid.S:
-        nxt, _, _ = C.look_step_ahead(grid, np.array([s], np.int32), np.array([int(np.argmax(q[s]))], np.int32), True)
-        s, n = int(nxt[0]), n + 1
-    return n if grid.goal[s] else -1
-
-
 def _steps_to_shortest(grid, P, best, chunk=100, limit=20000):
     """Real steps until every learner's greedy walk from the start is a shortest path."""
     d = D.DynaOracle(grid, 3, 4)
@@ -98,14 +70,14 @@ def _steps_to_shortest(grid, P, best, chunk=100, limit=20000):
     while done < limit:
         d.dyna(chunk, P, 0.5, 0.95, int(0.1 * 65536))
         done += chunk
-        if all(_greedy_walk(grid, d.q[e]) == best for e in range(d.n)):
+        if all(_walks._greedy_walk(grid, d.q[e]) == best for e in range(d.n)):
             return done
     return None
 
 
 def test_planning_finds_the_shortest_path_in_fewer_real_steps():
     grid = C.Grid.from_env(GridUniverseEnv(custom_world_fp=G.level_path('maze_11x11.txt')))
-    best = _shortest_from_start(grid)
+    best = _walks._shortest_from_start(grid)
     with_planning = _steps_to_shortest(grid, 20, best)
     assert with_planning is not None
     without = _steps_to_shortest(grid, 0, best, limit=with_planning)

@@ -14,10 +14,8 @@ from oracle import gu_rng as R
 
 from . import _explore_oracle as EO
 from . import _td_oracle as O
+from ._behaviour import EXPLORE_BEHAVIOUR, coverage
 from ._tabular_cases import GRIDS, _grid
-
-# the settings of the behaviour checks
-BEHAVIOUR = dict(N=64, seed=7, alpha=0.1, gamma=0.99, plain_eps_q16=6554)
 
 
 def sparse_grid(W, H):
@@ -29,13 +27,8 @@ def sparse_grid(W, H):
     return C.Grid.from_lists(W, H, walls=[], goals=[S - 1], lava=[], starts=[0], reward=reward)
 
 
-def coverage(counts):
-    """Per learner: the state-action pairs it has tried."""
-    return (np.asarray(counts) != 0).sum(axis=(1, 2))
-
-
 def run_restatement(grid, T, rule, tables, eps_q16):
-    b = BEHAVIOUR
+    b = EXPLORE_BEHAVIOUR
     o = EO.ExploreOracle(grid, b['seed'], b['N'])
     o.set_tables(*tables)
     o.reset()
@@ -46,7 +39,7 @@ def run_restatement(grid, T, rule, tables, eps_q16):
 def behaviour_coverage(grid, T):
     """(coverage of the UCB learners, of the yardstick: the same restatement with zero tables and epsilon 0.1), per learner."""
     ucb, _ = run_restatement(grid, T, 'ucb', X.ucb_tables(1.0, 1024), 0)
-    plain, _ = run_restatement(grid, T, 'ucb', (np.zeros(2), np.zeros(2)), BEHAVIOUR['plain_eps_q16'])
+    plain, _ = run_restatement(grid, T, 'ucb', (np.zeros(2), np.zeros(2)), EXPLORE_BEHAVIOUR['plain_eps_q16'])
     return coverage(ucb.counts), coverage(plain.counts)
 
 

@@ -11,7 +11,7 @@ from oracle import c_oracle as C
 
 from . import _fa_oracle as FA
 from . import _td_oracle as O
-from .test_td_host import _bfs_lengths, _greedy_walk_lengths
+from ._walks import _bfs_lengths, _greedy_walk_lengths
 
 
 @pytest.mark.parametrize('method', [O.Q_LEARNING, O.SARSA])

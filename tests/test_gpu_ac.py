@@ -9,11 +9,11 @@ from griduniverse_amd import _lib
 from griduniverse_amd.algorithms import utils
 from griduniverse_amd.algorithms.policy_gradient import actor_critic
 from griduniverse_amd.engine import Engine
-from oracle import c_oracle as C
 
 from . import _ac_oracle as AO
 from . import _td_oracle as O
-from ._tabular_cases import GRIDS, _eps, _grid, _random_grids, _same, _spec
+from ._tabular_cases import (GRIDS, _eps, _grid, _same, _spec, counts_near_2_32, device_maze_batch, multigrid_batch, open_grid,
+                             same_env_state)
 
 pytestmark = pytest.mark.gpu
 
@@ -46,9 +46,7 @@ def test_tables_rows_and_stats_equal_the_oracle(grid, N):
     try:
         for _ in range(2):
             _launch(vec, o, T)
-        st = vec.get_state()
-        assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'], o.state.done)
-        assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
+        same_env_state(vec, o)
         assert o.h.any() and o.v.any()
     finally:
         vec.close()
@@ -73,14 +71,10 @@ def test_one_launch_equals_two():
         b.close()
 
 
-def _open(W, H):
-    return dict(W=W, H=H, starts=[0], goals=[W * H - 1], lava=[], walls=[])
-
-
 @pytest.mark.parametrize('W,H', [(2, 2), (4, 4)])
 def test_wall_bump_forwarding_on_small_open_grids(W, H):
     """On tiny grids many moves bump into the edge (s' == s): the next step must see the updated row and value."""
-    vec, o = _pair(_open(W, H), 256, 7, 0.5, 1.0)
+    vec, o = _pair(open_grid(W, H), 256, 7, 0.5, 1.0)
     try:
         for T in (123, 77):
             _launch(vec, o, T, aa=0.4, ac=0.5, gamma=0.8)
@@ -90,39 +84,27 @@ def test_wall_bump_forwarding_on_small_open_grids(W, H):
 
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
 def test_multigrid_learners_equal_the_oracle(n_grids, N):
-    grids = _random_grids(n_grids, 9, 9, 17)
-    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
-    group = N // n_grids
-    oracles = [AO.AcOracle(_grid(g), 6, group, env_id0=k * group) for k, g in enumerate(grids)]
+    vec, side = multigrid_batch(AO.AcOracle, n_grids, N)
     try:
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         for T in (150, 91):
             got = vec.actor_critic_run(T, 0.2, 0.25, 0.9, trajectory=True, stats=True)
-            parts = [o.ac(T, 0.2, 0.25, 0.9) for o in oracles]
-            _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-        assert vec.preferences().tobytes() == np.concatenate([o.h for o in oracles]).tobytes()
-        assert vec.state_values().tobytes() == np.concatenate([o.v for o in oracles]).tobytes()
+            _same(got, side.run(lambda o: o.ac(T, 0.2, 0.25, 0.9)))
+        assert vec.preferences().tobytes() == side.cat(lambda o: o.h).tobytes()
+        assert vec.state_values().tobytes() == side.cat(lambda o: o.v).tobytes()
     finally:
         vec.close()
 
 
 @pytest.mark.parametrize('n_grids', [4, 256])
 def test_device_maze_learners_equal_the_oracle(n_grids):
-    N, W, H, maze_seed = 256, 11, 11, 31
-    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
-    group = N // n_grids
-    oracles = []
-    for k in range(n_grids):
-        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
-        oracles.append(AO.AcOracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]), 2,
-                                   group, env_id0=k * group))
+    vec, side = device_maze_batch(AO.AcOracle, n_grids)
     try:
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         got = vec.actor_critic_run(200, 0.3, 0.3, 0.9, trajectory=True, stats=True)
-        parts = [o.ac(200, 0.3, 0.3, 0.9) for o in oracles]
-        _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-        assert vec.preferences().tobytes() == np.concatenate([o.h for o in oracles]).tobytes()
-        assert vec.state_values().tobytes() == np.concatenate([o.v for o in oracles]).tobytes()
+        _same(got, side.run(lambda o: o.ac(200, 0.3, 0.3, 0.9)))
+        assert vec.preferences().tobytes() == side.cat(lambda o: o.h).tobytes()
+        assert vec.state_values().tobytes() == side.cat(lambda o: o.v).tobytes()
     finally:
         vec.close()
 
@@ -132,10 +114,7 @@ def test_step_counts_across_the_epoch_boundary():
     N = 96
     vec, o = _pair(g, N, 12)
     try:
-        tc = np.full(N, 2 ** 32 - 100, np.uint64)
-        tc[::3] += 7  # per-env counts: envs cross the boundary at different steps
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N)
         for T in (130, 170):
             _launch(vec, o, T)
         assert np.array_equal(vec.get_state()['tcount'], tc + np.uint64(300))

@@ -1,6 +1,8 @@
 """Batched Expected SARSA (gu_esarsa_run, csrc/gu_td.hip) and Double Q-learning (gu_double_run, csrc/gu_double.hip) on the device
 against the CPU restatements of tests/_double_oracle.py: tables (both of a pair), trajectory rows, statistics and env state compared
 byte for byte."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -8,13 +10,13 @@ import griduniverse_amd as gua
 from griduniverse_amd import _lib
 from griduniverse_amd.engine import Engine
 from griduniverse_amd.grid import door_plane, fruit_plane, wind_plane
-from oracle import c_oracle as C
 
 from . import _double_oracle as O
 from . import _nstep_oracle as NO
 from . import _td_oracle as TD
-from ._tabular_cases import GRIDS, _eps, _grid, _random_grids, _same, _spec, spread_grid
-from .test_gpu_learners_at_scale import Learner, _crossing, _shared_grid_beyond_lds, _stores_past_a_boundary, big182
+from ._learners import DoubleQ, ExpectedSarsa, _crossing, _shared_grid_beyond_lds, _stores_past_a_boundary, big182
+from ._tabular_cases import (GRIDS, _eps, _grid, _same, _spec, code, counts_near_2_32, device_maze_batch, multigrid_batch, same_env_state,
+                             spread_grid)
 
 pytestmark = pytest.mark.gpu
 
@@ -58,12 +60,6 @@ def _tables(vec, kind):
     return vec.double_q_tables() if kind == 'double_q' else vec.q_table()
 
 
-def _same_state(vec, o):
-    st = vec.get_state()
-    for k in ('pos', 'done', 'episode', 'tcount'):
-        assert np.array_equal(st[k], getattr(o.state, k)), k
-
-
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('grid', sorted(GRIDS))
 @pytest.mark.parametrize('N', [1, 63, 4096])
@@ -78,7 +74,7 @@ def test_tables_rows_and_stats_equal_the_oracle(grid, kind, N):
             got = _tables(vec, kind)
             assert got.shape == o.q.shape and got.tobytes() == o.q.tobytes()
         assert (o.q != q0).any()
-        _same_state(vec, o)
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -112,45 +108,36 @@ def test_split_launches_with_changed_hyper_parameters(kind):
         for alpha, eps in ((0.5, 0.3), (0.1, 0.0), (0.3, 1.0), (0.2, 0.05)):
             _launch(vec, o, kind, 257, alpha, 0.95, eps)
         assert _tables(vec, kind).tobytes() == o.q.tobytes()
-        _same_state(vec, o)
+        same_env_state(vec, o)
     finally:
         vec.close()
 
 
-def _grouped(kind, vec, oracles, launches):
-    assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+def _grouped(kind, vec, side, launches):
+    assert np.array_equal(vec.reset(), side.reset())
     for T in launches:
         got = _device(vec, kind, T, 0.2, 0.9, 0.25, trajectory=True, stats=True)
-        parts = [_restate(o, kind, T, 0.2, 0.9, 0.25) for o in oracles]
-        _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-    assert _tables(vec, kind).tobytes() == np.concatenate([o.q for o in oracles]).tobytes()
+        _same(got, side.run(lambda o: _restate(o, kind, T, 0.2, 0.9, 0.25)))
+    assert _tables(vec, kind).tobytes() == side.cat(lambda o: o.q).tobytes()
 
 
 @pytest.mark.parametrize('kind', KINDS)
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
 def test_multigrid_learners_equal_the_oracle(kind, n_grids, N):
-    grids = _random_grids(n_grids, 9, 9, 17)
-    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
-    group = N // n_grids
+    vec, side = multigrid_batch(functools.partial(_oracle, kind), n_grids, N)
     try:
         _fill(vec, kind, 0.0)
-        _grouped(kind, vec, [_oracle(kind, _grid(g), 6, group, k * group) for k, g in enumerate(grids)],
-                 (150, 90) if n_grids == 4 else (60, 40))  # (one restatement per grid: shorter launches where there are 256)
+        _grouped(kind, vec, side, (150, 90) if n_grids == 4 else (60, 40))  # (one restatement per grid: shorter launches where there are 256)
     finally:
         vec.close()
 
 
 @pytest.mark.parametrize('kind', KINDS)
 def test_device_maze_learners_equal_the_oracle(kind):
-    N, W, H, maze_seed, n_grids = 256, 11, 11, 31, 256
-    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
-    oracles = []
-    for k in range(n_grids):
-        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
-        oracles.append(_oracle(kind, C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]), 2, 1, k))
+    vec, side = device_maze_batch(functools.partial(_oracle, kind), 256)
     try:
         _fill(vec, kind, 0.0)
-        _grouped(kind, vec, oracles, (50, 30))
+        _grouped(kind, vec, side, (50, 30))
     finally:
         vec.close()
 
@@ -161,10 +148,7 @@ def test_step_counts_across_the_epoch_boundary(kind):
     N = 96
     vec, o = _pair(kind, GRIDS['open8x8'](), N, 12)
     try:
-        tc = np.full(N, 2 ** 32 - 100, np.uint64)
-        tc[::3] += 7  # per-env counts: envs cross the boundary at different steps
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N)
         _launch(vec, o, kind, 300, 0.2, 0.9, 0.5)
         assert _tables(vec, kind).tobytes() == o.q.tobytes()
         assert np.array_equal(vec.get_state()['tcount'], tc + np.uint64(300))
@@ -225,35 +209,29 @@ def test_pairs_installed_for_some_envs_are_read_back_and_learned_on():
         vec.close()
 
 
-def _code(call):
-    with pytest.raises(gua.GuError) as err:
-        call()
-    return err.value.code
-
-
 def test_argument_and_state_errors():
     g = GRIDS['test_env']()
     with Engine(64, _spec(g)) as eng:
         lib, h = eng.lib, eng._h
-        assert _code(lambda: eng.double_run(10)) == -4  # before gu_double_init
-        assert _code(eng.double_get_q) == -4
-        assert _code(lambda: eng.double_set_q(np.zeros((1, eng.spec.S, 2, 4)))) == -4
-        assert _code(lambda: eng.esarsa_run(10)) == -4  # before gu_td_init
+        assert code(lambda: eng.double_run(10)) == -4  # before gu_double_init
+        assert code(eng.double_get_q) == -4
+        assert code(lambda: eng.double_set_q(np.zeros((1, eng.spec.S, 2, 4)))) == -4
+        assert code(lambda: eng.esarsa_run(10)) == -4  # before gu_td_init
         eng.td_init(0.25)
         eng.double_init(0.25)
-        assert _code(lambda: eng.double_get_q(60, 5)) == -1
-        assert _code(lambda: eng.double_get_q(-1, 2)) == -1
-        assert _code(lambda: eng.double_set_q(np.zeros((5, eng.spec.S, 2, 4)), env0=60)) == -1
-        assert _code(lambda: eng.double_init(float('inf'))) == -1
+        assert code(lambda: eng.double_get_q(60, 5)) == -1
+        assert code(lambda: eng.double_get_q(-1, 2)) == -1
+        assert code(lambda: eng.double_set_q(np.zeros((5, eng.spec.S, 2, 4)), env0=60)) == -1
+        assert code(lambda: eng.double_init(float('inf'))) == -1
         for fn in (lib.gu_esarsa_run, lib.gu_double_run):
             for kw in (dict(eps_q16=65537), dict(alpha=float('nan')), dict(gamma=float('inf')), dict(T=-1), dict(flags=_lib.F_AUTO_RESET)):
                 args = dict(T=10, alpha=0.1, gamma=0.9, eps_q16=0, flags=0)
                 args.update(kw)
-                assert _code(lambda: _lib.check(fn(h, args['T'], args['alpha'], args['gamma'], args['eps_q16'], args['flags']))) == -1, kw
+                assert code(lambda: _lib.check(fn(h, args['T'], args['alpha'], args['gamma'], args['eps_q16'], args['flags']))) == -1, kw
         # the agent trail is on and the launch writes no rows to feed it
         eng.trail_enable(16)
-        assert _code(lambda: eng.esarsa_run(10)) == -6
-        assert _code(lambda: eng.double_run(10)) == -6
+        assert code(lambda: eng.esarsa_run(10)) == -6
+        assert code(lambda: eng.double_run(10)) == -6
         assert eng.td_get_q().tobytes() == np.full((64, eng.spec.S, 4), 0.25).tobytes()
         assert eng.double_get_q().tobytes() == np.full((64, eng.spec.S, 2, 4), 0.25).tobytes()
 
@@ -305,8 +283,8 @@ def test_a_grid_of_another_state_count_drops_the_pairs():
         eng.double_run(40)
         assert eng.double_get_q().shape == (8, 16, 2, 4) and eng.double_get_q().any()
         eng.set_grid(_spec(GRIDS['open8x8']()))
-        assert _code(lambda: eng.double_run(5)) == -4
-        assert _code(eng.double_get_q) == -4
+        assert code(lambda: eng.double_run(5)) == -4
+        assert code(eng.double_get_q) == -4
         eng.double_init(0.5)
         assert eng.double_get_q().tobytes() == np.full((8, 64, 2, 4), 0.5).tobytes()
         eng.double_run(40)
@@ -317,44 +295,7 @@ def test_a_grid_of_another_state_count_drops_the_pairs():
         eng.double_run(10)
 
 
-# ---- big grids and a store past 4 GiB, with the machinery of tests/test_gpu_learners_at_scale.py ----
-class ExpectedSarsa(Learner):
-    def oracle(self, grid, seed, n, env_id0):
-        return O.EsarsaOracle(grid, seed, n, env_id0, 0.5)
-
-    def device(self, vec, T, **kw):
-        return vec.expected_sarsa_run(T, alpha=0.25, discount_factor=0.9, epsilon=0.3, **kw)
-
-    def restate(self, o, T):
-        return o.esarsa(T, 0.25, 0.9, _eps(0.3))
-
-
-class DoubleQ(Learner):
-    def oracle(self, grid, seed, n, env_id0):
-        return O.DoubleOracle(grid, seed, n, env_id0, 0.5)
-
-    def prepare(self, vec):
-        vec._ensure_pairs(0.5)
-
-    def device(self, vec, T, **kw):
-        return vec.double_q_run(T, alpha=0.25, discount_factor=0.9, epsilon=0.3, **kw)
-
-    def restate(self, o, T):
-        return o.run(T, 0.25, 0.9, _eps(0.3))
-
-    def got(self, vec, env0, n):
-        return dict(q=vec.double_q_tables(env0, n))
-
-    @staticmethod
-    def install(vec, tables, env0):
-        vec.set_double_q_tables(tables['q'], env0)
-
-    @staticmethod
-    def restate_install(o, tables, env0):
-        if len(tables['q']):
-            o.set_q(tables['q'], env0)
-
-
+# ---- big grids and a store past 4 GiB, with the adapters and the harness of tests/_learners.py ----
 @pytest.mark.parametrize('learner', [ExpectedSarsa, DoubleQ])
 def test_a_shared_grid_beyond_lds(learner):
     """182 x 182: the planes do not fit LDS, so the L2 instantiations run, on cells past 32 767."""

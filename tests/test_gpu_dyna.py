@@ -15,7 +15,8 @@ from oracle import c_oracle as C
 
 from . import _dyna_oracle as D
 from . import _golden as G
-from ._tabular_cases import GRIDS, _eps, _grid, _pair, _random_grids, _same, _spec
+from ._tabular_cases import (GRIDS, _eps, _grid, _pair, _random_grids, _same, _spec, counts_near_2_32, device_maze_batch, multigrid_batch,
+                             open_grid, same_env_state)
 
 pytestmark = pytest.mark.gpu
 
@@ -41,9 +42,7 @@ def test_tables_model_rows_and_stats_equal_the_oracle(grid, P):
             _same(got, o.dyna(T, P, 0.25, 0.9, _eps(0.2)))
             assert vec.q_table().tobytes() == o.q.tobytes()
             _same_model(vec, [o])
-        st = vec.get_state()
-        assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'], o.state.done)
-        assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -65,8 +64,7 @@ def test_4096_learners_equal_the_oracle(grid):
 def test_planning_that_rewrites_the_current_row(W, H):
     """On a tiny grid planning rewrites the row of the state the learner stands in on almost every update: the next real step
     must choose from the row after planning, not from a stale copy."""
-    g = dict(W=W, H=H, starts=[0], goals=[W * H - 1], lava=[], walls=[])
-    vec, o = _pair(g, 128, 13, q0=0.75)
+    vec, o = _pair(open_grid(W, H), 128, 13, q0=0.75)
     try:
         for eps in (0.0, 0.2):
             got = vec.dyna_run(150, 50, alpha=0.5, discount_factor=0.9, epsilon=eps, trajectory=True, stats=True)
@@ -79,39 +77,27 @@ def test_planning_that_rewrites_the_current_row(W, H):
 
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
 def test_multigrid_learners_equal_the_oracle(n_grids, N):
-    grids = _random_grids(n_grids, 9, 9, 17)
-    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
-    group = N // n_grids
-    oracles = [D.DynaOracle(_grid(g), 6, group, env_id0=k * group) for k, g in enumerate(grids)]
+    vec, side = multigrid_batch(D.DynaOracle, n_grids, N)
     try:
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         for T, P in ((100, 5), (60, 1)):
             got = vec.dyna_run(T, P, alpha=0.2, discount_factor=0.9, epsilon=0.25, trajectory=True, stats=True)
-            parts = [o.dyna(T, P, 0.2, 0.9, _eps(0.25)) for o in oracles]
-            _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-        assert vec.q_table().tobytes() == np.concatenate([o.q for o in oracles]).tobytes()
-        _same_model(vec, oracles)
+            _same(got, side.run(lambda o: o.dyna(T, P, 0.2, 0.9, _eps(0.25))))
+        assert vec.q_table().tobytes() == side.cat(lambda o: o.q).tobytes()
+        _same_model(vec, side.oracles)
     finally:
         vec.close()
 
 
 @pytest.mark.parametrize('n_grids', [4, 256])
 def test_device_maze_learners_equal_the_oracle(n_grids):
-    N, W, H, maze_seed = 256, 11, 11, 31
-    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
-    group = N // n_grids
-    oracles = []
-    for k in range(n_grids):
-        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
-        oracles.append(D.DynaOracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]), 2, group,
-                                    env_id0=k * group))
+    vec, side = device_maze_batch(D.DynaOracle, n_grids)
     try:
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         got = vec.dyna_run(120, 5, alpha=0.3, discount_factor=0.9, epsilon=0.1, trajectory=True, stats=True)
-        parts = [o.dyna(120, 5, 0.3, 0.9, _eps(0.1)) for o in oracles]
-        _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-        assert vec.q_table().tobytes() == np.concatenate([o.q for o in oracles]).tobytes()
-        _same_model(vec, oracles)
+        _same(got, side.run(lambda o: o.dyna(120, 5, 0.3, 0.9, _eps(0.1))))
+        assert vec.q_table().tobytes() == side.cat(lambda o: o.q).tobytes()
+        _same_model(vec, side.oracles)
     finally:
         vec.close()
 
@@ -191,10 +177,7 @@ def test_step_counts_across_the_epoch_boundaries(P, t0):
     N = 96
     vec, o = _pair(g, N, 12)
     try:
-        tc = np.full(N, t0, np.uint64)
-        tc[::3] += 7  # per-env counts: envs cross at different steps
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N, t0)
         got = vec.dyna_run(100, P, alpha=0.2, discount_factor=0.9, epsilon=0.5, trajectory=True, stats=True)
         _same(got, o.dyna(100, P, 0.2, 0.9, _eps(0.5)))
         assert vec.q_table().tobytes() == o.q.tobytes()

@@ -14,9 +14,10 @@ from oracle import c_oracle as C
 
 from . import _explore_oracle as EO
 from . import _td_oracle as TD
-from ._tabular_cases import GRIDS, _eps, _grid, _pair, _random_grids, _same, _spec
-from .test_explore_host import BEHAVIOUR, coverage
-from .test_td_host import _bfs_lengths, _greedy_walk_lengths
+from ._behaviour import EXPLORE_BEHAVIOUR, coverage
+from ._tabular_cases import (GRIDS, _eps, _grid, _pair, _same, _spec, code, counts_near_2_32, device_maze_batch, multigrid_batch,
+                             same_env_state)
+from ._walks import _bfs_lengths, _greedy_walk_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -49,12 +50,6 @@ def _same_tables(vec, oracles):
     assert got.dtype == np.uint32 and got.tobytes() == np.concatenate([o.counts for o in oracles]).tobytes()
 
 
-def _same_state(vec, oracles):
-    st = vec.get_state()
-    for k in ('pos', 'done', 'episode', 'tcount'):
-        assert np.array_equal(st[k], np.concatenate([getattr(o.state, k) for o in oracles])), k
-
-
 def _run(vec, o, T, rule, eps, alpha=0.25, gamma=0.9):
     got = vec.explore_run(T, rule, alpha=alpha, discount_factor=gamma, epsilon=eps, trajectory=True, stats=True)
     _same(got, o.explore(T, MODES[rule], alpha, gamma, _eps(eps)))
@@ -72,7 +67,7 @@ def test_tables_counts_rows_stats_and_state_equal_the_oracle(grid, rule, case):
         _install(vec, [o], U, B)
         for T in (200, 100):  # two launches: the second starts from the first one's tables and counts
             _run(vec, o, T, rule, eps)
-        _same_state(vec, [o])
+        same_env_state(vec, o)
         assert np.array_equal(o.counts.astype(np.int64).sum(axis=(1, 2)), np.full(63, 300))
     finally:
         vec.close()
@@ -87,7 +82,7 @@ def test_4096_learners_equal_the_oracle(rule):
         _install(vec, [o], U, B)
         _run(vec, o, 120, rule, 0.05, alpha=0.3, gamma=0.95)
         _run(vec, o, 40, rule, 0.0, alpha=0.3, gamma=0.95)
-        _same_state(vec, [o])
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -141,42 +136,30 @@ def test_split_launch_equals_one_launch(rule):
 @pytest.mark.parametrize('rule', ['ucb', 'thompson'])
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
 def test_a_batch_of_distinct_mazes_equals_the_oracle(n_grids, N, rule):
-    grids = _random_grids(n_grids, 9, 9, 17)
-    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
-    group = N // n_grids
-    oracles = [EO.ExploreOracle(_grid(g), 6, group, env_id0=k * group) for k, g in enumerate(grids)]
+    vec, side = multigrid_batch(EO.ExploreOracle, n_grids, N)
     try:
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         for case, T in (('epsilon', 60), ('l2', 30)):
             U, B, eps = _tables(case, rule)
-            _install(vec, oracles, U, B)
+            _install(vec, side.oracles, U, B)
             got = vec.explore_run(T, rule, alpha=0.2, discount_factor=0.9, epsilon=eps, trajectory=True, stats=True)
-            parts = [o.explore(T, MODES[rule], 0.2, 0.9, _eps(eps)) for o in oracles]
-            _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-        _same_tables(vec, oracles)
-        _same_state(vec, oracles)
+            _same(got, side.run(lambda o: o.explore(T, MODES[rule], 0.2, 0.9, _eps(eps))))
+        _same_tables(vec, side.oracles)
+        same_env_state(vec, side)
     finally:
         vec.close()
 
 
 def test_device_mazes_equal_the_oracle():
-    N, W, H, maze_seed, n_grids = 256, 11, 11, 31, 4
-    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
-    group = N // n_grids
-    oracles = []
-    for k in range(n_grids):
-        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
-        oracles.append(EO.ExploreOracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]), 2, group,
-                                        env_id0=k * group))
+    vec, side = device_maze_batch(EO.ExploreOracle, 4)
     try:
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         U, B, _ = _tables('builder1024', 'thompson')
-        _install(vec, oracles, U, B)
+        _install(vec, side.oracles, U, B)
         got = vec.explore_run(80, 'thompson', alpha=0.2, discount_factor=0.9, epsilon=0.0, trajectory=True, stats=True)
-        parts = [o.explore(80, EO.THOMPSON, 0.2, 0.9, 0) for o in oracles]
-        _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-        _same_tables(vec, oracles)
-        _same_state(vec, oracles)
+        _same(got, side.run(lambda o: o.explore(80, EO.THOMPSON, 0.2, 0.9, 0)))
+        _same_tables(vec, side.oracles)
+        same_env_state(vec, side)
     finally:
         vec.close()
 
@@ -187,15 +170,12 @@ def test_step_counts_across_the_epoch_boundary():
     N = 96
     vec, o = _pair(g, N, 12)
     try:
-        tc = np.full(N, 2 ** 32 - 30, np.uint64)
-        tc[::3] += 7  # per-env counts: envs cross at different steps
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N, 2 ** 32 - 30)
         U, B, _ = _tables('builder1024', 'thompson')
         _install(vec, [o], U, B)
         _run(vec, o, 60, 'thompson', 0.1, alpha=0.2, gamma=0.9)
         assert np.array_equal(vec.get_state()['tcount'], tc + np.uint64(60))
-        _same_state(vec, [o])
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -248,12 +228,6 @@ def test_explore_run_ends_the_sarsa_carry():
         vec.close()
 
 
-def _code(call):
-    with pytest.raises(gua.GuError) as err:
-        call()
-    return err.value.code
-
-
 def test_edges_and_errors():
     g = GRIDS['test_env']()
     ok = np.ones(8)
@@ -262,26 +236,26 @@ def test_edges_and_errors():
         S = eng.spec.S
         buf = np.zeros((8, S, 4), np.uint32)
         # before gu_td_init
-        assert _code(eng.explore_init) == -4
-        assert _code(lambda: eng.explore_run(10)) == -4
+        assert code(eng.explore_init) == -4
+        assert code(lambda: eng.explore_run(10)) == -4
         # the tables need neither grid-sized storage nor Q tables; their checks
         for C_, U, B in ((1, ok, ok), (4097, np.ones(4097), np.ones(4097)), (0, ok, ok), (-3, ok, ok)):
-            assert _code(lambda: _lib.check(lib.gu_explore_set_tables(h, C_, p(U), p(B)))) == -1
+            assert code(lambda: _lib.check(lib.gu_explore_set_tables(h, C_, p(U), p(B)))) == -1
         for k, v in ((0, -1e-9), (7, float('nan')), (3, float('inf')), (5, -float('inf'))):
             for which in (0, 1):
                 t = [ok.copy(), ok.copy()]
                 t[which][k] = v
-                assert _code(lambda: eng.set_exploration(*t)) == -1
-        assert _code(lambda: _lib.check(lib.gu_explore_set_tables(h, 8, None, p(ok)))) == -1
-        assert _code(lambda: _lib.check(lib.gu_explore_set_tables(h, 8, p(ok), None))) == -1
+                assert code(lambda: eng.set_exploration(*t)) == -1
+        assert code(lambda: _lib.check(lib.gu_explore_set_tables(h, 8, None, p(ok)))) == -1
+        assert code(lambda: _lib.check(lib.gu_explore_set_tables(h, 8, p(ok), None))) == -1
         with pytest.raises(ValueError):
             eng.set_exploration(np.ones(4), np.ones(5))
         eng.td_init(0.5)
-        assert _code(lambda: eng.explore_run(10)) == -4        # no counts
-        assert _code(lambda: eng.explore_get_counts()) == -4
-        assert _code(lambda: eng.explore_set_counts(buf)) == -4
+        assert code(lambda: eng.explore_run(10)) == -4        # no counts
+        assert code(lambda: eng.explore_get_counts()) == -4
+        assert code(lambda: eng.explore_set_counts(buf)) == -4
         eng.explore_init()
-        assert _code(lambda: eng.explore_run(10)) == -4        # no tables (every set_tables above was refused)
+        assert code(lambda: eng.explore_run(10)) == -4        # no tables (every set_tables above was refused)
         eng.set_exploration(np.zeros(2), np.zeros(2))          # the smallest; +0.0 entries are fine
         eng.set_exploration(*X.ucb_tables(1.0, 4096))          # the largest
         eng.reset()
@@ -293,8 +267,8 @@ def test_edges_and_errors():
         for kw in (dict(mode=2), dict(mode=-1), dict(eps_q16=65537), dict(T=-1), dict(T=100000001), dict(alpha=float('nan')),
                    dict(gamma=float('inf')), dict(flags=_lib.F_AUTO_RESET)):
             a = dict(args, **kw)
-            assert _code(lambda: _lib.check(lib.gu_explore_run(h, a['T'], a['mode'], a['alpha'], a['gamma'], a['eps_q16'], a['flags']))) == -1, kw
-        assert _code(lambda: eng.explore_run(10, trajectory=True)) == -4  # no trajectory buffer reserved
+            assert code(lambda: _lib.check(lib.gu_explore_run(h, a['T'], a['mode'], a['alpha'], a['gamma'], a['eps_q16'], a['flags']))) == -1, kw
+        assert code(lambda: eng.explore_run(10, trajectory=True)) == -4  # no trajectory buffer reserved
         with pytest.raises(KeyError):
             eng.explore_run(10, 'optimistic')
         # T = 0 changes nothing
@@ -304,11 +278,11 @@ def test_edges_and_errors():
         assert all(np.array_equal(before[k], after[k]) for k in before)
         assert eng.td_get_q().tobytes() == q.tobytes() and eng.explore_get_counts().tobytes() == c.tobytes()
         # the count accessors
-        assert _code(lambda: eng.explore_get_counts(6, 3)) == -1
-        assert _code(lambda: eng.explore_get_counts(-1, 2)) == -1
-        assert _code(lambda: eng.explore_set_counts(buf[:3], env0=6)) == -1
-        assert _code(lambda: _lib.check(lib.gu_explore_get_counts(h, 0, 8, None))) == -1
-        assert _code(lambda: _lib.check(lib.gu_explore_set_counts(h, 0, 8, None))) == -1
+        assert code(lambda: eng.explore_get_counts(6, 3)) == -1
+        assert code(lambda: eng.explore_get_counts(-1, 2)) == -1
+        assert code(lambda: eng.explore_set_counts(buf[:3], env0=6)) == -1
+        assert code(lambda: _lib.check(lib.gu_explore_get_counts(h, 0, 8, None))) == -1
+        assert code(lambda: _lib.check(lib.gu_explore_set_counts(h, 0, 8, None))) == -1
         assert eng.explore_get_counts(8, 0).shape == (0, S, 4)
         with pytest.raises(ValueError):
             eng.explore_set_counts(np.zeros((2, S, 3), np.uint32))
@@ -321,9 +295,9 @@ def test_edges_and_errors():
         assert not eng.explore_get_counts().any()
         # a grid of another size drops the counts with the Q tables; the U and B tables stay
         eng.set_grid(_spec(GRIDS['default4x4']()))
-        assert _code(eng.explore_init) == -4
+        assert code(eng.explore_init) == -4
         eng.td_init()
-        assert _code(lambda: eng.explore_run(10)) == -4 and _code(lambda: eng.explore_get_counts()) == -4
+        assert code(lambda: eng.explore_run(10)) == -4 and code(lambda: eng.explore_get_counts()) == -4
         eng.explore_init()
         eng.reset()
         eng.explore_run(10)
@@ -349,7 +323,7 @@ def test_coverage_on_the_device_equals_the_restatement():
     rewards (start 0, goal 63, -1 a step).  The device equals the restatement by construction, which is what is asserted; the
     coverage (mean / least per learner, of 252 pairs) is printed.  With a -1 step reward a table of zeros is optimistic already,
     so the two are expected to be close here."""
-    b = BEHAVIOUR
+    b = EXPLORE_BEHAVIOUR
     g = dict(W=8, H=8, starts=[0], goals=[63], lava=[], walls=[])
     for name, tables, eps_q16 in (('UCB', X.ucb_tables(1.0, 1024), 0), ('epsilon-greedy', (np.zeros(2), np.zeros(2)), b['plain_eps_q16'])):
         vec = gua.VecGridUniverse(b['N'], template=_spec(g), seed=b['seed'])

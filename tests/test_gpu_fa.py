@@ -12,8 +12,8 @@ from oracle import c_oracle as C
 
 from . import _fa_oracle as FA
 from . import _td_oracle as O
-from ._tabular_cases import GRIDS, _eps, _grid, _random_grids, _same, _spec
-from .test_td_host import _bfs_lengths, _greedy_walk_lengths
+from ._tabular_cases import GRIDS, _eps, _grid, _same, _spec, counts_near_2_32, multigrid_batch, same_env_state
+from ._walks import _bfs_lengths, _greedy_walk_lengths
 
 pytestmark = pytest.mark.gpu
 
@@ -44,12 +44,6 @@ def _tables(vec, o):
     assert vec.fa_q_table().tobytes() == o.q_tables().tobytes()
 
 
-def _state(vec, o):
-    st = vec.get_state()
-    assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'], o.state.done)
-    assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
-
-
 @pytest.mark.parametrize('feats', sorted(FEATURES))
 @pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
 @pytest.mark.parametrize('grid', sorted(GRIDS))
@@ -64,7 +58,7 @@ def test_weights_values_rows_and_stats_equal_the_oracle(grid, method, N, feats):
             got = vec.fa_run(T, method, alpha=0.25 / o.K, discount_factor=0.9, epsilon=0.2, trajectory=True, stats=True)
             _same(got, o.run(T, METHODS[method], 0.25 / o.K, 0.9, _eps(0.2)))
             _tables(vec, o)
-        _state(vec, o)
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -79,7 +73,7 @@ def test_every_number_of_slots(K, method):
             got = vec.fa_run(T, method, alpha=0.3 / K, discount_factor=0.95, epsilon=0.3, trajectory=True, stats=True)
             _same(got, o.run(T, METHODS[method], 0.3 / K, 0.95, _eps(0.3)))
             _tables(vec, o)
-        _state(vec, o)
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -122,7 +116,7 @@ def test_forwarding_when_s_and_s2_share_slots(K, per_column, method):
             got = vec.fa_run(T, method, alpha=0.2 / K, discount_factor=0.9, epsilon=0.4, trajectory=True, stats=True)
             _same(got, o.run(T, METHODS[method], 0.2 / K, 0.9, _eps(0.4)))
             _tables(vec, o)
-        _state(vec, o)
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -136,7 +130,7 @@ def test_split_launches_with_changed_hyper_parameters(method):
             got = vec.fa_run(257, method, alpha=alpha, discount_factor=gamma, epsilon=eps, trajectory=True, stats=True)
             _same(got, o.run(257, METHODS[method], alpha, gamma, _eps(eps)))
         _tables(vec, o)
-        _state(vec, o)
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -171,7 +165,7 @@ def test_sarsa_carry_is_ended_by_reset_set_weights_another_learner_and_set_featu
         o.set_features(*feats, w0=1.0)
         _same(vec.fa_run(70, 'sarsa', **run), o.run(70, FA.SARSA, 0.05, 0.9, _eps(0.3)), keys)
         _tables(vec, o)
-        _state(vec, o)
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -179,20 +173,16 @@ def test_sarsa_carry_is_ended_by_reset_set_weights_another_learner_and_set_featu
 @pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map and phi), one grid per env (global map and phi)
 def test_multigrid_learners_share_one_feature_table(method, n_grids, N):
-    grids = _random_grids(n_grids, 9, 9, 17)
     phi, F = tile_coding(9, 9, 4, 3)
-    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
-    group = N // n_grids
-    oracles = [FA.FaOracle(_grid(g), 6, group, phi, F, env_id0=k * group) for k, g in enumerate(grids)]
+    vec, side = multigrid_batch(lambda grid, seed, n, env_id0: FA.FaOracle(grid, seed, n, phi, F, env_id0=env_id0), n_grids, N)
     try:
         vec.set_features(phi, F)
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         for T in (150, 90):
             got = vec.fa_run(T, method, alpha=0.05, discount_factor=0.9, epsilon=0.25, trajectory=True, stats=True)
-            parts = [o.run(T, METHODS[method], 0.05, 0.9, _eps(0.25)) for o in oracles]
-            _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-        assert vec.weights().tobytes() == np.concatenate([o.w for o in oracles]).tobytes()
-        assert vec.fa_q_table().tobytes() == np.concatenate([o.q_tables() for o in oracles]).tobytes()
+            _same(got, side.run(lambda o: o.run(T, METHODS[method], 0.05, 0.9, _eps(0.25))))
+        assert vec.weights().tobytes() == side.cat(lambda o: o.w).tobytes()
+        assert vec.fa_q_table().tobytes() == side.cat(lambda o: o.q_tables()).tobytes()
     finally:
         vec.close()
 
@@ -203,10 +193,7 @@ def test_step_counts_across_the_epoch_boundary(method):
     N = 96
     vec, o = _pair(g, N, 12, tile_coding(8, 8, 4, 4))
     try:
-        tc = np.full(N, 2 ** 32 - 100, np.uint64)
-        tc[::3] += 7  # per-env counts: envs cross the boundary at different steps
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N)
         got = vec.fa_run(300, method, alpha=0.05, discount_factor=0.9, epsilon=0.5, trajectory=True, stats=True)
         _same(got, o.run(300, METHODS[method], 0.05, 0.9, _eps(0.5)))
         _tables(vec, o)
@@ -229,7 +216,7 @@ def test_feature_tables_that_do_not_fit_lds_are_read_through_l2(method, feats):
             got = vec.fa_run(T, method, alpha=0.03, discount_factor=0.9, epsilon=0.3, trajectory=True, stats=True)
             _same(got, o.run(T, METHODS[method], 0.03, 0.9, _eps(0.3)))
         _tables(vec, o)
-        _state(vec, o)
+        same_env_state(vec, o)
     finally:
         vec.close()
 

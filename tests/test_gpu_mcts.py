@@ -10,13 +10,11 @@ import griduniverse_amd as gua
 from griduniverse_amd import _lib
 from griduniverse_amd.algorithms.search import tree_search, uct_tables
 from griduniverse_amd.engine import Engine
-from oracle import c_oracle as C
 
 from . import _mcts_oracle as MO
 from . import _td_oracle as TD
-from ._tabular_cases import GRIDS, _eps, _grid, _pair, _random_grids, _same, _spec
-from .test_mcts_host import TREE_BEHAVIOUR, plain_total, tree_behaviour_totals
-from .test_search_host import BEHAVIOUR
+from ._behaviour import SEARCH_BEHAVIOUR, TREE_BEHAVIOUR, plain_total, tree_behaviour_totals
+from ._tabular_cases import GRIDS, _eps, _pair, _same, _spec, counts_near_2_32, device_maze_batch, multigrid_batch, same_env_state
 
 pytestmark = pytest.mark.gpu
 
@@ -34,12 +32,6 @@ def _same_trees(vec, oracles):
     for k, name in (('state', 't_state'), ('parent', 't_parent'), ('child', 't_child'), ('visits', 't_visits'), ('w', 't_w'), ('count', 'count')):
         want = cat(name)
         assert tree[k].dtype == want.dtype and tree[k].shape == want.shape and tree[k].tobytes() == want.tobytes(), k
-
-
-def _same_state(vec, oracles):
-    st = vec.get_state()
-    for k in ('pos', 'done', 'episode', 'tcount'):
-        assert np.array_equal(st[k], np.concatenate([getattr(o.state, k) for o in oracles])), k
 
 
 def _run(vec, o, T, M, H, D, eps_sim, alpha=0.25, gamma=0.9, eps=0.2):
@@ -63,7 +55,7 @@ def test_tables_rows_stats_state_and_trees_equal_the_oracle(grid, M, H, D, eps_s
     try:
         for part in (T - T // 3, T // 3):  # two launches: the second starts from the first one's tables
             _run(vec, o, part, M, H, D, eps_sim)
-        _same_state(vec, [o])
+        same_env_state(vec, o)
         assert o.sim_steps.sum() > 0
     finally:
         vec.close()
@@ -74,7 +66,7 @@ def test_4096_learners_equal_the_oracle():
     vec, o = _pair(g, 4096, 5)
     try:
         _run(vec, o, 12, 8, 4, 8, 13107, alpha=0.3, gamma=0.95, eps=0.3)
-        _same_state(vec, [o])
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -85,7 +77,7 @@ def test_the_largest_shapes():
     try:
         _run(vec, o, 1, 255, 64, 256, 65536, eps=0.0)
         assert (o.root_visits.sum(axis=1) == 255).all() and o.count.max() > 64
-        _same_state(vec, [o])
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -138,42 +130,31 @@ def test_split_launch_equals_one_launch(M, H, D, eps_sim):
         b.close()
 
 
-def _group_run(vec, oracles, launches):
-    assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+def _group_run(vec, side, launches):
+    assert np.array_equal(vec.reset(), side.reset())
     for T, M, H, D, eps_sim in launches:
         got = vec.tree_search_run(T, M, H, D, alpha=0.2, discount_factor=0.9, epsilon=0.25, rollout_epsilon=eps_sim, trajectory=True,
                                   stats=True)
-        parts = [o.tree_search(T, M, H, D, 0.2, 0.9, _eps(0.25), _eps(eps_sim)) for o in oracles]
-        _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-    assert vec.q_table().tobytes() == np.concatenate([o.q for o in oracles]).tobytes()
-    _same_trees(vec, oracles)
-    _same_state(vec, oracles)
+        _same(got, side.run(lambda o: o.tree_search(T, M, H, D, 0.2, 0.9, _eps(0.25), _eps(eps_sim))))
+    assert vec.q_table().tobytes() == side.cat(lambda o: o.q).tobytes()
+    _same_trees(vec, side.oracles)
+    same_env_state(vec, side)
 
 
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
 def test_multigrid_learners_equal_the_oracle(n_grids, N):
-    grids = _random_grids(n_grids, 9, 9, 17)
-    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
-    group = N // n_grids
-    oracles = [MO.MctsOracle(_grid(g), 6, group, env_id0=k * group) for k, g in enumerate(grids)]
+    vec, side = multigrid_batch(MO.MctsOracle, n_grids, N)
     try:
-        _group_run(vec, oracles, ((3, 3, 2, 2, 1.0), (2, 3, 2, 2, 0.2)) if n_grids == 256 else ((12, 8, 4, 4, 1.0), (6, 8, 4, 4, 0.2)))
+        _group_run(vec, side, ((3, 3, 2, 2, 1.0), (2, 3, 2, 2, 0.2)) if n_grids == 256 else ((12, 8, 4, 4, 1.0), (6, 8, 4, 4, 0.2)))
     finally:
         vec.close()
 
 
 @pytest.mark.parametrize('n_grids', [4, 256])
 def test_device_maze_learners_equal_the_oracle(n_grids):
-    N, W, H, maze_seed = 256, 11, 11, 31
-    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
-    group = N // n_grids
-    oracles = []
-    for k in range(n_grids):
-        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
-        oracles.append(MO.MctsOracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]), 2, group,
-                                     env_id0=k * group))
+    vec, side = device_maze_batch(MO.MctsOracle, n_grids)
     try:
-        _group_run(vec, oracles, ((4, 3, 2, 2, 0.1),) if n_grids == 256 else ((12, 8, 5, 3, 0.1),))
+        _group_run(vec, side, ((4, 3, 2, 2, 0.1),) if n_grids == 256 else ((12, 8, 5, 3, 0.1),))
     finally:
         vec.close()
 
@@ -185,13 +166,10 @@ def test_step_counts_across_the_epoch_boundaries(M, H, D, t0):
     N = 96
     vec, o = _pair(g, N, 12)
     try:
-        tc = np.full(N, t0, np.uint64)
-        tc[::3] += 7  # per-env counts: envs cross at different steps
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N, t0)
         _run(vec, o, 60, M, H, D, 32768, alpha=0.2, gamma=0.9, eps=0.3)
         assert np.array_equal(vec.get_state()['tcount'], tc + np.uint64(60))
-        _same_state(vec, [o])
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -333,7 +311,7 @@ def test_edges_and_errors():
 
 def test_tree_search_finishes_more_episodes_than_plain_q_learning_on_the_device():
     """The totals of tests/test_mcts_host.py, which the device equals by construction: asserted here once, on open8x8."""
-    b = BEHAVIOUR
+    b = SEARCH_BEHAVIOUR
     M, H, D = TREE_BEHAVIOUR['open8x8']
     vec = gua.VecGridUniverse(b['N'], template=_spec(GRIDS['open8x8']()), seed=b['seed'])
     try:

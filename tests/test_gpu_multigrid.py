@@ -6,21 +6,9 @@ import griduniverse_amd as gua
 from griduniverse_amd.engine import Engine
 from griduniverse_amd.grid import GridSpec
 from oracle import c_oracle as C
-from tests.test_maze_structure import check_maze_structure
+from tests._mazes import check_maze_structure, oracle_grid, random_specs
 
 pytestmark = pytest.mark.gpu
-
-
-def oracle_grid(spec):
-    return C.Grid(spec.W, spec.H, spec.wall, spec.lava, spec.goal, spec.reward, spec.starts)
-
-
-def random_specs(rs, n, W, H):
-    S, specs = W * H, []
-    for _ in range(n):
-        pick = lambda k: [int(x) for x in rs.choice(S, size=int(k), replace=False)]  # noqa: E731
-        specs.append(GridSpec(W, H, pick(rs.randint(1, 4)), pick(rs.randint(1, 3)), pick(rs.randint(0, 5)), pick(rs.randint(0, S // 4))))
-    return specs
 
 
 @pytest.mark.parametrize('group', [128, 50, 1])

@@ -8,11 +8,11 @@ import pytest
 import griduniverse_amd as gua
 from griduniverse_amd import _lib
 from griduniverse_amd.engine import Engine
-from oracle import c_oracle as C
 
 from . import _nstep_oracle as NO
 from . import _td_oracle as O
-from ._tabular_cases import GRIDS, _eps, _grid, _pair, _random_grids, _same, _spec
+from ._tabular_cases import (GRIDS, _eps, _pair, _same, _spec, counts_near_2_32, device_maze_batch, multigrid_batch, open_grid,
+                             same_env_state)
 
 pytestmark = pytest.mark.gpu
 
@@ -47,9 +47,7 @@ def test_tables_rows_stats_and_windows_equal_the_oracle(grid, method, n, N):
             _launch(vec, o, T, method, n)
         if n > 1:
             assert o.count.any()  # (the boundary did cut windows)
-        st = vec.get_state()
-        assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'], o.state.done)
-        assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -137,17 +135,13 @@ def test_the_window_is_dropped_by_any_other_call(kind):
         vec.close()
 
 
-def _open(W, H):
-    return dict(W=W, H=H, starts=[0], goals=[W * H - 1], lava=[], walls=[])
-
-
 @pytest.mark.parametrize('eps', [0.0, 0.5])
 @pytest.mark.parametrize('n', [4, 16])
 @pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
 @pytest.mark.parametrize('W,H', [(2, 2), (4, 4)])
 def test_forwarding_on_small_open_grids(W, H, method, n, eps):
     """On tiny grids the updated pair often lies in the row of s' that the lane holds in registers."""
-    g = _open(W, H)
+    g = open_grid(W, H)
     vec, o = _pair(g, 256, 7, 0.5)
     try:
         for T in (123, 77):
@@ -159,40 +153,28 @@ def test_forwarding_on_small_open_grids(W, H, method, n, eps):
 @pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
 def test_multigrid_learners_equal_the_oracle(method, n_grids, N):
-    grids = _random_grids(n_grids, 9, 9, 17)
-    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
-    group = N // n_grids
-    oracles = [NO.NstepOracle(_grid(g), 6, group, env_id0=k * group) for k, g in enumerate(grids)]
+    vec, side = multigrid_batch(NO.NstepOracle, n_grids, N)
     try:
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         for T in (150, 91):
             got = vec.nstep_run(T, 6, method, alpha=0.2, discount_factor=0.9, epsilon=0.25, trajectory=True, stats=True)
-            parts = [o.nstep(T, METHODS[method], 6, 0.2, 0.9, _eps(0.25)) for o in oracles]
-            _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-        assert vec.q_table().tobytes() == np.concatenate([o.q for o in oracles]).tobytes()
+            _same(got, side.run(lambda o: o.nstep(T, METHODS[method], 6, 0.2, 0.9, _eps(0.25))))
+        assert vec.q_table().tobytes() == side.cat(lambda o: o.q).tobytes()
         w = vec.nstep_window()
         for k in ('count', 'sa', 'reward'):
-            assert w[k].tobytes() == np.concatenate([o.window()[k] for o in oracles]).tobytes(), k
+            assert w[k].tobytes() == side.cat(lambda o: o.window()[k]).tobytes(), k
     finally:
         vec.close()
 
 
 @pytest.mark.parametrize('n_grids', [4, 256])
 def test_device_maze_learners_equal_the_oracle(n_grids):
-    N, W, H, maze_seed = 256, 11, 11, 31
-    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
-    group = N // n_grids
-    oracles = []
-    for k in range(n_grids):
-        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
-        oracles.append(NO.NstepOracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]), 2,
-                                      group, env_id0=k * group))
+    vec, side = device_maze_batch(NO.NstepOracle, n_grids)
     try:
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         got = vec.nstep_run(200, 8, 'sarsa', alpha=0.3, discount_factor=0.9, epsilon=0.1, trajectory=True, stats=True)
-        parts = [o.nstep(200, O.SARSA, 8, 0.3, 0.9, _eps(0.1)) for o in oracles]
-        _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-        assert vec.q_table().tobytes() == np.concatenate([o.q for o in oracles]).tobytes()
+        _same(got, side.run(lambda o: o.nstep(200, O.SARSA, 8, 0.3, 0.9, _eps(0.1))))
+        assert vec.q_table().tobytes() == side.cat(lambda o: o.q).tobytes()
     finally:
         vec.close()
 
@@ -203,10 +185,7 @@ def test_step_counts_across_the_epoch_boundary(method):
     N = 96
     vec, o = _pair(g, N, 12)
     try:
-        tc = np.full(N, 2 ** 32 - 100, np.uint64)
-        tc[::3] += 7  # per-env counts: envs cross the boundary at different steps
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N)
         for T in (130, 170):
             _launch(vec, o, T, method, 5, alpha=0.2, eps=0.5)
         assert np.array_equal(vec.get_state()['tcount'], tc + np.uint64(300))

@@ -15,7 +15,7 @@ from . import _is_oracle as IO
 from . import _numeric_edges as NE
 from . import _reinforce_oracle as RO
 from . import _td_oracle as TD
-from ._tabular_cases import GRIDS, _grid, _same, _spec
+from ._tabular_cases import GRIDS, _grid, _same, _spec, same_env_state
 
 pytestmark = pytest.mark.gpu
 
@@ -135,12 +135,6 @@ def test_probe_changes_nothing_and_checks_its_arguments():
 
 # ---- through the real kernels, with crafted tables
 
-def _same_state(vec, o):
-    st = vec.get_state()
-    assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'], o.state.done)
-    assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
-
-
 IS_N = 8191  # one env per vector; every exponent of NE.IS_EXPONENTS occurs at least six times
 
 
@@ -166,7 +160,7 @@ def test_is_run_exposes_all_53_bits_of_the_reciprocal_at_every_exponent():
         q, cw = vec.q_table(), vec.importance_weights()
         _bytes(q, o.q, 'Q')
         _bytes(cw, o.c, 'C')
-        _same_state(vec, o)
+        same_env_state(vec, o)
         # without the restatement: one entry of the start row moved, to -1 / x exactly; its weight is x
         moved = q[:, START, :] != 0.0
         assert (moved.sum(axis=1) == 1).all() and not np.delete(q, START, axis=1).any()
@@ -210,7 +204,7 @@ def _check_softmax_learner(vec, o, idx, first, covered, want):
     h, v = vec.preferences(), vec.state_values()
     _bytes(h, o.h, 'H')
     _bytes(v, o.v, 'V')
-    _same_state(vec, o)
+    same_env_state(vec, o)
     assert np.isfinite(h).all()
     _bytes(h[idx, START, first][covered], want[covered], 'H[start][first maximum] against the exact rational')
 
@@ -261,7 +255,7 @@ def test_is_run_walks_down_to_the_lower_weight_bound():
         q, c = vec.q_table(), vec.importance_weights()
         _bytes(q, o.q, 'Q')
         _bytes(c, o.c, 'C')
-        _same_state(vec, o)
+        same_env_state(vec, o)
         assert not vec.off_policy_episode_buffer()['count'].any()
         # the closed form, without the restatement
         want_c = np.zeros((200, 4))
@@ -292,7 +286,7 @@ def test_is_run_ends_passes_at_and_above_the_weight_cap():
         print('passes ended by W == w_cap: %d, by W > w_cap: %d, of %d' % (o.cap_eq, o.cap_gt, o.passes))
         _bytes(vec.q_table(), o.q, 'Q')
         _bytes(vec.importance_weights(), o.c, 'C')
-        _same_state(vec, o)
+        same_env_state(vec, o)
         assert (o.c[o.c > 0] < 16.0 * 192).all() and np.isfinite(o.q).all()  # (no single addition to C reached the cap)
     finally:
         vec.close()

@@ -9,19 +9,15 @@ from griduniverse_amd import _lib
 from griduniverse_amd.algorithms import utils
 from griduniverse_amd.algorithms.policy_gradient import reinforce
 from griduniverse_amd.engine import Engine
-from oracle import c_oracle as C
 
 from . import _lambda_oracle as LO
 from . import _nstep_oracle as NO
 from . import _reinforce_oracle as RO
 from . import _td_oracle as O
-from ._tabular_cases import GRIDS, _eps, _grid, _random_grids, _same, _spec
+from ._tabular_cases import (GRIDS, _eps, _grid, _same, _spec, counts_near_2_32, device_maze_batch, multigrid_batch, open_grid,
+                             same_env_state)
 
 pytestmark = pytest.mark.gpu
-
-
-def _open(W, H):
-    return dict(W=W, H=H, starts=[0], goals=[W * H - 1], lava=[], walls=[])
 
 
 def _pair(g, N, seed, h0=0.0, v0=0.0):
@@ -43,12 +39,6 @@ def _same_buffer(vec, oracles):
     assert buf['count'].tobytes() == np.concatenate([o.buf_cnt for o in oracles]).tobytes()
     assert buf['sa'].tobytes() == np.concatenate([o.buf_sa for o in oracles]).tobytes()
     assert buf['reward'].tobytes() == np.concatenate([o.buf_r for o in oracles]).tobytes()
-
-
-def _same_state(vec, o):
-    st = vec.get_state()
-    assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'], o.state.done)
-    assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
 
 
 def _launch(vec, o, T, L, aa=0.05, ab=0.3, gamma=0.9):
@@ -80,7 +70,7 @@ def test_tables_rows_stats_state_and_buffer_equal_the_oracle(grid, N, L):
     try:
         for launch, T in enumerate((_FIRST_T[grid, N][(1, 7, 64).index(L)], 151 if N < 4096 else 37)):
             _launch(vec, o, T, L)
-            _same_state(vec, o)
+            same_env_state(vec, o)
             if launch == 0:
                 assert (o.state.done != 0).any() and ((o.buf_cnt > 0).any() or L == 1)
         assert o.h.any() and o.v.any()
@@ -196,7 +186,7 @@ def test_another_call_in_between_drops_the_buffer(between):
         else:
             _same_buffer(vec, [o])
         _launch(vec, o, 250, 64)
-        _same_state(vec, o)
+        same_env_state(vec, o)
         assert vec.q_table().tobytes() == o.q.tobytes()
     finally:
         vec.close()
@@ -231,50 +221,39 @@ def test_reinforce_run_drops_the_sarsa_carry_and_both_windows():
 def test_repeated_states_and_rewritten_rows_on_small_open_grids(W, H, L):
     """Tiny grids: many wall bumps, states repeated inside a segment (the pass compounds), and with L = 3 truncations whose pass
     rewrites the row of the state the lane stands in (the next step must act on the rewritten row)."""
-    vec, o = _pair(_open(W, H), 256, 7, 0.5, 1.0)
+    vec, o = _pair(open_grid(W, H), 256, 7, 0.5, 1.0)
     try:
         for T in (123, 77):
             _launch(vec, o, T, L, aa=0.2, ab=0.5, gamma=0.8)
-        _same_state(vec, o)
+        same_env_state(vec, o)
     finally:
         vec.close()
 
 
-def _group_launches(vec, oracles, runs):
-    assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+def _group_launches(vec, side, runs):
+    assert np.array_equal(vec.reset(), side.reset())
     for T, L in runs:
         got = vec.reinforce_run(T, L, 0.05, 0.25, 0.9, trajectory=True, stats=True)
-        parts = [o.reinforce(T, L, 0.05, 0.25, 0.9) for o in oracles]
-        _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-        _same_buffer(vec, oracles)
-    assert vec.preferences().tobytes() == np.concatenate([o.h for o in oracles]).tobytes()
-    assert vec.state_values().tobytes() == np.concatenate([o.v for o in oracles]).tobytes()
+        _same(got, side.run(lambda o: o.reinforce(T, L, 0.05, 0.25, 0.9)))
+        _same_buffer(vec, side.oracles)
+    assert vec.preferences().tobytes() == side.cat(lambda o: o.h).tobytes()
+    assert vec.state_values().tobytes() == side.cat(lambda o: o.v).tobytes()
 
 
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
 def test_multigrid_learners_equal_the_oracle(n_grids, N):
-    grids = _random_grids(n_grids, 9, 9, 17)
-    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
-    group = N // n_grids
-    oracles = [RO.ReinforceOracle(_grid(g), 6, group, env_id0=k * group) for k, g in enumerate(grids)]
+    vec, side = multigrid_batch(RO.ReinforceOracle, n_grids, N)
     try:
-        _group_launches(vec, oracles, [(150, 24), (91, 24)])
+        _group_launches(vec, side, [(150, 24), (91, 24)])
     finally:
         vec.close()
 
 
 @pytest.mark.parametrize('n_grids', [4, 256])
 def test_device_maze_learners_equal_the_oracle(n_grids):
-    N, W, H, maze_seed = 256, 11, 11, 31
-    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
-    group = N // n_grids
-    oracles = []
-    for k in range(n_grids):
-        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
-        oracles.append(RO.ReinforceOracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]),
-                                          2, group, env_id0=k * group))
+    vec, side = device_maze_batch(RO.ReinforceOracle, n_grids)
     try:
-        _group_launches(vec, oracles, [(120, 32), (80, 32)])
+        _group_launches(vec, side, [(120, 32), (80, 32)])
     finally:
         vec.close()
 
@@ -284,10 +263,7 @@ def test_step_counts_across_the_epoch_boundary():
     N = 96
     vec, o = _pair(g, N, 12)
     try:
-        tc = np.full(N, 2 ** 32 - 100, np.uint64)
-        tc[::3] += 7  # per-env counts: envs cross the boundary at different steps
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N)
         for T in (130, 170):
             _launch(vec, o, T, 24)
         assert np.array_equal(vec.get_state()['tcount'], tc + np.uint64(300))
@@ -298,7 +274,7 @@ def test_step_counts_across_the_epoch_boundary():
 def test_the_longest_segment():
     """L = GU_REINFORCE_MAX on an open 32 x 32 grid (a random walk from one corner does not find the other in 1024 steps):
     segments of 1024 steps, walked back in one pass."""
-    vec, o = _pair(_open(32, 32), 128, 5)
+    vec, o = _pair(open_grid(32, 32), 128, 5)
     try:
         for T in (1100, 1000):
             _launch(vec, o, T, _lib.REINFORCE_MAX, aa=0.001, ab=0.1, gamma=0.99)
@@ -338,7 +314,7 @@ def test_errors():
         _same_tables(vec, o)
         _same_buffer(vec, [o])
         _launch(vec, o, 20, 16)  # (the rejected calls changed nothing either: the buffer is still carried)
-        _same_state(vec, o)
+        same_env_state(vec, o)
         part = vec.episode_buffer(10, 3)
         assert part['count'].tobytes() == o.buf_cnt[10:13].tobytes() and part['sa'].tobytes() == o.buf_sa[10:13].tobytes()
     finally:

@@ -10,12 +10,11 @@ import griduniverse_amd as gua
 from griduniverse_amd import _lib
 from griduniverse_amd.algorithms.search import rollout_search
 from griduniverse_amd.engine import Engine
-from oracle import c_oracle as C
 
 from . import _search_oracle as SO
 from . import _td_oracle as TD
-from ._tabular_cases import GRIDS, _eps, _grid, _pair, _random_grids, _same, _spec
-from .test_search_host import BEHAVIOUR, behaviour_totals
+from ._behaviour import SEARCH_BEHAVIOUR, search_behaviour_totals
+from ._tabular_cases import GRIDS, _eps, _pair, _same, _spec, counts_near_2_32, device_maze_batch, multigrid_batch, same_env_state
 
 pytestmark = pytest.mark.gpu
 
@@ -26,12 +25,6 @@ def _same_search(vec, oracles):
     got = vec.search_scores()
     assert got['score'].tobytes() == np.concatenate([o.score for o in oracles]).tobytes()
     assert got['sim_steps'].dtype == np.int64 and np.array_equal(got['sim_steps'], np.concatenate([o.sim_steps for o in oracles]))
-
-
-def _same_state(vec, oracles):
-    st = vec.get_state()
-    for k in ('pos', 'done', 'episode', 'tcount'):
-        assert np.array_equal(st[k], np.concatenate([getattr(o.state, k) for o in oracles])), k
 
 
 def _run(vec, o, T, M, D, eps_sim, alpha=0.25, gamma=0.9, eps=0.2):
@@ -54,7 +47,7 @@ def test_tables_rows_stats_state_and_scores_equal_the_oracle(grid, M, D, eps_sim
     try:
         for part in (T - T // 3, T // 3):  # two launches: the second starts from the first one's tables
             _run(vec, o, part, M, D, eps_sim)
-        _same_state(vec, [o])
+        same_env_state(vec, o)
         if D > 0:
             assert o.sim_steps.sum() > 0
     finally:
@@ -67,7 +60,7 @@ def test_4096_learners_equal_the_oracle():
     try:
         _run(vec, o, 30, 2, 8, 13107, alpha=0.3, gamma=0.95, eps=0.3)
         _run(vec, o, 10, 2, 8, 65536, alpha=0.3, gamma=0.95, eps=0.3)
-        _same_state(vec, [o])
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -117,41 +110,30 @@ def test_split_launch_equals_one_launch(M, D, eps_sim):
         b.close()
 
 
-def _group_run(vec, oracles, launches):
-    assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+def _group_run(vec, side, launches):
+    assert np.array_equal(vec.reset(), side.reset())
     for T, M, D, eps_sim in launches:
         got = vec.search_run(T, M, D, alpha=0.2, discount_factor=0.9, epsilon=0.25, rollout_epsilon=eps_sim, trajectory=True, stats=True)
-        parts = [o.search(T, M, D, 0.2, 0.9, _eps(0.25), _eps(eps_sim)) for o in oracles]
-        _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-    assert vec.q_table().tobytes() == np.concatenate([o.q for o in oracles]).tobytes()
-    _same_search(vec, oracles)
-    _same_state(vec, oracles)
+        _same(got, side.run(lambda o: o.search(T, M, D, 0.2, 0.9, _eps(0.25), _eps(eps_sim))))
+    assert vec.q_table().tobytes() == side.cat(lambda o: o.q).tobytes()
+    _same_search(vec, side.oracles)
+    same_env_state(vec, side)
 
 
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
 def test_multigrid_learners_equal_the_oracle(n_grids, N):
-    grids = _random_grids(n_grids, 9, 9, 17)
-    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
-    group = N // n_grids
-    oracles = [SO.SearchOracle(_grid(g), 6, group, env_id0=k * group) for k, g in enumerate(grids)]
+    vec, side = multigrid_batch(SO.SearchOracle, n_grids, N)
     try:
-        _group_run(vec, oracles, ((16, 2, 4, 1.0), (8, 2, 4, 0.2)))
+        _group_run(vec, side, ((16, 2, 4, 1.0), (8, 2, 4, 0.2)))
     finally:
         vec.close()
 
 
 @pytest.mark.parametrize('n_grids', [4, 256])
 def test_device_maze_learners_equal_the_oracle(n_grids):
-    N, W, H, maze_seed = 256, 11, 11, 31
-    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
-    group = N // n_grids
-    oracles = []
-    for k in range(n_grids):
-        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
-        oracles.append(SO.SearchOracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]), 2, group,
-                                       env_id0=k * group))
+    vec, side = device_maze_batch(SO.SearchOracle, n_grids)
     try:
-        _group_run(vec, oracles, ((20, 2, 5, 0.1),))
+        _group_run(vec, side, ((20, 2, 5, 0.1),))
     finally:
         vec.close()
 
@@ -163,13 +145,10 @@ def test_step_counts_across_the_epoch_boundaries(M, D, t0):
     N = 96
     vec, o = _pair(g, N, 12)
     try:
-        tc = np.full(N, t0, np.uint64)
-        tc[::3] += 7  # per-env counts: envs cross at different steps
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N, t0)
         _run(vec, o, 60, M, D, 32768, alpha=0.2, gamma=0.9, eps=0.3)
         assert np.array_equal(vec.get_state()['tcount'], tc + np.uint64(60))
-        _same_state(vec, [o])
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -263,7 +242,7 @@ def test_edges_and_errors():
 
 def test_search_finishes_more_episodes_than_plain_q_learning_on_the_device():
     """The totals of tests/test_search_host.py, which the device equals by construction: asserted here once on open8x8."""
-    b = BEHAVIOUR
+    b = SEARCH_BEHAVIOUR
     g = GRIDS['open8x8']()
     kw = dict(alpha=b['alpha'], discount_factor=b['gamma'], epsilon=b['eps_q16'] / 65536.0, stats=True)
     vec = gua.VecGridUniverse(b['N'], template=_spec(g), seed=b['seed'])
@@ -280,7 +259,7 @@ def test_search_finishes_more_episodes_than_plain_q_learning_on_the_device():
         vec.close()
     print('open8x8 on the device: search {} finished episodes (least per learner {}), plain Q-learning {}'.format(
         int(got.sum()), int(got.min()), int(plain.sum())))
-    assert (int(got.sum()), int(plain.sum()), int(got.min())) == behaviour_totals('open8x8')
+    assert (int(got.sum()), int(plain.sum()), int(got.min())) == search_behaviour_totals('open8x8')
     assert got.sum() >= 3 * plain.sum() and got.min() >= 2
 
 

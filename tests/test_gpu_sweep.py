@@ -17,7 +17,8 @@ from oracle import c_oracle as C
 
 from . import _golden as G
 from . import _sweep_oracle as SW
-from ._tabular_cases import GRIDS, _eps, _grid, _pair, _random_grids, _same, _spec
+from ._tabular_cases import (GRIDS, SideBySide, _eps, _grid, _pair, _random_grids, _same, _spec, counts_near_2_32, device_maze_batch,
+                             multigrid_batch, open_grid, same_env_state)
 
 pytestmark = pytest.mark.gpu
 
@@ -53,17 +54,14 @@ def _same_all(vec, oracles, heap=True):
     assert q['key'].dtype == np.uint64 and q['key'].tobytes() == key.tobytes()
     assert q['size'].dtype == np.int32 and q['size'].tobytes() == np.concatenate([o.size for o in oracles]).tobytes()
     assert q['priority'].tobytes() == SW.priorities(key).tobytes()
-    st = vec.get_state()
-    for k in ('pos', 'done', 'episode', 'tcount'):
-        assert np.array_equal(st[k], np.concatenate([getattr(o.state, k) for o in oracles])), k
+    same_env_state(vec, oracles)
     if heap:
         _same_heap(vec, oracles)
 
 
 def _run(vec, oracles, T, P, theta, alpha, gamma, eps, heap=True):
     got = vec.sweep_run(T, P, theta=theta, alpha=alpha, discount_factor=gamma, epsilon=eps, trajectory=True, stats=True)
-    parts = [o.sweep(T, P, theta, alpha, gamma, _eps(eps)) for o in oracles]
-    _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
+    _same(got, SideBySide(oracles).run(lambda o: o.sweep(T, P, theta, alpha, gamma, _eps(eps))))
     _same_all(vec, oracles, heap)
 
 
@@ -83,8 +81,7 @@ def test_everything_equals_the_oracle_and_the_heap_is_a_heap(grid, P, theta):
 
 @pytest.mark.parametrize('W,H', [(2, 2), (4, 4)])
 def test_planning_that_rewrites_the_current_row_and_drains_the_queue(W, H):
-    g = dict(W=W, H=H, starts=[0], goals=[W * H - 1], lava=[], walls=[])
-    vec, o = _pair(g, 128, 13, q0=0.75)
+    vec, o = _pair(open_grid(W, H), 128, 13, q0=0.75)
     try:
         for eps in (0.0, 0.2):
             _run(vec, [o], 150, 50, 1e-4, 0.5, 0.9, eps)
@@ -115,31 +112,21 @@ def test_an_oversized_grid_is_refused():
 
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
 def test_multigrid_learners_equal_the_oracle(n_grids, N):
-    grids = _random_grids(n_grids, 9, 9, 17)
-    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
-    group = N // n_grids
-    oracles = [SW.SweepOracle(_grid(g), 6, group, env_id0=k * group) for k, g in enumerate(grids)]
+    vec, side = multigrid_batch(SW.SweepOracle, n_grids, N)
     try:
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         for T, P in (((100, 5), (60, 1)) if n_grids == 4 else ((40, 5), (20, 1))):  # (256 one-env oracles: the CPU side is the slow one)
-            _run(vec, oracles, T, P, 1e-4, 0.2, 0.9, 0.25)
+            _run(vec, side.oracles, T, P, 1e-4, 0.2, 0.9, 0.25)
     finally:
         vec.close()
 
 
 @pytest.mark.parametrize('n_grids', [4, 256])
 def test_device_maze_learners_equal_the_oracle(n_grids):
-    N, W, H, maze_seed = 256, 11, 11, 31
-    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
-    group = N // n_grids
-    oracles = []
-    for k in range(n_grids):
-        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
-        oracles.append(SW.SweepOracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]), 2, group,
-                                      env_id0=k * group))
+    vec, side = device_maze_batch(SW.SweepOracle, n_grids)
     try:
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
-        _run(vec, oracles, 120 if n_grids == 4 else 50, 5, 1e-4, 0.3, 0.9, 0.1)  # (256 one-env oracles: the CPU side is the slow one)
+        assert np.array_equal(vec.reset(), side.reset())
+        _run(vec, side.oracles, 120 if n_grids == 4 else 50, 5, 1e-4, 0.3, 0.9, 0.1)  # (256 one-env oracles: the CPU side is the slow one)
     finally:
         vec.close()
 
@@ -183,10 +170,7 @@ def test_step_counts_across_the_epoch_boundary():
     N, t0 = 96, 2 ** 32 - 60
     vec, o = _pair(GRIDS['open8x8'](), N, 12)
     try:
-        tc = np.full(N, t0, np.uint64)
-        tc[::3] += 7
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N, t0)
         _run(vec, [o], 100, 3, 1e-4, 0.2, 0.9, 0.5)
         assert np.array_equal(vec.get_state()['tcount'], tc + np.uint64(100))
     finally:

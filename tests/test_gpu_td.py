@@ -14,7 +14,7 @@ from oracle import c_oracle as C
 
 from . import _td_oracle as O
 from . import _golden as G
-from ._tabular_cases import GRIDS, _eps, _grid, _pair, _random_grids, _same, _spec
+from ._tabular_cases import GRIDS, _eps, _grid, _pair, _same, _spec, counts_near_2_32, device_maze_batch, multigrid_batch, same_env_state
 
 pytestmark = pytest.mark.gpu
 
@@ -37,9 +37,7 @@ def test_tables_rows_and_stats_equal_the_oracle(grid, method, N):
             want = o.run(T, METHODS[method], 0.25, 0.9, _eps(0.2))
             _same(got, want)
             assert vec.q_table().tobytes() == o.q.tobytes()
-        st = vec.get_state()
-        assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'], o.state.done)
-        assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
+        same_env_state(vec, o)
     finally:
         vec.close()
 
@@ -78,39 +76,25 @@ def test_sarsa_interrupted_by_reset_starts_with_a_fresh_action():
 @pytest.mark.parametrize('method', ['q_learning', 'sarsa'])
 @pytest.mark.parametrize('n_grids,N', [(4, 256), (256, 256)])  # groups of 64 (LDS-staged map), one grid per env (global map)
 def test_multigrid_learners_equal_the_oracle(method, n_grids, N):
-    grids = _random_grids(n_grids, 9, 9, 17)
-    vec = gua.VecGridUniverse(N, templates=[_spec(g) for g in grids], seed=6)
-    group = N // n_grids
-    oracles = [O.TdOracle(_grid(g), 6, group, env_id0=k * group) for k, g in enumerate(grids)]
+    vec, side = multigrid_batch(O.TdOracle, n_grids, N)
     try:
-        first = vec.reset()
-        assert np.array_equal(first, np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         for T in (150, 90):
             got = vec.td_run(T, method, alpha=0.2, discount_factor=0.9, epsilon=0.25, trajectory=True, stats=True)
-            parts = [o.run(T, METHODS[method], 0.2, 0.9, _eps(0.25)) for o in oracles]
-            want = {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]}
-            _same(got, want)
-        assert vec.q_table().tobytes() == np.concatenate([o.q for o in oracles]).tobytes()
+            _same(got, side.run(lambda o: o.run(T, METHODS[method], 0.2, 0.9, _eps(0.25))))
+        assert vec.q_table().tobytes() == side.cat(lambda o: o.q).tobytes()
     finally:
         vec.close()
 
 
 @pytest.mark.parametrize('n_grids', [4, 256])
 def test_device_maze_learners_equal_the_oracle(n_grids):
-    N, W, H, maze_seed = 256, 11, 11, 31
-    vec = gua.VecGridUniverse(N, grid_shape=(W, H), device_mazes=n_grids, maze_seed=maze_seed, seed=2)
-    group = N // n_grids
-    oracles = []
-    for k in range(n_grids):
-        wall, start, goal = C.generate_maze(maze_seed, k, W, H)
-        oracles.append(O.TdOracle(C.Grid.from_lists(W, H, walls=np.flatnonzero(wall).tolist(), goals=[goal], starts=[start]), 2, group,
-                                  env_id0=k * group))
+    vec, side = device_maze_batch(O.TdOracle, n_grids)
     try:
-        assert np.array_equal(vec.reset(), np.concatenate([o.reset() for o in oracles]))
+        assert np.array_equal(vec.reset(), side.reset())
         got = vec.td_run(200, 'q_learning', alpha=0.3, discount_factor=0.9, epsilon=0.1, trajectory=True, stats=True)
-        parts = [o.run(200, O.Q_LEARNING, 0.3, 0.9, _eps(0.1)) for o in oracles]
-        _same(got, {k: np.concatenate([p[k] for p in parts], axis=-1) for k in parts[0]})
-        assert vec.q_table().tobytes() == np.concatenate([o.q for o in oracles]).tobytes()
+        _same(got, side.run(lambda o: o.run(200, O.Q_LEARNING, 0.3, 0.9, _eps(0.1))))
+        assert vec.q_table().tobytes() == side.cat(lambda o: o.q).tobytes()
     finally:
         vec.close()
 
@@ -121,10 +105,7 @@ def test_step_counts_across_the_epoch_boundary(method):
     N = 96
     vec, o = _pair(g, N, 12)
     try:
-        tc = np.full(N, 2 ** 32 - 100, np.uint64)
-        tc[::3] += 7  # per-env counts: envs cross the boundary at different steps
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N)
         got = vec.td_run(300, method, alpha=0.2, discount_factor=0.9, epsilon=0.5, trajectory=True, stats=True)
         _same(got, o.run(300, METHODS[method], 0.2, 0.9, _eps(0.5)))
         assert vec.q_table().tobytes() == o.q.tobytes()

@@ -26,7 +26,7 @@ import pytest
 from griduniverse_amd import Engine, GridSpec
 from oracle import c_oracle as C
 from tests import _golden as G
-from tests.test_gpu_multigrid import oracle_grid, random_specs
+from tests._mazes import oracle_grid, random_specs
 
 pytestmark = pytest.mark.gpu
 

@@ -16,7 +16,7 @@ from oracle import c_oracle as C
 from . import _golden as G
 from . import _td_oracle as TD
 from . import _wind_oracle as O
-from ._tabular_cases import GRIDS, _eps, _grid, _same, _spec
+from ._tabular_cases import GRIDS, _eps, _grid, _same, _spec, counts_near_2_32
 
 pytestmark = pytest.mark.gpu
 
@@ -220,10 +220,7 @@ def test_the_gust_epoch_changes_inside_a_launch(method):
     N = 96
     vec, o = _pair('book', N, 12, O.GUST_THIRDS, q0=0.0)
     try:
-        tc = np.full(N, 2 ** 32 - 20, np.uint64)
-        tc[::3] += 7  # envs cross the boundary at different steps
-        vec.set_state(tcount=tc)
-        o.set_state(tcount=tc)
+        tc = counts_near_2_32(vec, o, N, 2 ** 32 - 20)
         got = vec.td_run(60, method, alpha=0.2, discount_factor=0.9, epsilon=0.5, trajectory=True, stats=True)
         _same(got, o.td_run(60, METHODS[method], 0.2, 0.9, _eps(0.5)))
         assert vec.q_table().tobytes() == o.q.tobytes()

@@ -15,16 +15,11 @@ from oracle import c_oracle as C
 from . import _golden as G
 from . import _lambda_oracle as LO
 from . import _td_oracle as O
+from . import _walks
+from ._lambda_oracle import signed_zero_table
 from ._tabular_cases import GRIDS, _grid
-from .test_dyna_host import _greedy_walk, _shortest_from_start
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def signed_zero_table(n, S, seed=1):
-    """A table of -0.0 and 2.0 entries.  Learned with alpha = -0.0 it keeps -0.0 in pairs of the window while later steps have
-    g = +0.0, so an update by g * P_j with P_j = 0 would turn them into +0.0: only the P_j != 0 rule keeps lambda = 0 exact there."""
-    return np.where(np.random.default_rng(seed).random((n, S, 4)) < 0.5, -0.0, 2.0)
 
 
 @pytest.mark.parametrize('signed_zeros', [False, True])
@@ -212,14 +207,14 @@ def _steps_to_shortest(grid, best, lam, K, chunk=100, limit=30000):
     while done < limit:
         o.lam(chunk, LO.SARSA, K, lam, 0.1, 0.9, int(0.1 * 65536))
         done += chunk
-        if all(_greedy_walk(grid, o.q[e]) == best for e in range(o.n)):
+        if all(_walks._greedy_walk(grid, o.q[e]) == best for e in range(o.n)):
             return done
     return None
 
 
 def test_sarsa_lambda_finds_the_shortest_path_in_fewer_real_steps():
     grid = C.Grid.from_env(GridUniverseEnv(custom_world_fp=G.level_path('maze_11x11.txt')))
-    best = _shortest_from_start(grid)
+    best = _walks._shortest_from_start(grid)
     # measured with this restatement (which the device matches byte for byte): 6800 real steps for lambda = 0.9, 21 100 for
     # lambda = 0, which is one-step SARSA
     assert _steps_to_shortest(grid, best, 0.9, 32) == 6800

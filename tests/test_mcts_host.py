@@ -1,7 +1,6 @@
 """Monte-Carlo tree search (UCT at decision time), the parts that need no GPU: the CPU restatement against the tabular one, the
 invariants of the trees it builds, what the tree buys over plain Q-learning and over the flat rollout search, the argument checks of
 the Python layer, the UCB1 tables and the library's new symbols."""
-import functools
 import subprocess
 
 import numpy as np
@@ -14,32 +13,7 @@ from griduniverse_amd.algorithms.search import tree_search, uct_tables
 from . import _mcts_oracle as MO
 from . import _td_oracle as O
 from ._tabular_cases import GRIDS, _grid
-from .test_search_host import BEHAVIOUR, behaviour_totals
-
-# (M, H, D) of the behaviour check per grid, at test_search_host.py's BEHAVIOUR settings, uniform rollouts, uct_tables(3.0)
-TREE_BEHAVIOUR = {'open8x8': (16, 16, 16), 'default4x4': (64, 8, 4)}
-
-
-@functools.lru_cache(maxsize=None)
-def tree_behaviour_totals(name):
-    """(finished episodes of the tree-search learners, the least of one learner) on grid `name`; computed once per process
-    (test_gpu_mcts.py asserts the same totals on the device)."""
-    b = BEHAVIOUR
-    M, H, D = TREE_BEHAVIOUR[name]
-    o = MO.MctsOracle(_grid(GRIDS[name]()), b['seed'], b['N'])
-    o.tables = MO.uct_tables(3.0)
-    o.reset()
-    got = o.tree_search(b['T'], M, H, D, b['alpha'], b['gamma'], b['eps_q16'], 65536)['episodes']
-    return int(got.sum()), int(got.min())
-
-
-@functools.lru_cache(maxsize=None)
-def plain_total(name):
-    """Finished episodes of plain Q-learning at the same settings (the second entry of test_search_host.behaviour_totals)."""
-    b = BEHAVIOUR
-    plain = O.TdOracle(_grid(GRIDS[name]()), b['seed'], b['N'])
-    plain.reset()
-    return int(plain.run(b['T'], O.Q_LEARNING, b['alpha'], b['gamma'], b['eps_q16'])['episodes'].sum())
+from ._behaviour import plain_total, search_behaviour_totals, tree_behaviour_totals
 
 
 @pytest.mark.parametrize('grid', ['default4x4', 'open8x8', 'maze11', 'lava32'])
@@ -123,7 +97,7 @@ def test_tree_search_finishes_more_episodes_than_plain_q_learning_and_flat_searc
     if grid == 'open8x8':
         assert total >= 3 * plain and least >= 2
     else:
-        flat = behaviour_totals('default4x4')[0]  # the flat search's total
+        flat = search_behaviour_totals('default4x4')[0]  # the flat search's total
         print('default4x4: flat rollout search {}'.format(flat))
         assert total >= 1.8 * plain and total >= 1.2 * flat
 

@@ -14,7 +14,7 @@ from oracle import c_oracle as C
 from . import _golden as G
 from . import _nstep_oracle as N
 from . import _td_oracle as O
-from .test_dyna_host import _greedy_walk, _shortest_from_start
+from . import _walks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -131,14 +131,14 @@ def _steps_to_shortest(grid, n, best, chunk=100, limit=30000):
     while done < limit:
         o.nstep(chunk, O.SARSA, n, 0.1, 0.9, int(0.1 * 65536))
         done += chunk
-        if all(_greedy_walk(grid, o.q[e]) == best for e in range(o.n)):
+        if all(_walks._greedy_walk(grid, o.q[e]) == best for e in range(o.n)):
             return done
     return None
 
 
 def test_n_step_sarsa_finds_the_shortest_path_in_fewer_real_steps():
     grid = C.Grid.from_env(GridUniverseEnv(custom_world_fp=G.level_path('maze_11x11.txt')))
-    best = _shortest_from_start(grid)
+    best = _walks._shortest_from_start(grid)
     # measured with this restatement (which the device matches byte for byte): 8500 real steps for n = 8, 21 100 for n = 1
     assert _steps_to_shortest(grid, 8, best) == 8500
     assert _steps_to_shortest(grid, 1, best) == 21100

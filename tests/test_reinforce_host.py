@@ -17,7 +17,7 @@ from . import _ac_oracle as A
 from . import _golden as G
 from . import _reinforce_oracle as R
 from . import _td_oracle as O
-from .test_dyna_host import _greedy_walk, _shortest_from_start
+from . import _walks
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -120,7 +120,7 @@ def _steps_to_shortest(grid, best, chunk=500, limit=40000):
     while done < limit:
         o.reinforce(chunk, 256, 0.003, 0.1, 0.99)
         done += chunk
-        if all(_greedy_walk(grid, o.h[e]) == best for e in range(o.n)):
+        if all(_walks._greedy_walk(grid, o.h[e]) == best for e in range(o.n)):
             return done
     return None
 
@@ -131,7 +131,7 @@ def test_reinforce_learns_the_shortest_path_in_the_maze():
     (numpy's RNG, another 11x11 maze with a 24-step path, one learner at a time) needed 12 500-24 500 at L = 256 and 9 000-14 500
     at L = 64.  The budget is 40 000."""
     grid = C.Grid.from_env(GridUniverseEnv(custom_world_fp=G.level_path('maze_11x11.txt')))
-    best = _shortest_from_start(grid)
+    best = _walks._shortest_from_start(grid)
     assert best == 24
     assert _steps_to_shortest(grid, best) == 37000
 

@@ -12,23 +12,8 @@ from oracle import c_oracle as C
 
 from . import _search_oracle as SO
 from . import _td_oracle as O
+from ._behaviour import search_behaviour_totals
 from ._tabular_cases import GRIDS, _grid
-
-# the settings of the behaviour check (test_gpu_search.py asserts the same totals on the device)
-BEHAVIOUR = dict(N=64, seed=7, T=300, alpha=0.1, gamma=0.99, eps_q16=6554, M=4, D=16, eps_sim_q16=65536)
-
-
-def behaviour_totals(name):
-    """(finished episodes of the search learners, of plain Q-learning, the least of one search learner) on grid `name`."""
-    b = BEHAVIOUR
-    grid = _grid(GRIDS[name]())
-    plain = O.TdOracle(grid, b['seed'], b['N'])
-    plain.reset()
-    base = plain.run(b['T'], O.Q_LEARNING, b['alpha'], b['gamma'], b['eps_q16'])['episodes']
-    srch = SO.SearchOracle(grid, b['seed'], b['N'])
-    srch.reset()
-    got = srch.search(b['T'], b['M'], b['D'], b['alpha'], b['gamma'], b['eps_q16'], b['eps_sim_q16'])['episodes']
-    return int(got.sum()), int(base.sum()), int(got.min())
 
 
 @pytest.mark.parametrize('grid', ['default4x4', 'open8x8', 'maze11', 'lava32'])
@@ -82,7 +67,7 @@ def test_search_finishes_more_episodes_than_plain_q_learning(grid, ratio):
     margin for a detail restated differently) and every learner at least 2 episodes; on default4x4 1.4 times.
     Observed with this restatement (finished episodes, search against plain): open8x8 427 (every learner at least 2) against
     72; default4x4 1832 against 1001 -- the prototype's totals exactly."""
-    total, plain, least = behaviour_totals(grid)
+    total, plain, least = search_behaviour_totals(grid)
     print('{}: search {} finished episodes (least per learner {}), plain Q-learning {}'.format(grid, total, least, plain))
     assert plain > 0 and total >= ratio * plain
     if grid == 'open8x8':

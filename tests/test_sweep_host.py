@@ -16,6 +16,7 @@ from oracle import c_oracle as C
 from . import _dyna_oracle as D
 from . import _golden as G
 from . import _sweep_oracle as SW
+from . import _walks
 from ._tabular_cases import GRIDS, _grid
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -117,35 +118,6 @@ def test_geometric_predecessors_are_all_predecessors(name):
             assert geo == scan, (e, S)
 
 
-def _shortest_from_start(grid):
-    S = grid.S
-    s = np.repeat(np.arange(S, dtype=np.int32), 4)
-    a = np.tile(np.arange(4, dtype=np.int32), S)
-    nxt = C.look_step_ahead(grid, s, a, True)[0].reshape(S, 4)
-    dist = {int(grid.starts[0]): 0}
-    frontier = [int(grid.starts[0])]
-    while frontier:
-        nf = []
-        for c in frontier:
-            if grid.goal[c] or grid.lava[c]:
-                continue
-            for b in range(4):
-                n = int(nxt[c, b])
-                if n not in dist:
-                    dist[n] = dist[c] + 1
-                    nf.append(n)
-        frontier = nf
-    return min(v for k, v in dist.items() if grid.goal[k])
-
-
-def _greedy_walk(grid, q):
-    s, n = int(grid.starts[0]), 0
-    while not (grid.goal[s] or grid.lava[s]) and n <= grid.S:
-        nxt, _, _ = C.look_step_ahead(grid, np.array([s], np.int32), np.array([int(np.argmax(q[s]))], np.int32), True)
-        s, n = int(nxt[0]), n + 1
-    return n if grid.goal[s] else -1
-
-
 def steps_to_shortest(o, run, grid, best, chunk=50, limit=20000):
     """Real steps until every learner's greedy walk from the start is a shortest path."""
     o.reset()
@@ -153,7 +125,7 @@ def steps_to_shortest(o, run, grid, best, chunk=50, limit=20000):
     while done < limit:
         run(chunk)
         done += chunk
-        if all(_greedy_walk(grid, o.q[e]) == best for e in range(o.n)):
+        if all(_walks._greedy_walk(grid, o.q[e]) == best for e in range(o.n)):
             return done
     return None
 
@@ -162,7 +134,7 @@ def test_prioritized_sweeping_needs_fewer_real_steps_than_dyna_q():
     """4 learners on maze_11x11, alpha 0.5, gamma 0.95, epsilon 0.1, P = 5: real steps until every learner's greedy walk is a
     shortest path.  The direction only is asserted; README.md quotes the two counts (printed here)."""
     grid = C.Grid.from_env(GridUniverseEnv(custom_world_fp=G.level_path('maze_11x11.txt')))
-    best = _shortest_from_start(grid)
+    best = _walks._shortest_from_start(grid)
     sw = SW.SweepOracle(grid, 3, 4)
     sweeping = steps_to_shortest(sw, lambda T: sw.sweep(T, 5, 1e-4, 0.5, 0.95, EPS), grid, best)
     assert sweeping is not None

@@ -1,7 +1,6 @@
 """Batched tabular Q-learning / SARSA, the parts that need no GPU: the stream-4 words, the CPU restatement learning the optimal
 policy, the greedy-policy conversion and the library's new symbols."""
 import subprocess
-from collections import deque
 
 import numpy as np
 import pytest
@@ -13,6 +12,7 @@ from oracle import c_oracle as C
 from oracle import gu_rng as R
 
 from . import _td_oracle as O
+from ._walks import _bfs_lengths, _greedy_walk_lengths
 
 
 def test_epsilon_greedy_words_equal_the_oracle_across_the_epoch_boundary():
@@ -29,41 +29,6 @@ def test_epsilon_greedy_words_equal_the_oracle_across_the_epoch_boundary():
     got = rng.epsilon_greedy_words(3, [2, 9], t0, 2)
     assert got[1, 1] == R.word(3, 9, 4, 0, epoch=1) and got[0, 0] == R.word(3, 2, 4, 5)
     assert got[0, 0] != R.word(3, 2, 0, 5)
-
-
-def _bfs_lengths(grid):
-    """Shortest number of steps from every cell to a terminal cell (backwards BFS over the move rule); -1 unreachable."""
-    S = grid.S
-    s = np.repeat(np.arange(S, dtype=np.int32), 4)
-    a = np.tile(np.arange(4, dtype=np.int32), S)
-    nxt, _, _ = C.look_step_ahead(grid, s, a, True)
-    term = (grid.goal | grid.lava).astype(bool)
-    dist = np.full(S, -1)
-    dist[term] = 0
-    pred = [[] for _ in range(S)]
-    for i in range(S * 4):
-        if nxt[i] != s[i]:
-            pred[nxt[i]].append(s[i])
-    q = deque(np.flatnonzero(term).tolist())
-    while q:
-        c = q.popleft()
-        for p in pred[c]:
-            if dist[p] < 0 and not term[p]:
-                dist[p] = dist[c] + 1
-                q.append(p)
-    return dist
-
-
-def _greedy_walk_lengths(grid, q):
-    S = grid.S
-    out = np.full(S, -1)
-    for s0 in range(S):
-        s, n = s0, 0
-        while not (grid.goal[s] or grid.lava[s]) and n <= S:
-            nxt, _, _ = C.look_step_ahead(grid, np.array([s], np.int32), np.array([int(np.argmax(q[s]))], np.int32), True)
-            s, n = int(nxt[0]), n + 1
-        out[s0] = n if grid.goal[s] else -1
-    return out
 
 
 @pytest.mark.parametrize('W,H,T', [(4, 4, 3000), (8, 8, 12000)])
