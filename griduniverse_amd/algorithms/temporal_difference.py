@@ -19,7 +19,7 @@ from .. import _lib
 from ._batch import _CHUNK, learn, need_learners, unit
 
 
-def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind=None, gust=0.0, fruit=None, doors=None):
+def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind=None, gust=0.0, fruit=None, doors=None, boxes=None):
     need_learners(num_learners)
     unit('epsilon', epsilon)
     unit('gust', gust)
@@ -33,6 +33,11 @@ def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, s
             raise ValueError('doors exclude wind and fruit')
         if not isinstance(doors, dict) or 'doors' not in doors or set(doors) - {'doors', 'keys', 'levers'}:
             raise ValueError('doors must be dict(doors=, keys=, levers=)')
+    if boxes is not None:
+        if wind is not None or fruit is not None or doors is not None:
+            raise ValueError('boxes exclude wind, fruit and doors')
+        if not isinstance(boxes, dict) or not {'boxes', 'targets'} <= set(boxes) or set(boxes) - {'boxes', 'targets', 'on_target'}:
+            raise ValueError('boxes must be dict(boxes=, targets=, on_target=)')
 
     def prepare(vec):  # (the tables have S << F rows under fruit and S << D under doors: the overlay goes on before them)
         if wind is not None:
@@ -42,24 +47,28 @@ def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, s
             vec.set_fruit(*fruit)
         if doors is not None:
             vec.set_doors(doors['doors'], doors.get('keys'), doors.get('levers'))
+        if boxes is not None:
+            vec.set_boxes(boxes['boxes'], boxes['targets'], boxes.get('on_target', 5))
         vec._ensure_q(q0)
 
     return learn(env, num_learners, seed, num_steps, _CHUNK, prepare, lambda vec, T: vec.td_run(T, method, alpha, discount_factor, epsilon))
 
 
-def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None):
+def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None, boxes=None):
     """Epsilon-greedy Q-learning, `num_steps` env steps per learner (episodes restart at a start cell when they end).  Returns
     Q float64[S][4], or [L][S][4] for L = num_learners > 1.  `wind`: a strength array ([H, W], or [W] per column; blowing up) or a
     (strength, direction) pair as VecGridUniverse.set_wind takes them, gusting with probability `gust`; None: the calm grid.  `fruit`: (cells, kinds, values)
     as VecGridUniverse.set_fruit takes them -- the result then has S << F rows, row eaten * S + s for cell s with the mask `eaten` of
     eaten fruit; not together with `wind`.  `doors`: dict(doors=, keys=, levers=) as VecGridUniverse.set_doors takes them -- the result
-    then has S << D rows, row open * S + s for cell s under the mask `open` of open slots; not together with `wind` or `fruit`."""
-    return _td('q_learning', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit, doors)
+    then has S << D rows, row open * S + s for cell s under the mask `open` of open slots; not together with `wind` or `fruit`.  `boxes`: dict(boxes=, targets=, on_target=)
+    as VecGridUniverse.set_boxes takes them -- the result then has S << (b * B) rows, row word * S + s for cell s under the word
+    grid.pack_boxes(S, cells) of the boxes' cells; not together with `wind`, `fruit` or `doors`."""
+    return _td('q_learning', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit, doors, boxes)
 
 
-def sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None):
+def sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None, boxes=None):
     """Epsilon-greedy SARSA; arguments and result as `q_learning`."""
-    return _td('sarsa', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit, doors)
+    return _td('sarsa', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit, doors, boxes)
 
 
 def expected_sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):

@@ -147,3 +147,53 @@ __device__ __forceinline__ uint32_t gu_door_touch(uint32_t c, uint32_t open, boo
     const uint32_t bit = ((entered && kind >= 2u) ? 1u : 0u) << (c & 7u);
     return kind == 3u ? open ^ bit : open | bit;
 }
+
+// ------------------------------------------------------------------------------------
+// boxes (include/gu.h: gu_set_boxes): one byte per cell behind the two cell planes, bit 0 = target, bit 1 = a box stands here at every
+// reset; the env's word holds the cell of box k in bits [k * b, (k + 1) * b), b the smallest width with S <= 1 << b (at most 16, and
+// b * B <= 32: the last field's shift is (B - 1) * b < 32, so nothing ever shifts by 32)
+// ------------------------------------------------------------------------------------
+// The kernels' parameter word (gu_engine::overlay_param): on_target, B, b and the number of boxes that stand on a target at a reset.
+#define GU_BOX_PARAM(v, B, b, on0) ((uint32_t)(v) | ((uint32_t)(B) << 8) | ((uint32_t)(b) << 16) | ((uint32_t)(on0) << 24))
+#define GU_BOX_V(p) ((int32_t)((p) & 31u))
+#define GU_BOX_B(p) (((p) >> 8) & 15u)  /* at most 8: b = 4, sixteen cells */
+#define GU_BOX_BITS(p) (((p) >> 16) & 31u)
+#define GU_BOX_ON0(p) (((p) >> 24) & 15u)
+#define GU_BOX_TARGET 1u
+#define GU_BOX_INITIAL 2u
+#define GU_BOX_SOLVED_REWARD 10
+
+// the box that stands on cell c under the word w, or -1: B field extractions and compares (B and b are launch-uniform)
+__device__ __forceinline__ int32_t gu_box_at(uint32_t w, int32_t c, uint32_t B, uint32_t b)
+{
+    const uint32_t field = (1u << b) - 1u;
+    int32_t k = -1;
+    for (uint32_t i = 0; i < B; ++i) k = ((w >> (i * b)) & field) == (uint32_t)c ? (int32_t)i : k;
+    return k;
+}
+
+// how many boxes of w stand on a target: B reads of the box plane (once per launch; the rollout and the learners carry the count)
+__device__ __forceinline__ uint32_t gu_box_on_target(const uint8_t *bx, uint32_t w, uint32_t B, uint32_t b)
+{
+    const uint32_t field = (1u << b) - 1u;
+    uint32_t on = 0;
+    for (uint32_t i = 0; i < B; ++i) on += bx[(w >> (i * b)) & field] & GU_BOX_TARGET;
+    return on;
+}
+
+// The push of box k, which stands on the candidate cell c (flags fc, box byte bc), by action `act`: the SECOND round of reads of a
+// step, behind c -- the flags and the box byte of c2, the engine's move from c.  Returns true where the push is refused (c2 == c: the
+// border or a wall; a goal or lava cell; another box) and leaves w alone; else moves the box in w and sets `gain` to target[c2] -
+// target[c].  Only lanes that push call it, so a wave in which nobody pushes skips the round (the caller's branch).
+__device__ __forceinline__ bool gu_box_push(const uint8_t *f, const uint8_t *bx, int32_t c, uint32_t fc, uint32_t bc, uint32_t act, int32_t delta, int32_t k,
+                                            uint32_t B, uint32_t b, uint32_t &w, int32_t &gain)
+{
+    const int32_t c2 = gu_move(c, fc, act, delta);
+    const uint32_t f2 = f[c2], b2 = bx[c2];
+    const bool other = gu_box_at(w, c2, B, b) >= 0;  // (no short circuit: the two reads and the compares are ONE round, not three)
+    const bool refused = (c2 == c) | ((f2 & GU_CELL_TERM) != 0u) | other;
+    const uint32_t field = (1u << b) - 1u, at = (uint32_t)k * b;
+    w = refused ? w : ((w & ~(field << at)) | ((uint32_t)c2 << at));
+    gain = refused ? 0 : (int32_t)(b2 & GU_BOX_TARGET) - (int32_t)(bc & GU_BOX_TARGET);
+    return refused;
+}

@@ -1,8 +1,9 @@
-// gu_overlay.hip -- the overlay slot of a single-grid engine (DESIGN.md "Overlays"): wind, fruit or doors, at most one at a time.
+// gu_overlay.hip -- the overlay slot of a single-grid engine (DESIGN.md "Overlays"): wind, fruit, doors or boxes, at most one at a time.
 // An overlay is a third byte plane behind the engine's two cell planes (gu_engine::d_overlay_cell holds all three in one piece, which
-// its kernels stage in LDS where they fit 64 KiB) and, for fruit and doors, one uint32 mask per env.  Here is everything around a
-// feature's rule: the install path, the getters, the masks' copies, the masks' reset and the arguments of the step and rollout
-// launches.  The features keep their plane's validation and their kernels (gu_wind.hip, gu_fruit.hip, gu_doors.hip).
+// its kernels stage in LDS where they fit 64 KiB) and, for fruit, doors and boxes, one uint32 mask per env with its value at reset
+// (gu_engine::overlay_init: 0 but for boxes).  Here is everything around a feature's rule: the install path, the getters, the masks'
+// copies, the masks' reset and the arguments of the step and rollout launches.  The features keep their plane's validation and their
+// kernels (gu_wind.hip, gu_fruit.hip, gu_doors.hip, gu_boxes.hip).
 #include "gu_overlay.hpp"
 #include "gu_tabular.hpp"  // (gu_env_range, gu_env_copy)
 
@@ -25,10 +26,12 @@ void gu_overlay_free(gu_engine *h)
     h->overlay = GU_OVERLAY_NONE;
     h->overlay_bits = 0;
     h->overlay_param = 0;
+    h->overlay_init = 0;
+    h->box_flags.clear();
     std::fill(h->fruit_value, h->fruit_value + 3, 0);
 }
 
-int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bits, uint32_t param)
+int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bits, uint32_t param, uint32_t init)
 {
     GU_TRY(gu_overlay_admits(h, kind));
     GU_HIP(hipStreamSynchronize(h->stream));
@@ -44,7 +47,7 @@ int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bit
         if (e == hipSuccess && bits) e = hipMalloc(&mask, mask_bytes);
         if (e == hipSuccess) e = hipMemcpy(cell, h->d_cell, 2 * cb, hipMemcpyDeviceToDevice);
         if (e == hipSuccess) e = hipMemcpy(cell + 2 * cb, padded.data(), cb, hipMemcpyHostToDevice);
-        if (e == hipSuccess && bits) e = hipMemset(mask, 0, mask_bytes);  // (the last step that can fail: behind it the call is not refused)
+        if (e == hipSuccess && bits) e = hipMemsetD32((hipDeviceptr_t)mask, (int)init, (size_t)h->N);  // (the last step that can fail: behind it the call is not refused)
         if (e != hipSuccess) {
             gu_release(cell, mask);
             return gu_fail(e == hipErrorOutOfMemory ? GU_ERR_NOMEM : GU_ERR_HIP, "gu_set_%s: the planes and masks: %s", GU_OVERLAY_NAME[kind], hipGetErrorString(e));
@@ -60,6 +63,7 @@ int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bit
     h->d_overlay_mask = mask;
     h->overlay_bits = bits;
     h->overlay_param = param;
+    h->overlay_init = init;
     return GU_OK;
 }
 
@@ -102,22 +106,23 @@ int gu_overlay_set_masks(gu_engine *h, int kind, int64_t env0, int64_t n, const 
     return gu_env_copy(h, hipMemcpyHostToDevice, masks, h->d_overlay_mask, env0, n, 1);
 }
 
-// gu_reset and gu_reset_done clear the masks of the envs they reset, in a launch of its own IN FRONT of gu_reset_kernel (it reads the
+// gu_reset and gu_reset_done set the masks of the envs they reset to the slot's reset value (0 but for boxes), in a launch of its own IN FRONT of gu_reset_kernel (it reads the
 // done flags that the reset is about to clear); that kernel is untouched and engines without masks never get here
 __global__ void __launch_bounds__(GU_BLOCK) gu_overlay_reset_kernel(uint32_t *__restrict__ masks, const uint8_t *__restrict__ mask, const int32_t *__restrict__ done,
-                                                                     int32_t only_done, int64_t N)
+                                                                     int32_t only_done, int64_t N, uint32_t init)
 {
     const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= N) return;
     bool take = !mask || mask[e];
     if (only_done && !done[e]) take = false;
-    if (take) masks[e] = 0u;
+    if (take) masks[e] = init;
 }
 
 int gu_overlay_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done)
 {
     if (!h->d_overlay_mask) return GU_OK;
-    hipLaunchKernelGGL(gu_overlay_reset_kernel, dim3(gu_blocks(h->N, GU_BLOCK)), dim3(GU_BLOCK), 0, h->stream, h->d_overlay_mask, d_mask, h->done(), only_done ? 1 : 0, h->N);
+    hipLaunchKernelGGL(gu_overlay_reset_kernel, dim3(gu_blocks(h->N, GU_BLOCK)), dim3(GU_BLOCK), 0, h->stream, h->d_overlay_mask, d_mask, h->done(), only_done ? 1 : 0, h->N,
+                       h->overlay_init);
     GU_HIP(hipGetLastError());
     return GU_OK;
 }
@@ -128,10 +133,10 @@ int gu_overlay_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done)
 int gu_overlay_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward, int32_t *host_done,
                            uint32_t *host_seq, uint32_t seq, uint32_t *host_err)
 {
-    static void (*const step[])(gu_engine *, bool, const OverlayStepArgs &) = {nullptr, gu_wind_step, gu_fruit_step, gu_doors_step};
+    static void (*const step[])(gu_engine *, bool, const OverlayStepArgs &) = {nullptr, gu_wind_step, gu_fruit_step, gu_doors_step, gu_boxes_step};
     const OverlayStepArgs a{h->d_overlay_cell, h->cell_bytes, h->W, h->delta_lut, d_actions_row, h->pos(), h->reward(), h->done(), h->d_episode, h->d_tcount,
                             h->d_overlay_mask, h->d_starts, (uint32_t)h->n_starts, h->seed_prefix, (uint32_t)h->env_id0, h->overlay_param, h->steps_taken, h->N, flags,
-                            gu_grid_sel(h), host_obs, host_reward, host_done, host_seq, seq, h->d_blocks_done, host_err, h->d_done_bits};
+                            gu_grid_sel(h), host_obs, host_reward, host_done, host_seq, seq, h->d_blocks_done, host_err, h->d_done_bits, h->overlay_init};
     step[h->overlay](h, gu_lds_block(h, GU_BLOCK, 3) != 0, a);
     GU_HIP(hipGetLastError());
     gu_envs_touched(h, 1);
@@ -141,9 +146,11 @@ int gu_overlay_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t 
 // `r` is what gu_launch_rollout has filled in (state, tables, rows, streams)
 void gu_overlay_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &r)
 {
-    static void (*const rollout[])(gu_engine *, const GuRolloutPlan &, const OverlayRolloutArgs &) = {nullptr, gu_wind_rollout, gu_fruit_rollout, gu_doors_rollout};
+    static void (*const rollout[])(gu_engine *, const GuRolloutPlan &, const OverlayRolloutArgs &) = {nullptr, gu_wind_rollout, gu_fruit_rollout, gu_doors_rollout,
+                                                                                                      gu_boxes_rollout};
     OverlayRolloutArgs a{};
-    a.cell = h->d_overlay_cell, a.cell_bytes = h->cell_bytes, a.W = h->W, a.lut = h->delta_lut, a.gs = r.gs, a.mask = h->d_overlay_mask, a.param = h->overlay_param;
+    a.cell = h->d_overlay_cell, a.cell_bytes = h->cell_bytes, a.W = h->W, a.lut = h->delta_lut, a.gs = r.gs, a.mask = h->d_overlay_mask, a.param = h->overlay_param,
+    a.init = h->overlay_init;
     a.greedy = r.greedy, a.pi_thr = r.pi_thr, a.actions = r.actions;
     a.pos = r.pos, a.reward = r.reward, a.done = r.done, a.episode = r.episode, a.tcount = r.tcount, a.done_bits = r.done_bits;
     a.starts = r.starts, a.n_starts = r.n_starts, a.env_id0 = r.env_id0, a.seed_prefix = h->seed_prefix;

@@ -125,14 +125,21 @@ __device__ __forceinline__ uint64_t gu_dyna_pack(int32_t s2, int32_t r, int32_t 
 // fruit's: the kernel sets `rows` and `eaten` before begin() and stores `eaten` behind end().  move() turns the candidate cell back
 // at a closed door and lets a key or lever of the cell ENTERED change `eaten2`; it reads the candidate's three bytes together and
 // picks behind the gate (the head of gu_doors.hip), so the gate adds no dependent read to a step.
-template <bool LDS, bool ROWS = true, int WIND = 0, bool FRUIT = false, bool DOORS = false>
+// BOXES (include/gu.h: gu_set_boxes; never with WIND, FRUIT or DOORS): a.cell carries the box plane behind the two cell planes and the
+// table has S << (b * B) rows.  The env's word of box cells lives where the masks live -- `eaten` the word the lane stands under,
+// `eaten2` the one behind move() --, so the rows and their comparisons are the masked ones.  The kernel sets `rows`, `eaten`, `bparam`
+// (GU_BOX_PARAM) and `binit` (the word at reset) before begin() and stores `eaten` behind end().  The lane carries the count of boxes on
+// a target beside the word (`on`, `on2`), as the rollout kernel does (the head of gu_boxes.hip); move() applies rules 2-6 of
+// gu_set_boxes, the push behind a branch that only pushing lanes take.
+template <bool LDS, bool ROWS = true, int WIND = 0, bool FRUIT = false, bool DOORS = false, bool BOXES = false>
 struct TabLane {
-    static constexpr bool MASKED = FRUIT || DOORS;  // the table has a row per (cell, mask)
+    static constexpr bool MASKED = FRUIT || DOORS || BOXES;  // the table has a row per (cell, mask)
     CellMap m;
-    const uint8_t *wd;  // WIND: the wind plane; FRUIT: the fruit plane; DOORS: the door plane
+    const uint8_t *wd;  // WIND: the wind plane; FRUIT: the fruit plane; DOORS: the door plane; BOXES: the box plane
     uint32_t gust_q16;  // WIND == 2
     uint32_t fvalues;   // FRUIT
-    uint32_t eaten, eaten2;  // MASKED: the env's mask (eaten fruit / open slots), and the one behind move()
+    uint32_t bparam, binit, on, on2;  // BOXES: the parameter word, the word at reset, boxes on a target under `eaten` and behind move()
+    uint32_t eaten, eaten2;  // MASKED: the env's mask (eaten fruit / open slots / box cells), and the one behind move()
     int32_t S, rows;         // MASKED: states, and rows of one learner's table (S << F, S << D)
     LaneGrid lg;
     int64_t e;
@@ -161,6 +168,7 @@ struct TabLane {
         prefix = gu_rng_prefix(gu_rng_seed_prefix_epoch(a.seed_prefix, (uint32_t)(t >> 32)), env);
         qe = ROWS ? a.q + (MASKED ? e * rows : e * a.S) * 4 : nullptr;
         if (MASKED) eaten2 = eaten;
+        if (BOXES) on = on2 = gu_box_on_target(wd, eaten, GU_BOX_B(bparam), GU_BOX_BITS(bparam));
         s = a.pos[e];
         r = a.reward[e];
         d = a.done[e];
@@ -179,6 +187,7 @@ struct TabLane {
             ++ep;
             d = 0;
             if (MASKED) eaten = eaten2 = 0u;  // the fruit grows back; the doors are shut again
+            if (BOXES) eaten = eaten2 = binit, on = on2 = GU_BOX_ON0(bparam);  // the boxes are back where they began
             if (ROWS) q = gu_q_load(qe + row() * 4);
         }
     }
@@ -200,7 +209,21 @@ struct TabLane {
             if (WIND == 2 && __builtin_amdgcn_ballot_w64(k > 0u) != 0ull) k = gu_wind_gust(k, gu_rng_word(prefix, GU_RNG_STREAM_WIND, (uint32_t)t), gust_q16);
             s2 = gu_wind_push<LDS>(m.f, s2, c, k, a.lut, a.W);
         }
-        if (DOORS) {
+        if (BOXES) {
+            // rules 2-6 of gu_set_boxes on the candidate s2 (gu_boxes_move of gu_boxes.hip, with the bytes of s' read behind the push)
+            const uint32_t B = GU_BOX_B(bparam), b = GU_BOX_BITS(bparam);
+            const bool solved = on == B;
+            const int32_t c = s2, at = gu_box_at(eaten, c, B, b), k = ((c != s) & !solved) ? at : -1;
+            bool stay = solved;
+            int32_t gain = 0;
+            eaten2 = eaten;
+            if (k >= 0) stay = gu_box_push(m.f, wd, c, m.f[c], wd[c], ua, gu_delta<LDS>(ua, a.lut, a.W), k, B, b, eaten2, gain);
+            s2 = stay ? s : c;
+            on2 = on + (uint32_t)gain;
+            const bool won = on2 == B;
+            r = won ? GU_BOX_SOLVED_REWARD : m.r[s2] + GU_BOX_V(bparam) * gain;
+            d = won ? 1 : (m.f[s2] >> GU_CELL_TERM_BIT) & 1;
+        } else if (DOORS) {
             // A closed door refuses entry as a wall does; the key or lever of a cell entered changes the mask behind the step.  The door
             // byte of the candidate is read BESIDE its flags and reward byte, and the gate picks between them and the bytes of s (its
             // reward byte is read beside its flags): two rounds of reads on the chain, as without doors.
@@ -243,6 +266,7 @@ struct TabLane {
         q = n;
         s = s2;
         if (MASKED) eaten = eaten2;
+        if (BOXES) on = on2;
         if (a.tr_obs) {
             const int64_t row = (int64_t)i * a.N + e;
             a.tr_obs[row] = s2;

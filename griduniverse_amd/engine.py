@@ -200,10 +200,32 @@ class Engine(object):
         """Install the masks uint32[n] of envs env0 .. env0+n-1 (gu_set_doors_state)."""
         self._set_masks(self.lib.gu_set_doors_state, mask, env0, 'mask')
 
+    def set_boxes(self, box, on_target=0):
+        """Install the box plane uint8[S] (grid.box_plane) and what a box pushed onto a target pays (0 .. 16); None takes the boxes
+        away again (gu_set_boxes).  Sets every env's word to the initial boxes' cells."""
+        b = None if box is None else _lib.as_array(box, np.uint8, (self.spec.S,), 'box')
+        check(self.lib.gu_set_boxes(self._h, ptr(b), int(on_target)))
+
+    def get_boxes(self):
+        """(box uint8[S], on_target, B, b): the plane, the pay, the number of boxes and the bits of one box's cell in an env's word,
+        or None while no boxes are set (gu_get_boxes)."""
+        box = np.empty(self.spec.S, np.uint8)
+        v, n, b = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
+        check(self.lib.gu_get_boxes(self._h, ptr(box), ctypes.byref(v), ctypes.byref(n), ctypes.byref(b)))
+        return (box, v.value, n.value, b.value) if n.value else None
+
+    def get_boxes_state(self, env0=0, n=None):
+        """uint32[n]: the words of envs env0 .. env0+n-1, box k's cell in bits [k * b, (k + 1) * b) (gu_get_boxes_state)."""
+        return self._get_masks(self.lib.gu_get_boxes_state, env0, n)
+
+    def set_boxes_state(self, words, env0=0):
+        """Install the words uint32[n] of envs env0 .. env0+n-1 (gu_set_boxes_state)."""
+        self._set_masks(self.lib.gu_set_boxes_state, words, env0, 'words')
+
     @property
     def td_rows(self):
         """Rows of one env's Q table: S, or S << F while F fruits are set (include/gu.h: gu_set_fruit), or S << D while doors with
-        D slots are set (gu_set_doors)."""
+        D slots are set (gu_set_doors), or S << (b * B) while B boxes of b bits each are set (gu_set_boxes)."""
         return self.spec.S << self.stores()['overlay_bits']
 
     def seed(self, seed):
@@ -307,12 +329,12 @@ class Engine(object):
         check(self.lib.gu_rollout(self._h, int(T), _POLICIES[policy], flags))
 
     ROLLOUT_FORM = ('family', 'layout', 'map', 'block', 'workgroups', 'lds_bytes', 'flags', 'K', 'row_shift', 'stream_words', 'pace_slot', 'pace_mode')
-    ROLLOUT_FAMILIES = {0: None, 1: 'general', 2: 'rows', 3: 'kstep', 4: 'wind', 5: 'fruit', 6: 'doors'}
+    ROLLOUT_FAMILIES = {0: None, 1: 'general', 2: 'rows', 3: 'kstep', 4: 'wind', 5: 'fruit', 6: 'doors', 7: 'boxes'}
     ROLLOUT_FLAG_BITS = ('pair', 'half', 'per_wave', 'pi_lds', 'straddle', 'entry_table', 'xcd_remap')
 
     def rollout_last_form(self):
         """What the last rollout of this engine ran on (gu_diag_rollout_form): dict with the twelve form words under the names of
-        ROLLOUT_FORM ('family' as a name: 'general', 'rows', 'kstep', 'wind', 'fruit', 'doors'; None before the first rollout), each flag bit as a
+        ROLLOUT_FORM ('family' as a name: 'general', 'rows', 'kstep', 'wind', 'fruit', 'doors', 'boxes'; None before the first rollout), each flag bit as a
         bool under its name in ROLLOUT_FLAG_BITS, and the raw words as 'words'."""
         words = np.zeros(len(self.ROLLOUT_FORM), np.int32)
         n = ctypes.c_int32(0)

@@ -164,6 +164,8 @@ FRUIT_KINDS = {'apple': 1, 'lemon': 2, 'melon': 3}  # the kind codes (0: no frui
 FRUIT_MAX = 32  # fruits per grid: one bit each in an env's uint32 mask
 DOOR_KINDS = {'door': 1, 'key': 2, 'lever': 3}  # the kind codes of include/gu.h, gu_set_doors (0: nothing)
 DOOR_SLOTS_MAX = 8  # slots per grid: one bit each in an env's mask of open slots
+BOX_TARGET, BOX_INITIAL = 1, 2  # the bits of a box byte (include/gu.h, gu_set_boxes)
+BOX_ON_TARGET_MAX = 16  # the most a box pushed onto a target may pay
 
 
 def fruit_plane(W, H, cells, kinds='apple'):
@@ -246,3 +248,103 @@ def door_plane(W, H, doors, keys=None, levers=None):
                     raise ValueError('cell {} is named twice'.format(c))
                 plane[c] = slot | (DOOR_KINDS[name[:-1]] << 4)
     return plane
+
+
+# ---- boxes: the per-cell plane and the per-env word of include/gu.h, gu_set_boxes ----------------------------------
+def _cell_list(what, cells, S, least):
+    """Sorted distinct cell indices from a cell or a list of cells (ValueError)."""
+    c = np.atleast_1d(np.asarray([] if cells is None else cells))
+    if c.ndim != 1 or (c.size and (c.dtype == bool or not np.issubdtype(c.dtype, np.integer))):
+        raise ValueError('{} must be a list of cell indices'.format(what))
+    if c.size < least:
+        raise ValueError('{} must name at least {} cell'.format(what, least))
+    if c.size and (c.min() < 0 or c.max() >= S):
+        raise ValueError('{} must lie in 0 .. {}'.format(what, S - 1))
+    if np.unique(c).size != c.size:
+        raise ValueError('{} names a cell twice'.format(what))
+    return sorted(int(x) for x in c)
+
+
+def box_bits(S):
+    """b: the bits of one box's cell in an env's word, the smallest width with S <= 1 << b (at least 1)."""
+    return max(1, int(S - 1).bit_length())
+
+
+def box_plane(W, H, boxes, targets):
+    """uint8[S]: the box plane of a W x H grid as gu_set_boxes takes it -- bit 0 of a cell: it is a target, bit 1: a box stands on it at
+    every reset; a cell may be both.  `boxes`, `targets`: a cell or a list of distinct cells.  At least one box, at least as many
+    targets as boxes, at least one box off target, and the boxes' cells must fit an env's word: box_bits(S) * len(boxes) <= 32."""
+    W, H = int(W), int(H)
+    S = W * H
+    bx, tg = _cell_list('boxes', boxes, S, 1), _cell_list('targets', targets, S, 1)
+    if len(tg) < len(bx):
+        raise ValueError('{} targets for {} boxes: every box needs a target'.format(len(tg), len(bx)))
+    if set(bx) <= set(tg):
+        raise ValueError('every box stands on a target: nothing is left to solve')
+    if box_bits(S) * len(bx) > 32:
+        raise ValueError('{} boxes of {} bits each do not fit the 32 bits of an env\'s word'.format(len(bx), box_bits(S)))
+    plane = np.zeros(S, np.uint8)
+    plane[tg] |= BOX_TARGET
+    plane[bx] |= BOX_INITIAL
+    return plane
+
+
+def pack_boxes(S, cells):
+    """uint32[n] (or one uint32 for a 1-d `cells`): the words that hold the box cells int[n, B] -- box k in bits [k * b, (k + 1) * b),
+    b = box_bits(S).  Every cell must lie in 0 .. S-1, no two boxes of a word on one cell, and b * B <= 32."""
+    c = np.asarray(cells)
+    if c.ndim not in (1, 2) or c.shape[-1] == 0 or c.dtype == bool or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError('cells must be integers of shape (B,) or (n, B)')
+    b, B = box_bits(S), c.shape[-1]
+    if b * B > 32:
+        raise ValueError('{} boxes of {} bits each do not fit the 32 bits of an env\'s word'.format(B, b))
+    if c.size and (c.min() < 0 or c.max() >= S):
+        raise ValueError('box cells must lie in 0 .. {}'.format(S - 1))
+    rows = c.reshape(-1, B).astype(np.uint64)
+    if any(np.unique(r).size != B for r in rows):
+        raise ValueError('two boxes of one env on the same cell')
+    words = (rows << (np.arange(B, dtype=np.uint64) * np.uint64(b))).sum(axis=1).astype(np.uint32)  # (distinct fields: the sum is the or)
+    return words[0] if c.ndim == 1 else words
+
+
+def unpack_boxes(S, words, B):
+    """int32[n, B] (or int32[B] for one word): the box cells held by the words, the inverse of pack_boxes."""
+    w = np.asarray(words)
+    b = box_bits(S)
+    if not 1 <= int(B) or b * int(B) > 32:
+        raise ValueError('B must be at least 1 and {} bits each must fit 32 bits'.format(b))
+    flat = np.atleast_1d(w).astype(np.uint64)
+    cells = ((flat[:, None] >> (np.arange(int(B), dtype=np.uint64) * np.uint64(b))) & np.uint64((1 << b) - 1)).astype(np.int32)
+    return cells[0] if w.ndim == 0 else cells
+
+
+def sokoban_level(text):
+    """(GridSpec, boxes, targets) from a level in the standard XSB characters: '#' wall, '@' agent, '+' agent on a target, '$' box, '*'
+    box on a target, '.' target, ' ' or '-' floor.  Rows are the lines of `text` (empty lines before and behind are dropped), ragged
+    rows are padded with floor.  The grid has the agent's cell as its start and neither goal nor lava cells: its episodes end by
+    solving the level."""
+    lines = [ln.rstrip('\r') for ln in str(text).split('\n')]
+    while lines and not lines[0].strip():
+        lines.pop(0)
+    while lines and not lines[-1].strip():
+        lines.pop()
+    if not lines:
+        raise ValueError('the level is empty')
+    W, H = max(len(ln) for ln in lines), len(lines)
+    walls, boxes, targets, agents = [], [], [], []
+    for y, ln in enumerate(lines):
+        for x, ch in enumerate(ln):
+            s = y * W + x
+            if ch not in '#@+$*. -':
+                raise ValueError('character {!r} in row {}: a level holds # @ + $ * . - and spaces'.format(ch, y))
+            if ch == '#':
+                walls.append(s)
+            if ch in '@+':
+                agents.append(s)
+            if ch in '$*':
+                boxes.append(s)
+            if ch in '+*.':
+                targets.append(s)
+    if len(agents) != 1:
+        raise ValueError('a level has one agent, got {}'.format(len(agents)))
+    return GridSpec(W, H, agents, [], [], walls), boxes, targets

@@ -19,7 +19,7 @@ import numpy as np
 from . import _lib, softmax
 from .engine import Engine
 from .envs.griduniverse_env import GridUniverseEnv
-from .grid import DOOR_KINDS, FRUIT_KINDS, GridSpec, door_plane, fruit_plane, wind_plane
+from .grid import BOX_INITIAL, BOX_ON_TARGET_MAX, BOX_TARGET, DOOR_KINDS, FRUIT_KINDS, GridSpec, box_bits, box_plane, door_plane, fruit_plane, pack_boxes, unpack_boxes, wind_plane
 
 
 def _q16(x):
@@ -236,8 +236,63 @@ class VecGridUniverse(object):
         """Install masks uint32[n] (or one number) for envs env0 ..; no bit at or above the number of slots in use."""
         self.engine.set_doors_state(_masks(mask, self._mask_width(3), 'mask must hold masks of the {} door slots set'), env0)
 
+    def set_boxes(self, boxes, targets=None, on_target=5):
+        """Pushable boxes on the engine's grid (single-grid engines; include/gu.h: gu_set_boxes): a box refuses entry unless the
+        agent's move can push it one cell on -- not into a wall, the border, a goal or lava cell or another box --, a push onto a
+        target cell adds `on_target` (0 .. 16) to the step's reward and a push off one takes it back, and the step after which every
+        box stands on a target pays +10 and ends the episode.  Every reset puts the boxes back.  `boxes`, `targets` as
+        grid.box_plane takes them (cells not on a wall, goal or lava cell, no box on a start cell); set_boxes(None) takes the boxes
+        away.  step, rollout and td_run follow the boxes (td_run learns on S << bits rows, bits = boxes x grid.box_bits(S), at most
+        10); the other learners, the DP and look-ahead calls, the path search, the trail, wind, fruit and doors are refused while
+        they are set.  A box pushed into a corner ends no episode: an auto-resetting env comes back only through a goal or lava
+        cell.  sense, render and the N = 1 GridUniverseEnv facade show box and target cells as free cells."""
+        if boxes is None:
+            if targets is not None:
+                raise ValueError('set_boxes(None) takes the boxes away: targets must be None too')
+            self.engine.set_boxes(None)
+            return
+        if isinstance(on_target, (bool, np.bool_)) or not isinstance(on_target, (int, np.integer)) or not 0 <= int(on_target) <= BOX_ON_TARGET_MAX:
+            raise ValueError('on_target must be an integer in 0 .. {}'.format(BOX_ON_TARGET_MAX))
+        plane = box_plane(self.spec.W, self.spec.H, boxes, targets)
+        blocked = (self.spec.wall | self.spec.goal | self.spec.lava) & (plane != 0)
+        if blocked.any():
+            raise ValueError('a box or target on cell {}, which is a wall or a goal or lava cell'.format(int(np.flatnonzero(blocked)[0])))
+        on_start = [s for s in self.spec.starts if plane[s] & BOX_INITIAL]
+        if on_start:
+            raise ValueError('a box on cell {}, which is a start cell'.format(on_start[0]))
+        self.engine.set_boxes(plane, int(on_target))
+
+    def boxes(self):
+        """None while no boxes are set, else dict(boxes=int64[B] ascending (index = box), targets=int64 ascending, on_target=int)."""
+        got = self.engine.get_boxes()
+        if got is None:
+            return None
+        return dict(boxes=np.flatnonzero(got[0] & BOX_INITIAL), targets=np.flatnonzero(got[0] & BOX_TARGET), on_target=got[1])
+
+    def box_cells(self, env0=0, n=None):
+        """int32[n, B]: the cells of the B boxes of envs env0 .. env0+n-1 (to the end when n is None); box k is the one that began
+        on the k-th initial cell in ascending order."""
+        got = self.engine.get_boxes()
+        if got is None:
+            raise ValueError('no boxes set: call set_boxes first')
+        return unpack_boxes(self.spec.S, self.engine.get_boxes_state(env0, n), got[2])
+
+    def set_box_cells(self, cells, env0=0):
+        """Install the box cells int[n, B] (or [B] for one env) of envs env0 ..: distinct cells, none on a wall, goal or lava cell."""
+        c = np.asarray(cells)
+        B = self._mask_width(4) // box_bits(self.spec.S)
+        if not B:
+            raise ValueError('no boxes set: call set_boxes first')
+        if c.ndim not in (1, 2) or c.shape[-1] != B:
+            raise ValueError('cells must hold the cells of the {} boxes set, shape (n, {})'.format(B, B))
+        words = np.atleast_1d(pack_boxes(self.spec.S, c))
+        blocked = (self.spec.wall | self.spec.goal | self.spec.lava)[c.reshape(-1)]
+        if blocked.any():
+            raise ValueError('a box on cell {}, which is a wall or a goal or lava cell'.format(int(c.reshape(-1)[np.flatnonzero(blocked)[0]])))
+        self.engine.set_boxes_state(words, env0)
+
     def _mask_width(self, overlay):
-        """Bits of an env's mask in use while `overlay` (2 fruit, 3 doors: include/gu.h, GU_STORE_OVERLAY) is set, else 0."""
+        """Bits of an env's mask in use while `overlay` (2 fruit, 3 doors, 4 boxes: include/gu.h, GU_STORE_OVERLAY) is set, else 0."""
         st = self.engine.stores()
         return st['overlay_bits'] if st['overlay'] == overlay else 0
 
@@ -289,7 +344,9 @@ class VecGridUniverse(object):
     def q_table(self, env0=0, n=None):
         """float64[n, S, 4]: the Q tables of envs env0 .. env0+n-1 (to the end when n is None).  While F fruits are set
         (set_fruit) the tables have S << F rows: row eaten * S + s belongs to cell s with the mask `eaten`.  While doors with D slots
-        are set (set_doors) they have S << D rows: row open * S + s belongs to cell s under the mask `open`."""
+        are set (set_doors) they have S << D rows: row open * S + s belongs to cell s under the mask `open`.  While B boxes are set
+        (set_boxes) they have S << (b * B) rows, b = grid.box_bits(S): row word * S + s belongs to cell s under the word
+        grid.pack_boxes(S, cells)."""
         return self.engine.td_get_q(env0, n)
 
     def set_q_table(self, q, env0=0):

@@ -305,6 +305,60 @@ int gu_get_doors(gu_handle h, uint8_t *door /* zeros when none */, int32_t *n_sl
 int gu_get_doors_state(gu_handle h, int64_t env0, int64_t n, uint32_t *open);
 int gu_set_doors_state(gu_handle h, int64_t env0, int64_t n, const uint32_t *open);  /* a bit at or above D: GU_ERR_INVALID */
 
+/* ---- boxes: Sokoban -- cells that refuse entry, and move ---------------------------------------------------------
+ * Build-defined (the reference lists a Sokoban extension and has none; restated on the CPU by tests/_boxes_oracle.py).  Boxes are a
+ * property of a SINGLE-GRID engine, and the fourth kind of overlay: they exclude wind, fruit, doors and the agent trail as those
+ * exclude each other.  They consist of one byte per cell, box[s] -- bit 0 = the cell is a TARGET, bit 1 = a box stands here at every
+ * reset, bits 2..7 zero; a cell may be both --, and one uint32 word per env.  Neither a target nor an initial box may lie on a wall, a
+ * goal cell or a lava cell, and an initial box may not lie on a start cell.  B is the number of initial boxes, B >= 1; there must be
+ * at least B targets, and at least one initial box must be off target (an env is never born solved).
+ * THE WORD: b is the smallest width with S <= 1 << b.  Box k, numbered by ascending initial cell, keeps its identity for the whole
+ * episode; its cell sits in bits [k * b, (k + 1) * b) of the env's word.  b * B must be <= 32 (5 boxes at S <= 64, 4 at S <= 256, 3
+ * at S <= 1024, 2 up to S = 65536; b * B == 32 is legal).  `init` is the word of the initial boxes.
+ * SOLVED means that every box stands on a target cell.
+ * One step of env e from cell s under the word w with a valid action a:
+ *   1. the lazy auto-reset, where the call has one, sets w = init together with the position: the boxes are back where they began;
+ *   2. if w is solved already, nothing moves: s' = s, r = +10, d = 1.  This is absorbing, as a goal cell is, and a property of w, not
+ *      of done[];
+ *   3. c is the candidate cell, from the engine's move rule exactly as without boxes;
+ *   4. if c != s and box k stands on c, then c2 is the engine's move from c with the same action (the OPEN bits of c itself: the
+ *      border and walls refuse it).  The push is refused when c2 == c, when c2 is a goal or lava cell, or when another box stands on
+ *      c2.  A refused push is a bump: s' = s, w unchanged.  Otherwise box k moves to c2 and s' = c.  Without a box on c, s' = c;
+ *   5. a box refuses ENTRY only: an agent that stands on a box cell (after gu_set_state or gu_set_boxes_state) leaves it like any
+ *      cell;
+ *   6. if w' is solved, then r = +10 and d = 1, in place of everything else.  Otherwise r = R[s'] + v * (target[c2] - target[c]) on a
+ *      push and R[s'] without one, and d is the engine's for s'.  v is on_target, 0 .. 16: pushing a box off a target takes back what
+ *      pushing it on paid, so no cycle earns reward;
+ *   7. t += 1.
+ * A rejected action (outside -4 .. 3) moves nothing and changes no word.  No RNG stream is added and none is drawn differently.
+ * Every path that resets an env sets its word to init: gu_reset (masked envs only), gu_reset_done, the lazy resets inside the
+ * kernels, and gu_set_boxes itself, for every env.  gu_set_state and gu_seed leave the words alone.
+ * DEADLOCK: a box that can never reach a target again (in a corner, say) ends no episode.  An auto-resetting env comes back only
+ * through a goal or lava cell, so a grid for learners should have one.
+ * While boxes are set, gu_step (pinned I/O and the completion word included), gu_step_device, gu_rollout (all four policies,
+ * GU_F_TRAJECTORY / GU_F_STATS; GU_F_PACKED returns GU_ERR_UNSUPPORTED; rows are the three [T][N] planes) and gu_td_run (both methods)
+ * run their box kernels (csrc/gu_boxes.hip, csrc/gu_td.hip); every call that is refused while doors are set (gu_set_doors above) is
+ * refused in the same way, with GU_ERR_UNSUPPORTED.  Calls that read rows or state only are unaffected; sense and render show box and
+ * target cells as free cells.
+ * THE LEARNERS' TABLES: while boxes are set a gu_td_run table has S << (b * B) rows and row w * S + s belongs to cell s under the word
+ * w, exactly as under doors.  gu_td_init takes at most 10 bits (b * B <= 10: one box up to S = 1024, two up to S = 32) and returns
+ * GU_ERR_INVALID above.
+ * gu_set_boxes: box[S] and on_target, or NULL = no boxes again.  GU_ERR_STATE without a grid; GU_ERR_UNSUPPORTED on a multi-grid
+ *              engine, while wind, fruit or doors are set and while the agent trail is on (each of those refuses while boxes are
+ *              set); GU_ERR_INVALID for a malformed byte, a box or target on a wall or terminal cell, an initial box on a start cell,
+ *              no box, fewer targets than boxes, every box on a target, b * B > 32 or on_target outside 0 .. 16.  A refused call
+ *              leaves the engine as it was.  Ends what the learners carry, destroys a captured step graph and drops the Q tables
+ *              whenever it changes their row count, as gu_set_doors does.  Keeps positions and step counts.  gu_set_grid,
+ *              gu_set_grids and gu_generate_mazes drop the boxes.
+ * gu_get_boxes: the plane (zeros when none), on_target, B (0 = none set) and b; every pointer may be NULL.
+ * gu_get_boxes_state / gu_set_boxes_state: the words of envs env0 .. env0+n-1; GU_ERR_STATE while no boxes are set; GU_ERR_INVALID for
+ *              a word with a bit at or above b * B, a field >= S, two equal fields, or a field on a wall or terminal cell.  Setting
+ *              words ends the learners' carries. */
+int gu_set_boxes(gu_handle h, const uint8_t *box /* [S], NULL = no boxes again */, int32_t on_target /* 0 .. 16 */);
+int gu_get_boxes(gu_handle h, uint8_t *box /* zeros when none */, int32_t *on_target, int32_t *n_boxes /* 0 = none set */, int32_t *bits_per_box);
+int gu_get_boxes_state(gu_handle h, int64_t env0, int64_t n, uint32_t *words);
+int gu_set_boxes_state(gu_handle h, int64_t env0, int64_t n, const uint32_t *words);
+
 /* ---- RNG ---------------------------------------------------------------------
  * Keys the per-env counter RNG (MurmurHash3 of seed, global env id, stream,
  * counter -- 32-bit counters, no stream repeats before 2^32 draws; host view:
@@ -388,8 +442,8 @@ int gu_set_state(gu_handle h, const int32_t *pos, const int32_t *done, const uin
 enum {
     GU_STORE_S = 0,         /* states of the grid; 0 without a grid */
     GU_STORE_N_GRIDS,       /* grids installed (gu_set_grids, gu_generate_mazes) */
-    GU_STORE_OVERLAY,       /* 0 none, 1 wind, 2 fruit, 3 doors */
-    GU_STORE_OVERLAY_BITS,  /* bits of an env's mask in use: F fruits, D door slots, else 0 */
+    GU_STORE_OVERLAY,       /* 0 none, 1 wind, 2 fruit, 3 doors, 4 boxes */
+    GU_STORE_OVERLAY_BITS,  /* bits of an env's mask in use: F fruits, D door slots, b * B under boxes, else 0 */
     GU_STORE_TD_ROWS,       /* rows per env of the Q tables (gu_td_init); 0 = none for the current rows */
     GU_STORE_DOUBLE,        /* states of the pairs of tables (gu_double_init); 0 = none */
     GU_STORE_DYNA,          /* states of the models (gu_dyna_init); 0 = none */
