@@ -10,6 +10,7 @@ import numpy as np
 from oracle import c_oracle as C
 from oracle import gu_rng as R
 
+from ._start_log import StartLog
 from ._td_oracle import Q_LEARNING, SARSA, choose, row_max, words  # noqa: F401  (re-exported for the tests)
 
 TARGET, INITIAL = 1, 2
@@ -53,6 +54,7 @@ class BoxesOracle(object):
         self.state.pos[:] = grid.starts[0]  # where gu_set_grid puts every env
         self.reward = np.zeros(n, np.int32)
         self.env_ids = np.arange(env_id0, env_id0 + n, dtype=np.uint64)
+        self.starts = StartLog(grid.starts)  # what the lazy resets drew
         self.q0 = q0
         self.carry = np.full(n, -1, np.int32)
         self.carry_valid = False
@@ -93,6 +95,11 @@ class BoxesOracle(object):
         d = self._lazy_reset()
         self.carry_valid = False
         return d
+
+    def set_state(self, tcount=None):
+        self.carry_valid = False
+        if tcount is not None:
+            self.state.tcount[:] = tcount
 
     def saw_everything(self, resets=True):
         """Has the log met every event?  resets=False: all but the lazy reset, which a run without auto-reset cannot meet."""
@@ -142,6 +149,7 @@ class BoxesOracle(object):
             d &= who
         if d.any():
             C.reset(self.grid, self.seed, self.state, d.astype(np.uint8))
+            self.starts.note(self.state.pos[d])
             self.log['reset_restored'] += int((self.cells[d] != self.init).any(axis=1).sum()) if self.B else 0
             self.cells[d] = self.init
         return d

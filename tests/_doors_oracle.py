@@ -10,6 +10,7 @@ import numpy as np
 from oracle import c_oracle as C
 from oracle import gu_rng as R
 
+from ._start_log import StartLog
 from ._td_oracle import Q_LEARNING, SARSA, choose, row_max, words  # noqa: F401  (re-exported for the tests)
 
 DOOR, KEY, LEVER = 1, 2, 3
@@ -33,6 +34,7 @@ class DoorsOracle(object):
         self.state.pos[:] = grid.starts[0]  # where gu_set_grid puts every env
         self.reward = np.zeros(n, np.int32)
         self.env_ids = np.arange(env_id0, env_id0 + n, dtype=np.uint64)
+        self.starts = StartLog(grid.starts)  # what the lazy resets drew
         self.q0 = q0
         self.carry = np.full(n, -1, np.int32)
         self.carry_valid = False
@@ -66,6 +68,11 @@ class DoorsOracle(object):
         d = self._lazy_reset()
         self.carry_valid = False
         return d
+
+    def set_state(self, tcount=None):
+        self.carry_valid = False
+        if tcount is not None:
+            self.state.tcount[:] = tcount
 
     def saw_everything(self):
         return all(self.log[k] > 0 for k in EVENTS)
@@ -103,6 +110,7 @@ class DoorsOracle(object):
             d &= who
         if d.any():
             C.reset(self.grid, self.seed, self.state, d.astype(np.uint8))
+            self.starts.note(self.state.pos[d])
             self.open[d] = 0
         return d
 

@@ -7,6 +7,7 @@ import numpy as np
 from oracle import c_oracle as C
 from oracle import gu_rng as R
 
+from ._start_log import StartLog
 from ._td_oracle import Q_LEARNING, SARSA, choose, row_max, words  # noqa: F401  (re-exported for the tests)
 
 
@@ -23,6 +24,7 @@ class FruitOracle(object):
         self.state.pos[:] = grid.starts[0]  # where gu_set_grid puts every env
         self.reward = np.zeros(n, np.int32)
         self.env_ids = np.arange(env_id0, env_id0 + n, dtype=np.uint64)
+        self.starts = StartLog(grid.starts)  # what the lazy resets drew
         self.q0 = q0
         self.carry = np.full(n, -1, np.int32)
         self.carry_valid = False
@@ -84,6 +86,7 @@ class FruitOracle(object):
             d &= who
         if d.any():
             C.reset(self.grid, self.seed, self.state, d.astype(np.uint8))
+            self.starts.note(self.state.pos[d])
             self.eaten[d] = 0
         return d
 

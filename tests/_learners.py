@@ -1,7 +1,8 @@
 """How the tests drive each batched learner: one adapter per entry point (its CPU restatement of tests/_*_oracle.py, its stores on
-the device and in the restatement, one launch of each), the registry LEARNERS of all of them, and the harness that compares a learner
-with its restatement on a shared grid beyond LDS and on per-env stores across 2^32 bytes.  Used by test_gpu_learners_at_scale.py
-(which says what the cases are for), test_gpu_double.py and test_learner_harness_host.py."""
+the device and in the restatement, one launch of each), the registry LEARNERS of all of them, and the harnesses that compare a learner
+with its restatement: on an engine whose first env has any global id (_against_restatement; on a shared grid beyond LDS,
+_shared_grid_beyond_lds) and on per-env stores across 2^32 bytes.  Used by test_gpu_learners_at_scale.py and test_gpu_env_ids.py
+(which say what the cases are for), test_gpu_double.py, test_learner_harness_host.py and test_env_ids_host.py."""
 import numpy as np
 import pytest
 
@@ -476,9 +477,10 @@ def _same_state(st, o, env0, where):
         assert np.array_equal(st[k][env0:env0 + o.n], getattr(o.state, k)), (where, k)
 
 
-def _open(N, g, seed, learner):
-    """N envs on grid g with the learner's stores at their fills; the test skips where the library finds no room for them."""
-    vec = gua.VecGridUniverse(N, template=_spec(g), seed=seed)
+def _open(N, g, seed, learner, env_id0=0):
+    """N envs on grid g, the shard that starts at global env id env_id0, with the learner's stores at their fills; the test skips
+    where the library finds no room for them."""
+    vec = gua.VecGridUniverse(N, template=_spec(g), seed=seed, env_id0=env_id0)
     try:
         learner.prepare(vec)
     except gua.GuError as err:
@@ -501,28 +503,67 @@ def _launch(vec, learner, T, **kw):
         raise
 
 
-def _shared_grid_beyond_lds(learner, g, bar, seed=3, N=130):
-    """Two launches with rows and statistics; rows, statistics, env state and every store, whole, by bytes.  And so that the case
-    cannot pass empty: an episode ended, some env stood on a cell >= bar, and the tables left their fill."""
+def _against_restatement(learner, g, N, seed, env_id0, bar=None):
+    """Two launches of learner.T with rows and statistics on the engine whose first env has the global id env_id0; rows, statistics,
+    env state and every store, whole, by bytes, against the restatement built at that id.  And so that the case cannot pass empty: an
+    episode ended, the tables left their fill and, where `bar` is given, some env stood on a cell >= bar.  Returns what _restated
+    returns: the restatement, its first reset and its rows."""
     grid = _grid(g)
-    assert grid.S > 32767  # gu_lds_block returns 0: the L2 instantiation, the arithmetic deltas
-    vec = _open(N, g, seed, learner)
+    vec = _open(N, g, seed, learner, env_id0)
     try:
-        o = learner.oracle(grid, seed, N, 0)
-        assert np.array_equal(vec.reset(), o.reset())
-        top, episodes = int(o.state.pos.max()), 0
+        o = learner.oracle(grid, seed, N, env_id0)
+        first = o.reset()
+        assert np.array_equal(vec.reset(), first)
+        top, rows = int(o.state.pos.max()), []
         for T in learner.T:
             got = _launch(vec, learner, T, trajectory=True, stats=True)
             want = learner.restate(o, T)
             _same(got, want)
             _same_stores(learner.got(vec, 0, N), learner.want(o), T)
-            top, episodes = max(top, int(want['obs'].max())), episodes + int(want['episodes'].sum())
+            top = max(top, int(want['obs'].max()))
+            rows.append(want)
         _same_state(vec.get_state(), o, 0, 'state')
-        assert episodes > 0 and top >= bar
-        for name, table, fill in learner.learned(o):
-            assert (table != fill).any(), name
+        ran = dict(o=o, first=first, rows=rows)
+        _ran_something(learner, ran)
+        assert bar is None or top >= bar
+        return ran
     finally:
         vec.close()
+
+
+def _restated(learner, g, N, seed, env_id0, launches=None):
+    """The restatement's side of _against_restatement alone: dict(o=, first=, rows=) after the launches of learner.T."""
+    o = learner.oracle(_grid(g), seed, N, env_id0)
+    first = o.reset()
+    return dict(o=o, first=first, rows=[learner.restate(o, T) for T in (launches or learner.T)])
+
+
+def _ran_something(learner, ran):
+    """An episode ended and the tables left their fill."""
+    assert sum(int(want['episodes'].sum()) for want in ran['rows']) > 0
+    for name, table, fill in learner.learned(ran['o']):
+        assert (table != fill).any(), name
+
+
+def env_ids(N):
+    """The first env ids of the shards the tests run at: one whose low bits disagree with the lane index, one whose batch of N envs
+    straddles bit 31, and the highest gu_create admits (env_id0 + num_envs <= 0xFFFFFFFF)."""
+    return (77, 2 ** 31 - 40, 2 ** 32 - 1 - N)
+
+
+def _a_shard_worth_comparing(learner, g, ran, ran0):
+    """The conditions under which a comparison at env_id0 != 0 says something, on the restatement alone (`ran` at the id under test,
+    `ran0` the same at id 0): an episode ended, every table left its fill, the first reset put envs on every start cell (two at
+    least), and the rows differ from those at id 0 -- a kernel that ignored the id would not pass."""
+    _ran_something(learner, ran)
+    assert len(g['starts']) > 1 and set(ran['first'].tolist()) == set(g['starts'])
+    assert any(not np.array_equal(a['obs'], b['obs']) for a, b in zip(ran['rows'], ran0['rows']))
+
+
+def _shared_grid_beyond_lds(learner, g, bar, seed=3, N=130):
+    """Part A of test_gpu_learners_at_scale.py: _against_restatement on a grid beyond LDS, where some env stood on a cell >= bar."""
+    assert _grid(g).S > 32767  # gu_lds_block returns 0: the L2 instantiation, the arithmetic deltas
+    _against_restatement(learner, g, N, seed, 0, bar)
 
 
 def _tables_for_setter(learner, o):

@@ -6,6 +6,7 @@ import numpy as np
 from oracle import c_oracle as C
 from oracle import gu_rng as R
 
+from ._start_log import StartLog
 from ._td_oracle import Q_LEARNING, SARSA, choose, row_max, words  # noqa: F401  (re-exported for the tests)
 
 M32 = 0xFFFFFFFF
@@ -77,6 +78,7 @@ class WindOracle(object):
         self.state.pos[:] = grid.starts[0]  # where gu_set_grid puts every env
         self.reward = np.zeros(n, np.int32)
         self.env_ids = np.arange(env_id0, env_id0 + n, dtype=np.uint64)
+        self.starts = StartLog(grid.starts)  # what the lazy resets drew
         self.q = None if q0 is None else np.full((n, grid.S, 4), float(q0), np.float64)  # (None: no learners, no tables)
         self.carry = np.full(n, -1, np.int32)
         self.carry_valid = False
@@ -90,6 +92,11 @@ class WindOracle(object):
     def reset(self, mask=None):
         self.carry_valid = False
         return C.reset(self.grid, self.seed, self.state, mask)
+
+    def reset_done(self):
+        d = self._lazy_reset()
+        self.carry_valid = False
+        return d
 
     def set_state(self, tcount=None):
         self.carry_valid = False
@@ -118,6 +125,7 @@ class WindOracle(object):
             d &= who
         if d.any():
             C.reset(self.grid, self.seed, self.state, d.astype(np.uint8))
+            self.starts.note(self.state.pos[d])
         return d
 
     def step(self, actions, auto_reset=False):

@@ -1,6 +1,7 @@
 """Config 5 parity: the float64 DP kernels (csrc/gu_vi.hip) against golden tables captured from the
 reference's core/algorithms (bit-exact: compared as raw bytes), and the fused sweep+step launch
 against the oracle."""
+import functools
 import warnings
 
 import numpy as np
@@ -632,3 +633,64 @@ def test_calls_of_thousands_of_rounds_return_every_delta(vi_path, gu_option):
             out[mode] = res
     assert out['default'][:7] == out['one_workgroup'][:7] == out['per_launch'][:7]
     assert out['default'][7:] == out['per_launch'][7:]
+
+
+# ---- the fused sweep + step kernels on an engine that is a shard ----
+SHARD_GRID = dict(W=6, H=5, starts=[0, 24, 5], goals=[16], lava=[14, 27], walls=[9])
+SHARD_N, SHARD_ROUNDS, SHARD_GAMMA = 700, 23, 0.9
+
+
+@functools.lru_cache(maxsize=None)
+def _fused_rounds_restated(env_id0):
+    """SHARD_ROUNDS fused rounds of SHARD_N envs whose first env has the global id env_id0, with the C oracle alone, as
+    test_fused_sweep_step_launch restates them: per round (v, pi, delta, obs, reward, done), and the state left behind."""
+    grid, S = C.Grid.from_lists(**SHARD_GRID), SHARD_GRID['W'] * SHARD_GRID['H']
+    st = C.State(SHARD_N, env_id0)
+    first = C.reset(grid, 3, st)
+    v, pi, rounds = np.zeros(S), np.ones((S, 4)) / 4, []
+    for _ in range(SHARD_ROUNDS):
+        v, pi, delta = C.value_iteration_step(grid, SHARD_GAMMA, pi, v)
+        acts = np.argmax(pi, axis=1).astype(np.int32)
+        if st.done.any():  # the lazy auto-reset comes before the action is looked up, as in the kernel
+            C.reset(grid, 3, st, mask=st.done.astype(bool))
+        want = C.rollout(grid, 3, st, 1, False, actions=acts[st.pos.copy()][None, :])
+        rounds.append((v, pi, delta, want['obs'][0], want['reward'][0], want['done'][0]))
+    return first, rounds, st
+
+
+@pytest.mark.parametrize('env_id0', [77, 2 ** 31 - 40])
+def test_fused_sweep_step_on_a_shard(env_id0):
+    """gu_vi.hip's and gu_vi_xcd.hip's fused kernels derive the stream-1 prefix of the lazy reset from a.env_id0 + e themselves; every
+    other test runs them at env_id0 = 0.  Three starts, and episodes end from round 3 on: the draws decide where the envs stand.
+    23 single launches round by round, then one call of 23 rounds: tables, deltas, positions, rewards, done flags and episode
+    counts as bytes (the autouse vi_path sends both through every form)."""
+    first, rounds, st = _fused_rounds_restated(env_id0)
+    first0, rounds0, st0 = _fused_rounds_restated(0)
+    assert st.episode.min() >= 2 and set(first.tolist()) == set(SHARD_GRID['starts'])  # every env was reset lazily, and more than once
+    assert not np.array_equal(st.pos, st0.pos) and any(not np.array_equal(a[3], b[3]) for a, b in zip(rounds, rounds0))
+    S = SHARD_GRID['W'] * SHARD_GRID['H']
+    spec = GridSpec(SHARD_GRID['W'], SHARD_GRID['H'], SHARD_GRID['starts'], SHARD_GRID['goals'], SHARD_GRID['lava'], SHARD_GRID['walls'])
+
+    def same_state(eng, k):
+        obs, rew, don = eng.read_outputs()
+        s = eng.get_state()
+        v_got, pi_got = eng.vi_get()
+        v, pi, _, w_obs, w_rew, w_don = rounds[k]
+        assert v_got.tobytes() == v.tobytes() and pi_got.tobytes() == pi.tobytes(), k
+        assert obs.tobytes() == w_obs.tobytes() and rew.tobytes() == w_rew.tobytes() and np.array_equal(don != 0, w_don != 0), k
+        assert s['pos'].tobytes() == w_obs.tobytes() and np.array_equal(s['done'] != 0, w_don != 0), k
+
+    with Engine(SHARD_N, spec, env_id0=env_id0, seed=3) as eng:
+        assert np.array_equal(eng.reset(), first)
+        eng.vi_set(np.zeros(S), np.ones((S, 4)) / 4)
+        for k in range(SHARD_ROUNDS):
+            assert eng.vi_sweep_step(SHARD_GAMMA, auto_reset=True) == rounds[k][2], k
+            same_state(eng, k)
+        assert eng.get_state()['episode'].tobytes() == st.episode.tobytes()
+    with Engine(SHARD_N, spec, env_id0=env_id0, seed=3) as eng:
+        assert np.array_equal(eng.reset(), first)
+        eng.vi_set(np.zeros(S), np.ones((S, 4)) / 4)
+        deltas = eng.vi_sweep_step_run(SHARD_GAMMA, SHARD_ROUNDS, auto_reset=True)
+        assert deltas.tobytes() == np.array([r[2] for r in rounds], np.float64).tobytes()
+        same_state(eng, SHARD_ROUNDS - 1)
+        assert eng.get_state()['episode'].tobytes() == st.episode.tobytes()
