@@ -2,15 +2,15 @@
 the agent's and the pushed box's -- comes from the C oracle's look_step_ahead (care_about_terminal on) and every reset from its
 reset, the action words come from oracle/gu_rng.py, and the learner on (cell, word) reuses the epsilon-greedy rule of
 tests/_td_oracle.py.  The oracle keeps a log of what its runs met (the nine EVENTS), so that a comparison can show it compared
-something.  Test infrastructure; it imports oracle/ read-only."""
+something.  Only the rule is here: the resets, gu_step's rejected actions, the rollout policies and td_run around it are
+tests/_overlay_oracle.py's.  Test infrastructure; it imports oracle/ read-only."""
 import collections
 
 import numpy as np
 
 from oracle import c_oracle as C
-from oracle import gu_rng as R
 
-from ._start_log import StartLog
+from ._overlay_oracle import OverlayOracle
 from ._td_oracle import Q_LEARNING, SARSA, choose, row_max, words  # noqa: F401  (re-exported for the tests)
 
 TARGET, INITIAL = 1, 2
@@ -45,20 +45,12 @@ def pack(S, cells):
     return (c << (np.arange(c.shape[1], dtype=np.uint64) * np.uint64(bits_of(S)))).sum(axis=1).astype(np.uint32)
 
 
-class BoxesOracle(object):
-    """N envs (and learners) on `grid` (a C.Grid) under the box plane `box` uint8[S] (None: no boxes) with on_target = v."""
+class BoxesOracle(OverlayOracle):
+    """N envs (and learners) on `grid` (a C.Grid) under the box plane `box` uint8[S] (None: no boxes) with on_target = v.  The
+    learner's row is word * S + cell."""
 
     def __init__(self, grid, seed, n, box=None, v=5, env_id0=0, q0=0.0):
-        self.grid, self.seed, self.n = grid, int(seed), int(n)
-        self.state = C.State(n, env_id0)
-        self.state.pos[:] = grid.starts[0]  # where gu_set_grid puts every env
-        self.reward = np.zeros(n, np.int32)
-        self.env_ids = np.arange(env_id0, env_id0 + n, dtype=np.uint64)
-        self.starts = StartLog(grid.starts)  # what the lazy resets drew
-        self.q0 = q0
-        self.carry = np.full(n, -1, np.int32)
-        self.carry_valid = False
-        self.q = None
+        super().__init__(grid, seed, n, env_id0, q0)
         self.log = dict.fromkeys(EVENTS, 0)
         self.terminal = (np.asarray(grid.goal) | np.asarray(grid.lava)).astype(np.int32)
         self.set_boxes(box, v)
@@ -72,9 +64,7 @@ class BoxesOracle(object):
         self.init = np.flatnonzero(self.box & INITIAL).astype(np.int32)  # box k by ascending cell
         self.B, self.b = len(self.init), bits_of(S)
         self.cells = np.tile(self.init, (self.n, 1))  # [n, B]
-        self.carry_valid = False
-        if self.q0 is not None and (self.q is None or self.q.shape[1] != S << (self.b * self.B)):
-            self.q = np.full((self.n, S << (self.b * self.B), 4), float(self.q0), np.float64)
+        self._installed()
 
     @property
     def words(self):
@@ -85,21 +75,16 @@ class BoxesOracle(object):
         self.cells[env0:env0 + len(c)] = c
         self.carry_valid = False
 
-    def reset(self, mask=None):
-        self.carry_valid = False
-        took = np.ones(self.n, bool) if mask is None else np.asarray(mask) != 0
+    def _bits(self):
+        return self.b * self.B
+
+    def _row(self, pos):
+        return self.words.astype(np.int64) * self.grid.S + pos
+
+    def _restore(self, took, lazy=False):
+        if lazy:
+            self.log['reset_restored'] += int((self.cells[took] != self.init).any(axis=1).sum()) if self.B else 0
         self.cells[took] = self.init
-        return C.reset(self.grid, self.seed, self.state, mask)
-
-    def reset_done(self):
-        d = self._lazy_reset()
-        self.carry_valid = False
-        return d
-
-    def set_state(self, tcount=None):
-        self.carry_valid = False
-        if tcount is not None:
-            self.state.tcount[:] = tcount
 
     def saw_everything(self, resets=True):
         """Has the log met every event?  resets=False: all but the lazy reset, which a run without auto-reset cannot meet."""
@@ -142,83 +127,6 @@ class BoxesOracle(object):
         self.cells[who] = cells2[who]
         st.tcount[who] += np.uint64(1)
         return st.pos.copy(), self.reward.copy(), st.done.copy()
-
-    def _lazy_reset(self, who=None):
-        d = self.state.done != 0
-        if who is not None:
-            d &= who
-        if d.any():
-            C.reset(self.grid, self.seed, self.state, d.astype(np.uint8))
-            self.starts.note(self.state.pos[d])
-            self.log['reset_restored'] += int((self.cells[d] != self.init).any(axis=1).sum()) if self.B else 0
-            self.cells[d] = self.init
-        return d
-
-    def step(self, actions, auto_reset=False):
-        """gu_step: envs whose action lies outside -4 .. 3 do not step (nor reset, nor touch their word); returns (obs, reward, done, rejected)."""
-        self.carry_valid = False
-        a = np.asarray(actions, np.int64)
-        ok = (a >= -4) & (a <= 3)
-        if auto_reset:
-            self._lazy_reset(ok)
-        obs, rew, don = self._move(np.where(ok, a, 0), ok)
-        return obs, rew, don, ~ok
-
-    def rollout(self, T, policy='uniform', auto_reset=True, actions=None, pi=None):
-        """gu_rollout: rows [T, n], statistics and the state left behind."""
-        self.carry_valid = False
-        st = self.state
-        obs, rew, don = (np.empty((T, self.n), np.int32) for _ in range(3))
-        for i in range(T):
-            if auto_reset:
-                self._lazy_reset()
-            s = st.pos
-            if policy == 'uniform':
-                act = R.actions_v(self.seed, self.env_ids, st.tcount)
-            elif policy == 'stream':
-                act = np.asarray(actions[i], np.int32)
-            elif policy == 'greedy':
-                act = np.argmax(pi[s], axis=1).astype(np.int32)
-            else:
-                act = np.array([R.sampled_action(self.seed, int(e), int(t), pi[int(c)]) for e, t, c in zip(self.env_ids, st.tcount, s)], np.int32)
-            obs[i], rew[i], don[i] = self._move(act)
-        return dict(obs=obs, reward=rew, done=don, ret=rew.astype(np.int64).sum(axis=0), episodes=(don != 0).sum(axis=0).astype(np.int32))
-
-    def td_run(self, T, method, alpha, gamma, eps_q16):
-        """gu_td_run under boxes: tests/_td_oracle.py's TdOracle.run on the rows word * S + s."""
-        st, idx, S = self.state, np.arange(self.n), self.grid.S
-        alpha, gamma = float(alpha), float(gamma)
-        act = self.carry.copy() if (method == SARSA and self.carry_valid) else np.full(self.n, -1, np.int32)
-        obs, rew, don = (np.empty((T, self.n), np.int32) for _ in range(3))
-        for i in range(T):
-            d = self._lazy_reset()
-            act[d] = -1
-            row = self.words.astype(np.int64) * S + st.pos
-            need = act < 0
-            if need.any():
-                w = words(self.seed, self.env_ids, st.tcount)
-                act = np.where(need, choose(self.q[idx, row], w, eps_q16), act).astype(np.int32)
-            s2, r, dn = self._move(act)
-            dn = dn != 0
-            row2 = self.words.astype(np.int64) * S + s2
-            nxt = self.q[idx, row2].copy()  # pre-update row of (s', w')
-            if method == SARSA:
-                a2 = choose(nxt, words(self.seed, self.env_ids, st.tcount), eps_q16)
-                m = nxt[idx, a2]
-                a2 = np.where(dn, -1, a2).astype(np.int32)
-            else:
-                m = row_max(nxt)
-                a2 = np.full(self.n, -1, np.int32)
-            rf = r.astype(np.float64)
-            target = np.where(dn, rf, rf + gamma * m)
-            qa = self.q[idx, row, act]
-            self.q[idx, row, act] = qa + alpha * (target - qa)
-            act = a2
-            obs[i], rew[i], don[i] = s2, r, dn
-        if T > 0:
-            self.carry = act
-            self.carry_valid = method == SARSA
-        return dict(obs=obs, reward=rew, done=don, ret=rew.astype(np.int64).sum(axis=0), episodes=don.sum(axis=0).astype(np.int32))
 
 
 def shortest_solution(grid, box, v, start):

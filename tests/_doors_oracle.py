@@ -2,15 +2,15 @@
 cell comes from the C oracle's look_step_ahead (care_about_terminal on) and every reset from its reset, the action words come from
 oracle/gu_rng.py, and the learner on (cell, open) reuses the epsilon-greedy rule of tests/_td_oracle.py.  The oracle keeps a log of
 what its runs met (bumps on closed doors, passages, key pick-ups, lever pulls), so that a comparison can show it compared something.
-Test infrastructure; it imports oracle/ read-only."""
+Only the rule is here: the resets, gu_step's rejected actions, the rollout policies and td_run around it are
+tests/_overlay_oracle.py's.  Test infrastructure; it imports oracle/ read-only."""
 import collections
 
 import numpy as np
 
 from oracle import c_oracle as C
-from oracle import gu_rng as R
 
-from ._start_log import StartLog
+from ._overlay_oracle import OverlayOracle
 from ._td_oracle import Q_LEARNING, SARSA, choose, row_max, words  # noqa: F401  (re-exported for the tests)
 
 DOOR, KEY, LEVER = 1, 2, 3
@@ -25,54 +25,36 @@ def slots_of(door):
     return np.asarray(door, np.int64) & 7
 
 
-class DoorsOracle(object):
-    """N envs (and learners) on `grid` (a C.Grid) under the door plane `door` uint8[S] (None: no doors)."""
+class DoorsOracle(OverlayOracle):
+    """N envs (and learners) on `grid` (a C.Grid) under the door plane `door` uint8[S] (None: no doors).  The learner's row is
+    open * S + cell."""
 
     def __init__(self, grid, seed, n, door=None, env_id0=0, q0=0.0):
-        self.grid, self.seed, self.n = grid, int(seed), int(n)
-        self.state = C.State(n, env_id0)
-        self.state.pos[:] = grid.starts[0]  # where gu_set_grid puts every env
-        self.reward = np.zeros(n, np.int32)
-        self.env_ids = np.arange(env_id0, env_id0 + n, dtype=np.uint64)
-        self.starts = StartLog(grid.starts)  # what the lazy resets drew
-        self.q0 = q0
-        self.carry = np.full(n, -1, np.int32)
-        self.carry_valid = False
-        self.q = None
+        super().__init__(grid, seed, n, env_id0, q0)
         self.log = dict.fromkeys(EVENTS, 0)
         self.terminal = (np.asarray(grid.goal) | np.asarray(grid.lava)).astype(np.int32)
         self.set_doors(door)
 
     def set_doors(self, door):
         """gu_set_doors: clears every mask; the tables go (back to q0: the caller's gu_td_init) when their row count changes."""
-        S = self.grid.S
-        self.door = np.zeros(S, np.uint8) if door is None else np.asarray(door, np.uint8).copy()
+        self.door = np.zeros(self.grid.S, np.uint8) if door is None else np.asarray(door, np.uint8).copy()
         self.D = int(np.unique(self.door[self.door != 0] & 7).size)
         self.open = np.zeros(self.n, np.uint32)
-        self.carry_valid = False
-        if self.q0 is not None and (self.q is None or self.q.shape[1] != S << self.D):
-            self.q = np.full((self.n, S << self.D, 4), float(self.q0), np.float64)
+        self._installed()
 
     def set_open(self, mask, env0=0):
         m = np.atleast_1d(np.asarray(mask, np.uint32))
         self.open[env0:env0 + m.size] = m
         self.carry_valid = False
 
-    def reset(self, mask=None):
-        self.carry_valid = False
-        took = np.ones(self.n, bool) if mask is None else np.asarray(mask) != 0
+    def _bits(self):
+        return self.D
+
+    def _row(self, pos):
+        return self.open.astype(np.int64) * self.grid.S + pos
+
+    def _restore(self, took, lazy=False):
         self.open[took] = 0
-        return C.reset(self.grid, self.seed, self.state, mask)
-
-    def reset_done(self):
-        d = self._lazy_reset()
-        self.carry_valid = False
-        return d
-
-    def set_state(self, tcount=None):
-        self.carry_valid = False
-        if tcount is not None:
-            self.state.tcount[:] = tcount
 
     def saw_everything(self):
         return all(self.log[k] > 0 for k in EVENTS)
@@ -103,82 +85,6 @@ class DoorsOracle(object):
         self.open[who] = new[who]
         st.tcount[who] += np.uint64(1)
         return st.pos.copy(), self.reward.copy(), st.done.copy()
-
-    def _lazy_reset(self, who=None):
-        d = self.state.done != 0
-        if who is not None:
-            d &= who
-        if d.any():
-            C.reset(self.grid, self.seed, self.state, d.astype(np.uint8))
-            self.starts.note(self.state.pos[d])
-            self.open[d] = 0
-        return d
-
-    def step(self, actions, auto_reset=False):
-        """gu_step: envs whose action lies outside -4 .. 3 do not step (nor reset, nor touch their mask); returns (obs, reward, done, rejected)."""
-        self.carry_valid = False
-        a = np.asarray(actions, np.int64)
-        ok = (a >= -4) & (a <= 3)
-        if auto_reset:
-            self._lazy_reset(ok)
-        obs, rew, don = self._move(np.where(ok, a, 0), ok)
-        return obs, rew, don, ~ok
-
-    def rollout(self, T, policy='uniform', auto_reset=True, actions=None, pi=None):
-        """gu_rollout: rows [T, n], statistics and the state left behind."""
-        self.carry_valid = False
-        st = self.state
-        obs, rew, don = (np.empty((T, self.n), np.int32) for _ in range(3))
-        for i in range(T):
-            if auto_reset:
-                self._lazy_reset()
-            s = st.pos
-            if policy == 'uniform':
-                act = R.actions_v(self.seed, self.env_ids, st.tcount)
-            elif policy == 'stream':
-                act = np.asarray(actions[i], np.int32)
-            elif policy == 'greedy':
-                act = np.argmax(pi[s], axis=1).astype(np.int32)
-            else:
-                act = np.array([R.sampled_action(self.seed, int(e), int(t), pi[int(c)]) for e, t, c in zip(self.env_ids, st.tcount, s)], np.int32)
-            obs[i], rew[i], don[i] = self._move(act)
-        return dict(obs=obs, reward=rew, done=don, ret=rew.astype(np.int64).sum(axis=0), episodes=(don != 0).sum(axis=0).astype(np.int32))
-
-    def td_run(self, T, method, alpha, gamma, eps_q16):
-        """gu_td_run under doors: tests/_td_oracle.py's TdOracle.run on the rows open * S + s."""
-        st, idx, S = self.state, np.arange(self.n), self.grid.S
-        alpha, gamma = float(alpha), float(gamma)
-        act = self.carry.copy() if (method == SARSA and self.carry_valid) else np.full(self.n, -1, np.int32)
-        obs, rew, don = (np.empty((T, self.n), np.int32) for _ in range(3))
-        for i in range(T):
-            d = self._lazy_reset()
-            act[d] = -1
-            row = self.open.astype(np.int64) * S + st.pos
-            need = act < 0
-            if need.any():
-                w = words(self.seed, self.env_ids, st.tcount)
-                act = np.where(need, choose(self.q[idx, row], w, eps_q16), act).astype(np.int32)
-            s2, r, dn = self._move(act)
-            dn = dn != 0
-            row2 = self.open.astype(np.int64) * S + s2
-            nxt = self.q[idx, row2].copy()  # pre-update row of (s', open')
-            if method == SARSA:
-                a2 = choose(nxt, words(self.seed, self.env_ids, st.tcount), eps_q16)
-                m = nxt[idx, a2]
-                a2 = np.where(dn, -1, a2).astype(np.int32)
-            else:
-                m = row_max(nxt)
-                a2 = np.full(self.n, -1, np.int32)
-            rf = r.astype(np.float64)
-            target = np.where(dn, rf, rf + gamma * m)
-            qa = self.q[idx, row, act]
-            self.q[idx, row, act] = qa + alpha * (target - qa)
-            act = a2
-            obs[i], rew[i], don[i] = s2, r, dn
-        if T > 0:
-            self.carry = act
-            self.carry_valid = method == SARSA
-        return dict(obs=obs, reward=rew, done=don, ret=rew.astype(np.int64).sum(axis=0), episodes=don.sum(axis=0).astype(np.int32))
 
 
 def shortest_walk(grid, door, start):

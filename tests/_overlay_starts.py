@@ -19,9 +19,8 @@ import numpy as np
 from griduniverse_amd.grid import box_plane, door_plane, fruit_plane, wind_plane
 
 from . import _boxes_oracle as BO
-from . import _doors_oracle as DO
-from . import _fruit_oracle as FO
 from . import _wind_oracle as WO
+from ._overlays import masks_of, overlay  # noqa: F401  (masks_of: re-exported for the tests)
 
 N, T, SEED = 130, 33, 6
 IDS = (0, 2 ** 31 - 40)
@@ -74,21 +73,14 @@ def plane(kind, name):
     return box_plane(W, H, *box_cells(name))
 
 
+def extra(kind):
+    """The setter's arguments behind the plane of `kind`: the gust probability, the fruit values, the boxes' pay."""
+    return {'wind': (0,), 'gusts': (WO.GUST_THIRDS,), 'fruit': (FRUIT_VALUES,), 'doors': (), 'boxes': (ON_TARGET,)}[kind]
+
+
 def oracle(kind, name, env_id0, n=N, seed=SEED, q0=None):
     """The restatement of n envs under `kind` on grid `name`, its first env the global id env_id0.  q0 None: no learners."""
-    grid, p = c_grid(name), plane(kind, name)
-    if kind in ('wind', 'gusts'):
-        return WO.WindOracle(grid, seed, n, wind=p, gust_q16=WO.GUST_THIRDS if kind == 'gusts' else 0, env_id0=env_id0, q0=q0)
-    if kind == 'fruit':
-        return FO.FruitOracle(grid, seed, n, p, FRUIT_VALUES, env_id0=env_id0, q0=q0)
-    if kind == 'doors':
-        return DO.DoorsOracle(grid, seed, n, p, env_id0=env_id0, q0=q0)
-    return BO.BoxesOracle(grid, seed, n, p, ON_TARGET, env_id0=env_id0, q0=q0)
-
-
-def masks_of(o, kind):
-    """The per-env overlay state of a restatement: eaten masks, open masks, box words; None under wind."""
-    return o.eaten if kind == 'fruit' else o.open if kind == 'doors' else o.words if kind == 'boxes' else None
+    return overlay(kind).oracle(c_grid(name), seed, n, plane(kind, name), *extra(kind), env_id0=env_id0, q0=q0)
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,7 +1,7 @@
 """Pushable boxes on the device (gu_set_boxes; csrc/gu_boxes.hip and the box gu_td_kernel instantiations) against the CPU restatement
 tests/_boxes_oracle.py: step, step_device, rollout and td_run compared byte for byte -- rows, statistics, positions, WORDS, tables --,
-twins on engines without boxes that do not rest on the restatement, every reset path, every refusal, and the engine after the boxes
-have been taken away against one that never had any.
+twins on engines without boxes that do not rest on the restatement, every reset path, the library's own refusals, and the engine after
+the boxes have been taken away against one that never had any.  (The calls that have no box form: tests/test_gpu_overlay.py.)
 
 Shapes: N = 64 and 130 (three waves, the last one partial), T = 33 (two full action words and a tail of one step).  'b8': 8 x 8 with 5
 boxes, b * B = 30, planes in LDS, S = 64 (b = 6).  's65': 13 x 5, S = 65 (b = 7).  'open150': 150 x 150 with 2 boxes, b = 15, three
@@ -19,14 +19,14 @@ import pytest
 
 import griduniverse_amd as gua
 from griduniverse_amd.algorithms.temporal_difference import q_learning
-from griduniverse_amd.grid import box_plane, door_plane, fruit_plane, pack_boxes, wind_plane
+from griduniverse_amd.grid import box_plane, pack_boxes
 
 from . import _boxes_oracle as O
+from ._overlays import METHODS, same_state
 from ._tabular_cases import _eps, _same, _spec, code
 
 pytestmark = pytest.mark.gpu
 
-METHODS = {'q_learning': O.Q_LEARNING, 'sarsa': O.SARSA}
 UP, RIGHT, DOWN, LEFT = 0, 1, 2, 3
 T = 33
 
@@ -92,10 +92,7 @@ def _pair(name, N, seed, q0=None, v=5):
 
 
 def _same_state(vec, o):
-    st = vec.get_state()
-    assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'] != 0, o.state.done != 0)
-    assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
-    assert np.array_equal(vec.engine.get_boxes_state(), o.words)
+    same_state(vec, o, 'boxes')
     assert np.array_equal(vec.box_cells(), o.cells)
 
 
@@ -428,92 +425,26 @@ def test_every_reset_path_restores_the_boxes_of_the_envs_it_resets():
         vec.close()
 
 
-# ---- 7: refusals ----
-def test_calls_without_a_box_form_are_refused_and_a_refused_call_changes_nothing():
+# ---- 7: refusals (the calls without a box form: tests/test_gpu_overlay.py) ----
+def test_a_refused_plane_or_word_leaves_plane_words_and_q_tables_as_they_were():
     g, boxes, targets = _case('claim')
     N, S = 64, 16
     vec = gua.VecGridUniverse(N, template=_spec(g), seed=1)
     try:
         eng = vec.engine
         vec.reset()
-        eng.upload_actions(np.zeros((4, N), np.int32))
-        eng.vi_set(np.zeros(S), np.full((S, 4), 0.25))
-        eng.reserve_trajectory(8)
-        calls = {
-            'gu_step_graph': lambda: eng.step_graph(0, 4),
-            'gu_dyna_run': lambda: vec.dyna_run(5, planning_steps=2),
-            'gu_sweep_run': lambda: vec.sweep_run(5),
-            'gu_nstep_run': lambda: vec.nstep_run(5),
-            'gu_lambda_run': lambda: vec.lambda_run(5),
-            'gu_esarsa_run': lambda: vec.expected_sarsa_run(5),
-            'gu_double_run': lambda: vec.double_q_run(5),
-            'gu_ac_run': lambda: vec.actor_critic_run(5),
-            'gu_look_step_ahead': lambda: eng.look_step_ahead([4], [1]),
-            'gu_vi_run': lambda: eng.vi_run(0.9, 1e-3, 3),
-            'gu_vi_greedy': lambda: eng.vi_greedy(0.9),
-            'gu_shortest_paths': lambda: eng.shortest_paths(),
-        }
-        vec._ensure_model()
-        vec._ensure_queue()
-        vec._ensure_ac()
-        vec._ensure_pairs()
         vec.set_boxes(boxes, targets)
         plane = eng.get_boxes()[0]
         vec._ensure_q()
         vec.td_run(50, 'q_learning')
         words, q, rows = eng.get_boxes_state(), vec.q_table(), eng.td_rows
         assert rows == S << 4 and q.any()
-        for name, call in calls.items():
-            with pytest.raises(gua.GuError) as err:
-                call()
-            assert err.value.code == -6 and 'boxes' in str(err.value), name
-        refused = {'trail': lambda: eng.trail_enable(16), 'wind': lambda: eng.set_wind(wind_plane(4, 4, np.ones(4, int)), 0),
-                   'fruit': lambda: eng.set_fruit(fruit_plane(4, 4, [1, 2]), (1, 2, 3)), 'doors': lambda: eng.set_doors(door_plane(4, 4, {0: 1}, keys={0: 2})),
-                   'packed': lambda: eng.rollout(8, 'uniform', True, 'packed')}
-        for name, call in refused.items():
-            with pytest.raises(gua.GuError) as err:
-                call()
-            assert err.value.code == -6 and 'boxes' in str(err.value), name
         assert code(lambda: eng.set_boxes(O.plane_of(S, [12], [10]), 5)) == -1  # a box on the lava cell
         assert code(lambda: eng.set_boxes_state(np.array([12], np.uint32))) == -1
-        assert eng.get_wind() is None and eng.get_fruit() is None and eng.get_doors() is None
         assert np.array_equal(eng.get_boxes()[0], plane) and np.array_equal(eng.get_boxes_state(), words)
         assert eng.td_rows == rows and vec.q_table().tobytes() == q.tobytes()
-        vec.rollout(8, 'uniform', auto_reset=True)  # what reads rows or state only is unaffected
-        vec.sense(radius=1)
-        vec.set_boxes(None)
-        for name, call in calls.items():  # the same calls succeed once the boxes are gone
-            call()
-        for name, put, take in (('wind', refused['wind'], lambda: eng.set_wind(None)), ('fruit', refused['fruit'], lambda: eng.set_fruit(None)),
-                                ('doors', refused['doors'], lambda: eng.set_doors(None)), ('trail', refused['trail'], lambda: eng.trail_enable(0))):
-            put()
-            with pytest.raises(gua.GuError) as err:
-                eng.set_boxes(plane, 5)
-            assert err.value.code == -6 and name in str(err.value)
-            take()
-        assert eng.get_boxes() is None
-        eng.set_boxes(plane, 5)
-        eng.set_grid(_spec(g))  # a new grid drops the boxes
-        assert eng.get_boxes() is None and eng.stores()['overlay'] == 0
-        eng.look_step_ahead([4], [1])
     finally:
         vec.close()
-    grids = [_spec(g), _spec(g)]
-    multi = gua.VecGridUniverse(N, templates=grids, seed=1)
-    try:
-        with pytest.raises(gua.GuError) as err:  # boxes are a property of a single-grid engine
-            multi.engine.set_boxes(plane, 5)
-        assert err.value.code == -6 and 'boxes' in str(err.value)
-        multi.engine.set_grid(_spec(g))
-        multi.engine.set_boxes(plane, 5)
-        multi.engine.set_grids(grids)  # ... and several grids drop them
-        assert multi.engine.get_boxes() is None
-        multi.engine.set_grid(_spec(g))
-        multi.engine.set_boxes(plane, 5)
-        multi.engine.generate_mazes(2, 4, 4, 5)  # ... as device mazes do
-        assert multi.engine.get_boxes() is None
-    finally:
-        multi.close()
 
 
 # ---- 8: the slot ----

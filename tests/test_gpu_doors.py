@@ -1,7 +1,7 @@
 """Doors, keys and levers on the device (gu_set_doors; csrc/gu_doors.hip and the door gu_td_kernel instantiations) against the CPU
 restatement tests/_doors_oracle.py: step, rollout and td_run compared byte for byte -- rows, statistics, positions, masks, tables --,
-twins on engines without doors that do not rest on the restatement, every reset path, every refusal, and the engine after the doors
-have been taken away against one that never had any.
+twins on engines without doors that do not rest on the restatement, every reset path, and the engine after the doors have been
+taken away against one that never had any.  (The calls that have no door form: tests/test_gpu_overlay.py.)
 
 Every comparison with the restatement also asserts on the restatement's own log that the run met a bump on a closed door, a passage
 through an open one, a key pick-up, a lever pulled open and a lever pulled shut.  Env 0 sees to that: it is placed on the case's
@@ -13,16 +13,16 @@ import numpy as np
 import pytest
 
 import griduniverse_amd as gua
-from griduniverse_amd.algorithms.exploration import ucb_tables
 from griduniverse_amd.algorithms.temporal_difference import q_learning
-from griduniverse_amd.grid import door_plane, fruit_plane, wind_plane
+from griduniverse_amd.grid import door_plane
 
 from . import _doors_oracle as O
+from ._overlays import METHODS, same_state, scatter as _scatter
 from ._tabular_cases import GRIDS, _eps, _grid, _same, _spec
 
 pytestmark = pytest.mark.gpu
 
-METHODS = {'q_learning': O.Q_LEARNING, 'sarsa': O.SARSA}
+_same_state = functools.partial(same_state, kind='doors')
 UP, RIGHT, DOWN, LEFT = 0, 1, 2, 3
 
 
@@ -80,11 +80,6 @@ def _mappings(plane):
     return out
 
 
-def _scatter(g, N):
-    free = np.array(O.free_cells(g), np.int32)
-    return free[np.random.RandomState(N).randint(0, len(free), N)]
-
-
 def _place(name, vec, o, scatter=True):
     """Positions scattered over the free cells and masks drawn at random per env; env 0 on the anchor with all doors shut."""
     g, plane, anchor, _ = _case(name)
@@ -111,13 +106,6 @@ def _pair(name, N, seed, q0=None, scatter=True):
     assert np.array_equal(vec.reset(), o.reset())
     _place(name, vec, o, scatter)
     return vec, o
-
-
-def _same_state(vec, o):
-    st = vec.get_state()
-    assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'] != 0, o.state.done != 0)
-    assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
-    assert np.array_equal(vec.doors_open(), o.open)
 
 
 def _with_byte(plane, cell, byte):
@@ -512,124 +500,6 @@ def test_every_reset_path_clears_the_masks_of_the_envs_it_resets():
         assert np.array_equal(vec.reset(), o.reset()) and not vec.doors_open().any()
     finally:
         vec.close()
-
-
-# ---- 10: refusals ----
-def test_calls_without_a_door_form_are_refused_while_doors_are_set():
-    g, plane, _, _ = _case('maze11')
-    N, S = 64, 121
-    vec = gua.VecGridUniverse(N, template=_spec(g), seed=1)
-    free = [s for s in O.free_cells(g) if not plane[s]]
-    try:
-        eng = vec.engine
-        vec.reset()
-        eng.upload_actions(np.zeros((4, N), np.int32))
-        eng.vi_set(np.zeros(S), np.full((S, 4), 0.25))
-        eng.reserve_trajectory(8)
-        vec.set_exploration(*ucb_tables(1.0, 16))
-        vec.set_features(np.arange(S, dtype=np.int32)[:, None])
-        cdf = np.tile(np.array([0.25, 0.5, 0.75, 1.0]), (S, 1))
-        u = np.random.RandomState(0).rand(256)
-        start = g['starts'][0]
-        calls = {
-            'gu_step_graph': lambda: eng.step_graph(0, 4),
-            'gu_dyna_run': lambda: vec.dyna_run(5, planning_steps=2),
-            'gu_sweep_run': lambda: vec.sweep_run(5),
-            'gu_search_run': lambda: vec.search_run(3, simulations=1, depth=2),
-            'gu_explore_run': lambda: vec.explore_run(5),
-            'gu_mcts_run': lambda: vec.tree_search_run(3, simulations=1, tree_depth=2, depth=2),  # (one simulation: the pool _ensure_tree made)
-            'gu_nstep_run': lambda: vec.nstep_run(5),
-            'gu_lambda_run': lambda: vec.lambda_run(5),
-            'gu_ac_run': lambda: vec.actor_critic_run(5),
-            'gu_reinforce_run': lambda: vec.reinforce_run(5),
-            'gu_is_run': lambda: vec.off_policy_mc_run(5),
-            'gu_fa_run': lambda: vec.fa_run(5),
-            'gu_look_step_ahead': lambda: eng.look_step_ahead([start], [1]),
-            'gu_vi_sweep': lambda: eng.vi_sweep(0.9, 1),
-            'gu_vi_run': lambda: eng.vi_run(0.9, 1e-3, 3),
-            'gu_vi_eval_run': lambda: eng.vi_eval_run(0.9, 1e-3, 3),
-            'gu_vi_greedy': lambda: eng.vi_greedy(0.9),
-            'gu_vi_sweep_step': lambda: eng.vi_sweep_step(0.9),
-            'gu_vi_sweep_step_run': lambda: eng.vi_sweep_step_run(0.9, 2),
-            'gu_mc_walk_lengths': lambda: eng.mc_walk_lengths(u, 8, [start], 16, cdf),
-            'gu_mc_walk_episodes': lambda: eng.mc_walk_episodes(u, cdf, np.zeros(N, np.int64), np.full(N, start, np.int32), 16, 8),
-            'gu_shortest_paths': lambda: eng.shortest_paths(),
-        }
-        # the tables the learners need exist before the doors are set (the inits are not refused either way)
-        vec._ensure_q()
-        vec._ensure_model()
-        vec._ensure_queue()
-        vec._ensure_counts()
-        vec._ensure_tree()
-        vec._ensure_ac()
-        vec._ensure_is()
-        eng.set_doors(plane)
-        for name, call in calls.items():
-            with pytest.raises(gua.GuError) as err:
-                call()
-            assert err.value.code == -6 and 'doors' in str(err.value), name
-        with pytest.raises(gua.GuError) as err:  # packed rows
-            eng.rollout(8, 'uniform', True, 'packed')
-        assert err.value.code == -6 and 'doors' in str(err.value)
-        with pytest.raises(gua.GuError) as err:  # the trail refuses while doors are set
-            eng.trail_enable(16)
-        assert err.value.code == -6 and 'doors' in str(err.value)
-        with pytest.raises(gua.GuError) as err:  # doors, then wind
-            eng.set_wind(wind_plane(11, 11, np.ones(11, int)), 0)
-        assert err.value.code == -6 and 'doors' in str(err.value)
-        with pytest.raises(gua.GuError) as err:  # doors, then fruit
-            eng.set_fruit(fruit_plane(11, 11, free[:2]), (1, 2, 3))
-        assert err.value.code == -6 and 'doors' in str(err.value)
-        assert eng.get_wind() is None and eng.get_fruit() is None and np.array_equal(eng.get_doors(), plane)
-        # what reads rows or state only is unaffected
-        vec.rollout(8, 'uniform', auto_reset=True)
-        eng.mc_evaluate(8, np.full(N, start, np.int32), 0.9 ** np.arange(8), np.ones(8, bool))
-        eng.vi_get()
-        vec.sense(radius=1)
-        vec.get_state()
-        vec.set_doors(None)
-        vec._ensure_tree()
-        for name, call in calls.items():  # the same calls succeed once the doors are gone
-            call()
-        eng.set_wind(wind_plane(11, 11, np.ones(11, int)), 0)  # wind, then doors
-        with pytest.raises(gua.GuError) as err:
-            eng.set_doors(plane)
-        assert err.value.code == -6 and 'wind' in str(err.value)
-        eng.set_wind(None)
-        eng.set_fruit(fruit_plane(11, 11, free[:2]), (1, 2, 3))  # fruit, then doors
-        with pytest.raises(gua.GuError) as err:
-            eng.set_doors(plane)
-        assert err.value.code == -6 and 'fruit' in str(err.value)
-        eng.set_fruit(None)
-        eng.trail_enable(16)  # the trail, then doors
-        with pytest.raises(gua.GuError) as err:
-            eng.set_doors(plane)
-        assert err.value.code == -6 and 'trail' in str(err.value)
-        eng.trail_enable(0)
-        assert eng.get_doors() is None  # (each refused call left the engine as it was)
-        eng.set_doors(plane)
-        assert eng.get_doors() is not None
-        eng.set_grid(_spec(g))  # a new grid drops the doors
-        assert eng.get_doors() is None
-        eng.look_step_ahead([start], [1])
-    finally:
-        vec.close()
-    grids = [_spec(g), _spec(g)]
-    multi = gua.VecGridUniverse(N, templates=grids, seed=1)
-    try:
-        with pytest.raises(gua.GuError) as err:  # doors are a property of a single-grid engine
-            multi.engine.set_doors(plane)
-        assert err.value.code == -6 and 'doors' in str(err.value)
-        multi.engine.set_grid(_spec(g))
-        multi.engine.set_doors(plane)
-        multi.engine.set_grids(grids)  # ... and several grids drop them
-        assert multi.engine.get_doors() is None
-        multi.engine.set_grid(_spec(g))
-        multi.engine.set_doors(plane)
-        multi.engine.generate_mazes(2, 11, 11, 5)  # ... as device mazes do
-        assert multi.engine.get_doors() is None
-    finally:
-        multi.close()
 
 
 # ---- 11: clearing the doors ----

@@ -1,22 +1,23 @@
 """Fruit on the device (gu_set_fruit; csrc/gu_fruit.hip and the fruit gu_td_kernel instantiations) against the CPU restatement
 tests/_fruit_oracle.py: step, rollout and td_run compared byte for byte -- rows, statistics, positions, masks, tables --, every reset
-path, every refusal, and the engine after the fruit has been taken away against one that never had any."""
+path, and the engine after the fruit has been taken away against one that never had any.  (The calls that
+have no fruit form: tests/test_gpu_overlay.py.)"""
 import functools
 
 import numpy as np
 import pytest
 
 import griduniverse_amd as gua
-from griduniverse_amd.algorithms.exploration import ucb_tables
 from griduniverse_amd.algorithms.temporal_difference import q_learning
-from griduniverse_amd.grid import fruit_plane, wind_plane
+from griduniverse_amd.grid import fruit_plane
 
 from . import _fruit_oracle as O
+from ._overlays import METHODS, policy_table as _policy_table, same_state, scatter as _scatter
 from ._tabular_cases import GRIDS, _eps, _grid, _same, _spec
 
 pytestmark = pytest.mark.gpu
 
-METHODS = {'q_learning': O.Q_LEARNING, 'sarsa': O.SARSA}
+_same_state = functools.partial(same_state, kind='fruit')
 VALUES = (3, -7, 16)
 
 
@@ -44,12 +45,6 @@ def _case(name):
     return g, fruit_plane(8, 8, list(range(1, 33)), [1 + k % 3 for k in range(32)])
 
 
-def _scatter(g, N):
-    taken = set(g['walls']) | set(g['goals']) | set(g['lava'])
-    free = np.array([s for s in range(g['W'] * g['H']) if s not in taken], np.int32)
-    return free[np.random.RandomState(N).randint(0, len(free), N)]
-
-
 def _pair(name, N, seed, q0=None, scatter=True, values=VALUES):
     """A batch of N envs on the case's grid under its fruit and the oracle of it, both reset (and then scattered over the grid)."""
     g, plane = _case(name)
@@ -64,13 +59,6 @@ def _pair(name, N, seed, q0=None, scatter=True, values=VALUES):
         vec.set_state(pos=_scatter(g, N))
         o.state.pos[:] = _scatter(g, N)
     return vec, o
-
-
-def _same_state(vec, o):
-    st = vec.get_state()
-    assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'] != 0, o.state.done != 0)
-    assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
-    assert np.array_equal(vec.fruit_eaten(), o.eaten)
 
 
 # ---- 1: round trip and errors ----
@@ -181,12 +169,6 @@ def test_step_and_step_device_equal_the_oracle(case, auto, N):
 
 
 # ---- 3: rollout ----
-def _policy_table(S):
-    pi = np.random.RandomState(1).dirichlet(np.ones(4), S)
-    pi[::7] = np.eye(4)[np.arange(len(pi[::7])) % 4]  # one-hot rows: thresholds that no word reaches
-    return pi
-
-
 @pytest.mark.parametrize('N', [200, 1])
 @pytest.mark.parametrize('auto', [True, False])
 @pytest.mark.parametrize('policy', ['uniform', 'stream', 'greedy', 'sample'])
@@ -362,113 +344,6 @@ def test_every_reset_path_clears_the_masks_of_the_envs_it_resets():
         assert np.array_equal(vec.reset(), o.reset()) and not vec.fruit_eaten().any()
     finally:
         vec.close()
-
-
-# ---- 9: refusals ----
-def test_calls_without_a_fruit_form_are_refused_while_fruit_is_set():
-    g, plane = _case('maze11')
-    N, S = 64, 121
-    vec = gua.VecGridUniverse(N, template=_spec(g), seed=1)
-    try:
-        eng = vec.engine
-        vec.reset()
-        eng.upload_actions(np.zeros((4, N), np.int32))
-        eng.vi_set(np.zeros(S), np.full((S, 4), 0.25))
-        eng.reserve_trajectory(8)
-        vec.set_exploration(*ucb_tables(1.0, 16))
-        vec.set_features(np.arange(S, dtype=np.int32)[:, None])
-        cdf = np.tile(np.array([0.25, 0.5, 0.75, 1.0]), (S, 1))
-        u = np.random.RandomState(0).rand(256)
-        start = g['starts'][0]
-        calls = {
-            'gu_step_graph': lambda: eng.step_graph(0, 4),
-            'gu_dyna_run': lambda: vec.dyna_run(5, planning_steps=2),
-            'gu_sweep_run': lambda: vec.sweep_run(5),
-            'gu_search_run': lambda: vec.search_run(3, simulations=1, depth=2),
-            'gu_explore_run': lambda: vec.explore_run(5),
-            'gu_mcts_run': lambda: vec.tree_search_run(3, simulations=1, tree_depth=2, depth=2),  # (one simulation: the pool _ensure_tree made)
-            'gu_nstep_run': lambda: vec.nstep_run(5),
-            'gu_lambda_run': lambda: vec.lambda_run(5),
-            'gu_ac_run': lambda: vec.actor_critic_run(5),
-            'gu_reinforce_run': lambda: vec.reinforce_run(5),
-            'gu_is_run': lambda: vec.off_policy_mc_run(5),
-            'gu_fa_run': lambda: vec.fa_run(5),
-            'gu_look_step_ahead': lambda: eng.look_step_ahead([start], [1]),
-            'gu_vi_sweep': lambda: eng.vi_sweep(0.9, 1),
-            'gu_vi_run': lambda: eng.vi_run(0.9, 1e-3, 3),
-            'gu_vi_eval_run': lambda: eng.vi_eval_run(0.9, 1e-3, 3),
-            'gu_vi_greedy': lambda: eng.vi_greedy(0.9),
-            'gu_vi_sweep_step': lambda: eng.vi_sweep_step(0.9),
-            'gu_vi_sweep_step_run': lambda: eng.vi_sweep_step_run(0.9, 2),
-            'gu_mc_walk_lengths': lambda: eng.mc_walk_lengths(u, 8, [start], 16, cdf),
-            'gu_mc_walk_episodes': lambda: eng.mc_walk_episodes(u, cdf, np.zeros(N, np.int64), np.full(N, start, np.int32), 16, 8),
-            'gu_shortest_paths': lambda: eng.shortest_paths(),
-        }
-        # the tables the learners need exist before the fruit is set (the inits are not refused either way)
-        vec._ensure_q()
-        vec._ensure_model()
-        vec._ensure_queue()
-        vec._ensure_counts()
-        vec._ensure_tree()
-        vec._ensure_ac()
-        vec._ensure_is()
-        eng.set_fruit(plane, VALUES)
-        for name, call in calls.items():
-            with pytest.raises(gua.GuError) as err:
-                call()
-            assert err.value.code == -6 and 'fruit' in str(err.value), name
-        with pytest.raises(gua.GuError) as err:  # packed rows
-            eng.rollout(8, 'uniform', True, 'packed')
-        assert err.value.code == -6 and 'fruit' in str(err.value)
-        with pytest.raises(gua.GuError) as err:  # the trail refuses while fruit is set
-            eng.trail_enable(16)
-        assert err.value.code == -6 and 'fruit' in str(err.value)
-        with pytest.raises(gua.GuError) as err:  # fruit, then wind
-            eng.set_wind(wind_plane(11, 11, np.ones(11, int)), 0)
-        assert err.value.code == -6 and 'fruit' in str(err.value)
-        # what reads rows or state only is unaffected
-        vec.rollout(8, 'uniform', auto_reset=True)
-        eng.mc_evaluate(8, np.full(N, start, np.int32), 0.9 ** np.arange(8), np.ones(8, bool))
-        eng.vi_get()
-        vec.sense(radius=1)
-        vec.get_state()
-        vec.set_fruit(None)
-        vec._ensure_tree()
-        for name, call in calls.items():  # the same calls succeed once the fruit is gone
-            call()
-        eng.set_wind(wind_plane(11, 11, np.ones(11, int)), 0)  # wind, then fruit
-        with pytest.raises(gua.GuError) as err:
-            eng.set_fruit(plane, VALUES)
-        assert err.value.code == -6 and 'wind' in str(err.value)
-        eng.set_wind(None)
-        eng.trail_enable(16)  # the trail, then fruit
-        with pytest.raises(gua.GuError) as err:
-            eng.set_fruit(plane, VALUES)
-        assert err.value.code == -6 and 'trail' in str(err.value)
-        eng.trail_enable(0)
-        eng.set_fruit(plane, VALUES)
-        assert eng.get_fruit() is not None
-        eng.set_grid(_spec(g))  # a new grid drops the fruit
-        assert eng.get_fruit() is None
-        eng.look_step_ahead([start], [1])
-    finally:
-        vec.close()
-    grids = [_spec(g), _spec(g)]
-    multi = gua.VecGridUniverse(N, templates=grids, seed=1)
-    try:
-        with pytest.raises(gua.GuError) as err:  # fruit is a property of a single-grid engine
-            multi.engine.set_fruit(plane, VALUES)
-        assert err.value.code == -6 and 'fruit' in str(err.value)
-        multi.engine.set_grid(_spec(g))
-        multi.engine.set_fruit(plane, VALUES)
-        multi.engine.set_grids(grids)  # ... and several grids drop it
-        assert multi.engine.get_fruit() is None
-        multi.engine.set_grid(_spec(g))
-        multi.engine.set_fruit(plane, VALUES)
-        multi.engine.generate_mazes(2, 11, 11, 5)  # ... as device mazes do
-        assert multi.engine.get_fruit() is None
-    finally:
-        multi.close()
 
 
 # ---- 10: clearing fruit ----

@@ -18,12 +18,11 @@ from griduniverse_amd.grid import GridSpec
 
 from . import _overlay_starts as S
 from ._overlay_starts import IDS, KINDS, N, POLICIES, SEED, T
+from ._overlays import METHODS, overlay, same_state as _same_state
 from ._tabular_cases import _eps, _same, code, counts_near_2_32
-from ._td_oracle import Q_LEARNING, SARSA
 
 pytestmark = pytest.mark.gpu
 
-METHODS = {'q_learning': Q_LEARNING, 'sarsa': SARSA}
 GRIDS = ('starts8', 'open150')
 ALPHA, GAMMA, EPS = 0.25, 0.9, 0.3
 
@@ -34,20 +33,7 @@ def _spec(name):
 
 
 def _install(vec, kind, name):
-    eng, plane = vec.engine, S.plane(kind, name)
-    if kind in ('wind', 'gusts'):
-        eng.set_wind(plane, S.WO.GUST_THIRDS if kind == 'gusts' else 0)
-    elif kind == 'fruit':
-        eng.set_fruit(plane, S.FRUIT_VALUES)
-    elif kind == 'doors':
-        eng.set_doors(plane)
-    else:
-        eng.set_boxes(plane, S.ON_TARGET)
-
-
-def _masks(vec, kind):
-    eng = vec.engine
-    return {'fruit': eng.get_fruit_state, 'doors': eng.get_doors_state, 'boxes': eng.get_boxes_state}.get(kind, lambda: None)()
+    overlay(kind).install(vec.engine, S.plane(kind, name), *S.extra(kind))
 
 
 def _again(vec, kind, name, env_id0, q0=None):
@@ -69,14 +55,6 @@ def _pair(kind, name, env_id0, q0=None):
     except BaseException:
         vec.close()
         raise
-
-
-def _same_state(vec, o, kind):
-    st = vec.get_state()
-    assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'] != 0, o.state.done != 0)
-    assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
-    if kind not in ('wind', 'gusts'):
-        assert np.array_equal(_masks(vec, kind), S.masks_of(o, kind))
 
 
 def _same_tables(vec, o):

@@ -1,6 +1,6 @@
 """Wind on the device (gu_set_wind; csrc/gu_wind.hip and the windy gu_td_kernel instantiations) against the CPU restatement
-tests/_wind_oracle.py: step, rollout and td_run compared byte for byte, the calm plane against the calm engine, and every call
-that has no windy form refused while wind is set."""
+tests/_wind_oracle.py: step, rollout and td_run compared byte for byte, and the calm plane against the calm engine.  (The calls
+that have no windy form: tests/test_gpu_overlay.py.)"""
 import functools
 
 import numpy as np
@@ -8,7 +8,6 @@ import pytest
 
 import griduniverse_amd as gua
 from griduniverse_amd import _lib
-from griduniverse_amd.algorithms.exploration import ucb_tables
 from griduniverse_amd.algorithms.temporal_difference import q_learning
 from griduniverse_amd.grid import wind_plane
 from oracle import c_oracle as C
@@ -16,12 +15,13 @@ from oracle import c_oracle as C
 from . import _golden as G
 from . import _td_oracle as TD
 from . import _wind_oracle as O
+from ._overlays import METHODS, policy_table as _policy_table, same_state, scatter as _scatter
 from ._tabular_cases import GRIDS, _eps, _grid, _same, _spec, counts_near_2_32
 
 pytestmark = pytest.mark.gpu
 
 GUSTS = [0, O.GUST_THIRDS]
-METHODS = {'q_learning': O.Q_LEARNING, 'sarsa': O.SARSA}
+_same_state = functools.partial(same_state, kind='wind')
 
 
 @functools.lru_cache(maxsize=None)
@@ -48,14 +48,6 @@ def _case(name):
 CASES = ['book', 'maze11', 'open150']
 
 
-def _scatter(g, N):
-    """N cells of the grid that are neither wall nor terminal: where the tests put the envs, so that a batch with one start cell
-    (and a deterministic policy) still walks the whole grid."""
-    taken = set(g['walls']) | set(g['goals']) | set(g['lava'])
-    free = np.array([s for s in range(g['W'] * g['H']) if s not in taken], np.int32)
-    return free[np.random.RandomState(N).randint(0, len(free), N)]
-
-
 def _pair(name, N, seed, gust_q16, q0=None, wind=True):
     """A batch of N envs on the case's grid under its wind and the oracle of it, both reset and then scattered over the grid."""
     g, plane = _case(name)
@@ -69,12 +61,6 @@ def _pair(name, N, seed, gust_q16, q0=None, wind=True):
     vec.set_state(pos=_scatter(g, N))
     o.state.pos[:] = _scatter(g, N)
     return vec, o
-
-
-def _same_state(vec, o):
-    st = vec.get_state()
-    assert np.array_equal(st['pos'], o.state.pos) and np.array_equal(st['done'] != 0, o.state.done != 0)
-    assert np.array_equal(st['episode'], o.state.episode) and np.array_equal(st['tcount'], o.state.tcount)
 
 
 def test_set_wind_and_wind_round_trip():
@@ -136,12 +122,6 @@ def test_step_and_step_device_equal_the_oracle(case, auto, gust):
         _same_state(vec, o2)
     finally:
         vec.close()
-
-
-def _policy_table(S):
-    pi = np.random.RandomState(1).dirichlet(np.ones(4), S)
-    pi[::7] = np.eye(4)[np.arange(len(pi[::7])) % 4]  # one-hot rows: thresholds that no word reaches
-    return pi
 
 
 @pytest.mark.parametrize('gust', GUSTS)
@@ -297,99 +277,6 @@ def test_a_calmed_engine_takes_the_original_kernels_again(gu_option):
         assert all(np.array_equal(tr[k][:, :2048], want[k]) for k in ('obs', 'reward', 'done'))
     finally:
         vec.close()
-
-
-def test_calls_without_a_windy_form_are_refused_while_wind_is_set():
-    g, plane = _case('maze11')
-    N, S = 64, 121
-    vec = gua.VecGridUniverse(N, template=_spec(g), seed=1)
-    try:
-        eng = vec.engine
-        vec.reset()
-        eng.upload_actions(np.zeros((4, N), np.int32))
-        eng.vi_set(np.zeros(S), np.full((S, 4), 0.25))
-        eng.reserve_trajectory(8)
-        vec.set_exploration(*ucb_tables(1.0, 16))
-        vec.set_features(np.arange(S, dtype=np.int32)[:, None])
-        cdf = np.tile(np.array([0.25, 0.5, 0.75, 1.0]), (S, 1))
-        u = np.random.RandomState(0).rand(256)
-        start = g['starts'][0]
-        calls = {
-            'gu_step_graph': lambda: eng.step_graph(0, 4),
-            'gu_dyna_run': lambda: vec.dyna_run(5, planning_steps=2),
-            'gu_search_run': lambda: vec.search_run(3, simulations=1, depth=2),
-            'gu_explore_run': lambda: vec.explore_run(5),
-            'gu_mcts_run': lambda: vec.tree_search_run(3, simulations=2, tree_depth=2, depth=2),
-            'gu_nstep_run': lambda: vec.nstep_run(5),
-            'gu_lambda_run': lambda: vec.lambda_run(5),
-            'gu_ac_run': lambda: vec.actor_critic_run(5),
-            'gu_reinforce_run': lambda: vec.reinforce_run(5),
-            'gu_is_run': lambda: vec.off_policy_mc_run(5),
-            'gu_fa_run': lambda: vec.fa_run(5),
-            'gu_look_step_ahead': lambda: eng.look_step_ahead([start], [1]),
-            'gu_vi_sweep': lambda: eng.vi_sweep(0.9, 1),
-            'gu_vi_run': lambda: eng.vi_run(0.9, 1e-3, 3),
-            'gu_vi_eval_run': lambda: eng.vi_eval_run(0.9, 1e-3, 3),
-            'gu_vi_greedy': lambda: eng.vi_greedy(0.9),
-            'gu_vi_sweep_step': lambda: eng.vi_sweep_step(0.9),
-            'gu_vi_sweep_step_run': lambda: eng.vi_sweep_step_run(0.9, 2),
-            'gu_mc_walk_lengths': lambda: eng.mc_walk_lengths(u, 8, [start], 16, cdf),
-            'gu_mc_walk_episodes': lambda: eng.mc_walk_episodes(u, cdf, np.zeros(N, np.int64), np.full(N, start, np.int32), 16, 8),
-            'gu_shortest_paths': lambda: eng.shortest_paths(),
-        }
-        # the tables the learners need exist before the wind is set (the inits are not refused either way)
-        vec._ensure_q()
-        vec._ensure_model()
-        vec._ensure_counts()
-        vec._ensure_tree()
-        vec._ensure_ac()
-        vec._ensure_is()
-        eng.set_wind(plane, O.GUST_THIRDS)
-        for name, call in calls.items():
-            with pytest.raises(gua.GuError) as err:
-                call()
-            assert err.value.code == -6 and 'wind' in str(err.value), name
-        with pytest.raises(gua.GuError) as err:  # the trail refuses while wind is set
-            eng.trail_enable(16)
-        assert err.value.code == -6 and 'wind' in str(err.value)
-        # what reads rows or state only is unaffected
-        vec.rollout(8, 'uniform', auto_reset=True)
-        eng.mc_evaluate(8, np.full(N, start, np.int32), 0.9 ** np.arange(8), np.ones(8, bool))
-        eng.vi_get()
-        vec.sense(radius=1)
-        vec.get_state()
-        vec.set_wind(None)
-        for name, call in calls.items():  # the same calls succeed once the wind is gone
-            call()
-        # wind refuses while the trail is on
-        eng.trail_enable(16)
-        with pytest.raises(gua.GuError) as err:
-            eng.set_wind(plane, 0)
-        assert err.value.code == -6 and 'trail' in str(err.value)
-        eng.trail_enable(0)
-        eng.set_wind(plane, 0)
-        assert eng.get_wind() is not None
-        eng.set_grid(_spec(g))  # a new grid drops the wind
-        assert eng.get_wind() is None
-        eng.look_step_ahead([start], [1])
-    finally:
-        vec.close()
-    grids = [_spec(g), _spec(g)]
-    multi = gua.VecGridUniverse(N, templates=grids, seed=1)
-    try:
-        with pytest.raises(gua.GuError) as err:  # wind is a property of a single-grid engine
-            multi.engine.set_wind(plane, 0)
-        assert err.value.code == -6 and 'wind' in str(err.value)
-        multi.engine.set_grid(_spec(g))
-        multi.engine.set_wind(plane, 0)
-        multi.engine.set_grids(grids)  # ... and several grids drop it
-        assert multi.engine.get_wind() is None
-        multi.engine.set_grid(_spec(g))
-        multi.engine.set_wind(plane, 0)
-        multi.engine.generate_mazes(2, 11, 11, 5)  # ... as device mazes do
-        assert multi.engine.get_wind() is None
-    finally:
-        multi.close()
 
 
 def _greedy_path(grid, wind, q, start, limit):
