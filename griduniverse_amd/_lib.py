@@ -85,6 +85,10 @@ SIGNATURES = {
     'gu_get_boxes': [_vp, _vp, _vp, _vp, _vp],
     'gu_get_boxes_state': [_vp, _i64, _i64, _vp],
     'gu_set_boxes_state': [_vp, _i64, _i64, _vp],
+    'gu_set_errands': [_vp, _vp, _i32, _vp, _vp],
+    'gu_get_errands': [_vp, _vp, _vp, _vp, _vp, _vp],
+    'gu_get_errands_state': [_vp, _i64, _i64, _vp],
+    'gu_set_errands_state': [_vp, _i64, _i64, _vp],
     'gu_seed': [_vp, _u64],
     'gu_reset': [_vp, _vp, _vp, _vp],
     'gu_reset_done': [_vp],

@@ -19,7 +19,7 @@ from .. import _lib
 from ._batch import _CHUNK, learn, need_learners, unit
 
 
-def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind=None, gust=0.0, fruit=None, doors=None, boxes=None):
+def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind=None, gust=0.0, fruit=None, doors=None, boxes=None, errands=None):
     need_learners(num_learners)
     unit('epsilon', epsilon)
     unit('gust', gust)
@@ -38,6 +38,11 @@ def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, s
             raise ValueError('boxes exclude wind, fruit and doors')
         if not isinstance(boxes, dict) or not {'boxes', 'targets'} <= set(boxes) or set(boxes) - {'boxes', 'targets', 'on_target'}:
             raise ValueError('boxes must be dict(boxes=, targets=, on_target=)')
+    if errands is not None:
+        if wind is not None or fruit is not None or doors is not None or boxes is not None:
+            raise ValueError('errands exclude wind, fruit, doors and boxes')
+        if not isinstance(errands, dict) or not {'cells', 'instructions'} <= set(errands) or set(errands) - {'cells', 'kinds', 'instructions', 'right', 'wrong', 'finish'}:
+            raise ValueError('errands must be dict(cells=, kinds=, instructions=, right=, wrong=, finish=)')
 
     def prepare(vec):  # (the tables have S << F rows under fruit and S << D under doors: the overlay goes on before them)
         if wind is not None:
@@ -49,12 +54,15 @@ def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, s
             vec.set_doors(doors['doors'], doors.get('keys'), doors.get('levers'))
         if boxes is not None:
             vec.set_boxes(boxes['boxes'], boxes['targets'], boxes.get('on_target', 5))
+        if errands is not None:
+            vec.set_errands(**errands)
         vec._ensure_q(q0)
 
     return learn(env, num_learners, seed, num_steps, _CHUNK, prepare, lambda vec, T: vec.td_run(T, method, alpha, discount_factor, epsilon))
 
 
-def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None, boxes=None):
+def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None, boxes=None,
+               errands=None):
     """Epsilon-greedy Q-learning, `num_steps` env steps per learner (episodes restart at a start cell when they end).  Returns
     Q float64[S][4], or [L][S][4] for L = num_learners > 1.  `wind`: a strength array ([H, W], or [W] per column; blowing up) or a
     (strength, direction) pair as VecGridUniverse.set_wind takes them, gusting with probability `gust`; None: the calm grid.  `fruit`: (cells, kinds, values)
@@ -62,13 +70,15 @@ def q_learning(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num
     eaten fruit; not together with `wind`.  `doors`: dict(doors=, keys=, levers=) as VecGridUniverse.set_doors takes them -- the result
     then has S << D rows, row open * S + s for cell s under the mask `open` of open slots; not together with `wind` or `fruit`.  `boxes`: dict(boxes=, targets=, on_target=)
     as VecGridUniverse.set_boxes takes them -- the result then has S << (b * B) rows, row word * S + s for cell s under the word
-    grid.pack_boxes(S, cells) of the boxes' cells; not together with `wind`, `fruit` or `doors`."""
-    return _td('q_learning', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit, doors, boxes)
+    grid.pack_boxes(S, cells) of the boxes' cells; not together with `wind`, `fruit` or `doors`.  `errands`: dict(cells=, kinds=,
+    instructions=, right=, wrong=, finish=) as VecGridUniverse.set_errands takes them -- the result then has S << bits rows, row word * S + s
+    for cell s under the word eaten | progress << F | instruction << (F + pb) (grid.errand_fields); not together with the other four."""
+    return _td('q_learning', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit, doors, boxes, errands)
 
 
-def sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None, boxes=None):
+def sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0, wind=None, gust=0.0, fruit=None, doors=None, boxes=None, errands=None):
     """Epsilon-greedy SARSA; arguments and result as `q_learning`."""
-    return _td('sarsa', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit, doors, boxes)
+    return _td('sarsa', env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind, gust, fruit, doors, boxes, errands)
 
 
 def expected_sarsa(env, num_steps, alpha=0.1, discount_factor=0.99, epsilon=0.1, num_learners=1, seed=0, q0=0.0):

@@ -114,7 +114,7 @@ struct GuPaceArgs {
     uint32_t adapt;         // 1: the slow loop moves the rule's aim (dec_q) by what the launches' start-to-start time says
 };
 
-enum { GU_OVERLAY_NONE = 0, GU_OVERLAY_WIND, GU_OVERLAY_FRUIT, GU_OVERLAY_DOORS, GU_OVERLAY_BOXES };  // gu_engine::overlay
+enum { GU_OVERLAY_NONE = 0, GU_OVERLAY_WIND, GU_OVERLAY_FRUIT, GU_OVERLAY_DOORS, GU_OVERLAY_BOXES, GU_OVERLAY_ERRANDS };  // gu_engine::overlay
 
 // What a learner carries from one launch to the next (gu_engine::carry; DESIGN.md "What the engine carries between calls"): the last
 // call that touched the envs was a launch of `owner` under `key` -- gu_td_run's and gu_fa_run's SARSA action (key 0), gu_nstep_run's
@@ -147,17 +147,19 @@ struct gu_engine {
     int32_t cell_bytes = 0;          // S rounded up to 16
     uint8_t *d_cell = nullptr;       // absorbing-aware planes    [2 * cell_bytes]
     uint8_t *d_cell_raw = nullptr;   // care_about_terminal=False [2 * cell_bytes]
-    // the overlay slot (gu_overlay.hip; DESIGN.md "Overlays"): wind, fruit, doors or boxes -- a third byte plane behind the two cell
-    // planes of a single-grid engine and, for fruit, doors and boxes, one uint32 word per env; at most one of them at a time
+    // the overlay slot (gu_overlay.hip; DESIGN.md "Overlays"): wind, fruit, doors, boxes or errands -- a third byte plane behind the two cell
+    // planes of a single-grid engine and, for all but wind, one uint32 word per env; at most one of them at a time
     int overlay = GU_OVERLAY_NONE;       // which one is set (GU_OVERLAY_*)
     uint8_t *d_overlay_cell = nullptr;   // [3 * cell_bytes] the planes of d_cell with the overlay's plane behind them -- what its kernels
                                          // stage in one piece; nullptr: none
     uint32_t *d_overlay_mask = nullptr;  // [N] fruit: the envs' masks of eaten fruit, doors: of open slots (bit = slot), boxes: the boxes'
-                                         // cells (b bits each); set to overlay_init by every reset; nullptr under wind
-    int32_t overlay_bits = 0;            // bits of a mask in use: F fruit cells (1 .. 32), D door slots (1 .. 8), b * B under boxes, 0
-                                         // under wind; gu_td_run's tables have S << overlay_bits rows
+                                         // cells (b bits each), errands: eaten | progress | instruction (gu_map.hpp); set to overlay_init by every reset (errands: their
+                                         // own reset kernel draws the instruction); nullptr under wind
+    int32_t overlay_bits = 0;            // bits of a mask in use: F fruit cells (1 .. 32), D door slots (1 .. 8), b * B under boxes, F + pb + ib
+                                         // under errands, 0 under wind; gu_td_run's tables have S << overlay_bits rows
     uint32_t overlay_param = 0;          // wind: gust_q16, the gust probability in 1/65536; fruit: the three kinds' values as int8 bytes
-                                         // 1 .. 3 (byte 0 zero), as the kernels take them; boxes: GU_BOX_PARAM (gu_map.hpp)
+                                         // 1 .. 3 (byte 0 zero), as the kernels take them; boxes: GU_BOX_PARAM (gu_map.hpp); errands: the instructions, one byte each
+    uint32_t overlay_param2 = 0;         // errands: GU_ERRAND_PARAM2 (gu_map.hpp) -- the pay and the word's field widths; 0 for every other kind
     uint32_t overlay_init = 0;           // the mask value at reset: 0 for fruit and doors, the initial boxes' cells under boxes
     std::vector<uint8_t> box_flags;      // boxes: the grid's flags plane [S] on the host, kept by gu_set_boxes for gu_set_boxes_state's checks
     int32_t fruit_value[3] = {0, 0, 0};  // ... and as gu_get_fruit hands them back
@@ -418,14 +420,15 @@ int gu_ensure_scratch(gu_engine *h, size_t bytes);
 #define GU_NEED_GRID(h) GU_REQUIRE((h)->has_grid, GU_ERR_STATE, "no grid set: call gu_set_grid first")
 
 // What the messages call an overlay, and how they tell the caller that it is set and which call takes it away (index: GU_OVERLAY_*)
-static const char *const GU_OVERLAY_NAME[5] = {"none", "wind", "fruit", "doors", "boxes"};
-static const char *const GU_OVERLAY_IS_SET[5] = {"", "the engine has wind set (gu_set_wind; NULL calms it again)",
+static const char *const GU_OVERLAY_NAME[6] = {"none", "wind", "fruit", "doors", "boxes", "errands"};
+static const char *const GU_OVERLAY_IS_SET[6] = {"", "the engine has wind set (gu_set_wind; NULL calms it again)",
                                                  "the engine has fruit set (gu_set_fruit; NULL takes it away again)",
                                                  "the engine has doors set (gu_set_doors; NULL takes them away again)",
-                                                 "the engine has boxes set (gu_set_boxes; NULL takes them away again)"};
+                                                 "the engine has boxes set (gu_set_boxes; NULL takes them away again)",
+                                                 "the engine has errands set (gu_set_errands; NULL takes them away again)"};
 
 // every call that moves envs or reads the move or reward rule and has no form for overlays refuses while one is set (include/gu.h:
-// gu_set_wind, gu_set_fruit, gu_set_doors, gu_set_boxes)
+// gu_set_wind, gu_set_fruit, gu_set_doors, gu_set_boxes, gu_set_errands)
 #define GU_NO_OVERLAY(h, fn) \
     GU_REQUIRE(!(h)->overlay, GU_ERR_UNSUPPORTED, "%s knows no %s: %s", fn, GU_OVERLAY_NAME[(h)->overlay], GU_OVERLAY_IS_SET[(h)->overlay])
 
@@ -589,9 +592,9 @@ struct OverlayRolloutArgs;
 // GU_ERR_UNSUPPORTED unless the engine can take an overlay of `kind`: one grid, no trail, no overlay of another kind
 int gu_overlay_admits(gu_engine *h, int kind);
 // Puts `kind` into the slot: `plane` [S] is the feature's plane, validated by its entry point, `bits` the mask bits in use (0: no
-// masks), `param` the kernels' parameter word, `init` the value every mask has now and after every reset.  plane == nullptr takes the
-// overlay away.  A refused call leaves the engine as it was.
-int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bits, uint32_t param, uint32_t init = 0u);
+// masks), `param` the kernels' parameter word, `init` the value every mask has now and after every reset, `param2` the second parameter word (errands).
+// plane == nullptr takes the overlay away.  A refused call leaves the engine as it was.
+int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bits, uint32_t param, uint32_t init = 0u, uint32_t param2 = 0u);
 void gu_overlay_free(gu_engine *h);
 int gu_overlay_get_plane(gu_engine *h, int kind, uint8_t *plane);  // [S]; zeros while `kind` is not set
 int gu_overlay_get_masks(gu_engine *h, int kind, int64_t env0, int64_t n, uint32_t *masks, const char *what);
@@ -602,15 +605,19 @@ int gu_overlay_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t 
                            uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
 void gu_overlay_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &r);  // (the launch alone: gu_launch_rollout checks and completes it)
 // ... and what each feature keeps of them: the ladder from the launch's shape to its kernel's instantiation (gu_wind.hip, gu_fruit.hip, gu_doors.hip,
-// gu_boxes.hip)
+// gu_boxes.hip, gu_errands.hip)
 void gu_wind_step(gu_engine *h, bool lds, const OverlayStepArgs &a);
 void gu_fruit_step(gu_engine *h, bool lds, const OverlayStepArgs &a);
 void gu_doors_step(gu_engine *h, bool lds, const OverlayStepArgs &a);
 void gu_boxes_step(gu_engine *h, bool lds, const OverlayStepArgs &a);
+void gu_errands_step(gu_engine *h, bool lds, const OverlayStepArgs &a);
 void gu_wind_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a);
 void gu_fruit_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a);
 void gu_doors_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a);
 void gu_boxes_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a);
+void gu_errands_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a);
+// errands: the reset of the words (eaten and progress cleared, the instruction drawn on stream 11 at the episode count BEFORE gu_reset_kernel increments it)
+int gu_errands_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done);
 // gu_td.hip: the mask bits in use become `bits` (0: none) -- Q tables whose row count is not S << bits go, with what hangs on them
 void gu_td_rows_changed(gu_engine *h, int32_t bits);
 

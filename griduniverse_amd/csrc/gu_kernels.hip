@@ -556,7 +556,8 @@ int gu_launch_rollout(gu_engine *h, int64_t T, int32_t policy, uint32_t flags)
     case GU_PLAN_WIND:
     case GU_PLAN_FRUIT:
     case GU_PLAN_DOORS:
-    case GU_PLAN_BOXES: gu_overlay_launch_rollout(h, p, a); break;
+    case GU_PLAN_BOXES:
+    case GU_PLAN_ERRANDS: gu_overlay_launch_rollout(h, p, a); break;
     case GU_PLAN_KSTEP: gu_kstep_launch(h, p, a); break;
     case GU_PLAN_ROWS:
         if (!gu_rows_launch(h, p, a)) return gu_fail(GU_ERR_HIP, "gu_rollout_rows_kernel reports static LDS: its table must start at LDS address 0");

@@ -197,3 +197,57 @@ __device__ __forceinline__ bool gu_box_push(const uint8_t *f, const uint8_t *bx,
     gain = refused ? 0 : (int32_t)(b2 & GU_BOX_TARGET) - (int32_t)(bc & GU_BOX_TARGET);
     return refused;
 }
+
+// ------------------------------------------------------------------------------------
+// errands (include/gu.h: gu_set_errands): the plane is fruit's (bits 0..4 the slot, bits 5..6 the kind); the env's word holds the
+// fruit eaten in bits [0, F), the progress p in bits [F, F + pb) and the instruction index j in bits [F + pb, F + pb + ib)
+// ------------------------------------------------------------------------------------
+// The two parameter words (gu_engine::overlay_param, overlay_param2), both wave-uniform.  The first holds the instructions, byte j
+// instruction j, position p in bits 2p .. 2p + 1, kind 0 the end mark (a list of four has none).  The second holds the pay as int8
+// bytes 0 .. 2 (right, wrong, finish) and F - 1, pb and I - 1 above them.
+#define GU_ERRAND_PARAM2(right, wrong, finish, F, pb, I)                                                                                   \
+    ((uint32_t)(uint8_t)(int8_t)(right) | ((uint32_t)(uint8_t)(int8_t)(wrong) << 8) | ((uint32_t)(uint8_t)(int8_t)(finish) << 16) |    \
+     ((uint32_t)((F) - 1) << 24) | ((uint32_t)(pb) << 27) | ((uint32_t)((I) - 1) << 29))
+#define GU_ERRAND_F(q) ((((q) >> 24) & 7u) + 1u)
+#define GU_ERRAND_PB(q) (((q) >> 27) & 3u)
+#define GU_ERRAND_I(q) ((((q) >> 29) & 3u) + 1u)
+
+// `rem` is what a lane carries beside its word: the env's instruction byte shifted right by 2p.  The wanted kind is rem & 3 and the
+// instruction is complete where rem == 0 (a list of four included: the byte is shifted out), so nothing in a step indexes the table.
+__device__ __forceinline__ uint32_t gu_errand_rem(uint32_t word, uint32_t instr, uint32_t q)
+{
+    const uint32_t F = GU_ERRAND_F(q), pb = GU_ERRAND_PB(q);
+    const uint32_t p = (word >> F) & ((1u << pb) - 1u), j = (word >> (F + pb)) & 3u;
+    return ((instr >> (8u * j)) & 0xFFu) >> (2u * p);
+}
+
+// Rule 1: the word and `rem` of an env that is being reset at episode count ep (the count BEFORE the reset increments it).
+// start_prefix is stream 1's (seed and env, no epoch).  One instruction: no word is hashed (the test is wave-uniform).
+__device__ __forceinline__ void gu_errand_draw(uint32_t start_prefix, uint32_t ep, uint32_t instr, uint32_t q, uint32_t &word, uint32_t &rem)
+{
+    const uint32_t I = GU_ERRAND_I(q);
+    uint32_t j = 0u;
+    if (I > 1u) j = (uint32_t)(((uint64_t)gu_rng_word(start_prefix, GU_RNG_STREAM_ERRAND, ep) * (uint64_t)I) >> 32);
+    word = j << (GU_ERRAND_F(q) + GU_ERRAND_PB(q));
+    rem = (instr >> (8u * j)) & 0xFFu;
+}
+
+// Rules 2, 4 and 5 on the bytes of the candidate cell (c the errand byte, rb the reward byte, term the terminal bit), all three read
+// beside each other: sets r and d and moves the word on.  Returns true where the word was complete already (rule 2): the caller
+// then keeps s.  Nothing branches.
+__device__ __forceinline__ bool gu_errand_touch(uint32_t c, int32_t rb, int32_t term, uint32_t q, uint32_t &word, uint32_t &rem, int32_t &r, int32_t &d)
+{
+    const bool complete = rem == 0u;
+    const uint32_t kind = (c >> 5) & 3u;
+    const uint32_t bit = (kind ? 1u : 0u) << (c & 31u);
+    const bool fresh = !complete && (bit & ~word) != 0u;
+    const bool right = fresh && kind == (rem & 3u);
+    word |= fresh ? bit : 0u;
+    word += right ? (1u << GU_ERRAND_F(q)) : 0u;
+    rem = right ? rem >> 2 : rem;
+    const bool fin = complete || (right && rem == 0u);
+    const int32_t pay = __builtin_amdgcn_sbfe((int32_t)q, right ? 0u : 8u, 8);
+    r = fin ? __builtin_amdgcn_sbfe((int32_t)q, 16u, 8) : rb + (fresh ? pay : 0);
+    d = fin ? 1 : term;
+    return complete;
+}

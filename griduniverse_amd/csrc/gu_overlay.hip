@@ -1,9 +1,9 @@
-// gu_overlay.hip -- the overlay slot of a single-grid engine (DESIGN.md "Overlays"): wind, fruit, doors or boxes, at most one at a time.
+// gu_overlay.hip -- the overlay slot of a single-grid engine (DESIGN.md "Overlays"): wind, fruit, doors, boxes or errands, at most one at a time.
 // An overlay is a third byte plane behind the engine's two cell planes (gu_engine::d_overlay_cell holds all three in one piece, which
 // its kernels stage in LDS where they fit 64 KiB) and, for fruit, doors and boxes, one uint32 mask per env with its value at reset
 // (gu_engine::overlay_init: 0 but for boxes).  Here is everything around a feature's rule: the install path, the getters, the masks'
 // copies, the masks' reset and the arguments of the step and rollout launches.  The features keep their plane's validation and their
-// kernels (gu_wind.hip, gu_fruit.hip, gu_doors.hip, gu_boxes.hip).
+// kernels (gu_wind.hip, gu_fruit.hip, gu_doors.hip, gu_boxes.hip, gu_errands.hip); errands keep their reset kernel too (it draws).
 #include "gu_overlay.hpp"
 #include "gu_tabular.hpp"  // (gu_env_range, gu_env_copy)
 
@@ -26,12 +26,13 @@ void gu_overlay_free(gu_engine *h)
     h->overlay = GU_OVERLAY_NONE;
     h->overlay_bits = 0;
     h->overlay_param = 0;
+    h->overlay_param2 = 0;
     h->overlay_init = 0;
     h->box_flags.clear();
     std::fill(h->fruit_value, h->fruit_value + 3, 0);
 }
 
-int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bits, uint32_t param, uint32_t init)
+int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bits, uint32_t param, uint32_t init, uint32_t param2)
 {
     GU_TRY(gu_overlay_admits(h, kind));
     GU_HIP(hipStreamSynchronize(h->stream));
@@ -63,6 +64,7 @@ int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bit
     h->d_overlay_mask = mask;
     h->overlay_bits = bits;
     h->overlay_param = param;
+    h->overlay_param2 = param2;
     h->overlay_init = init;
     return GU_OK;
 }
@@ -121,6 +123,7 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_overlay_reset_kernel(uint32_t *__
 int gu_overlay_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done)
 {
     if (!h->d_overlay_mask) return GU_OK;
+    if (h->overlay == GU_OVERLAY_ERRANDS) return gu_errands_before_reset(h, d_mask, only_done);  // (draws the instruction: gu_errands.hip)
     hipLaunchKernelGGL(gu_overlay_reset_kernel, dim3(gu_blocks(h->N, GU_BLOCK)), dim3(GU_BLOCK), 0, h->stream, h->d_overlay_mask, d_mask, h->done(), only_done ? 1 : 0, h->N,
                        h->overlay_init);
     GU_HIP(hipGetLastError());
@@ -133,10 +136,10 @@ int gu_overlay_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done)
 int gu_overlay_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward, int32_t *host_done,
                            uint32_t *host_seq, uint32_t seq, uint32_t *host_err)
 {
-    static void (*const step[])(gu_engine *, bool, const OverlayStepArgs &) = {nullptr, gu_wind_step, gu_fruit_step, gu_doors_step, gu_boxes_step};
+    static void (*const step[])(gu_engine *, bool, const OverlayStepArgs &) = {nullptr, gu_wind_step, gu_fruit_step, gu_doors_step, gu_boxes_step, gu_errands_step};
     const OverlayStepArgs a{h->d_overlay_cell, h->cell_bytes, h->W, h->delta_lut, d_actions_row, h->pos(), h->reward(), h->done(), h->d_episode, h->d_tcount,
                             h->d_overlay_mask, h->d_starts, (uint32_t)h->n_starts, h->seed_prefix, (uint32_t)h->env_id0, h->overlay_param, h->steps_taken, h->N, flags,
-                            gu_grid_sel(h), host_obs, host_reward, host_done, host_seq, seq, h->d_blocks_done, host_err, h->d_done_bits, h->overlay_init};
+                            gu_grid_sel(h), host_obs, host_reward, host_done, host_seq, seq, h->d_blocks_done, host_err, h->d_done_bits, h->overlay_init, h->overlay_param2};
     step[h->overlay](h, gu_lds_block(h, GU_BLOCK, 3) != 0, a);
     GU_HIP(hipGetLastError());
     gu_envs_touched(h, 1);
@@ -147,10 +150,10 @@ int gu_overlay_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t 
 void gu_overlay_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &r)
 {
     static void (*const rollout[])(gu_engine *, const GuRolloutPlan &, const OverlayRolloutArgs &) = {nullptr, gu_wind_rollout, gu_fruit_rollout, gu_doors_rollout,
-                                                                                                      gu_boxes_rollout};
+                                                                                                      gu_boxes_rollout, gu_errands_rollout};
     OverlayRolloutArgs a{};
     a.cell = h->d_overlay_cell, a.cell_bytes = h->cell_bytes, a.W = h->W, a.lut = h->delta_lut, a.gs = r.gs, a.mask = h->d_overlay_mask, a.param = h->overlay_param,
-    a.init = h->overlay_init;
+    a.init = h->overlay_init, a.param2 = h->overlay_param2;
     a.greedy = r.greedy, a.pi_thr = r.pi_thr, a.actions = r.actions;
     a.pos = r.pos, a.reward = r.reward, a.done = r.done, a.episode = r.episode, a.tcount = r.tcount, a.done_bits = r.done_bits;
     a.starts = r.starts, a.n_starts = r.n_starts, a.env_id0 = r.env_id0, a.seed_prefix = h->seed_prefix;

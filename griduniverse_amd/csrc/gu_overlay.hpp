@@ -1,11 +1,11 @@
-// gu_overlay.hpp -- what the kernels of the overlays share (DESIGN.md "Overlays"; gu_wind.hip, gu_fruit.hip, gu_doors.hip, gu_boxes.hip): the
+// gu_overlay.hpp -- what the kernels of the overlays share (DESIGN.md "Overlays"; gu_wind.hip, gu_fruit.hip, gu_doors.hip, gu_boxes.hip, gu_errands.hip): the
 // argument structs that gu_overlay.hip fills, the completion word of a step kernel and the per-lane policy of a rollout kernel.
 // Everything around a feature's move or reward rule; the rule itself stays written out in the feature's own kernels.
 #pragma once
 #include "gu_rollout.hpp"  // (gu_map.hpp, gu_rng.hpp, gu_sample_action, RolloutArgs)
 
 // ---- single step: gu_step_kernel's arguments with the overlay's plane behind the two cell planes.  A kernel ignores what it does
-// not use: wind reads no mask, doors no param, and only gusts ask for the step count. ----
+// not use: wind reads no mask, doors no param, only gusts ask for the step count and only errands read param2. ----
 struct OverlayStepArgs {
     const uint8_t *cell;  // [flags | reward | overlay]
     int32_t cell_bytes, W;
@@ -14,7 +14,7 @@ struct OverlayStepArgs {
     int32_t *pos, *reward, *done;
     uint32_t *episode;
     uint32_t *tcount;
-    uint32_t *mask;  // [N] fruit: eaten, doors: open, boxes: the boxes' cells (gu_engine::d_overlay_mask)
+    uint32_t *mask;  // [N] fruit: eaten, doors: open, boxes: the boxes' cells, errands: eaten | progress | instruction (gu_engine::d_overlay_mask)
     const int32_t *starts;
     uint32_t n_starts, seed_prefix, env_id0, param;  // param: gu_engine::overlay_param
     uint64_t steps_taken;
@@ -28,6 +28,7 @@ struct OverlayStepArgs {
     uint32_t *host_err;
     uint64_t *done_bits;
     uint32_t init;  // the mask of an env that has just been reset (gu_engine::overlay_init: 0 but for boxes)
+    uint32_t param2;  // gu_engine::overlay_param2 (errands: the pay and the field widths)
 };
 
 // ---- rollout: T steps per lane in one launch; the four policies with the calm kernels' action and sampling streams (0 and 2) ----
@@ -52,6 +53,7 @@ struct OverlayRolloutArgs {
     int32_t auto_reset;
     GridSel gs;
     uint32_t init;  // (as OverlayStepArgs::init)
+    uint32_t param2;  // (as OverlayStepArgs::param2)
 };
 
 // The completion word of a step kernel (gu_step_kernel and the overlays'): the host spins on a sequence number in page-locked memory

@@ -27,6 +27,7 @@
 #define GU_RNG_STREAM_MCTS 8u  // selection and rollout draws of the tree search (gu_mcts.hip): counter c & 0xFFFFFFFF, epoch c >> 32, keyed like stream 4
 #define GU_RNG_STREAM_WIND 9u  // the gusts of the wind (gu_map.hpp: gu_wind_gust): counter t & 0xFFFFFFFF, epoch t >> 32, keyed like stream 4
 #define GU_RNG_STREAM_DOUBLE 10u  // the coin of Double Q-learning (gu_double.hip), bit 0: counter t & 0xFFFFFFFF, epoch t >> 32, keyed like stream 4
+#define GU_RNG_STREAM_ERRAND 11u  // the instruction an env is given at a reset (gu_map.hpp: gu_errand_draw): counter = the episode count before the reset, no epoch, keyed like stream 1
 #ifndef GU_RNG_SAMPLE_LOG2
 #define GU_RNG_SAMPLE_LOG2 4u  // steps per hashed word of stream 2: 1 << this = 16 (oracle/gu_rng.py: SAMPLE_GROUP_LOG2)
 #endif

@@ -9,9 +9,9 @@
 #include <algorithm>
 #include <type_traits>
 
-enum { GU_PLAN_GENERAL = 1, GU_PLAN_ROWS = 2, GU_PLAN_KSTEP = 3, GU_PLAN_WIND = 4, GU_PLAN_FRUIT = 5, GU_PLAN_DOORS = 6, GU_PLAN_BOXES = 7 };  // kernel families (gu_diag_rollout_form, word 1)
+enum { GU_PLAN_GENERAL = 1, GU_PLAN_ROWS = 2, GU_PLAN_KSTEP = 3, GU_PLAN_WIND = 4, GU_PLAN_FRUIT = 5, GU_PLAN_DOORS = 6, GU_PLAN_BOXES = 7, GU_PLAN_ERRANDS = 8 };  // kernel families (gu_diag_rollout_form, word 1)
 static_assert(GU_PLAN_FRUIT - GU_PLAN_WIND == GU_OVERLAY_FRUIT - GU_OVERLAY_WIND && GU_PLAN_DOORS - GU_PLAN_WIND == GU_OVERLAY_DOORS - GU_OVERLAY_WIND &&
-                  GU_PLAN_BOXES - GU_PLAN_WIND == GU_OVERLAY_BOXES - GU_OVERLAY_WIND,
+                  GU_PLAN_BOXES - GU_PLAN_WIND == GU_OVERLAY_BOXES - GU_OVERLAY_WIND && GU_PLAN_ERRANDS - GU_PLAN_WIND == GU_OVERLAY_ERRANDS - GU_OVERLAY_WIND,
               "an overlay's family is GU_PLAN_WIND + its kind - GU_OVERLAY_WIND");
 // `exclude`: families (1u << family) and forms that the executor found it cannot run -- a table that could not be allocated, dynamic LDS
 // that does not start at address 0 -- and plans again without
@@ -329,7 +329,7 @@ inline GuRolloutPlan gu_rollout_plan(const gu_engine *h, int64_t T, int32_t poli
     const bool xcd = gu_opt(h, GU_OPT_ROLLOUT_XCD) != 0 && h->n_grids == 1;  // XCD-aware env-block order (see gu_env_block; measured slower, off)
     // ---- overlay, K-step, rows, general.  A launch during which an env passes a multiple of 2^32 steps goes to the general kernel,
     // which asks the RNG's epoch per lane and step.
-    if (h->overlay) {  // an overlay's kernel (gu_wind.hip, gu_fruit.hip, gu_doors.hip, gu_boxes.hip) serves every shape: three planes in LDS where they fit, int32 planes only
+    if (h->overlay) {  // an overlay's kernel (gu_wind.hip, gu_fruit.hip, gu_doors.hip, gu_boxes.hip, gu_errands.hip) serves every shape: three planes in LDS where they fit, int32 planes only
         p.family = GU_PLAN_WIND + h->overlay - GU_OVERLAY_WIND, p.block = GU_BLOCK, p.blocks = gu_blocks(h->N, GU_BLOCK);
         p.lds = gu_lds_block(h, GU_BLOCK, 3) ? 3 * (size_t)h->cell_bytes : 0;
         p.straddle = p.entry_table = false;  // (its kernel reads neither: it counts steps in 64 bits and asks the RNG's epoch per step)

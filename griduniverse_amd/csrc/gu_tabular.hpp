@@ -131,15 +131,22 @@ __device__ __forceinline__ uint64_t gu_dyna_pack(int32_t s2, int32_t r, int32_t 
 // (GU_BOX_PARAM) and `binit` (the word at reset) before begin() and stores `eaten` behind end().  The lane carries the count of boxes on
 // a target beside the word (`on`, `on2`), as the rollout kernel does (the head of gu_boxes.hip); move() applies rules 2-6 of
 // gu_set_boxes, the push behind a branch that only pushing lanes take.
-template <bool LDS, bool ROWS = true, int WIND = 0, bool FRUIT = false, bool DOORS = false, bool BOXES = false>
+// ERRANDS (include/gu.h: gu_set_errands; never with another kind): a.cell carries the errand plane (fruit's format) behind the two cell
+// planes and the table has S << (F + pb + ib) rows.  The env's word (eaten | progress | instruction) lives where the masks live, so the
+// rows and their comparisons are the masked ones.  The kernel sets `rows`, `eaten`, `fvalues` (the instructions) and `eparam2`
+// (GU_ERRAND_PARAM2) before begin() and stores `eaten` behind end().  The lane carries `rem`, its instruction byte shifted right by
+// 2p, beside the word (`rem2` behind move()), as the rollout kernel does (the head of gu_errands.hip); reset() draws the instruction
+// on stream 11 and move() applies rules 2-5 of gu_set_errands.
+template <bool LDS, bool ROWS = true, int WIND = 0, bool FRUIT = false, bool DOORS = false, bool BOXES = false, bool ERRANDS = false>
 struct TabLane {
-    static constexpr bool MASKED = FRUIT || DOORS || BOXES;  // the table has a row per (cell, mask)
+    static constexpr bool MASKED = FRUIT || DOORS || BOXES || ERRANDS;  // the table has a row per (cell, mask)
     CellMap m;
-    const uint8_t *wd;  // WIND: the wind plane; FRUIT: the fruit plane; DOORS: the door plane; BOXES: the box plane
+    const uint8_t *wd;  // WIND: the wind plane; FRUIT: the fruit plane; DOORS: the door plane; BOXES: the box plane; ERRANDS: the errand plane
     uint32_t gust_q16;  // WIND == 2
-    uint32_t fvalues;   // FRUIT
+    uint32_t fvalues;   // FRUIT: the kinds' values; ERRANDS: the instructions
+    uint32_t eparam2, rem, rem2;  // ERRANDS: the second parameter word, the rest of the env's instruction under `eaten` and behind move()
     uint32_t bparam, binit, on, on2;  // BOXES: the parameter word, the word at reset, boxes on a target under `eaten` and behind move()
-    uint32_t eaten, eaten2;  // MASKED: the env's mask (eaten fruit / open slots / box cells), and the one behind move()
+    uint32_t eaten, eaten2;  // MASKED: the env's mask (eaten fruit / open slots / box cells / errand word), and the one behind move()
     int32_t S, rows;         // MASKED: states, and rows of one learner's table (S << F, S << D)
     LaneGrid lg;
     int64_t e;
@@ -169,6 +176,7 @@ struct TabLane {
         qe = ROWS ? a.q + (MASKED ? e * rows : e * a.S) * 4 : nullptr;
         if (MASKED) eaten2 = eaten;
         if (BOXES) on = on2 = gu_box_on_target(wd, eaten, GU_BOX_B(bparam), GU_BOX_BITS(bparam));
+        if (ERRANDS) rem = rem2 = gu_errand_rem(eaten, fvalues, eparam2);
         s = a.pos[e];
         r = a.reward[e];
         d = a.done[e];
@@ -188,6 +196,10 @@ struct TabLane {
             d = 0;
             if (MASKED) eaten = eaten2 = 0u;  // the fruit grows back; the doors are shut again
             if (BOXES) eaten = eaten2 = binit, on = on2 = GU_BOX_ON0(bparam);  // the boxes are back where they began
+            if (ERRANDS) {  // another instruction, drawn at the episode count before the reset
+                gu_errand_draw(start_prefix, ep - 1u, fvalues, eparam2, eaten, rem);
+                eaten2 = eaten, rem2 = rem;
+            }
             if (ROWS) q = gu_q_load(qe + row() * 4);
         }
     }
@@ -223,6 +235,12 @@ struct TabLane {
             const bool won = on2 == B;
             r = won ? GU_BOX_SOLVED_REWARD : m.r[s2] + GU_BOX_V(bparam) * gain;
             d = won ? 1 : (m.f[s2] >> GU_CELL_TERM_BIT) & 1;
+        } else if (ERRANDS) {
+            // rules 2-5 of gu_set_errands on the candidate s2, its three bytes read together; a completed word keeps the cell behind the reads
+            const int32_t c = s2;
+            eaten2 = eaten, rem2 = rem;
+            const bool stay = gu_errand_touch(wd[c], m.r[c], (m.f[c] >> GU_CELL_TERM_BIT) & 1, eparam2, eaten2, rem2, r, d);
+            s2 = stay ? s : c;
         } else if (DOORS) {
             // A closed door refuses entry as a wall does; the key or lever of a cell entered changes the mask behind the step.  The door
             // byte of the candidate is read BESIDE its flags and reward byte, and the gate picks between them and the bytes of s (its
@@ -267,6 +285,7 @@ struct TabLane {
         s = s2;
         if (MASKED) eaten = eaten2;
         if (BOXES) on = on2;
+        if (ERRANDS) rem = rem2;
         if (a.tr_obs) {
             const int64_t row = (int64_t)i * a.N + e;
             a.tr_obs[row] = s2;

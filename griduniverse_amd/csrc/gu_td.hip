@@ -17,6 +17,7 @@ struct TdArgs : TabArgs {
     int32_t rows;
     uint32_t *eaten;  // (the door instantiations, gu_set_doors: the envs' masks of open slots, and rows = S << D)
     uint32_t box_init;  // the box instantiations (gu_set_boxes): fruit_values holds GU_BOX_PARAM, eaten the envs' words, rows = S << (b * B)
+    uint32_t param2;  // the errand instantiations (gu_set_errands): fruit_values holds the instructions, param2 GU_ERRAND_PARAM2, eaten the envs' words
     double pe, pg;    // TD_ESARSA: eps_q16 * 2^-18 and (65536 - eps_q16) * 2^-16, both exact
 };
 
@@ -26,17 +27,19 @@ enum TdRule { TD_Q = 0, TD_SARSA = 1, TD_ESARSA = 2 };  // (the first two are gu
 // FRUIT: the table has S << F rows and the lane learns on row eaten * S + s (TabLane); never together with WIND
 // DOORS: the table has S << D rows and the lane learns on row open * S + s; never together with WIND or FRUIT
 // BOXES: the table has S << (b * B) rows and the lane learns on row word * S + s; never together with WIND, FRUIT or DOORS
-template <TdRule RULE, bool LDS, int WIND = 0, bool FRUIT = false, bool DOORS = false, bool BOXES = false>
+// ERRANDS: the table has S << (F + pb + ib) rows and the lane learns on row word * S + s; never together with another kind
+template <TdRule RULE, bool LDS, int WIND = 0, bool FRUIT = false, bool DOORS = false, bool BOXES = false, bool ERRANDS = false>
 __global__ void __launch_bounds__(GU_BLOCK) gu_td_kernel(const TdArgs a)
 {
     constexpr bool SARSA = RULE == TD_SARSA;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    TabLane<LDS, true, WIND, FRUIT, DOORS, BOXES> L(a, smem);
+    TabLane<LDS, true, WIND, FRUIT, DOORS, BOXES, ERRANDS> L(a, smem);
     if (WIND == 2) L.gust_q16 = a.gust_q16;
     if (L.e < a.N) {
         if (FRUIT) L.fvalues = a.fruit_values;
         if (BOXES) L.bparam = a.fruit_values, L.binit = a.box_init;
-        if (FRUIT || DOORS || BOXES) L.rows = a.rows, L.eaten = a.eaten[L.e];
+        if (ERRANDS) L.fvalues = a.fruit_values, L.eparam2 = a.param2;
+        if (FRUIT || DOORS || BOXES || ERRANDS) L.rows = a.rows, L.eaten = a.eaten[L.e];
         L.begin(a);
         int32_t act = (SARSA && a.carry) ? (int32_t)a.next_a[L.e] : -1;
         for (int32_t i = 0; i < a.T; ++i) {
@@ -65,7 +68,7 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_td_kernel(const TdArgs a)
             L.step(a, i, s2, n);
         }
         L.end(a);
-        if (FRUIT || DOORS || BOXES) a.eaten[L.e] = L.eaten;
+        if (FRUIT || DOORS || BOXES || ERRANDS) a.eaten[L.e] = L.eaten;
         if (SARSA) a.next_a[L.e] = (int8_t)act;
     }
     L.ballot(a);
@@ -92,12 +95,15 @@ static int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, d
     a.next_a = h->d_td_next;
     a.carry = (method == 1 && gu_carry_is(h, GU_CARRY_TD_SARSA, 0)) ? 1 : 0;
     // the overlay's instantiations, on [flags | reward | overlay]; fruit and doors learn on S << bits rows and keep the env's mask in `eaten`
-    a.gust_q16 = a.fruit_values = h->overlay_param, a.rows = h->td_S, a.eaten = h->d_overlay_mask, a.box_init = h->overlay_init;
+    a.gust_q16 = a.fruit_values = h->overlay_param, a.rows = h->td_S, a.eaten = h->d_overlay_mask, a.box_init = h->overlay_init, a.param2 = h->overlay_param2;
     if (h->overlay) a.cell = h->d_overlay_cell;
     a.pe = (double)eps_q16 * 0x1p-18, a.pg = (double)(65536u - eps_q16) * 0x1p-16;
     int rc;
     if (method == TD_ESARSA) {  // (calm only: gu_esarsa_run refuses while an overlay is set)
         rc = gu_tabular_launch(h, gu_td_kernel<TD_ESARSA, true>, gu_td_kernel<TD_ESARSA, false>, a);
+    } else if (h->overlay == GU_OVERLAY_ERRANDS) {
+        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 0, false, false, false, true>, gu_td_kernel<TD_SARSA, false, 0, false, false, false, true>, a, GU_BLOCK, 0, 3)
+                         : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 0, false, false, false, true>, gu_td_kernel<TD_Q, false, 0, false, false, false, true>, a, GU_BLOCK, 0, 3);
     } else if (h->overlay == GU_OVERLAY_BOXES) {
         rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 0, false, false, true>, gu_td_kernel<TD_SARSA, false, 0, false, false, true>, a, GU_BLOCK, 0, 3)
                          : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 0, false, false, true>, gu_td_kernel<TD_Q, false, 0, false, false, true>, a, GU_BLOCK, 0, 3);
@@ -171,6 +177,8 @@ int gu_td_init(gu_handle h, double q0)
     // under fruit a table has a row per (cell, mask): S << F of them (gu_set_fruit), which ten fruits multiply by 1024
     GU_REQUIRE(h->overlay != GU_OVERLAY_BOXES || h->overlay_bits <= 10, GU_ERR_INVALID,
                "boxes of %d bits (boxes x bits per box): gu_td_init learns on S << bits rows and takes at most 10 bits", h->overlay_bits);
+    GU_REQUIRE(h->overlay != GU_OVERLAY_ERRANDS || h->overlay_bits <= 10, GU_ERR_INVALID,
+               "errands of %d bits (fruits + progress + instruction): gu_td_init learns on S << bits rows and takes at most 10 bits", h->overlay_bits);
     GU_REQUIRE(h->overlay_bits <= 10, GU_ERR_INVALID, "%d fruits: gu_td_init learns on S << F rows and takes at most 10 fruits", h->overlay_bits);
     GU_REQUIRE(GU_TD_ROWS(h) <= 0x7FFFFFFF, GU_ERR_INVALID, "%d states x 2^%d masks: more than 2^31 - 1 rows", h->S, h->overlay_bits);
     const int32_t rows = (int32_t)GU_TD_ROWS(h);

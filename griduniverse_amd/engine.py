@@ -222,10 +222,35 @@ class Engine(object):
         """Install the words uint32[n] of envs env0 .. env0+n-1 (gu_set_boxes_state)."""
         self._set_masks(self.lib.gu_set_boxes_state, words, env0, 'words')
 
+    def set_errands(self, errand, instr=(0, 0, 0, 0), n_instr=0, pay=(0, 0, 0)):
+        """Install the errand plane uint8[S] (grid.fruit_plane), the instruction bytes uint8[4] (grid.errand_bytes) of which the first
+        `n_instr` count, and the pay (right 0 .. 16, wrong -16 .. 0, finish 0 .. 16); None takes the errands away again
+        (gu_set_errands).  Sets every env's word to 0: instruction 0, nothing eaten."""
+        p = None if errand is None else _lib.as_array(errand, np.uint8, (self.spec.S,), 'errand')
+        i = _lib.as_array(instr, np.uint8, (4,), 'instr')
+        v = _lib.as_array(pay, np.int32, (3,), 'pay')
+        check(self.lib.gu_set_errands(self._h, ptr(p), int(n_instr), ptr(i), ptr(v)))
+
+    def get_errands(self):
+        """(errand uint8[S], instr uint8[4], n_instr, pay int32[3], F), or None while no errands are set (gu_get_errands)."""
+        errand, instr, pay = np.empty(self.spec.S, np.uint8), np.empty(4, np.uint8), np.empty(3, np.int32)
+        n, F = ctypes.c_int32(0), ctypes.c_int32(0)
+        check(self.lib.gu_get_errands(self._h, ptr(errand), ctypes.byref(n), ptr(instr), ptr(pay), ctypes.byref(F)))
+        return (errand, instr, n.value, pay, F.value) if n.value else None
+
+    def get_errands_state(self, env0=0, n=None):
+        """uint32[n]: the words of envs env0 .. env0+n-1, eaten | progress << F | instruction << (F + pb) (gu_get_errands_state)."""
+        return self._get_masks(self.lib.gu_get_errands_state, env0, n)
+
+    def set_errands_state(self, words, env0=0):
+        """Install the words uint32[n] of envs env0 .. env0+n-1 (gu_set_errands_state)."""
+        self._set_masks(self.lib.gu_set_errands_state, words, env0, 'words')
+
     @property
     def td_rows(self):
         """Rows of one env's Q table: S, or S << F while F fruits are set (include/gu.h: gu_set_fruit), or S << D while doors with
-        D slots are set (gu_set_doors), or S << (b * B) while B boxes of b bits each are set (gu_set_boxes)."""
+        D slots are set (gu_set_doors), or S << (b * B) while B boxes of b bits each are set (gu_set_boxes), or
+        S << (F + pb + ib) while errands are set (gu_set_errands)."""
         return self.spec.S << self.stores()['overlay_bits']
 
     def seed(self, seed):
@@ -329,12 +354,12 @@ class Engine(object):
         check(self.lib.gu_rollout(self._h, int(T), _POLICIES[policy], flags))
 
     ROLLOUT_FORM = ('family', 'layout', 'map', 'block', 'workgroups', 'lds_bytes', 'flags', 'K', 'row_shift', 'stream_words', 'pace_slot', 'pace_mode')
-    ROLLOUT_FAMILIES = {0: None, 1: 'general', 2: 'rows', 3: 'kstep', 4: 'wind', 5: 'fruit', 6: 'doors', 7: 'boxes'}
+    ROLLOUT_FAMILIES = {0: None, 1: 'general', 2: 'rows', 3: 'kstep', 4: 'wind', 5: 'fruit', 6: 'doors', 7: 'boxes', 8: 'errands'}
     ROLLOUT_FLAG_BITS = ('pair', 'half', 'per_wave', 'pi_lds', 'straddle', 'entry_table', 'xcd_remap')
 
     def rollout_last_form(self):
         """What the last rollout of this engine ran on (gu_diag_rollout_form): dict with the twelve form words under the names of
-        ROLLOUT_FORM ('family' as a name: 'general', 'rows', 'kstep', 'wind', 'fruit', 'doors', 'boxes'; None before the first rollout), each flag bit as a
+        ROLLOUT_FORM ('family' as a name: 'general', 'rows', 'kstep', 'wind', 'fruit', 'doors', 'boxes', 'errands'; None before the first rollout), each flag bit as a
         bool under its name in ROLLOUT_FLAG_BITS, and the raw words as 'words'."""
         words = np.zeros(len(self.ROLLOUT_FORM), np.int32)
         n = ctypes.c_int32(0)

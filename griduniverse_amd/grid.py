@@ -203,6 +203,82 @@ def fruit_plane(W, H, cells, kinds='apple'):
     return plane
 
 
+# ---- errands: the instructions of include/gu.h, gu_set_errands (the plane is fruit_plane's) -------------------------
+ERRAND_FRUIT_MAX, ERRAND_INSTRUCTIONS_MAX, ERRAND_LENGTH_MAX = 8, 4, 4
+_ERRAND_FILLERS = frozenset('collect get eat take pick up the a an and then first next finally'.split())
+_KIND_NAMES = {code: name for name, code in FRUIT_KINDS.items()}
+
+
+def parse_instruction(text):
+    """The list of kind names an instruction in words asks for, in order: 'Collect the lemon and then the apple' gives
+    ['lemon', 'apple'].  The text is lower-cased and split on everything that is not a letter; the words collect, get, eat, take,
+    pick, up, the, a, an, and, then, first, next and finally are dropped, and every other word must be 'apple', 'lemon' or 'melon'
+    (ValueError) -- so 'after' and 'before', which would turn the order round, raise rather than being mis-read."""
+    if not isinstance(text, str):
+        raise ValueError('an instruction in words must be a string')
+    words = [w for w in ''.join(ch if ch.isalpha() and ch.isascii() else ' ' for ch in text.lower()).split() if w not in _ERRAND_FILLERS]
+    for w in words:
+        if w not in FRUIT_KINDS:
+            raise ValueError("an instruction names 'apple', 'lemon' and 'melon' only: {!r}".format(w))
+    return words
+
+
+def _errand_kinds(instruction):
+    """The kind codes 1 .. 3 of one instruction: a string (parse_instruction) or a list of kind names or codes."""
+    ks = parse_instruction(instruction) if isinstance(instruction, str) else list(instruction)
+    codes = []
+    for k in ks:
+        if isinstance(k, str) and k in FRUIT_KINDS:
+            k = FRUIT_KINDS[k]
+        if isinstance(k, (str, bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= 3:
+            raise ValueError("a kind is one of 'apple', 'lemon', 'melon', or a code 1 .. 3")
+        codes.append(int(k))
+    if not 1 <= len(codes) <= ERRAND_LENGTH_MAX:
+        raise ValueError('an instruction names 1 .. {} kinds, got {}'.format(ERRAND_LENGTH_MAX, len(codes)))
+    return codes
+
+
+def instruction_text(kinds):
+    """The inverse of parse_instruction: ['lemon', 'apple'] gives 'collect the lemon and then the apple'."""
+    return 'collect ' + ' and then '.join('the ' + _KIND_NAMES[k] for k in _errand_kinds(list(kinds)))
+
+
+def errand_bytes(instructions):
+    """uint8[4]: one byte per instruction as gu_set_errands takes them -- position p in bits 2p .. 2p+1, kind 0 the end mark (a list
+    of four has none), unused bytes zero.  `instructions`: 1 .. 4 of them, each a string or a list of kind names or codes."""
+    if isinstance(instructions, str) or not 1 <= len(instructions) <= ERRAND_INSTRUCTIONS_MAX:
+        raise ValueError('1 .. {} instructions, each a string or a list of kinds'.format(ERRAND_INSTRUCTIONS_MAX))
+    out = np.zeros(4, np.uint8)
+    for j, ins in enumerate(instructions):
+        out[j] = sum(k << (2 * p) for p, k in enumerate(_errand_kinds(ins)))
+    return out
+
+
+def pack_errands(instructions):
+    """The engine's parameter word of the instructions: byte j holds instruction j (errand_bytes)."""
+    return int(errand_bytes(instructions).view('<u4')[0])
+
+
+def errand_widths(F, instructions):
+    """(pb, ib): the bits of the progress and of the instruction index in an env's word, behind the F bits of eaten fruit."""
+    lengths = [len(_errand_kinds(ins)) for ins in instructions]
+    return max(lengths).bit_length(), (len(lengths) - 1).bit_length()
+
+
+def errand_fields(words, F, instructions):
+    """(eaten, progress, instruction): the three fields of the envs' words uint32[n] under F fruit and `instructions`."""
+    w = np.asarray(words).astype(np.uint32)
+    pb, ib = errand_widths(F, instructions)
+    return w & np.uint32((1 << F) - 1), (w >> np.uint32(F)) & np.uint32((1 << pb) - 1), (w >> np.uint32(F + pb)) & np.uint32((1 << ib) - 1)
+
+
+def errand_words(eaten, progress, instruction, F, instructions):
+    """uint32: the words of the fields, the inverse of errand_fields."""
+    pb, _ = errand_widths(F, instructions)
+    e, p, j = (np.asarray(x).astype(np.uint32) for x in (eaten, progress, instruction))
+    return (e | (p << np.uint32(F)) | (j << np.uint32(F + pb))).astype(np.uint32)
+
+
 # ---- doors, keys and levers: the per-cell plane of include/gu.h, gu_set_doors ---------------------------------------
 def _slot_cells(what, mapping, S):
     """{slot: sorted list of cells} of one argument of door_plane: a mapping slot -> cell or list of cells (None: empty)."""

@@ -14,6 +14,8 @@ one, keyed by (seed, GLOBAL env id, stream, counter):
                                 word & 3, greedy tie index (((word >> 2) & 0x3FFF) * ties) >> 14
     stream 9  gusts of wind   : one word per step taken from a cell with wind while gust_q16 > 0 (gu_set_wind), counter and epoch
                                 as stream 4; the strength k changes iff (word >> 16) < gust_q16, to k + 1 if word & 1 else k - 1
+    stream 11 errands         : the instruction an env is given at a reset while errands are set (gu_set_errands): index =
+                                (word(episode) * I) >> 32, keyed like stream 1 with the episode count before the reset
     stream 10 Double Q coin   : one word per step of gu_double_run, counter and epoch as stream 4 at the same step count; bit 0 picks
                                 the table that learns (0: A from B's estimate, 1: B from A's)
 
@@ -85,3 +87,10 @@ def wind_words(seed, env_ids, t):
     broadcast against each other); see gu_set_wind in include/gu.h."""
     t = np.asarray(t, dtype=np.uint64)
     return words(seed, np.asarray(env_ids, dtype=np.uint64), 9, t & _M32, t >> np.uint64(32))
+
+
+def errand_words(seed, env_ids, episodes):
+    """uint32: the stream-11 words behind the instructions that the resets number `episodes` (0 = first reset after gu_seed) give the
+    global env ids `env_ids` (the two broadcast against each other): instruction = (word * I) >> 32; see gu_set_errands in
+    include/gu.h."""
+    return words(seed, np.asarray(env_ids, dtype=np.uint64), 11, episodes)

@@ -19,7 +19,8 @@ import numpy as np
 from . import _lib, softmax
 from .engine import Engine
 from .envs.griduniverse_env import GridUniverseEnv
-from .grid import BOX_INITIAL, BOX_ON_TARGET_MAX, BOX_TARGET, DOOR_KINDS, FRUIT_KINDS, GridSpec, box_bits, box_plane, door_plane, fruit_plane, pack_boxes, unpack_boxes, wind_plane
+from .grid import (BOX_INITIAL, BOX_ON_TARGET_MAX, BOX_TARGET, DOOR_KINDS, ERRAND_FRUIT_MAX, FRUIT_KINDS, GridSpec, box_bits, box_plane, door_plane, errand_bytes,
+                   errand_fields, errand_words, fruit_plane, pack_boxes, unpack_boxes, wind_plane)
 
 
 def _q16(x):
@@ -291,8 +292,80 @@ class VecGridUniverse(object):
             raise ValueError('a box on cell {}, which is a wall or a goal or lava cell'.format(int(c.reshape(-1)[np.flatnonzero(blocked)[0]])))
         self.engine.set_boxes_state(words, env0)
 
+    def set_errands(self, cells, kinds='apple', instructions=None, right=5, wrong=-8, finish=10):
+        """Errands on the engine's grid (single-grid engines; include/gu.h: gu_set_errands): fruit on `cells` of `kinds`, as
+        grid.fruit_plane takes them (1 .. 8 cells, none on a wall, goal or lava cell), and 1 .. 4 `instructions`, each a string
+        ('collect the lemon and then the apple': grid.parse_instruction) or a list of 1 .. 4 kind names.  Every reset gives the env
+        one of the instructions (RNG stream 11) and grows the fruit back.  A fruit eaten in the instruction's order adds `right`
+        (0 .. 16) to the step's reward, any other fruit adds `wrong` (-16 .. 0) and is gone; the step that eats the instruction's last
+        entry pays `finish` (0 .. 16) and ends the episode.  An instruction may name a kind at most as often as there is fruit of it.
+        set_errands(None) takes the errands away.  step, rollout and td_run follow the errands (td_run learns on S << bits rows, bits
+        = F + bits of the progress + bits of the instruction index, at most 10); everything refused under fruit is refused while
+        they are set.  sense and render show fruit cells as free cells."""
+        if cells is None:
+            self.engine.set_errands(None)
+            return
+        pay = (right, wrong, finish)
+        if any(isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) for v in pay) or not (0 <= right <= 16 and -16 <= wrong <= 0 and 0 <= finish <= 16):
+            raise ValueError('right must be an integer in 0 .. 16, wrong in -16 .. 0 and finish in 0 .. 16')
+        if instructions is None:
+            raise ValueError('instructions: 1 .. 4 of them, each a string or a list of kind names')
+        instr = errand_bytes(instructions)
+        plane = fruit_plane(self.spec.W, self.spec.H, cells, kinds)
+        if np.count_nonzero(plane) > ERRAND_FRUIT_MAX:
+            raise ValueError('1 .. {} fruit cells, got {}'.format(ERRAND_FRUIT_MAX, int(np.count_nonzero(plane))))
+        blocked = (self.spec.wall | self.spec.goal | self.spec.lava) & (plane != 0)
+        if blocked.any():
+            raise ValueError('fruit on cell {}, which is a wall or a goal or lava cell'.format(int(np.flatnonzero(blocked)[0])))
+        have = np.bincount((plane[plane != 0] >> 5) & 3, minlength=4)
+        for j in range(len(instructions)):
+            named = np.bincount([(int(instr[j]) >> (2 * p)) & 3 for p in range(4)], minlength=4)
+            if (named[1:] > have[1:]).any():
+                raise ValueError('instruction {} names a kind more often than there is fruit of it'.format(j))
+        self.engine.set_errands(plane, instr, len(instructions), np.array(pay, np.int32))
+
+    def errands(self):
+        """None while no errands are set, else dict(cells=int64[F] ascending (index = slot), kinds=list of names, instructions=list of
+        lists of kind names, right=, wrong=, finish=)."""
+        got = self.engine.get_errands()
+        if got is None:
+            return None
+        plane, instr, n, pay, _ = got
+        cells = np.flatnonzero(plane)
+        names = {code: name for name, code in FRUIT_KINDS.items()}
+        lists = [[names[(int(instr[j]) >> (2 * p)) & 3] for p in range(4) if (int(instr[j]) >> (2 * p)) & 3] for j in range(n)]
+        return dict(cells=cells, kinds=[names[int(c) >> 5] for c in plane[cells]], instructions=lists, right=int(pay[0]), wrong=int(pay[1]), finish=int(pay[2]))
+
+    def errand_state(self, env0=0, n=None):
+        """dict(eaten=uint32[n], progress=uint32[n], instruction=uint32[n]) of envs env0 .. env0+n-1 (to the end when n is None): the
+        mask of eaten fruit (bit k: the k-th fruit cell in ascending order), how many entries of its instruction the env has carried
+        out, and which instruction its last reset gave it."""
+        got = self.errands()
+        if got is None:
+            raise ValueError('no errands set: call set_errands first')
+        e, p, j = errand_fields(self.engine.get_errands_state(env0, n), len(got['cells']), got['instructions'])
+        return dict(eaten=e, progress=p, instruction=j)
+
+    def set_errand_state(self, eaten=0, progress=0, instruction=0, env0=0):
+        """Install the three fields (arrays of one length n, or single numbers) for envs env0 ..: no bit of `eaten` at or above the
+        number of fruits, `instruction` below the number of instructions, `progress` at most that instruction's length."""
+        got = self.errands()
+        if got is None:
+            raise ValueError('no errands set: call set_errands first')
+        F, lists = len(got['cells']), got['instructions']
+        try:
+            e, p, j = np.broadcast_arrays(*(np.atleast_1d(np.asarray(x)) for x in (eaten, progress, instruction)))
+        except ValueError:
+            raise ValueError('eaten, progress and instruction must be of one length')
+        for x in (e, p, j):
+            if x.ndim != 1 or x.dtype == bool or not np.issubdtype(x.dtype, np.integer) or (x.size and x.min() < 0):
+                raise ValueError('eaten, progress and instruction must be non-negative integers, one per env')
+        if e.size and (e.max() >> F or j.max() >= len(lists) or (p > np.array([len(k) for k in lists])[j]).any()):
+            raise ValueError('eaten must hold masks of the {} fruits set, instruction an index below {} and progress at most its length'.format(F, len(lists)))
+        self.engine.set_errands_state(errand_words(e, p, j, F, lists), env0)
+
     def _mask_width(self, overlay):
-        """Bits of an env's mask in use while `overlay` (2 fruit, 3 doors, 4 boxes: include/gu.h, GU_STORE_OVERLAY) is set, else 0."""
+        """Bits of an env's mask in use while `overlay` (2 fruit, 3 doors, 4 boxes, 5 errands: include/gu.h, GU_STORE_OVERLAY) is set, else 0."""
         st = self.engine.stores()
         return st['overlay_bits'] if st['overlay'] == overlay else 0
 

@@ -359,6 +359,64 @@ int gu_get_boxes(gu_handle h, uint8_t *box /* zeros when none */, int32_t *on_ta
 int gu_get_boxes_state(gu_handle h, int64_t env0, int64_t n, uint32_t *words);
 int gu_set_boxes_state(gu_handle h, int64_t env0, int64_t n, const uint32_t *words);
 
+/* ---- errands: ordered fruit-collection instructions, one per episode ------------------------------------------------
+ * Build-defined (the reference's roadmap lists natural language grounding -- "collect the lemon and then the apple" -- and a
+ * multi-task interface, and has neither; restated on the CPU by tests/_errands_oracle.py).  Errands are a property of a SINGLE-GRID
+ * engine, and the fifth kind of overlay: they exclude wind, fruit, doors, boxes and the agent trail as those exclude each other.
+ * THE PLANE: one byte per cell, errand[s], in fruit's format exactly -- bits 0..4 the slot, bits 5..6 the kind (0 = no fruit, 1 / 2 / 3
+ * = apple, lemon, melon), bit 7 zero, and kind 0 requires the whole byte to be 0.  F is the number of fruit cells, 1 .. 8; their slots
+ * are exactly 0 .. F-1, each used once.  A fruit may not lie on a wall or on a goal or lava cell; it may lie on a start cell.
+ * THE INSTRUCTIONS: I of them, 1 .. 4, each a list of L_j kinds, 1 <= L_j <= 4.  instr[j] holds instruction j: position p sits in bits
+ * 2p .. 2p+1, kind 0 ends the list (nothing may follow it), a list of four has no end mark; instr[j] is zero for j >= I.  An instruction
+ * may name a kind at most as often as the plane holds fruit of that kind, so a fresh episode can always carry it out.
+ * THE PAY: pay[3] = right in 0 .. 16, wrong in -16 .. 0, finish in 0 .. 16.  A fruit cannot lie on a terminal cell, so the step that
+ * eats one pays the cell's -1 beside right or wrong and the completing step pays finish alone: no step pays more than 17 in absolute
+ * value, and fruit's bound on a launch's int32 reward sum holds (gu_set_fruit above).
+ * THE WORD: one uint32 per env.  Bits [0, F): the fruit eaten (bit = slot).  Bits [F, F + pb): the progress p, pb = bit_length(max L_j).
+ * Bits [F + pb, F + pb + ib): the index j of the env's instruction, ib = bit_length(I - 1).  F + pb + ib bits are in use (at most 13).
+ * One step of env e from cell s under the word (eaten, p, j) with a valid action:
+ *   1. the lazy auto-reset, where the call has one, sets eaten = 0 and p = 0 together with the position and draws j = (w * I) >> 32,
+ *      w the word of RNG stream 11, keyed like stream 1 (seed, global env id, no epoch) with the value of episode[e] BEFORE this reset
+ *      increments it as its counter.  With I = 1 no word need be hashed;
+ *   2. if p == L_j, nothing moves: s' = s, r = finish, d = 1.  This is absorbing, and a property of the word, as "solved" is for boxes;
+ *   3. otherwise s' comes from the engine's move rule exactly as without errands: an errand never changes a move;
+ *   4. c = errand[s'].  If c holds a fruit whose bit of eaten is clear, the bit is set.  If its kind is entry p of instruction j, then
+ *      p += 1; if now p == L_j, then r = finish and d = 1, in place of everything else, and otherwise r = R[s'] + right.  If its kind is
+ *      not that entry, then r = R[s'] + wrong and p stays: the fruit is gone, and the instruction may now be impossible -- such an env
+ *      comes back through a goal or lava cell only, as under a boxes deadlock;
+ *   5. without a fresh fruit, r and d are the engine's for s';
+ *   6. t += 1.
+ * So a reset does not eat the fruit of the start cell; a later step that ends there does, and so does a wall bump that leaves the
+ * agent on it.  A rejected action (outside -4 .. 3) moves nothing, eats nothing and draws nothing.  Streams 0, 1, 2 and 4 are drawn as
+ * they are without errands.
+ * Every path that resets an env clears eaten and p and draws j by rule 1: gu_reset (masked envs only, with or without start_choice),
+ * gu_reset_done, and the lazy resets inside the kernels.  gu_set_errands itself sets every word to 0: instruction 0, nothing eaten.
+ * gu_set_state and gu_seed leave the words alone.
+ * While errands are set, gu_step (pinned I/O and the completion word included), gu_step_device, gu_rollout (all four policies,
+ * GU_F_TRAJECTORY / GU_F_STATS; GU_F_PACKED returns GU_ERR_UNSUPPORTED; rows are the three [T][N] planes) and gu_td_run (both methods)
+ * run their errand kernels (csrc/gu_errands.hip, csrc/gu_td.hip); every call that is refused while fruit is set (gu_set_fruit above) is
+ * refused in the same way, with GU_ERR_UNSUPPORTED.  Calls that read rows or state only are unaffected; sense and render show fruit
+ * cells as free cells.
+ * THE LEARNERS' TABLES: the instruction is part of the learner's state.  While errands are set a gu_td_run table has
+ * S << (F + pb + ib) rows and row word * S + s belongs to cell s under the word, exactly as under fruit.  gu_td_init takes at most 10
+ * bits and returns GU_ERR_INVALID above.  No other learner has an errands form.
+ * gu_set_errands: errand[S], n_instr = I, instr[4] and pay[3], or errand = NULL = no errands again.  GU_ERR_STATE without a grid;
+ *              GU_ERR_UNSUPPORTED on a multi-grid engine, while wind, fruit, doors or boxes are set and while the agent trail is on
+ *              (each of those refuses while errands are set); GU_ERR_INVALID for a malformed byte, a repeated or missing slot, more
+ *              than 8 fruits, a fruit on a wall or terminal cell, I outside 1 .. 4, an empty or malformed instruction, a non-zero
+ *              byte behind the I instructions, an instruction that names a kind more often than the plane holds it, or pay outside
+ *              its ranges.  A refused call leaves the engine as it was.  Ends what the learners carry, destroys a captured step graph
+ *              and drops the Q tables whenever it changes their row count, as gu_set_fruit does.  Keeps positions and step counts.
+ *              gu_set_grid, gu_set_grids and gu_generate_mazes drop the errands.
+ * gu_get_errands: the plane (zeros when none), I (0 = none set), the instruction bytes, the pay and F; every pointer may be NULL.
+ * gu_get_errands_state / gu_set_errands_state: the words of envs env0 .. env0+n-1; GU_ERR_STATE while no errands are set;
+ *              GU_ERR_INVALID for a word with a bit at or above F + pb + ib, with j >= I or with p > L_j, and the engine stays as it
+ *              was.  Setting words ends the learners' carries. */
+int gu_set_errands(gu_handle h, const uint8_t *errand /* [S], NULL = no errands again */, int32_t n_instr, const uint8_t instr[4] /* one byte each */, const int32_t pay[3]);
+int gu_get_errands(gu_handle h, uint8_t *errand /* zeros when none */, int32_t *n_instr /* 0 = none set */, uint8_t instr[4], int32_t pay[3], int32_t *n_fruit);
+int gu_get_errands_state(gu_handle h, int64_t env0, int64_t n, uint32_t *words);
+int gu_set_errands_state(gu_handle h, int64_t env0, int64_t n, const uint32_t *words);
+
 /* ---- RNG ---------------------------------------------------------------------
  * Keys the per-env counter RNG (MurmurHash3 of seed, global env id, stream,
  * counter -- 32-bit counters, no stream repeats before 2^32 draws; host view:
@@ -442,8 +500,8 @@ int gu_set_state(gu_handle h, const int32_t *pos, const int32_t *done, const uin
 enum {
     GU_STORE_S = 0,         /* states of the grid; 0 without a grid */
     GU_STORE_N_GRIDS,       /* grids installed (gu_set_grids, gu_generate_mazes) */
-    GU_STORE_OVERLAY,       /* 0 none, 1 wind, 2 fruit, 3 doors, 4 boxes */
-    GU_STORE_OVERLAY_BITS,  /* bits of an env's mask in use: F fruits, D door slots, b * B under boxes, else 0 */
+    GU_STORE_OVERLAY,       /* 0 none, 1 wind, 2 fruit, 3 doors, 4 boxes, 5 errands */
+    GU_STORE_OVERLAY_BITS,  /* bits of an env's mask in use: F fruits, D door slots, b * B under boxes, F + pb + ib under errands, else 0 */
     GU_STORE_TD_ROWS,       /* rows per env of the Q tables (gu_td_init); 0 = none for the current rows */
     GU_STORE_DOUBLE,        /* states of the pairs of tables (gu_double_init); 0 = none */
     GU_STORE_DYNA,          /* states of the models (gu_dyna_init); 0 = none */
@@ -606,7 +664,7 @@ int gu_sweep_get_queue(gu_handle h, int64_t env0, int64_t n, uint64_t *key, int3
 int gu_diag_sweep_heap(gu_handle h, int64_t env0, int64_t n, uint64_t *heap, int32_t *pos);
 /* gu_diag_rollout_form : introspection -- what the last gu_rollout of this engine ran on, as the launcher planned it
  *                      (csrc/gu_rollout_plan.hpp; DESIGN.md "Rollout dispatch").  *count = 12 words; with `form`, capacity >= 12:
- *                      kernel family (1 general, 2 transition-row, 3 K-step, 4 windy, 5 fruit, 6 doors); row layout (0 none, 1 planes, 2 packed, 3 triples);
+ *                      kernel family (1 general, 2 transition-row, 3 K-step, 4 windy, 5 fruit, 6 doors, 7 boxes, 8 errands); row layout (0 none, 1 planes, 2 packed, 3 triples);
  *                      MAP of the general kernel (0 / 1 / 3 / 5), else -1; workgroup size; workgroups; dynamic LDS bytes; flag bits (1 pair
  *                      tables, 2 half waves, 4 per-wave grids, 8 thresholds in LDS, 16 straddles a 2^32-step boundary, 32 first step on the
  *                      table, 64 XCD-aware block order); K of the K-step kernel; log2 of the table's row pitch; staged action words per lane;
