@@ -4,7 +4,7 @@
 // uint32 word per env (gu_engine::d_overlay_mask) that holds the cell of box k in bits [k * b, (k + 1) * b).  Here are the plane's and
 // the words' validation, the box step kernel (gu_step, gu_step_device) and the box rollout kernel (gu_rollout); the slot, the launches'
 // arguments, the words' copies and resets are gu_overlay.hip's and gu_overlay.hpp's; the field arithmetic and the push are gu_map.hpp's
-// (gu_box_at, gu_box_push), shared with the learners' lane (TabLane's BOXES parameter, gu_tabular.hpp; gu_td.hip instantiates it).
+// (gu_box_at, gu_box_push), shared with the learners' lane (BoxOverlay, gu_tabular_overlay.hpp; gu_td.hip instantiates it).
 //
 // THE HOT PATH, decided on purpose (none of it is measured beside an alternative: only the form below was built; what is measured is
 // this kernel beside the doors kernel of the same shape, tools/boxes_rate.py).

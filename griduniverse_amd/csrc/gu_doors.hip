@@ -3,8 +3,8 @@
 // third byte plane behind the engine's two cell planes (gu_engine::d_overlay_cell holds all three in one piece) and one uint32 mask of
 // open slots per env (gu_engine::d_overlay_mask).  Here are the plane's validation, the door step kernel (gu_step, gu_step_device) and
 // the door rollout kernel (gu_rollout); the slot, the launches' arguments, the masks and everything else the overlays share is
-// gu_overlay.hip's and gu_overlay.hpp's; the door learners are instantiations of gu_td_kernel (gu_td.hip, through TabLane's DOORS
-// parameter).
+// gu_overlay.hip's and gu_overlay.hpp's; the door learners are instantiations of gu_td_kernel (gu_td.hip, through DoorOverlay of
+// gu_tabular_overlay.hpp).
 //
 // THE GATE, decided on purpose.  The rule reads door[c] after flags[s] has produced the candidate c: taken literally that is a second
 // dependent LDS read in front of the reads at s', in a loop whose speed is its dependent chain.  A derived 16-bit plane that names,
@@ -17,7 +17,7 @@
 // cost is two VGPRs and three selects per step, and one more round of reads behind a lazy reset (the start cell's bytes).  The
 // derived-plane form was not built, so there is no measured difference between the two to quote; what was measured is this kernel
 // beside the fruit kernel, which has no gate at all (tools/doors_rate.py, profiles/doors_rate.json: 0.98 .. 1.08 of its rate).  The
-// learners' lane (TabLane::move, gu_tabular.hpp) gates the same way, with the bytes of s read beside each other instead of carried.
+// learners' lane (DoorOverlay::move, gu_tabular_overlay.hpp) gates the same way, with the bytes of s read beside each other instead of carried.
 // The step kernel takes one step per launch and reads door[c] behind the candidate, as the rule is written.
 //
 // One lane per env.  The mask stays in a VGPR for the whole launch: one load at the start, one store at the end.  Plain stores, no

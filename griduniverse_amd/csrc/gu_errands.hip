@@ -4,7 +4,7 @@
 // per env -- the fruit eaten, the progress p and the index j of the instruction the env was given at its last reset.  Here are the
 // plane's and the instructions' validation, the words' reset kernel (it DRAWS: stream 11 at the episode count before the reset), the step
 // kernel and the rollout kernel; the slot, the launches' arguments and everything else the overlays share is gu_overlay.hip's and
-// gu_overlay.hpp's; the learners are instantiations of gu_td_kernel (gu_td.hip, through TabLane's ERRANDS parameter).
+// gu_overlay.hpp's; the learners are instantiations of gu_td_kernel (gu_td.hip, through ErrandOverlay of gu_tabular_overlay.hpp).
 //
 // One lane per env, like the fruit kernels.  The three planes are staged in LDS where they fit 64 KiB, else all three are read from
 // L2.  An errand never changes a move: the errand byte of the candidate cell is read BESIDE its flags and its reward byte, so the

@@ -3,7 +3,7 @@
 // planes (gu_engine::d_overlay_cell holds all three in one piece), three engine-wide values and one uint32 "eaten" mask per env
 // (gu_engine::d_overlay_mask).  Here are the plane's validation, the fruit step kernel (gu_step, gu_step_device) and the fruit rollout
 // kernel (gu_rollout); the slot, the launches' arguments, the masks and everything else the overlays share is gu_overlay.hip's and
-// gu_overlay.hpp's; the fruit learners are instantiations of gu_td_kernel (gu_td.hip, through TabLane's FRUIT parameter).
+// gu_overlay.hpp's; the fruit learners are instantiations of gu_td_kernel (gu_td.hip, through FruitOverlay of gu_tabular_overlay.hpp).
 //
 // One lane per env, like the calm kernels.  The three planes are staged in LDS where they fit 64 KiB (gu_lds_block(h, bs, 3)),
 // else all three are read from L2.  Fruit never changes a move: the fruit byte of s' is read BESIDE the flags and the reward byte of

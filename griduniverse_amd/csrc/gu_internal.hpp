@@ -589,6 +589,8 @@ struct RolloutArgs;
 struct GuRolloutPlan;
 struct OverlayStepArgs;
 struct OverlayRolloutArgs;
+struct TabArgs;
+struct OverlayLaneArgs;
 // GU_ERR_UNSUPPORTED unless the engine can take an overlay of `kind`: one grid, no trail, no overlay of another kind
 int gu_overlay_admits(gu_engine *h, int kind);
 // Puts `kind` into the slot: `plane` [S] is the feature's plane, validated by its entry point, `bits` the mask bits in use (0: no
@@ -604,6 +606,7 @@ int gu_overlay_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done)
 int gu_overlay_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t flags, int32_t *host_obs, int32_t *host_reward, int32_t *host_done,
                            uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
 void gu_overlay_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &r);  // (the launch alone: gu_launch_rollout checks and completes it)
+void gu_overlay_lane_args(gu_engine *h, TabArgs &a, OverlayLaneArgs &o);  // (the overlay's part of gu_launch_td's arguments: gu_tabular.hpp)
 // ... and what each feature keeps of them: the ladder from the launch's shape to its kernel's instantiation (gu_wind.hip, gu_fruit.hip, gu_doors.hip,
 // gu_boxes.hip, gu_errands.hip)
 void gu_wind_step(gu_engine *h, bool lds, const OverlayStepArgs &a);

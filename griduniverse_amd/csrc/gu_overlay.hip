@@ -2,7 +2,7 @@
 // An overlay is a third byte plane behind the engine's two cell planes (gu_engine::d_overlay_cell holds all three in one piece, which
 // its kernels stage in LDS where they fit 64 KiB) and, for fruit, doors and boxes, one uint32 mask per env with its value at reset
 // (gu_engine::overlay_init: 0 but for boxes).  Here is everything around a feature's rule: the install path, the getters, the masks'
-// copies, the masks' reset and the arguments of the step and rollout launches.  The features keep their plane's validation and their
+// copies, the masks' reset and the arguments of the step, rollout and learner launches.  The features keep their plane's validation and their
 // kernels (gu_wind.hip, gu_fruit.hip, gu_doors.hip, gu_boxes.hip, gu_errands.hip); errands keep their reset kernel too (it draws).
 #include "gu_overlay.hpp"
 #include "gu_tabular.hpp"  // (gu_env_range, gu_env_copy)
@@ -161,4 +161,11 @@ void gu_overlay_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const Rollo
     a.ret = p.stats ? r.ret : nullptr, a.episodes_fin = p.stats ? r.episodes_fin : nullptr;
     a.N = h->N, a.T = r.T, a.steps_taken = h->steps_taken, a.auto_reset = p.auto_mode ? 1 : 0;
     rollout[h->overlay](h, p, a);
+}
+
+// the overlay block of a learner launch (gu_td.hip), and the three planes in the place of the engine's two
+void gu_overlay_lane_args(gu_engine *h, TabArgs &a, OverlayLaneArgs &o)
+{
+    o.param = h->overlay_param, o.param2 = h->overlay_param2, o.init = h->overlay_init, o.rows = h->td_S, o.word = h->d_overlay_mask;
+    if (h->overlay) a.cell = h->d_overlay_cell;
 }

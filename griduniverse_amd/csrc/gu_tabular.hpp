@@ -8,7 +8,7 @@
 //
 // One lane per env, like the rollout.  Per real step the lane (TabLane)
 //   - draws one word of RNG stream 4, keyed by its 64-bit step count t (epsilon test, explore action, tie break),
-//   - moves with the engine's rule (gu_move on the staged cell map, absorbing terminal),
+//   - moves with the engine's rule (gu_move on the staged cell map, absorbing terminal) or its overlay's (gu_tabular_overlay.hpp),
 //   - reads the row Q[s'] (32 bytes: two 16-byte loads) -- the only dependent gather of the step -- and
 //   - writes back the one updated entry Q[s][a] (8 bytes).
 // The row of the current state stays in VGPRs from one step to the next; a wall bump (s' == s) forwards the updated entry
@@ -107,47 +107,47 @@ __device__ __forceinline__ uint64_t gu_dyna_pack(int32_t s2, int32_t r, int32_t 
     return (uint64_t)(uint32_t)r | ((uint64_t)((uint32_t)s2 | ((uint32_t)d << 31)) << 32);
 }
 
+// ---- the overlay as the lane sees it.  The block of a kernel's arguments that gu_overlay_lane_args (gu_overlay.hip) fills from the slot: ----
+struct OverlayLaneArgs {
+    uint32_t param;         // gu_engine::overlay_param
+    int32_t rows;           // rows of one learner's table (gu_engine::td_S: S << overlay_bits)
+    uint32_t *word;         // [N] the envs' words (gu_engine::d_overlay_mask)
+    uint32_t init, param2;  // gu_engine::overlay_init (the word of an env that has just been reset) and overlay_param2
+};
+
+// ... and no overlay, which lists what a kind supplies (gu_tabular_overlay.hpp holds the five): PLANES of a.cell (2 or 3) and MASKED (the
+// table has a row per (cell, word)); load(): its parameters and the env's word, before begin(); begin(): what it derives from the word,
+// and the word behind the move = the word; reset(): the word of an env just reset (`ep`: the episode count before the reset); commit():
+// step() makes the word behind the move current; key() / key2(): the word and the one behind the move, for row() and row2(); store():
+// the env's word, behind end().  A kind with a plane has move() too (TabLane::move), which takes the whole move in the engine's place.
+struct NoOverlay {
+    static constexpr int PLANES = 2;
+    static constexpr bool MASKED = false;
+    __device__ __forceinline__ void load(const OverlayLaneArgs &, int64_t) {}
+    __device__ __forceinline__ void begin(const uint8_t *) {}
+    __device__ __forceinline__ void reset(uint32_t, uint32_t) {}
+    __device__ __forceinline__ void commit() {}
+    __device__ __forceinline__ uint32_t key() const { return 0u; }
+    __device__ __forceinline__ uint32_t key2() const { return 0u; }
+    __device__ __forceinline__ void store(const OverlayLaneArgs &, int64_t) const {}
+};
+
 // ---- the lane: state, prologue, auto-reset, move, Q[s][a] update, record, epilogue ----
 // A kernel constructs it (staging the map), runs begin .. end on live lanes and ballot on all; its own rule sits between move and step.
 // ROWS = false (gu_fa.hip): the lane has no table of rows of its own -- begin / reset / next_row read nothing from a.q, and the
 // kernel keeps `q` (for gu_fa.hip: the folded row of the current state) itself.
-// WIND (include/gu.h: gu_set_wind; 0 = calm, 1 = wind without gusts, 2 = with gusts): a.cell then carries the wind plane behind the two
-// cell planes (gu_engine::d_overlay_cell; staged with them), the kernel sets `gust_q16` (its own arguments hold it: TabArgs does not),
-// and move() pushes the agent behind its action.  The calm instantiations hold none of it.
-// FRUIT (include/gu.h: gu_set_fruit): a.cell carries the fruit plane behind the two cell planes (gu_engine::d_overlay_cell), the kernel
-// sets `fvalues`, `rows` and `eaten` before begin() and stores `eaten` behind end() (its own arguments hold them), and the table has S << F
-// rows: the lane stands on row eaten * S + s.  move() leaves the mask behind the step in `eaten2`, step() makes it current.  A wall
-// bump onto an uneaten fruit keeps the cell and changes the row, so next_row() and update() compare ROWS, not cells.  The
-// instantiations without fruit hold none of it (row() is s there).
-// DOORS (include/gu.h: gu_set_doors; never with WIND or FRUIT): a.cell carries the door plane behind the two cell planes
-// (gu_engine::d_overlay_cell) and the table has S << D rows.  The env's mask of open slots lives where fruit keeps its mask of eaten
-// fruit -- `eaten` is the mask the lane stands under, `eaten2` the one behind move() --, so the rows and their comparisons are
-// fruit's: the kernel sets `rows` and `eaten` before begin() and stores `eaten` behind end().  move() turns the candidate cell back
-// at a closed door and lets a key or lever of the cell ENTERED change `eaten2`; it reads the candidate's three bytes together and
-// picks behind the gate (the head of gu_doors.hip), so the gate adds no dependent read to a step.
-// BOXES (include/gu.h: gu_set_boxes; never with WIND, FRUIT or DOORS): a.cell carries the box plane behind the two cell planes and the
-// table has S << (b * B) rows.  The env's word of box cells lives where the masks live -- `eaten` the word the lane stands under,
-// `eaten2` the one behind move() --, so the rows and their comparisons are the masked ones.  The kernel sets `rows`, `eaten`, `bparam`
-// (GU_BOX_PARAM) and `binit` (the word at reset) before begin() and stores `eaten` behind end().  The lane carries the count of boxes on
-// a target beside the word (`on`, `on2`), as the rollout kernel does (the head of gu_boxes.hip); move() applies rules 2-6 of
-// gu_set_boxes, the push behind a branch that only pushing lanes take.
-// ERRANDS (include/gu.h: gu_set_errands; never with another kind): a.cell carries the errand plane (fruit's format) behind the two cell
-// planes and the table has S << (F + pb + ib) rows.  The env's word (eaten | progress | instruction) lives where the masks live, so the
-// rows and their comparisons are the masked ones.  The kernel sets `rows`, `eaten`, `fvalues` (the instructions) and `eparam2`
-// (GU_ERRAND_PARAM2) before begin() and stores `eaten` behind end().  The lane carries `rem`, its instruction byte shifted right by
-// 2p, beside the word (`rem2` behind move()), as the rollout kernel does (the head of gu_errands.hip); reset() draws the instruction
-// on stream 11 and move() applies rules 2-5 of gu_set_errands.
-template <bool LDS, bool ROWS = true, int WIND = 0, bool FRUIT = false, bool DOORS = false, bool BOXES = false, bool ERRANDS = false>
+// OV (gu_td.hip alone sets it): the engine's overlay, one of the structs of gu_tabular_overlay.hpp.  The lane stages OV::PLANES planes,
+// hands the rule of a move to `ov` and, under OV::MASKED, stands on row ov.key() * S + s of a table of `rows` rows; a wall bump may
+// then keep the cell and change the row, so next_row() and update() compare ROWS, not cells.  The kernel calls load() before begin()
+// and store() behind end().  The calm instantiations hold none of it.  (Where `ov` stands among the members decides the order of the
+// loop's register copies in some instantiations: profiles/learner_overlay_asm.txt.)
+template <bool LDS, bool ROWS = true, class OV = NoOverlay>
 struct TabLane {
-    static constexpr bool MASKED = FRUIT || DOORS || BOXES || ERRANDS;  // the table has a row per (cell, mask)
+    static constexpr bool MASKED = OV::MASKED;
     CellMap m;
-    const uint8_t *wd;  // WIND: the wind plane; FRUIT: the fruit plane; DOORS: the door plane; BOXES: the box plane; ERRANDS: the errand plane
-    uint32_t gust_q16;  // WIND == 2
-    uint32_t fvalues;   // FRUIT: the kinds' values; ERRANDS: the instructions
-    uint32_t eparam2, rem, rem2;  // ERRANDS: the second parameter word, the rest of the env's instruction under `eaten` and behind move()
-    uint32_t bparam, binit, on, on2;  // BOXES: the parameter word, the word at reset, boxes on a target under `eaten` and behind move()
-    uint32_t eaten, eaten2;  // MASKED: the env's mask (eaten fruit / open slots / box cells / errand word), and the one behind move()
-    int32_t S, rows;         // MASKED: states, and rows of one learner's table (S << F, S << D)
+    const uint8_t *wd;  // OV::PLANES == 3: the overlay's plane, behind the two cell planes (gu_engine::d_overlay_cell)
+    int32_t S, rows;  // MASKED: states, and rows of one learner's table (S << bits)
+    OV ov;
     LaneGrid lg;
     int64_t e;
     uint32_t env, start_prefix, prefix, ep;
@@ -158,12 +158,14 @@ struct TabLane {
 
     __device__ __forceinline__ TabLane(const TabArgs &a, uint8_t *smem)
     {
-        m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, (WIND || MASKED) ? 3 : 2);
-        if (WIND || MASKED) wd = m.f + 2 * a.cell_bytes;
+        m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, OV::PLANES);
+        if (OV::PLANES == 3) wd = m.f + 2 * a.cell_bytes;
         if (MASKED) S = a.S;
         e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
         d = 0;
     }
+
+    __device__ __forceinline__ void load(const OverlayLaneArgs &o) { rows = o.rows, ov.load(o, e); }
 
     __device__ __forceinline__ void begin(const TabArgs &a)
     {
@@ -174,9 +176,7 @@ struct TabLane {
         // stream 4: the epoch t >> 32 hashed behind the seed, hoisted; recomputed in the step that crosses a multiple of 2^32
         prefix = gu_rng_prefix(gu_rng_seed_prefix_epoch(a.seed_prefix, (uint32_t)(t >> 32)), env);
         qe = ROWS ? a.q + (MASKED ? e * rows : e * a.S) * 4 : nullptr;
-        if (MASKED) eaten2 = eaten;
-        if (BOXES) on = on2 = gu_box_on_target(wd, eaten, GU_BOX_B(bparam), GU_BOX_BITS(bparam));
-        if (ERRANDS) rem = rem2 = gu_errand_rem(eaten, fvalues, eparam2);
+        if (OV::PLANES == 3) ov.begin(wd);
         s = a.pos[e];
         r = a.reward[e];
         d = a.done[e];
@@ -194,19 +194,14 @@ struct TabLane {
             s = lg.starts[gu_rng_start_index(start_prefix, ep, lg.n_starts)];
             ++ep;
             d = 0;
-            if (MASKED) eaten = eaten2 = 0u;  // the fruit grows back; the doors are shut again
-            if (BOXES) eaten = eaten2 = binit, on = on2 = GU_BOX_ON0(bparam);  // the boxes are back where they began
-            if (ERRANDS) {  // another instruction, drawn at the episode count before the reset
-                gu_errand_draw(start_prefix, ep - 1u, fvalues, eparam2, eaten, rem);
-                eaten2 = eaten, rem2 = rem;
-            }
+            ov.reset(start_prefix, ep - 1u);
             if (ROWS) q = gu_q_load(qe + row() * 4);
         }
     }
 
     // the table row the lane stands on, and the one it stands on behind move()
-    __device__ __forceinline__ int64_t row() const { return MASKED ? (int64_t)eaten * S + s : (int64_t)s; }
-    __device__ __forceinline__ int64_t row2(int32_t s2) const { return MASKED ? (int64_t)eaten2 * S + s2 : (int64_t)s2; }
+    __device__ __forceinline__ int64_t row() const { return MASKED ? (int64_t)ov.key() * S + s : (int64_t)s; }
+    __device__ __forceinline__ int64_t row2(int32_t s2) const { return MASKED ? (int64_t)ov.key2() * S + s2 : (int64_t)s2; }
 
     // the stream-4 word of step t
     __device__ __forceinline__ uint32_t word() const { return gu_rng_word(prefix, GU_RNG_STREAM_TD, (uint32_t)t); }
@@ -214,46 +209,12 @@ struct TabLane {
     // take action ua from s: sets r and d, advances t (re-keying stream 4 where t crosses a multiple of 2^32), returns s'
     __device__ __forceinline__ int32_t move(const TabArgs &a, uint32_t ua)
     {
-        int32_t s2 = gu_move(s, m.f[s], ua, gu_delta<LDS>(ua, a.lut, a.W));
-        if (WIND) {  // the wind of the cell the agent leaves, gusting on the stream-9 word of step t (hashed only where some lane stands in wind)
-            const uint32_t c = wd[s];
-            uint32_t k = GU_WIND_STRENGTH(c);
-            if (WIND == 2 && __builtin_amdgcn_ballot_w64(k > 0u) != 0ull) k = gu_wind_gust(k, gu_rng_word(prefix, GU_RNG_STREAM_WIND, (uint32_t)t), gust_q16);
-            s2 = gu_wind_push<LDS>(m.f, s2, c, k, a.lut, a.W);
-        }
-        if (BOXES) {
-            // rules 2-6 of gu_set_boxes on the candidate s2 (gu_boxes_move of gu_boxes.hip, with the bytes of s' read behind the push)
-            const uint32_t B = GU_BOX_B(bparam), b = GU_BOX_BITS(bparam);
-            const bool solved = on == B;
-            const int32_t c = s2, at = gu_box_at(eaten, c, B, b), k = ((c != s) & !solved) ? at : -1;
-            bool stay = solved;
-            int32_t gain = 0;
-            eaten2 = eaten;
-            if (k >= 0) stay = gu_box_push(m.f, wd, c, m.f[c], wd[c], ua, gu_delta<LDS>(ua, a.lut, a.W), k, B, b, eaten2, gain);
-            s2 = stay ? s : c;
-            on2 = on + (uint32_t)gain;
-            const bool won = on2 == B;
-            r = won ? GU_BOX_SOLVED_REWARD : m.r[s2] + GU_BOX_V(bparam) * gain;
-            d = won ? 1 : (m.f[s2] >> GU_CELL_TERM_BIT) & 1;
-        } else if (ERRANDS) {
-            // rules 2-5 of gu_set_errands on the candidate s2, its three bytes read together; a completed word keeps the cell behind the reads
-            const int32_t c = s2;
-            eaten2 = eaten, rem2 = rem;
-            const bool stay = gu_errand_touch(wd[c], m.r[c], (m.f[c] >> GU_CELL_TERM_BIT) & 1, eparam2, eaten2, rem2, r, d);
-            s2 = stay ? s : c;
-        } else if (DOORS) {
-            // A closed door refuses entry as a wall does; the key or lever of a cell entered changes the mask behind the step.  The door
-            // byte of the candidate is read BESIDE its flags and reward byte, and the gate picks between them and the bytes of s (its
-            // reward byte is read beside its flags): two rounds of reads on the chain, as without doors.
-            const uint32_t c = wd[s2];
-            const bool shut = gu_door_closed(c, eaten);
-            eaten2 = gu_door_touch(c, eaten, !shut && s2 != s);
-            r = shut ? m.r[s] : m.r[s2];
-            d = ((shut ? m.f[s] : m.f[s2]) >> GU_CELL_TERM_BIT) & 1;
-            s2 = shut ? s : s2;
+        int32_t s2;
+        if constexpr (OV::PLANES == 3) {
+            s2 = ov.template move<LDS>(*this, a, ua);  // the overlay's rule in the place of the engine's
         } else {
+            s2 = gu_move(s, m.f[s], ua, gu_delta<LDS>(ua, a.lut, a.W));
             r = m.r[s2];
-            if (FRUIT) r += gu_fruit_eat(wd[s2], fvalues, eaten2);  // (read beside the flags and the reward byte of s': the chain does not grow)
             d = (m.f[s2] >> GU_CELL_TERM_BIT) & 1;
         }
         ++t;
@@ -283,9 +244,7 @@ struct TabLane {
     {
         q = n;
         s = s2;
-        if (MASKED) eaten = eaten2;
-        if (BOXES) on = on2;
-        if (ERRANDS) rem = rem2;
+        ov.commit();
         if (a.tr_obs) {
             const int64_t row = (int64_t)i * a.N + e;
             a.tr_obs[row] = s2;
@@ -295,6 +254,8 @@ struct TabLane {
         ret += r;
         fin += d;
     }
+
+    __device__ __forceinline__ void store(const OverlayLaneArgs &o) const { ov.store(o, e); }
 
     __device__ __forceinline__ void end(const TabArgs &a) const
     {

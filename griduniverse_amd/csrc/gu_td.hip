@@ -1,45 +1,31 @@
 // gu_td.hip -- batched tabular Q-learning, SARSA and Expected SARSA for gfx950 (include/gu.h: gu_td_run, gu_esarsa_run; restated on
 // the CPU by tests/_td_oracle.py and tests/_double_oracle.py).  The lane, the Q-row rules, the layout and the rounding are
-// gu_tabular.hpp's; what is here is the update rule: Q-learning bootstraps on max_a Q[s'][a], SARSA draws its next action a' from
+// gu_tabular.hpp's, the overlays' rules gu_tabular_overlay.hpp's; what is here is the update rule: Q-learning bootstraps on max_a Q[s'][a], SARSA draws its next action a' from
 // Q[s'] with the next stream-4 word (unless s' is terminal), bootstraps on Q[s'][a'] and takes a' in the next step -- across launches
 // too, through next_a.  Expected SARSA acts as Q-learning does and bootstraps on the mean of Q[s'] under the epsilon-greedy policy:
 // pe * (the row's sum) + pg * (its maximum), pe = eps / 4 and pg = 1 - eps from the host -- no division, whatever the number of ties.
-#include "gu_tabular.hpp"
+#include "gu_tabular_overlay.hpp"  // (gu_tabular.hpp)
 
 #include <algorithm>
 
 struct TdArgs : TabArgs {
     int8_t *next_a;  // [N] SARSA: the action carried to the next launch (-1: none)
     int32_t carry;   // 1: this launch directly follows a SARSA launch on the same engine -- start with next_a
-    uint32_t gust_q16;  // the windy instantiations: the engine's gust probability (gu_set_wind); a.cell then holds three planes
-    // the fruit instantiations (gu_set_fruit; a.cell holds three planes): the kinds' values, the envs' masks, the rows of one table (S << F)
-    uint32_t fruit_values;
-    int32_t rows;
-    uint32_t *eaten;  // (the door instantiations, gu_set_doors: the envs' masks of open slots, and rows = S << D)
-    uint32_t box_init;  // the box instantiations (gu_set_boxes): fruit_values holds GU_BOX_PARAM, eaten the envs' words, rows = S << (b * B)
-    uint32_t param2;  // the errand instantiations (gu_set_errands): fruit_values holds the instructions, param2 GU_ERRAND_PARAM2, eaten the envs' words
+    OverlayLaneArgs ov;  // the engine's overlay (gu_overlay_lane_args; a.cell then holds three planes)
     double pe, pg;    // TD_ESARSA: eps_q16 * 2^-18 and (65536 - eps_q16) * 2^-16, both exact
 };
 
 enum TdRule { TD_Q = 0, TD_SARSA = 1, TD_ESARSA = 2 };  // (the first two are gu_td_run's method numbers)
 
-// WIND: 0 = calm, 1 = wind without gusts (no stream-9 hash in the code), 2 = with gusts (gu_tabular.hpp: TabLane)
-// FRUIT: the table has S << F rows and the lane learns on row eaten * S + s (TabLane); never together with WIND
-// DOORS: the table has S << D rows and the lane learns on row open * S + s; never together with WIND or FRUIT
-// BOXES: the table has S << (b * B) rows and the lane learns on row word * S + s; never together with WIND, FRUIT or DOORS
-// ERRANDS: the table has S << (F + pb + ib) rows and the lane learns on row word * S + s; never together with another kind
-template <TdRule RULE, bool LDS, int WIND = 0, bool FRUIT = false, bool DOORS = false, bool BOXES = false, bool ERRANDS = false>
+// OV: the engine's overlay (gu_tabular_overlay.hpp); under a MASKED one the table has S << bits rows and the lane learns on row word * S + s
+template <TdRule RULE, bool LDS, class OV = NoOverlay>
 __global__ void __launch_bounds__(GU_BLOCK) gu_td_kernel(const TdArgs a)
 {
     constexpr bool SARSA = RULE == TD_SARSA;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    TabLane<LDS, true, WIND, FRUIT, DOORS, BOXES, ERRANDS> L(a, smem);
-    if (WIND == 2) L.gust_q16 = a.gust_q16;
+    TabLane<LDS, true, OV> L(a, smem);
     if (L.e < a.N) {
-        if (FRUIT) L.fvalues = a.fruit_values;
-        if (BOXES) L.bparam = a.fruit_values, L.binit = a.box_init;
-        if (ERRANDS) L.fvalues = a.fruit_values, L.eparam2 = a.param2;
-        if (FRUIT || DOORS || BOXES || ERRANDS) L.rows = a.rows, L.eaten = a.eaten[L.e];
+        L.load(a.ov);
         L.begin(a);
         int32_t act = (SARSA && a.carry) ? (int32_t)a.next_a[L.e] : -1;
         for (int32_t i = 0; i < a.T; ++i) {
@@ -68,7 +54,7 @@ __global__ void __launch_bounds__(GU_BLOCK) gu_td_kernel(const TdArgs a)
             L.step(a, i, s2, n);
         }
         L.end(a);
-        if (FRUIT || DOORS || BOXES || ERRANDS) a.eaten[L.e] = L.eaten;
+        L.store(a.ov);
         if (SARSA) a.next_a[L.e] = (int8_t)act;
     }
     L.ballot(a);
@@ -94,35 +80,25 @@ static int gu_launch_td(gu_engine *h, int64_t T, int32_t method, double alpha, d
     gu_tabular_args(h, a, T, alpha, gamma, eps_q16, flags);
     a.next_a = h->d_td_next;
     a.carry = (method == 1 && gu_carry_is(h, GU_CARRY_TD_SARSA, 0)) ? 1 : 0;
-    // the overlay's instantiations, on [flags | reward | overlay]; fruit and doors learn on S << bits rows and keep the env's mask in `eaten`
-    a.gust_q16 = a.fruit_values = h->overlay_param, a.rows = h->td_S, a.eaten = h->d_overlay_mask, a.box_init = h->overlay_init, a.param2 = h->overlay_param2;
-    if (h->overlay) a.cell = h->d_overlay_cell;
+    gu_overlay_lane_args(h, a, a.ov);
     a.pe = (double)eps_q16 * 0x1p-18, a.pg = (double)(65536u - eps_q16) * 0x1p-16;
-    int rc;
-    if (method == TD_ESARSA) {  // (calm only: gu_esarsa_run refuses while an overlay is set)
-        rc = gu_tabular_launch(h, gu_td_kernel<TD_ESARSA, true>, gu_td_kernel<TD_ESARSA, false>, a);
-    } else if (h->overlay == GU_OVERLAY_ERRANDS) {
-        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 0, false, false, false, true>, gu_td_kernel<TD_SARSA, false, 0, false, false, false, true>, a, GU_BLOCK, 0, 3)
-                         : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 0, false, false, false, true>, gu_td_kernel<TD_Q, false, 0, false, false, false, true>, a, GU_BLOCK, 0, 3);
-    } else if (h->overlay == GU_OVERLAY_BOXES) {
-        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 0, false, false, true>, gu_td_kernel<TD_SARSA, false, 0, false, false, true>, a, GU_BLOCK, 0, 3)
-                         : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 0, false, false, true>, gu_td_kernel<TD_Q, false, 0, false, false, true>, a, GU_BLOCK, 0, 3);
-    } else if (h->overlay == GU_OVERLAY_DOORS) {
-        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 0, false, true>, gu_td_kernel<TD_SARSA, false, 0, false, true>, a, GU_BLOCK, 0, 3)
-                         : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 0, false, true>, gu_td_kernel<TD_Q, false, 0, false, true>, a, GU_BLOCK, 0, 3);
-    } else if (h->overlay == GU_OVERLAY_FRUIT) {
-        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 0, true>, gu_td_kernel<TD_SARSA, false, 0, true>, a, GU_BLOCK, 0, 3)
-                         : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 0, true>, gu_td_kernel<TD_Q, false, 0, true>, a, GU_BLOCK, 0, 3);
-    } else if (h->overlay == GU_OVERLAY_WIND) {
-        if (h->overlay_param)  // (gusts)
-            rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 2>, gu_td_kernel<TD_SARSA, false, 2>, a, GU_BLOCK, 0, 3)
-                             : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 2>, gu_td_kernel<TD_Q, false, 2>, a, GU_BLOCK, 0, 3);
-        else
-            rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true, 1>, gu_td_kernel<TD_SARSA, false, 1>, a, GU_BLOCK, 0, 3)
-                             : gu_tabular_launch(h, gu_td_kernel<TD_Q, true, 1>, gu_td_kernel<TD_Q, false, 1>, a, GU_BLOCK, 0, 3);
-    } else {
-        rc = method == 1 ? gu_tabular_launch(h, gu_td_kernel<TD_SARSA, true>, gu_td_kernel<TD_SARSA, false>, a)
-                         : gu_tabular_launch(h, gu_td_kernel<TD_Q, true>, gu_td_kernel<TD_Q, false>, a);
+    // the overlay and the rule become template arguments here, each once (Expected SARSA is calm only: gu_esarsa_run refuses an overlay)
+    int rc = GU_OK;
+    auto launch = [&](auto ov) {
+        using OV = decltype(ov);
+        gu_pick<TD_Q, TD_SARSA, TD_ESARSA>(method, [&](auto rule) {
+            constexpr TdRule RULE = (TdRule) decltype(rule)::value;
+            if constexpr (RULE != TD_ESARSA || OV::PLANES == 2)
+                rc = gu_tabular_launch(h, gu_td_kernel<RULE, true, OV>, gu_td_kernel<RULE, false, OV>, a, GU_BLOCK, 0, OV::PLANES);
+        });
+    };
+    switch (h->overlay) {
+    case GU_OVERLAY_WIND: h->overlay_param ? launch(WindOverlay<true>{}) : launch(WindOverlay<false>{}); break;  // (gusts or none)
+    case GU_OVERLAY_FRUIT: launch(FruitOverlay{}); break;
+    case GU_OVERLAY_DOORS: launch(DoorOverlay{}); break;
+    case GU_OVERLAY_BOXES: launch(BoxOverlay{}); break;
+    case GU_OVERLAY_ERRANDS: launch(ErrandOverlay{}); break;
+    default: launch(NoOverlay{});
     }
     return rc != GU_OK ? rc : gu_tabular_after(h, T, flags, method == 1 ? GuCarry{GU_CARRY_TD_SARSA, 0} : GuCarry{});
 }

@@ -4,7 +4,7 @@
 // (gu_map.hpp: gu_wind_push).  Here are the
 // plane's validation, the windy step kernel (gu_step, gu_step_device) and the windy rollout kernel (gu_rollout); the slot, the launches'
 // arguments and everything else the overlays share is gu_overlay.hip's and gu_overlay.hpp's; the windy learners are instantiations
-// of gu_td_kernel (gu_td.hip, through TabLane's WIND parameter).
+// of gu_td_kernel (gu_td.hip, through WindOverlay of gu_tabular_overlay.hpp).
 //
 // One lane per env, like the calm kernels.  The three planes are staged in LDS where they fit 64 KiB (gu_lds_block(h, bs, 3)),
 // else all three are read from L2.  A windy step is a chain of 2 + k dependent plane reads (the wind byte and the flags of the
