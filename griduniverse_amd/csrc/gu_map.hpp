@@ -65,10 +65,18 @@ __device__ __forceinline__ LaneGrid gu_lane_grid(const GridSel &gs, const int32_
 }
 
 // delta[a]: LUT = four int16 lanes {-W, +1, +W, -1}; ARITH = any W (grids too big for the LUT / LDS)
-template <bool LUT>
+// SHIFT64: the lookup as ONE 64-bit shift by 16 a (v_lshrrev_b64) -- or, false, a select between the LUT's halves and a 16-bit field
+// of the one selected (32-bit instructions only, one more of them).  The 64-bit shift has a FAULT on gfx950: when the register that
+// holds its shift amount is the LAST of the wave's VGPR allocation (v63 of 64, v31 of 32) and other waves share the SIMD, it now and
+// then shifts by the low six bits of what lies behind the allocation -- the lane index, v0 of the neighbour's registers -- instead:
+// the move's delta is then lut >> lane, the env leaves the grid (docs/HISTORY.md "64-bit shift by the last VGPR";
+// tests/test_gpu_launch_shapes.py saw it, tests/test_shift_amount_register.py keeps every kernel of the built library clear of it).
+// Where the register allocator puts the amount is not ours to say, so only the kernels measured with the one shift keep it.
+template <bool LUT, bool SHIFT64 = true>
 __device__ __forceinline__ int32_t gu_delta(uint32_t a, uint64_t lut, int32_t W)
 {
-    if (LUT) return __builtin_amdgcn_sbfe((int32_t)(uint32_t)(lut >> (a << 4)), 0, 16);
+    if (LUT && SHIFT64) return __builtin_amdgcn_sbfe((int32_t)(uint32_t)(lut >> (a << 4)), 0, 16);
+    if (LUT) return __builtin_amdgcn_sbfe((int32_t)(a > 1u ? (uint32_t)(lut >> 32) : (uint32_t)lut), (a & 1u) << 4, 16);
     const int32_t sign = (int32_t)(a & 2u) - 1;  // UP,RIGHT -> -1 ; DOWN,LEFT -> +1
     return (a & 1u) ? -sign : sign * W;
 }

@@ -474,6 +474,10 @@ template <int POLICY, int AUTO, int TRAJ, bool STATS, int MAP>
 __global__ void __launch_bounds__(GU_MAX_BLOCK) gu_rollout_kernel(const RolloutArgs a)
 {
     constexpr bool LDS = MAP == 1 || MAP == 3;
+    // the move's delta by one 64-bit shift only in the launches that write int32 rows, which were measured with it (the headline among
+    // them); the others look it up in 32-bit halves: gu_map.hpp, gu_delta -- the statistics-only stream launch without auto-reset lost
+    // envs to that shift at workgroups of 512 and 1024
+    constexpr bool SHIFT64 = TRAJ == 1 || TRAJ == 3;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     // this lane's state is asked for BEFORE the grid is staged, so that the two round trips to memory overlap (at the start of a
     // launch the loads queue behind what is left of the previous launch's stores: ~1 us each)
@@ -562,7 +566,7 @@ __global__ void __launch_bounds__(GU_MAX_BLOCK) gu_rollout_kernel(const RolloutA
     auto move5 = [&](uint32_t act, int32_t delta, auto &&in_the_shadow) {
         int32_t cand = s + delta;
         asm volatile("" : "+v"(cand));  // (kept as the sum it is: select(go, s + delta, s), not s + select(go, delta, 0) with its sign extension)
-        const int32_t candq = sq + gu_delta<true>(act, a.lut_p, 0);
+        const int32_t candq = sq + gu_delta<true, SHIFT64>(act, a.lut_p, 0);
         const uint32_t word = word_at(candq);
         in_the_shadow();  // (what the caller has to issue that does not depend on the gather: the row stores of the step before)
         const uint32_t four = four_of(word, candq);
@@ -630,7 +634,7 @@ __global__ void __launch_bounds__(GU_MAX_BLOCK) gu_rollout_kernel(const RolloutA
 
     // `soff`: wave-uniform byte offset of this step's row from the resource base
     auto step = [&](uint32_t act, uint32_t soff) {
-        const int32_t delta = gu_delta<MAP != 0>(act, lut, W);
+        const int32_t delta = gu_delta<MAP != 0, SHIFT64>(act, lut, W);
         if (AUTO == 1) {
             // lazy `if done: env.reset()` (env:187-193) with a single start cell: two selects keyed directly on the
             // TERM bit of the record that just arrived (no separate done register on the dependent chain).  A variant

@@ -27,97 +27,9 @@ from griduniverse_amd import Engine, GridSpec
 from oracle import c_oracle as C
 from tests import _golden as G
 from tests._mazes import oracle_grid, random_specs
+from tests._rollout_shapes import LAUNCHES, POLICIES, STATE_KEYS, _diff, _general, _multi_oracle_and_engine, _oracle_and_engine, _policy_table, _run, spec_of
 
 pytestmark = pytest.mark.gpu
-
-LAUNCHES = (21, 67)
-POLICIES = ['uniform', 'stream', 'greedy', 'sample']
-STATE_KEYS = ('pos', 'done', 'episode', 'tcount')
-
-
-def spec_of(meta):
-    return GridSpec(meta['W'], meta['H'], meta['starts'], meta['goals'], meta['lava'], meta['walls'], meta['reward'])
-
-
-def _policy_table(policy, S, seed=3):
-    """greedy: a one-hot policy (the oracle follows `pi`, the engine its argmax); sample: rows with exact zeros and ones among them."""
-    rs = np.random.RandomState(seed)
-    if policy == 'greedy':
-        return np.eye(4)[rs.randint(0, 4, S)]
-    if policy == 'sample':
-        pi = rs.dirichlet(np.ones(4) * 0.5, S)
-        hot = rs.rand(S) < 0.35
-        pi[hot] = np.eye(4)[rs.randint(0, 4, int(hot.sum()))]
-        return pi
-    return None
-
-
-def _diff(got, want):
-    """What differs, for the assertion message: how many words, and in which lanes of sixteen (the hazard's signature: 12 .. 15)."""
-    bad = np.asarray(got) != np.asarray(want)
-    lanes = np.bincount(np.nonzero(bad)[-1] % 16, minlength=16) if bad.ndim else bad
-    return '%d of %d words differ; by env %% 16: %s' % (int(bad.sum()), bad.size, lanes.tolist())
-
-
-def _oracle_and_engine(meta, N, seed, env_id0=0):
-    grid = C.Grid.from_lists(**meta)
-    st = C.State(N, env_id0)
-    eng = Engine(N, spec_of(meta), seed=seed, env_id0=env_id0)
-    assert np.array_equal(eng.reset(), C.reset(grid, seed, st))
-    return grid, st, eng
-
-
-def _multi_oracle_and_engine(specs, N, seed, env_id0=0):
-    """Engine on several grids (env e on specs[e // (N // len(specs))]) and one oracle (grid, state, env slice) per grid."""
-    group = N // len(specs)
-    eng = Engine(N, specs[0], seed=seed, env_id0=env_id0)
-    eng.set_grids(specs)
-    first = eng.reset()
-    parts = []
-    for g, spec in enumerate(specs):
-        sl = slice(g * group, (g + 1) * group)
-        grid, st = oracle_grid(spec), C.State(group, env_id0 + g * group)
-        assert np.array_equal(C.reset(grid, seed, st), first[sl]), g
-        parts.append((grid, st, sl))
-    return parts, eng
-
-
-def _launch_and_compare(eng, parts, seed, T, policy, auto, expect, tag, table=None, acts_seed=0):
-    """One launch of T steps: the form is `expect`, rows / statistics / state are the oracle's (parts: (grid, state, env slice))."""
-    acts = None
-    if policy == 'stream':
-        acts = np.random.RandomState(1000 + acts_seed).randint(0, 4, (T, eng.N)).astype(np.int32)
-        eng.upload_actions(acts)
-    eng.rollout(T, policy, auto, True, stats=True)
-    form = eng.rollout_last_form()
-    assert {k: form[k] for k in expect} == expect, (tag, T, form)
-    got = eng.read_trajectory(0, T)
-    ret, eps = eng.read_stats()
-    state = eng.get_state()
-    for grid, st, sl in parts:
-        kw = dict(actions=acts[:, sl]) if acts is not None else dict(pi=table) if table is not None else {}
-        want = C.rollout(grid, seed, st, T, auto, stats=True, **kw)
-        for k in ('obs', 'reward', 'done'):
-            assert np.array_equal(got[k][:, sl], want[k]), (tag, T, k, sl, _diff(got[k][:, sl], want[k]))
-        assert np.array_equal(ret[sl], want['ret']) and np.array_equal(eps[sl], want['episodes']), (tag, T, 'statistics', sl)
-        for k in STATE_KEYS:
-            assert np.array_equal(state[k][sl], getattr(st, k)), (tag, T, k, sl)
-
-
-def _run(eng, parts, seed, policy, auto, expect, tag, table=None, launches=LAUNCHES):
-    """The launches of every case on one engine, each continuing the one before; `expect`: the form, or launch index -> form."""
-    with eng:
-        eng.reserve_trajectory(max(launches))
-        if table is not None:
-            eng.vi_set(np.zeros(table.shape[0]), table)
-        for i, T in enumerate(launches):
-            _launch_and_compare(eng, parts, seed, T, policy, auto, expect(i) if callable(expect) else expect, tag, table, acts_seed=i)
-
-
-def _general(map_, block, **bits):
-    form = dict(family='general', layout=3, map=map_, block=block, pair=False, half=False, per_wave=False, straddle=False)
-    form.update(bits)
-    return form
 
 
 # ---- 1. the general kernel, one grid in LDS (MAP 1) -----------------------------------------------------------------------------
@@ -271,8 +183,9 @@ def test_row_kernel_with_and_without_pairs_and_half_waves(gu_option, rows, polic
     planner's rule, gu_plan_rows -- triples go to the pairs under the uniform policy up to a workgroup per four CUs), whole waves
     and half waves (rollout_half_waves).  2080 = 65 x 32 envs: with half waves 128 envs per workgroup, an odd number of half waves,
     the last workgroup holds one; 2120 is no multiple of 32, the planner must then refuse half waves and the rows are right all the
-    same.  The row kernel's workgroup stays at 256 here: it grows only when several workgroups share a CU's LDS, which takes far
-    more envs (hundreds of thousands on a 32 x 32 grid) than a seconds-long test has."""
+    same.  The row kernel's workgroup stays at 256 here: it grows to 512 when one table takes more than half a CU's LDS and the batch
+    needs more than one 256-lane workgroup per CU -- 256 x CUs + 64 envs on a 72 x 72 grid already; tests/test_gpu_launch_shapes.py
+    runs that shape, the triples among its row layouts."""
     gu_option('traj_layout', 1)
     gu_option('rollout_rows', rows)
     info = Engine.device_info(0)
