@@ -21,6 +21,7 @@ class FruitOracle(OverlayOracle):
 
     def __init__(self, grid, seed, n, fruit=None, values=(0, 0, 0), env_id0=0, q0=0.0):
         super().__init__(grid, seed, n, env_id0, q0)
+        self.log = dict(eaten=0)  # fruit eaten
         self.set_fruit(fruit, values)
 
     def set_fruit(self, fruit, values=(0, 0, 0)):
@@ -55,6 +56,7 @@ class FruitOracle(OverlayOracle):
         bit = np.where(kind != 0, np.int64(1) << (c & 31), 0).astype(np.uint32)
         fresh = (bit & ~self.eaten) != 0
         r = (r + np.where(fresh, self.value[kind], 0)).astype(np.int32)
+        self.log['eaten'] += int((fresh & who).sum())
         st.pos[who] = s2[who]
         st.done[who] = d[who]
         self.reward[who] = r[who]

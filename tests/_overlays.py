@@ -1,7 +1,8 @@
 """The overlay kinds of an engine (csrc/gu_overlay.hip; DESIGN.md "Overlays"), one entry each, for the tests that treat them alike: the
 slot and refusal tests of tests/test_gpu_overlay.py, the cases of tests/_overlay_starts.py, and the kinds' own device files.  An entry
 knows how to install its plane on an engine and take it away, how to read the plane, its parameters and the per-env masks back, what
-a plane means for the slot (mask bits, reset value), a plane that the kind's own validation refuses, and the kind's CPU restatement.
+a plane means for the slot (mask bits, reset value, the bits a reset sets), a plane that the kind's own validation refuses, and the
+kind's CPU restatement.
 Beside the table: the calls that have no overlay form, and the helpers that every kind's device file used to copy.  Nothing here needs
 a device."""
 import collections
@@ -9,8 +10,11 @@ import types
 
 import numpy as np
 
+from griduniverse_amd.grid import errand_bytes
+
 from . import _boxes_oracle as BO
 from . import _doors_oracle as DO
+from . import _errands_oracle as EO
 from . import _fruit_oracle as FO
 from . import _wind_oracle as WO
 from ._td_oracle import Q_LEARNING, SARSA
@@ -58,6 +62,28 @@ class Overlay(object):
     def masks_of(self, o):
         return getattr(o, self.state) if self.state else None
 
+    def reset_bits(self, plane):
+        """The bits of a mask that a reset sets to reset_value(plane): all of them."""
+        return 0xFFFFFFFF
+
+
+class Errands(Overlay):
+    """`extra` is (instructions, pay) as the restatement takes them; the engine takes the instruction bytes, their count and the pay.
+    A reset clears the eaten bits and the progress and DRAWS the instruction's index above them (stream 11: tests/test_gpu_errands.py
+    holds the draw against the restatement); the install leaves index 0 in every word."""
+
+    def install(self, eng, plane, *extra):
+        instructions, pay = extra or self.extra
+        eng.set_errands(plane, errand_bytes([list(i) for i in instructions]), len(instructions), np.array(pay, np.int32))
+
+    def reset_bits(self, plane):
+        return (1 << (self.bits(plane) - (len(self.extra[0]) - 1).bit_length())) - 1
+
+
+def errand_bits(plane, instructions):
+    """F + pb + ib: a bit per fruit, the progress 0 .. the longest list, the instruction's index."""
+    return int(np.count_nonzero(plane)) + max(len(i) for i in instructions).bit_length() + (len(instructions) - 1).bit_length()
+
 
 def _with(plane, cell, byte, clear=False):
     p = np.zeros_like(plane) if clear else plane.copy()
@@ -73,7 +99,7 @@ def _box_word(plane):
     return sum(int(s) << (k * _box_bits(plane)) for k, s in enumerate(np.flatnonzero(plane & BO.INITIAL)))
 
 
-OVERLAYS = collections.OrderedDict((k.name, k) for k in (  # in the order of stores()['overlay']: 1 wind, 2 fruit, 3 doors, 4 boxes
+OVERLAYS = collections.OrderedDict((k.name, k) for k in (  # in the order of stores()['overlay']: 1 wind, 2 fruit, 3 doors, 4 boxes, 5 errands
     Overlay('wind', (WO.GUST_THIRDS,), WO.WindOracle, None, bits=lambda p: 0, reset_value=lambda p: 0,
             invalid=lambda p, g: _with(p, 5, 0x80)),  # a wind byte with a high bit
     Overlay('fruit', ((1, 5, -5),), FO.FruitOracle, 'eaten', bits=lambda p: int(np.count_nonzero(p)), reset_value=lambda p: 0,
@@ -82,6 +108,9 @@ OVERLAYS = collections.OrderedDict((k.name, k) for k in (  # in the order of sto
             invalid=lambda p, g: _with(p, 20, DO.DOOR << 4, clear=True)),  # a door of slot 0 and no key or lever for it
     Overlay('boxes', (5,), BO.BoxesOracle, 'words', bits=lambda p: _box_bits(p) * int(np.count_nonzero(p & BO.INITIAL)), reset_value=_box_word,
             invalid=lambda p, g: _with(p, g['walls'][0], BO.TARGET)),  # a target on a wall
+    # (two instructions that every plane with two apples and a lemon can carry out; bits = F + pb + ib under them)
+    Errands('errands', (EO.TD_INSTRUCTIONS, EO.CASE_PAY), EO.ErrandsOracle, 'words', bits=lambda p: errand_bits(p, EO.TD_INSTRUCTIONS),
+            reset_value=lambda p: 0, invalid=lambda p, g: _with(p, g['walls'][0], (1 << 5) | int(np.count_nonzero(p)))),  # a fruit (the next slot) on a wall
 ))
 
 
@@ -91,7 +120,7 @@ def overlay(kind):
 
 
 def masks_of(o, kind):
-    """The per-env overlay state of a restatement: eaten masks, open masks, box words; None under wind."""
+    """The per-env overlay state of a restatement: eaten masks, open masks, box words, errand words; None under wind."""
     return overlay(kind).masks_of(o)
 
 

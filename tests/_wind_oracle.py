@@ -76,6 +76,7 @@ class WindOracle(OverlayOracle):
 
     def __init__(self, grid, seed, n, wind=None, gust_q16=0, env_id0=0, q0=0.0):
         super().__init__(grid, seed, n, env_id0, q0)
+        self.log = dict(gust_moved=0)  # moves that a gust ended on another cell than the cell's own strength would
         self.set_wind(wind, gust_q16)
 
     def set_wind(self, wind, gust_q16=0):
@@ -95,10 +96,13 @@ class WindOracle(OverlayOracle):
         who = np.ones(self.n, bool) if who is None else who
         s = st.pos.copy()
         c = self.wind[s].astype(np.int64)
-        k = (c >> 2) & 3
+        k = k0 = (c >> 2) & 3
         if self.gust_q16:
             k = gusted(k, gust_words(self.seed, self.env_ids, st.tcount), self.gust_q16)
-        s2, r, d = push(self.grid, s, (np.asarray(act) & 3).astype(np.int32), k, (c & 3).astype(np.int32))
+        a, direction = (np.asarray(act) & 3).astype(np.int32), (c & 3).astype(np.int32)
+        s2, r, d = push(self.grid, s, a, k, direction)
+        if self.gust_q16:
+            self.log['gust_moved'] += int(((s2 != push(self.grid, s, a, k0, direction)[0]) & who).sum())
         st.pos[who] = s2[who]
         st.done[who] = d[who]
         self.reward[who] = r[who]

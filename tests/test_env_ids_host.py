@@ -66,7 +66,7 @@ def test_every_overlay_run_draws_all_three_starts(kind, env_id0):
         o = _fresh(kind, grid, env_id0)
         S.rollout_of(o, grid, policy)
         S.drew_every_start(o)
-    td_grid = 'learn4' if kind == 'boxes' else grid
+    td_grid = S.td_grid(kind, grid)
     for method in (Q_LEARNING, SARSA):  # td_run
         o = _fresh(kind, td_grid, env_id0, q0=S.Q0)
         o.td_run(300, method, 0.25, 0.9, _eps(0.3))
@@ -86,7 +86,7 @@ def test_every_overlay_run_draws_all_three_starts(kind, env_id0):
 
 
 @pytest.mark.parametrize('env_id0', S.IDS)
-@pytest.mark.parametrize('kind,grid', [('fruit', 'starts8'), ('doors', 'starts8'), ('boxes', 'one_box8')])
+@pytest.mark.parametrize('kind,grid', [('fruit', 'starts8'), ('doors', 'starts8'), ('boxes', 'one_box8'), ('errands', 'starts8')])
 def test_the_epoch_cases_reset_behind_the_crossing(kind, grid, env_id0):
     tc = np.full(S.N, 2 ** 32 - 20, np.uint64)
     tc[::3] += 7  # (counts_near_2_32 of tests/_tabular_cases.py)
@@ -107,10 +107,12 @@ def test_the_planes_keep_clear_of_the_start_cells_and_the_ids_differ():
     for grid in ('starts8', 'open150', 'learn4', 'one_box8'):
         g = S.grid_dict(grid)
         assert len(set(g['starts'])) == 3
-        for kind in ('fruit', 'doors', 'boxes'):
+        for kind in ('fruit', 'doors', 'boxes', 'errands'):
             if grid in ('learn4', 'one_box8') and kind != 'boxes':
                 continue
             assert not S.plane(kind, grid)[g['starts']].any(), (grid, kind)
+    for grid in ('starts8', 'open150'):
+        assert not S.plane('errands', S.td_grid('errands', grid))[S.grid_dict(grid)['starts']].any(), grid
     a, b = (S.oracle('fruit', 'starts8', i) for i in S.IDS)
     assert not np.array_equal(a.reset(), b.reset())  # (a kernel that ignored the id would not pass at the second)
     assert S.IDS[0] == 0 and S.IDS[1] < 2 ** 31 < S.IDS[1] + S.N

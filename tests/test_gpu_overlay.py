@@ -1,6 +1,6 @@
-"""The overlay slot of an engine (csrc/gu_overlay.hip; DESIGN.md "Overlays"): wind, fruit, doors and boxes share one third plane, one
-array of masks and one install path.  What each feature computes is checked against its CPU restatement in tests/test_gpu_wind.py,
-test_gpu_fruit.py, test_gpu_doors.py and test_gpu_boxes.py; here the SLOT is checked, for every kind of tests/_overlays.py alike, with
+"""The overlay slot of an engine (csrc/gu_overlay.hip; DESIGN.md "Overlays"): wind, fruit, doors, boxes and errands share one third
+plane, one array of masks and one install path.  What each feature computes is checked against its CPU restatement in
+tests/test_gpu_wind.py, test_gpu_fruit.py, test_gpu_doors.py, test_gpu_boxes.py and test_gpu_errands.py; here the SLOT is checked, for every kind of tests/_overlays.py alike, with
 engines that only ever had one overlay (or none) as the reference: one engine cycled through the kinds -- so that a reset value, a
 parameter word or a mask buffer left by an earlier tenant would show --, refused installs that must leave everything as it was, a new
 grid that drops the overlay, the masks' reset to the slot's reset value, and every call that has no overlay form refused while a
@@ -9,7 +9,8 @@ kind is set.
 Shapes: an 8 x 8 grid (three planes in LDS) and, for the cycle, 150 x 150 (two planes fit 64 KiB and three, 67 536 bytes, do not: the
 L2 kernels); N = 130 envs (three waves, the last one partial: the windy kernels run its dead lanes); T = 33 steps (one full action
 word, a word boundary and a tail).  One box: b = 6 bits on the small grid, so gu_td_init takes it (64 << 6 rows), and 15 on the large
-one.  The refusals: the 11 x 11 maze, N = 64."""
+one.  The errands lie on the fruit plane's cells (four fruit and the registry's two instructions: seven bits).  The refusals: the
+11 x 11 maze, N = 64."""
 import functools
 
 import numpy as np
@@ -46,11 +47,16 @@ def _case(name):
                   fruit=fruit_plane(W, H, [2, W + 1, 3 * W + 3 + 1, 2 * W], ['apple', 'lemon', 'melon', 'apple']),
                   doors=door_plane(W, H, {0: [2 * W + 1, 2 * W + 2], 1: W + 2}, keys={0: 1}, levers={1: W}),
                   boxes=box_plane(W, H, [BOX], list(TARGETS)))
+    planes['errands'] = planes['fruit']  # (two apples and a lemon: the registry's two instructions; fruit and errands read one plane two ways)
     return g, planes
 
 
 def _pattern(kind, g, planes):
-    """Masks that differ from the reset value for most envs and differ between neighbours; under boxes: free cells."""
+    """Masks that differ from the reset value for most envs and differ between neighbours; under boxes: free cells; under errands:
+    words that gu_set_errands_state takes (progress 0 or 1, which both of the registry's instructions reach, behind pb = 2 bits)."""
+    if kind == 'errands':
+        F, i = int(np.count_nonzero(planes[kind])), np.arange(N)
+        return (((i * 7 + 1) % (1 << F)) | ((i % 2) << F) | ((i // 2 % 2) << (F + 2))).astype(np.uint32)
     if kind != 'boxes':
         return ((np.arange(N) * 7 + 1) % (1 << OVERLAYS[kind].bits(planes[kind]))).astype(np.uint32)
     free = np.array([s for s in range(g['W'] * g['H']) if s not in g['walls'] + g['goals'] + g['lava']], np.uint32)
@@ -95,9 +101,10 @@ def _reference(grid, kind):
         vec.close()
 
 
-# ---- 1: one slot, cycled: each kind behind the one before it, and boxes behind and before every other tenant ----
+# ---- 1: one slot, cycled: each kind behind the one before it, and boxes and errands behind and before every other tenant ----
 ORDERS = {'three': (None, 'wind', None, 'fruit', None, 'doors', None),
-          'four': (None, 'boxes', None, 'wind', None, 'boxes', None, 'fruit', None, 'boxes', None, 'doors', None, 'boxes', None)}
+          'four': (None, 'boxes', None, 'wind', None, 'boxes', None, 'fruit', None, 'boxes', None, 'doors', None, 'boxes', None),
+          'five': (None, 'errands', None, 'fruit', None, 'errands', None, 'boxes', None, 'errands', None, 'doors', None, 'wind', None, 'errands', None)}
 
 
 @pytest.mark.parametrize('grid', ['open8', 'open150'])
@@ -124,7 +131,7 @@ def test_one_engine_cycled_through_the_overlays_equals_engines_that_only_had_one
                 assert got[k] == want[k], (kind, had, k)
             had = kind
         # (each overlay changed what the envs did or were paid)
-        assert len({_reference(grid, k)['uniform obs'] + _reference(grid, k)['uniform reward'] for k in (None,) + KINDS}) == 5
+        assert len({_reference(grid, k)['uniform obs'] + _reference(grid, k)['uniform reward'] for k in (None,) + KINDS}) == len(KINDS) + 1
     finally:
         vec.close()
 
@@ -211,17 +218,25 @@ def test_reset_sets_the_masks_of_exactly_the_envs_it_takes_to_the_slots_reset_va
         assert (pattern != init).sum() > N // 2
         take = np.arange(N) % 3 == 0
         K.set_masks(eng, pattern)
+        rb = K.reset_bits(planes[kind])  # (every bit; under errands a reset draws the instruction's index above them)
+
+        def after(took):
+            """The masks, of the envs the reset took the bits it sets alone."""
+            masks = K.masks(eng)
+            assert rb == 0xFFFFFFFF or len(set((masks[took] & ~np.uint32(rb)).tolist())) == 2  # (both instructions were drawn)
+            return np.where(took, masks & np.uint32(rb), masks)
+
         vec.reset(take.astype(np.uint8))  # gu_reset under a mask of envs
-        assert np.array_equal(K.masks(eng), np.where(take, init, pattern))
+        assert np.array_equal(after(take), np.where(take, init, pattern))
         K.set_masks(eng, pattern)
         done = (np.arange(N) % 5 < 2).astype(np.int32)
         vec.set_state(done=done)
         eng.reset_done()  # gu_reset_done: the done envs only
-        assert np.array_equal(K.masks(eng), np.where(done != 0, init, pattern))
+        assert np.array_equal(after(done != 0), np.where(done != 0, init, pattern))
         assert not vec.get_state()['done'].any()
         K.set_masks(eng, pattern)
         vec.reset()  # every env
-        assert (K.masks(eng) == init).all()
+        assert (after(np.ones(N, bool)) == init).all()
     finally:
         vec.close()
 
@@ -237,7 +252,8 @@ def _maze11():
     planes = dict(wind=wind_plane(11, 11, rs.randint(0, 4, (11, 11)), rs.randint(0, 4, (11, 11))),
                   fruit=fruit_plane(11, 11, [free[3], free[len(free) // 2], free[-4]], ['apple', 'lemon', 'melon']),
                   doors=door_plane(11, 11, {0: 45, 1: 23, 2: [67, 102]}, keys={0: 13, 2: 100}, levers={1: 12, 2: 34}),
-                  boxes=box_plane(11, 11, [13], [12]))
+                  boxes=box_plane(11, 11, [13], [12]),
+                  errands=fruit_plane(11, 11, [free[3], free[len(free) // 2], free[-4]], ['apple', 'lemon', 'apple']))
     return g, planes
 
 

@@ -1,8 +1,8 @@
-"""Wind, fruit, doors and boxes on grids with THREE start cells, and on an engine that is a shard (env_id0 = 2^31 - 40: the batch
-straddles bit 31), against the CPU restatements tests/_{wind,fruit,doors,boxes}_oracle.py built at the same id, byte for byte: rows,
-statistics, positions, masks or words, episode counts, tables.
+"""Wind, fruit, doors, boxes and errands on grids with THREE start cells, and on an engine that is a shard (env_id0 = 2^31 - 40: the
+batch straddles bit 31), against the CPU restatements tests/_{wind,fruit,doors,boxes,errands}_oracle.py built at the same id, byte for
+byte: rows, statistics, positions, masks or words, episode counts, tables.
 
-The fruit, door and box step kernels each carry their own copy of the lazy reset, their rollout kernels another (start_prefix beside
+The fruit, door, box and errand step kernels each carry their own copy of the lazy reset, their rollout kernels another (start_prefix beside
 the policy's epoch-folded prefix), and every overlay kernel writes a.env_id0 + e out by itself.  Every other overlay test runs at
 env_id0 = 0 on a grid with one start cell, where gu_rng_start_index(...) is always 0: a wrong prefix, a wrong episode count or the
 policy's prefix in place of the stream-1 prefix gives the same bytes there.  Here every case asserts on the restatement's log
@@ -33,7 +33,7 @@ def _spec(name):
 
 
 def _install(vec, kind, name):
-    overlay(kind).install(vec.engine, S.plane(kind, name), *S.extra(kind))
+    overlay(kind).install(vec.engine, S.plane(kind, name), *S.extra(kind, name))
 
 
 def _again(vec, kind, name, env_id0, q0=None):
@@ -120,8 +120,11 @@ def test_rollout_equals_the_oracle(kind, grid, policy, env_id0):
 
 
 # ---- 3: td_run ----
-# (on 'open150' where the kind's own tests run it there: boxes refuse it, their word takes more than 10 bits; the boxes' learners run on 'learn4')
-TD_CASES = [(kind, grid) for kind in KINDS[:4] for grid in GRIDS] + [('boxes', 'learn4')]
+# (every kind that learns on the grid, S.td_grid: the boxes refuse 'open150', their word takes more than 10 bits, and their learners
+# run on 'learn4' in the place of 'starts8'; the errands learn under the planes ':td' -- six bits on 'starts8', three on 'open150', where
+# the six bits of tests/test_gpu_errands.py are 46 MB a table and run with six learners there)
+TD_CASES = [(kind, S.td_grid(kind, grid)) for kind in KINDS for grid in GRIDS if (kind, grid) != ('boxes', 'open150')]
+assert len(TD_CASES) == 2 * len(KINDS) - 1 and ('boxes', 'learn4') in TD_CASES and ('errands', 'open150:td') in TD_CASES
 
 
 @pytest.mark.parametrize('env_id0', IDS)
@@ -197,10 +200,11 @@ def test_set_boxes_refuses_a_box_on_the_second_and_on_the_third_start(grid):
 
 # ---- 6: the step count crosses 2^32 inside a launch ----
 @pytest.mark.parametrize('env_id0', IDS)
-@pytest.mark.parametrize('kind,grid', [('fruit', 'starts8'), ('doors', 'starts8'), ('boxes', 'one_box8')])
+@pytest.mark.parametrize('kind,grid', [('fruit', 'starts8'), ('doors', 'starts8'), ('boxes', 'one_box8'), ('errands', 'starts8')])
 def test_the_epoch_changes_inside_a_launch(kind, grid, env_id0):
-    """Streams 0, 2 and 4 are re-keyed in the step that crosses a multiple of 2^32; stream 1, which draws the start cell, has no
-    epoch: resets behind the crossing still draw with the prefix of epoch 0.  ('one_box8': the boxes' learners take 10 bits.)"""
+    """Streams 0, 2 and 4 are re-keyed in the step that crosses a multiple of 2^32; stream 1, which draws the start cell, and stream
+    11, which draws the instruction, have no epoch: resets behind the crossing still draw with the prefix of epoch 0.  ('one_box8':
+    the boxes' learners take 10 bits, as the errands' five fruit and three instructions do.)"""
     vec, o = _pair(kind, grid, env_id0, q0=0.0)
     try:
         tc = counts_near_2_32(vec, o, N, 2 ** 32 - 20)

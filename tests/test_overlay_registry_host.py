@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from . import _overlay_starts as S
-from ._overlays import NO_OVERLAY_CALLS, OVERLAYS, masks_of, same_state
+from ._overlays import NO_OVERLAY_CALLS, OVERLAYS, errand_bits, masks_of, same_state
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'griduniverse_amd', 'csrc')
 
@@ -83,10 +83,13 @@ def test_bits_reset_value_and_invalid_plane_agree_with_the_restatement(kind, gri
     K, plane = OVERLAYS[kind], S.plane(kind, grid)
     o = K.oracle(S.c_grid(grid), 0, 3, plane, q0=None)
     assert K.bits(plane) == o._bits()
+    if kind == 'errands':  # (the registry's two instructions under five fruit; the case's own three: ten bits)
+        assert K.bits(plane) == 5 + 2 + 1 and S.oracle(kind, grid, 0, n=3)._bits() == errand_bits(plane, S.extra(kind, grid)[0]) == 5 + 3 + 2
     if K.state:
         assert (masks_of(o, kind) == K.reset_value(plane)).all()
         o.reset()
-        assert (masks_of(o, kind) == K.reset_value(plane)).all()
+        assert (masks_of(o, kind) & K.reset_bits(plane) == K.reset_value(plane)).all()
+        assert K.reset_bits(plane) == 0xFFFFFFFF or (kind == 'errands' and K.reset_bits(plane) == (1 << 7) - 1 and (masks_of(o, kind) >> 7).any())
     else:
         assert masks_of(o, kind) is None and K.reset_value(plane) == 0
     g = dict(S.grid_dict(grid), walls=[21, 45])
