@@ -2,8 +2,9 @@
 // moves rewrite (include/gu.h: gu_set_boxes; restated on the CPU by tests/_boxes_oracle.py).  The boxes are an overlay (DESIGN.md
 // "Overlays"): a third byte plane behind the engine's two cell planes (bit 0: target, bit 1: a box stands here at every reset) and one
 // uint32 word per env (gu_engine::d_overlay_mask) that holds the cell of box k in bits [k * b, (k + 1) * b).  Here are the plane's and
-// the words' validation, the box step kernel (gu_step, gu_step_device) and the box rollout kernel (gu_rollout); the slot, the launches'
-// arguments, the words' copies and resets are gu_overlay.hip's and gu_overlay.hpp's; the field arithmetic and the push are gu_map.hpp's
+// the words' validation and the box rule, BoxRule, around which gu_overlay.hpp's two frames are the box step kernel (gu_step,
+// gu_step_device) and the box rollout kernel (gu_rollout); the slot, the launches' arguments, the words' copies and resets are
+// gu_overlay.hip's and gu_overlay.hpp's; the field arithmetic and the push are gu_map.hpp's
 // (gu_box_at, gu_box_push), shared with the learners' lane (BoxOverlay, gu_tabular_overlay.hpp; gu_td.hip instantiates it).
 //
 // THE HOT PATH, decided on purpose (none of it is measured beside an alternative: only the form below was built; what is measured is
@@ -25,7 +26,7 @@
 //   derived from the word with B reads once, at the start of the launch; behind a lazy reset it is the count of the reset word, a
 //   launch-uniform constant that the host works out (it travels in the parameter word).  Cost: one VGPR.
 //   A solved word is absorbing without a branch: the step is computed as ever and a select keeps s and w.
-// The step kernel takes one step per launch: it derives the count with its B reads and carries nothing.
+// The step kernel takes one step per launch: BoxRule::load derives the count with its B reads, as at the start of a rollout.
 //
 // One lane per env.  The word stays in a VGPR for the whole launch: one load at the start, one store at the end.  Plain stores, no
 // schedule (GuPacer).
@@ -34,169 +35,69 @@
 #include <algorithm>
 #include <vector>
 
-// One step of rules 2 .. 6 of gu_set_boxes from cell s (flags fs, reward byte rs) under the word w with `on` boxes on a target:
-// leaves s', its two bytes, w' and the count in place and returns the reward; d is the done flag.  `m` and `bx` are the staged planes.
-template <bool LDS>
-__device__ __forceinline__ int32_t gu_boxes_move(const CellMap &m, const uint8_t *bx, uint32_t param, uint32_t act, uint64_t lut, int32_t W, int32_t &s, uint32_t &fs,
-                                                 int32_t &rs, uint32_t &w, uint32_t &on, int32_t &d)
-{
-    const uint32_t B = GU_BOX_B(param), b = GU_BOX_BITS(param);
-    const int32_t delta = gu_delta<LDS>(act, lut, W);
-    const bool solved = on == B;  // rule 2: nothing moves
-    const int32_t c = gu_move(s, fs, act, delta);
-    // three reads behind the one address c: flags, reward byte, box byte
-    const uint32_t fc = m.f[c], bc = bx[c];
-    const int32_t rc = m.r[c];
-    const int32_t at = gu_box_at(w, c, B, b);  // (computed for every lane: selects, no branch of its own)
-    const int32_t k = ((c != s) & !solved) ? at : -1;
-    bool stay = solved;
-    int32_t gain = 0;
-    if (k >= 0) stay = gu_box_push(m.f, bx, c, fc, bc, act, delta, k, B, b, w, gain);  // the second round: pushing lanes only
-    s = stay ? s : c;
-    fs = stay ? fs : fc;
-    rs = stay ? rs : rc;
-    on += (uint32_t)gain;
-    const bool done = on == B;
-    d = done ? 1 : (int32_t)(fs >> GU_CELL_TERM_BIT) & 1;
-    return done ? GU_BOX_SOLVED_REWARD : rs + GU_BOX_V(param) * gain;
-}
+// ------------------------------------------------------------------------------------
+// the rule (the interface: gu_overlay.hpp): rules 2 .. 6 of gu_set_boxes
+// ------------------------------------------------------------------------------------
+struct BoxRule {
+    static constexpr bool DONE_IN_PLACE = true;  // (gu_overlay.hpp: its kernel handed d to the rule by reference)
+    uint32_t w;
+    uint32_t fs;  // the flags and the reward byte of the cell stood on, and the count of boxes on a target, carried from step to step
+    int32_t rs;
+    uint32_t on;
 
-// ------------------------------------------------------------------------------------
-// single step: gu_step_kernel's rules (rejected actions, lazy auto-reset, done ballot, host copies) around the box rule
-// ------------------------------------------------------------------------------------
-template <bool LDS>
-__global__ void __launch_bounds__(GU_BLOCK) gu_boxes_step_kernel(const OverlayStepArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const CellMap m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, 3);
-    const uint8_t *bx = m.f + 2 * a.cell_bytes;
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int32_t d = 0;
-    if (e < a.N) {
-        const uint32_t raw = (uint32_t)a.actions[e];
-        const uint32_t act = raw & 3u;
-        int32_t s = a.pos[e], r;
-        if (a.host_err && !GU_ACTION_OK(raw)) {  // (gu_step_kernel: this env does not step, its word stays, and the host is told)
-            __hip_atomic_store(a.host_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            a.tcount[e] -= 1u;
-            r = a.reward[e];
-            d = a.done[e];
-        } else {
-            uint32_t w = a.mask[e];
-            if ((a.flags & GU_F_AUTO_RESET) && a.done[e]) {  // lazy `if done: env.reset()`: the boxes are back where they began
-                const uint32_t ep = a.episode[e];
-                s = a.starts[gu_rng_start_index(gu_rng_prefix(a.seed_prefix, a.env_id0 + (uint32_t)e), ep, a.n_starts)];
-                a.episode[e] = ep + 1;
-                w = a.init;
-            }
-            uint32_t fs = m.f[s], on = gu_box_on_target(bx, w, GU_BOX_B(a.param), GU_BOX_BITS(a.param));
-            int32_t rs = m.r[s];
-            r = gu_boxes_move<LDS>(m, bx, a.param, act, a.lut, a.W, s, fs, rs, w, on, d);
-            a.pos[e] = s;
-            a.reward[e] = r;
-            a.done[e] = d;
-            a.mask[e] = w;
-        }
-        if (a.host_obs) a.host_obs[e] = s;
-        if (a.host_reward) a.host_reward[e] = r;
-        if (a.host_done) a.host_done[e] = d;
+    template <class ARGS>
+    __device__ __forceinline__ void load(const ARGS &a, const OverlayMap &m, uint32_t word, int32_t s)
+    {
+        w = word;
+        fs = m.f[s];
+        rs = m.r[s];
+        on = gu_box_on_target(m.o, w, GU_BOX_B(a.param), GU_BOX_BITS(a.param));  // (the B reads, once per launch)
     }
-    const uint64_t bits = __ballot(d != 0);
-    if ((threadIdx.x & 63) == 0 && e < a.N) a.done_bits[e >> 6] = bits;
-    gu_step_publish(a.host_seq, a.seq, a.blocks_done);
-}
 
-void gu_boxes_step(gu_engine *h, bool lds, const OverlayStepArgs &a)
-{
-    const dim3 grid(gu_blocks(h->N, GU_BLOCK)), block(GU_BLOCK);
-    if (lds) hipLaunchKernelGGL(gu_boxes_step_kernel<true>, grid, block, 3 * (size_t)h->cell_bytes, h->stream, a);
-    else hipLaunchKernelGGL(gu_boxes_step_kernel<false>, grid, block, 0, h->stream, a);
-}
-
-// ------------------------------------------------------------------------------------
-// rollout: T steps per lane in one launch; the four policies with the calm kernels' streams 0, 1 and 2
-// ------------------------------------------------------------------------------------
-// Auto-reset, rows and statistics are launch-uniform tests on the arguments.  The step count is 64 bits wide and streams 0 and 2 are
-// re-keyed in the step that crosses a multiple of 2^32, so no launch needs another form.
-template <int POLICY, bool LDS>
-__global__ void __launch_bounds__(GU_BLOCK) gu_boxes_rollout_kernel(const OverlayRolloutArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const CellMap m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, 3);
-    const uint8_t *bx = m.f + 2 * a.cell_bytes;
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int32_t d = 0;
-    if (e < a.N) {
-        const uint32_t env = a.env_id0 + (uint32_t)e;
-        int32_t s = a.pos[e], r = a.reward[e];
-        d = a.done[e];
-        uint32_t ep = a.episode[e], w = a.mask[e];
-        uint32_t fs = m.f[s];  // the flags and the reward byte of the cell stood on, and the count of boxes on a target, carried from step to step
-        int32_t rs = m.r[s];
-        uint32_t on = gu_box_on_target(bx, w, GU_BOX_B(a.param), GU_BOX_BITS(a.param));
-        const uint64_t t0 = a.steps_taken + (uint64_t)(int64_t)(int32_t)a.tcount[e];
-        const uint32_t start_prefix = gu_rng_prefix(a.seed_prefix, env);  // stream 1: no epoch
-        OverlayPolicy<POLICY> P;
-        P.begin(a, env, t0);
-        int32_t ret = 0, fin = 0;
-        for (int64_t i = 0; i < a.T; ++i) {
-            if (a.auto_reset && d) {  // lazy `if done: env.reset()`: the boxes are back where they began
-                s = a.starts[gu_rng_start_index(start_prefix, ep, a.n_starts)];
-                ++ep;
-                w = a.init;
-                on = GU_BOX_ON0(a.param);
-                fs = m.f[s];
-                rs = m.r[s];
-            }
-            const uint32_t act = P.act(a, i, e, s);
-            r = gu_boxes_move<LDS>(m, bx, a.param, act, a.lut, a.W, s, fs, rs, w, on, d);
-            P.next(a);
-            if (a.tr_obs) {
-                const int64_t row = i * a.N + e;
-                a.tr_obs[row] = s;
-                a.tr_reward[row] = r;
-                a.tr_done[row] = d;
-            }
-            ret += r;
-            fin += d;
-        }
-        a.pos[e] = s;
-        a.reward[e] = r;
-        a.done[e] = d;
-        a.episode[e] = ep;
-        a.mask[e] = w;
-        if (a.ret) {
-            a.ret[e] = ret;
-            a.episodes_fin[e] = fin;
-        }
+    template <class ARGS>
+    __device__ __forceinline__ void reset(const ARGS &a, const OverlayMap &m, uint32_t, uint32_t, int32_t s)
+    {
+        w = a.init;  // the boxes are back where they began
+        on = GU_BOX_ON0(a.param);
+        fs = m.f[s];
+        rs = m.r[s];
     }
-    const uint64_t bits = __ballot(d != 0);
-    if ((threadIdx.x & 63) == 0 && e < a.N) a.done_bits[e >> 6] = bits;
-}
 
-void gu_boxes_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a)
-{
-    gu_pick<3, 2, 1, 0>(p.policy, [&](auto policy_c) {
-        gu_pick<0, 1>(p.lds != 0, [&](auto lds_c) {
-            constexpr int POLICY = decltype(policy_c)::value;
-            constexpr bool LDS = decltype(lds_c)::value != 0;
-            gu_lds_launch<gu_boxes_rollout_kernel<POLICY, LDS>, false>(h, p.blocks, p.block, p.lds, a);
-        });
-    });
-}
+    // One step from cell s (flags fs, reward byte rs) under the word w with `on` boxes on a target: leaves s', its two bytes, w' and the
+    // count in place
+    template <bool LDS, class ARGS>
+    __device__ __forceinline__ void move(const ARGS &a, const OverlayMap &m, uint32_t act, int32_t &s, int32_t &r, int32_t &d)
+    {
+        const uint32_t B = GU_BOX_B(a.param), b = GU_BOX_BITS(a.param);
+        const int32_t delta = gu_delta<LDS>(act, a.lut, a.W);
+        const bool solved = on == B;  // rule 2: nothing moves
+        const int32_t c = gu_move(s, fs, act, delta);
+        // three reads behind the one address c: flags, reward byte, box byte
+        const uint32_t fc = m.f[c], bc = m.o[c];
+        const int32_t rc = m.r[c];
+        const int32_t at = gu_box_at(w, c, B, b);  // (computed for every lane: selects, no branch of its own)
+        const int32_t k = ((c != s) & !solved) ? at : -1;
+        bool stay = solved;
+        int32_t gain = 0;
+        if (k >= 0) stay = gu_box_push(m.f, m.o, c, fc, bc, act, delta, k, B, b, w, gain);  // the second round: pushing lanes only
+        s = stay ? s : c;
+        fs = stay ? fs : fc;
+        rs = stay ? rs : rc;
+        on += (uint32_t)gain;
+        const bool done = on == B;
+        d = done ? 1 : (int32_t)(fs >> GU_CELL_TERM_BIT) & 1;
+        r = done ? GU_BOX_SOLVED_REWARD : rs + GU_BOX_V(a.param) * gain;
+    }
+
+    __device__ __forceinline__ uint32_t word() const { return w; }
+};
+
+void gu_boxes_step(gu_engine *h, bool lds, const OverlayStepArgs &a) { gu_overlay_step_launch<BoxRule>(h, lds, a); }
+void gu_boxes_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a) { gu_overlay_rollout_launch<BoxRule>(h, p, a); }
 
 // ------------------------------------------------------------------------------------
 // entry points
 // ------------------------------------------------------------------------------------
-// the flags plane of the engine's grid on the host (wall and terminal bits: what neither a box nor a target may lie on)
-static int gu_boxes_flags(gu_engine *h, std::vector<uint8_t> &flags)
-{
-    flags.resize((size_t)h->S);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    GU_HIP(hipMemcpy(flags.data(), h->d_cell, (size_t)h->S, hipMemcpyDeviceToHost));
-    return GU_OK;
-}
-
 static int32_t gu_boxes_width(int32_t S)  // the smallest b with S <= 1 << b (at least 1)
 {
     int32_t b = 1;
@@ -214,7 +115,7 @@ int gu_set_boxes(gu_handle h, const uint8_t *box, int32_t on_target)
     if (!box) return gu_overlay_install(h, GU_OVERLAY_BOXES, nullptr, 0, 0u);
     GU_REQUIRE(on_target >= 0 && on_target <= 16, GU_ERR_INVALID, "on_target %d out of range (0 .. 16)", on_target);
     std::vector<uint8_t> flags;
-    GU_TRY(gu_boxes_flags(h, flags));
+    GU_TRY(gu_overlay_grid_flags(h, flags));  // (wall and terminal bits: what neither a box nor a target may lie on)
     std::vector<int32_t> starts((size_t)h->n_starts);
     GU_HIP(hipMemcpy(starts.data(), h->d_starts, starts.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     const int32_t b = gu_boxes_width(h->S);

@@ -2,9 +2,10 @@
 // the CPU by tests/_errands_oracle.py).  Errands are the fifth overlay kind (DESIGN.md "Overlays"): fruit's byte plane behind the engine's
 // two cell planes, two engine-wide parameter words (the instructions, and the pay with the field widths: gu_map.hpp) and one uint32 word
 // per env -- the fruit eaten, the progress p and the index j of the instruction the env was given at its last reset.  Here are the
-// plane's and the instructions' validation, the words' reset kernel (it DRAWS: stream 11 at the episode count before the reset), the step
-// kernel and the rollout kernel; the slot, the launches' arguments and everything else the overlays share is gu_overlay.hip's and
-// gu_overlay.hpp's; the learners are instantiations of gu_td_kernel (gu_td.hip, through ErrandOverlay of gu_tabular_overlay.hpp).
+// instructions' validation, the words' reset kernel (it DRAWS: stream 11 at the episode count before the reset) and the errand rule,
+// ErrandRule, around which gu_overlay.hpp's two frames are the step kernel and the rollout kernel; the slot, the launches' arguments,
+// the plane's format (fruit's) and everything else the overlays share is gu_overlay.hip's and gu_overlay.hpp's; the learners are
+// instantiations of gu_td_kernel (gu_td.hip, through ErrandOverlay of gu_tabular_overlay.hpp).
 //
 // One lane per env, like the fruit kernels.  The three planes are staged in LDS where they fit 64 KiB, else all three are read from
 // L2.  An errand never changes a move: the errand byte of the candidate cell is read BESIDE its flags and its reward byte, so the
@@ -14,7 +15,6 @@
 #include "gu_overlay.hpp"
 
 #include <algorithm>
-#include <vector>
 
 // ------------------------------------------------------------------------------------
 // the reset of the words: gu_reset and gu_reset_done, in front of gu_reset_kernel (which increments episode[])
@@ -43,128 +43,39 @@ int gu_errands_before_reset(gu_engine *h, const uint8_t *d_mask, bool only_done)
 }
 
 // ------------------------------------------------------------------------------------
-// single step: gu_step_kernel's rules (rejected actions, lazy auto-reset, done ballot, host copies) with the errand of s'
+// the rule (the interface: gu_overlay.hpp): the engine's move, and the errand byte of the candidate cell beside its flags and its reward byte
 // ------------------------------------------------------------------------------------
-template <bool LDS>
-__global__ void __launch_bounds__(GU_BLOCK) gu_errands_step_kernel(const OverlayStepArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const CellMap m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, 3);
-    const uint8_t *er = m.f + 2 * a.cell_bytes;
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int32_t d = 0;
-    if (e < a.N) {
-        const uint32_t raw = (uint32_t)a.actions[e];
-        const uint32_t act = raw & 3u;
-        int32_t s = a.pos[e], r;
-        if (a.host_err && !GU_ACTION_OK(raw)) {  // (gu_step_kernel: this env does not step, eats nothing, draws nothing, and the host is told)
-            __hip_atomic_store(a.host_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            a.tcount[e] -= 1u;
-            r = a.reward[e];
-            d = a.done[e];
-        } else {
-            uint32_t word = a.mask[e], rem;
-            if ((a.flags & GU_F_AUTO_RESET) && a.done[e]) {  // lazy `if done: env.reset()`: the fruit grows back, another instruction is given
-                const uint32_t ep = a.episode[e];
-                const uint32_t start_prefix = gu_rng_prefix(a.seed_prefix, a.env_id0 + (uint32_t)e);
-                s = a.starts[gu_rng_start_index(start_prefix, ep, a.n_starts)];
-                a.episode[e] = ep + 1;
-                gu_errand_draw(start_prefix, ep, a.param, a.param2, word, rem);
-            } else {
-                rem = gu_errand_rem(word, a.param, a.param2);
-            }
-            const int32_t c = gu_move(s, m.f[s], act, gu_delta<LDS>(act, a.lut, a.W));
-            const bool stay = gu_errand_touch(er[c], m.r[c], (m.f[c] >> GU_CELL_TERM_BIT) & 1, a.param2, word, rem, r, d);
-            s = stay ? s : c;
-            a.pos[e] = s;
-            a.reward[e] = r;
-            a.done[e] = d;
-            a.mask[e] = word;
-        }
-        if (a.host_obs) a.host_obs[e] = s;
-        if (a.host_reward) a.host_reward[e] = r;
-        if (a.host_done) a.host_done[e] = d;
+struct ErrandRule {
+    static constexpr bool DONE_IN_PLACE = true;  // (gu_overlay.hpp: its kernel handed d to the rule by reference)
+    uint32_t w, rem;  // (`rem`: the head of this file)
+
+    template <class ARGS>
+    __device__ __forceinline__ void load(const ARGS &a, const OverlayMap &, uint32_t word, int32_t)
+    {
+        w = word;
+        rem = gu_errand_rem(w, a.param, a.param2);
     }
-    const uint64_t bits = __ballot(d != 0);
-    if ((threadIdx.x & 63) == 0 && e < a.N) a.done_bits[e >> 6] = bits;
-    gu_step_publish(a.host_seq, a.seq, a.blocks_done);
-}
 
-void gu_errands_step(gu_engine *h, bool lds, const OverlayStepArgs &a)
-{
-    const dim3 grid(gu_blocks(h->N, GU_BLOCK)), block(GU_BLOCK);
-    if (lds) hipLaunchKernelGGL(gu_errands_step_kernel<true>, grid, block, 3 * (size_t)h->cell_bytes, h->stream, a);
-    else hipLaunchKernelGGL(gu_errands_step_kernel<false>, grid, block, 0, h->stream, a);
-}
-
-// ------------------------------------------------------------------------------------
-// rollout: T steps per lane in one launch; the four policies with the calm kernels' action and sampling streams (0 and 2)
-// ------------------------------------------------------------------------------------
-template <int POLICY, bool LDS>
-__global__ void __launch_bounds__(GU_BLOCK) gu_errands_rollout_kernel(const OverlayRolloutArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const CellMap m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, 3);
-    const uint8_t *er = m.f + 2 * a.cell_bytes;
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    int32_t d = 0;
-    if (e < a.N) {
-        const uint32_t env = a.env_id0 + (uint32_t)e;
-        int32_t s = a.pos[e], r = a.reward[e];
-        d = a.done[e];
-        uint32_t ep = a.episode[e], word = a.mask[e];
-        uint32_t rem = gu_errand_rem(word, a.param, a.param2);
-        const uint64_t t0 = a.steps_taken + (uint64_t)(int64_t)(int32_t)a.tcount[e];
-        const uint32_t start_prefix = gu_rng_prefix(a.seed_prefix, env);  // streams 1 and 11: no epoch
-        OverlayPolicy<POLICY> P;
-        P.begin(a, env, t0);
-        int32_t ret = 0, fin = 0;
-        for (int64_t i = 0; i < a.T; ++i) {
-            if (a.auto_reset && d) {  // lazy `if done: env.reset()`: the fruit grows back, another instruction is given
-                s = a.starts[gu_rng_start_index(start_prefix, ep, a.n_starts)];
-                gu_errand_draw(start_prefix, ep, a.param, a.param2, word, rem);
-                ++ep;
-                d = 0;
-            }
-            const uint32_t act = P.act(a, i, e, s);
-            const int32_t c = gu_move(s, m.f[s], act, gu_delta<LDS>(act, a.lut, a.W));
-            // three reads behind the one address c: flags, reward byte, errand byte
-            const bool stay = gu_errand_touch(er[c], m.r[c], (m.f[c] >> GU_CELL_TERM_BIT) & 1, a.param2, word, rem, r, d);
-            s = stay ? s : c;
-            P.next(a);
-            if (a.tr_obs) {
-                const int64_t row = i * a.N + e;
-                a.tr_obs[row] = s;
-                a.tr_reward[row] = r;
-                a.tr_done[row] = d;
-            }
-            ret += r;
-            fin += d;
-        }
-        a.pos[e] = s;
-        a.reward[e] = r;
-        a.done[e] = d;
-        a.episode[e] = ep;
-        a.mask[e] = word;
-        if (a.ret) {
-            a.ret[e] = ret;
-            a.episodes_fin[e] = fin;
-        }
+    template <class ARGS>
+    __device__ __forceinline__ void reset(const ARGS &a, const OverlayMap &, uint32_t start_prefix, uint32_t ep, int32_t)
+    {
+        gu_errand_draw(start_prefix, ep, a.param, a.param2, w, rem);  // the fruit grows back, another instruction is given
     }
-    const uint64_t bits = __ballot(d != 0);
-    if ((threadIdx.x & 63) == 0 && e < a.N) a.done_bits[e >> 6] = bits;
-}
 
-void gu_errands_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a)
-{
-    gu_pick<3, 2, 1, 0>(p.policy, [&](auto policy_c) {
-        gu_pick<0, 1>(p.lds != 0, [&](auto lds_c) {
-            constexpr int POLICY = decltype(policy_c)::value;
-            constexpr bool LDS = decltype(lds_c)::value != 0;
-            gu_lds_launch<gu_errands_rollout_kernel<POLICY, LDS>, false>(h, p.blocks, p.block, p.lds, a);
-        });
-    });
-}
+    template <bool LDS, class ARGS>
+    __device__ __forceinline__ void move(const ARGS &a, const OverlayMap &m, uint32_t act, int32_t &s, int32_t &r, int32_t &d)
+    {
+        const int32_t c = gu_move(s, m.f[s], act, gu_delta<LDS>(act, a.lut, a.W));
+        // three reads behind the one address c: flags, reward byte, errand byte
+        const bool stay = gu_errand_touch(m.o[c], m.r[c], (m.f[c] >> GU_CELL_TERM_BIT) & 1, a.param2, w, rem, r, d);
+        s = stay ? s : c;
+    }
+
+    __device__ __forceinline__ uint32_t word() const { return w; }
+};
+
+void gu_errands_step(gu_engine *h, bool lds, const OverlayStepArgs &a) { gu_overlay_step_launch<ErrandRule>(h, lds, a); }
+void gu_errands_rollout(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a) { gu_overlay_rollout_launch<ErrandRule>(h, p, a); }
 
 // ------------------------------------------------------------------------------------
 // entry points
@@ -199,24 +110,8 @@ int gu_set_errands(gu_handle h, const uint8_t *errand, int32_t n_instr, const ui
     GU_REQUIRE(pay[0] >= 0 && pay[0] <= 16, GU_ERR_INVALID, "right = %d outside 0 .. 16", pay[0]);
     GU_REQUIRE(pay[1] >= -16 && pay[1] <= 0, GU_ERR_INVALID, "wrong = %d outside -16 .. 0", pay[1]);
     GU_REQUIRE(pay[2] >= 0 && pay[2] <= 16, GU_ERR_INVALID, "finish = %d outside 0 .. 16", pay[2]);
-    std::vector<uint8_t> flags((size_t)h->S);
-    GU_HIP(hipStreamSynchronize(h->stream));
-    GU_HIP(hipMemcpy(flags.data(), h->d_cell, (size_t)h->S, hipMemcpyDeviceToHost));
     int32_t F = 0, of_kind[4] = {0, 0, 0, 0};
-    uint32_t slots = 0;
-    for (int32_t s = 0; s < h->S; ++s) {
-        const uint32_t c = errand[s], kind = (c >> 5) & 3u, slot = c & 31u;
-        if (!c) continue;
-        GU_REQUIRE(!(c & 0x80u) && kind != 0u, GU_ERR_INVALID, "errand byte 0x%02x of cell %d: bit 7 must be zero, and kind 0 means the whole byte is zero", c, s);
-        GU_REQUIRE(F < 8, GU_ERR_INVALID, "more than 8 fruits");
-        GU_REQUIRE(!(flags[s] & (GU_CELL_WALL | GU_CELL_TERM)), GU_ERR_INVALID, "fruit on cell %d, which is a wall or a goal or lava cell", s);
-        GU_REQUIRE(slot < 8u && !((slots >> slot) & 1u), GU_ERR_INVALID, "slot %u of cell %d is used twice or lies above 7", slot, s);
-        slots |= 1u << slot;
-        ++of_kind[kind];
-        ++F;
-    }
-    GU_REQUIRE(F >= 1, GU_ERR_INVALID, "no fruit in the plane (NULL takes the errands away)");
-    GU_REQUIRE(slots == (1u << F) - 1u, GU_ERR_INVALID, "the %d fruits must use the slots 0 .. %d, each once (slot mask 0x%02x)", F, F - 1, slots);
+    GU_TRY(gu_overlay_fruit_plane(h, GU_OVERLAY_ERRANDS, errand, 8, &F, of_kind));
     uint32_t packed = 0, max_len = 0;
     for (int32_t j = 0; j < 4; ++j) {
         if (j >= n_instr) {

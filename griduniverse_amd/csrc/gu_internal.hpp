@@ -598,6 +598,9 @@ int gu_overlay_admits(gu_engine *h, int kind);
 // plane == nullptr takes the overlay away.  A refused call leaves the engine as it was.
 int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bits, uint32_t param, uint32_t init = 0u, uint32_t param2 = 0u);
 void gu_overlay_free(gu_engine *h);
+int gu_overlay_grid_flags(gu_engine *h, std::vector<uint8_t> &flags);  // [S] the grid's flags plane, read back for a plane's validation
+// fruit's and errands' plane format; at most `cap` fruits, counted into *n_fruit and, where of_kind is given, per kind into of_kind[4]
+int gu_overlay_fruit_plane(gu_engine *h, int kind, const uint8_t *plane, int32_t cap, int32_t *n_fruit, int32_t *of_kind = nullptr);
 int gu_overlay_get_plane(gu_engine *h, int kind, uint8_t *plane);  // [S]; zeros while `kind` is not set
 int gu_overlay_get_masks(gu_engine *h, int kind, int64_t env0, int64_t n, uint32_t *masks, const char *what);
 int gu_overlay_set_masks(gu_engine *h, int kind, int64_t env0, int64_t n, const uint32_t *masks, const char *what);
@@ -607,8 +610,8 @@ int gu_overlay_launch_step(gu_engine *h, const int32_t *d_actions_row, uint32_t 
                            uint32_t *host_seq, uint32_t seq, uint32_t *host_err);
 void gu_overlay_launch_rollout(gu_engine *h, const GuRolloutPlan &p, const RolloutArgs &r);  // (the launch alone: gu_launch_rollout checks and completes it)
 void gu_overlay_lane_args(gu_engine *h, TabArgs &a, OverlayLaneArgs &o);  // (the overlay's part of gu_launch_td's arguments: gu_tabular.hpp)
-// ... and what each feature keeps of them: the ladder from the launch's shape to its kernel's instantiation (gu_wind.hip, gu_fruit.hip, gu_doors.hip,
-// gu_boxes.hip, gu_errands.hip)
+// ... and what each feature keeps of them: the launch of its kernel's instantiation for the launch's shape (gu_wind.hip: its own ladder; gu_fruit.hip,
+// gu_doors.hip, gu_boxes.hip, gu_errands.hip: one line each, gu_overlay.hpp's ladder around the kind's rule struct, so each kind compiles in its own object)
 void gu_wind_step(gu_engine *h, bool lds, const OverlayStepArgs &a);
 void gu_fruit_step(gu_engine *h, bool lds, const OverlayStepArgs &a);
 void gu_doors_step(gu_engine *h, bool lds, const OverlayStepArgs &a);

@@ -2,8 +2,10 @@
 // An overlay is a third byte plane behind the engine's two cell planes (gu_engine::d_overlay_cell holds all three in one piece, which
 // its kernels stage in LDS where they fit 64 KiB) and, for fruit, doors and boxes, one uint32 mask per env with its value at reset
 // (gu_engine::overlay_init: 0 but for boxes).  Here is everything around a feature's rule: the install path, the getters, the masks'
-// copies, the masks' reset and the arguments of the step, rollout and learner launches.  The features keep their plane's validation and their
-// kernels (gu_wind.hip, gu_fruit.hip, gu_doors.hip, gu_boxes.hip, gu_errands.hip); errands keep their reset kernel too (it draws).
+// copies, the masks' reset, the arguments of the step, rollout and learner launches, the readback of the grid's flags that a plane is
+// validated against and the plane format that fruit and errands share.  The features keep their plane's validation and their rule:
+// wind in kernels of its own (gu_wind.hip), fruit, doors, boxes and errands in a rule struct for the two frames of gu_overlay.hpp
+// (gu_fruit.hip, gu_doors.hip, gu_boxes.hip, gu_errands.hip); errands keep their reset kernel too (it draws).
 #include "gu_overlay.hpp"
 #include "gu_tabular.hpp"  // (gu_env_range, gu_env_copy)
 
@@ -66,6 +68,45 @@ int gu_overlay_install(gu_engine *h, int kind, const uint8_t *plane, int32_t bit
     h->overlay_param = param;
     h->overlay_param2 = param2;
     h->overlay_init = init;
+    return GU_OK;
+}
+
+// the flags plane of the engine's grid on the host (wall and terminal bits: what nothing of an overlay's plane may lie on)
+int gu_overlay_grid_flags(gu_engine *h, std::vector<uint8_t> &flags)
+{
+    flags.resize((size_t)h->S);
+    GU_HIP(hipStreamSynchronize(h->stream));
+    GU_HIP(hipMemcpy(flags.data(), h->d_cell, (size_t)h->S, hipMemcpyDeviceToHost));
+    return GU_OK;
+}
+
+// The plane format that fruit and errands share (bits 0..4 the slot, bits 5..6 the kind): bit 7 zero, kind 0 only in a zero byte, no
+// fruit on a wall or terminal cell, at most `cap` fruits, which use the slots 0 .. F - 1 each once.  Each kind keeps its own words.
+int gu_overlay_fruit_plane(gu_engine *h, int kind, const uint8_t *plane, int32_t cap, int32_t *n_fruit, int32_t *of_kind)
+{
+    const bool errands = kind == GU_OVERLAY_ERRANDS;
+    std::vector<uint8_t> flags;
+    GU_TRY(gu_overlay_grid_flags(h, flags));
+    int32_t F = 0;
+    uint32_t slots = 0;
+    for (int32_t s = 0; s < h->S; ++s) {
+        const uint32_t c = plane[s], k = (c >> 5) & 3u, slot = c & 31u;
+        if (!c) continue;
+        GU_REQUIRE(!(c & 0x80u) && k != 0u, GU_ERR_INVALID, "%s byte 0x%02x of cell %d: bit 7 must be zero, and kind 0 means the whole byte is zero", errands ? "errand" : "fruit",
+                   c, s);
+        GU_REQUIRE(F < cap, GU_ERR_INVALID, "more than %d fruits", cap);
+        GU_REQUIRE(!(flags[s] & (GU_CELL_WALL | GU_CELL_TERM)), GU_ERR_INVALID, "fruit on cell %d, which is a wall or a goal or lava cell", s);
+        GU_REQUIRE(slot < (uint32_t)cap && !((slots >> slot) & 1u), GU_ERR_INVALID,
+                   errands ? "slot %u of cell %d is used twice or lies above 7" : "slot %u is used twice (second at cell %d)", slot, s);
+        slots |= 1u << slot;
+        if (of_kind) ++of_kind[k];
+        ++F;
+    }
+    GU_REQUIRE(F >= 1, GU_ERR_INVALID, "no fruit in the plane (NULL takes the %s away)", GU_OVERLAY_NAME[kind]);
+    GU_REQUIRE(slots == (F == 32 ? ~0u : (1u << F) - 1u), GU_ERR_INVALID,
+               errands ? "the %d fruits must use the slots 0 .. %d, each once (slot mask 0x%02x)" : "the %d fruits must use the slots 0 .. %d, each once (slot mask 0x%08x)", F,
+               F - 1, slots);
+    *n_fruit = F;
     return GU_OK;
 }
 

@@ -1,6 +1,7 @@
 // gu_overlay.hpp -- what the kernels of the overlays share (DESIGN.md "Overlays"; gu_wind.hip, gu_fruit.hip, gu_doors.hip, gu_boxes.hip, gu_errands.hip): the
-// argument structs that gu_overlay.hip fills, the completion word of a step kernel and the per-lane policy of a rollout kernel.
-// Everything around a feature's move or reward rule; the rule itself stays written out in the feature's own kernels.
+// argument structs that gu_overlay.hip fills, the completion word of a step kernel, the per-lane policy of a rollout kernel, and, for the
+// four kinds that keep a word per env, the step kernel and the rollout kernel themselves: two frames around a rule struct of the kind's
+// own file, with the ladders from launch shape to instantiation.  The rule stays written out in that struct; wind keeps its own kernels.
 #pragma once
 #include "gu_rollout.hpp"  // (gu_map.hpp, gu_rng.hpp, gu_sample_action, RolloutArgs)
 
@@ -116,3 +117,167 @@ struct OverlayPolicy {
         }
     }
 };
+
+// ------------------------------------------------------------------------------------
+// the two frames of fruit, doors, boxes and errands: everything of a step and of a rollout kernel that is contract and not rule
+// ------------------------------------------------------------------------------------
+// These four kinds keep a uint32 word per env and move one lane at a time, so their kernels differ in the rule alone.  Wind's do not
+// fit and are not bent to: they run every lane of the wave, lanes past the batch included (the push loop and the gust ballot are
+// wave-uniform), carry no word and take GUST as a template parameter -- another frame, gu_wind.hip's own.
+//
+// A kind's RULE is a struct that holds the lane's word and what the kind carries beside it, with four functions; `a` is the launch's
+// OverlayStepArgs or OverlayRolloutArgs (a rule reads param, param2, init, lut and W of it), `m` the staged planes:
+//   void load(const ARGS &a, const OverlayMap &m, uint32_t word, int32_t s)
+//        the word as it came from mask[e], and the carried values derived from it and from the cell s stood on (once per launch);
+//   void reset(const ARGS &a, const OverlayMap &m, uint32_t start_prefix, uint32_t ep, int32_t s)
+//        what a lazy reset restores: start_prefix is stream 1's (seed and env, no epoch), ep the episode count BEFORE the reset
+//        increments it, s the start cell;
+//   template <bool LDS> void move(const ARGS &a, const OverlayMap &m, uint32_t act, int32_t &s, int32_t &r, int32_t &d)
+//        one step of the rule: leaves the cell, the reward, the done flag and the lane's own state behind the step;
+//   uint32_t word() const
+//        the word to store in mask[e];
+//   static constexpr bool DONE_IN_PLACE
+//        for the compiler, not for the reader: true where the rollout frame hands its own `d` to move, false where move writes a copy
+//        that the frame assigns.  The values are the same; what differs is when the compiler first sees `d` as a value (a variable
+//        whose address goes to a force-inlined function stays in memory until that function is inlined), and with it whether the
+//        done ballot is taken from a VGPR or from a carried SGPR pair and which registers the loop gets.  Each kind states the form
+//        its kernel had before the frames, so every loop keeps its instruction sequence (docs/HISTORY.md "Overlay frames").
+// The step/rollout rule is NOT the learners' (OV of gu_tabular_overlay.hpp): that one takes the lane by reference for reasons of code
+// generation (docs/HISTORY.md "Learner lane"), and the two stay apart.
+struct OverlayMap {
+    const uint8_t *f;  // flags plane
+    const int8_t *r;   // reward plane
+    const uint8_t *o;  // the overlay's plane
+};
+
+template <bool LDS, class ARGS>
+__device__ __forceinline__ OverlayMap gu_stage_overlay(const ARGS &a, uint8_t *smem)
+{
+    const CellMap m = gu_stage_map<LDS>(a.cell, a.cell_bytes, smem, a.gs, 3);
+    return OverlayMap{m.f, m.r, m.f + 2 * a.cell_bytes};
+}
+
+// single step: gu_step_kernel's rules (rejected actions, lazy auto-reset, done ballot, host copies, completion word) around RULE::move
+template <class RULE, bool LDS>
+__global__ void __launch_bounds__(GU_BLOCK) gu_overlay_step_kernel(const OverlayStepArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const OverlayMap m = gu_stage_overlay<LDS>(a, smem);
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t done = 0;  // (the ballot's; lanes past the batch vote 0)
+    if (e < a.N) {
+        const uint32_t raw = (uint32_t)a.actions[e];
+        const uint32_t act = raw & 3u;
+        int32_t s = a.pos[e], r, d;
+        if (a.host_err && !GU_ACTION_OK(raw)) {  // (gu_step_kernel: this env does not step, its word stays, nothing is drawn, and the host is told)
+            __hip_atomic_store(a.host_err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            a.tcount[e] -= 1u;
+            r = a.reward[e];
+            d = a.done[e];
+        } else {
+            RULE R;
+            R.load(a, m, a.mask[e], s);
+            if ((a.flags & GU_F_AUTO_RESET) && a.done[e]) {  // lazy `if done: env.reset()`
+                const uint32_t ep = a.episode[e];
+                const uint32_t start_prefix = gu_rng_prefix(a.seed_prefix, a.env_id0 + (uint32_t)e);
+                s = a.starts[gu_rng_start_index(start_prefix, ep, a.n_starts)];
+                a.episode[e] = ep + 1;
+                R.reset(a, m, start_prefix, ep, s);
+            }
+            R.template move<LDS>(a, m, act, s, r, d);
+            a.pos[e] = s;
+            a.reward[e] = r;
+            a.done[e] = d;
+            a.mask[e] = R.word();
+        }
+        if (a.host_obs) a.host_obs[e] = s;
+        if (a.host_reward) a.host_reward[e] = r;
+        if (a.host_done) a.host_done[e] = d;
+        done = d;
+    }
+    const uint64_t bits = __ballot(done != 0);
+    if ((threadIdx.x & 63) == 0 && e < a.N) a.done_bits[e >> 6] = bits;
+    gu_step_publish(a.host_seq, a.seq, a.blocks_done);
+}
+
+// rollout: T steps per lane in one launch.  Auto-reset, rows and statistics are launch-uniform tests on the arguments; the state and
+// the word stay in VGPRs for the whole launch: one load at the start, one store at the end.  Plain stores, no schedule (GuPacer).
+template <class RULE, int POLICY, bool LDS>
+__global__ void __launch_bounds__(GU_BLOCK) gu_overlay_rollout_kernel(const OverlayRolloutArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const OverlayMap m = gu_stage_overlay<LDS>(a, smem);
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int32_t d = 0;
+    if (e < a.N) {
+        const uint32_t env = a.env_id0 + (uint32_t)e;
+        int32_t s = a.pos[e], r = a.reward[e];
+        d = a.done[e];
+        uint32_t ep = a.episode[e];
+        RULE R;
+        R.load(a, m, a.mask[e], s);
+        const uint64_t t0 = a.steps_taken + (uint64_t)(int64_t)(int32_t)a.tcount[e];
+        const uint32_t start_prefix = gu_rng_prefix(a.seed_prefix, env);  // stream 1 (and the errands' 11): no epoch
+        OverlayPolicy<POLICY> P;
+        P.begin(a, env, t0);
+        int32_t ret = 0, fin = 0;
+        for (int64_t i = 0; i < a.T; ++i) {
+            if (a.auto_reset && d) {  // lazy `if done: env.reset()`
+                s = a.starts[gu_rng_start_index(start_prefix, ep, a.n_starts)];
+                R.reset(a, m, start_prefix, ep, s);
+                ++ep;
+                d = 0;
+            }
+            const uint32_t act = P.act(a, i, e, s);
+            if constexpr (RULE::DONE_IN_PLACE) {
+                R.template move<LDS>(a, m, act, s, r, d);
+            } else {  // (the same values through a copy: see DONE_IN_PLACE above)
+                int32_t d1;
+                R.template move<LDS>(a, m, act, s, r, d1);
+                d = d1;
+            }
+            P.next(a);
+            if (a.tr_obs) {
+                const int64_t row = i * a.N + e;
+                a.tr_obs[row] = s;
+                a.tr_reward[row] = r;
+                a.tr_done[row] = d;
+            }
+            ret += r;
+            fin += d;
+        }
+        a.pos[e] = s;
+        a.reward[e] = r;
+        a.done[e] = d;
+        a.episode[e] = ep;
+        a.mask[e] = R.word();
+        if (a.ret) {
+            a.ret[e] = ret;
+            a.episodes_fin[e] = fin;
+        }
+    }
+    const uint64_t bits = __ballot(d != 0);
+    if ((threadIdx.x & 63) == 0 && e < a.N) a.done_bits[e >> 6] = bits;
+}
+
+// the ladders from launch shape to instantiation; a kind's gu_<kind>_step and gu_<kind>_rollout call them from its own file, so each
+// kind's ten instantiations compile in their own object
+template <class RULE>
+static void gu_overlay_step_launch(gu_engine *h, bool lds, const OverlayStepArgs &a)
+{
+    const dim3 grid(gu_blocks(h->N, GU_BLOCK)), block(GU_BLOCK);
+    if (lds) hipLaunchKernelGGL((gu_overlay_step_kernel<RULE, true>), grid, block, 3 * (size_t)h->cell_bytes, h->stream, a);
+    else hipLaunchKernelGGL((gu_overlay_step_kernel<RULE, false>), grid, block, 0, h->stream, a);
+}
+
+template <class RULE>
+static void gu_overlay_rollout_launch(gu_engine *h, const GuRolloutPlan &p, const OverlayRolloutArgs &a)
+{
+    gu_pick<3, 2, 1, 0>(p.policy, [&](auto policy_c) {  // (the lists run backwards, as gu_rollout.hpp's do: the kernels keep their order in the code object)
+        gu_pick<0, 1>(p.lds != 0, [&](auto lds_c) {
+            constexpr int POLICY = decltype(policy_c)::value;
+            constexpr bool LDS = decltype(lds_c)::value != 0;
+            gu_lds_launch<gu_overlay_rollout_kernel<RULE, POLICY, LDS>, false>(h, p.blocks, p.block, p.lds, a);
+        });
+    });
+}

@@ -82,7 +82,7 @@ struct DoorOverlay {
 
 // Boxes (gu_set_boxes): the table has S << (b * B) rows and the lane stands on row word * S + s.  The lane carries the count of boxes
 // on a target beside the word of box cells, as the rollout kernel does (the head of gu_boxes.hip); move() applies rules 2-6 of
-// gu_set_boxes on the candidate (gu_boxes_move of gu_boxes.hip, with the bytes of s' read behind the push), the push behind a branch
+// gu_set_boxes on the candidate (BoxRule::move of gu_boxes.hip, with the bytes of s' read behind the push), the push behind a branch
 // that only pushing lanes take.
 struct BoxOverlay {
     static constexpr int PLANES = 3;

@@ -1,6 +1,7 @@
 """Pushable boxes, the parts that need no GPU: the box plane, the words, the XSB parser, the argument checks, the library's symbols, the
 CPU restatement against the calm C oracle in two identities that do not rest on the new code, rules 2-6 on hand-written walks, and the
 learning claim on the 4 x 4 grid."""
+import re
 import subprocess
 
 import numpy as np
@@ -128,7 +129,9 @@ def test_header_binding_and_library_hold_the_box_entry_points_and_kernels():
         assert name in _lib.SIGNATURES
         assert header is None or 'int ' + name + '(gu_handle h' in header, name
     blob = open(_lib.LIB_PATH, 'rb').read()
-    assert b'gu_boxes_step_kernel' in blob and b'gu_boxes_rollout_kernel' in blob and b'gu_overlay_reset_kernel' in blob
+    for frame in (b'gu_overlay_step_kernel', b'gu_overlay_rollout_kernel'):  # the frame's name and the kind's rule type in ONE mangled symbol
+        assert re.search(frame + rb'I\d+BoxRule', blob), frame
+    assert b'gu_overlay_reset_kernel' in blob
     assert gua.Engine.ROLLOUT_FAMILIES[7] == 'boxes'
 
 

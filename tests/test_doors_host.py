@@ -1,6 +1,7 @@
 """Doors, keys and levers, the parts that need no GPU: the door plane, the argument checks, the library's symbols, the CPU restatement
 against the calm C oracle in two identities that do not rest on the new code, rule 5 on hand-written walks, and the learning claim on
 the 7 x 3 grid."""
+import re
 import subprocess
 
 import numpy as np
@@ -118,7 +119,9 @@ def test_library_exports_the_door_entry_points_and_kernels():
         assert ' T ' + name + '\n' in syms, name
         assert name in _lib.SIGNATURES
     blob = open(_lib.LIB_PATH, 'rb').read()
-    assert b'gu_doors_step_kernel' in blob and b'gu_doors_rollout_kernel' in blob and b'gu_overlay_reset_kernel' in blob
+    for frame in (b'gu_overlay_step_kernel', b'gu_overlay_rollout_kernel'):  # the frame's name and the kind's rule type in ONE mangled symbol
+        assert re.search(frame + rb'I\d+DoorRule', blob), frame
+    assert b'gu_overlay_reset_kernel' in blob
     assert gua.Engine.ROLLOUT_FAMILIES[6] == 'doors'
 
 

@@ -1,6 +1,7 @@
 """Errands, the parts that need no GPU: the restatement (tests/_errands_oracle.py) against hand-written walks, the instructions in
 words, the packing and the word's fields, the argument checks of the facade, the conditions that keep the device cases from being
 vacuous, the library's symbols and the learning claim on the 5 x 3 grid."""
+import re
 import subprocess
 
 import numpy as np
@@ -254,7 +255,9 @@ def test_library_exports_the_errands_entry_points_and_kernels():
         assert ' T ' + name + '\n' in syms, name
         assert name in _lib.SIGNATURES
     blob = open(_lib.LIB_PATH, 'rb').read()
-    assert b'gu_errands_step_kernel' in blob and b'gu_errands_rollout_kernel' in blob and b'gu_errands_reset_kernel' in blob
+    for frame in (b'gu_overlay_step_kernel', b'gu_overlay_rollout_kernel'):  # the frame's name and the kind's rule type in ONE mangled symbol
+        assert re.search(frame + rb'I\d+ErrandRule', blob), frame
+    assert b'gu_errands_reset_kernel' in blob
     assert gua.Engine.ROLLOUT_FAMILIES[8] == 'errands'
 
 

@@ -1,5 +1,6 @@
 """Fruit, the parts that need no GPU: the fruit plane, the CPU restatement against the calm C oracle, what fruit changes in a rollout's
 rows (and what it does not), the argument checks, the library's symbols and the learning claim on the 5 x 3 grid."""
+import re
 import subprocess
 
 import numpy as np
@@ -168,7 +169,9 @@ def test_library_exports_the_fruit_entry_points_and_kernels():
         assert ' T ' + name + '\n' in syms, name
         assert name in _lib.SIGNATURES
     blob = open(_lib.LIB_PATH, 'rb').read()
-    assert b'gu_fruit_step_kernel' in blob and b'gu_fruit_rollout_kernel' in blob and b'gu_overlay_reset_kernel' in blob
+    for frame in (b'gu_overlay_step_kernel', b'gu_overlay_rollout_kernel'):  # the frame's name and the kind's rule type in ONE mangled symbol
+        assert re.search(frame + rb'I\d+FruitRule', blob), frame
+    assert b'gu_overlay_reset_kernel' in blob
     assert gua.Engine.ROLLOUT_FAMILIES[5] == 'fruit'
 
 
