@@ -27,6 +27,7 @@ TD_Q_LEARNING, TD_SARSA = 0, 1
 NSTEP_MAX = 16  # GU_NSTEP_MAX: the largest n of gu_nstep_run
 LAMBDA_MAX = 64  # GU_LAMBDA_MAX: the largest K (trace length) of gu_lambda_run
 REINFORCE_MAX = 1024  # GU_REINFORCE_MAX: the largest L (segment length) of gu_reinforce_run
+EVAL_MAX_K, EVAL_MAX_LANES, EVAL_BUDGET = 65535, 1 << 24, 100000000  # gu_td_evaluate: K, K * N and K * L at most
 IS_MAX = 1024  # GU_IS_MAX: the largest L (segment length) of gu_is_run
 SEARCH_MAX_M = 64   # GU_SEARCH_MAX_M: the most rollouts per action of gu_search_run
 SEARCH_MAX_D = 256  # GU_SEARCH_MAX_D: their largest depth
@@ -118,6 +119,7 @@ SIGNATURES = {
     'gu_td_init': [_vp, _f64],
     'gu_td_run': [_vp, _i64, _i32, _f64, _f64, _u32, _u32],
     'gu_td_get_q': [_vp, _i64, _i64, _vp],
+    'gu_td_evaluate': [_vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     'gu_td_set_q': [_vp, _i64, _i64, _vp],
     'gu_esarsa_run': [_vp, _i64, _f64, _f64, _u32, _u32],
     'gu_double_init': [_vp, _f64],

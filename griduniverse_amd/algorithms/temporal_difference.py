@@ -19,9 +19,9 @@ from .. import _lib
 from ._batch import _CHUNK, learn, need_learners, unit
 
 
-def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind=None, gust=0.0, fruit=None, doors=None, boxes=None, errands=None):
-    need_learners(num_learners)
-    unit('epsilon', epsilon)
+def overlay_installer(wind=None, gust=0.0, fruit=None, doors=None, boxes=None, errands=None):
+    """The checks of the overlay arguments that q_learning and sarsa take (ValueError), and the function that puts the overlay they
+    name on a batch (algorithms.evaluation walks under it too)."""
     unit('gust', gust)
     if fruit is not None:
         if wind is not None:
@@ -44,7 +44,7 @@ def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, s
         if not isinstance(errands, dict) or not {'cells', 'instructions'} <= set(errands) or set(errands) - {'cells', 'kinds', 'instructions', 'right', 'wrong', 'finish'}:
             raise ValueError('errands must be dict(cells=, kinds=, instructions=, right=, wrong=, finish=)')
 
-    def prepare(vec):  # (the tables have S << F rows under fruit and S << D under doors: the overlay goes on before them)
+    def install(vec):
         if wind is not None:
             strength, direction = wind if isinstance(wind, tuple) else (wind, 'up')
             vec.set_wind(strength, direction, gust)
@@ -56,6 +56,17 @@ def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, s
             vec.set_boxes(boxes['boxes'], boxes['targets'], boxes.get('on_target', 5))
         if errands is not None:
             vec.set_errands(**errands)
+
+    return install
+
+
+def _td(method, env, num_steps, alpha, discount_factor, epsilon, num_learners, seed, q0, wind=None, gust=0.0, fruit=None, doors=None, boxes=None, errands=None):
+    need_learners(num_learners)
+    unit('epsilon', epsilon)
+    install = overlay_installer(wind, gust, fruit, doors, boxes, errands)
+
+    def prepare(vec):  # (the tables have S << F rows under fruit and S << D under doors: the overlay goes on before them)
+        install(vec)
         vec._ensure_q(q0)
 
     return learn(env, num_learners, seed, num_steps, _CHUNK, prepare, lambda vec, T: vec.td_run(T, method, alpha, discount_factor, epsilon))

@@ -2,7 +2,8 @@
 // Dyna-Q; gu_sweep.hip: prioritized sweeping; gu_nstep.hip: n-step Q-learning and SARSA; gu_lambda.hip: SARSA(lambda) and Watkins's
 // Q(lambda); gu_search.hip: rollout search; gu_explore.hip: UCB / Thompson; gu_mcts.hip: tree search; gu_is.hip: off-policy
 // Monte-Carlo; gu_ac.hip: actor-critic; gu_reinforce.hip: REINFORCE with baseline); gu_double.hip (Double Q-learning, on a pair of
-// tables) and gu_fa.hip (semi-gradient SARSA / Q-learning on features) use the lane without its table.
+// tables) and gu_fa.hip (semi-gradient SARSA / Q-learning on features) use the lane without its table; gu_eval.hip (greedy evaluation)
+// walks with the lane and learns nothing.
 // N independent learners, learner e owns env e and its own float64 table Q_e[S][4], advanced T real steps per launch.  The
 // semantics are build-defined (the reference has no tabular code) and stated in include/gu.h (gu_td_run, gu_dyna_run, gu_nstep_run).
 //
@@ -136,7 +137,7 @@ struct NoOverlay {
 // A kernel constructs it (staging the map), runs begin .. end on live lanes and ballot on all; its own rule sits between move and step.
 // ROWS = false (gu_fa.hip): the lane has no table of rows of its own -- begin / reset / next_row read nothing from a.q, and the
 // kernel keeps `q` (for gu_fa.hip: the folded row of the current state) itself.
-// OV (gu_td.hip alone sets it): the engine's overlay, one of the structs of gu_tabular_overlay.hpp.  The lane stages OV::PLANES planes,
+// OV (gu_td.hip and gu_eval.hip set it): the engine's overlay, one of the structs of gu_tabular_overlay.hpp.  The lane stages OV::PLANES planes,
 // hands the rule of a move to `ov` and, under OV::MASKED, stands on row ov.key() * S + s of a table of `rows` rows; a wall bump may
 // then keep the cell and change the row, so next_row() and update() compare ROWS, not cells.  The kernel calls load() before begin()
 // and store() behind end().  The calm instantiations hold none of it.  (Where `ov` stands among the members decides the order of the
@@ -197,6 +198,28 @@ struct TabLane {
             ov.reset(start_prefix, ep - 1u);
             if (ROWS) q = gu_q_load(qe + row() * 4);
         }
+    }
+
+    // gu_eval.hip, in the place of begin(): the lane stands at the start of test episode k (include/gu.h: gu_td_evaluate, rules 1 and
+    // 2) -- what reset() gives a freshly seeded env at episode count k, on cell s0 instead where s0 >= 0, at step count t0 of epoch
+    // 0.  Nothing of the env's own state is read.  Call load() first.
+    __device__ __forceinline__ void begin_test(const TabArgs &a, uint32_t k, uint32_t t0, int32_t s0)
+    {
+        lg = gu_lane_grid<LDS>(a.gs, a.starts, a.n_starts, (uint32_t)e, m);
+        env = a.env_id0 + (uint32_t)e;
+        start_prefix = gu_rng_prefix(a.seed_prefix, env);
+        t = t0;
+        prefix = gu_rng_prefix(gu_rng_seed_prefix_epoch(a.seed_prefix, 0u), env);
+        qe = a.q + (MASKED ? e * rows : e * a.S) * 4;
+        ep = k;
+        r = ret = fin = 0;
+        d = 1;
+        reset(a);
+        if (s0 >= 0) {
+            s = s0;
+            q = gu_q_load(qe + row() * 4);
+        }
+        d = (m.f[s] >> GU_CELL_TERM_BIT) & 1;
     }
 
     // the table row the lane stands on, and the one it stands on behind move()
@@ -457,17 +480,18 @@ static inline void gu_tabular_args(gu_engine *h, TabArgs &a, int64_t T, double a
 
 // launch the LDS instantiation where every block uses one grid whose planes fit, else the L2 one; blocks of at most `bs` lanes,
 // and `lane_lds` bytes of dynamic LDS per lane after the planes (gu_lambda.hip's ring; none for the other learners)
-// (`planes`: 3 for the windy instantiations, whose a.cell carries the wind plane behind the two cell planes)
+// (`planes`: 3 for the windy instantiations, whose a.cell carries the wind plane behind the two cell planes; `ny`: the launch's second
+// dimension -- gu_eval.hip's test episodes; the lanes of every blockIdx.y are the same N envs)
 template <class A>
-static int gu_tabular_launch(gu_engine *h, void (*lds)(A), void (*l2)(A), const A &a, int bs = GU_BLOCK, size_t lane_lds = 0, int planes = 2)
+static int gu_tabular_launch(gu_engine *h, void (*lds)(A), void (*l2)(A), const A &a, int bs = GU_BLOCK, size_t lane_lds = 0, int planes = 2, unsigned ny = 1)
 {
     const int lds_bs = gu_lds_block(h, bs, planes);
     if (lds_bs) {
         const size_t bytes = (size_t)planes * (size_t)h->cell_bytes + lane_lds * (size_t)lds_bs;
         if (bytes > 64 * 1024) GU_HIP(hipFuncSetAttribute((const void *)lds, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-        hipLaunchKernelGGL(lds, dim3(gu_blocks(h->N, lds_bs)), dim3(lds_bs), bytes, h->stream, a);
+        hipLaunchKernelGGL(lds, dim3(gu_blocks(h->N, lds_bs), ny), dim3(lds_bs), bytes, h->stream, a);
     } else {
-        hipLaunchKernelGGL(l2, dim3(gu_blocks(h->N, bs)), dim3(bs), lane_lds * (size_t)bs, h->stream, a);
+        hipLaunchKernelGGL(l2, dim3(gu_blocks(h->N, bs), ny), dim3(bs), lane_lds * (size_t)bs, h->stream, a);
     }
     GU_HIP(hipGetLastError());
     return GU_OK;

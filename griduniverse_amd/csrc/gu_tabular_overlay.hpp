@@ -1,5 +1,5 @@
 // gu_tabular_overlay.hpp -- the five overlay kinds as the learners' lane knows them (gu_tabular.hpp: TabLane's OV and NoOverlay, which
-// lists what a kind supplies; gu_td.hip alone includes this).  Each struct holds its kind's fields and states its rule once, on the
+// lists what a kind supplies; gu_td.hip and gu_eval.hip include this).  Each struct holds its kind's fields and states its rule once, on the
 // device helpers of gu_map.hpp that the kind's own step and rollout kernels use.  move() is TabLane::move's whole rule under the kind:
 // from cell l.s of the lane `l` with action ua it sets l.r, l.d and the word behind the move and returns s' (l.wd: the kind's plane,
 // l.prefix and l.t: the lane's stream prefix and step count).  It starts from gu_move's candidate itself, and reads the lane through

@@ -484,6 +484,20 @@ class Engine(object):
         q = _tables(q, (self.td_rows, 4), 'q')
         check(self.lib.gu_td_set_q(self._h, int(env0), q.shape[0], ptr(q)))
 
+    def td_evaluate(self, K, L, gamma=1.0, first_state=None):
+        """K greedy test episodes of at most L steps per env on its td_init table (include/gu.h: gu_td_evaluate): nothing learns and
+        nothing of the engine moves.  first_state: int32[K, N] start cells in the place of the drawn ones.  Returns a dict of [K, N]
+        arrays: ret, len, outcome (0 ran to L, 1 goal, 2 other terminal cell, 3 ended by the overlay), end, word (uint32) and disc
+        (float64, the return discounted by gamma)."""
+        K = int(K)
+        if first_state is not None:
+            first_state = _lib.as_array(np.asarray(first_state, np.int32), np.int32, (max(K, 0), self.N), 'first_state')
+        out = {k: np.empty((max(K, 0), self.N), np.int32) for k in ('ret', 'len', 'outcome', 'end')}
+        out['word'] = np.empty((max(K, 0), self.N), np.uint32)
+        out['disc'] = np.empty((max(K, 0), self.N), np.float64)
+        check(self.lib.gu_td_evaluate(self._h, K, int(L), float(gamma), ptr(first_state), *(ptr(out[k]) for k in ('ret', 'len', 'outcome', 'end', 'word', 'disc'))))
+        return out
+
     # ------------------------------------------------------------------ Expected SARSA and Double Q-learning (include/gu.h: gu_esarsa_run, gu_double_*)
     def esarsa_run(self, T, alpha=0.1, gamma=0.99, eps_q16=6554, trajectory=False, stats=False):
         """T Expected SARSA iterations per env in one launch on the td_init tables: acts as Q-learning does, bootstraps on the mean of

@@ -43,6 +43,30 @@ def check_off_policy_args(max_episode_len, epsilon, w_cap):
         raise ValueError('w_cap must lie in [1, 2**256]')
 
 
+def check_evaluate_args(episodes, max_steps, discount_factor, first_state, num_envs, S):
+    """The argument checks of evaluate() and algorithms.evaluation (ValueError); returns first_state as int32[episodes, num_envs] or None.  S None: the
+    library checks the cells' range."""
+    for name, v in (('episodes', episodes), ('max_steps', max_steps)):
+        if v is None and name == 'max_steps':
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 1:
+            raise ValueError('{} must be an integer of at least 1'.format(name))
+    if episodes > _lib.EVAL_MAX_K or episodes * num_envs > _lib.EVAL_MAX_LANES:
+        raise ValueError('episodes must be at most {} and episodes x envs at most {}'.format(_lib.EVAL_MAX_K, _lib.EVAL_MAX_LANES))
+    if max_steps is not None and episodes * max_steps > _lib.EVAL_BUDGET:
+        raise ValueError('episodes x max_steps must be at most {}'.format(_lib.EVAL_BUDGET))
+    if not np.isfinite(float(discount_factor)):
+        raise ValueError('discount_factor must be finite')
+    if first_state is None:
+        return None
+    f = np.asarray(first_state)
+    if f.dtype == bool or not np.issubdtype(f.dtype, np.integer) or f.shape != (episodes, num_envs):
+        raise ValueError('first_state must be integers of shape ({}, {})'.format(episodes, num_envs))
+    if S is not None and f.size and (f.min() < 0 or f.max() >= S):
+        raise ValueError('first_state must hold cells in 0 .. {}'.format(S - 1))
+    return np.ascontiguousarray(f, np.int32)
+
+
 def _masks(masks, bits, message):
     """uint32[n] from masks (or one number) of `bits` bits each, as set_fruit_eaten and set_doors_open take them (ValueError)."""
     m = np.atleast_1d(np.asarray(masks))
@@ -427,6 +451,22 @@ class VecGridUniverse(object):
         S << F rows while F fruits are set and S << D rows while doors with D slots are set, as q_table()."""
         self._ensure_q()
         self.engine.td_set_q(q, env0)
+
+    def evaluate(self, episodes=1, max_steps=None, discount_factor=1.0, first_state=None):
+        """`episodes` greedy test episodes of at most `max_steps` steps per env on its own Q table, with the move rule the learners
+        use, the overlay's included (include/gu.h: gu_td_evaluate).  Nothing learns, and the envs, what the learners carry, rows and
+        statistics stay as they are.  Test episode k starts where a reset at episode count k puts a freshly seeded env, or on
+        first_state[k][e] (int [episodes, N]); every step takes the first maximum of the row (np.argmax).  max_steps None: the rows of
+        a table (a greedy walk without gusts that has not ended by then is in a loop), clipped to the budget of 1e8 // episodes.
+        Returns a dict of [episodes, N] arrays: ret (int32), length (int32), outcome (int32: 0 ran to max_steps, 1 reached a goal,
+        2 ended on another terminal cell, 3 ended by the overlay: boxes solved, errand completed), end (int32, the last cell), word
+        (uint32, the last overlay word) and discounted (float64).  The first call gives every env a table of zeros."""
+        first_state = check_evaluate_args(episodes, max_steps, discount_factor, first_state, self.num_envs, self.spec.S)
+        self._ensure_q()
+        if max_steps is None:
+            max_steps = max(1, min(self.engine.td_rows, _lib.EVAL_BUDGET // int(episodes)))
+        out = self.engine.td_evaluate(episodes, max_steps, discount_factor, first_state)
+        return dict(ret=out['ret'], length=out['len'], outcome=out['outcome'], end=out['end'], word=out['word'], discounted=out['disc'])
 
     def expected_sarsa_run(self, T, alpha=0.1, discount_factor=0.99, epsilon=0.1, trajectory=False, stats=False):
         """T iterations of batched tabular Expected SARSA (Sutton & Barto 6.6) on the tables of td_run: env e acts epsilon-greedily

@@ -567,6 +567,35 @@ int gu_td_set_q(gu_handle h, int64_t env0, int64_t n, const double *q);
  * windows, episode buffers).  Flags and errors as gu_td_run; GU_ERR_UNSUPPORTED while wind, fruit or doors are set. */
 int gu_esarsa_run(gu_handle h, int64_t T, double alpha, double gamma, uint32_t eps_q16, uint32_t flags);
 
+/* ---- batched greedy evaluation: env e walks K test episodes of at most L steps on its table Q_e (the gu_td_* tables, S << overlay_bits
+ * rows), nothing learns and nothing of the engine moves ----
+ * (build-defined; tests/_eval_oracle.py is the CPU restatement.)  Test episode k of env e:
+ *   1. Start: what a reset at episode count k gives a freshly seeded env: the cell starts[gu_rng_start_index(stream 1, k, n_starts)] of
+ *      the env's grid -- or first_state[k][e] where first_state is given (the cell only) --, and the overlay word that reset leaves: 0,
+ *      the boxes' word at reset, or under errands the instruction drawn on stream 11 at count k.  The env's own pos, done, episode,
+ *      tcount and word are neither read nor written.
+ *   2. A start cell whose terminal bit is set ends the episode at once: len = 0, ret = 0, disc = 0, outcome by rule 6.
+ *   3. Step i takes the FIRST of the actions whose value equals the row maximum exactly, in ascending order; the maximum is folded left
+ *      to right with `>` as in gu_td_run.  Where no entry compares equal (a NaN in entry 0) the action is 0.  No RNG word is drawn.
+ *      (np.argmax on finite rows.)
+ *   4. (s', r, d) by the engine's move rule, or the overlay's, at step count k * L + i in epoch 0 (a gust is the stream-9 word at that
+ *      counter).  Under fruit, doors, boxes and errands the row is word * S + s.
+ *   5. ret += r (int32);  disc = disc + w * (double)r;  w = w * gamma, from w = 1.0 and disc = 0.0, float64 with one rounding per
+ *      operation;  len += 1.  The episode ends when d is set or after L steps.
+ *   6. outcome: 0 = L steps without an end; 1 = ended on a terminal cell whose reward is the positive one (goal); 2 = ended on any
+ *      other terminal cell (lava); 3 = ended by the overlay while the cell's terminal bit is clear (boxes solved, errand completed, or
+ *      an absorbing completed word).  end = the last cell; word = the last overlay word (0 under no overlay and under wind; under
+ *      errands the instruction's index stays readable in it).
+ * The outputs are host arrays [K][N]; any of them may be NULL.  The call is synchronous.
+ * GU_ERR_STATE without a grid or before gu_td_init.  GU_ERR_INVALID for K < 1, L < 1, K * L > 1e8 (the learners' budget; it keeps the
+ * step count below 2^32), K > 65535 or K * N > 2^24 (the launch's second dimension, and 32 bytes of scratch per test episode: 512 MiB),
+ * a non-finite gamma, or a first_state outside 0 .. S-1 (the message names the first offender); nothing is written then.
+ * The call has no other effect: what the learners carry (SARSA's next action, windows, episode buffers), the trajectory buffer, the
+ * statistics, the done ballots, the step graph and gu_get_stores are as before, and the agent trail does not refuse it.  It serves
+ * single-grid engines under every overlay and multi-grid engines in all their forms. */
+int gu_td_evaluate(gu_handle h, int32_t K, int32_t L, double gamma, const int32_t *first_state, int32_t *ret, int32_t *len,
+                   int32_t *outcome, int32_t *end, uint32_t *word, double *disc);
+
 /* ---- batched tabular Double Q-learning (Sutton & Barto 6.7): learner e owns env e and a PAIR of tables A_e[S][4], B_e[S][4] ----
  * (build-defined; tests/_double_oracle.py is the CPU restatement.)  The pair is storage of its own, q[N][S][2][4] float64 -- the A
  * row and the B row of a state side by side --, not the gu_td_* tables.  One iteration of gu_double_run for env e at step count t,
